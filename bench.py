@@ -9,9 +9,15 @@ init_iter 2, Godunov_PLM), one 256^3 box per GPU (weak scaling: rank r owns box 
 Inputs are generated on the device (closed-form initial condition), so the timed region starts with
 everything resident in HBM.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 256] [--no-cpu-baseline]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 256] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
 For N > 1 launch with  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly K steps in one region and prints the headline line (value, ms_per_step, the solver
+counters of the timed steps).  --full adds everything else the line used to carry: the median of --repeats timed regions, the
+in-step kernel probes and the rooflines, the isolated kernel loops, the section breakdown, the multigrid cycle shape of the reference,
+the secondary workloads (AMR, multi-box, per-GPU shard proxy, LidDrivenCavity, C3, C5) and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of large boxes).
 """
 import argparse
 import ctypes as C
@@ -34,7 +40,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n", type=int, default=int(os.environ.get("IAMRX_BENCH_N", "256")), help="cells per direction of the per-GPU box")
     ap.add_argument("--c", type=float, default=1.0, help="prob.c (1 = fully 3-D regtest default)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; value = median region (SURVEY 8d: median of 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: repeated regions, rooflines, sections, secondary workloads, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; value = median region (default: 1; with --full 5, SURVEY 8d: median of 5)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-upstream-shape", action="store_true", help="skip the pass with the reference's multigrid cycle shape")
     ap.add_argument("--no-multibox", action="store_true", help="skip the single-GPU 8-box / 64-box runs of the same problem")
@@ -507,6 +518,49 @@ def upstream_shape_pass(lib, N, g, lay, c, steps=3):
     return ({k: st.median(v) for k, v in ms.items()}, {k: st.median(v) for k, v in its.items()}, el / steps * 1e3)
 
 
+DUMP_POINTS = 1 << 20      # points per field of --dump-outputs: velocity (3), density, tracer and pressure in float64 = 48 MB
+
+
+def sample_valid(mf, npts_max, seed):
+    """the valid points (cells or nodes) of this rank's boxes of mf as an (npoints, ncomp) float64 array, box after box, i fastest inside a
+    box: all of them when there are at most npts_max, otherwise npts_max of them at positions drawn by a generator seeded with `seed` --
+    the same positions in every run with the same arguments -- in increasing order"""
+    import numpy as np
+    boxes = [mf.layout.local_box(li)[:2] for li in range(mf.nlocal())]
+    shapes = [tuple(hi[d] - lo[d] + 1 + mf.typ[d] for d in range(3)) for lo, hi in boxes]
+    sizes = [int(np.prod(s)) for s in shapes]
+    total = sum(sizes)
+    pick = np.arange(total) if total <= npts_max else np.sort(np.random.default_rng(seed).choice(total, npts_max, replace=False))
+    parts, start = [], 0
+    for li, (shp, sz) in enumerate(zip(shapes, sizes)):
+        sel = pick[(pick >= start) & (pick < start + sz)] - start
+        start += sz
+        if sel.size == 0:
+            continue
+        a, flo = mf.to_numpy(li)
+        blo = boxes[li][0]
+        i, j, k = np.unravel_index(sel, shp, order="F")
+        parts.append(a[i + blo[0] - flo[0], j + blo[1] - flo[1], k + blo[2] - flo[2], :])
+        del a
+    return np.concatenate(parts) if parts else np.zeros((0, mf.ncomp))
+
+
+def dump_outputs(ns, N, out_dir, dt):
+    """--dump-outputs: what a caller of the timed step receives from its last step, as out_dir/<name>.npy in float64 -- the new state
+    (velocity, density, tracer) at the cells and the pressure at the nodes of this rank's boxes, each a fixed, seeded sample of
+    DUMP_POINTS points when the boxes hold more (sample_valid), and the step's dt"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    S = sample_valid(ns.data(N.NavierStokes.S_NEW), DUMP_POINTS, seed=0)
+    np.save(os.path.join(out_dir, "velocity.npy"), np.ascontiguousarray(S[:, 0:3]))
+    np.save(os.path.join(out_dir, "density.npy"), np.ascontiguousarray(S[:, 3]))
+    np.save(os.path.join(out_dir, "tracer.npy"), np.ascontiguousarray(S[:, 4]))
+    del S
+    P = sample_valid(ns.data(N.NavierStokes.P_NEW), DUMP_POINTS, seed=1)
+    np.save(os.path.join(out_dir, "pressure.npy"), np.ascontiguousarray(P[:, 0]))
+    np.save(os.path.join(out_dir, "dt.npy"), np.array([dt], dtype=np.float64))
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -557,7 +611,7 @@ def main():
     # HIP events around every 7th finest-level launch of the two smoother kernels that lead the step's kernel time (k_abec_gsrb,
     # k_nodal_gs4; profiles/round3_kernel_stats.csv), on their launch stream: opened during the warm-up (creates the event pools),
     # re-opened for the timed region and read after it -> roofline.avg_ms is measured inside the timed steps
-    probe_on = world == 1 and os.environ.get("IAMRX_BENCH_PROBE", "1") != "0"
+    probe_on = a.full and world == 1 and os.environ.get("IAMRX_BENCH_PROBE", "1") != "0"
     # stride 7: a V-cycle issues 8 finest-level colour passes (the first of them the cheaper zero-initial-guess form), so a stride of 8 would
     # time the same position of every cycle
     PROBES = {"gs4": (0, (n + 1) ** 3, 7), "gsrb": (1, n ** 3, 7), "god_z": (2, n ** 3, 1), "pred_z": (3, n ** 3, 1)}
@@ -611,11 +665,13 @@ def main():
     s0 = nsync()
     x0 = nexch()
     regions = []
-    for _rep in range(max(1, a.repeats)):
+    repeats = a.repeats if a.repeats is not None else (5 if a.full else 1)
+    last_dt = None
+    for _rep in range(max(1, repeats)):
         barrier()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            ns.step()
+            last_dt = ns.step()
             sm, sn, sv = ns.stats()
             mac_ms.append(sm.vcycle_ms); nod_ms.append(sn.vcycle_ms); visc_ms.append(sv.vcycle_ms)
             mac_it.append(sm.iters); nod_it.append(sn.iters); visc_it.append(sv.iters)
@@ -643,18 +699,42 @@ def main():
     el = sorted(regions)[nreg // 2]
     cells_total = float(n) ** 3 * world
     value = cells_total * a.steps / el
+    if a.dump_outputs and rank == 0:
+        dump_outputs(ns, N, a.dump_outputs, last_dt)
 
     out = None
-    # the 2-level AMR workload is collective too: every rank runs it (base and refined level sharded over the ranks)
-    amr_res = amr_workload(lib, a.amr_n, a.amr_steps, rank, world, dist if world > 1 else None) if (a.amr_n > 0 and a.amr_steps > 0) else None
-    # per-section breakdown (separate, synchronised pass so it does not perturb the timed region); a time step is collective:
-    # EVERY rank takes these two steps
-    ns.profile(2)
-    for _ in range(2):
-        ns.step()
-    sec = ns.profile(0)
+    amr_res, sec = None, None
+    if a.full:
+        # the 2-level AMR workload is collective too: every rank runs it (base and refined level sharded over the ranks)
+        amr_res = amr_workload(lib, a.amr_n, a.amr_steps, rank, world, dist if world > 1 else None) if (a.amr_n > 0 and a.amr_steps > 0) else None
+        # per-section breakdown (separate, synchronised pass so it does not perturb the timed region); a time step is collective:
+        # EVERY rank takes these two steps
+        ns.profile(2)
+        for _ in range(2):
+            ns.step()
+        sec = ns.profile(0)
     if rank == 0:
         import statistics as st
+        out = {
+            "metric": "cells-advanced/sec", "value": value, "unit": "cells/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": el / a.steps * 1e3, "repeats": nreg, "ms_per_step_of_each_region": [r / a.steps * 1e3 for r in regions],
+            "protocol": "median of `repeats` timed regions of `steps` steps each (SURVEY 8d), every region between barrier + synchronize, max over ranks",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"TaylorGreen 3D single level, one {n}^3 box per GPU in a {pgrid[0]}x{pgrid[1]}x{pgrid[2]} arrangement ({ntot[0]}x{ntot[1]}x{ntot[2]} cells), periodic, "
+                                   f"nu=1e-4 cfl=0.7 Godunov_PLM be_cn_theta=0.5, full NavierStokes::advance per step",
+                       "cells": cells_total, "prob_c": a.c},
+            "mlmg_vcycle_ms": {"mac_cc": st.median(mac_ms), "nodal": st.median(nod_ms), "tensor_visc": st.median(visc_ms)},
+            "mlmg_iters": {"mac_cc": st.median(mac_it), "nodal": st.median(nod_it), "tensor_visc": st.median(visc_it)},
+            # solves of the timed steps that stopped on the round-off floor of their residual (within 10x of the target, < 10 % gained over
+            # three cycles: converged == 2, a warning on stderr) instead of reaching the reference's tolerance -- of nreg * steps solves each
+            "mlmg_stalled_solves": {"mac_cc": stalled[0], "nodal": stalled[1], "tensor_visc": stalled[2], "of_solves_each": nreg * a.steps},
+            "device_mallocs_in_timed_region": mallocs_in_loop,
+            "host_syncs_per_step": syncs_in_loop / a.steps,
+            "transport": transport if world > 1 else "none (single GPU)",
+            "halo_exchanges_rank0": exch,
+        }
+    if rank == 0 and a.full:
         kr = kernel_rooflines(lib, n) if world == 1 else {}
         # dominant kernel of the step by summed duration (profiles/round3_kernel_stats.csv): k_abec_gsrb, one colour pass of the
         # cell-centred GSRB smoother (MAC projection, scalar diffusion); second: k_nodal_gs4 (reported beside it)
@@ -752,34 +832,17 @@ def main():
         roofline_pred = godunov_roofline("pred_z", insitu.get("pred_z"), "k_pred_z<14, 14, 256, false, false> grid=%d" % zgrid, 72.0 * cells,
                                          "k_pred_z<14,14> (fused z-marching ExtrapVelToFaces)")
         ups = upstream_shape_pass(lib, N, g, lay, a.c) if (world == 1 and not a.no_upstream_shape) else None
-        out = {
-            "metric": "cells-advanced/sec", "value": value, "unit": "cells/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": el / a.steps * 1e3, "repeats": nreg, "ms_per_step_of_each_region": [r / a.steps * 1e3 for r in regions],
-            "protocol": "median of `repeats` timed regions of `steps` steps each (SURVEY 8d), every region between barrier + synchronize, max over ranks",
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"TaylorGreen 3D single level, one {n}^3 box per GPU in a {pgrid[0]}x{pgrid[1]}x{pgrid[2]} arrangement ({ntot[0]}x{ntot[1]}x{ntot[2]} cells), periodic, "
-                                   f"nu=1e-4 cfl=0.7 Godunov_PLM be_cn_theta=0.5, full NavierStokes::advance per step",
-                       "cells": cells_total, "prob_c": a.c},
-            "mlmg_vcycle_ms": {"mac_cc": st.median(mac_ms), "nodal": st.median(nod_ms), "tensor_visc": st.median(visc_ms)},
-            "mlmg_iters": {"mac_cc": st.median(mac_it), "nodal": st.median(nod_it), "tensor_visc": st.median(visc_it)},
-            # solves of the timed steps that stopped on the round-off floor of their residual (within 10x of the target, < 10 % gained over
-            # three cycles: converged == 2, a warning on stderr) instead of reaching the reference's tolerance -- of nreg * steps solves each
-            "mlmg_stalled_solves": {"mac_cc": stalled[0], "nodal": stalled[1], "tensor_visc": stalled[2], "of_solves_each": nreg * a.steps},
+        out.update({
             "mlmg_vcycle_ms_upstream_shape": ups[0] if ups else None,
             "mlmg_iters_upstream_shape": ups[1] if ups else None,
             "ms_per_step_upstream_shape": ups[2] if ups else None,
             "sections_ms_per_step": {k: v / 2 for k, v in zip(["predict_velocity", "mac_project", "advection", "updates", "viscous", "nodal_project"], sec[:6])},
-            "device_mallocs_in_timed_region": mallocs_in_loop,
-            "host_syncs_per_step": syncs_in_loop / a.steps,
-            "transport": transport if world > 1 else "none (single GPU)",
-            "halo_exchanges_rank0": exch,
             "kernels": kr,
             "roofline": roofline_gs4,
             "roofline_abec_sweep": roofline_abec,
             "roofline_godunov_advection": roofline_god,
             "roofline_godunov_prediction": roofline_pred,
-        }
+        })
         if amr_res is not None:
             out["amr"] = amr_res
         if world == 1 and not a.no_multibox:
@@ -814,6 +877,7 @@ def main():
                 out["rayleigh_taylor"] = {"error": str(e)[:200]}
         if not a.no_cpu_baseline and world == 1:       # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(a.cpu_n, a.cpu_steps, a.cpu_threads if a.cpu_threads > 0 else usable_cpus())
+    if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -1,4 +1,4 @@
-"""CPU suite: the N > 1 path on world_size-2 gloo.
+"""CPU suite: the N > 1 path on gloo (world size 2, and 8 for the layout of bench.py --gpus 8).
 
 The boxes of a level are split over two ranks; every ghost exchange is driven by the PRODUCT's host-side
 planner (iamrx_host_fill_plan: local copies + packed peer messages) with torch.distributed(gloo) as the
@@ -18,7 +18,24 @@ OWNERS = [0, 0, 1, 1]
 NSWEEP = 3
 
 
-def global_fields():
+def bench_layout(world, n=8):
+    """the layout bench.py builds for `world` GPUs (proc_grid: rows never cut, y and z split), one n^3 box per rank"""
+    sys.path.insert(0, ROOT)
+    import bench
+    pg = bench.proc_grid(world)
+    boxes = []
+    for r in range(world):
+        ix, iy, iz = r % pg[0], (r // pg[0]) % pg[1], r // (pg[0] * pg[1])
+        boxes.append(((n * ix, n * iy, n * iz), (n * ix + n - 1, n * iy + n - 1, n * iz + n - 1)))
+    return tuple(n * pg[d] for d in range(3)), boxes, list(range(world))
+
+
+def layout(case):
+    """(domain, boxes, owners): "x4" = four slabs in x on two ranks; "bench8" = bench.py's 8-GPU layout, one box per rank"""
+    return bench_layout(8) if case == "bench8" else (N, BOXES, OWNERS)
+
+
+def global_fields(N=N):
     rng = np.random.default_rng(42)
     phi = rng.standard_normal(N)
     rhs = rng.standard_normal(N)
@@ -36,10 +53,10 @@ def global_fields():
     return phi, rhs, b
 
 
-def reference_single_box(orc):
+def reference_single_box(orc, N=N):
     L = orc.lib()
     g = orc.geom(N)
-    phi0, rhs0, b0 = global_fields()
+    phi0, rhs0, b0 = global_fields(N)
     b = []
     for d in range(3):
         f = orc.Fab(N, orc.face(d), 0, 1)
@@ -58,7 +75,7 @@ def reference_single_box(orc):
     return phi.valid(N)[..., 0].copy()
 
 
-def worker(rank, world, port, out_dir):
+def worker(rank, world, port, out_dir, case="x4"):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import torch
@@ -70,9 +87,10 @@ def worker(rank, world, port, out_dir):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     L = orc.lib()
+    N, BOXES, OWNERS = layout(case)
     geom = lib.Geom.make(N)
     desc = host_plan(lib, BOXES, OWNERS, rank, (0, 0, 0), 1, geom)
-    phi0, rhs0, b0 = global_fields()
+    phi0, rhs0, b0 = global_fields(N)
     mine = [i for i, o in enumerate(OWNERS) if o == rank]
     fabs, levs, keep = {}, {}, []
     for bi in mine:
@@ -165,3 +183,27 @@ def test_two_rank_gloo_halo_exchange_matches_single_rank(orc, tmp_path):
                 got[tuple(slice(lo[q], hi[q] + 1) for q in range(3))] = z[f"box{bi}"]
     assert np.array_equal(got, ref), np.abs(got - ref).max()
     assert gmax[0] == gmax[1] == np.abs(ref).max()
+
+
+def test_eight_rank_gloo_halo_exchange_of_the_bench_layout(orc, tmp_path):
+    """the layout of bench.py --gpus 8 (1 x 2 x 4 boxes of 8^3, every rank owns one box, every face of a box towards another rank or its
+    periodic image) on an 8-member gloo world: the product's plans, message matching and the all-reduce give the single-box sweep bit
+    for bit.  No device is opened: the eight-rank world of the GPU path is bounded by the processes a test may run on the GPU."""
+    import torch.multiprocessing as mp
+    n, boxes, owners = layout("bench8")
+    assert len(set(owners)) == 8 and n == (8, 16, 32)
+    ref = reference_single_box(orc, n)
+    import socket
+    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    mp.spawn(worker, args=(8, port, str(tmp_path), "bench8"), nprocs=8, join=True)
+    got = np.zeros(n)
+    gmax = []
+    for r in range(8):
+        z = np.load(os.path.join(str(tmp_path), f"rank{r}.npz"))
+        gmax.append(float(z["gmax"]))
+        lo, hi = boxes[r]
+        got[tuple(slice(lo[q], hi[q] + 1) for q in range(3))] = z[f"box{r}"]
+    assert np.array_equal(got, ref), np.abs(got - ref).max()
+    assert all(g == np.abs(ref).max() for g in gmax)

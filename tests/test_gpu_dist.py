@@ -14,6 +14,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = (16, 16, 16)
 BOXES = [((0, 0, 0), (15, 15, 7)), ((0, 0, 8), (15, 15, 15))]
 NSTEPS = 2
+# rank processes started at once.  The machines that run this suite stop a job in which more than 6 processes have the GPU open; the
+# pytest process holds the device as well, so 4 ranks keep a margin.  An 8-member world runs on the CPU instead
+# (tests/test_cpu_dist.py::test_eight_rank_gloo_halo_exchange_of_the_bench_layout).
+MAX_RANKS = 4
 
 
 def free_port():
@@ -40,7 +44,7 @@ def run(rank, world, port, out_dir, agg, case="tg"):
     if case == "rows128":    # boxes whose rows span the domain, split in y and z over the ranks: the multi-box red + black sweep with its two-layer
         N = (128, 96, 64)    # exchange, issued in two parts around the exchange (interior tiles on the main stream, the rest on the side stream)
         BOXES = [((0, 48 * (q % 2), 32 * (q // 2)), (127, 48 * (q % 2) + 47, 32 * (q // 2) + 31)) for q in range(4)]
-    if case.startswith("grid"):   # bench.py's layout for N ranks: one 16^3 box per rank on the most cubic process grid (4 -> 2x2x1, 8 -> 2x2x2)
+    if case.startswith("grid"):   # bench.py's layout for N ranks: one 16^3 box per rank on its process grid (4 -> 1x2x2, 8 -> 1x2x4)
         import bench
         nr = int(case[4:])
         pg = bench.proc_grid(nr)
@@ -70,7 +74,7 @@ def run(rank, world, port, out_dir, agg, case="tg"):
     if case == "regrid":
         return run_regrid(rank, world, out_dir)
     owners = list(range(len(BOXES))) if world > 1 else [0] * len(BOXES)     # case 'tg' on 3 ranks: rank 2 owns no box
-    if case == "rows128":
+    if case == "rows128" or case.startswith("grid"):
         owners = [q % world for q in range(len(BOXES))]
     if case == "slabs":
         owners = [(q // 4) % world for q in range(len(BOXES))]
@@ -388,30 +392,36 @@ def test_four_ranks_stacked_boxes_like_the_bench(tmp_path):
 
 @pytest.mark.parametrize("nr", [4, 8])
 def test_bench_process_grid_layouts(tmp_path, nr):
-    """the box layout bench.py builds for 4 / 8 GPUs (proc_grid: 2x2x1 / 2x2x2, every rank has a neighbour in each refined direction,
-    SURVEY 8e) on nr ranks sharing the GPU over the callback transport: same result as one rank holding all boxes"""
+    """the box layout bench.py builds for 4 / 8 GPUs (proc_grid: 1x2x2 / 1x2x4, every rank has a neighbour in each refined direction,
+    SURVEY 8e) on ranks sharing the GPU over the callback transport: same result as one rank holding all boxes.  At most MAX_RANKS rank
+    processes: the 8-box layout runs on 4 ranks that own two boxes each (box q on rank q % 4: every box still has its neighbours in y and
+    z on other ranks)"""
     import torch.multiprocessing as mp
     port = free_port()
     mp.spawn(run, args=(1, port, str(tmp_path), None, f"grid{nr}"), nprocs=1, join=True)
     ref = np.load(os.path.join(str(tmp_path), "w1_r0.npz"))
-    mp.spawn(run, args=(nr, free_port(), str(tmp_path), None, f"grid{nr}"), nprocs=nr, join=True)
-    for r in range(nr):
-        z = np.load(os.path.join(str(tmp_path), f"w{nr}_r{r}.npz"))
+    world = min(nr, MAX_RANKS)
+    mp.spawn(run, args=(world, free_port(), str(tmp_path), None, f"grid{nr}"), nprocs=world, join=True)
+    seen = set()
+    for r in range(world):
+        z = np.load(os.path.join(str(tmp_path), f"w{world}_r{r}.npz"))
         assert np.allclose(z["dts"], ref["dts"], rtol=1e-10, atol=0)
-        key = f"box{r}"
-        assert np.abs(z[key] - ref[key]).max() <= 1e-9, np.abs(z[key] - ref[key]).max()
+        for key in [k for k in z.files if k.startswith("box")]:
+            seen.add(key)
+            assert np.abs(z[key] - ref[key]).max() <= 1e-9, (key, np.abs(z[key] - ref[key]).max())
+    assert seen == {f"box{q}" for q in range(nr)}
 
 
 def test_bench_script_multi_rank_path(tmp_path):
     """bench.py launched the way the driver launches it for N > 1 (torch.distributed.run, one process per rank), here with 2 ranks
-    sharing the GPU over the host-staged transport (IAMRX_BENCH_TRANSPORT=gloo): the script must run to the end on every rank and
-    rank 0 must print one JSON line with the whole-job aggregate"""
+    sharing the GPU over the host-staged transport (IAMRX_BENCH_TRANSPORT=gloo), with --full (the sharded AMR workload and the section
+    pass are collective): the script must run to the end on every rank and rank 0 must print one JSON line with the whole-job aggregate"""
     import json
     import subprocess
     env = dict(os.environ, IAMRX_BENCH_TRANSPORT="gloo", MASTER_ADDR="127.0.0.1", IAMRX_BENCH_N="32")     # "--n" would be eaten by torchrun
     port = free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -419,6 +429,7 @@ def test_bench_script_multi_rank_path(tmp_path):
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["cells"] == 2 * 32 ** 3 and "cpu_baseline" not in d and d["transport"].startswith("gloo")
+    assert d["repeats"] == 5 and "amr" in d and "sections_ms_per_step" in d
     assert abs(d["value"] - d["config"]["cells"] * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
 
 

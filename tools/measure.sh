@@ -14,9 +14,9 @@ if [ -z "$SKIP_PMC" ]; then
 fi
 bash tools/profile_bench.sh $tag > $out/${tag}_profile.log 2>&1
 tail -12 $out/${tag}_profile.log
-# (profile_bench.sh leaves the bench line of the run UNDER rocprofv3 in ${tag}_bench.json: kept under its own name; the plain run is the record)
+# (profile_bench.sh leaves the bench line of the run UNDER rocprofv3 in ${tag}_bench.json: kept under its own name; the run without the profiler is the record)
 mv $out/${tag}_bench.json $out/${tag}_bench_under_rocprofv3.json
-timeout 1500 python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout 1500 python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 tail -c 300 $out/${tag}_bench.json
 export NAMELEN=90 NTOP=45
 bash tools/profile_step.sh > $out/${round}_step_1box.txt 2>&1
