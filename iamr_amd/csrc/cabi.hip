@@ -249,6 +249,79 @@ int iamrx_mf_copy(iamrx_mf d, iamrx_mf s, int sc, int dc, int nc, int ng) { IAMR
 int iamrx_mf_fill_boundary(iamrx_mf m, const iamrx_geom* g) { IAMRX_TRY m->mf.FillBoundary(to_geom(g)); IAMRX_CATCH }
 int iamrx_mf_norm0(iamrx_mf m, int comp, int nc, int ng, double* out) { IAMRX_TRY *out = m->mf.norm0(comp, nc, ng); IAMRX_CATCH }
 
+// device results of the reductions whose finish stays on the device (forms of the device-resident Krylov loop), read back here
+static double* reduce_dev_out()
+{
+    static double* d = nullptr;
+    if (!d) IAMRX_HIP_CHECK(hipMalloc(&d, 8 * sizeof(double)));
+    return d;
+}
+static void reduce_dev_read(double* out, int n)
+{
+    auto& ctx = Context::get();
+    IAMRX_HIP_CHECK(hipMemcpyAsync(out, reduce_dev_out(), n * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
+    ctx.sync();
+}
+
+extern "C++" template <int NC>
+static void norm0_max_f(const MultiFab& m, int comp, int ng, bool on_device, double* out)
+{
+    const FabD* tab = m.d_tab;
+    // |v| per point with a NaN kept as NaN: the combine steps of k_reduce_max_f / k_reduce_finish must carry it wherever it sits
+    auto f = [=] __device__(int i, int j, int k, int fab, double* mm) {
+        for (int n = 0; n < NC; ++n) { const double a = fabs(tab[fab](i, j, k, comp + n)); if (a > mm[n] || a != a) mm[n] = a; }
+    };
+    if (on_device) { reduce_max_f_dev<NC>(*m.layout, m.type, ng, f, reduce_dev_out()); reduce_dev_read(out, NC); }
+    else reduce_max_f<NC>(*m.layout, m.type, ng, f, out);
+    for (int n = 0; n < NC; ++n) if (out[n] != out[n]) out[n] = INFINITY;
+}
+
+int iamrx_mf_norm0_comps(iamrx_mf m, int comp, int nc, int ng, int form, double* out)
+{
+    IAMRX_TRY
+    if (form == 0) { reduce_norm0_comps(m->mf, comp, nc, ng, out); return 0; }
+    if (form != 1 && form != 2) throw Error("iamrx_mf_norm0_comps: form must be 0, 1 or 2");
+    const bool dev = form == 2;
+    if (nc == 1) norm0_max_f<1>(m->mf, comp, ng, dev, out);
+    else if (nc == 3) norm0_max_f<3>(m->mf, comp, ng, dev, out);
+    else if (nc == 6) norm0_max_f<6>(m->mf, comp, ng, dev, out);
+    else throw Error("iamrx_mf_norm0_comps: forms 1 and 2 take ncomp = 1, 3 or 6");
+    IAMRX_CATCH
+}
+
+int iamrx_mf_minmax(iamrx_mf m, int comp, int ng, double* mn, double* mx) { IAMRX_TRY reduce_minmax(m->mf, comp, ng, *mn, *mx); IAMRX_CATCH }
+
+// the owner weights of the nodal solver: half_lo / half_hi as NodalMG sets them from its boundary codes (inflow is a Neumann wall there)
+static Geometry owner_geom(const iamrx_geom* g, const int lobc[3], const int hibc[3])
+{
+    Geometry r = to_geom(g);
+    for (int d = 0; d < 3; ++d) {
+        const int lo = lobc ? lobc[d] : lo_periodic, hi = hibc ? hibc[d] : lo_periodic;
+        r.half_lo[d] = (!r.periodic[d] && (lo == lo_neumann || lo == lo_inflow)) ? 1 : 0;
+        r.half_hi[d] = (!r.periodic[d] && (hi == lo_neumann || hi == lo_inflow)) ? 1 : 0;
+    }
+    return r;
+}
+
+int iamrx_mf_dot(const iamrx_geom* g, const int lobc[3], const int hibc[3], iamrx_mf x0, iamrx_mf y0, iamrx_mf x1, iamrx_mf y1, int comp,
+                 int nc, int on_device, double out[2])
+{
+    IAMRX_TRY
+    if (!x1 != !y1) throw Error("iamrx_mf_dot: x1 and y1 are both given or both NULL");
+    const int nout = x1 ? 2 : 1;
+    const MultiFab* xs[2] = {&x0->mf, x1 ? &x1->mf : nullptr};
+    const MultiFab* ys[2] = {&y0->mf, y1 ? &y1->mf : nullptr};
+    const Geometry gg = owner_geom(g, lobc, hibc);
+    if (on_device) { reduce_dots_dev(nout, xs, ys, comp, nc, gg, reduce_dev_out()); reduce_dev_read(out, nout); }
+    else reduce_dots(nout, xs, ys, comp, nc, gg, out);
+    IAMRX_CATCH
+}
+
+int iamrx_mf_sum_unique(const iamrx_geom* g, const int lobc[3], const int hibc[3], iamrx_mf m, int comp, double* out)
+{
+    IAMRX_TRY *out = reduce_sum_unique(m->mf, comp, owner_geom(g, lobc, hibc)); IAMRX_CATCH
+}
+
 static AbecCoef make_coef(double alpha, double beta, iamrx_mf a, iamrx_mf bx, iamrx_mf by, iamrx_mf bz, int tensor)
 {
     AbecCoef c;

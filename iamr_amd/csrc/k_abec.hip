@@ -1633,7 +1633,6 @@ __device__ __forceinline__ void norm_commit(double mx, unsigned long long* out)
         if (bits > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, bits);
     }
 }
-__device__ __forceinline__ double norm_term(double v) { const double a = fabs(v); return a == a ? a : INFINITY; }
 
 template <int BMODE>
 __global__ void __launch_bounds__(256) k_abec_residual(Tiling t, const BoxD* __restrict__ boxes,
@@ -1917,6 +1916,7 @@ __device__ __forceinline__ double bot_sum(double v, double* red)
 template <int NW = BOT_NT / 64>
 __device__ __forceinline__ double bot_max(double v, double* red)
 {
+    v = v == v ? v : INFINITY;       // v = |.| of this thread; NaN -> +inf (launch.h: norm_term), which fmax keeps
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;

@@ -147,7 +147,7 @@ void launch_unpack_w(const CopyDesc* d, const int2* w, int nw, const FabD* dst, 
 template <int OP> __device__ __forceinline__ double red_op(double a, double b)
 {
     if (OP == 0) return a + b;
-    return a > b ? a : b;
+    return (a > b || a != a) ? a : b;          // maxima: a NaN operand wins on either side (the functor reductions' partials may hold one)
 }
 template <int OP> __device__ __forceinline__ double block_reduce(double v)
 {
@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(256) k_norm0(Tiling t, const BoxD* __restrict_
     if (tile_ijk(t, b, i, j, k0, k1)) {
         const FabD a = tab[fab];
         for (int n = 0; n < nc; ++n)
-            for (int k = k0; k <= k1; ++k) { double v = fabs(a(i, j, k, comp + n)); m = v > m ? v : m; }
+            for (int k = k0; k <= k1; ++k) { const double v = norm_term(a(i, j, k, comp + n)); m = v > m ? v : m; }
     }
     m = block_reduce<1>(m);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = m;
@@ -241,7 +241,8 @@ double reduce_norm0(const MultiFab& mf, int comp, int nc, int ng, bool global)
     return finish_to_host(1, 1, np, global);
 }
 
-// largest and smallest value of one component in ONE pass and one read-back (partials: block maxima of v, then of -v)
+// largest and smallest value of one component in ONE pass and one read-back (partials: block maxima of v, then of -v); a NaN counts as
+// +inf in both (mx = +inf, mn = -inf)
 __global__ void __launch_bounds__(256) k_minmax(Tiling t, const BoxD* __restrict__ boxes, int t0, int t1, int t2, int ng,
                                                 const FabD* __restrict__ tab, int comp, double* __restrict__ partials, int np)
 {
@@ -251,7 +252,11 @@ __global__ void __launch_bounds__(256) k_minmax(Tiling t, const BoxD* __restrict
     const bool in = tile_ijk(t, b, i, j, k0, k1);
     const FabD a = tab[fab];
     double hi = -1.7976931348623157e308, lo = -1.7976931348623157e308;
-    if (in) for (int k = k0; k <= k1; ++k) { const double v = a(i, j, k, comp); hi = v > hi ? v : hi; lo = -v > lo ? -v : lo; }
+    if (in)
+        for (int k = k0; k <= k1; ++k) {
+            const double v = a(i, j, k, comp), vh = v == v ? v : INFINITY, vl = v == v ? -v : INFINITY;
+            hi = vh > hi ? vh : hi; lo = vl > lo ? vl : lo;
+        }
     hi = block_reduce<1>(hi);
     lo = block_reduce<1>(lo);
     if (threadIdx.x == 0) {
@@ -289,7 +294,7 @@ __global__ void __launch_bounds__(256) k_norm0_comps(Tiling t, const BoxD* __res
     const FabD a = tab[fab];
     for (int n = 0; n < nc; ++n) {
         double m = 0.0;
-        if (in) for (int k = k0; k <= k1; ++k) { double v = fabs(a(i, j, k, comp + n)); m = v > m ? v : m; }
+        if (in) for (int k = k0; k <= k1; ++k) { const double v = norm_term(a(i, j, k, comp + n)); m = v > m ? v : m; }
         m = block_reduce<1>(m);
         if (threadIdx.x == 0) partials[(size_t)n * np + (size_t)blockIdx.y * gridDim.x + blockIdx.x] = m;
     }

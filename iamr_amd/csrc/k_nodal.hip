@@ -1206,6 +1206,7 @@ __device__ __forceinline__ double nb_sum(double v, double* red)
 }
 __device__ __forceinline__ double nb_max(double v, double* red)
 {
+    v = v == v ? v : INFINITY;       // v = |.| of this thread; NaN -> +inf (the rule of every max norm), which fmax keeps
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -1355,6 +1356,7 @@ __device__ __forceinline__ double nbg_sum(double v, double* red)
 }
 __device__ __forceinline__ double nbg_max(double v, double* red)
 {
+    v = v == v ? v : INFINITY;       // v = |.| of this thread; NaN -> +inf (the rule of every max norm), which fmax keeps
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;

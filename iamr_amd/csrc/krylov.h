@@ -59,6 +59,8 @@ template <class Apply>
 int bicgstab_device(const Layout& lay, const IndexType& type, int nc, const Geometry& g, MultiFab& sol, MultiFab& r, const MultiFab& rh, MultiFab& ph, MultiFab& sh,
                     MultiFab& v, MultiFab& t, double rnorm0, double eps_rel, double eps_abs, int maxiter, Apply apply, int& niters, double& rnorm)
 {
+    // no iteration allowed: what the host-driven loop returns when its loop body never runs (no launch, no status word to wait for)
+    if (maxiter < 1) { niters = 1; rnorm = rnorm0; return 0; }
     auto& ctx = Context::get();
     static double* S = nullptr;
     static double* hS = nullptr;       // two pinned copies, alternating
@@ -99,7 +101,7 @@ int bicgstab_device(const Layout& lay, const IndexType& type, int nc, const Geom
                 solt[f](i, j, k, n) = 1.0 * solt[f](i, j, k, n) + alpha * pht[f](i, j, k, n);
                 const double s = 1.0 * rt[f](i, j, k, n) + malpha * vt[f](i, j, k, n);
                 sht[f](i, j, k, n) = s;
-                const double a = fabs(s);
+                const double a = norm_term(s);
                 m[0] = a > m[0] ? a : m[0];
             }
         }, S + KS_NORM);
@@ -115,7 +117,7 @@ int bicgstab_device(const Layout& lay, const IndexType& type, int nc, const Geom
                 solt[f](i, j, k, n) = 1.0 * solt[f](i, j, k, n) + omega * s;
                 const double rn = 1.0 * s + momega * tt[f](i, j, k, n);
                 rt[f](i, j, k, n) = rn;
-                const double a = fabs(rn);
+                const double a = norm_term(rn);
                 m[0] = a > m[0] ? a : m[0];
             }
         }, S + KS_NORM);

@@ -170,6 +170,10 @@ __device__ __forceinline__ bool tile_ijk(const Tiling& t, const BoxD& b, int& i,
     return i <= b.hi[0] && j <= b.hi[1] && k0 <= b.hi[2];
 }
 
+// The one rule of every maximum of absolute values (norms): a point's term is |v|, NaN -> +inf.  A maximum over such terms never meets a
+// NaN, so it does not depend on the order it is formed in (lane, wave, workgroup, box): a NaN anywhere gives +inf, +-inf gives +inf.
+__device__ __forceinline__ double norm_term(double v) { const double a = fabs(v); return a == a ? a : INFINITY; }
+
 __device__ __forceinline__ BoxD dev_grow_convert(BoxD b, int t0, int t1, int t2, int ng)
 {
     b.lo[0] -= ng; b.lo[1] -= ng; b.lo[2] -= ng;
@@ -215,14 +219,15 @@ __global__ void __launch_bounds__(256) k_reduce_max_f(Tiling t, const BoxD* __re
 #pragma unroll
     for (int n = 0; n < NOUT; ++n) {
         double v = m[n];
-        for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(v, off, 64); v = o > v ? o : v; }
+        // (a NaN partial wins on either side of every combine: where it sits does not decide whether it survives)
+        for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(v, off, 64); v = (o > v || o != o) ? o : v; }
         if (lane == 0) sm[n][w] = v;
     }
     __syncthreads();
     if (threadIdx.x < NOUT) {
         const int n = threadIdx.x;
         double v = sm[n][0];
-        for (int q = 1; q < 4; ++q) v = sm[n][q] > v ? sm[n][q] : v;
+        for (int q = 1; q < 4; ++q) v = (sm[n][q] > v || sm[n][q] != sm[n][q]) ? sm[n][q] : v;
         partials[(size_t)n * np + (size_t)blockIdx.y * gridDim.x + blockIdx.x] = v;
     }
 }

@@ -878,6 +878,8 @@ MGStats CellMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, double
     level_residual(L0.g, coef(0), L0.res, phi, &rhs, &st.resnorm0);      // the residual launch reduces its own max norm
     st.rhsnorm0 = rhs.norm0(0, nc, 0);
     const double max_norm = st.rhsnorm0 >= st.resnorm0 ? st.rhsnorm0 : st.resnorm0;
+    // (see NodalMG::solve)
+    if (!std::isfinite(max_norm)) throw Error("iamrx MLMG: the right-hand side or the initial residual is not finite");
     const double res_target = std::max(atol, std::max(rtol, 1.e-16) * max_norm);
     st.resnorm = st.resnorm0;
     if (m_o.verbose) printf("iamrx MLMG: rhs %.6e resid0 %.6e target %.3e levels %d\n", st.rhsnorm0, st.resnorm0, res_target, st.nlevels);

@@ -472,6 +472,9 @@ MGStats NodalMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, doubl
     L0.res_filled = false;
     st.rhsnorm0 = rhs.norm0(0, 1, 0);
     const double max_norm = st.rhsnorm0 >= st.resnorm0 ? st.rhsnorm0 : st.resnorm0;
+    // a NaN or inf in the right-hand side or the initial residual (the norms report both as +inf) leaves nothing to converge to, and with
+    // res_target = +inf every convergence test below would pass
+    if (!std::isfinite(max_norm)) throw Error("iamrx nodal MLMG: the right-hand side or the initial residual is not finite");
     const double res_target = std::max(atol, std::max(rtol, 1.e-16) * max_norm);
     st.resnorm = st.resnorm0;
     if (m_o.verbose) printf("iamrx nodal MLMG: rhs %.6e resid0 %.6e levels %d (fused sweep %d, single-workgroup coarse smoother %d, ghost width %d)\n",

@@ -256,6 +256,19 @@ class MultiFab:
         check(lib().iamrx_mf_norm0(self.h, comp, self.ncomp if ncomp is None else ncomp, ngrow, C.byref(out)))
         return out.value
 
+    def norm0_comps(self, comp=0, ncomp=None, ngrow=0, form=0):
+        """per-component max norms; form 0 MultiFab::norm0_comps, 1 / 2 the functor reduction with the host / device finish (ncomp 1, 3, 6)"""
+        nc = self.ncomp - comp if ncomp is None else ncomp
+        out = (C.c_double * nc)()
+        check(lib().iamrx_mf_norm0_comps(self.h, comp, nc, ngrow, form, out))
+        return list(out)
+
+    def minmax(self, comp=0, ngrow=0):
+        """(smallest, largest) value of one component over the valid region grown by ngrow"""
+        mn, mx = C.c_double(), C.c_double()
+        check(lib().iamrx_mf_minmax(self.h, comp, ngrow, C.byref(mn), C.byref(mx)))
+        return mn.value, mx.value
+
     def dev_ptr(self, li=0):
         p = C.POINTER(C.c_double)()
         check(lib().iamrx_mf_dev_ptr(self.h, li, C.byref(p)))
@@ -271,6 +284,20 @@ class MultiFab:
 
 def _h(m):
     return m.h if m is not None else None
+
+
+def dot(geom, x0, y0, x1=None, y1=None, comp=0, ncomp=1, on_device=0, lobc=(0, 0, 0), hibc=(0, 0, 0)):
+    """owner-weighted dot products x0.y0 (and x1.y1); lobc / hibc: the nodal solver's LinOpBC codes (Neumann walls weigh 1/2)"""
+    out = (C.c_double * 2)()
+    check(lib().iamrx_mf_dot(C.byref(geom), i3(lobc), i3(hibc), x0.h, y0.h, _h(x1), _h(y1), comp, ncomp, int(on_device), out))
+    return list(out) if x1 is not None else out[0]
+
+
+def sum_unique(geom, m, comp=0, lobc=(0, 0, 0), hibc=(0, 0, 0)):
+    """owner-weighted sum of one component (MultiFab::sum_unique), the weights of dot()"""
+    out = C.c_double()
+    check(lib().iamrx_mf_sum_unique(C.byref(geom), i3(lobc), i3(hibc), m.h, comp, C.byref(out)))
+    return out.value
 
 
 def abec_gsrb(geom, alpha, beta, a, b, phi, rhs, redblack, omega=1.15, lobc=(0, 0, 0), hibc=(0, 0, 0), maxorder=3):

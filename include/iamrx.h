@@ -154,6 +154,24 @@ int iamrx_mf_fill_boundary(iamrx_mf m, const iamrx_geom* g);              /* Fil
 int iamrx_mf_fill_physbc(iamrx_mf m, const iamrx_geom* g, int scomp, int ncomp, const int* bcrec, const double* extdir_lo,
                          const double* extdir_hi);
 int iamrx_mf_norm0(iamrx_mf m, int comp, int ncomp, int ngrow, double* out);   /* MultiFab::norm0: Source/NavierStokesBase.cpp:4408 */
+/* The library's other level-wide reductions, each a thin call of the internal one (tests/test_gpu_reductions.py compares them with
+ * numpy).  Every maximum of absolute values follows one rule: a NaN anywhere in the region read gives +inf, +-inf gives +inf, and the
+ * result does not depend on where the NaN sits.
+ * norm0_comps: out[n] = max |m(comp + n)| over the valid region grown by ngrow, n < ncomp.  form 0: MultiFab::norm0_comps; form 1: the
+ * functor reduction (reduce_max_f<ncomp>, finish read back by the host); form 2: the same with the finish left on the device
+ * (reduce_max_f_dev<ncomp>, the device-resident Krylov loop's form), then copied back.  Forms 1 and 2 take ncomp = 1, 3 or 6; their
+ * per-point functor keeps a NaN as NaN, so the combine steps have to carry it to the end, where it is reported as +inf. */
+int iamrx_mf_norm0_comps(iamrx_mf m, int comp, int ncomp, int ngrow, int form, double* out);
+/* smallest and largest value of one component over the valid region grown by ngrow; a NaN gives mn = -inf, mx = +inf */
+int iamrx_mf_minmax(iamrx_mf m, int comp, int ngrow, double* mn, double* mx);
+/* owner-weighted dot products over the valid points (MultiFab::Dot of the solvers): out[0] = x0.y0, out[1] = x1.y1 (x1 = y1 = NULL: out[0]
+ * only), components comp .. comp + ncomp - 1.  Nodal / face data: every point counted once, weight 1/2 per Neumann wall a node lies on;
+ * lobc / hibc are the LinOpBC codes of iamrx_nodal_solve and give the walls as the nodal solver sees them.  on_device: the finish
+ * left on the device (the device-resident Krylov loop's form), then copied back. */
+int iamrx_mf_dot(const iamrx_geom* g, const int lobc[3], const int hibc[3], iamrx_mf x0, iamrx_mf y0, iamrx_mf x1, iamrx_mf y1, int comp,
+                 int ncomp, int on_device, double out[2]);
+/* owner-weighted sum of one component (MultiFab::sum_unique), with the weights of iamrx_mf_dot */
+int iamrx_mf_sum_unique(const iamrx_geom* g, const int lobc[3], const int hibc[3], iamrx_mf m, int comp, double* out);
 
 /* host-only (works without a GPU): the ghost-exchange plan that `rank` executes for FillBoundary of a level
  * (FabArray::FillBoundary role).  desc: 16 ints per descriptor = kind (0 local copy, 1 pack+send, 2 recv+unpack),
