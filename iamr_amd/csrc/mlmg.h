@@ -83,6 +83,44 @@ long mg_agglomeration_cells();
 bool mg_agglomerate_level(const Layout& coarse);      // mlmg.hip
 bool mg_slab_level(const Geometry& g, const Layout& l, int min_width, bool slab_problem);      // mlmg.hip: y kept at two cells from here on
 Geometry mg_slab_geom(const Geometry& fine);
+// Krylov iterations of the device bottom solvers, summed over the V-cycles of the running solve (one counter: solves do not overlap)
+int* mg_bottom_iters_dev();
+
+// What a level of either hierarchy (CellMG, NodalMG) is as far as the hierarchy goes; the solvers' Level structs add their operator's arrays.
+struct MGLevel {
+    Geometry g;
+    LayoutP layout;
+    bool slab = false;         // slab level (mlmg.hip: mg_slab_level): two cells in y kept; virt = the one-plane coarsening of the level
+    LayoutP virt;              // above, through which the restrictions go (vres: their target, duplicated into res / tmp_d)
+    MultiFab vres;
+    // agglomeration (multi-rank): from this level down every rank holds the whole level; dist = the distributed coarsening
+    // of the level above, through which restriction results are gathered and corrections are picked out
+    bool agg = false;
+    LayoutP dist;
+    MultiFab tmp_d;
+    bool res_filled = false;   // the ghost layer of the level's `res` is current (filled once per V-cycle, not once per smooth call)
+};
+// c = the coarsening of level f (geometry and layouts): isotropic while every box is coarsenable (MLLinOp::defineGrids), else a slab level,
+// agglomerated where mg_agglomerate_level says so; false: f cannot be coarsened
+bool mg_coarsen_level(const MGLevel& f, const MGOpts& o, MGLevel& c);      // mlmg.hip
+
+// A restriction onto level C: op(target) writes dst; its distributed form (agglomerated level: gathered afterwards); or, for a slab level,
+// the one-plane virtual level, whose plane is then duplicated.  dist_arr / virt_arr: arrays on C.dist / C.virt where C has them.
+template <class Op>
+void mg_restrict_to(const MGLevel& C, MultiFab& dst, MultiFab& dist_arr, MultiFab& virt_arr, Op op)
+{
+    MultiFab& held = C.agg ? dist_arr : dst;
+    op(C.slab ? virt_arr : held);
+    if (C.slab) slab_duplicate(held, virt_arr);
+    if (C.agg) gather_to_replicated(dst, dist_arr);
+}
+// The correction of level C as the level above can read it: an agglomerated level's is picked out into its distributed form (ng ghost layers)
+inline const MultiFab& mg_correction_of(MGLevel& C, const MultiFab& cor, int ng)
+{
+    if (!C.agg) return cor;
+    scatter_from_replicated(C.tmp_d, cor, ng);
+    return C.tmp_d;
+}
 
 
 struct MGStats {
@@ -118,6 +156,7 @@ public:
     void fluxes(MultiFab& phi, MultiFab* const flux[3], MultiFab* const add_to[3]);
     int nlevels() const { return (int)m_lev.size(); }
     AbecCoef coef(int l) const;
+    AbecCoef smoother_coef(int l) const;   // the smoother acts on the ABec part; cross terms enter through the residual
     const Geometry& geom(int l) const { return m_lev[l].g; }
     void applyBC(int l, MultiFab& phi, bool inhomog, const MultiFab* bcval, bool corners = true);
     // cf_ghosts_current: the coarse/fine ghost cells are already what a fill would write (kept so by the passes themselves, k_abec.hip cf_maintain)
@@ -135,27 +174,18 @@ public:
     MultiFab& cor(int l) { return m_lev[l].cor; }
 
 private:
-    struct Level {
-        Geometry g;
-        LayoutP layout;
+    struct Level : MGLevel {
         MultiFab a, b[3];          // owned (coarse levels)
         MultiFab cor, res, rescor;
         MultiFab buf;              // second buffer of the fused (out-of-place) GSRB sweeps
         int wk_flag = -1;          // the colour passes of this level apply the domain walls themselves (abec_gsrb_walls_inkernel_ok; -1: not asked yet)
-        bool res_filled = false;   // multi-box sweep kernel: the ghost layer of `res` is current (filled once per V-cycle)
-        bool slab = false;         // slab level (mlmg.hip: mg_slab_level): two cells in y kept; virt = the one-plane coarsening of the level
-        LayoutP virt;              // above, through which the restrictions go (vres: their target, duplicated into res / tmp_d)
-        MultiFab vres;
-        // agglomeration (multi-rank): from this level down every rank holds the whole level; dist = the distributed coarsening
-        // of the level above, through which restriction results are gathered and corrections are picked out
-        bool agg = false;
-        LayoutP dist;
-        MultiFab tmp_d;
         MultiFab cfm;              // coarse/fine mask (levels that do not cover the domain), see cf_build_mask
         CfTab cftab;
     };
     int bicgstab(int l, MultiFab& sol, const MultiFab& rhs, double eps_rel, double eps_abs, int& niters);
     void bottom_solve(MGStats& st);
+    // nsweeps out-of-place sweeps sweep(in, out, zero, last) between sol and buf, the result in sol (or in acc: see smooth_n)
+    template <class Sweep> void pingpong(MultiFab& sol, MultiFab& buf, int nsweeps, bool sol_is_zero, MultiFab* acc, Sweep sweep);
     bool tail_fused() const;
     void cf_bcval(MultiFab& bcval);
     void subtract_mean(int l, MultiFab& mf);
@@ -226,20 +256,11 @@ public:
     MultiFab& cor(int l) { return m_lev[l].cor; }
 
 private:
-    struct Level {
-        Geometry g;
-        LayoutP layout;
+    struct Level : MGLevel {
         MultiFab sig;              // cell, 1 ghost
         MultiFab cor, res, rescor; // node, 1 ghost
         MultiFab tmp;              // Jacobi scratch
-        bool agg = false;          // see CellMG::Level
-        LayoutP dist;
-        MultiFab tmp_d;
-        bool slab = false;         // slab level, see CellMG::Level
-        LayoutP virt;
-        MultiFab vres;
         MultiFab xb;               // second buffer of the out-of-place fused Gauss-Seidel sweeps
-        bool res_filled = false;   // the ghost nodes of `res` are current (filled once per V-cycle, not once per smooth call)
         MultiFab dm;               // Dirichlet node mask (defined only if the level has Dirichlet nodes, see NodalMG ctor)
         const MultiFab* dmask() const { return dm.defined() ? &dm : nullptr; }
     };

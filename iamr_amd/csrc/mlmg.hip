@@ -15,12 +15,7 @@ void parallel_copy(MultiFab& dst, const MultiFab& src, int scomp, int dcomp, int
 
 CycleTimer& cycle_timer() { static CycleTimer t; return t; }
 
-long mg_agglomeration_cells()
-{
-    static long v = -1;
-    v = (long)tune("MG_AGGLOMERATE_CELLS", 2097152.0);
-    return v;
-}
+long mg_agglomeration_cells() { return (long)tune("MG_AGGLOMERATE_CELLS", 2097152.0); }
 
 // A coarse multigrid level is agglomerated -- continued on a layout that holds the whole level on this rank, its boxes merged
 // (Layout::make_replicated) -- when it is small (IAMRX_MG_AGGLOMERATE_CELLS) and either spread over several ranks or, on one rank, made of
@@ -52,6 +47,39 @@ Geometry mg_slab_geom(const Geometry& f)
     c.domain.lo[1] = 0; c.domain.hi[1] = 1;
     for (int d = 0; d < 3; ++d) c.dx[d] = f.dx[d] * 2.0;
     return c;
+}
+
+bool mg_coarsen_level(const MGLevel& f, const MGOpts& o, MGLevel& c)
+{
+    bool dom_ok = true;
+    for (int d = 0; d < 3; ++d) if (f.g.domain.len(d) % 2 != 0 || f.g.domain.len(d) / 2 < o.min_width) dom_ok = false;
+    const bool iso = dom_ok && f.layout->coarsenable(2, o.min_width);
+    const bool slab = !iso && mg_slab_level(f.g, *f.layout, o.min_width, o.slab != 0);
+    if (!iso && !slab) return false;
+    // (everything else of the geometry -- the nodal solver's half_lo / half_hi -- is the fine level's, as in mg_slab_geom)
+    c.g = f.g;
+    c.g.domain = slab ? mg_slab_geom(f.g).domain : coarsen(f.g.domain, 2);
+    for (int d = 0; d < 3; ++d) c.g.dx[d] = f.g.dx[d] * 2.0;
+    c.slab = slab;
+    if (slab) {
+        c.virt = f.layout->coarsened(2);             // the one-plane coarsening the transfers write to
+        c.layout = f.layout->slab_coarsened();
+    } else c.layout = f.layout->coarsened(2);
+    if (mg_agglomerate_level(*c.layout)) {
+        c.agg = true;
+        c.dist = c.layout;
+        c.layout = c.dist->make_replicated();
+    }
+    return true;
+}
+
+// Krylov iterations of the device bottom solvers, summed over the V-cycles of the running solve (one counter: solves do not overlap -- a
+// nodal solve never runs inside a cell-centred one or the reverse)
+int* mg_bottom_iters_dev()
+{
+    static int* d = nullptr;
+    if (!d) { IAMRX_HIP_CHECK(hipMalloc(&d, sizeof(int))); IAMRX_HIP_CHECK(hipMemset(d, 0, sizeof(int))); }
+    return d;
 }
 
 CellMG::CellMG(const Geometry& g, LayoutP layout, int ncomp, const DomainBC& bc, const MGOpts& o)
@@ -93,6 +121,14 @@ AbecCoef CellMG::coef(int l) const
             c.tensor_eta = m_tensor_eta ? 1 : 0;
         }
     }
+    return c;
+}
+
+// the smoother acts on the ABec part; cross terms enter through the residual
+AbecCoef CellMG::smoother_coef(int l) const
+{
+    AbecCoef c = coef(l);
+    c.tensor = 0;
     return c;
 }
 
@@ -160,28 +196,8 @@ void CellMG::prepare()
         // a single box of at most 8^3 cells is solved by the single-workgroup device bottom solver (k_abec_bottom): no need to coarsen
         // further (IAMRX_MG_DEVICE_BOTTOM=0: host-driven BiCGStab on the coarsest possible level, upstream's shape)
         if (m_o.device_bottom && !m_tensor && !m_o.bottom_smoother_only && abec_bottom_device_ok(f.g, *f.layout, m_bcn.data(), (int)m_bcn.size(), m_ncomp, m_cf)) break;
-        bool dom_ok = true;
-        for (int d = 0; d < 3; ++d) if (f.g.domain.len(d) % 2 != 0 || f.g.domain.len(d) / 2 < m_o.min_width) dom_ok = false;
-        const bool iso = dom_ok && f.layout->coarsenable(2, m_o.min_width);
-        const bool slab = !iso && mg_slab_level(f.g, *f.layout, m_o.min_width, m_o.slab != 0);
-        if (!iso && !slab) break;
         Level c;
-        c.g = f.g;
-        if (slab) {
-            c.g = mg_slab_geom(f.g);
-            c.slab = true;
-            c.virt = f.layout->coarsened(2);             // the one-plane coarsening the transfers write to
-            c.layout = f.layout->slab_coarsened();
-        } else {
-        c.g.domain = coarsen(f.g.domain, 2);
-        for (int d = 0; d < 3; ++d) c.g.dx[d] = f.g.dx[d] * 2.0;
-        c.layout = f.layout->coarsened(2);
-        }
-        if (mg_agglomerate_level(*c.layout)) {
-            c.agg = true;
-            c.dist = c.layout;
-            c.layout = c.dist->make_replicated();
-        }
+        if (!mg_coarsen_level(f, m_o, c)) break;
         m_lev.push_back(std::move(c));
     }
     const int nl = (int)m_lev.size();
@@ -225,15 +241,11 @@ void CellMG::prepare()
             AbecCoef fc = coef(l - 1);
             if (L.agg) L.tmp_d.define(L.dist, cell_type(), m_ncomp, 0);
             if (L.slab) L.vres.define(L.virt, cell_type(), m_ncomp, 0);
-            // (slab level: the transfer writes the one-plane virtual level, whose plane is duplicated into the level's two)
             auto coarsen_into = [&](MultiFab& dst, IndexType t, int nc, const std::function<void(MultiFab&)>& op) {
-                LayoutP own = L.agg ? L.dist : L.layout;
-                MultiFab dist_arr;
-                MultiFab* target = &dst;
-                if (L.agg) { dist_arr.define(own, t, nc, 0); target = &dist_arr; }
-                if (L.slab) { MultiFab v(L.virt, t, nc, 0); op(v); slab_duplicate(*target, v); }
-                else op(*target);
-                if (L.agg) gather_to_replicated(dst, dist_arr);
+                MultiFab dist_arr, v;
+                if (L.agg) dist_arr.define(L.dist, t, nc, 0);
+                if (L.slab) v.define(L.virt, t, nc, 0);
+                mg_restrict_to(L, dst, dist_arr, v, op);
             };
             if (m_a0) {
                 L.a.define(L.layout, cell_type(), 1, 0);
@@ -302,18 +314,16 @@ static bool cf_maintain_on()
 bool CellMG::zero_first_pass_ok(int l, const MultiFab& sol) const
 {
     if (m_dd_sweeps > 0 || fused_smoother_ok(l)) return false;
-    AbecCoef c = coef(l);
+    const AbecCoef c = smoother_coef(l);
     const bool wrap = !m_cf && periodic_wrap_ok(m_lev[l].g, *m_lev[l].layout, 2);
     // (walls applied inside the colour passes: the first pass from zero reads no ghost cell either)
-    c.tensor = 0;
     const bool wk = !wrap && abec_gsrb_walls_inkernel_ok(m_lev[l].g, c, sol, (int)m_bcn.size(), m_bcn.data(), m_cf);
     return abec_gsrb_zero_ok(c, sol, (int)m_bcn.size(), wrap || wk, m_cf);
 }
 
 void CellMG::smooth(int l, MultiFab& sol, const MultiFab& rhs, bool skip_fill, bool cf_ghosts_current, bool sol_is_zero)
 {
-    AbecCoef c = coef(l);
-    c.tensor = 0;   // the smoother acts on the ABec part; cross terms enter through the residual
+    const AbecCoef c = smoother_coef(l);
     // one box spanning a fully periodic domain: the kernel reads the periodic images from the valid cells, no ghost fills
     const bool wrap = !m_cf && periodic_wrap_ok(m_lev[l].g, *m_lev[l].layout, 2);
     const bool maint = m_cf && m_ncomp == 1 && !m_tensor && cf_maintain_on();
@@ -366,124 +376,98 @@ bool CellMG::fused_smoother_ok(int l) const
 bool CellMG::nbr_sweep_ok(int l, const MultiFab& sol, const MultiFab& rhs) const
 {
     if (l != 0 || !m_nbr || m_cf) return false;
-    AbecCoef c = coef(l);
-    c.tensor = 0;
-    return abec_gsrb_rb_nbr_ok(m_lev[l].g, c, sol, rhs, (int)m_bcn.size(), m_bcn.data());
+    return abec_gsrb_rb_nbr_ok(m_lev[l].g, smoother_coef(l), sol, rhs, (int)m_bcn.size(), m_bcn.data());
 }
 
 // smooth_n runs the sweep kernel with in-kernel coarse/fine faces on this level (a refined box strictly inside its domain, finest level)
 bool CellMG::cf_sweep_ok(int l, const MultiFab& sol) const
 {
     if (l != 0 || !m_cf) return false;
-    AbecCoef c = coef(l);
-    c.tensor = 0;
-    return abec_gsrb_rb_cf_ok(m_lev[l].g, c, sol);
+    return abec_gsrb_rb_cf_ok(m_lev[l].g, smoother_coef(l), sol);
+}
+
+// Out-of-place sweeps ping-pong between sol and buf.  From a zero start the first sweep reads no input: an odd number of sweeps starts
+// "from" the buffer and ends in sol without a copy.  acc: the last sweep writes acc + correction into acc instead (see smooth_n).
+template <class Sweep>
+void CellMG::pingpong(MultiFab& sol, MultiFab& buf, int nsweeps, bool sol_is_zero, MultiFab* acc, Sweep sweep)
+{
+    MultiFab* a = &sol;
+    MultiFab* b = &buf;
+    if (sol_is_zero && (nsweeps & 1)) std::swap(a, b);
+    for (int i = 0; i < nsweeps; ++i) {
+        const bool last = acc && i == nsweeps - 1;
+        sweep(*a, last ? *acc : *b, sol_is_zero && i == 0, last);
+        if (last) { m_acc_done = true; return; }
+        std::swap(a, b);
+    }
+    if (a != &sol) MultiFab::Copy(sol, *a, 0, 0, m_ncomp, 0);
 }
 
 void CellMG::smooth_n(int l, MultiFab& sol, const MultiFab& rhs, int nsweeps, bool skip_first_fill, bool sol_is_zero, MultiFab* acc)
 {
     if (l != 0) acc = nullptr;
     if (nsweeps <= 0) { if (sol_is_zero) sol.setVal(0.0); return; }
-    if (cf_sweep_ok(l, sol)) {
-        // red + black in one out-of-place launch per sweep, the coarse/fine ghost values formed inside the kernel (no k_cf_fill, no ghost
-        // maintenance; sol's ghost cells are left stale: every reader behind a smoothing call fills them)
-        AbecCoef c = coef(l);
-        c.tensor = 0;
-        Level& L = m_lev[l];
+    Level& L = m_lev[l];
+    const AbecCoef c = smoother_coef(l);
+    const DomainBC* bcs = m_bcn.data();
+    const int nbc = (int)m_bcn.size();
+    // Red + black in one out-of-place launch per sweep (k_abec_gsrb_rb), on the finest level only (on a coarser level of 128 cells in x a
+    // march of a few planes does not beat two colour passes): a refined box strictly inside its domain -- the coarse/fine ghost values are
+    // formed inside the kernel (no k_cf_fill, no ghost maintenance; sol's ghost cells are left stale: every reader behind a smoothing call
+    // fills them) -- or one box spanning a periodic domain
+    const bool cfs = cf_sweep_ok(l, sol);
+    if (cfs || (!m_cf && l == 0 && abec_gsrb_rb_ok(L.g, c, sol, nbc, bcs))) {
         if (!L.buf.defined()) L.buf.define(L.layout, cell_type(), m_ncomp, 1);
-        MultiFab* a = &sol;
-        MultiFab* b = &L.buf;
-        if (sol_is_zero && (nsweeps & 1)) std::swap(a, b);
         const double om = m_dd_sweeps > 0 ? dd_omega() : m_o.omega;
-        for (int i = 0; i < nsweeps; ++i) {
-            const bool last = acc && i == nsweeps - 1;
-            abec_gsrb_rb(L.g, c, *a, last ? *acc : *b, rhs, om, sol_is_zero && i == 0, m_bcn.data(), (int)m_bcn.size(), &L.cftab, last);
-            if (last) { m_acc_done = true; return; }
-            std::swap(a, b);
-        }
-        if (a != &sol) MultiFab::Copy(sol, *a, 0, 0, m_ncomp, 0);
+        pingpong(sol, L.buf, nsweeps, sol_is_zero, acc, [&](MultiFab& in, MultiFab& out, bool zero, bool last) {
+            abec_gsrb_rb(L.g, c, in, out, rhs, om, zero, bcs, nbc, cfs ? &L.cftab : nullptr, last);
+        });
         return;
     }
-    if (!m_cf) {
-        // one box spanning a periodic domain: red + black in one out-of-place launch per sweep (k_abec_gsrb_rb), ping-pong with the level's buffer
-        AbecCoef c = coef(l);
-        c.tensor = 0;
-        // (finest level only: on a coarser level of 128 cells in x a march of a few planes does not beat two colour passes)
-        if (l == 0 && abec_gsrb_rb_ok(m_lev[l].g, c, sol, (int)m_bcn.size(), m_bcn.data())) {
-            Level& L = m_lev[l];
-            if (!L.buf.defined()) L.buf.define(L.layout, cell_type(), m_ncomp, 1);
-            MultiFab* a = &sol;
-            MultiFab* b = &L.buf;
-            // from a zero start the first sweep reads no input: an odd number of sweeps starts "from" the buffer and ends in sol without a copy
-            if (sol_is_zero && (nsweeps & 1)) std::swap(a, b);
-            const double om = m_dd_sweeps > 0 ? dd_omega() : m_o.omega;
-            for (int i = 0; i < nsweeps; ++i) {
-                const bool last = acc && i == nsweeps - 1;
-                abec_gsrb_rb(L.g, c, *a, last ? *acc : *b, rhs, om, sol_is_zero && i == 0, m_bcn.data(), (int)m_bcn.size(), nullptr, last);
-                if (last) { m_acc_done = true; return; }
-                std::swap(a, b);
-            }
-            if (a != &sol) MultiFab::Copy(sol, *a, 0, 0, m_ncomp, 0);
-            return;
+    // several boxes covering the domain: the same sweep per box, one two-layer exchange of the correction in front of it (none in
+    // front of a sweep from zero), the ghost layer of the right-hand side once per V-cycle
+    if (!m_cf && nbr_sweep_ok(l, sol, rhs)) {
+        if (!L.buf.defined() || L.buf.ngrow != sol.ngrow) L.buf.define(L.layout, cell_type(), m_ncomp, sol.ngrow);
+        if (!(&rhs == &L.res && L.res_filled)) {
+            const int one[3] = {1, 1, 1};
+            const_cast<MultiFab&>(rhs).FillBoundary(L.g, 0, m_ncomp, one);
+            if (&rhs == &L.res) L.res_filled = true;
         }
-        // several boxes covering the domain: the same sweep per box, one two-layer exchange of the correction in front of it (none in
-        // front of a sweep from zero), the ghost layer of the right-hand side once per V-cycle
-        if (nbr_sweep_ok(l, sol, rhs)) {
-            Level& L = m_lev[l];
-            if (!L.buf.defined() || L.buf.ngrow != sol.ngrow) L.buf.define(L.layout, cell_type(), m_ncomp, sol.ngrow);
-            if (!(&rhs == &L.res && L.res_filled)) {
-                const int one[3] = {1, 1, 1};
-                const_cast<MultiFab&>(rhs).FillBoundary(L.g, 0, m_ncomp, one);
-                if (&rhs == &L.res) L.res_filled = true;
+        const double om = m_dd_sweeps > 0 ? dd_omega() : m_o.omega;
+        // Overlap (IAMRX_HALO_OVERLAP, 1: on where the level exchanges with other ranks; 2: always; 0: off): the exchange of the two ghost
+        // layers, k_abec_rb_ghost and the tiles next to box faces are issued on the context's side stream, the tiles that read no
+        // ghost cell on the main stream in front of them -- the messages travel while the interior of the box is swept
+        auto& ctx = Context::get();
+        const int ov_mode = (int)tune("HALO_OVERLAP", 1);
+        const CopyPlan& fplan = fill_boundary_plan(*L.layout, cell_type(), sol.ngrow, L.g);      // (built and uploaded in front of any fork)
+        const bool overlap = ov_mode != 0 && (ov_mode == 2 || !fplan.peers.empty()) && abec_gsrb_rb_nbr_splits(L.g, *L.layout);
+        pingpong(sol, L.buf, nsweeps, sol_is_zero, acc, [&](MultiFab& in, MultiFab& out, bool z, bool last) {
+            if (z || !overlap) {
+                if (!z) in.FillBoundary(L.g);
+                abec_gsrb_rb_nbr(L.g, c, in, out, rhs, om, z, bcs, nbc, 0, nullptr, last);
+            } else {
+                ctx.fork_side();
+                abec_gsrb_rb_nbr(L.g, c, in, out, rhs, om, false, bcs, nbc, 1, ctx.stream, last);
+                in.FillBoundary(L.g, 0, m_ncomp, nullptr, -1, ctx.side);
+                abec_gsrb_rb_nbr(L.g, c, in, out, rhs, om, false, bcs, nbc, 2, ctx.side, last);
+                ctx.join_side();
             }
-            MultiFab* a = &sol;
-            MultiFab* b = &L.buf;
-            if (sol_is_zero && (nsweeps & 1)) std::swap(a, b);
-            const double om = m_dd_sweeps > 0 ? dd_omega() : m_o.omega;
-            // Overlap (IAMRX_HALO_OVERLAP, 1: on where the level exchanges with other ranks; 2: always; 0: off): the exchange of the two ghost
-            // layers, k_abec_rb_ghost and the tiles next to box faces are issued on the context's side stream, the tiles that read no
-            // ghost cell on the main stream in front of them -- the messages travel while the interior of the box is swept
-            auto& ctx = Context::get();
-            const int ov_mode = (int)tune("HALO_OVERLAP", 1);
-            const CopyPlan& fplan = fill_boundary_plan(*L.layout, cell_type(), sol.ngrow, L.g);      // (built and uploaded in front of any fork)
-            const bool overlap = ov_mode != 0 && (ov_mode == 2 || !fplan.peers.empty()) && abec_gsrb_rb_nbr_splits(L.g, *L.layout);
-            for (int i = 0; i < nsweeps; ++i) {
-                const bool z = sol_is_zero && i == 0;
-                const bool last = acc && i == nsweeps - 1;
-                MultiFab& out = last ? *acc : *b;
-                if (z || !overlap) {
-                    if (!z) a->FillBoundary(L.g);
-                    abec_gsrb_rb_nbr(L.g, c, *a, out, rhs, om, z, m_bcn.data(), (int)m_bcn.size(), 0, nullptr, last);
-                } else {
-                    ctx.fork_side();
-                    abec_gsrb_rb_nbr(L.g, c, *a, out, rhs, om, false, m_bcn.data(), (int)m_bcn.size(), 1, ctx.stream, last);
-                    a->FillBoundary(L.g, 0, m_ncomp, nullptr, -1, ctx.side);
-                    abec_gsrb_rb_nbr(L.g, c, *a, out, rhs, om, false, m_bcn.data(), (int)m_bcn.size(), 2, ctx.side, last);
-                    ctx.join_side();
-                }
-                if (last) { m_acc_done = true; return; }
-                std::swap(a, b);
-            }
-            if (a != &sol) MultiFab::Copy(sol, *a, 0, 0, m_ncomp, 0);
-            return;
-        }
+        });
+        return;
     }
     if (!fused_smoother_ok(l)) {
         for (int i = 0; i < nsweeps; ++i) smooth(l, sol, rhs, skip_first_fill && i == 0, i > 0, sol_is_zero && i == 0);
         return;
     }
     IAMRX_ASSERT(!sol_is_zero);
-    Level& L = m_lev[l];
-    AbecCoef c = coef(l);
-    c.tensor = 0;   // the smoother acts on the ABec part; cross terms enter through the residual
     if (!L.buf.defined()) L.buf.define(L.layout, cell_type(), m_ncomp, 1);
     MultiFab* a = &sol;
     MultiFab* b = &L.buf;
     for (int i = 0; i < nsweeps; ++i) {
         if (!(skip_first_fill && i == 0)) applyBC(l, *a, false, nullptr);
-        abec_gsrb_fused(L.g, c, *a, *b, rhs, m_o.omega, m_bcn.data(), (int)m_bcn.size());
+        abec_gsrb_fused(L.g, c, *a, *b, rhs, m_o.omega, bcs, nbc);
         applyBC(l, *b, false, nullptr);
-        abec_gsrb(L.g, c, *b, rhs, 1, m_o.omega, m_bcn.data(), (int)m_bcn.size(), true);
+        abec_gsrb(L.g, c, *b, rhs, 1, m_o.omega, bcs, nbc, true);
         std::swap(a, b);
     }
     if (a != &sol) MultiFab::Copy(sol, *a, 0, 0, m_ncomp, 0);
@@ -498,81 +482,14 @@ void CellMG::subtract_mean(int l, MultiFab& mf)
     }
 }
 
+// krylov.h: the initial residual and the operator application of the level, handed to the loop both solvers share
 int CellMG::bicgstab(int l, MultiFab& sol, const MultiFab& rhs, double eps_rel, double eps_abs, int& niters)
 {
-    Level& L = m_lev[l];
-    const Geometry& g = L.g;
-    const int nc = m_ncomp;
-    AbecCoef c = coef(l);
-    MultiFab ph(L.layout, cell_type(), nc, 1), sh(L.layout, cell_type(), nc, 1);
-    MultiFab sorig(L.layout, cell_type(), nc, 0), p(L.layout, cell_type(), nc, 0), r(L.layout, cell_type(), nc, 0);
-    MultiFab s(L.layout, cell_type(), nc, 0), rh(L.layout, cell_type(), nc, 0), v(L.layout, cell_type(), nc, 0), t(L.layout, cell_type(), nc, 0);
-    ph.setVal(0.0); sh.setVal(0.0);
-    applyBC(l, sol, false, nullptr);
-    abec_residual(g, c, r, sol, &rhs);
-    MultiFab::Copy(sorig, sol, 0, 0, nc, 0);
-    MultiFab::Copy(rh, r, 0, 0, nc, 0);
-    sol.setVal(0.0);
-    double rnorm = r.norm0(0, nc, 0);
-    const double rnorm0 = rnorm;
-    int ret = 0, nit = 1;
-    double rho_1 = 0, alpha = 0, omega = 0;
-    if (rnorm0 == 0 || rnorm0 < eps_abs) { niters = 0; MultiFab::Copy(sol, sorig, 0, 0, nc, 0); return 0; }
-    // Krylov bound: an N-unknown system needs at most N iterations in exact arithmetic; more only chases round-off
-    // (observed: ~175 iterations per V-cycle on a 2^3 level whose rhs is at round-off level).  Cap at 2N.
-    const long nunk = (long)g.domain.npts() * nc;
-    const int maxiter = (int)std::min<long>(m_o.bottom_maxiter, std::max<long>(8, 2 * nunk));
-    if (tune("KRYLOV_DEVICE", 1) != 0 && (Context::get().comm->nranks == 1 || L.layout->replicated)) {
-        // krylov.h: the same loop with its scalars on the device (one status word per iteration comes back, one iteration late)
-        ret = bicgstab_device(*L.layout, cell_type(), nc, g, sol, r, rh, ph, sh, v, t, rnorm0, eps_rel, eps_abs, maxiter,
-                              [&](MultiFab& out, MultiFab& in) { applyBC(l, in, false, nullptr); abec_residual(g, c, out, in, nullptr); }, nit, rnorm);
-    } else
-    for (; nit <= maxiter; ++nit) {
-        double rho;
-        { const MultiFab* xs[1] = {&rh}; const MultiFab* ys[1] = {&r}; reduce_dots(1, xs, ys, 0, nc, g, &rho); }
-        if (rho == 0) { ret = 1; break; }
-        if (nit == 1) MultiFab::Copy(p, r, 0, 0, nc, 0);
-        else {
-            const double beta = (rho / rho_1) * (alpha / omega);
-            mf_lincomb(p, 1.0, p, -omega, v, 0, nc, 0);
-            mf_lincomb(p, 1.0, r, beta, p, 0, nc, 0);
-        }
-        MultiFab::Copy(ph, p, 0, 0, nc, 0);
-        applyBC(l, ph, false, nullptr);
-        abec_residual(g, c, v, ph, nullptr);
-        double rhTv;
-        { const MultiFab* xs[1] = {&rh}; const MultiFab* ys[1] = {&v}; reduce_dots(1, xs, ys, 0, nc, g, &rhTv); }
-        if (rhTv != 0) alpha = rho / rhTv; else { ret = 2; break; }
-        mf_lincomb(sol, 1.0, sol, alpha, ph, 0, nc, 0);
-        mf_lincomb(s, 1.0, r, -alpha, v, 0, nc, 0);
-        rnorm = s.norm0(0, nc, 0);
-        if (rnorm < eps_rel * rnorm0 || rnorm < eps_abs) break;
-        MultiFab::Copy(sh, s, 0, 0, nc, 0);
-        applyBC(l, sh, false, nullptr);
-        abec_residual(g, c, t, sh, nullptr);
-        double tv[2];
-        { const MultiFab* xs[2] = {&t, &t}; const MultiFab* ys[2] = {&t, &s}; reduce_dots(2, xs, ys, 0, nc, g, tv); }
-        if (tv[0] != 0) omega = tv[1] / tv[0]; else { ret = 3; break; }
-        mf_lincomb(sol, 1.0, sol, omega, sh, 0, nc, 0);
-        mf_lincomb(r, 1.0, s, -omega, t, 0, nc, 0);
-        rnorm = r.norm0(0, nc, 0);
-        if (rnorm < eps_rel * rnorm0 || rnorm < eps_abs) break;
-        if (omega == 0) { ret = 4; break; }
-        rho_1 = rho;
-    }
-    if (ret == 0 && rnorm > eps_rel * rnorm0 && rnorm > eps_abs) ret = 8;
-    if ((ret == 0 || ret == 8) && rnorm < rnorm0) mf_lincomb(sol, 1.0, sol, 1.0, sorig, 0, nc, 0);
-    else { sol.setVal(0.0); mf_lincomb(sol, 1.0, sol, 1.0, sorig, 0, nc, 0); }
-    niters = nit;
-    return ret;
-}
-
-// Krylov iterations of the device bottom solver, summed over the V-cycles of the running solve (one counter: solves do not overlap)
-static int* bottom_iters_dev()
-{
-    static int* d = nullptr;
-    if (!d) { IAMRX_HIP_CHECK(hipMalloc(&d, sizeof(int))); IAMRX_HIP_CHECK(hipMemset(d, 0, sizeof(int))); }
-    return d;
+    const Geometry& g = m_lev[l].g;
+    const AbecCoef c = coef(l);
+    return bottom_bicgstab(m_lev[l].layout, cell_type(), m_ncomp, g, sol, (long)g.domain.npts() * m_ncomp, m_o.bottom_maxiter, eps_rel, eps_abs,
+                           [&](MultiFab& r) { applyBC(l, sol, false, nullptr); abec_residual(g, c, r, sol, &rhs); },
+                           [&](MultiFab& out, MultiFab& in) { applyBC(l, in, false, nullptr); abec_residual(g, c, out, in, nullptr); }, niters);
 }
 
 
@@ -726,8 +643,7 @@ void CellMG::bottom_solve(MGStats& st)
     const int l = (int)m_lev.size() - 1;
     Level& L = m_lev[l];
     if (m_dd_sweeps > 0) {                 // diagonally dominant operator: no hierarchy, see prepare()
-        AbecCoef c = coef(l);
-        c.tensor = 0;
+        const AbecCoef c = smoother_coef(l);
         if ((!m_cf && (abec_gsrb_rb_ok(L.g, c, L.cor, (int)m_bcn.size(), m_bcn.data()) ||
                        nbr_sweep_ok(l, L.cor, L.res))) || cf_sweep_ok(l, L.cor)) {
             smooth_n(l, L.cor, L.res, m_dd_sweeps, true, true, m_acc);      // the first sweep takes the correction as zero: no fill, nothing read
@@ -744,9 +660,8 @@ void CellMG::bottom_solve(MGStats& st)
         return;
     }
     if (m_bottom_dev) {
-        const long nunk = L.layout->total_cells() * m_ncomp;
-        const int maxiter = (int)std::min<long>(m_o.bottom_maxiter, std::max<long>(8, 2 * nunk));
-        abec_bottom_solve(L.g, coef(l), L.cor, L.res, m_bcn[0], m_singular, m_o.bottom_reltol, maxiter, m_o.nub, m_o.nuf, m_o.omega, bottom_iters_dev(),
+        const int maxiter = krylov_maxiter(m_o.bottom_maxiter, L.layout->total_cells() * m_ncomp);
+        abec_bottom_solve(L.g, coef(l), L.cor, L.res, m_bcn[0], m_singular, m_o.bottom_reltol, maxiter, m_o.nub, m_o.nuf, m_o.omega, mg_bottom_iters_dev(),
                           m_cf ? &L.cftab : nullptr);
         return;
     }
@@ -788,44 +703,33 @@ void CellMG::vcycle(MGStats& st)
         // zero initial guess of the correction: where the first colour pass reads no ghost cell it also takes the place of the fill
         // (the sweep kernel takes "zero" per component: the three components of a tensor solve start from zero too)
         bool rb_zero = false;
-        if (l == 0 && !m_cf && m_ncomp > 1) { AbecCoef cz = coef(l); cz.tensor = 0; rb_zero = abec_gsrb_rb_ok(L.g, cz, L.cor, (int)m_bcn.size(), m_bcn.data()); }
+        if (l == 0 && !m_cf && m_ncomp > 1) rb_zero = abec_gsrb_rb_ok(L.g, smoother_coef(l), L.cor, (int)m_bcn.size(), m_bcn.data());
         const bool z = m_o.nu1 > 0 && (zero_first_pass_ok(l, L.cor) || nbr_sweep_ok(l, L.cor, L.res) || cf_sweep_ok(l, L.cor) || rb_zero);
         if (!z) L.cor.setVal(0.0);
         smooth_n(l, L.cor, L.res, m_o.nu1, true, z);
         const AbecCoef cl = coef(l);
         // (one box spanning a periodic domain: the fused residual + restriction reads the periodic images itself)
         if (m_cf || !abec_residual_reads_no_ghosts(L.g, cl, L.rescor, L.cor, L.res, true)) applyBC(l, L.cor, false, nullptr);
-        // the restriction writes: the coarse level's residual; its distributed form (agglomerated level: gathered afterwards); or, for a
-        // slab level, the one-plane virtual level, whose plane is then duplicated
-        Level& C = m_lev[l + 1];
-        MultiFab& held = C.agg ? C.tmp_d : C.res;
-        MultiFab& target = C.slab ? C.vres : held;
-        if (abec_resid_restrict_ok(cl, L.cor, L.res)) abec_resid_restrict(L.g, cl, target, L.cor, L.res);       // residual and restriction in one pass
-        else {
-            level_residual(L.g, cl, L.rescor, L.cor, &L.res);
-            cc_restrict(target, L.rescor);
-        }
-        if (C.slab) slab_duplicate(held, C.vres);
-        if (C.agg) gather_to_replicated(C.res, C.tmp_d);
+        Level& C = m_lev[l + 1];                 // (mlmg.h: through the one-plane level of a slab level / the distributed form of an agglomerated one)
+        mg_restrict_to(C, C.res, C.tmp_d, C.vres, [&](MultiFab& target) {
+            if (abec_resid_restrict_ok(cl, L.cor, L.res)) abec_resid_restrict(L.g, cl, target, L.cor, L.res);       // residual and restriction in one pass
+            else {
+                level_residual(L.g, cl, L.rescor, L.cor, &L.res);
+                cc_restrict(target, L.rescor);
+            }
+        });
     }
     if (tail) {
         Level& F = m_lev[nl - 2];
         Level& C = m_lev[nl - 1];
-        const long nunk = C.layout->total_cells() * m_ncomp;
-        const int maxiter = (int)std::min<long>(m_o.bottom_maxiter, std::max<long>(8, 2 * nunk));
-        AbecCoef cF = coef(nl - 2), cC = coef(nl - 1);
-        cF.tensor = 0; cC.tensor = 0;
-        abec_tail_solve(F.g, cF, F.cor, F.res, C.g, cC, m_bcn[0], m_singular, m_o.bottom_reltol, maxiter, m_o.nub, m_o.nuf, m_o.nu1, m_o.nu2, m_o.omega,
-                        bottom_iters_dev());
+        const int maxiter = krylov_maxiter(m_o.bottom_maxiter, C.layout->total_cells() * m_ncomp);
+        abec_tail_solve(F.g, smoother_coef(nl - 2), F.cor, F.res, C.g, smoother_coef(nl - 1), m_bcn[0], m_singular, m_o.bottom_reltol, maxiter, m_o.nub, m_o.nuf,
+                        m_o.nu1, m_o.nu2, m_o.omega, mg_bottom_iters_dev());
     } else
     bottom_solve(st);
     for (int l = nsm - 1; l >= 0; --l) {
         Level& L = m_lev[l];
-        if (m_lev[l + 1].agg) {
-            scatter_from_replicated(m_lev[l + 1].tmp_d, m_lev[l + 1].cor, 0);
-            cc_prolong_add(L.cor, m_lev[l + 1].tmp_d);
-        } else
-        cc_prolong_add(L.cor, m_lev[l + 1].cor);
+        cc_prolong_add(L.cor, mg_correction_of(m_lev[l + 1], m_lev[l + 1].cor, 0));
         smooth_n(l, L.cor, L.res, m_o.nu2, false, false, l == 0 ? m_acc : nullptr);
     }
 }
@@ -886,7 +790,7 @@ MGStats CellMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, double
     double vc_ms = 0.0;
     hipGraphExec_t vc_exec = nullptr;
     cycle_timer().used = 0;
-    if (m_bottom_dev) IAMRX_HIP_CHECK(hipMemsetAsync(bottom_iters_dev(), 0, sizeof(int), ctx.stream));
+    if (m_bottom_dev) IAMRX_HIP_CHECK(hipMemsetAsync(mg_bottom_iters_dev(), 0, sizeof(int), ctx.stream));
     if (m_o.fixed_iters <= 0 && st.resnorm0 <= res_target) st.converged = 1;
     else {
         const int maxit = m_o.fixed_iters > 0 ? m_o.fixed_iters : m_o.max_iters;
@@ -948,7 +852,7 @@ MGStats CellMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, double
     applyBC(0, phi, true, bcvp);
     if (m_bottom_dev && st.iters > 0) {
         int h = 0;
-        IAMRX_HIP_CHECK(hipMemcpyAsync(&h, bottom_iters_dev(), sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+        IAMRX_HIP_CHECK(hipMemcpyAsync(&h, mg_bottom_iters_dev(), sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
         ctx.sync();
         st.bottom_iters_total = h;
     }

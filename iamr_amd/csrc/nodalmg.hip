@@ -14,20 +14,10 @@ namespace iamrx {
 void nodal_restrict(MultiFab& crse, const MultiFab& fine);
 void nodal_interp_add(MultiFab& fine, const MultiFab& crse, const MultiFab& sig_fine);
 
-static bool nodal_fused()
-{
-    static int v = -1;
-    // plane-fused sweep (2 launches + 2 fills instead of 8 + 8): measured per sweep on MI355X 0.69 vs 0.79 ms at 256^3,
-    // 0.11 vs 0.20 ms at 128^3, 0.03 vs 0.09 ms at <= 64^3.  IAMRX_NODAL_FUSED=0 selects the 8 colour passes.
-    v = tune("NODAL_FUSED", 1) != 0 ? 1 : 0;
-    return v == 1;
-}
-static bool nodal_small()
-{
-    static int v = -1;
-    v = tune("NODAL_SMALL", 1) != 0 ? 1 : 0;
-    return v == 1;
-}
+// plane-fused sweep (2 launches + 2 fills instead of 8 + 8): measured per sweep on MI355X 0.69 vs 0.79 ms at 256^3,
+// 0.11 vs 0.20 ms at 128^3, 0.03 vs 0.09 ms at <= 64^3.  IAMRX_NODAL_FUSED=0 selects the 8 colour passes.
+static bool nodal_fused() { return tune("NODAL_FUSED", 1) != 0; }
+static bool nodal_small() { return tune("NODAL_SMALL", 1) != 0; }
 bool nodal_smooth_small(const Geometry& g, MultiFab& x, const MultiFab& rhs, const MultiFab& sig, int nsweeps);
 bool nodal_bottom_device_ok(const Geometry& g, const Layout& l);
 void nodal_bottom_solve(const Geometry& g, MultiFab& cor, const MultiFab& res, const MultiFab& sig, bool singular, double eps_rel, int maxiter,
@@ -35,11 +25,12 @@ void nodal_bottom_solve(const Geometry& g, MultiFab& cor, const MultiFab& res, c
 bool nodal_bottom_device_ok_general(const Geometry& g, const Layout& l);
 void nodal_bottom_solve_general(const Geometry& g, MultiFab& cor, const MultiFab& res, const MultiFab& sig, const MultiFab* dmask, bool singular,
                                 double eps_rel, int maxiter, int nsweeps, int nub, int nuf, int* d_iters);
-static int* nodal_bottom_iters_dev()
+// unique nodes of a level: the unknowns behind the Krylov iteration cap (krylov_maxiter)
+static long nodal_unknowns(const Geometry& g)
 {
-    static int* d = nullptr;
-    if (!d) { IAMRX_HIP_CHECK(hipMalloc(&d, sizeof(int))); IAMRX_HIP_CHECK(hipMemset(d, 0, sizeof(int))); }
-    return d;
+    long n = 1;
+    for (int d = 0; d < 3; ++d) n *= g.domain.len(d) + (g.periodic[d] ? 0 : 1);
+    return n;
 }
 
 NodalMG::NodalMG(const Geometry& g, LayoutP layout, const DomainBC& bc_in, const MGOpts& o) : m_g(g), m_bc(bc_in), m_o(o)
@@ -64,30 +55,8 @@ NodalMG::NodalMG(const Geometry& g, LayoutP layout, const DomainBC& bc_in, const
         // a fully periodic single box of at most 8^3 cells is solved by the single-workgroup device bottom solver (k_nodal_bottom)
         if (m_o.device_bottom && m_o.nodal_smoother == 0 && !m_o.bottom_smoother_only &&
             (nodal_bottom_device_ok(f.g, *f.layout) || nodal_bottom_device_ok_general(f.g, *f.layout))) break;
-        bool dom_ok = true;
-        for (int d = 0; d < 3; ++d) if (f.g.domain.len(d) % 2 != 0 || f.g.domain.len(d) / 2 < m_o.min_width) dom_ok = false;
-        const bool iso = dom_ok && f.layout->coarsenable(2, m_o.min_width);
-        const bool slab = !iso && mg_slab_level(f.g, *f.layout, m_o.min_width, m_o.slab != 0);     // (mlmg.hip: y kept at two cells, transfers through the one-plane level)
-        if (!iso && !slab) break;
         Level c;
-        c.g = f.g;
-        if (slab) {
-            const Geometry sg = mg_slab_geom(f.g);
-            c.g.domain = sg.domain;
-            for (int d = 0; d < 3; ++d) c.g.dx[d] = sg.dx[d];
-            c.slab = true;
-            c.virt = f.layout->coarsened(2);
-            c.layout = f.layout->slab_coarsened();
-        } else {
-        c.g.domain = coarsen(f.g.domain, 2);
-        for (int d = 0; d < 3; ++d) c.g.dx[d] = f.g.dx[d] * 2.0;
-        c.layout = f.layout->coarsened(2);
-        }
-        if (mg_agglomerate_level(*c.layout)) {
-            c.agg = true;
-            c.dist = c.layout;
-            c.layout = c.dist->make_replicated();
-        }
+        if (!mg_coarsen_level(f, m_o, c)) break;     // (mlmg.hip: isotropic, slab or agglomerated level)
         m_lev.push_back(std::move(c));
     }
     for (auto& L : m_lev) {
@@ -144,11 +113,9 @@ void NodalMG::setSigma(const MultiFab& sig, int comp)
         {
             Level& C = m_lev[l];
             MultiFab sd, sv;
-            MultiFab* held = &C.sig;
-            if (C.agg) { sd.define(C.dist, cell_type(), 1, 0); held = &sd; }
-            if (C.slab) { sv.define(C.virt, cell_type(), 1, 0); cc_restrict(sv, m_lev[l - 1].sig); slab_duplicate(*held, sv); }
-            else cc_restrict(*held, m_lev[l - 1].sig);
-            if (C.agg) gather_to_replicated(C.sig, sd);
+            if (C.agg) sd.define(C.dist, cell_type(), 1, 0);
+            if (C.slab) sv.define(C.virt, cell_type(), 1, 0);
+            mg_restrict_to(C, C.sig, sd, sv, [&](MultiFab& target) { cc_restrict(target, m_lev[l - 1].sig); });
         }
         m_lev[l].sig.FillBoundary(m_lev[l].g);
         cc_mirror_bc(m_lev[l].g, m_lev[l].sig);
@@ -287,75 +254,17 @@ void NodalMG::subtract_mean(int l, MultiFab& mf)
     mf_add_scalar(mf, -s / cnt, 0, 1, 0);
 }
 
+// krylov.h: the initial residual and the operator application of the level, handed to the loop both solvers share
 int NodalMG::bicgstab(int l, MultiFab& sol, const MultiFab& rhs, double eps_rel, double eps_abs, int& niters)
 {
     Level& L = m_lev[l];
-    const Geometry& g = L.g;
-    auto mk = [&](int ng) { return MultiFab(L.layout, node_type(), 1, ng); };
-    MultiFab ph = mk(1), sh = mk(1), sorig = mk(0), p = mk(0), r = mk(0), s = mk(0), rh = mk(0), v = mk(0), t = mk(0);
-    ph.setVal(0.0); sh.setVal(0.0);
-    residual(l, r, sol, rhs);
-    MultiFab::Copy(sorig, sol, 0, 0, 1, 0);
-    MultiFab::Copy(rh, r, 0, 0, 1, 0);
-    sol.setVal(0.0);
-    double rnorm = r.norm0(0, 1, 0);
-    const double rnorm0 = rnorm;
-    int ret = 0, nit = 1;
-    double rho_1 = 0, alpha = 0, omega = 0;
-    if (rnorm0 == 0 || rnorm0 < eps_abs) { niters = 0; MultiFab::Copy(sol, sorig, 0, 0, 1, 0); return 0; }
-    // Krylov bound (see CellMG::bicgstab): cap at twice the number of unique nodes of the bottom level
-    long nunk = 1;
-    for (int d = 0; d < 3; ++d) nunk *= g.domain.len(d) + (g.periodic[d] ? 0 : 1);
-    const int maxiter = (int)std::min<long>(m_o.bottom_maxiter, std::max<long>(8, 2 * nunk));
-    if (tune("KRYLOV_DEVICE", 1) != 0 && (Context::get().comm->nranks == 1 || L.layout->replicated)) {
-        // krylov.h: the same loop with its scalars on the device (one status word per iteration comes back, one iteration late)
-        ret = bicgstab_device(*L.layout, node_type(), 1, g, sol, r, rh, ph, sh, v, t, rnorm0, eps_rel, eps_abs, maxiter,
-                              [&](MultiFab& out, MultiFab& in) {
-                                  fillbc(l, in);
-                                  nodal_residual(g, out, in, L.sig, nullptr);
-                                  if (L.dmask()) nodal_zero_masked(out, L.dm);
-                              }, nit, rnorm);
-    } else
-    for (; nit <= maxiter; ++nit) {
-        double rho;
-        { const MultiFab* xs[1] = {&rh}; const MultiFab* ys[1] = {&r}; reduce_dots(1, xs, ys, 0, 1, g, &rho); }
-        if (rho == 0) { ret = 1; break; }
-        if (nit == 1) MultiFab::Copy(p, r, 0, 0, 1, 0);
-        else {
-            const double beta = (rho / rho_1) * (alpha / omega);
-            mf_lincomb(p, 1.0, p, -omega, v, 0, 1, 0);
-            mf_lincomb(p, 1.0, r, beta, p, 0, 1, 0);
-        }
-        MultiFab::Copy(ph, p, 0, 0, 1, 0);
-        fillbc(l, ph);
-        nodal_residual(g, v, ph, L.sig, nullptr);
-        if (L.dmask()) nodal_zero_masked(v, L.dm);
-        double rhTv;
-        { const MultiFab* xs[1] = {&rh}; const MultiFab* ys[1] = {&v}; reduce_dots(1, xs, ys, 0, 1, g, &rhTv); }
-        if (rhTv != 0) alpha = rho / rhTv; else { ret = 2; break; }
-        mf_lincomb(sol, 1.0, sol, alpha, ph, 0, 1, 0);
-        mf_lincomb(s, 1.0, r, -alpha, v, 0, 1, 0);
-        rnorm = s.norm0(0, 1, 0);
-        if (rnorm < eps_rel * rnorm0 || rnorm < eps_abs) break;
-        MultiFab::Copy(sh, s, 0, 0, 1, 0);
-        fillbc(l, sh);
-        nodal_residual(g, t, sh, L.sig, nullptr);
-        if (L.dmask()) nodal_zero_masked(t, L.dm);
-        double tv[2];
-        { const MultiFab* xs[2] = {&t, &t}; const MultiFab* ys[2] = {&t, &s}; reduce_dots(2, xs, ys, 0, 1, g, tv); }
-        if (tv[0] != 0) omega = tv[1] / tv[0]; else { ret = 3; break; }
-        mf_lincomb(sol, 1.0, sol, omega, sh, 0, 1, 0);
-        mf_lincomb(r, 1.0, s, -omega, t, 0, 1, 0);
-        rnorm = r.norm0(0, 1, 0);
-        if (rnorm < eps_rel * rnorm0 || rnorm < eps_abs) break;
-        if (omega == 0) { ret = 4; break; }
-        rho_1 = rho;
-    }
-    if (ret == 0 && rnorm > eps_rel * rnorm0 && rnorm > eps_abs) ret = 8;
-    if ((ret == 0 || ret == 8) && rnorm < rnorm0) mf_lincomb(sol, 1.0, sol, 1.0, sorig, 0, 1, 0);
-    else { sol.setVal(0.0); mf_lincomb(sol, 1.0, sol, 1.0, sorig, 0, 1, 0); }
-    niters = nit;
-    return ret;
+    return bottom_bicgstab(L.layout, node_type(), 1, L.g, sol, nodal_unknowns(L.g), m_o.bottom_maxiter, eps_rel, eps_abs,
+                           [&](MultiFab& r) { residual(l, r, sol, rhs); },
+                           [&](MultiFab& out, MultiFab& in) {
+                               fillbc(l, in);
+                               nodal_residual(L.g, out, in, L.sig, nullptr);
+                               if (L.dmask()) nodal_zero_masked(out, L.dm);
+                           }, niters);
 }
 
 bool NodalMG::bottom_on_device()
@@ -374,13 +283,8 @@ void NodalMG::vcycle(MGStats& st)
         for (int i = 0; i < m_o.nodal_nu1; ++i) smooth(l, L.cor, L.res, i == 0);
         residual(l, L.rescor, L.cor, L.res, nullptr, m_o.nodal_nu1 > 0);          // (smooth() has just filled the ghost nodes)
         fillbc(l, L.rescor);
-        {
-            Level& C = m_lev[l + 1];
-            MultiFab& held = C.agg ? C.tmp_d : C.res;
-            nodal_restrict(C.slab ? C.vres : held, L.rescor);
-            if (C.slab) slab_duplicate(held, C.vres);
-            if (C.agg) gather_to_replicated(C.res, C.tmp_d);
-        }
+        Level& C = m_lev[l + 1];
+        mg_restrict_to(C, C.res, C.tmp_d, C.vres, [&](MultiFab& target) { nodal_restrict(target, L.rescor); });
         m_lev[l + 1].res_filled = false;
         if (m_lev[l + 1].dmask()) nodal_zero_masked(m_lev[l + 1].res, m_lev[l + 1].dm);   // mlndlap_restriction: 0 on Dirichlet nodes
     }
@@ -391,15 +295,13 @@ void NodalMG::vcycle(MGStats& st)
         if (m_o.bottom_smoother_only) {
             for (int i = 0; i < m_o.nuf; ++i) smooth(l, B.cor, B.res);
         } else if (bottom_on_device()) {
-            long nunk = 1;
-            for (int d = 0; d < 3; ++d) nunk *= B.g.domain.len(d) + (B.g.periodic[d] ? 0 : 1);
-            const int maxiter = (int)std::min<long>(m_o.bottom_maxiter, std::max<long>(8, 2 * nunk));
+            const int maxiter = krylov_maxiter(m_o.bottom_maxiter, nodal_unknowns(B.g));
             if (!B.dmask() && nodal_bottom_device_ok(B.g, *B.layout))           // fully periodic: the wrap-only kernel
                 nodal_bottom_solve(B.g, B.cor, B.res, B.sig, m_singular, m_o.bottom_reltol, maxiter, m_o.nodal_sweeps, m_o.nub, m_o.nuf,
-                                   nodal_bottom_iters_dev());
+                                   mg_bottom_iters_dev());
             else                                                                // walls / Dirichlet mask / refined patch
                 nodal_bottom_solve_general(B.g, B.cor, B.res, B.sig, B.dmask(), m_singular, m_o.bottom_reltol, maxiter, m_o.nodal_sweeps, m_o.nub,
-                                           m_o.nuf, nodal_bottom_iters_dev());
+                                           m_o.nuf, mg_bottom_iters_dev());
         } else {
             MultiFab rb(B.layout, node_type(), 1, 0);
             MultiFab::Copy(rb, B.res, 0, 0, 1, 0);
@@ -419,11 +321,7 @@ void NodalMG::vcycle(MGStats& st)
         Level& L = m_lev[l];
         // (a level that was smoothed on the way up comes with its ghost nodes filled; the bottom level comes from its solver)
         if (l + 1 == nl - 1 || m_o.nodal_nu2 <= 0) fillbc(l + 1, m_lev[l + 1].cor);
-        if (m_lev[l + 1].agg) {
-            scatter_from_replicated(m_lev[l + 1].tmp_d, m_lev[l + 1].cor, 1);
-            nodal_interp_add(L.cor, m_lev[l + 1].tmp_d, L.sig);
-        } else
-        nodal_interp_add(L.cor, m_lev[l + 1].cor, L.sig);
+        nodal_interp_add(L.cor, mg_correction_of(m_lev[l + 1], m_lev[l + 1].cor, 1), L.sig);
         if (L.dmask()) nodal_zero_masked(L.cor, L.dm);                  // mlndlap_interpadd: Dirichlet nodes take no correction
         // the finest level's correction is added to the solution node by node: nobody reads its ghost nodes
         for (int i = 0; i < m_o.nodal_nu2; ++i) smooth(l, L.cor, L.res, false, l == 0 && i == m_o.nodal_nu2 - 1);
@@ -482,7 +380,7 @@ MGStats NodalMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, doubl
     double vc_ms = 0.0;
     cycle_timer().used = 0;
     const bool bdev = bottom_on_device();
-    if (bdev) IAMRX_HIP_CHECK(hipMemsetAsync(nodal_bottom_iters_dev(), 0, sizeof(int), ctx.stream));
+    if (bdev) IAMRX_HIP_CHECK(hipMemsetAsync(mg_bottom_iters_dev(), 0, sizeof(int), ctx.stream));
     if (m_o.fixed_iters <= 0 && st.resnorm0 <= res_target) st.converged = 1;
     else {
         const int maxit = m_o.fixed_iters > 0 ? m_o.fixed_iters : m_o.max_iters;
@@ -517,7 +415,7 @@ MGStats NodalMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, doubl
     if (st.iters > 0) st.vcycle_ms = vc_ms / st.iters;
     if (bdev && st.iters > 0) {
         int h = 0;
-        IAMRX_HIP_CHECK(hipMemcpyAsync(&h, nodal_bottom_iters_dev(), sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+        IAMRX_HIP_CHECK(hipMemcpyAsync(&h, mg_bottom_iters_dev(), sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
         ctx.sync();
         st.bottom_iters_total = h;
     }

@@ -1,5 +1,5 @@
 """BiCGStab of the multigrid bottom solvers with its scalars on the device (iamr_amd/csrc/krylov.h, round 6) against the host-driven loop
-it replaces (CellMG::bicgstab / NodalMG::bicgstab: amrex::MLCGSolver::solve_bicgstab with five read-backs per iteration).  Same operations
+it replaces (bicgstab_host in the same file, the one loop of both solvers: amrex::MLCGSolver::solve_bicgstab with five read-backs per iteration).  Same operations
 on the same doubles in the same order: iteration counts equal, solutions equal to round-off of one multiply-add (the compiler is free in how
 it orders a kernel's independent loads, not in its arithmetic: the build uses -ffp-contract=off)."""
 import numpy as np
