@@ -51,7 +51,9 @@ class Amr:
                 check(lib().iamrx_amr_level_boxes(self.h, l, C.byref(nb), arr))
                 hl = C.c_void_p()
                 check(lib().iamrx_amr_level_layout(self.h, l, C.byref(hl)))
-                lays.append(Layout.from_handle(hl, [(tuple(arr[6 * q:6 * q + 3]), tuple(arr[6 * q + 3:6 * q + 6])) for q in range(nb.value)]))
+                own = (C.c_int * max(1, nb.value))()
+                check(lib().iamrx_layout_owners(hl, own))            # who the regrid's knapsack gave every box to
+                lays.append(Layout.from_handle(hl, [(tuple(arr[6 * q:6 * q + 3]), tuple(arr[6 * q + 3:6 * q + 6])) for q in range(nb.value)], list(own[:nb.value])))
             self.layouts = lays
         self.levels = []
         for l in range(n.value):

@@ -10,23 +10,26 @@ writer produces them, iamr_amd/plotfile.py, which is pinned byte for byte on the
                               dt_level, dt_min, n_cycle, level_steps, level_count; then per level (AmrLevel::checkPoint): level, geometry,
                               the BoxArray, the number of state types and per state type (StateData::checkPoint) domain, BoxArray, old / new
                               time interval, the number of MultiFabs written (2: new + old, "dump_old") and their relative paths
-  Level_<l>/SD_<t>_New_MF_H, _D_00000 / SD_<t>_Old_MF_*     State_Type (t = 0: u v w rho tracer, 1 ghost cell), Press_Type (1, nodal),
-                              Gradp_Type (2, 3 comps)
+  Level_<l>/SD_<t>_New_MF_H, _D_<rank:05d> / SD_<t>_Old_MF_*     State_Type (t = 0: u v w rho tracer, 1 ghost cell), Press_Type (1,
+                              nodal), Gradp_Type (2, 3 comps); one _D_ file per rank that owns boxes of the level
   iamrx_restart.json          what this library keeps beyond upstream's StateData and needs for a BIT-IDENTICAL continuation: the
                               initial-guess history of the MAC solve (two potentials per level + the dt they belong to), the step counter of
-                              every level, the single-level driver's dt estimate, the box owners
+                              every level, the single-level driver's dt estimate, the box owners and (if more than one) the number of ranks that wrote
   Level_<l>/MacPhiHist_<q>_*  the two MAC potentials
 
 Old data are always written: the pressure of two steps ago seeds the initial guess of the next level projection (navierstokes.hip), so a
 restart from new data alone would converge to the same answer along a different path -- equal to solver tolerance, not to the bit.
-Host-side I/O (control plane): plain Python + numpy, one rank (the driver gathers nothing across ranks: multi-rank checkpoints are not
-implemented and refused)."""
+Host-side I/O (control plane): plain Python + numpy.  A run on several ranks writes the way VisMF does: every rank its own <name>_D_<rank>
+with the fabs it owns, rank 0 the <name>_H files (file and offset per grid), Header and iamrx_restart.json.  Order: rank 0 makes the
+directories, barrier, data files, one sum per MultiFab that carries offsets / minima / maxima to everyone, headers -- so a complete Header
+implies complete data.  Barrier and sum are lib.comm_allreduce (iamrx_comm_allreduce), whichever transport is installed.  restart() reads
+a checkpoint on any number of ranks (see there)."""
 import ctypes as C
 import json
 import os
 import numpy as np
 
-from .plotfile import REAL_DESC, _fmt17
+from .plotfile import data_file, write_fabs, write_vismf_header, merge_meta, gather_meta, comm_ops
 
 STATE_TYPES = [  # (name, selector new, selector old, index type, ncomp)
     ("State_Type", 0, 1, (0, 0, 0), 5),      # 5 + do_trac2 + do_temp components (the level's nstate)
@@ -39,43 +42,59 @@ def _box(lo, hi, typ=(0, 0, 0)):
     return "((" + ",".join(str(v) for v in lo) + ") (" + ",".join(str(v) for v in hi) + ") (" + ",".join(str(v) for v in typ) + "))"
 
 
+def _local_indices(lay):
+    """global indices of the boxes this rank owns, in the order of its local fabs (increasing)"""
+    return [lay.local_box(li)[2] for li in range(lay.nlocal())]
+
+
+def _write_vismf_data(dirname, name, boxes, typ, arrays, ngrow, rank=0, owned=None):
+    """phase A of VisMF::Write of one MultiFab, every rank: <name>_D_<rank:05d> with the fabs this rank owns; boxes: ALL valid cell boxes of
+    the MultiFab, owned: the global indices (increasing) of those `arrays` belong to (None: every box); arrays: per owned box
+    (nx + 2 ng, ..., ncomp) incl. ghost cells.  A rank that owns nothing writes no file.  Returns [(global index, offset, minima, maxima)]."""
+    owned = list(range(len(boxes))) if owned is None else list(owned)
+    assert len(owned) == len(arrays) and all(p < q for p, q in zip(owned, owned[1:])), owned
+    fabs = []
+    for gi, a in zip(owned, arrays):
+        lo, hi = boxes[gi]
+        glo = [lo[d] - ngrow for d in range(3)]
+        ghi = [hi[d] + typ[d] + ngrow for d in range(3)]
+        assert np.shape(a)[:3] == tuple(ghi[d] - glo[d] + 1 for d in range(3)), (np.shape(a), glo, ghi)
+        fabs.append((_box(glo, ghi, typ), a))
+    if not fabs:
+        return []
+    res = write_fabs(os.path.join(dirname, os.path.basename(name) + data_file(rank)), fabs)
+    return [(gi, off, mn, mx) for gi, (off, mn, mx) in zip(owned, res)]
+
+
+def _write_vismf_header(dirname, name, boxes, typ, nc, ngrow, metas):
+    """phase B, one rank: <name>_H from metas = {rank: what its _write_vismf_data returned}: the BoxArray converted to the index type (as
+    BoxArray::writeOn does), file and offset per grid, minima and maxima in global box order"""
+    rows = merge_meta(len(boxes), metas)
+    base = os.path.basename(name)
+    write_vismf_header(os.path.join(dirname, base + "_H"), nc, ngrow, [_box(lo, [hi[d] + typ[d] for d in range(3)], typ) for lo, hi in boxes],
+                       [(base + data_file(r), off) for r, off, _, _ in rows], [r[2] for r in rows], [r[3] for r in rows])
+
+
 def _write_vismf(dirname, name, boxes, typ, arrays, ngrow):
-    """VisMF::Write of one MultiFab: <name>_H + <name>_D_00000; arrays: per box (nx + 2 ng, ..., ncomp) incl. ghost cells; boxes: the
-    valid cell boxes (written converted to the index type, as BoxArray::writeOn does)"""
+    """VisMF::Write of one MultiFab by ONE writer holding every box: <name>_H + <name>_D_00000"""
     nc = arrays[0].shape[-1] if arrays else 0
-    fname = os.path.basename(name) + "_D_00000"
-    offsets, mins, maxs = [], [], []
-    with open(os.path.join(dirname, fname), "wb") as f:
-        for (lo, hi), a in zip(boxes, arrays):
-            a = np.asarray(a, dtype="<f8")
-            glo = [lo[d] - ngrow for d in range(3)]
-            ghi = [hi[d] + typ[d] + ngrow for d in range(3)]
-            assert a.shape[:3] == tuple(ghi[d] - glo[d] + 1 for d in range(3)), (a.shape, glo, ghi)
-            offsets.append(f.tell())
-            f.write(f"FAB {REAL_DESC}{_box(glo, ghi, typ)} {nc}\n".encode())
-            f.write(np.asfortranarray(a).tobytes(order="F"))
-            mins.append([a[..., n].min() for n in range(nc)])
-            maxs.append([a[..., n].max() for n in range(nc)])
-    with open(os.path.join(dirname, os.path.basename(name) + "_H"), "w") as f:
-        f.write(f"1\n0\n{nc}\n{ngrow}\n({len(boxes)} 0\n")
-        for lo, hi in boxes:
-            f.write(_box(lo, [hi[d] + typ[d] for d in range(3)], typ) + "\n")
-        f.write(f")\n{len(boxes)}\n")
-        for o in offsets:
-            f.write(f"FabOnDisk: {fname} {o}\n")
-        for vals in (mins, maxs):
-            f.write(f"\n{len(boxes)},{nc}\n")
-            for row in vals:
-                f.write("".join(_fmt17(v) + "," for v in row) + "\n")
+    _write_vismf_header(dirname, name, boxes, typ, nc, ngrow, {0: _write_vismf_data(dirname, name, boxes, typ, arrays, ngrow)})
 
 
-def _read_vismf(dirname, name):
+def _vismf_ncomp(dirname, name):
+    with open(os.path.join(dirname, name + "_H")) as f:
+        return int(f.read().split("\n")[2])
+
+
+def _read_vismf(dirname, name, grids=None):
+    """the fabs (ghost cells included) of one MultiFab, following `FabOnDisk: <file> <offset>` per grid; grids: the global indices to load
+    (a rank reads only what it owns), None: all"""
     import re
     with open(os.path.join(dirname, name + "_H")) as f:
         txt = f.read()
     files = [(m.group(1), int(m.group(2))) for m in re.finditer(r"FabOnDisk: (\S+) (\d+)", txt)]
     out = []
-    for fn, off in files:
+    for fn, off in (files if grids is None else [files[q] for q in grids]):
         with open(os.path.join(dirname, fn), "rb") as f:
             f.seek(off)
             head = f.readline().decode()
@@ -102,13 +121,19 @@ def _level_views(run):
 
 
 def write(run, root, step, max_level=None):
-    """checkpoint of `run` (iamr_amd.amr.Amr or iamr_amd.ns.NavierStokes) into <root><step:05d>; returns the directory"""
-    from .lib import lib, check
+    """checkpoint of `run` (iamr_amd.amr.Amr or iamr_amd.ns.NavierStokes) into <root><step:05d>; returns the directory.  Collective: every
+    rank of the library's communicator calls it and writes the fabs it owns; rank 0 writes the headers once the data are complete."""
+    from .lib import lib, check, comm_rank
     L = lib()
     levels, lays, geoms, amr = _level_views(run)
     nlev = len(levels)
+    rank, world = comm_rank()
+    allreduce, barrier = comm_ops(world)
     path = f"{root}{step:05d}"
-    os.makedirs(path, exist_ok=True)
+    if rank == 0:
+        for l in range(nlev):
+            os.makedirs(os.path.join(path, f"Level_{l}"), exist_ok=True)
+    barrier()                                   # the directories exist before anyone writes into them
     max_level = nlev - 1 if max_level is None else max_level
     dt_level, dt_min, n_cycle = (C.c_double * nlev)(), (C.c_double * nlev)(), (C.c_int * nlev)()
     counters, stop = (C.c_int * 2)(), C.c_double(-1.0)
@@ -143,12 +168,13 @@ def write(run, root, step, max_level=None):
     H.append(" ".join(str(int(v)) for v in level_count))                         # level_count
     extra = {"stop_time": stop.value, "level_steps0": int(counters[0]), "level_count": int(counters[1]),
              "level_counts": [int(v) for v in level_count], "levels": []}
+    if world > 1:
+        extra["world"] = world                  # the writing world size (absent: one rank, as every earlier checkpoint)
+    mfs = []                                    # (directory, name, index type, ncomp, ngrow, boxes, owners, this rank's metadata)
     for l, (lev, lay, g) in enumerate(zip(levels, lays, geoms)):
         ld = os.path.join(path, f"Level_{l}")
-        os.makedirs(ld, exist_ok=True)
         boxes = [(list(lo), list(hi)) for lo, hi in lay.boxes]
-        if any(o != 0 for o in lay.owners):
-            raise NotImplementedError("checkpoint: multi-rank checkpoints are not implemented")
+        owned = _local_indices(lay)
         n = [geoms[0].n[d] * 2 ** l for d in range(3)]
         H += [str(l), _geom_line(g, n), f"({len(boxes)} 0"] + [_box(lo, hi) for lo, hi in boxes] + [")", str(len(STATE_TYPES))]
         st = states[l]
@@ -163,15 +189,24 @@ def write(run, root, step, max_level=None):
             for tag, sel in (("New", snew), ("Old", sold)):
                 mf = lev.data(sel)
                 arrays = [mf.to_numpy(li)[0] for li in range(mf.nlocal())]
-                _write_vismf(ld, f"SD_{t}_{tag}_MF", boxes, typ, arrays, 1)
+                mfs.append((ld, f"SD_{t}_{tag}_MF", typ, mf.ncomp, 1, boxes, lay.owners, _write_vismf_data(ld, f"SD_{t}_{tag}_MF", boxes, typ, arrays, 1, rank, owned)))
         for q in range(2):
             mf = lev.data(10 + q)
-            _write_vismf(ld, f"MacPhiHist_{q}", boxes, (0, 0, 0), [mf.to_numpy(li)[0] for li in range(mf.nlocal())], 0)
-        extra["levels"].append({"state": st, "boxes": boxes, "owners": list(lay.owners)})
-    with open(os.path.join(path, "Header"), "w") as f:
-        f.write("\n".join(H) + "\n")
-    with open(os.path.join(path, "iamrx_restart.json"), "w") as f:
-        json.dump(extra, f)
+            arrays = [mf.to_numpy(li)[0] for li in range(mf.nlocal())]
+            mfs.append((ld, f"MacPhiHist_{q}", (0, 0, 0), 1, 0, boxes, lay.owners, _write_vismf_data(ld, f"MacPhiHist_{q}", boxes, (0, 0, 0), arrays, 0, rank, owned)))
+        extra["levels"].append({"state": st, "boxes": boxes, "owners": [int(o) for o in lay.owners]})
+    # one sum per MultiFab carries offsets, minima and maxima to everyone and orders all data files before the headers: a complete Header
+    # implies complete data
+    for ld, name, typ, nc, ngrow, boxes, owners, meta in mfs:
+        metas = gather_meta(len(boxes), nc, meta, owners, allreduce)
+        if rank == 0:
+            _write_vismf_header(ld, name, boxes, typ, nc, ngrow, metas)
+    if rank == 0:
+        with open(os.path.join(path, "iamrx_restart.json"), "w") as f:
+            json.dump(extra, f)
+        with open(os.path.join(path, "Header"), "w") as f:
+            f.write("\n".join(H) + "\n")
+    barrier()
     return path
 
 
@@ -219,21 +254,66 @@ def read_header(path):
                 level_count=level_count, boxes=boxes)
 
 
-def restart(path, geom0, params, opts=None, single_level=False, stop_time=None):
+def deal_owners(boxes_per_level, world):
+    """owner rank of every box for a restart on `world` ranks when the checkpoint was written by another number of ranks: deterministic,
+    the same on every rank.  Level 0 by the owner formula of lib.Layout.decompose (contiguous chunks of the box list); refined levels
+    largest box first onto the least-loaded rank (load in cells; ties: lower box index first, lower rank first)."""
+    out = []
+    for l, boxes in enumerate(boxes_per_level):
+        nb = len(boxes)
+        if l == 0:
+            per = (nb + world - 1) // world
+            out.append([min(i // per, world - 1) for i in range(nb)])
+            continue
+        cells = [int(np.prod([hi[d] - lo[d] + 1 for d in range(3)])) for lo, hi in boxes]
+        load, own = [0] * world, [0] * nb
+        for q in sorted(range(nb), key=lambda q: (-cells[q], q)):
+            r = min(range(world), key=lambda r: (load[r], r))
+            own[q] = r
+            load[r] += cells[q]
+        out.append(own)
+    return out
+
+
+def restart_owners(path, world):
+    """owners per level a restart of checkpoint `path` on `world` ranks uses: the recorded ones if the checkpoint was written by `world`
+    ranks, otherwise deal_owners"""
+    hd = read_header(path)
+    with open(os.path.join(path, "iamrx_restart.json")) as f:
+        extra = json.load(f)
+    nlev = hd["finest_level"] + 1
+    if int(extra.get("world", 1)) == world:
+        own = [[int(o) for o in extra["levels"][l]["owners"]] for l in range(nlev)]
+        if all(len(own[l]) == len(hd["boxes"][l]) and all(0 <= o < world for o in own[l]) for l in range(nlev)):
+            return own
+    return deal_owners([hd["boxes"][l] for l in range(nlev)], world)
+
+
+def restart(path, geom0, params, opts=None, single_level=False, stop_time=None, rank=None, world=None):
     """amr.restart: rebuild the run from a checkpoint directory.  geom0 / params / opts / stop_time come from the inputs file, as upstream
     re-reads them (a restart with a later stop_time is the usual reason to restart; the checkpoint's own stop_time is used only if none is
     given); returns an iamr_amd.amr.Amr (or a NavierStokes level if single_level and the checkpoint holds one level) that continues
-    exactly where the checkpointed run stood -- no post_init."""
+    exactly where the checkpointed run stood -- no post_init.
+
+    rank / world: this process in the run that restarts (default: the library's communicator).  Any world size can read any checkpoint.
+    If `world` is the world size that wrote it, every box goes back to its recorded owner.  Otherwise the boxes are dealt out again
+    (deal_owners: level 0 as Layout.decompose does, refined levels largest first onto the least-loaded rank) -- a distribution for the
+    time until the next regrid, which redeals the levels it rebuilds with the library's own knapsack.  Every rank reads only its grids."""
     from . import lib as Lb
     from .lib import lib, check
     from .ns import NavierStokes
     from .amr import Amr
     L = lib()
+    if rank is None or world is None:
+        rank, world = Lb.comm_rank()
+    elif (rank, world) != Lb.comm_rank():       # the layouts below take their local boxes from the library's communicator
+        raise ValueError(f"checkpoint.restart: rank {rank} of {world} given, but the library's communicator says {Lb.comm_rank()}")
     hd = read_header(path)
     with open(os.path.join(path, "iamrx_restart.json")) as f:
         extra = json.load(f)
     nlev = hd["finest_level"] + 1
-    lays = [Lb.Layout([(tuple(lo), tuple(hi)) for lo, hi in hd["boxes"][l]]) for l in range(nlev)]
+    owners = restart_owners(path, world)
+    lays = [Lb.Layout([(tuple(lo), tuple(hi)) for lo, hi in hd["boxes"][l]], owners[l]) for l in range(nlev)]
     if single_level and nlev == 1:
         run = NavierStokes(geom0, lays[0], params, opts)
         levels = [run]
@@ -242,15 +322,16 @@ def restart(path, geom0, params, opts=None, single_level=False, stop_time=None):
         levels = run.levels
     for l, lev in enumerate(levels):
         ld = os.path.join(path, f"Level_{l}")
+        mine = _local_indices(lays[l])
         for t, (name, snew, sold, typ, nc) in enumerate(STATE_TYPES):
             for tag, sel in (("New", snew), ("Old", sold)):
-                arrays = _read_vismf(ld, f"SD_{t}_{tag}_MF")
-                mf = Lb.MultiFab(lays[l], typ, arrays[0].shape[-1] if (t == 0 and arrays) else nc, 1)
+                arrays = _read_vismf(ld, f"SD_{t}_{tag}_MF", mine)
+                mf = Lb.MultiFab(lays[l], typ, _vismf_ncomp(ld, f"SD_{t}_{tag}_MF") if t == 0 else nc, 1)
                 for li, a in enumerate(arrays):
                     mf.from_numpy(a, li)
                 lev.set_data(sel, mf)
         for q in range(2):
-            arrays = _read_vismf(ld, f"MacPhiHist_{q}")
+            arrays = _read_vismf(ld, f"MacPhiHist_{q}", mine)
             mf = Lb.MultiFab(lays[l], (0, 0, 0), 1, 0)
             for li, a in enumerate(arrays):
                 mf.from_numpy(a, li)

@@ -214,6 +214,13 @@ int iamrx_layout_local_box(iamrx_layout l, int li, int lo_hi[6], int* gi)
     if (gi) *gi = l->p->local[li];
     IAMRX_CATCH
 }
+int iamrx_layout_owners(iamrx_layout l, int* owners)
+{
+    IAMRX_TRY
+    const auto& o = l->p->owner;
+    for (size_t q = 0; q < o.size(); ++q) owners[q] = o[q];
+    IAMRX_CATCH
+}
 
 int iamrx_mf_create(iamrx_layout l, const int type[3], int ncomp, int ngrow, iamrx_mf* out)
 {

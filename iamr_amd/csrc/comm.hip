@@ -177,6 +177,19 @@ int iamrx_comm_rank(int* rank, int* nranks)
     if (nranks) *nranks = c ? c->nranks : 1;
     return 0;
 }
+// Comm::allreduce of a host buffer through whatever communicator is installed (RCCL, the callback transport; one rank: the buffer stays
+// as it is): the barrier and the metadata exchange of the host-side I/O layer
+int iamrx_comm_allreduce(double* vals, int n, int op)
+{
+    try {
+        auto& c = Context::get().comm;
+        if (op < 0 || op > 2) throw Error("iamrx_comm_allreduce: op must be 0 (sum), 1 (max) or 2 (min)");
+        if (n < 0 || (n > 0 && !vals)) throw Error("iamrx_comm_allreduce: null buffer or negative count");
+        if (!c || c->nranks <= 1 || n == 0) return 0;
+        c->allreduce(vals, n, op == 0 ? ReduceOp::Sum : (op == 1 ? ReduceOp::Max : ReduceOp::Min));
+        return 0;
+    } catch (const std::exception& e) { g_cerr = e.what(); return 1; }
+}
 // transport probe: every rank sends `count` doubles to `peer` and receives as many from it through the installed communicator's
 // exchange() (the halo-exchange primitive); peer == own rank is a loop-back through the same Send / Recv calls.  Returns 0 if the
 // received data are the pattern the peer sent.

@@ -95,6 +95,30 @@ def sync():
     check(lib().iamrx_sync())
 
 
+def comm_rank():
+    """(rank, number of ranks) of the installed communicator; (0, 1) without one"""
+    r, n = C.c_int(), C.c_int()
+    check(lib().iamrx_comm_rank(C.byref(r), C.byref(n)))
+    return r.value, n.value
+
+
+def comm_allreduce(a, op=0):
+    """in-place all-reduce of a float64 numpy array over the ranks (include/iamrx.h: iamrx_comm_allreduce); op 0 sum, 1 max, 2 min.
+    Collective; one rank: `a` stays as it is."""
+    if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous):
+        raise TypeError("comm_allreduce: a C-contiguous float64 numpy array is reduced in place")
+    L = lib()
+    if L.iamrx_comm_allreduce(a.ctypes.data_as(C.POINTER(C.c_double)), int(a.size), int(op)) != 0:
+        L.iamrx_comm_last_error.restype = C.c_char_p
+        raise IamrxError(L.iamrx_comm_last_error().decode())
+    return a
+
+
+def comm_barrier():
+    """every rank has arrived (a one-element sum through comm_allreduce)"""
+    comm_allreduce(np.zeros(1), 0)
+
+
 def mg_opts(**kw):
     o = MgOpts()
     lib().iamrx_mg_default_opts(C.byref(o))

@@ -10,7 +10,8 @@ Source/NavierStokesBase.cpp:3344-3352 / AmrLevel::writePlotFile role):
   <dir>/Level_<l>/Cell_H  VisMF header: version 1, how 0, ncomp, ngrow, the BoxArray, "FabOnDisk: file offset" per grid, and the
                           per-grid / per-component minima and maxima
   <dir>/Level_<l>/Cell_D_00000   per grid: "FAB ((8, (64 11 52 0 1 12 0 1023)),(8, (8 7 6 5 4 3 2 1)))(box) ncomp\\n" + the doubles
-                          (little endian, Fortran order, one component after the other)
+                          (little endian, Fortran order, one component after the other); a run on several ranks writes one
+                          Cell_D_<rank:05d> per rank that owns grids of the level (PlotFile.write_data / write_headers)
 
 Host-side I/O (control plane): plain Python + numpy, dimension-generic (2-D files of the reference can be read)."""
 import os
@@ -37,16 +38,87 @@ def _box_str(lo, hi):
     return "((" + ",".join(str(v) for v in lo) + ") (" + ",".join(str(v) for v in hi) + ") (" + ",".join("0" for _ in range(dim)) + "))"
 
 
-class Level:
-    """one AMR level of a plotfile: index domain, mesh spacing, boxes and the data of every box (array (n..., ncomp), Fortran order)"""
+def data_file(rank):
+    """name (after the MultiFab's prefix) of the data file rank `rank` writes: VisMF's one file per writer"""
+    return f"_D_{rank:05d}"
 
-    def __init__(self, domain, dx, boxes, data=None, step=0, time=0.0):
+
+def write_fabs(path, fabs):
+    """one writer's data file: fabs = [(box text of the FAB header, array (n..., ncomp))] one after the other -> per fab
+    (offset, minima[nc], maxima[nc]).  The doubles go out x fastest, component outermost (the FAB byte order)."""
+    out = []
+    with open(path, "wb") as f:
+        for box, a in fabs:
+            a = np.asarray(a, dtype="<f8")
+            nc = a.shape[-1]
+            off = f.tell()
+            f.write(f"FAB {REAL_DESC}{box} {nc}\n".encode())
+            f.write(np.asfortranarray(a).tobytes(order="F"))
+            out.append((off, [a[..., n].min() for n in range(nc)], [a[..., n].max() for n in range(nc)]))
+    return out
+
+
+def write_vismf_header(path, nc, ngrow, boxes, fab_files, mins, maxs):
+    """VisMF header of one MultiFab: boxes = the BoxArray as text, fab_files = (file, offset) per grid, mins / maxs per grid and component,
+    all in global box order"""
+    with open(path, "w") as f:
+        f.write(f"1\n0\n{nc}\n{ngrow}\n({len(boxes)} 0\n")
+        for b in boxes:
+            f.write(b + "\n")
+        f.write(f")\n{len(boxes)}\n")
+        for fn, o in fab_files:
+            f.write(f"FabOnDisk: {fn} {o}\n")
+        for vals in (mins, maxs):
+            f.write(f"\n{len(boxes)},{nc}\n")
+            for row in vals:
+                f.write("".join(_fmt17(v) + "," for v in row) + "\n")
+
+
+def merge_meta(nboxes, metas):
+    """metas = {rank: [(global box index, offset, minima, maxima), ...]} of one MultiFab from every writer -> (owner, offset, minima,
+    maxima) per box in global order; every box must have exactly one writer"""
+    rows = [None] * nboxes
+    for rank in sorted(metas):
+        for gi, off, mn, mx in metas[rank]:
+            if rows[gi] is not None:
+                raise ValueError(f"box {gi} was written by ranks {rows[gi][0]} and {rank}")
+            rows[gi] = (rank, int(off), list(mn), list(mx))
+    missing = [q for q, r in enumerate(rows) if r is None]
+    if missing:
+        raise ValueError(f"no rank wrote boxes {missing}")
+    return rows
+
+
+def gather_meta(nboxes, nc, meta, owners, allreduce):
+    """the metadata exchange of a collective write: `meta` = this rank's [(global box index, offset, minima, maxima)] of one MultiFab;
+    every box has one owner, who contributes its row of an [nboxes x (1 + 2 nc)] table, everyone else zeros; one sum (`allreduce(table,
+    0)`: lib.comm_allreduce) gives every rank the table (offsets are far below 2^53: doubles carry them exactly).  Returns the `metas`
+    dictionary merge_meta takes."""
+    T = np.zeros((nboxes, 1 + 2 * nc))
+    for gi, off, mn, mx in meta:
+        T[gi, 0] = off
+        T[gi, 1:1 + nc] = mn
+        T[gi, 1 + nc:] = mx
+    allreduce(T, 0)
+    metas = {}
+    for gi in range(nboxes):
+        metas.setdefault(int(owners[gi]), []).append((gi, int(T[gi, 0]), list(T[gi, 1:1 + nc]), list(T[gi, 1 + nc:])))
+    return metas
+
+
+class Level:
+    """one AMR level of a plotfile: index domain, mesh spacing, boxes and the data of every box (array (n..., ncomp), Fortran order).
+    A rank of a multi-rank run holds the whole box list but only the data of the boxes it owns: `owned` = their global indices,
+    increasing, one per entry of `data` (None: every box, in order)."""
+
+    def __init__(self, domain, dx, boxes, data=None, step=0, time=0.0, owned=None):
         self.domain = (tuple(domain[0]), tuple(domain[1]))
         self.dx = tuple(dx)
         self.boxes = [(tuple(lo), tuple(hi)) for lo, hi in boxes]
         self.data = data
         self.step = step
         self.time = time
+        self.owned = None if owned is None else [int(q) for q in owned]
         self.fab_files = None      # reader: (file, offset) per box
 
 
@@ -83,6 +155,8 @@ class PlotFile:
         return "\n".join(L) + "\n"
 
     def write(self, path):
+        """one writer holding every box (pinned byte for byte on the reference's plotfiles, tests/test_cpu_plotfile.py; the two-phase
+        form below writes the same files for one rank, tests/test_cpu_multirank_io.py)"""
         os.makedirs(path, exist_ok=True)
         with open(os.path.join(path, "Header"), "w") as f:
             f.write(self.header_text())
@@ -112,6 +186,50 @@ class PlotFile:
                     f.write(f"\n{len(lv.boxes)},{nc}\n")
                     for row in vals:
                         f.write("".join(_fmt17(v) + "," for v in row) + "\n")
+
+    # ------------------------------------------------------------------------------ writer of a multi-rank run, in two phases
+    # (AMReX's format: one data file per writer, headers that name a file and an offset per grid).  Neither phase knows about
+    # communicators: the caller carries the metadata from the writers to the rank that writes the headers (write_collective does).
+    def make_dirs(self, path):
+        """the plotfile's directories (one rank, before anyone writes data)"""
+        for l in range(len(self.levels)):
+            os.makedirs(os.path.join(path, f"Level_{l}"), exist_ok=True)
+
+    def write_data(self, path, rank=0):
+        """phase A, every rank: Level_<l>/Cell_D_<rank:05d> with the fabs this rank owns (Level.owned / Level.data) in increasing global
+        box index; a rank without a box of a level writes no file for it.  Returns per level [(global index, offset, minima, maxima)]."""
+        nc = len(self.names)
+        meta = []
+        for l, lv in enumerate(self.levels):
+            owned = list(range(len(lv.boxes))) if lv.owned is None else lv.owned
+            assert len(owned) == len(lv.data) and all(a < b for a, b in zip(owned, owned[1:])), owned
+            fabs = []
+            for gi, a in zip(owned, lv.data):
+                lo, hi = lv.boxes[gi]
+                assert np.shape(a) == tuple(h - q + 1 for q, h in zip(lo, hi)) + (nc,), (np.shape(a), lo, hi)
+                fabs.append((_box_str(lo, hi), a))
+            if not fabs:
+                meta.append([])
+                continue
+            ld = os.path.join(path, f"Level_{l}")
+            os.makedirs(ld, exist_ok=True)
+            res = write_fabs(os.path.join(ld, "Cell" + data_file(rank)), fabs)
+            meta.append([(gi, off, mn, mx) for gi, (off, mn, mx) in zip(owned, res)])
+        return meta
+
+    def write_headers(self, path, metas):
+        """phase B, one rank, once all data files are complete: Header and every Level_<l>/Cell_H from metas = {rank: what that rank's
+        write_data returned}; grids, FabOnDisk lines and the min / max tables in global box order"""
+        os.makedirs(path, exist_ok=True)
+        nc = len(self.names)
+        for l, lv in enumerate(self.levels):
+            rows = merge_meta(len(lv.boxes), {r: m[l] for r, m in metas.items()})
+            ld = os.path.join(path, f"Level_{l}")
+            os.makedirs(ld, exist_ok=True)
+            write_vismf_header(os.path.join(ld, "Cell_H"), nc, 0, [_box_str(lo, hi) for lo, hi in lv.boxes],
+                               [("Cell" + data_file(r), off) for r, off, _, _ in rows], [r[2] for r in rows], [r[3] for r in rows])
+        with open(os.path.join(path, "Header"), "w") as f:      # last: a complete Header implies complete data
+            f.write(self.header_text())
 
     # ------------------------------------------------------------------------------------------------ reader
     @staticmethod
@@ -172,6 +290,33 @@ class PlotFile:
                 cnt = int(np.prod(shape))
                 a = np.frombuffer(f.read(8 * cnt), dtype="<f8" if little else ">f8").reshape(shape, order="F")
                 lv.data.append(a.astype(np.float64))
+
+
+def comm_ops(world):
+    """(allreduce(array, op), barrier()) of the library's communicator for the collective writers; one rank: nothing to do (and no
+    library needed)"""
+    if world == 1:
+        return (lambda a, op=0: a), (lambda: None)
+    from .lib import comm_allreduce, comm_barrier
+    return comm_allreduce, comm_barrier
+
+
+def write_collective(pf, path, owners, rank=0, world=1):
+    """every rank of a run writes its part of plotfile `pf` (Level.owned / Level.data = what this rank holds; owners[l] = owner rank of
+    every box of level l): rank 0 makes the directories -- barrier -- data files -- one sum per level carries offsets, minima and maxima
+    to everyone (gather_meta) and orders the data before the headers -- rank 0 writes the headers.  Collective over the library's
+    communicator (lib.comm_allreduce: RCCL or the callback transport alike)."""
+    allreduce, barrier = comm_ops(world)
+    if rank == 0:
+        pf.make_dirs(path)
+    barrier()
+    meta = pf.write_data(path, rank)
+    nc = len(pf.names)
+    gathered = [gather_meta(len(lv.boxes), nc, meta[l], owners[l], allreduce) for l, lv in enumerate(pf.levels)]
+    if rank == 0:
+        ranks = sorted({r for g in gathered for r in g})
+        pf.write_headers(path, {r: [g.get(r, []) for g in gathered] for r in ranks})
+    barrier()
 
 
 def compare(path_a, path_b):

@@ -1,7 +1,10 @@
 """`python -m iamr_amd.run <inputs file> [key=value ...]` -- IAMR's main loop (Source/main.cpp:60-145: ParmParse, Amr::init,
 `while (step < max_step && time < stop_time) coarseTimeStep`) driving libiamrx.so from an unmodified IAMR inputs file (SURVEY row
 f4): one level, or a hierarchy of fixed refined grids (amr.max_level > 0 with amr.regrid_file, subcycled, inviscid).  Under
-torch.distributed.run a single-level run shards its boxes over the ranks (one process per GPU)."""
+torch.distributed.run the boxes of every level are spread over the ranks (one process per GPU); plotfiles and checkpoints are written
+by all ranks together (every rank the fabs it owns, rank 0 the headers) and amr.restart reads a checkpoint on any number of ranks.
+IAMRX_RUN_TRANSPORT=gloo: the ranks talk through torch.distributed's gloo on host buffers and all use device 0 (several ranks on the one
+GPU of a test machine); unset: nccl + RCCL, one GPU per rank."""
 import os
 import sys
 import time
@@ -49,8 +52,15 @@ def build_amr(pr, lib, N, world=1, **mg_kw):
     return amr, amr.layouts, g0
 
 
+def local_indices(lay):
+    """global indices (in lay.boxes) of the boxes this rank owns, in the order of its local fabs"""
+    return [lay.local_box(li)[2] for li in range(lay.nlocal())]
+
+
 def level_arrays(ns, lay, N, derived=()):
-    """valid-region arrays of the level's boxes: the state components, then the derived quantities asked for (NavierStokes::derive)"""
+    """valid-region arrays of the boxes of the level THIS RANK owns (local_indices(lay) says which of lay.boxes they are): the state
+    components, then the derived quantities asked for (NavierStokes::derive -- collective: its ghost fill talks to the other ranks, so
+    every rank calls this, also one that owns nothing)"""
     import numpy as np
     S = ns.data(N.NavierStokes.S_NEW)
     D = [ns.derive(name) for name in derived]
@@ -130,8 +140,11 @@ def enforce_plane(levels, pr):
 
 
 def write_plot_amr(amr, lays, pr, N, step, root):
-    """NavierStokesBase::writePlotFile role for the hierarchy: one AMReX plotfile with every level (the five state components)"""
-    from .plotfile import PlotFile, Level
+    """NavierStokesBase::writePlotFile role for the hierarchy: one AMReX plotfile with every level (the five state components).
+    Collective: every rank calls it and writes the boxes it owns (plotfile.write_collective)."""
+    from .plotfile import PlotFile, Level, write_collective
+    from .lib import comm_rank
+    rank, world = comm_rank()
     names, der, kept = plot_names_and_filter(pr)
     levels = []
     dts = amr.dts()
@@ -146,30 +159,26 @@ def write_plot_amr(amr, lays, pr, N, step, root):
             levels.append(Level(((0, 0), (n[0] - 1, n[2] - 1)), [dx[0], dx[2]], boxes, arrs, step * 2 ** l, amr.time))
         else:
             out_names, arrs = select_components(names, arrs, kept)
-            levels.append(Level(((0, 0, 0), tuple(v - 1 for v in n)), dx, boxes, arrs, step * 2 ** l, amr.time))
+            levels.append(Level(((0, 0, 0), tuple(v - 1 for v in n)), dx, lays[l].boxes, arrs, step * 2 ** l, amr.time, owned=local_indices(lays[l])))
     path = f"{root}{step:05d}"
-    if pr.get("slab"):
+    if pr.get("slab"):                      # single-rank runs (main): every box is local
         PlotFile(out_names, amr.time, [pr["prob_lo"][0], pr["prob_lo"][2]], [pr["prob_hi"][0], pr["prob_hi"][2]], levels).write(path)
     else:
-        PlotFile(out_names, amr.time, pr["prob_lo"], pr["prob_hi"], levels).write(path)
+        write_collective(PlotFile(out_names, amr.time, pr["prob_lo"], pr["prob_hi"], levels), path, [lay.owners for lay in lays], rank, world)
     return path
 
 
 def main_amr(pr, inp, lib, N, rank=0, world=1):
     """hierarchy run; world > 1: the boxes of every level are spread over the ranks (level 0 by Layout.decompose, fixed refined grids
-    round-robin, regridded levels by the library's knapsack), plotfiles are written by single-rank runs only"""
+    round-robin, regridded levels by the library's knapsack, restarted levels as checkpoint.restart says)"""
     say = print if rank == 0 else (lambda *a, **k: None)
-    check_int, check_root = (pr.get("check_int", -1), pr.get("check_file", "chk")) if world == 1 else (-1, "chk")
+    check_int, check_root = pr.get("check_int", -1), pr.get("check_file", "chk")
     plot_int, plot_root = pr.get("plot_int", -1), pr.get("plot_file", "plt")
-    if world > 1:
-        plot_int = -1
     if pr.get("restart"):
         # amr.restart (Amr::restart): grids, data, times and step counters come from the checkpoint, parameters from the inputs file
         from . import checkpoint
-        if world > 1:
-            raise NotImplementedError("iamr_amd.run: amr.restart runs on one rank")
         g0 = lib.Geom.make(pr["n"], prob_lo=pr["prob_lo"], prob_hi=pr["prob_hi"], periodic=pr["periodic"])
-        amr = checkpoint.restart(pr["restart"], g0, N.ns_params(**pr["params"]), stop_time=pr["stop_time"])
+        amr = checkpoint.restart(pr["restart"], g0, N.ns_params(**pr["params"]), stop_time=pr["stop_time"], rank=rank, world=world)
         if pr.get("regrid"):
             amr.set_regrid(**pr["regrid"])
         lays = amr.layouts
@@ -193,7 +202,7 @@ def main_amr(pr, inp, lib, N, rank=0, world=1):
         lays = amr.layouts                      # a regrid during the step replaces them
         step += 1
         say(f"STEP = {step} TIME = {amr.time:.12g} DT = {dt:.12g} LEVELS = {amr.nlev} GRIDS = {[len(l.boxes) for l in lays]}")
-        if plot_int > 0 and step % plot_int == 0:
+        if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports
             say("PLOTFILE:", write_plot_amr(amr, lays, pr, N, step, plot_root))
         if check_int > 0 and step % check_int == 0:
             from . import checkpoint
@@ -225,8 +234,11 @@ def build(inp, lib, N, nranks=1, pr=None):
 
 def write_plot(ns, lay, pr, N, step, root):
     """NavierStokesBase::writePlotFile role (single level): AMReX-format plotfile <root><step:05d> with the state variables of
-    amr.plot_vars and the derived quantities of amr.derive_plot_vars.  Single-rank runs only (every box is local)."""
-    from .plotfile import from_level_data
+    amr.plot_vars and the derived quantities of amr.derive_plot_vars.  Collective: every rank of the library's communicator calls it and
+    writes the boxes it owns (plotfile.write_collective); `lay` names all boxes and their owners."""
+    from .plotfile import from_level_data, write_collective
+    from .lib import comm_rank
+    rank, world = comm_rank()
     names, der, kept = plot_names_and_filter(pr)
     boxes, arrs = level_arrays(ns, lay, N, der)
     path = f"{root}{step:05d}"
@@ -236,7 +248,9 @@ def write_plot(ns, lay, pr, N, step, root):
         from_level_data((pr["n"][0], pr["n"][2]), (pr["prob_lo"][0], pr["prob_lo"][2]), (pr["prob_hi"][0], pr["prob_hi"][2]), boxes, arrs, ns.time, step, names=out_names).write(path)
     else:
         out_names, arrs = select_components(names, arrs, kept)
-        from_level_data(tuple(pr["n"]), tuple(pr["prob_lo"]), tuple(pr["prob_hi"]), boxes, arrs, ns.time, step, names=out_names).write(path)
+        pf = from_level_data(tuple(pr["n"]), tuple(pr["prob_lo"]), tuple(pr["prob_hi"]), lay.boxes, arrs, ns.time, step, names=out_names)
+        pf.levels[0].owned = local_indices(lay)
+        write_collective(pf, path, [lay.owners], rank, world)
     return path
 
 
@@ -253,37 +267,52 @@ def main(argv):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     from . import lib
     from . import ns as N
+    # IAMRX_RUN_TRANSPORT=gloo: host-staged transport (comm.init_gloo_callback), every rank on device 0 -- several ranks on one GPU, where
+    # RCCL cannot connect two ranks; unset: nccl + RCCL, rank r on GPU LOCAL_RANK
+    transport = os.environ.get("IAMRX_RUN_TRANSPORT", "")
+    if transport not in ("", "gloo"):
+        raise ValueError(f"IAMRX_RUN_TRANSPORT={transport!r}: only 'gloo' (or unset: RCCL) is known")
     if world > 1:
-        import torch
         import torch.distributed as dist
-        torch.cuda.set_device(local_rank)
-        dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+        if transport == "gloo":
+            local_rank = 0
+            dist.init_process_group("gloo", rank=rank, world_size=world)
+        else:
+            import torch
+            torch.cuda.set_device(local_rank)
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     lib.init(local_rank)
     if world > 1:
         from . import comm
-        comm.init_rccl_from_torch(dist)
+        if transport == "gloo":
+            comm.init_gloo_callback(dist)
+        else:
+            comm.init_rccl_from_torch(dist)
     pr = inp.problem()
     if pr.get("slab") and world > 1:
         raise NotImplementedError("iamr_amd.run: two-dimensional inputs (run on a y-periodic slab) are single-rank runs")
+    say = print if rank == 0 else (lambda *a, **k: None)
     if pr["fine_boxes"] or pr.get("regrid") or (pr.get("restart") and pr.get("max_level", 0) > 0):
-        return main_amr(pr, inp, lib, N, rank, world)
+        rc = main_amr(pr, inp, lib, N, rank, world)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return rc
     plot_int, plot_root = pr.get("plot_int", -1), pr.get("plot_file", "plt")
-    check_int, check_root = (pr.get("check_int", -1), pr.get("check_file", "chk")) if world == 1 else (-1, "chk")
+    check_int, check_root = pr.get("check_int", -1), pr.get("check_file", "chk")
     if pr.get("restart"):
         from . import checkpoint
-        if world > 1:
-            raise NotImplementedError("iamr_amd.run: amr.restart runs on one rank")
         g = lib.Geom.make(pr["n"], prob_lo=pr["prob_lo"], prob_hi=pr["prob_hi"], periodic=pr["periodic"])
-        ns = checkpoint.restart(pr["restart"], g, N.ns_params(**pr["params"]), single_level=True, stop_time=pr["stop_time"])
+        ns = checkpoint.restart(pr["restart"], g, N.ns_params(**pr["params"]), single_level=True, stop_time=pr["stop_time"], rank=rank, world=world)
         lay = ns.layout
         step = checkpoint.read_header(pr["restart"])["level_steps"][0]
-        print(f"RESTART from {pr['restart']}: step {step}, time {ns.time:.12g}")
+        say(f"RESTART from {pr['restart']}: step {step}, time {ns.time:.12g}")
     else:
         ns, lay, g, pr = build(inp, lib, N, world, pr)
         ns.post_init(pr["stop_time"])
         step = 0
-        if plot_int > 0 and world == 1:
-            print("PLOTFILE:", write_plot(ns, lay, pr, N, 0, plot_root))
+        if plot_int > 0:
+            say("PLOTFILE:", write_plot(ns, lay, pr, N, 0, plot_root))
     if rank == 0 and inp.ignored:
         print("inputs: ignored (I/O / verbosity / AMR bookkeeping) keys:", " ".join(sorted(inp.ignored)))
     t0 = time.perf_counter()
@@ -296,11 +325,11 @@ def main(argv):
         step += 1
         if rank == 0:
             print(f"STEP = {step} TIME = {ns.time:.12g} DT = {dt:.12g}")
-        if plot_int > 0 and world == 1 and step % plot_int == 0:
-            print("PLOTFILE:", write_plot(ns, lay, pr, N, step, plot_root))
+        if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports
+            say("PLOTFILE:", write_plot(ns, lay, pr, N, step, plot_root))
         if check_int > 0 and step % check_int == 0:
             from . import checkpoint
-            print("CHECKPOINT:", checkpoint.write(ns, check_root, step))
+            say("CHECKPOINT:", checkpoint.write(ns, check_root, step))
     lib.sync()
     if rank == 0:
         print(f"Run time = {time.perf_counter() - t0:.6f}")

@@ -123,6 +123,10 @@ typedef void (*iamrx_exchange_cb)(int nsend, const int* send_peers, double** sen
                                   int nrecv, const int* recv_peers, double** recv_bufs, const long* recv_counts);
 int iamrx_comm_init_callback(int rank, int nranks, iamrx_allreduce_cb ar, iamrx_exchange_cb ex);
 int iamrx_comm_rank(int* rank, int* nranks);
+/* all-reduce of a HOST buffer over the ranks through the installed communicator (RCCL or the callback transport; one rank: the buffer is
+ * left as it is); op as iamrx_allreduce_cb.  Collective.  The ParallelDescriptor::ReduceRealSum / Barrier role for host-side code (the
+ * plotfile / checkpoint writers exchange file offsets and minima / maxima with it and use a one-element sum as their barrier). */
+int iamrx_comm_allreduce(double* vals, int n, int op);
 /* transport probe: exchange `count` doubles with `peer` through the installed communicator (peer == own rank: loop-back); 0 = data intact */
 int iamrx_comm_probe_exchange(int peer, long count);
 const char* iamrx_comm_last_error(void);
@@ -138,6 +142,8 @@ int iamrx_layout_coalesced_boxes(iamrx_layout l, int* nboxes, int* lo_hi /* 6 in
 int iamrx_layout_destroy(iamrx_layout l);
 int iamrx_layout_nlocal(iamrx_layout l, int* nlocal);
 int iamrx_layout_local_box(iamrx_layout l, int local_idx, int lo_hi[6], int* global_idx);
+/* the DistributionMapping: owner rank of every box, in box order (nboxes ints) -- what a regrid's knapsack dealt (iamrx_amr_level_layout) */
+int iamrx_layout_owners(iamrx_layout l, int* owners /* nboxes */);
 int iamrx_mf_create(iamrx_layout l, const int type[3] /* 1 = nodal in that direction */, int ncomp, int ngrow, iamrx_mf* out);
 int iamrx_mf_destroy(iamrx_mf m);
 int iamrx_mf_info(iamrx_mf m, int* ncomp, int* ngrow, int type[3], int* nlocal);
