@@ -167,6 +167,19 @@ class Amr:
         check(lib().iamrx_amr_time(self.h, None, arr))
         return list(arr)
 
+    def sum_integrated(self):
+        """(mass, tracer, kinetic energy) of the composite grid now (NavierStokes::sum_integrated_quantities, NavierStokes.cpp:1046-1079)"""
+        v = (C.c_double * 3)()
+        check(lib().iamrx_amr_sum_integrated(self.h, v))
+        return tuple(v)
+
+    def last_sum(self):
+        """(level-0 step, time, (mass, tracer, kinetic energy)) the hierarchy last computed by itself (ns.sum_interval > 0: after post_init and
+        in level 0's post_timestep), or None"""
+        st, tm, v = C.c_int(), C.c_double(), (C.c_double * 3)()
+        check(lib().iamrx_amr_last_sum(self.h, C.byref(st), C.byref(tm), v))
+        return None if st.value < 0 else (st.value, tm.value, tuple(v))
+
     def profile(self, enable):
         """-> (hierarchy sections [16], per-level sections [nlev][8]) accumulated so far; then enable: 1 reset + start, 0 stop, -1 keep"""
         sec = (C.c_double * 16)()

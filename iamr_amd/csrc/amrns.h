@@ -29,6 +29,12 @@ public:
     void level_sync(int l, int crse_iteration = -1);      // crse_iteration: of level l within the step of level l-1 (-1: the last one)
     void post_timestep(int l, int crse_iteration = -1);
     void time_step(int l, double time, int iteration, int niter);
+    // NavierStokes::sum_integrated_quantities (NavierStokes.cpp:1046-1079): composite mass, tracer and kinetic energy -- every level over the
+    // cells the next finer one does not cover, the levels added coarsest first.  post_init and level 0's post_timestep (every
+    // sum_interval-th level-0 step) call it and leave what they found in last_sum (last_sum_step: the level-0 step count then, -1: never)
+    void sum_integrated_quantities(double out[3]);
+    double last_sum[3] = {0.0, 0.0, 0.0}, last_sum_time = 0.0;
+    int last_sum_step = -1;
     // ---- regridding (Amr::regrid from level 0 at the start of a coarse step; NavierStokes::errorEst, NS_error.cpp:10-145;
     // NavierStokesBase::init(AmrLevel&) / init(), NavierStokesBase.cpp:1713-1806) ----
     struct TagRule {

@@ -1223,6 +1223,30 @@ void AmrNS::post_timestep(int l, int crse_iteration)
         { AmrTimer t(*this, 4); level_sync(l, crse_iteration); }
     }
     if (l > 0) mf_saxpy(lev[l]->p_avg, 1.0 / (double)n_cycle[l], lev[l]->P[lev[l]->pnew], 0, 0, 1, 0);      // incrPAvg
+    // NavierStokesBase.cpp:2589-2592: level_steps is level 0's count, already incremented (time_step)
+    if (l == 0 && p.sum_interval > 0 && level_steps % p.sum_interval == 0) {
+        sum_integrated_quantities(last_sum);
+        last_sum_step = level_steps; last_sum_time = lev[0]->time;
+    }
+    lev[l]->time_average(dt_level[l], level_steps);                                                       // :2630-2634
+    // The levels above l have just reached level l's time through their own sub-steps, and have summed the same interval in smaller pieces:
+    // their three scalars equal level l's up to the rounding of those sums.  They take level l's, so that at the end of a coarse step ONE
+    // time_avg / time_avg_fluct describes the hierarchy -- what <chk>/TimeAverage holds and what a regrid hands to a new level.
+    if (lev[l]->has_average())
+        for (size_t k = l + 1; k < lev.size(); ++k) { lev[k]->time_avg = lev[l]->time_avg; lev[k]->time_avg_fluct = lev[l]->time_avg_fluct; lev[k]->dt_avg = lev[l]->dt_avg; }
+}
+
+void AmrNS::sum_integrated_quantities(double out[3])
+{
+    out[0] = out[1] = out[2] = 0.0;
+    const int fin = (int)lev.size() - 1;
+    for (int l = 0; l <= fin; ++l) {
+        NavierStokes& s = *lev[l];
+        double v[3];
+        if (l < fin) { MultiFab fc = fine_coverage(s.layout, lev[l + 1]->layout, s.g, lev[l + 1]->ratio); s.sum_integrated(&fc, v); }
+        else s.sum_integrated(nullptr, v);
+        for (int q = 0; q < 3; ++q) out[q] += v[q];
+    }
 }
 
 // Amr::timeStep
@@ -1257,6 +1281,7 @@ void AmrNS::time_step(int l, double time, int iteration, int niter)
     dt_min[l] = iteration == 1 ? dt_new : std::min(dt_min[l], dt_new);
     s.time = time + dt_level[l];
     s.nstep += 1;
+    if (l == 0) level_steps += 1;          // Amr::timeStep: level_steps[level]++ before the finer levels step and before post_timestep
     if ((int)level_count_v.size() > l) level_count_v[l] += 1;
     if (l < (int)lev.size() - 1) {
         const int nc = n_cycle[l + 1];
@@ -1396,6 +1421,13 @@ void AmrNS::post_init(double stop_time_)
         s.dt = dt_save[k];
     }
     level_steps = 0;
+    // NavierStokes::post_init, NavierStokes.cpp:1284-1297: the integrated quantities of the initial data; the initial state is the first
+    // sample of the time averages, its weight the first dt of level 0.  Upstream's post_init returns at once on levels > 0 (:1257-1261),
+    // so its refined levels never take this sample and start their time_avg one coarse step short of level 0's; here every level takes
+    // it with the same weight, and all levels agree on time_avg from the start.
+    last_sum_step = -1;
+    if (p.sum_interval > 0) { sum_integrated_quantities(last_sum); last_sum_step = 0; last_sum_time = lev[0]->time; }
+    for (int k = 0; k < nl; ++k) { lev[k]->time_avg = lev[k]->time_avg_fluct = lev[k]->dt_avg = 0.0; lev[k]->time_average(dt_level[0], 0); }
 }
 
 // NavierStokesBase::computeNewDt (NavierStokesBase.cpp:945-1035); post_regrid: limited by the pre-regrid dt instead of change_max x dt
@@ -1449,7 +1481,6 @@ double AmrNS::coarse_step()
     if ((int)level_count_v.size() < rg.max_level + 1) level_count_v.resize(rg.max_level + 1, 0);
     if (!level_count_v.empty()) level_count_v[0] = level_count;      // level_count: the value checkpoints carry (Amr::level_count[0])
     time_step(0, lev[0]->time, 1, 1);
-    level_steps += 1;
     level_count = level_count_v.empty() ? level_count + 1 : level_count_v[0];
     for (size_t i = 0; i < lev.size(); ++i) lev[i]->dt = dt_level[i];
     return dt_level[0];

@@ -324,6 +324,19 @@ bool AmrNS::install_grids(const std::vector<std::vector<BoxD>>& grids, int lbase
         if (ol) parallel_copy(s.P[0], ol->P[ol->pnew], 0, 0, 1, 0, 0, &s.g);
         MultiFab::Copy(s.P[1], s.P[0], 0, 0, 1, 1);
         s.make_rho_curr_time();
+        // ---- time averages (NavierStokesBase::init(old), NavierStokesBase.cpp:1734-1737: FillPatch of Average_Type): the old level's
+        // accumulators where it existed, cell_cons_interp of the level below elsewhere.  A level that did not exist before takes the
+        // interpolant and the three scalars of the level below -- upstream's init() (:1759-1806) fills neither.
+        // Average_Type has int_dir on every face (average_bc, NS_BC.H:52-55), which leaves the coarse values beyond a wall undefined;
+        // first-order extrapolation there defines them.
+        if (s.has_average()) {
+            BCRec abc[6];
+            for (int n = 0; n < 6; ++n) for (int d = 0; d < 3; ++d) abc[n].lo[d] = abc[n].hi[d] = s.g.periodic[d] ? (int)bc_int_dir : (int)bc_foextrap;
+            sync_interp_cellcons(s.Savg, 0, c.Savg, 0, 6, c.g, s.g, m_ratio, abc);
+            if (ol) parallel_copy(s.Savg, ol->Savg, 0, 0, 6, 0, 0, &s.g);
+            const NavierStokes& from = ol ? *ol : c;
+            s.time_avg = from.time_avg; s.time_avg_fluct = from.time_avg_fluct; s.dt_avg = from.dt_avg;
+        }
     }
     // the replaced levels: drop what the layout-keyed caches hold for them (a cached level mask keeps its layout alive otherwise)
     ProfScope ps_drop_("ri_drop_old");

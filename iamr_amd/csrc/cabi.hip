@@ -896,6 +896,7 @@ void iamrx_ns_default_params(iamrx_ns_params* p)
     p->do_denminmax = d.do_denminmax; p->do_scalminmax = d.do_scalminmax;
     p->do_trac2 = d.do_trac2; p->do_cons_trac2 = d.do_cons_trac2; p->tracer2_diff_coef = d.tracer2_diff_coef; p->do_temp = d.do_temp; p->temp_cond_coef = d.temp_cond_coef;
     p->use_ppm = d.use_ppm;
+    p->avg_interval = d.avg_interval; p->compute_fluctuations = d.compute_fluctuations; p->sum_interval = d.sum_interval;
 }
 
 static NSParams to_params(const iamrx_ns_params* p)
@@ -914,6 +915,8 @@ static NSParams to_params(const iamrx_ns_params* p)
     q.do_denminmax = p->do_denminmax; q.do_scalminmax = p->do_scalminmax;
     q.do_trac2 = p->do_trac2; q.do_cons_trac2 = p->do_cons_trac2; q.tracer2_diff_coef = p->tracer2_diff_coef; q.do_temp = p->do_temp; q.temp_cond_coef = p->temp_cond_coef;
     q.use_ppm = p->use_ppm;
+    q.avg_interval = p->avg_interval; q.compute_fluctuations = p->compute_fluctuations; q.sum_interval = p->sum_interval;
+    if (q.avg_interval < 0) throw Error("iamrx_ns_params: avg_interval must be >= 0");
     return q;
 }
 
@@ -974,6 +977,7 @@ int iamrx_ns_data(iamrx_ns ns, int which, iamrx_mf* out)
     case 6: case 7: case 8: m = &n.umac(which - 6); break;
     case 9: m = &n.Aofs(); break;
     case 10: case 11: m = &n.mac_phi_history(which - 10); break;
+    case 12: m = &n.average_data(); break;
     default: throw Error("iamrx_ns_data: bad selector");
     }
     // copy the current contents into a library-owned MultiFab of the same shape (old/new swap every step,
@@ -990,16 +994,30 @@ int iamrx_ns_derive(iamrx_ns ns, const char* name, iamrx_mf out, int ocomp)
 {
     IAMRX_TRY
     NavierStokes& n = *ns->ns;
+    const int nc = std::string(name) == "velocity_average" ? 6 : 1;      // der_vel_avg: mean and rms of the three velocities
+    if (ocomp < 0 || ocomp + nc > out->mf.ncomp) throw Error("iamrx_ns_derive: out has too few components for '" + std::string(name) + "'");
     if (out->mf.layout->id == n.lay()->id) n.derive(name, out->mf, ocomp);
     else {
         IAMRX_ASSERT(out->mf.layout->id == n.user_layout->id && out->mf.type.cell());
-        MultiFab t(n.lay(), cell_type(), 1, 0), u(n.user_layout, cell_type(), 1, 0);
+        MultiFab t(n.lay(), cell_type(), nc, 0), u(n.user_layout, cell_type(), nc, 0);
         n.derive(name, t, 0);
-        relayout_copy(u, t, 1);
-        MultiFab::Copy(out->mf, u, 0, ocomp, 1, 0);
+        relayout_copy(u, t, nc);
+        MultiFab::Copy(out->mf, u, 0, ocomp, nc, 0);
     }
     IAMRX_CATCH
 }
+
+int iamrx_ns_time_average(iamrx_ns ns, double dt_level, int level0_steps) { IAMRX_TRY ns->ns->time_average(dt_level, level0_steps); IAMRX_CATCH }
+int iamrx_ns_average_state(iamrx_ns ns, int set, double v[3])
+{
+    IAMRX_TRY
+    NavierStokes& n = *ns->ns;
+    if (!n.has_average()) throw Error("iamrx_ns_average_state: the level keeps no time averages (avg_interval = 0)");
+    if (set) { n.time_avg = v[0]; n.time_avg_fluct = v[1]; n.dt_avg = v[2]; }
+    else { v[0] = n.time_avg; v[1] = n.time_avg_fluct; v[2] = n.dt_avg; }
+    IAMRX_CATCH
+}
+int iamrx_ns_sum_integrated(iamrx_ns ns, double sums[3]) { IAMRX_TRY ns->ns->sum_integrated(nullptr, sums); IAMRX_CATCH }
 
 int iamrx_ns_set_data(iamrx_ns ns, int which, iamrx_mf src)
 {
@@ -1014,6 +1032,7 @@ int iamrx_ns_set_data(iamrx_ns ns, int which, iamrx_mf src)
     case 4: m = &n.get_new_data(2); break;
     case 5: m = &n.get_old_data(2); break;
     case 10: case 11: m = &n.mac_phi_history(which - 10); break;
+    case 12: m = &n.average_data(); break;
     default: throw Error("iamrx_ns_set_data: bad selector");
     }
     // fewer components than the level holds: the leading ones (the state without the divu / dsdt components a temperature run appends)
@@ -1417,6 +1436,15 @@ int iamrx_amr_coarse_step(iamrx_amr a, double* dt0)
     const double d = a->amr->coarse_step();
     if (a->amr->grid_generation() != before) amr_refresh_levels(a);      // the step regridded
     if (dt0) *dt0 = d;
+    IAMRX_CATCH
+}
+int iamrx_amr_sum_integrated(iamrx_amr a, double sums[3]) { IAMRX_TRY a->amr->sum_integrated_quantities(sums); IAMRX_CATCH }
+int iamrx_amr_last_sum(iamrx_amr a, int* step, double* time, double sums[3])
+{
+    IAMRX_TRY
+    *step = a->amr->last_sum_step;
+    if (time) *time = a->amr->last_sum_time;
+    for (int q = 0; q < 3; ++q) sums[q] = a->amr->last_sum[q];
     IAMRX_CATCH
 }
 int iamrx_amr_time(iamrx_amr a, double* time, double* dt_levels)

@@ -454,6 +454,53 @@ double reduce_sum_unique(const MultiFab& mf, int comp, const Geometry& g, bool g
     return finish_to_host(0, 1, np, global);
 }
 
+// NavierStokes::sum_integrated_quantities (NavierStokes.cpp:1046-1079): the three sums of one level in ONE pass over its state -- mass
+// (volWgtSum "density"), tracer (volWgtSum "tracer") and kinetic energy (volWgtSum "energy" = derkeng, NS_derive.cpp:266-295) -- over the
+// cells the finer level does not cover (MASK: cov != 0 there; such a cell is skipped, not multiplied by zero, so what it holds cannot
+// reach the sums).  A NaN in a counted cell makes its sum NaN.  partials[q * np + block]; the caller applies the cell volume.
+template <bool MASK>
+__global__ void __launch_bounds__(256) k_sum_integrated(Tiling t, const BoxD* __restrict__ boxes, const FabD* __restrict__ st, const FabD* __restrict__ cov,
+                                                        int rho_comp, int trac_comp, double* __restrict__ partials, int np)
+{
+    const int fab = tile_fab(t);
+    const BoxD b = boxes[fab];
+    int i, j, k0, k1;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    if (tile_ijk(t, b, i, j, k0, k1)) {
+        const FabD s = st[fab];
+        for (int k = k0; k <= k1; ++k) {
+            if (MASK && cov[fab](i, j, k) != 0.0) continue;
+            const double u = s(i, j, k, 0), v = s(i, j, k, 1), w = s(i, j, k, 2), r = s(i, j, k, rho_comp), q = s(i, j, k, trac_comp);
+            s0 += r; s1 += q; s2 += 0.5 * r * (u * u + v * v + w * w);
+        }
+    }
+    const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    s0 = block_reduce<0>(s0);
+    if (threadIdx.x == 0) partials[slot] = s0;
+    s1 = block_reduce<0>(s1);
+    if (threadIdx.x == 0) partials[(size_t)np + slot] = s1;
+    s2 = block_reduce<0>(s2);
+    if (threadIdx.x == 0) partials[2 * (size_t)np + slot] = s2;
+}
+
+// out[0..3) = sum rho, sum tracer, sum rho |u|^2 / 2 over the valid cells of THIS RANK's boxes (cov: cells with cov != 0 left out; null:
+// none).  Two stages like every sum here (block partials in a fixed order, then one block over them): the same call gives the same bits.
+void reduce_sum_integrated(const MultiFab& S, int rho_comp, int trac_comp, const MultiFab* cov, double out[3])
+{
+    IAMRX_ASSERT(S.type.cell() && (!cov || (cov->type.cell() && cov->layout->id == S.layout->id)));
+    out[0] = out[1] = out[2] = 0.0;
+    if (S.nlocal() == 0) return;
+    auto& ctx = Context::get();
+    Tiling t = level_tiling(*S.layout, S.type, 0, 8, true);
+    dim3 g = t.grid();
+    const int np = (int)(g.x * g.y);
+    ctx.ensure_scratch((size_t)3 * np + 16);
+    if (cov) hipLaunchKernelGGL((k_sum_integrated<true>), g, Tiling::block(), 0, ctx.stream, t, S.layout->d_boxes, S.d_tab, cov->d_tab, rho_comp, trac_comp, ctx.d_scratch, np);
+    else hipLaunchKernelGGL((k_sum_integrated<false>), g, Tiling::block(), 0, ctx.stream, t, S.layout->d_boxes, S.d_tab, (const FabD*)nullptr, rho_comp, trac_comp, ctx.d_scratch, np);
+    finish_to_host(0, 3, np, false);
+    for (int q = 0; q < 3; ++q) out[q] = ctx.h_scratch[q];
+}
+
 // ------------------------------------------------------------------ BLAS-1 style
 void mf_lincomb(MultiFab& dst, double a, const MultiFab& x, double b, const MultiFab& y, int comp, int nc, int ng)
 {

@@ -19,6 +19,8 @@ double reduce_norm0(const MultiFab& mf, int comp, int nc, int ng, bool global = 
 void reduce_norm0_comps(const MultiFab& mf, int comp, int nc, int ng, double* out, bool global = false);   // per-component maxima, one read-back
 void reduce_minmax(const MultiFab& mf, int comp, int ng, double& mn, double& mx, bool global = true);   // one pass, one read-back
 double reduce_sum_unique(const MultiFab& mf, int comp, const Geometry& g, bool global = false);   // sum over owner copies
+// this rank's sums of density, tracer and kinetic energy over the valid cells where cov (may be null) is zero: one pass over the state
+void reduce_sum_integrated(const MultiFab& S, int rho_comp, int trac_comp, const MultiFab* cov, double out[3]);
 // nout simultaneous dot products over the valid region, owner-masked for nodal data: out[q] = <x_q, y_q>
 void reduce_dots(int nout, const MultiFab* const* x, const MultiFab* const* y, int comp, int nc, const Geometry& g, double* out, bool local = false);
 // ... with the results left on the device (no read-back): krylov.h
@@ -38,6 +40,12 @@ void mf_lincomb(MultiFab& dst, double a, const MultiFab& x, double b, const Mult
 void mf_saxpy(MultiFab& y, double a, const MultiFab& x, int xcomp, int ycomp, int nc, int ng);                          // y += a*x
 void mf_add_scalar(MultiFab& y, double a, int comp, int nc, int ng);
 void mf_mult(MultiFab& y, double a, int comp, int nc, int ng);
+
+// ---- k_stats.hip: on-the-fly velocity statistics (NS_average.cpp, NS_derive.cpp:11-45) ------
+// avg(0..2) += dt_avg * vel; fluct: avg(3..5) += dt_avg * (vel - avg(0..2) / t_sum)^2 with the updated avg(0..2); vel = S(vcomp..)
+void stats_accumulate(MultiFab& avg, const MultiFab& S, int vcomp, double dt_avg, double t_sum, bool fluct);
+// out(ocomp..ocomp+2) = avg(0..2) / t_mean, out(ocomp+3..ocomp+5) = sqrt(avg(3..5) / t_fluct); a zero divisor counts as 1
+void stats_derive_vel_avg(MultiFab& out, int ocomp, const MultiFab& avg, double t_mean, double t_fluct);
 
 struct DomainBC;
 // ---- k_bc.hip -----------------------------------------------------------------------------

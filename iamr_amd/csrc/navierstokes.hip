@@ -83,6 +83,7 @@ NavierStokes::NavierStokes(const Geometry& geom, LayoutP lay, const NSParams& pa
         for (int n = 1; n < nscal; ++n) if (scal_diff[n] > 0.0) { diff_b[n][d].define(layout, face_type(d), 1, 0); diff_b[n][d].setVal(scal_diff[n]); diff_b[n][d].mark_uniform(scal_diff[n]); }
     }
     aofs.define(layout, cell_type(), nstate, 0);
+    if (p.avg_interval > 0) { Savg.define(layout, cell_type(), 6, 0); Savg.setVal(0.0); }     // Average_Type, NS_setup.cpp:389-405
     mac_phi.define(layout, cell_type(), 1, 1);
     mac_phi.setVal(0.0);
     rho_ptime.define(layout, cell_type(), 1, 1);
@@ -278,7 +279,34 @@ void NavierStokes::derive(const std::string& name, MultiFab& out, int ocomp)
             ot[f](i, j, k, ocomp) = 0.125 * (p(i + 1, j, k) + p(i, j, k) + p(i + 1, j + 1, k) + p(i, j + 1, k)
                                            + p(i + 1, j, k + 1) + p(i, j, k + 1) + p(i + 1, j + 1, k + 1) + p(i, j + 1, k + 1));
         });
-    } else throw Error("NavierStokes::derive: unknown derived quantity '" + name + "' (energy, mag_vort, avg_pressure)");
+    } else if (name == "velocity_average" && has_average()) {  // der_vel_avg, NS_derive.cpp:11-45: 6 components
+        IAMRX_ASSERT(ocomp + 6 <= out.ncomp);
+        stats_derive_vel_avg(out, ocomp, Savg, time_avg, time_avg_fluct);
+    } else throw Error("NavierStokes::derive: unknown derived quantity '" + name + "' (energy, mag_vort, avg_pressure" + (has_average() ? ", velocity_average)" : ")"));
+}
+
+// NavierStokesBase::time_average (NS_average.cpp:19-69), statement by statement
+void NavierStokes::time_average(double dt_level, int level0_steps)
+{
+    if (!has_average()) return;
+    dt_avg = dt_avg + dt_level;
+    if (level0_steps % p.avg_interval != 0) return;
+    const bool fluct = p.compute_fluctuations == 1;
+    stats_accumulate(Savg, S[inew], Xvel, dt_avg, time_avg + dt_avg, fluct);
+    time_avg = time_avg + dt_avg;
+    time_avg_fluct = fluct ? time_avg_fluct + dt_avg : 0.0;
+    dt_avg = 0.0;
+}
+
+// the level's share of NavierStokes::sum_integrated_quantities (NavierStokes.cpp:1046-1079; amrex volumeWeightedSum: the cells under the
+// finer level do not count, the weight is the cell volume): one fused reduction (k_basic.hip), then one sum over the ranks
+void NavierStokes::sum_integrated(const MultiFab* fine_cov, double out[3])
+{
+    reduce_sum_integrated(S[inew], Density, Tracer, fine_cov, out);
+    const double vol = g.dx[0] * g.dx[1] * g.dx[2];
+    for (int q = 0; q < 3; ++q) out[q] *= vol;
+    auto& comm = Context::get().comm;
+    if (comm && comm->nranks > 1 && !layout->replicated) comm->allreduce(out, 3, ReduceOp::Sum);
 }
 
 void NavierStokes::fillpatch(MultiFab& dst, const MultiFab& src, int scomp, int ncomp, const BCRec* bc)

@@ -247,6 +247,9 @@ struct NSParams {
     int do_temp = 0;                     // ns.do_temp: temperature, the last state component (NavierStokes.cpp:47-48)
     double temp_cond_coef = 0.0;         // ns.temp_cond_coef
     int use_ppm = 0;                     // ns.advection_scheme: 0 Godunov_PLM, 1 Godunov_PPM (NavierStokesBase.cpp:548-553)
+    // ns.avg_interval / ns.compute_fluctuations (NS_average.cpp, NavierStokesBase.cpp:487-488): time averages of the velocity, sampled
+    // every avg_interval level-0 steps (0: off); ns.sum_interval (NavierStokesBase.cpp:452, 2589-2592): integrated quantities (<= 0: off)
+    int avg_interval = 0, compute_fluctuations = 0, sum_interval = 0;
 };
 
 enum StateComp { Xvel = 0, Yvel = 1, Zvel = 2, Density = 3, Tracer = 4, MAXSCAL = 4, MAXSTATE = 3 + MAXSCAL, MAXSLOT = MAXSCAL + 2 };   // Tracer2 / Temp: NavierStokes::Tracer2 / Temp (-1: absent)
@@ -272,12 +275,27 @@ public:
     double advance(double dt, int iteration, int ncycle);   // NavierStokes::advance(time, dt, iteration, ncycle); returns the dt estimate
     double estTimeStep();                      // NavierStokesBase::estTimeStep
     // derived quantities of the plotfile (derive_lst of NS_setup.cpp:436-449): "energy" = rho |u|^2 / 2 (derkeng), "mag_vort" = |curl u|
-    // (dermgvort, ghost cells by FillPatch), "avg_pressure" = mean of the 8 nodes of the cell (deravgpres); new-time data; out: cell, >= 1 comp
+    // (dermgvort, ghost cells by FillPatch), "avg_pressure" = mean of the 8 nodes of the cell (deravgpres); new-time data; out: cell, >= 1 comp;
+    // with avg_interval > 0 also "velocity_average" (der_vel_avg, NS_derive.cpp:11-45): 6 components, mean velocity and rms fluctuation
     void derive(const std::string& name, MultiFab& out, int ocomp = 0);
     MultiFab& get_new_data(int type) { return type == 0 ? S[inew] : (type == 1 ? P[pnew] : Gp[pnew]); }
     MultiFab& get_old_data(int type) { return type == 0 ? S[1 - inew] : (type == 1 ? P[1 - pnew] : Gp[1 - pnew]); }
     MultiFab& umac(int d) { return u_mac[d]; }
     MultiFab& Aofs() { return aofs; }
+    // ---- on-the-fly velocity statistics (Average_Type, NS_setup.cpp:389-405; defined only with avg_interval > 0): components 0..2 the
+    // time integral of u, v, w, 3..5 the time integral of the squared fluctuation; no ghost cells, on the level's working layout like the
+    // state, zero at initialisation.  The reference keeps an old and a new copy of this state type and writes both identically in
+    // time_average (NS_average.cpp:45-55); nothing ever reads them at different times, so ONE array is kept here.
+    // time_avg / time_avg_fluct / dt_avg: NavierStokesBase::time_avg[level] etc. (NavierStokesBase.cpp:2467-2522)
+    bool has_average() const { return p.avg_interval > 0; }
+    MultiFab& average_data() { if (!has_average()) throw Error("iamrx NavierStokes: no time averages (ns.avg_interval = 0)"); return Savg; }
+    double time_avg = 0.0, time_avg_fluct = 0.0, dt_avg = 0.0;
+    // NavierStokesBase::time_average (NS_average.cpp:19-69): dt_avg += dt_level; every avg_interval-th level-0 step the accumulation
+    // kernel (k_stats.hip), then the three scalars.  Nothing happens (no launch) with avg_interval = 0.
+    void time_average(double dt_level, int level0_steps);
+    // this level's part of NavierStokes::sum_integrated_quantities (NavierStokes.cpp:1046-1079): volume-weighted sums of density, tracer and
+    // kinetic energy over the cells where fine_cov (this level's layout; null: none) is zero, summed over the ranks
+    void sum_integrated(const MultiFab* fine_cov, double out[3]);
     double time = 0.0, dt = 0.0;
     int nstep = 0;
     MGStats st_mac, st_nodal, st_visc, st_scal;
@@ -366,7 +384,7 @@ private:
     LayoutP layout;
     NSParams p;
     MGOpts o;
-    MultiFab S[2], P[2], Gp[2];
+    MultiFab S[2], P[2], Gp[2], Savg;
     int inew = 0, pnew = 0;
     MultiFab u_mac[3], aofs, rho_ptime, rho_ctime, rho_half;
     MultiFab eta[3];

@@ -7,7 +7,7 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   amr.n_cell, amr.max_level (must be 0), amr.max_grid_size (32), geometry.prob_lo / prob_hi / is_periodic / coord_sys (0),
   ns.cfl, ns.init_iter, ns.init_vel_iter, ns.init_shrink, ns.change_max, ns.fixed_dt, ns.init_dt, ns.gravity,
   ns.be_cn_theta, ns.do_mom_diff, ns.do_cons_trac, ns.vel_visc_coef, ns.scal_diff_coefs, ns.lo_bc, ns.hi_bc, ns.advection_scheme,
-  ns.visc_tol, godunov.use_forces_in_trans, mac_proj.mac_tol / mac_abs_tol, proj.proj_tol / proj_abs_tol,
+  ns.visc_tol, ns.avg_interval, ns.compute_fluctuations, ns.avg_in_checkpoint, ns.sum_interval, godunov.use_forces_in_trans, mac_proj.mac_tol / mac_abs_tol, proj.proj_tol / proj_abs_tol,
   {x,y,z}{lo,hi}.velocity / .density / .tracer, prob.probtype (1: fluid at rest, 4: constant velocity + blob, 5: DoubleShearLayer, 7: Euler, 10: RayleighTaylor, 11: TaylorGreen), prob.velocity_factor, prob.a/b/c,
   prob.density_ic, prob.rho_1 / rho_2 / tra_1 / tra_2 / interface_width / perturbation_amplitude (probtype 10), max_step, stop_time
 (reference: Source/NavierStokesBase.cpp:431-557, Source/NavierStokes.cpp:250-310, Source/MacProj.cpp:62-75,
@@ -20,7 +20,7 @@ import re
 # I/O, verbosity and grid-generation keys that do not change the numbers of a fixed-grid run: matched EXACTLY or, for the entries
 # ending in ".", as a prefix of a whole ParmParse namespace
 _IGNORED_KEYS = ("amr.v", "amr.verbose", "ns.v", "ns.verbose", "proj.v", "proj.verbose", "mac_proj.v", "mac_proj.verbose", "mac.v", "diffuse.v",
-                 "diffuse.verbose", "nodal_proj.verbose", "ns.sum_interval", "ns.getForceVerbose", "amr.grid_log", "amr.probin_file",
+                 "diffuse.verbose", "nodal_proj.verbose", "ns.getForceVerbose", "amr.grid_log", "amr.probin_file",
                  "amr.blocking_factor", "amr.regrid_int", "amr.ref_ratio", "amr.regrid_file", "amr.initial_grid_file", "amr.refinement_indicators", "amr.n_error_buf", "amr.grid_eff",
                  "amr.check_per", "amr.checkpoint_files_output", "amr.plot_files_output", "amr.plot_per",
                  "amr.plotfile_on_restart", "amr.checkpoint_on_restart")
@@ -375,6 +375,16 @@ class Inputs:
                     if sname not in snames and self.has(f"{name}{side}.{sname}"):
                         self.real(f"{name}{side}.{sname}", 0.0)
         p["scal_bc_lo"], p["scal_bc_hi"] = slo, shi
+        # on-the-fly velocity statistics and integrated quantities (NavierStokesBase.cpp:452, 487-488, 539; defaults :109, 151-152)
+        p["avg_interval"] = self.integer("ns.avg_interval", 0)
+        p["compute_fluctuations"] = self.integer("ns.compute_fluctuations", 0)
+        p["avg_in_checkpoint"] = self.integer("ns.avg_in_checkpoint", 1)
+        p["sum_interval"] = self.integer("ns.sum_interval", -1)
+        if p["avg_interval"] < 0:
+            raise ValueError(f"inputs: ns.avg_interval = {p['avg_interval']} must be >= 0")
+        if slab and p["avg_interval"] > 0:
+            raise NotImplementedError("inputs: ns.avg_interval > 0 in a two-dimensional run: the slab's plane extraction handles "
+                                      "single-component derived fields only, so velocity_average could not be written")
         probtype = self.integer("prob.probtype")
         if probtype == 1:
             prob = dict(probtype=1, rho0=1.0)

@@ -14,12 +14,16 @@ class NsParams(C.Structure):
                 ("init_dt", C.c_double), ("tracer_diff_coef", C.c_double), ("phys_lo", C.c_int * 3), ("phys_hi", C.c_int * 3),
                 ("wall_vel_lo", C.c_double * 9), ("wall_vel_hi", C.c_double * 9),
                 ("scal_bc_lo", C.c_double * 12), ("scal_bc_hi", C.c_double * 12), ("do_cons_trac", C.c_int), ("do_denminmax", C.c_int), ("do_scalminmax", C.c_int),
-                ("do_trac2", C.c_int), ("do_cons_trac2", C.c_int), ("tracer2_diff_coef", C.c_double), ("do_temp", C.c_int), ("temp_cond_coef", C.c_double), ("use_ppm", C.c_int)]
+                ("do_trac2", C.c_int), ("do_cons_trac2", C.c_int), ("tracer2_diff_coef", C.c_double), ("do_temp", C.c_int), ("temp_cond_coef", C.c_double), ("use_ppm", C.c_int),
+                ("avg_interval", C.c_int), ("compute_fluctuations", C.c_int), ("sum_interval", C.c_int)]
 
 
 def ns_params(**kw):
     p = NsParams()
     lib().iamrx_ns_default_params(C.byref(p))
+    # ns.avg_in_checkpoint (NavierStokesBase.cpp:539) only steers amr.restart (checkpoint.restart): it travels with the parameters as a
+    # plain attribute, the library's struct does not hold it
+    p.avg_in_checkpoint = int(kw.pop("avg_in_checkpoint", 1))
     for k, v in kw.items():
         if k in ("phys_lo", "phys_hi"):
             setattr(p, k, (C.c_int * 3)(*[int(x) for x in v]))
@@ -129,8 +133,11 @@ def tensor_solve_cf(geom, soln, rhs, a, b, acoef, eta, crse_vel, cgeom, ratio=2,
 class NavierStokes:
     """level object with the reference's method names (NavierStokes::advance, post_init, ...)"""
     S_NEW, S_OLD, P_NEW, P_OLD, GP_NEW, GP_OLD, UMAC_X, UMAC_Y, UMAC_Z, AOFS = range(10)
+    AVERAGE = 12          # the time-average accumulators (Average_Type, NS_setup.cpp:389-405): 6 components, no ghost cells
+    VEL_AVG_NAMES = ["x_vel_average", "y_vel_average", "z_vel_average", "x_vel_rms", "y_vel_rms", "z_vel_rms"]   # NS_setup.cpp:417-427
     _types = {0: ((0, 0, 0), 5, 1), 1: ((0, 0, 0), 5, 1), 2: ((1, 1, 1), 1, 1), 3: ((1, 1, 1), 1, 1), 4: ((0, 0, 0), 3, 1),
-              5: ((0, 0, 0), 3, 1), 6: ((1, 0, 0), 1, 1), 7: ((0, 1, 0), 1, 1), 8: ((0, 0, 1), 1, 1), 9: ((0, 0, 0), 5, 0)}
+              5: ((0, 0, 0), 3, 1), 6: ((1, 0, 0), 1, 1), 7: ((0, 1, 0), 1, 1), 8: ((0, 0, 1), 1, 1), 9: ((0, 0, 0), 5, 0),
+              12: ((0, 0, 0), 6, 0)}
 
     def __init__(self, geom, layout, params=None, opts=None):
         self.geom = geom
@@ -187,11 +194,34 @@ class NavierStokes:
         return MultiFab(self.layout, typ, nc, ng, _handle=h, _owned=True)
 
     def derive(self, name):
-        """derived quantity of the plotfile ("energy", "mag_vort", "avg_pressure": NavierStokes::derive) as a one-component cell MultiFab"""
+        """derived quantity of the plotfile ("energy", "mag_vort", "avg_pressure": NavierStokes::derive) as a one-component cell MultiFab;
+        "velocity_average" (only with avg_interval > 0; der_vel_avg, NS_derive.cpp:11-45) has the six components VEL_AVG_NAMES"""
         from .lib import MultiFab, CELL
-        out = MultiFab(self.layout, CELL, 1, 0)
+        out = MultiFab(self.layout, CELL, 6 if name == "velocity_average" else 1, 0)
         check(lib().iamrx_ns_derive(self.h, name.encode(), out.h, 0))
         return out
+
+    def time_average(self, dt_level, level0_steps):
+        """NavierStokesBase::time_average (NS_average.cpp:19-69); a hierarchy calls it itself, the driver of a single level after post_init
+        and after every step"""
+        check(lib().iamrx_ns_time_average(self.h, C.c_double(dt_level), int(level0_steps)))
+
+    @property
+    def average_state(self):
+        """(time_avg, time_avg_fluct, dt_avg) of the level"""
+        v = (C.c_double * 3)()
+        check(lib().iamrx_ns_average_state(self.h, 0, v))
+        return tuple(v)
+
+    @average_state.setter
+    def average_state(self, v):
+        check(lib().iamrx_ns_average_state(self.h, 1, (C.c_double * 3)(*[float(x) for x in v])))
+
+    def sum_integrated(self):
+        """(mass, tracer, kinetic energy) integrated over ALL cells of this level (NavierStokes::sum_integrated_quantities, one level)"""
+        v = (C.c_double * 3)()
+        check(lib().iamrx_ns_sum_integrated(self.h, v))
+        return tuple(v)
 
     @property
     def nstate(self):

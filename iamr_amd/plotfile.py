@@ -348,10 +348,20 @@ def state_names(do_trac2=0, do_temp=0):
 DERIVE_NAMES = ["energy", "mag_vort", "avg_pressure"]          # derive_lst order (NS_setup.cpp:436-449; no particles, no time averages)
 
 
-def plot_selection(state, plot_vars="ALL", derive_plot_vars="NONE"):
+# "velocity_average" (NS_setup.cpp:412-431): one derived quantity of six plotfile components; declared only with ns.avg_interval > 0, and
+# then in front of "energy"
+VEL_AVG_NAMES = ["x_vel_average", "y_vel_average", "z_vel_average", "x_vel_rms", "y_vel_rms", "z_vel_rms"]
+
+
+def plot_selection(state, plot_vars="ALL", derive_plot_vars="NONE", averaging=False):
     """(indices of the state components, names of the derived quantities) a plotfile holds: amr.plot_vars picks state variables (ALL: every
     one), amr.derive_plot_vars derived ones (ALL: the derive list in its order; default NONE) -- Amr::initPltAndChk / fillDerivePlotVarList.
-    Unknown names raise, as amrex::Amr aborts on them."""
+    Unknown names raise, as amrex::Amr aborts on them.  averaging (ns.avg_interval > 0): "velocity_average" exists, first in the derive
+    list; it is returned as its six component names VEL_AVG_NAMES (run.level_arrays derives them together)."""
+    known = (["velocity_average"] if averaging else []) + DERIVE_NAMES
+
+    def expand(names):
+        return [c for nm in names for c in (VEL_AVG_NAMES if nm == "velocity_average" else [nm])]
     if plot_vars == "ALL":
         keep = list(range(len(state)))
     elif plot_vars == "NONE":
@@ -362,14 +372,14 @@ def plot_selection(state, plot_vars="ALL", derive_plot_vars="NONE"):
             raise ValueError(f"amr.plot_vars: not state variables: {bad} (have {state})")
         keep = [q for q, nm in enumerate(state) if nm in plot_vars]           # plotfile order = state order (Amr::statePlotVars is a list filled in descriptor order)
     if derive_plot_vars == "ALL":
-        der = list(DERIVE_NAMES)
+        der = expand(known)
     elif derive_plot_vars == "NONE":
         der = []
     else:
-        bad = [v for v in derive_plot_vars if v not in DERIVE_NAMES]
+        bad = [v for v in derive_plot_vars if v not in known]
         if bad:
-            raise ValueError(f"amr.derive_plot_vars: unknown derived quantities {bad} (have {DERIVE_NAMES})")
-        der = list(derive_plot_vars)
+            raise ValueError(f"amr.derive_plot_vars: unknown derived quantities {bad} (have {known})")
+        der = expand(derive_plot_vars)
     return keep, der
 
 

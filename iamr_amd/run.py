@@ -63,7 +63,9 @@ def level_arrays(ns, lay, N, derived=()):
     every rank calls this, also one that owns nothing)"""
     import numpy as np
     S = ns.data(N.NavierStokes.S_NEW)
-    D = [ns.derive(name) for name in derived]
+    # the six names of "velocity_average" (plotfile.plot_selection) are ONE derived quantity of six components
+    va = N.NavierStokes.VEL_AVG_NAMES
+    D = [ns.derive("velocity_average" if name == va[0] else name) for name in derived if name not in va[1:]]
     boxes, arrs = [], []
     for li in range(S.nlocal()):
         a, lo = S.to_numpy(li)
@@ -83,7 +85,7 @@ def plot_names_and_filter(pr):
     pv = pr.get("plot_vars", "ALL")
     if pr.get("slab") and isinstance(pv, list):          # a 2-D inputs file names the plane's velocities x_velocity, y_velocity: y is the slab's z
         pv = ["z_velocity" if v == "y_velocity" else v for v in pv]
-    keep, der = plot_selection(state, pv, pr.get("derive_plot_vars", "NONE"))
+    keep, der = plot_selection(state, pv, pr.get("derive_plot_vars", "NONE"), averaging=pr["params"].get("avg_interval", 0) > 0)
     kept = {state[q] for q in keep} | set(der)
     return state + der, der, kept
 
@@ -110,6 +112,21 @@ def _plane(boxes, arrs, names):
     n2 = ["x_velocity", "y_velocity"] + list(names[3:])
     return ([((boxes[q][0][0], boxes[q][0][2]), (boxes[q][1][0], boxes[q][1][2])) for q in keep],
             [arrs[q][:, 0, :, :][..., comps].copy() for q in keep], n2)
+
+
+def sum_lines(time, sums, pr=None):
+    """the three lines of NavierStokes::sum_integrated_quantities (NavierStokes.cpp:1075-1078; 12 significant digits) for (mass, tracer,
+    kinetic energy).  A two-dimensional run on its slab reports the plane integrals: the sums divided by the slab's thickness."""
+    if pr is not None and pr.get("slab"):
+        thick = pr["prob_hi"][1] - pr["prob_lo"][1]
+        sums = [v / thick for v in sums]
+    return [f"TIME= {time:.12g} {name}= {v:.12g}" for name, v in zip(("MASS", "TRAC", "KINETIC ENERGY"), sums)]
+
+
+def say_sums(say, time, sums, pr):
+    say("")
+    for line in sum_lines(time, sums, pr):
+        say(line)
 
 
 def enforce_plane(levels, pr):
@@ -168,9 +185,9 @@ def write_plot_amr(amr, lays, pr, N, step, root):
     return path
 
 
-def main_amr(pr, inp, lib, N, rank=0, world=1):
+def main_amr(pr, inp, lib, N, rank=0, world=1, observe=None):
     """hierarchy run; world > 1: the boxes of every level are spread over the ranks (level 0 by Layout.decompose, fixed refined grids
-    round-robin, regridded levels by the library's knapsack, restarted levels as checkpoint.restart says)"""
+    round-robin, regridded levels by the library's knapsack, restarted levels as checkpoint.restart says); observe: see main"""
     say = print if rank == 0 else (lambda *a, **k: None)
     check_int, check_root = pr.get("check_int", -1), pr.get("check_file", "chk")
     plot_int, plot_root = pr.get("plot_int", -1), pr.get("plot_file", "plt")
@@ -188,6 +205,10 @@ def main_amr(pr, inp, lib, N, rank=0, world=1):
         amr, lays, g0 = build_amr(pr, lib, N, world)
         amr.post_init(pr["stop_time"])
         step = 0
+        if amr.last_sum() is not None:          # ns.sum_interval > 0: the hierarchy summed its initial data (NavierStokes.cpp:1284-1285)
+            say_sums(say, amr.last_sum()[1], amr.last_sum()[2], pr)
+        if observe:
+            observe(amr, 0, None)
         if plot_int > 0:
             say("PLOTFILE:", write_plot_amr(amr, lays, pr, N, 0, plot_root))
     if inp.ignored:
@@ -202,6 +223,11 @@ def main_amr(pr, inp, lib, N, rank=0, world=1):
         lays = amr.layouts                      # a regrid during the step replaces them
         step += 1
         say(f"STEP = {step} TIME = {amr.time:.12g} DT = {dt:.12g} LEVELS = {amr.nlev} GRIDS = {[len(l.boxes) for l in lays]}")
+        ls = amr.last_sum()                     # level 0's post_timestep summed in this step (NavierStokesBase.cpp:2589-2592)
+        if ls is not None and ls[0] == step:    # (a slab was flattened after the step: what is reported is what is kept)
+            say_sums(say, ls[1], amr.sum_integrated() if pr.get("slab") else ls[2], pr)
+        if observe:
+            observe(amr, step, dt)
         if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports
             say("PLOTFILE:", write_plot_amr(amr, lays, pr, N, step, plot_root))
         if check_int > 0 and step % check_int == 0:
@@ -254,7 +280,9 @@ def write_plot(ns, lay, pr, N, step, root):
     return path
 
 
-def main(argv):
+def main(argv, observe=None):
+    """observe (optional): called as observe(run, step, dt) with the level or the hierarchy once the initial data are in place (step 0, dt
+    None; not after a restart) and after every coarse step -- for callers that follow a run from inside its own loop"""
     from .inputs import Inputs
     files = [a for a in argv if "=" not in a]
     over = [a for a in argv if "=" in a]
@@ -293,13 +321,14 @@ def main(argv):
         raise NotImplementedError("iamr_amd.run: two-dimensional inputs (run on a y-periodic slab) are single-rank runs")
     say = print if rank == 0 else (lambda *a, **k: None)
     if pr["fine_boxes"] or pr.get("regrid") or (pr.get("restart") and pr.get("max_level", 0) > 0):
-        rc = main_amr(pr, inp, lib, N, rank, world)
+        rc = main_amr(pr, inp, lib, N, rank, world, observe)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
         return rc
     plot_int, plot_root = pr.get("plot_int", -1), pr.get("plot_file", "plt")
     check_int, check_root = pr.get("check_int", -1), pr.get("check_file", "chk")
+    sum_int, avg_int = pr["params"].get("sum_interval", -1), pr["params"].get("avg_interval", 0)
     if pr.get("restart"):
         from . import checkpoint
         g = lib.Geom.make(pr["n"], prob_lo=pr["prob_lo"], prob_hi=pr["prob_hi"], periodic=pr["periodic"])
@@ -311,6 +340,13 @@ def main(argv):
         ns, lay, g, pr = build(inp, lib, N, world, pr)
         ns.post_init(pr["stop_time"])
         step = 0
+        # NavierStokes::post_init, NavierStokes.cpp:1284-1297: the sums of the initial data, which are also the first sample of the averages
+        if sum_int > 0:
+            say_sums(say, ns.time, ns.sum_integrated(), pr)
+        if avg_int > 0:
+            ns.time_average(ns.dt, 0)
+        if observe:
+            observe(ns, 0, None)
         if plot_int > 0:
             say("PLOTFILE:", write_plot(ns, lay, pr, N, 0, plot_root))
     if rank == 0 and inp.ignored:
@@ -325,6 +361,13 @@ def main(argv):
         step += 1
         if rank == 0:
             print(f"STEP = {step} TIME = {ns.time:.12g} DT = {dt:.12g}")
+        # NavierStokesBase::post_timestep on the one level (NavierStokesBase.cpp:2589-2592, 2630-2634)
+        if sum_int > 0 and step % sum_int == 0:
+            say_sums(say, ns.time, ns.sum_integrated(), pr)
+        if avg_int > 0:
+            ns.time_average(dt, step)
+        if observe:
+            observe(ns, step, dt)
         if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports
             say("PLOTFILE:", write_plot(ns, lay, pr, N, step, plot_root))
         if check_int > 0 and step % check_int == 0:

@@ -448,6 +448,9 @@ typedef struct iamrx_ns_params {
     int do_temp;                 /* ns.do_temp: temperature as the last state component (Source/NavierStokes.cpp:47-48; temp_bc, RhoInverse_Laplacian_S) */
     double temp_cond_coef;       /* ns.temp_cond_coef */
     int use_ppm;                 /* ns.advection_scheme: 0 = Godunov_PLM, 1 = Godunov_PPM, 2 = BDS (Source/NavierStokesBase.cpp:548-553, 4654-4656) */
+    int avg_interval;            /* ns.avg_interval (Source/NavierStokesBase.cpp:487, Source/NS_average.cpp:8-17): > 0: time averages of the velocity, a sample every avg_interval level-0 steps; 0: off */
+    int compute_fluctuations;    /* ns.compute_fluctuations (Source/NavierStokesBase.cpp:488): 1 = also the time integral of the squared velocity fluctuation */
+    int sum_interval;            /* ns.sum_interval (Source/NavierStokesBase.cpp:452, 2589-2592): > 0: a hierarchy forms its integrated quantities every sum_interval level-0 steps; <= 0: off */
 } iamrx_ns_params;
 void iamrx_ns_default_params(iamrx_ns_params* p);     /* defaults of Source/NavierStokesBase.cpp:96-170 */
 int iamrx_ns_create(const iamrx_geom* g, iamrx_layout l, const iamrx_ns_params* p, const iamrx_mg_opts* o, iamrx_ns* out);
@@ -462,18 +465,35 @@ int iamrx_ns_advance(iamrx_ns ns, double dt, double* dt_est);
 int iamrx_ns_time(iamrx_ns ns, double* time, double* dt, int* nstep);
 /* snapshot COPY (caller destroys it with iamrx_mf_destroy) of a persistent array: 0 S_new, 1 S_old, 2 P_new,
  * 3 P_old, 4 Gp_new, 5 Gp_old, 6..8 u_mac, 9 aofs  (get_new_data/get_old_data role); 10, 11: the last two MAC potentials (the
- * initial-guess history of the MAC solve, part of a checkpoint) */
+ * initial-guess history of the MAC solve, part of a checkpoint);
+ * 12: the time-average accumulators (the reference's Average_Type, Source/NS_setup.cpp:389-405; only with avg_interval > 0): 6 components,
+ * no ghost cells -- 0..2 the time integral of u, v, w, 3..5 the time integral of the squared fluctuation (Source/NS_average.cpp:45-55) */
 int iamrx_ns_data(iamrx_ns ns, int which, iamrx_mf* out);
 /* Derived quantities of the plotfile (derive_lst, Source/NS_setup.cpp:436-449; amr.derive_plot_vars): "energy" = rho |u|^2 / 2 (derkeng,
  * Source/NS_derive.cpp:266-295), "mag_vort" = |curl u| (dermgvort, :86-264, ghost cells by FillPatch), "avg_pressure" = mean of the eight
- * nodes of the cell (deravgpres, :51-80) of the level's new-time data, into component ocomp of the cell-centred out (the level's layout). */
+ * nodes of the cell (deravgpres, :51-80) of the level's new-time data, into component ocomp of the cell-centred out (the level's layout).
+ * With avg_interval > 0 also "velocity_average" (der_vel_avg, Source/NS_derive.cpp:11-45; declared Source/NS_setup.cpp:412-431): SIX
+ * components from ocomp on, x/y/z_vel_average = accumulator / time_avg and x/y/z_vel_rms = sqrt(accumulator / time_avg_fluct), a zero
+ * divisor counting as 1.  Without averages the name is unknown. */
 int iamrx_ns_derive(iamrx_ns ns, const char* name, iamrx_mf out, int ocomp);
+/* NavierStokesBase::time_average (Source/NS_average.cpp:19-69) as NavierStokes::post_init (Source/NavierStokes.cpp:1287-1297) and
+ * NavierStokesBase::post_timestep (Source/NavierStokesBase.cpp:2630-2634) call it: dt_avg += dt_level; if level0_steps is a multiple of
+ * avg_interval the new-time velocity enters the accumulators with weight dt_avg, then time_avg += dt_avg, time_avg_fluct += dt_avg (or
+ * = 0 without fluctuations), dt_avg = 0.  A hierarchy (iamrx_amr_post_init / iamrx_amr_coarse_step) makes these calls itself; the caller
+ * of iamrx_ns_post_init / iamrx_ns_step makes them for a single level.  No-op with avg_interval = 0. */
+int iamrx_ns_time_average(iamrx_ns ns, double dt_level, int level0_steps);
+/* NavierStokesBase::time_avg / time_avg_fluct / dt_avg of the level (Source/NavierStokesBase.cpp:2467-2522; checkpointed in
+ * <chk>/TimeAverage, :863-888): v[3] = time_avg, time_avg_fluct, dt_avg.  set = 0: read, 1: write.  Error with avg_interval = 0. */
+int iamrx_ns_average_state(iamrx_ns ns, int set, double v[3]);
+/* One level's part of NavierStokes::sum_integrated_quantities (Source/NavierStokes.cpp:1046-1079): sums[3] = volume-weighted sums of
+ * density (MASS), tracer (TRAC) and rho |u|^2 / 2 (KINETIC ENERGY) over ALL cells of the level, on all ranks.  One fused reduction. */
+int iamrx_ns_sum_integrated(iamrx_ns ns, double sums[3]);
 
 /* overwrite state (0,1), pressure (2,3) or grad p (4,5) with src (same layout and ngrow; ncomp at most the array's: the leading
  * components are set): the role of NavierStokes::initData for caller-supplied initial data (Source/NavierStokes.cpp:318-420).
  * The state arrays hold u v w density tracer [tracer2] [temp], and with ns.do_temp two more components, divu and dsdt (the
  * reference's Divu_Type / Dsdt_Type), which the library computes. */
-int iamrx_ns_set_data(iamrx_ns ns, int which, iamrx_mf src);      /* which: 0..5, 10, 11 */
+int iamrx_ns_set_data(iamrx_ns ns, int which, iamrx_mf src);      /* which: 0..5, 10, 11, 12 */
 /* checkpoint / restart of one level (AmrLevel::checkPoint / NavierStokesBase::restart role, Source/NavierStokesBase.cpp:856-897,
  * 2706-2727): what outlives a time step besides the arrays of iamrx_ns_data.  state[16] = time, dt, nstep, State_Type new / old time,
  * Press_Type new interval [2], old interval [2], dt of the last MAC solve, two history flags, dt estimate of the last advance,
@@ -635,6 +655,13 @@ int iamrx_amr_level_counts(iamrx_amr a, int set, int* counts, int n);
 int iamrx_ns_set_stop_time(iamrx_ns ns, double stop_time);
 int iamrx_amr_coarse_step(iamrx_amr a, double* dt0);         /* dt0: the level-0 time step used */
 int iamrx_amr_time(iamrx_amr a, double* time, double* dt_levels /* [nlev] or NULL */);
+/* NavierStokes::sum_integrated_quantities (Source/NavierStokes.cpp:1046-1079; amrex volumeWeightedSum): composite MASS, TRAC and KINETIC
+ * ENERGY of the hierarchy now -- every level over the cells the next finer level does not cover, weighted with the cell volume, the levels
+ * added coarsest first.  iamrx_amr_last_sum: what the hierarchy itself computed with sum_interval > 0, after post_init
+ * (Source/NavierStokes.cpp:1284-1285; *step = 0) and in level 0's post_timestep of every sum_interval-th level-0 step
+ * (Source/NavierStokesBase.cpp:2589-2592; *step = that step count); *step = -1: nothing yet. */
+int iamrx_amr_sum_integrated(iamrx_amr a, double sums[3]);
+int iamrx_amr_last_sum(iamrx_amr a, int* step, double* time /* or NULL */, double sums[3]);
 /* the pieces of NavierStokesBase::post_timestep(lev) one by one (lev < finest), for a caller that drives the loop itself:
  * NavierStokes::reflux, avgDown, mac_sync (= MacProj::mac_sync_solve + mac_sync_compute + the state update and SyncInterp),
  * NavierStokesBase::level_sync (= SyncInterp + Projection::MLsyncProject) */
