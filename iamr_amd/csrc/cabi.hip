@@ -146,6 +146,29 @@ int iamrx_host_fill_plan_wall_ext(int nboxes, const int* lo_hi, const int* owner
     IAMRX_CATCH
 }
 
+// host-only (no device needed): the path a smoothing call of the cell-centred multigrid takes on a level (abec_smooth_plan, k_abec.hip).
+// out (12 ints): path (0 COLOUR, 1 RB_BOX, 2 RB_CF, 3 RB_NBR, 4 FUSED_SHELL), wavefronts, two parts, first sweep from zero; then the colour
+// pass: kernel (0 general, 1 gsrb1, 2 gsrb2, 3 gsrb2 per component), mode, planes in flight, maintain, allcf, wrap, walls_inkernel, zero_ok
+int iamrx_host_abec_smoother_plan(int nboxes, const int* lo_hi, const iamrx_geom* g, const int lobc[3], const int hibc[3], int maxorder, int ncomp,
+                                  int coef, int has_a, int has_cf, int finest, const int ngrow[4], int out[12])
+{
+    IAMRX_TRY
+    if (nboxes < 1 || coef < 0 || coef > 2) throw Error("iamrx_host_abec_smoother_plan: at least one box; coef is 0 (stored), 1 (density) or 2 (uniform)");
+    std::vector<BoxD> b(nboxes);
+    AbecLevel lv;
+    for (int i = 0; i < nboxes; ++i)
+        for (int d = 0; d < 3; ++d) { b[i].lo[d] = lo_hi[6 * i + d]; b[i].hi[d] = lo_hi[6 * i + 3 + d]; lv.max_len[d] = std::max(lv.max_len[d], b[i].len(d)); }
+    const DomainBC bc = to_bc(lobc, hibc, maxorder);
+    lv.boxes = &b; lv.nlocal = nboxes; lv.ncomp = ncomp;
+    lv.phi_ngrow = ngrow[0]; lv.rhs_ngrow = ngrow[1]; lv.sig_ngrow = ngrow[2]; lv.a_ngrow = ngrow[3];
+    lv.sig = coef == 1; lv.b_uniform = coef == 2; lv.has_a = has_a != 0; lv.nbc = 1; lv.bcs = &bc; lv.has_cf = has_cf != 0; lv.finest = finest != 0;
+    const AbecSmoothPlan p = abec_smooth_plan(to_geom(g), lv);
+    const AbecColourForm& f = p.colour;
+    const int v[12] = {(int)p.path, p.nw, p.nbr_splits, p.zero_first, (int)f.kernel, f.mode, f.np, f.maintain, f.allcf, f.wrap, f.walls_inkernel, f.zero_ok};
+    std::copy(v, v + 12, out);
+    IAMRX_CATCH
+}
+
 static hipEvent_t g_ev0 = nullptr, g_ev1 = nullptr;
 int iamrx_timer_start(void)
 {
@@ -342,7 +365,9 @@ int iamrx_abec_gsrb(const iamrx_geom* g, double alpha, double beta, iamrx_mf a, 
 {
     IAMRX_TRY
     DomainBC b = to_bc(lobc, hibc, maxorder);
-    abec_gsrb(to_geom(g), make_coef(alpha, beta, a, bx, by, bz, 0), phi->mf, rhs->mf, redblack, omega, &b, 1);
+    const Geometry gg = to_geom(g);
+    const AbecCoef c = make_coef(alpha, beta, a, bx, by, bz, 0);
+    abec_gsrb(gg, c, abec_colour_form(gg, abec_level(c, phi->mf, rhs->mf.ngrow, 1, &b)), phi->mf, rhs->mf, redblack, omega, &b, 1);
     IAMRX_CATCH
 }
 
@@ -370,14 +395,15 @@ int iamrx_abec_form(const iamrx_geom* g, int coef, iamrx_mf rho, int rho_comp, d
     } else throw Error("iamrx_abec_form: coef is 1 (recomputed from rho) or 2 (uniform)");
     const bool wrap = op == 4 || op == 5;
     if (wrap && !periodic_wrap_ok(gg, *phi->mf.layout, 1)) throw Error("iamrx_abec_form: op 4 / 5 need one box spanning a periodic domain");
-    if (op == 0 || op == 1 || wrap) abec_gsrb(gg, c, phi->mf, rhs->mf, op & 1, omega, &b, 1, false, wrap);
+    const AbecLevel lv = abec_level(c, phi->mf, rhs->mf.ngrow, 1, &b, op == 10 || op == 11);
+    if (op == 0 || op == 1 || wrap) abec_gsrb(gg, c, abec_colour_form(gg, lv, wrap), phi->mf, rhs->mf, op & 1, omega, &b, 1);
     else if (op == 2) abec_residual(gg, c, out->mf, phi->mf, &rhs->mf);
     else if (op == 3) {
         if (!abec_resid_restrict_ok(c, phi->mf, rhs->mf)) throw Error("iamrx_abec_form: the fused residual + restriction does not apply to these arrays");
         abec_resid_restrict(gg, c, out->mf, phi->mf, rhs->mf);
     } else if (op == 6 || op == 7) {
         if (!abec_gsrb_rb_ok(gg, c, phi->mf, 1, &b)) throw Error("iamrx_abec_form: the one-launch red + black sweep does not apply to this level");
-        abec_gsrb_rb(gg, c, phi->mf, out->mf, rhs->mf, omega, op == 7, &b, 1);
+        abec_gsrb_rb(gg, c, abec_smooth_plan(gg, lv), phi->mf, out->mf, rhs->mf, omega, op == 7, &b, 1);
     } else if (op == 8 || op == 9) {
         // the same sweep on a level of several boxes (k_abec_rb_ghost + k_abec_gsrb_rb<.., NBR>): phi and out with two ghost layers, rhs with
         // one, rho with two (its ghost cells beyond domain walls: the caller's); the ghost fills of the sweep are done here
@@ -386,7 +412,7 @@ int iamrx_abec_form(const iamrx_geom* g, int coef, iamrx_mf rho, int rho_comp, d
         if (coef == 1) rho->mf.FillBoundary(gg);
         rhs->mf.FillBoundary(gg);
         if (op == 8) p.FillBoundary(gg);
-        abec_gsrb_rb_nbr(gg, c, p, out->mf, rhs->mf, omega, op == 9, &b, 1);
+        abec_gsrb_rb_nbr(gg, c, abec_smooth_plan(gg, lv), p, out->mf, rhs->mf, omega, op == 9, &b, 1);
     } else if (op == 10 || op == 11) {
         // the sweep on a refined box strictly inside the domain (ratio 2): every face a coarse/fine face whose homogeneous ghost value of
         // order `maxorder` the kernel forms itself (k_abec_gsrb_rb<.., W3>); phi's ghost cells are not read
@@ -394,7 +420,7 @@ int iamrx_abec_form(const iamrx_geom* g, int coef, iamrx_mf rho, int rho_comp, d
         double loc[3];
         for (int d = 0; d < 3; ++d) loc[d] = 0.5 * 2 * gg.dx[d];
         const CfTab tab = cf_make_tab(loc, gg.dx, maxorder);
-        abec_gsrb_rb(gg, c, phi->mf, out->mf, rhs->mf, omega, op == 11, &b, 1, &tab);
+        abec_gsrb_rb(gg, c, abec_smooth_plan(gg, lv), phi->mf, out->mf, rhs->mf, omega, op == 11, &b, 1, &tab);
     } else throw Error("iamrx_abec_form: bad op");
     IAMRX_CATCH
 }
@@ -409,16 +435,17 @@ int iamrx_abec_gsrb_sweep(const iamrx_geom* g, double alpha, double beta, iamrx_
     DomainBC b = to_bc(lobc, hibc, maxorder);
     AbecCoef c = make_coef(alpha, beta, a, bx, by, bz, 0);
     MultiFab& p = phi->mf;
+    const AbecColourForm f = abec_colour_form(gg, abec_level(c, p, rhs->mf.ngrow, 1, &b));
     auto fill = [&](MultiFab& m) { m.FillBoundary(gg); abec_apply_domain_bc(gg, m, b, false, nullptr); };
     if (fused) {
         MultiFab buf(p.layout, cell_type(), p.ncomp, 1);
         fill(p);
         abec_gsrb_fused(gg, c, p, buf, rhs->mf, omega, &b, 1);
         fill(buf);
-        abec_gsrb(gg, c, buf, rhs->mf, 1, omega, &b, 1, true);
+        abec_gsrb(gg, c, f, buf, rhs->mf, 1, omega, &b, 1, true);
         MultiFab::Copy(p, buf, 0, 0, p.ncomp, 0);
     } else {
-        for (int rb = 0; rb < 2; ++rb) { fill(p); abec_gsrb(gg, c, p, rhs->mf, rb, omega, &b, 1); }
+        for (int rb = 0; rb < 2; ++rb) { fill(p); abec_gsrb(gg, c, f, p, rhs->mf, rb, omega, &b, 1); }
     }
     IAMRX_CATCH
 }

@@ -1050,78 +1050,200 @@ static bool rb_make_bc(const Geometry& g, const DomainBC& bc, RbBC& r)
     return true;
 }
 
-// bcs: the level's boundary conditions (nbc sets: one per component, or one for all); null: fully periodic levels only.
-// IAMRX_GSRB_RB_WALLS (1): 0 = index-wrap levels only.
-// (decided from the level's global box list: every rank takes the same path -- ADVICE round 4; a rank without the box launches nothing)
-bool abec_gsrb_rb_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi, int nbc, const DomainBC* bcs)
+// IAMRX_ABEC_SIG (1): 0 = the smoother and the residual read the stored face coefficients also where AbecCoef::sig is given
+static bool abec_sig_on() { return tune("ABEC_SIG", 1) != 0; }
+
+AbecLevel abec_level(const AbecCoef& c, const MultiFab& phi, int rhs_ngrow, int nbc, const DomainBC* bcs, bool has_cf, bool finest)
 {
-    if (tune("GSRB_RB", 1) == 0 || tune("ABEC_SIG", 1) == 0 || tune("PERIODIC_WRAP", 1) == 0) return false;
+    AbecLevel lv;
     const Layout& l = *phi.layout;
-    if (l.boxes.size() != 1) return false;             // (decided on the GLOBAL box list: every rank takes the same path, a rank that does not own the box launches nothing)
-    const BoxD& b = l.boxes[0];
-    bool walls = false;
-    for (int d = 0; d < 3; ++d) {
-        if (b.lo[d] != g.domain.lo[d] || b.hi[d] != g.domain.hi[d] || b.len(d) < 4) return false;
-        if (!g.periodic[d]) walls = true;
-    }
-    if (walls) {
-        if (!bcs || nbc < 1 || tune("GSRB_RB_WALLS", 1) == 0) return false;
-        for (int n = 0; n < phi.ncomp; ++n) { RbBC r; if (!rb_make_bc(g, bcs[n < nbc ? n : 0], r)) return false; }
-    }
-    const int nx = b.len(0);
-    if (nx != 128 && nx != 256) return false;                      // whole rows in 1 or 2 wavefronts of a workgroup
-    if ((b.len(1) & 1) || (b.len(2) & 1) || b.len(1) < 16 || b.len(2) < 16) return false;
-    if (phi.ngrow < 1 || c.b[0]->ncomp != 1) return false;
-    if (c.sig) return phi.ncomp == 1 && c.sig->ngrow >= 1 && !(c.a && c.alpha != 0.0);
-    return c.b_uniform != 0;
+    lv.boxes = &l.boxes; lv.nlocal = l.nlocal();
+    for (int d = 0; d < 3; ++d) lv.max_len[d] = l.max_len[d];
+    lv.ncomp = phi.ncomp; lv.phi_ngrow = phi.ngrow; lv.rhs_ngrow = rhs_ngrow;
+    lv.sig = c.sig != nullptr; lv.sig_ngrow = c.sig ? c.sig->ngrow : 0;
+    lv.has_a = c.a && c.alpha != 0.0; lv.a_ngrow = c.a ? c.a->ngrow : 0;
+    lv.b_uniform = c.b_uniform != 0; lv.tensor_eta = c.tensor_eta != 0; lv.tensor = c.tensor != 0; lv.b_ncomp = c.b[0]->ncomp;
+    lv.nbc = nbc; lv.bcs = bcs; lv.has_cf = has_cf; lv.finest = finest;
+    return lv;
 }
 
-// The sweep on a REFINED level that is one box strictly inside its domain (k_abec_gsrb_rb<.., WALLS, .., W3>): every face of the box is a
-// coarse/fine face, whose homogeneous ghost value (k_cf_fill, correction form) is the three-weight formula of the level's CfTab -- the
-// kernel evaluates it on the values at hand and reads no ghost cell of phi.  IAMRX_GSRB_RB_CF (1): 0 = colour passes (k_abec_gsrb2<.., CF>).
-bool abec_gsrb_rb_cf_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi)
+// the sweep kernel's rows: 128 or 256 cells (whole rows in 1 or 2 wavefronts of a workgroup), at least 16 cells in y and z
+static bool rb_shape_ok(const BoxD& b, int nx) { return (nx == 128 || nx == 256) && b.len(0) == nx && b.len(1) >= 16 && b.len(2) >= 16; }
+// the two-weight ghost formula covers the wall conditions of every component (a fully periodic level has none)
+static bool rb_walls_covered(const Geometry& g, const AbecLevel& lv)
 {
-    if (tune("GSRB_RB", 1) == 0 || tune("ABEC_SIG", 1) == 0 || tune("GSRB_RB_CF", 1) == 0) return false;
-    const Layout& l = *phi.layout;
-    if (l.boxes.size() != 1) return false;             // (decided on the GLOBAL box list: every rank takes the same path, a rank that does not own the box launches nothing)
-    const BoxD& b = l.boxes[0];
+    if (g.periodic[0] && g.periodic[1] && g.periodic[2]) return true;
+    if (!lv.bcs || lv.nbc < 1) return false;
+    for (int n = 0; n < lv.ncomp; ++n) { RbBC r; if (!rb_make_bc(g, lv.bcs[n < lv.nbc ? n : 0], r)) return false; }
+    return true;
+}
+// where the box lies: spans the domain in every direction (with at least min_len cells) / touches no side of it
+static bool box_spans(const Geometry& g, const BoxD& b, int min_len)
+{
+    for (int d = 0; d < 3; ++d) if (b.lo[d] != g.domain.lo[d] || b.hi[d] != g.domain.hi[d] || b.len(d) < min_len) return false;
+    return true;
+}
+static bool box_strictly_inside(const Geometry& g, const BoxD& b)
+{
     for (int d = 0; d < 3; ++d) if (!(b.lo[d] > g.domain.lo[d] && b.hi[d] < g.domain.hi[d])) return false;
-    const int nx = b.len(0);
-    if (nx != 128 && nx != 256) return false;
-    if ((b.len(1) & 1) || (b.len(2) & 1) || b.len(1) < 16 || b.len(2) < 16) return false;
-    if (phi.ngrow < 1 || c.b[0]->ncomp != 1) return false;
-    if (c.sig) return phi.ncomp == 1 && c.sig->ngrow >= 1 && !(c.a && c.alpha != 0.0);
-    return c.b_uniform != 0;
-}
-
-// The sweep on a level of SEVERAL boxes that covers its domain (k_abec_gsrb_rb<.., NBR>: a chopped level, the boxes of a sharded level):
-// what the level must look like -- rows of 128 or 256 cells in every box, no coarse/fine faces (the caller knows), wall conditions the
-// kernel has a ghost formula for.  The arrays: phi (both buffers) with two ghost layers, the density with two, rhs and the a-term with one
-// (abec_gsrb_rb_nbr asserts them).  IAMRX_GSRB_RB_NBR (1): 0 = colour passes with a ghost fill in front of each.
-bool abec_gsrb_rb_nbr_level_ok(const Geometry& g, const Layout& l, int ncomp, bool sig_form, bool has_a, int nbc, const DomainBC* bcs)
-{
-    if (tune("GSRB_RB", 1) == 0 || tune("ABEC_SIG", 1) == 0 || tune("GSRB_RB_NBR", 1) == 0) return false;
-    if (l.boxes.size() < 2 || l.total_cells() != g.domain.npts()) return false;
-    const int nx = l.boxes[0].len(0);
-    if (nx != 128 && nx != 256) return false;
-    for (const BoxD& b : l.boxes) if (b.len(0) != nx || b.len(1) < 16 || b.len(2) < 16) return false;
-    bool walls = false;
-    for (int d = 0; d < 3; ++d) if (!g.periodic[d]) walls = true;
-    if (walls) {
-        if (!bcs || nbc < 1 || tune("GSRB_RB_WALLS", 1) == 0) return false;
-        for (int n = 0; n < ncomp; ++n) { RbBC r; if (!rb_make_bc(g, bcs[n < nbc ? n : 0], r)) return false; }
-    }
-    if (sig_form) return ncomp == 1 && !has_a;
     return true;
 }
 
+AbecColourForm abec_colour_form(const Geometry& g, const AbecLevel& lv, bool wrap, bool walls_inkernel)
+{
+    AbecColourForm f;
+    const std::vector<BoxD>& boxes = *lv.boxes;
+    const bool sig = lv.sig && abec_sig_on(), uni = lv.b_uniform && lv.b_ncomp == 1 && abec_sig_on();
+    const bool gsrb2 = tune("GSRB2", 1) != 0 && lv.phi_ngrow >= 1;
+    f.wrap = wrap;
+    f.has_cf = lv.has_cf;
+    // one-component coarse/fine levels: the colour passes keep the coarse/fine ghost cells current themselves (cf_maintain), so only the
+    // first pass of a smoothing call needs the k_cf_fill launch; IAMRX_CF_MAINTAIN=0: a fill in front of every pass
+    f.maintain = lv.has_cf && lv.ncomp == 1 && !lv.tensor && tune("CF_MAINTAIN", 1) != 0;
+    f.gen_mc = lv.ncomp > 1 && lv.b_ncomp == 1;
+    f.gen_mode = (lv.ncomp == 1 && sig && !lv.tensor_eta) ? 1 : (uni ? 2 : 0);
+    // IAMRX_GSRB1_NP (1): planes in flight per thread of the pipelined one-component pass (0: the general kernel)
+    const int np = (int)tune("GSRB1_NP", 1);
+    const bool one = np > 0 && lv.ncomp == 1 && lv.nbc == 1 && lv.b_ncomp == 1 && !lv.tensor_eta;
+    if (one) {
+        f.mode = sig ? 1 : (uni ? 2 : 0);
+        // IAMRX_GSRB2 (1): the pair-marching kernel where the coefficients are not arrays (needs a ghost layer for its 16-byte loads)
+        f.kernel = (f.mode != 0 && gsrb2 && (f.mode == 2 || lv.sig_ngrow >= 1)) ? AbecColourForm::GSRB2 : AbecColourForm::GSRB1;
+        // with coarse/fine faces the pipelined form would read a ghost cell that cf_maintain rewrote for the plane before: one plane in flight
+        f.np = lv.has_cf ? 1 : (np >= 4 ? 4 : (np >= 2 ? 2 : 1));
+        // one box strictly inside the domain (no neighbour box, no domain face, no periodic image next to it): all of its ghost cells are
+        // coarse/fine ghost cells and the maintaining colour pass takes the masks as constants.  IAMRX_GSRB2_ALLCF = 0: loads them.
+        f.allcf = f.kernel == AbecColourForm::GSRB2 && f.maintain && boxes.size() == 1 && lv.nlocal == 1 && tune("GSRB2_ALLCF", 1) != 0 &&
+                  box_strictly_inside(g, boxes[0]);
+    }
+    // IAMRX_GSRB2_MULTI = 1 (off by default: measured equal, 3 x 112 us against 336 us at 256^3 -- both forms move the half-used lines of
+    // the red-black layout at the achievable HBM rate): several components with constant coefficients (the tensor solves of a
+    // constant-viscosity run, the unit-coefficient tensor solve of diffuse_tensor_Vsync) as one pair-marching launch per component
+    // with its own constants b_d (x 4/3 on the normal component of the tensor operator) -- the expressions of k_abec_gsrb<true, 2>
+    else if (uni && lv.ncomp > 1 && gsrb2 && tune("GSRB2_MULTI", 0) != 0) f.kernel = AbecColourForm::GSRB2_PER_COMP;
+    // The passes can apply the domain walls themselves (WallK): one box spanning a domain with non-periodic sides whose boundary conditions
+    // the two-weight ghost formula covers, and a kernel that takes the table -- the pair-marching kernels read the ghost cells.
+    const bool walls = !(g.periodic[0] && g.periodic[1] && g.periodic[2]);
+    f.walls_inkernel = walls_inkernel && !wrap && walls && tune("GSRB_WALLS_INKERNEL", 1) != 0 && !lv.has_cf && lv.ncomp <= 3 && lv.phi_ngrow >= 1 && boxes.size() == 1 &&
+                       box_spans(g, boxes[0], 2) && rb_walls_covered(g, lv) && (f.kernel == AbecColourForm::GSRB1 || f.kernel == AbecColourForm::GENERAL);
+    f.zero_ok = tune("GSRB_ZERO", 1) != 0 && one && (f.wrap || f.walls_inkernel) && !lv.has_cf;
+    return f;
+}
+
+AbecSmoothPlan abec_smooth_plan(const Geometry& g, const AbecLevel& lv)
+{
+    AbecSmoothPlan p;
+    p.ncomp = lv.ncomp; p.phi_ngrow = lv.phi_ngrow; p.rhs_ngrow = lv.rhs_ngrow;
+    const std::vector<BoxD>& boxes = *lv.boxes;      // (the GLOBAL box list: every rank takes the same path -- ADVICE round 4; a rank without the box launches nothing)
+    const bool periodic = g.periodic[0] && g.periodic[1] && g.periodic[2];
+    // one box spanning a fully periodic domain: the kernel reads the periodic images from the valid cells, no ghost fills (periodic_wrap_ok)
+    const bool wrap = !lv.has_cf && tune("PERIODIC_WRAP", 1) != 0 && periodic && boxes.size() == 1 && lv.nlocal == 1 && box_spans(g, boxes[0], 2);
+    p.colour = abec_colour_form(g, lv, wrap, true);
+    // Red + black in one out-of-place launch per sweep (k_abec_gsrb_rb), on the finest level only (on a coarser level of 128 cells in x a
+    // march of a few planes does not beat two colour passes).  The coefficient forms it has: the density form (one component, no a-term)
+    // and constants.  IAMRX_GSRB_RB (1): 0 = none of the three sweeps.
+    const int nx = boxes.empty() ? 0 : boxes[0].len(0);
+    const bool form1 = lv.b_ncomp == 1 && (lv.sig ? (lv.ncomp == 1 && !lv.has_a) : lv.b_uniform);
+    const bool rb = lv.finest && tune("GSRB_RB", 1) != 0 && abec_sig_on() && form1 && lv.phi_ngrow >= 1;
+    bool faces = false;                   // the sweep forms ghost values at walls, coarse/fine faces or ghost columns
+    if (rb && boxes.size() == 1 && rb_shape_ok(boxes[0], nx) && !(boxes[0].len(1) & 1) && !(boxes[0].len(2) & 1) && (!lv.sig || lv.sig_ngrow >= 1)) {
+        // one box spanning its domain; IAMRX_GSRB_RB_WALLS (1): 0 = index-wrap levels only
+        if (!lv.has_cf && tune("PERIODIC_WRAP", 1) != 0 && box_spans(g, boxes[0], 4) && rb_walls_covered(g, lv) && (periodic || tune("GSRB_RB_WALLS", 1) != 0)) {
+            p.path = AbecSmoothPlan::RB_BOX; faces = !periodic;
+        }
+        // a REFINED level that is one box strictly inside its domain (k_abec_gsrb_rb<.., WALLS, .., W3>): every face of the box is a
+        // coarse/fine face, whose homogeneous ghost value (k_cf_fill, correction form) is the three-weight formula of the level's CfTab -- the
+        // kernel evaluates it on the values at hand and reads no ghost cell of phi (no k_cf_fill, no ghost maintenance; phi's ghost cells are
+        // left stale: every reader behind a smoothing call fills them).  IAMRX_GSRB_RB_CF (1): 0 = colour passes (k_abec_gsrb2<.., CF>)
+        else if (lv.has_cf && tune("GSRB_RB_CF", 1) != 0 && box_strictly_inside(g, boxes[0])) { p.path = AbecSmoothPlan::RB_CF; faces = true; }
+    }
+    // SEVERAL boxes that cover the domain (k_abec_gsrb_rb<.., NBR>: a chopped level, the boxes of a sharded level): rows of 128 or 256 cells
+    // in every box, no coarse/fine faces, wall conditions the kernel has a ghost formula for.  The arrays: phi (both buffers) with two ghost
+    // layers, the density with two, rhs and the a-term with one.  IAMRX_GSRB_RB_NBR (1): 0 = colour passes with a ghost fill in front of each
+    else if (rb && !lv.has_cf && tune("GSRB_RB_NBR", 1) != 0 && boxes.size() >= 2 && lv.phi_ngrow >= 2 && lv.rhs_ngrow >= 1 &&
+             (lv.sig ? lv.sig_ngrow >= 2 : (!lv.has_a || lv.a_ngrow >= 1)) && rb_walls_covered(g, lv) && (periodic || tune("GSRB_RB_WALLS", 1) != 0)) {
+        long cells = 0;
+        bool rows = true;
+        for (const BoxD& b : boxes) { cells += b.npts(); rows = rows && rb_shape_ok(b, nx); }
+        if (rows && cells == g.domain.npts()) {
+            p.path = AbecSmoothPlan::RB_NBR; faces = !periodic || nx != g.domain.len(0);
+            // two parts: rows that span the domain (no ghost columns) and boxes tall enough for tiles in the middle
+            p.nbr_splits = lv.max_len[0] == g.domain.len(0) && lv.max_len[1] >= 48 && lv.max_len[2] >= 32;
+        }
+    }
+    // The density form with walls, coarse/fine faces or ghost columns needs more than the 128 VGPRs a 1024-thread workgroup leaves a thread
+    // (72 ... 116 bytes of scratch per lane, 210 us per 256^3 sweep): 12 wavefronts (768 threads: 168 VGPRs) trade two of the eight rows of
+    // a tile for a spill-free loop.  IAMRX_GSRB_RB_NW12 (1): 0 = 16 everywhere
+    if (p.sweep_kernel()) p.nw = (lv.sig && faces && tune("GSRB_RB_NW12", 1) != 0) ? 12 : 16;
+    // The fused sweep (opt-in, IAMRX_GSRB_FUSED: on MI355X the single-pass kernel -- 62 B/cell of HBM traffic instead of 130 -- is still
+    // slower than the two colour passes: 233 VGPRs -> 2 waves/SIMD with three barriers per plane, 0.41 ms vs 2 x 0.18 ms at 256^3)
+    // refreshes the ghost cells once per sweep, from a state in which the black cells off the box surfaces are already updated.  That
+    // equals the reference sequence (ghost fill in front of each colour) only if a ghost value depends on nothing but the first cell
+    // inside the box: periodic / neighbour images, Neumann, and Dirichlet extrapolation of order <= 2.
+    bool fused = tune("GSRB_FUSED", 0) != 0 && !lv.has_cf;
+    for (int d = 0; d < 3 && fused; ++d) {
+        if (lv.max_len[d] < 16) fused = false;
+        if (g.periodic[d]) continue;
+        for (int n = 0; n < lv.nbc; ++n)
+            for (int t : {lv.bcs[n].lo[d], lv.bcs[n].hi[d]})
+                if (!(t == lo_neumann || (t == lo_dirichlet && std::min(g.domain.len(d) + 1, lv.bcs[n].maxorder) <= 2))) fused = false;
+    }
+    if (fused && !p.sweep_kernel()) p.path = AbecSmoothPlan::FUSED_SHELL;
+    // From zero: the sweep kernels take "zero" per component and read no input; the colour passes where the first one reads no ghost cell.
+    // (One box with walls and one component starts from zero only where its colour passes could: the sweep kernel could always.)
+    p.zero_first = p.path == AbecSmoothPlan::RB_NBR || p.path == AbecSmoothPlan::RB_CF || (p.path == AbecSmoothPlan::RB_BOX && lv.ncomp > 1) ||
+                   (!fused && p.colour.zero_ok);
+    return p;
+}
+
+bool abec_gsrb_rb_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi, int nbc, const DomainBC* bcs)
+{
+    return abec_smooth_plan(g, abec_level(c, phi, 0, nbc, bcs)).path == AbecSmoothPlan::RB_BOX;
+}
+bool abec_gsrb_rb_cf_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi)
+{
+    return abec_smooth_plan(g, abec_level(c, phi, 0, 0, nullptr, true)).path == AbecSmoothPlan::RB_CF;
+}
 bool abec_gsrb_rb_nbr_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi, const MultiFab& rhs, int nbc, const DomainBC* bcs)
 {
-    const bool has_a = c.a && c.alpha != 0.0;
-    if (!abec_gsrb_rb_nbr_level_ok(g, *phi.layout, phi.ncomp, c.sig != nullptr, has_a, nbc, bcs)) return false;
-    if (phi.ngrow < 2 || rhs.ngrow < 1 || c.b[0]->ncomp != 1) return false;
-    if (c.sig) return c.sig->ngrow >= 2;
-    return c.b_uniform != 0 && (!has_a || c.a->ngrow >= 1);
+    return abec_smooth_plan(g, abec_level(c, phi, rhs.ngrow, nbc, bcs)).path == AbecSmoothPlan::RB_NBR;
+}
+bool abec_gsrb_rb_nbr_level_ok(const Geometry& g, const Layout& l, int ncomp, bool sig_form, bool has_a, int nbc, const DomainBC* bcs)
+{
+    AbecLevel lv;
+    lv.boxes = &l.boxes; lv.nlocal = l.nlocal();
+    for (int d = 0; d < 3; ++d) lv.max_len[d] = l.max_len[d];
+    lv.ncomp = ncomp; lv.phi_ngrow = 2; lv.rhs_ngrow = 1; lv.sig_ngrow = 2; lv.a_ngrow = 1;
+    lv.sig = sig_form; lv.b_uniform = !sig_form; lv.has_a = has_a; lv.nbc = nbc; lv.bcs = bcs;
+    return abec_smooth_plan(g, lv).path == AbecSmoothPlan::RB_NBR;
+}
+
+// component n of a sweep: its constants (x 4/3 on the normal component of the eta form) ...
+static BUni comp_buni(const AbecCoef& c, int n)
+{
+    BUni bn;
+    for (int d = 0; d < 3; ++d) bn.v[d] = c.bu[d] * ((c.tensor_eta && n == d) ? 4.0 / 3.0 : 1.0);
+    return bn;
+}
+// ... and the ghost formulas of its faces as the sweep kernel applies them: the domain's wall conditions (periodic sides: none), or (cf)
+// the level's coarse/fine formula on every face of box b
+static RbBC comp_rbbc(const Geometry& g, const DomainBC* bcs, int nbc, int n, const CfTab* cf, const BoxD& b)
+{
+    RbBC r;
+    for (int d = 0; d < 3; ++d) { r.per[d] = 1; r.c1lo[d] = r.c2lo[d] = r.c1hi[d] = r.c2hi[d] = 0.0; r.dlo[d] = g.domain.lo[d]; r.dhi[d] = g.domain.hi[d]; }
+    if (cf) {
+        // every face a coarse/fine face: k_cf_fill's weights (NX = min(len + 1, maxorder) points, the first of them the boundary value: zero here)
+        for (int d = 0; d < 3; ++d) {
+            const int NX = std::min(b.len(d) + 1, cf->maxorder);
+            const double* w = cf->c[d][NX - 2];
+            r.per[d] = 0;
+            r.c1lo[d] = r.c1hi[d] = w[1];
+            r.c2lo[d] = r.c2hi[d] = NX > 2 ? w[2] : 0.0;
+            r.c3lo[d] = r.c3hi[d] = NX > 3 ? w[3] : 0.0;
+            r.dlo[d] = b.lo[d]; r.dhi[d] = b.hi[d];
+        }
+    } else if (!(g.periodic[0] && g.periodic[1] && g.periodic[2])) rb_make_bc(g, bcs[n < nbc ? n : 0], r);
+    return r;
 }
 
 // one red + black sweep pin -> pout (pin != pout); zero: pin is identically zero and is not read
@@ -1146,64 +1268,27 @@ static void abec_gsrb_rb_nw(const Geometry& g, const AbecCoef& c, const MultiFab
     // (the in-step probe of bench.py times the plain sweep: the last sweep of a cycle also carries the `sol += cor` pass, ACC)
     const bool rec = !acc && pin.ncomp == 1 && kernel_probe_begin(PROBE_ABEC_GSRB, (long)l.max_len[0] * l.max_len[1] * l.max_len[2]);
     for (int n = 0; n < pin.ncomp; ++n) {
-        BUni bn;
-        for (int d = 0; d < 3; ++d) bn.v[d] = c.bu[d] * ((c.tensor_eta && n == d) ? 4.0 / 3.0 : 1.0);
-        RbBC rbc;
-        if (cf) {
-            // every face a coarse/fine face: k_cf_fill's weights (NX = min(len + 1, maxorder) points, the first of them the boundary value: zero here)
-            for (int d = 0; d < 3; ++d) {
-                const int NX = std::min(b.len(d) + 1, cf->maxorder);
-                const double* w = cf->c[d][NX - 2];
-                rbc.per[d] = 0;
-                rbc.c1lo[d] = rbc.c1hi[d] = w[1];
-                rbc.c2lo[d] = rbc.c2hi[d] = NX > 2 ? w[2] : 0.0;
-                rbc.c3lo[d] = rbc.c3hi[d] = NX > 3 ? w[3] : 0.0;
-                rbc.dlo[d] = b.lo[d]; rbc.dhi[d] = b.hi[d];
-            }
-        } else
-        if (walls) rb_make_bc(g, bcs[n < nbc ? n : 0], rbc);
-#define IAMRX_RBL(M, HA, WL, T3, AC, SC, SS) hipLaunchKernelGGL((k_abec_gsrb_rb<M, NW, HA, WL, false, false, T3, AC>), dim3((unsigned)nwg), dim3(64 * NW), 0, ctx.stream, b, P, O, R, Af, Sf, \
-                                                      c.alpha, dhx, dhy, dhz, omega, SC, SS, bn, wpr, tz, nty, zero ? 1 : 0, n, xcd_chunk, rbc)
-#define IAMRX_RB(M, HA, WL, SC, SS) do { if (acc) IAMRX_RBL(M, HA, WL, false, true, SC, SS); else IAMRX_RBL(M, HA, WL, false, false, SC, SS); } while (0)
-#define IAMRX_RB3(M, HA, SC, SS) do { if (acc) IAMRX_RBL(M, HA, true, true, true, SC, SS); else IAMRX_RBL(M, HA, true, true, false, SC, SS); } while (0)
-        if (cf) {
-            if (c.sig) IAMRX_RB3(1, false, c.sig_comp, c.sig_scale);
-            else if (has_a) IAMRX_RB3(2, true, 0, 1.0);
-            else IAMRX_RB3(2, false, 0, 1.0);
-        } else
-        if (walls) {
-            if (c.sig) IAMRX_RB(1, false, true, c.sig_comp, c.sig_scale);
-            else if (has_a) IAMRX_RB(2, true, true, 0, 1.0);
-            else IAMRX_RB(2, false, true, 0, 1.0);
-        } else {
-            if (c.sig) IAMRX_RB(1, false, false, c.sig_comp, c.sig_scale);
-            else if (has_a) IAMRX_RB(2, true, false, 0, 1.0);
-            else IAMRX_RB(2, false, false, 0, 1.0);
-        }
+        const BUni bn = comp_buni(c, n);
+        const RbBC rbc = comp_rbbc(g, bcs, nbc, n, cf, b);
+        // M 1: the density form (its component and scale travel), 2: constants, with (HA) or without the a-term; WL, T3: two- / three-weight faces
+#define IAMRX_RBL(M, HA, WL, T3, AC) hipLaunchKernelGGL((k_abec_gsrb_rb<M, NW, HA, WL, false, false, T3, AC>), dim3((unsigned)nwg), dim3(64 * NW), 0, ctx.stream, b, P, O, R, Af, Sf, \
+                           c.alpha, dhx, dhy, dhz, omega, M == 1 ? c.sig_comp : 0, M == 1 ? c.sig_scale : 1.0, bn, wpr, tz, nty, zero ? 1 : 0, n, xcd_chunk, rbc)
+#define IAMRX_RBA(M, HA, WL, T3) do { if (acc) IAMRX_RBL(M, HA, WL, T3, true); else IAMRX_RBL(M, HA, WL, T3, false); } while (0)
+#define IAMRX_RB(M, HA) do { if (cf) IAMRX_RBA(M, HA, true, true); else if (walls) IAMRX_RBA(M, HA, true, false); else IAMRX_RBA(M, HA, false, false); } while (0)
+        if (c.sig) IAMRX_RB(1, false); else if (has_a) IAMRX_RB(2, true); else IAMRX_RB(2, false);
 #undef IAMRX_RB
-#undef IAMRX_RB3
+#undef IAMRX_RBA
 #undef IAMRX_RBL
     }
     if (rec) kernel_probe_end(PROBE_ABEC_GSRB);
 }
-void abec_gsrb_rb(const Geometry& g, const AbecCoef& c, const MultiFab& pin, MultiFab& pout, const MultiFab& rhs, double omega, bool zero,
-                  const DomainBC* bcs, int nbc, const CfTab* cf, bool acc)
+void abec_gsrb_rb(const Geometry& g, const AbecCoef& c, const AbecSmoothPlan& p, const MultiFab& pin, MultiFab& pout, const MultiFab& rhs, double omega,
+                  bool zero, const DomainBC* bcs, int nbc, const CfTab* cf, bool acc)
 {
-    IAMRX_ASSERT((cf ? abec_gsrb_rb_cf_ok(g, c, pin) : abec_gsrb_rb_ok(g, c, pin, nbc, bcs)) && pin.d_tab != pout.d_tab && pout.ngrow >= 1 && rhs.ncomp == pin.ncomp);
+    IAMRX_ASSERT(p.path == (cf ? AbecSmoothPlan::RB_CF : AbecSmoothPlan::RB_BOX) && p.made_for(pin, rhs) && pin.d_tab != pout.d_tab && pout.ngrow >= 1 && rhs.ncomp == pin.ncomp);
     if (pin.nlocal() == 0) return;
-    // The density form on a domain with walls needs more than the 128 VGPRs a 1024-thread workgroup leaves a thread (72 bytes of scratch per
-    // lane, 210 us per 256^3 sweep): 12 wavefronts (768 threads: 168 VGPRs) trade two of the eight rows of a tile for a spill-free loop
-    const bool walls = cf != nullptr || !(g.periodic[0] && g.periodic[1] && g.periodic[2]);
-    const int wpr = pin.layout->boxes[pin.layout->local[0]].len(0) / 128;
-    if (walls && c.sig && 12 % wpr == 0 && 12 / wpr >= 3 && tune("GSRB_RB_NW12", 1) != 0) abec_gsrb_rb_nw<12>(g, c, pin, pout, rhs, omega, zero, bcs, nbc, cf, acc);
+    if (p.nw == 12) abec_gsrb_rb_nw<12>(g, c, pin, pout, rhs, omega, zero, bcs, nbc, cf, acc);
     else abec_gsrb_rb_nw<16>(g, c, pin, pout, rhs, omega, zero, bcs, nbc, cf, acc);
-}
-
-// the sweep of this level can be issued in two parts -- the tiles that read no ghost cell (sel 1) and the others (sel 2, behind the exchange):
-// rows that span the domain (no ghost columns) and boxes tall enough for tiles in the middle
-bool abec_gsrb_rb_nbr_splits(const Geometry& g, const Layout& l)
-{
-    return l.max_len[0] == g.domain.len(0) && l.max_len[1] >= 48 && l.max_len[2] >= 32;
 }
 
 // the same on a level of several boxes (see k_abec_gsrb_rb<.., NBR>): pin's two ghost layers, rhs's (and the a-term's) one and the density's
@@ -1247,211 +1332,135 @@ static void abec_gsrb_rb_nbr_nw(const Geometry& g, const AbecCoef& c, MultiFab& 
     const dim3 ggrid((unsigned)((maxface + 255) / 256), (unsigned)(6 * nbox));
     const bool rec = !acc && sel == 0 && pin.ncomp == 1 && kernel_probe_begin(PROBE_ABEC_GSRB, (long)l.max_len[0] * l.max_len[1] * l.max_len[2]);
     for (int n = 0; n < pin.ncomp; ++n) {
-        BUni bn;
-        for (int d = 0; d < 3; ++d) bn.v[d] = c.bu[d] * ((c.tensor_eta && n == d) ? 4.0 / 3.0 : 1.0);
-        RbBC rbc;
-        for (int d = 0; d < 3; ++d) { rbc.per[d] = 1; rbc.c1lo[d] = rbc.c2lo[d] = rbc.c1hi[d] = rbc.c2hi[d] = 0.0; }
-        if (walls) rb_make_bc(g, bcs[n < nbc ? n : 0], rbc);
-        for (int d = 0; d < 3; ++d) { rbc.dlo[d] = g.domain.lo[d]; rbc.dhi[d] = g.domain.hi[d]; }
-#define IAMRX_RBG(M, HA, WL, SC, SS) if (sel != 1) hipLaunchKernelGGL((k_abec_rb_ghost<M, HA, WL>), ggrid, dim3(256), 0, strm, l.d_boxes, pin.d_tab, rhs.d_tab, At, St, \
-                                                       c.alpha, dhx, dhy, dhz, omega, SC, SS, bn, zero ? 1 : 0, n, rbc, xo ? 1 : 0)
-#define IAMRX_RBKL(M, HA, WL, XOO, AC, SC, SS) hipLaunchKernelGGL((k_abec_gsrb_rb<M, NW, HA, WL, true, XOO, false, AC>), dim3((unsigned)nwg, (unsigned)nbox), dim3(64 * NW), 0, strm, zb, Z, Z, Z, Z, Z, \
-                           c.alpha, dhx, dhy, dhz, omega, SC, SS, bn, wpr, tz, nty, zero ? 1 : 0, n, xcd_chunk, rbc, l.d_boxes, pin.d_tab, pout.d_tab, rhs.d_tab, At, St, sel)
-#define IAMRX_RBK(M, HA, WL, XOO, SC, SS) do { if (acc) IAMRX_RBKL(M, HA, WL, XOO, true, SC, SS); else IAMRX_RBKL(M, HA, WL, XOO, false, SC, SS); } while (0)
-#define IAMRX_RB(M, HA, WL, SC, SS) IAMRX_RBG(M, HA, WL, SC, SS); if (xo) IAMRX_RBK(M, HA, WL, true, SC, SS); else IAMRX_RBK(M, HA, WL, false, SC, SS)
-        if (walls) {
-            if (c.sig) { IAMRX_RB(1, false, true, c.sig_comp, c.sig_scale); }
-            else if (has_a) { IAMRX_RB(2, true, true, 0, 1.0); }
-            else { IAMRX_RB(2, false, true, 0, 1.0); }
-        } else {
-            if (c.sig) { IAMRX_RB(1, false, false, c.sig_comp, c.sig_scale); }
-            else if (has_a) { IAMRX_RB(2, true, false, 0, 1.0); }
-            else { IAMRX_RB(2, false, false, 0, 1.0); }
-        }
+        const BUni bn = comp_buni(c, n);
+        const RbBC rbc = comp_rbbc(g, bcs, nbc, n, nullptr, zb);
+#define IAMRX_RBG(M, HA, WL) if (sel != 1) hipLaunchKernelGGL((k_abec_rb_ghost<M, HA, WL>), ggrid, dim3(256), 0, strm, l.d_boxes, pin.d_tab, rhs.d_tab, At, St, \
+                                                       c.alpha, dhx, dhy, dhz, omega, M == 1 ? c.sig_comp : 0, M == 1 ? c.sig_scale : 1.0, bn, zero ? 1 : 0, n, rbc, xo ? 1 : 0)
+#define IAMRX_RBKL(M, HA, WL, XOO, AC) hipLaunchKernelGGL((k_abec_gsrb_rb<M, NW, HA, WL, true, XOO, false, AC>), dim3((unsigned)nwg, (unsigned)nbox), dim3(64 * NW), 0, strm, zb, Z, Z, Z, Z, Z, \
+                           c.alpha, dhx, dhy, dhz, omega, M == 1 ? c.sig_comp : 0, M == 1 ? c.sig_scale : 1.0, bn, wpr, tz, nty, zero ? 1 : 0, n, xcd_chunk, rbc, l.d_boxes, pin.d_tab, pout.d_tab, \
+                           rhs.d_tab, At, St, sel)
+#define IAMRX_RBK(M, HA, WL, XOO) do { if (acc) IAMRX_RBKL(M, HA, WL, XOO, true); else IAMRX_RBKL(M, HA, WL, XOO, false); } while (0)
+#define IAMRX_RBW(M, HA, WL) do { IAMRX_RBG(M, HA, WL); if (xo) IAMRX_RBK(M, HA, WL, true); else IAMRX_RBK(M, HA, WL, false); } while (0)
+#define IAMRX_RB(M, HA) do { if (walls) IAMRX_RBW(M, HA, true); else IAMRX_RBW(M, HA, false); } while (0)
+        if (c.sig) IAMRX_RB(1, false); else if (has_a) IAMRX_RB(2, true); else IAMRX_RB(2, false);
 #undef IAMRX_RB
+#undef IAMRX_RBW
 #undef IAMRX_RBK
 #undef IAMRX_RBKL
 #undef IAMRX_RBG
     }
     if (rec) kernel_probe_end(PROBE_ABEC_GSRB);
 }
-void abec_gsrb_rb_nbr(const Geometry& g, const AbecCoef& c, MultiFab& pin, MultiFab& pout, const MultiFab& rhs, double omega, bool zero,
-                      const DomainBC* bcs, int nbc, int sel, hipStream_t on, bool acc)
+void abec_gsrb_rb_nbr(const Geometry& g, const AbecCoef& c, const AbecSmoothPlan& p, MultiFab& pin, MultiFab& pout, const MultiFab& rhs, double omega,
+                      bool zero, const DomainBC* bcs, int nbc, int sel, hipStream_t on, bool acc)
 {
-    IAMRX_ASSERT(abec_gsrb_rb_nbr_ok(g, c, pin, rhs, nbc, bcs) && pin.d_tab != pout.d_tab && pout.ngrow >= 1 && rhs.ncomp == pin.ncomp && pout.ncomp == pin.ncomp);
+    IAMRX_ASSERT(p.path == AbecSmoothPlan::RB_NBR && p.made_for(pin, rhs) && pin.d_tab != pout.d_tab && pout.ngrow >= 1 && rhs.ncomp == pin.ncomp && pout.ncomp == pin.ncomp);
     if (pin.nlocal() == 0) return;
-    // the density form with walls or ghost columns spills at 1024 threads (76 ... 116 bytes of scratch per lane): 12 wavefronts, see abec_gsrb_rb
-    const bool walls = !(g.periodic[0] && g.periodic[1] && g.periodic[2]);
-    const Layout& l = *pin.layout;
-    const int wpr = l.max_len[0] / 128;
-    const bool xo = l.max_len[0] != g.domain.len(0);
-    if (c.sig && (walls || xo) && 12 % wpr == 0 && 12 / wpr >= 3 && tune("GSRB_RB_NW12", 1) != 0) abec_gsrb_rb_nbr_nw<12>(g, c, pin, pout, rhs, omega, zero, bcs, nbc, sel, on, acc);
+    if (p.nw == 12) abec_gsrb_rb_nbr_nw<12>(g, c, pin, pout, rhs, omega, zero, bcs, nbc, sel, on, acc);
     else abec_gsrb_rb_nbr_nw<16>(g, c, pin, pout, rhs, omega, zero, bcs, nbc, sel, on, acc);
 }
 
-// IAMRX_ABEC_SIG (1): 0 = the smoother and the residual read the stored face coefficients also where AbecCoef::sig is given
-static bool abec_sig_on() { return tune("ABEC_SIG", 1) != 0; }
-
-bool abec_gsrb_zero_ok(const AbecCoef& c, const MultiFab& phi, int nbc, bool wrap, bool has_cf)
+// the device copy of the wall formulas of a level's (up to three) components for the colour passes.  (They travel as a pointer to a small
+// device table: 300 bytes more of kernel arguments cost the colour passes of the small levels 1 us each.)
+static const WallK* wallk_table(const Geometry& g, const DomainBC* bcs, int nbc)
 {
-    return tune("GSRB_ZERO", 1) != 0 && tune("GSRB1_NP", 1) > 0 && wrap && !has_cf && phi.ncomp == 1 && nbc == 1 && c.b[0]->ncomp == 1 && !c.tensor_eta;
-}
-
-// the colour passes of this level can apply the domain walls themselves (WallK): one box spanning a domain with non-periodic sides whose
-// boundary conditions the two-weight ghost formula covers, and a dispatch of abec_gsrb that ends in k_abec_gsrb / k_abec_gsrb1.  The caller
-// then fills periodic ghost cells only (if any) and passes walls_inkernel = true.  Rank-independent.
-bool abec_gsrb_walls_inkernel_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi, int nbc, const DomainBC* bcs, bool cf)
-{
-    if (tune("GSRB_WALLS_INKERNEL", 1) == 0 || cf || !bcs || nbc < 1 || phi.ncomp > 3 || phi.ngrow < 1) return false;
-    const Layout& l = *phi.layout;
-    if (l.boxes.size() != 1) return false;
-    const BoxD& b = l.boxes[0];
-    bool walls = false;
-    for (int d = 0; d < 3; ++d) {
-        if (b.lo[d] != g.domain.lo[d] || b.hi[d] != g.domain.hi[d] || b.len(d) < 2) return false;
-        if (!g.periodic[d]) walls = true;
-    }
-    if (!walls) return false;
-    for (int n = 0; n < phi.ncomp; ++n) { RbBC r; if (!rb_make_bc(g, bcs[n < nbc ? n : 0], r)) return false; }
-    // abec_gsrb's dispatch (below): the pair-marching kernels read the ghost cells
-    const bool uni = c.b_uniform && c.b[0]->ncomp == 1 && abec_sig_on();
-    const int np = (int)tune("GSRB1_NP", 1);
-    const int mode = (c.sig && abec_sig_on()) ? 1 : (uni ? 2 : 0);
-    const bool pair_ok = mode != 0 && tune("GSRB2", 1) != 0 && phi.ngrow >= 1 && (mode == 2 || c.sig->ngrow >= 1);
-    if (np > 0 && phi.ncomp == 1 && nbc == 1 && c.b[0]->ncomp == 1 && !c.tensor_eta) return !pair_ok;
-    if (uni && phi.ncomp > 1 && c.b[0]->ncomp == 1 && phi.ngrow >= 1 && tune("GSRB2", 1) != 0 && tune("GSRB2_MULTI", 0) != 0) return false;
-    return true;
-}
-
-void abec_gsrb(const Geometry& g, const AbecCoef& c, MultiFab& phi, const MultiFab& rhs, int redblack, double omega, const DomainBC* bcs, int nbc, bool shell_only,
-               bool wrap, const MultiFab* cfm, const CfTab* cftab, bool cf_maintain_ghosts, bool phi_is_zero, bool walls_inkernel)
-{
-    // (the wall formulas travel as a pointer to a small device table, null when off: 300 bytes more of kernel arguments cost the colour
-    // passes of the small levels 1 us each)
-    const WallK* wk = nullptr;
-    if (walls_inkernel) {
-        IAMRX_ASSERT(!shell_only && !wrap && cfm == nullptr && phi.ncomp <= 3);      // (the caller asked abec_gsrb_walls_inkernel_ok)
-        WallK h;
-        std::memset(&h, 0, sizeof(h));
-        h.on = 1;
-        for (int n = 0; n < 3; ++n) {
-            RbBC r;
-            rb_make_bc(g, bcs[n < nbc ? n : 0], r);
-            for (int d = 0; d < 3; ++d) {
-                h.per[d] = r.per[d];
-                h.c1lo[n][d] = r.c1lo[d]; h.c2lo[n][d] = r.c2lo[d]; h.c1hi[n][d] = r.c1hi[d]; h.c2hi[n][d] = r.c2hi[d];
-            }
-        }
-        // device copies of the few distinct tables of a run, kept for its life
-        static std::vector<std::pair<WallK, WallK*>> tabs;
-        for (auto& t : tabs) if (std::memcmp(&t.first, &h, sizeof(h)) == 0) wk = t.second;
-        if (!wk) {
-            WallK* d = nullptr;
-            IAMRX_HIP_CHECK(hipMalloc(&d, sizeof(WallK)));
-            IAMRX_HIP_CHECK(hipMemcpy(d, &h, sizeof(WallK), hipMemcpyHostToDevice));
-            tabs.emplace_back(h, d);
-            wk = d;
+    WallK h;
+    std::memset(&h, 0, sizeof(h));
+    h.on = 1;
+    for (int n = 0; n < 3; ++n) {
+        RbBC r;
+        rb_make_bc(g, bcs[n < nbc ? n : 0], r);
+        for (int d = 0; d < 3; ++d) {
+            h.per[d] = r.per[d];
+            h.c1lo[n][d] = r.c1lo[d]; h.c2lo[n][d] = r.c2lo[d]; h.c1hi[n][d] = r.c1hi[d]; h.c2hi[n][d] = r.c2hi[d];
         }
     }
-    IAMRX_ASSERT(!phi_is_zero || (!shell_only && abec_gsrb_zero_ok(c, phi, nbc, wrap || walls_inkernel, cfm != nullptr)));
+    // device copies of the few distinct tables of a run, kept for its life
+    static std::vector<std::pair<WallK, WallK*>> tabs;
+    for (auto& t : tabs) if (std::memcmp(&t.first, &h, sizeof(h)) == 0) return t.second;
+    WallK* d = nullptr;
+    IAMRX_HIP_CHECK(hipMalloc(&d, sizeof(WallK)));
+    IAMRX_HIP_CHECK(hipMemcpy(d, &h, sizeof(WallK), hipMemcpyHostToDevice));
+    tabs.emplace_back(h, d);
+    return d;
+}
+
+void abec_gsrb(const Geometry& g, const AbecCoef& c, const AbecColourForm& f, MultiFab& phi, const MultiFab& rhs, int redblack, double omega,
+               const DomainBC* bcs, int nbc, bool shell_only, bool phi_is_zero, const MultiFab* cfm, const CfTab* cftab)
+{
+    // the shell pass behind the fused sweep reads the ghost cells its caller has just filled: the general kernel, no images, no table
+    const bool wrap = f.wrap && !shell_only;
+    const WallK* wk = (f.walls_inkernel && !shell_only) ? wallk_table(g, bcs, nbc) : nullptr;
+    IAMRX_ASSERT(f.has_cf == (cfm && cftab) && (!phi_is_zero || (!shell_only && f.zero_ok)));
     const int zero = phi_is_zero ? 1 : 0;
     CfC1 cfc;
     cfc.maxorder = cftab ? cftab->maxorder : 2;
-    cfc.maintain = (cf_maintain_ghosts && cfm && cftab && phi.ncomp == 1 && !shell_only) ? 1 : 0;
+    cfc.maintain = (f.maintain && !shell_only) ? 1 : 0;
     for (int d = 0; d < 3; ++d) for (int q = 0; q < 3; ++q) {
         cfc.c1[d][q] = cftab ? cftab->c[d][q][1] : 0.0; cfc.c2[d][q] = cftab ? cftab->c[d][q][2] : 0.0; cfc.c3[d][q] = cftab ? cftab->c[d][q][3] : 0.0;
     }
-    const FabD* cft = (cfm && cftab) ? cfm->d_tab : nullptr;
+    const FabD* cft = f.has_cf ? cfm->d_tab : nullptr;
     if (phi.nlocal() == 0) return;
     auto& ctx = Context::get();
     const Layout& l = *phi.layout;
-    Tiling t = pair_tiling(l, 8);                 // (a flat tile list on a level of unequal boxes: launch.h)
+    const AbecColourForm::Kernel kernel = shell_only ? AbecColourForm::GENERAL : f.kernel;
+    const bool pairs = kernel == AbecColourForm::GSRB2 || kernel == AbecColourForm::GSRB2_PER_COMP;
+    const Tiling t = pair_tiling(l, pairs ? (int)tune("GSRB2_TZ", 32) : 8);                 // (a flat tile list on a level of unequal boxes: launch.h)
     const double dhx = c.beta / (g.dx[0] * g.dx[0]), dhy = c.beta / (g.dx[1] * g.dx[1]), dhz = c.beta / (g.dx[2] * g.dx[2]);
-    GsrbBC gb = make_gsrb_bc(g, bcs, nbc);
+    const GsrbBC gb = make_gsrb_bc(g, bcs, nbc);
     // the scalar (MAC projection / scalar diffusion) colour pass over whole boxes can be timed in place (bench.py)
     const bool rec = phi.ncomp == 1 && !shell_only && kernel_probe_begin(PROBE_ABEC_GSRB, (long)l.max_len[0] * l.max_len[1] * l.max_len[2]);
     BUni bu;
     for (int d = 0; d < 3; ++d) bu.v[d] = c.bu[d];
-    const bool uni = c.b_uniform && c.b[0]->ncomp == 1 && abec_sig_on();
-    // IAMRX_GSRB1_NP (1): planes in flight per thread of the pipelined one-component pass (0: the general kernel)
-    const int np = (int)tune("GSRB1_NP", 1);
-    const int mode = (c.sig && abec_sig_on()) ? 1 : (uni ? 2 : 0);
-    const bool pair_ok = mode != 0 && tune("GSRB2", 1) != 0 && phi.ngrow >= 1 && (mode == 2 || c.sig->ngrow >= 1);
-    // with coarse/fine faces the pipelined form would read a ghost cell that cf_maintain rewrote for the plane before: one plane in flight
-    if (np > 0 && phi.ncomp == 1 && !shell_only && nbc == 1 && c.b[0]->ncomp == 1 && !c.tensor_eta) {
-        const FabD *t0 = mode == 1 ? c.sig->d_tab : c.b[0]->d_tab, *t1 = mode == 1 ? c.sig->d_tab : c.b[1]->d_tab, *t2 = mode == 1 ? c.sig->d_tab : c.b[2]->d_tab;
-#define IAMRX_GS1(M, N) if (cft) IAMRX_GS1C(M, 1, true); else IAMRX_GS1C(M, N, false)
-#define IAMRX_GS1C(M, N, C) hipLaunchKernelGGL((k_abec_gsrb1<M, N, C>), t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, phi.d_tab, rhs.d_tab, \
-                           c.a ? c.a->d_tab : nullptr, t0, t1, t2, c.alpha, dhx, dhy, dhz, redblack, omega, gb, wrap ? 1 : 0, c.sig_comp, c.sig_scale, bu, cft, cfc, zero, wk)
-        // IAMRX_GSRB2 (1): the pair-marching kernel where the coefficients are not arrays (needs a ghost layer for its 16-byte loads)
-        if (pair_ok) {
-            Tiling t2 = pair_tiling(l, (int)tune("GSRB2_TZ", 32));
-#define IAMRX_GS2(M, C, MT, SG, SC, SS) hipLaunchKernelGGL((k_abec_gsrb2<M, C, MT>), t2.grid(), Tiling::block(), 0, ctx.stream, t2, l.d_boxes, phi.d_tab, rhs.d_tab, \
-                                   c.a ? c.a->d_tab : nullptr, SG, c.alpha, dhx, dhy, dhz, redblack, omega, gb, wrap ? 1 : 0, SC, SS, bu, cft, cfc, zero, 0, 0)
-            const bool mt = cft && cfc.maintain;
-            // one box strictly inside the domain (no neighbour box, no domain face, no periodic image next to it): all of its ghost cells are
-            // coarse/fine ghost cells and the maintaining colour pass takes the masks as constants.  IAMRX_GSRB2_ALLCF = 0: loads them.
-            bool allcf = mt && l.boxes.size() == 1 && l.nlocal() == 1 && tune("GSRB2_ALLCF", 1) != 0;
-            for (int d = 0; d < 3 && allcf; ++d) allcf = l.boxes[0].lo[d] > g.domain.lo[d] && l.boxes[0].hi[d] < g.domain.hi[d];
-            if (allcf) {
-                if (mode == 1) hipLaunchKernelGGL((k_abec_gsrb2<1, true, true, true>), t2.grid(), Tiling::block(), 0, ctx.stream, t2, l.d_boxes, phi.d_tab, rhs.d_tab,
-                                   c.a ? c.a->d_tab : nullptr, c.sig->d_tab, c.alpha, dhx, dhy, dhz, redblack, omega, gb, wrap ? 1 : 0, c.sig_comp, c.sig_scale, bu, cft, cfc, zero, 0, 0);
-                else hipLaunchKernelGGL((k_abec_gsrb2<2, true, true, true>), t2.grid(), Tiling::block(), 0, ctx.stream, t2, l.d_boxes, phi.d_tab, rhs.d_tab,
-                                   c.a ? c.a->d_tab : nullptr, nullptr, c.alpha, dhx, dhy, dhz, redblack, omega, gb, wrap ? 1 : 0, 0, 1.0, bu, cft, cfc, zero, 0, 0);
-            }
-            else if (mode == 1) {
-                if (mt) IAMRX_GS2(1, true, true, c.sig->d_tab, c.sig_comp, c.sig_scale);
-                else if (cft) IAMRX_GS2(1, true, false, c.sig->d_tab, c.sig_comp, c.sig_scale);
-                else IAMRX_GS2(1, false, false, c.sig->d_tab, c.sig_comp, c.sig_scale);
-            } else {
-                if (mt) IAMRX_GS2(2, true, true, nullptr, 0, 1.0);
-                else if (cft) IAMRX_GS2(2, true, false, nullptr, 0, 1.0);
-                else IAMRX_GS2(2, false, false, nullptr, 0, 1.0);
-            }
-#undef IAMRX_GS2
-        }
-        else if (np >= 4) { if (mode == 1) { IAMRX_GS1(1, 4); } else if (mode == 2) { IAMRX_GS1(2, 4); } else { IAMRX_GS1(0, 4); } }
-        else if (np >= 2) { if (mode == 1) { IAMRX_GS1(1, 2); } else if (mode == 2) { IAMRX_GS1(2, 2); } else { IAMRX_GS1(0, 2); } }
-        else { if (mode == 1) { IAMRX_GS1(1, 1); } else if (mode == 2) { IAMRX_GS1(2, 1); } else { IAMRX_GS1(0, 1); } }
+    const FabD* at = c.a ? c.a->d_tab : nullptr;
+    // M: the coefficient mode of the launch (1: everything from the density array; its constants travel, the others get 0 and 1)
+#define IAMRX_BT(M, d) (M == 1 ? c.sig->d_tab : c.b[d]->d_tab)
+#define IAMRX_SC(M) (M == 1 ? c.sig_comp : 0), (M == 1 ? c.sig_scale : 1.0)
+#define IAMRX_PER_MODE(m, L) switch (m) { case 1: L(1); break; case 2: L(2); break; default: L(0); break; }
+    switch (kernel) {
+    case AbecColourForm::GSRB1: {
+#define IAMRX_GS1(M, N, C) hipLaunchKernelGGL((k_abec_gsrb1<M, N, C>), t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, phi.d_tab, rhs.d_tab, at, \
+                                  IAMRX_BT(M, 0), IAMRX_BT(M, 1), IAMRX_BT(M, 2), c.alpha, dhx, dhy, dhz, redblack, omega, gb, wrap ? 1 : 0, c.sig_comp, c.sig_scale, bu, cft, cfc, zero, wk)
+#define IAMRX_GS1N(M) switch (cft ? 0 : f.np) { case 0: IAMRX_GS1(M, 1, true); break; case 4: IAMRX_GS1(M, 4, false); break; case 2: IAMRX_GS1(M, 2, false); break; default: IAMRX_GS1(M, 1, false); break; }
+        IAMRX_PER_MODE(f.mode, IAMRX_GS1N)
+#undef IAMRX_GS1N
 #undef IAMRX_GS1
-#undef IAMRX_GS1C
+        break;
     }
-    else if (phi.ncomp == 1 && c.sig && !c.tensor_eta && abec_sig_on())
-        hipLaunchKernelGGL((k_abec_gsrb<false, 1>), t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, phi.d_tab, rhs.d_tab,
-                           c.a ? c.a->d_tab : nullptr, c.sig->d_tab, c.sig->d_tab, c.sig->d_tab,
-                           c.alpha, dhx, dhy, dhz, redblack, omega, 1, 1, gb, shell_only ? 1 : 0, 0, wrap ? 1 : 0, cft, cfc, c.sig_comp, c.sig_scale, BUni(), wk);
-    else if (uni && phi.ncomp > 1 && !shell_only && c.b[0]->ncomp == 1 && phi.ngrow >= 1 && tune("GSRB2", 1) != 0 && tune("GSRB2_MULTI", 0) != 0) {
-        // IAMRX_GSRB2_MULTI = 1 (off by default: measured equal, 3 x 112 us against 336 us at 256^3 -- both forms move the half-used lines of
-        // the red-black layout at the achievable HBM rate): several components with constant coefficients (the tensor solves of a
-        // constant-viscosity run, the unit-coefficient tensor solve of diffuse_tensor_Vsync) as one pair-marching launch per component
-        // with its own constants b_d (x 4/3 on the normal component of the tensor operator) -- the expressions of k_abec_gsrb<true, 2>
-        Tiling t2 = pair_tiling(l, (int)tune("GSRB2_TZ", 32));
+    case AbecColourForm::GSRB2: {
+#define IAMRX_GS2(M, C, MT, AL) hipLaunchKernelGGL((k_abec_gsrb2<M, C, MT, AL>), t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, phi.d_tab, rhs.d_tab, at, \
+                                  M == 1 ? c.sig->d_tab : nullptr, c.alpha, dhx, dhy, dhz, redblack, omega, gb, wrap ? 1 : 0, IAMRX_SC(M), bu, cft, cfc, zero, 0, 0)
+#define IAMRX_GS2F(M) switch (f.allcf ? 3 : (cft && cfc.maintain) ? 2 : cft ? 1 : 0) { case 3: IAMRX_GS2(M, true, true, true); break; case 2: IAMRX_GS2(M, true, true, false); break; \
+                                  case 1: IAMRX_GS2(M, true, false, false); break; default: IAMRX_GS2(M, false, false, false); break; }
+        if (f.mode == 1) IAMRX_GS2F(1) else IAMRX_GS2F(2)
+#undef IAMRX_GS2F
+#undef IAMRX_GS2
+        break;
+    }
+    case AbecColourForm::GSRB2_PER_COMP:
         for (int n = 0; n < phi.ncomp; ++n) {
-            BUni bn;
-            for (int d = 0; d < 3; ++d) bn.v[d] = bu.v[d] * ((c.tensor_eta && n == d) ? 4.0 / 3.0 : 1.0);
+            const BUni bn = comp_buni(c, n);
             const int bq = gb.nbc == 1 ? 0 : (n < 3 ? n : 0);
-#define IAMRX_GS2M(C) hipLaunchKernelGGL((k_abec_gsrb2<2, C, false>), t2.grid(), Tiling::block(), 0, ctx.stream, t2, l.d_boxes, phi.d_tab, rhs.d_tab, \
-                                  c.a ? c.a->d_tab : nullptr, nullptr, c.alpha, dhx, dhy, dhz, redblack, omega, gb, wrap ? 1 : 0, 0, 1.0, bn, cft, cfc, 0, n, bq)
+#define IAMRX_GS2M(C) hipLaunchKernelGGL((k_abec_gsrb2<2, C, false>), t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, phi.d_tab, rhs.d_tab, at, \
+                                  nullptr, c.alpha, dhx, dhy, dhz, redblack, omega, gb, wrap ? 1 : 0, 0, 1.0, bn, cft, cfc, 0, n, bq)
             if (cft) IAMRX_GS2M(true); else IAMRX_GS2M(false);
 #undef IAMRX_GS2M
         }
+        break;
+    case AbecColourForm::GENERAL: {
+#define IAMRX_GS(MC, M) hipLaunchKernelGGL((k_abec_gsrb<MC, M>), t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, phi.d_tab, rhs.d_tab, at, \
+                               IAMRX_BT(M, 0), IAMRX_BT(M, 1), IAMRX_BT(M, 2), c.alpha, dhx, dhy, dhz, redblack, omega, phi.ncomp, M == 0 ? c.b[0]->ncomp : 1, gb, shell_only ? 1 : 0, \
+                               c.tensor_eta, wrap ? 1 : 0, cft, cfc, IAMRX_SC(M), M == 2 ? bu : BUni(), wk)
+#define IAMRX_GSM(M) if (f.gen_mc) IAMRX_GS(true, M); else IAMRX_GS(false, M)
+        if (f.gen_mode == 1) IAMRX_GS(false, 1); else if (f.gen_mode == 2) { IAMRX_GSM(2); } else { IAMRX_GSM(0); }
+#undef IAMRX_GSM
+#undef IAMRX_GS
+        break;
     }
-    else if (uni && phi.ncomp > 1)
-        hipLaunchKernelGGL((k_abec_gsrb<true, 2>), t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, phi.d_tab, rhs.d_tab,
-                           c.a ? c.a->d_tab : nullptr, c.b[0]->d_tab, c.b[1]->d_tab, c.b[2]->d_tab,
-                           c.alpha, dhx, dhy, dhz, redblack, omega, phi.ncomp, 1, gb, shell_only ? 1 : 0, c.tensor_eta, wrap ? 1 : 0, cft, cfc, 0, 1.0, bu, wk);
-    else if (uni)
-        hipLaunchKernelGGL((k_abec_gsrb<false, 2>), t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, phi.d_tab, rhs.d_tab,
-                           c.a ? c.a->d_tab : nullptr, c.b[0]->d_tab, c.b[1]->d_tab, c.b[2]->d_tab,
-                           c.alpha, dhx, dhy, dhz, redblack, omega, phi.ncomp, 1, gb, shell_only ? 1 : 0, c.tensor_eta, wrap ? 1 : 0, cft, cfc, 0, 1.0, bu, wk);
-    else if (phi.ncomp > 1 && c.b[0]->ncomp == 1)
-        hipLaunchKernelGGL((k_abec_gsrb<true, 0>), t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, phi.d_tab, rhs.d_tab,
-                           c.a ? c.a->d_tab : nullptr, c.b[0]->d_tab, c.b[1]->d_tab, c.b[2]->d_tab,
-                           c.alpha, dhx, dhy, dhz, redblack, omega, phi.ncomp, c.b[0]->ncomp, gb, shell_only ? 1 : 0, c.tensor_eta, wrap ? 1 : 0, cft, cfc, 0, 1.0, BUni(), wk);
-    else
-        hipLaunchKernelGGL((k_abec_gsrb<false, 0>), t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, phi.d_tab, rhs.d_tab,
-                           c.a ? c.a->d_tab : nullptr, c.b[0]->d_tab, c.b[1]->d_tab, c.b[2]->d_tab,
-                           c.alpha, dhx, dhy, dhz, redblack, omega, phi.ncomp, c.b[0]->ncomp, gb, shell_only ? 1 : 0, c.tensor_eta, wrap ? 1 : 0, cft, cfc, 0, 1.0, BUni(), wk);
+    }
+#undef IAMRX_PER_MODE
+#undef IAMRX_SC
+#undef IAMRX_BT
     if (rec) kernel_probe_end(PROBE_ABEC_GSRB);
 }
 

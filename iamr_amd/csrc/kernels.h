@@ -96,44 +96,82 @@ void cf_interp_edges(MultiFab& bcval, const MultiFab& cpatch, const MultiFab& cf
 // bcval(ghost cells with mask 1) = coarse data of cpatch (coarsened layout, 1 ghost cell) interpolated in the tangential directions
 // (InterpBndryData::setBndryValues, third order, ratio 2); cfm needs 2 ghost cells
 void cf_interp_bndry(MultiFab& bcval, const MultiFab& cpatch, const MultiFab& cfm, int ratio);
-// bcs: nbc DomainBC entries (nbc == 1: same BC for all components; nbc == ncomp: one per component, MLTensorOp::setDomainBC)
-void abec_gsrb(const Geometry& g, const AbecCoef& c, MultiFab& phi, const MultiFab& rhs, int redblack, double omega, const DomainBC* bcs, int nbc,
-               bool shell_only = false, bool wrap = false, const MultiFab* cfm = nullptr, const CfTab* cftab = nullptr, bool cf_maintain_ghosts = false,
-               bool phi_is_zero = false, bool walls_inkernel = false);
-// walls_inkernel: the pass applies the homogeneous domain boundary conditions itself (no ghost cell of phi is read in a non-periodic direction:
-// the caller fills periodic ghost cells only) -- allowed where this returns true
-bool abec_gsrb_walls_inkernel_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi, int nbc, const DomainBC* bcs, bool cf);
+// ---- the smoother path of a cell-centred multigrid level ----
+// What the choice rests on, as host data (no array, no device).  boxes is the level's GLOBAL box list: the path is decided from it, so
+// every rank takes the same one (a rank without a box launches nothing).  max_len / nlocal: Layout's.
+struct AbecLevel {
+    const std::vector<BoxD>* boxes = nullptr;
+    int nlocal = 0, max_len[3] = {0, 0, 0};
+    int ncomp = 1;
+    int phi_ngrow = 1, rhs_ngrow = 0, sig_ngrow = 0, a_ngrow = 0;      // ghost widths: correction, right-hand side, density, a-term
+    bool sig = false, b_uniform = false, has_a = false, tensor_eta = false;      // the coefficient form (AbecCoef); has_a: a given and alpha != 0
+    bool tensor = false;                                                // the level belongs to a tensor solve (no coarse/fine maintenance)
+    int b_ncomp = 1;
+    int nbc = 0;
+    const DomainBC* bcs = nullptr;         // nbc sets: one per component, or one for all; null: fully periodic levels only
+    bool has_cf = false;                   // coarse/fine faces (mask and table at hand)
+    bool finest = true;                    // level 0 of its hierarchy
+};
+AbecLevel abec_level(const AbecCoef& c, const MultiFab& phi, int rhs_ngrow, int nbc, const DomainBC* bcs, bool has_cf = false, bool finest = true);
+// One colour pass (abec_gsrb): the kernel and what it is told.  Filled by abec_smooth_plan, or by abec_colour_form for a caller that fills
+// the ghost cells itself.
+struct AbecColourForm {
+    enum Kernel { GENERAL, GSRB1, GSRB2, GSRB2_PER_COMP } kernel = GENERAL;
+    int mode = 0;                 // GSRB1 / GSRB2 coefficients: 0 stored face arrays, 1 recomputed from the density, 2 the constants bu
+    int np = 1;                   // GSRB1: planes in flight (1, 2 or 4)
+    bool gen_mc = false;          // the general kernel's <MC, mode> (also what a shell pass runs whatever `kernel` says)
+    int gen_mode = 0;
+    bool has_cf = false, maintain = false, allcf = false;     // coarse/fine faces; the passes keep their ghost cells current; all ghost cells are such
+    bool wrap = false;            // one box spanning a periodic domain: images read from the valid cells, no ghost fill
+    bool walls_inkernel = false;  // one box spanning a domain with walls: the pass applies them (WallK), the caller fills periodic ghost cells only
+    bool zero_ok = false;         // the first pass may be told that phi is zero instead of phi being set to zero (no ghost cell is read)
+};
+struct AbecSmoothPlan {
+    enum Path { COLOUR, RB_BOX, RB_CF, RB_NBR, FUSED_SHELL } path = COLOUR;
+    AbecColourForm colour;        // COLOUR, and the shell pass of FUSED_SHELL
+    int nw = 16;                  // RB_*: wavefronts per workgroup (12 or 16)
+    bool nbr_splits = false;      // RB_NBR: the sweep can be issued in two parts (tiles that read no ghost cell / the others)
+    bool zero_first = false;      // the first sweep of a smoothing call on this level may start from zero
+    int ncomp = 1, phi_ngrow = 1, rhs_ngrow = 0;      // what the plan was made for (the launchers assert it)
+    bool sweep_kernel() const { return path == RB_BOX || path == RB_CF || path == RB_NBR; }
+    bool made_for(const MultiFab& phi, const MultiFab& rhs) const { return phi.ncomp == ncomp && phi.ngrow == phi_ngrow && rhs.ngrow == rhs_ngrow; }
+};
+// THE decision: which of the five ways a smoothing call on this level runs, made once per level per solve
+AbecSmoothPlan abec_smooth_plan(const Geometry& g, const AbecLevel& lv);
+// the colour-pass part alone.  wrap: the level is one periodic box (periodic_wrap_ok); walls_inkernel: the passes may apply the walls
+// themselves where they can (false: the caller fills every ghost cell)
+AbecColourForm abec_colour_form(const Geometry& g, const AbecLevel& lv, bool wrap = false, bool walls_inkernel = false);
+// one red (0) or black (1) pass.  bcs: nbc DomainBC entries (nbc == 1: same BC for all components; nbc == ncomp: one per component,
+// MLTensorOp::setDomainBC).  shell_only: the black cells on box surfaces only (behind abec_gsrb_fused).  phi_is_zero: needs f.zero_ok.
+void abec_gsrb(const Geometry& g, const AbecCoef& c, const AbecColourForm& f, MultiFab& phi, const MultiFab& rhs, int redblack, double omega,
+               const DomainBC* bcs, int nbc, bool shell_only = false, bool phi_is_zero = false, const MultiFab* cfm = nullptr, const CfTab* cftab = nullptr);
 // the last two levels of a cell-centred V-cycle in one single-workgroup launch (k_abec_tail, k_abec.hip): pre-smoothing from zero, residual,
 // restriction, bottom solve, prolongation, post-smoothing -- the doubles of the launches it replaces
 bool abec_tail_ok(const Geometry& gF, const Layout& lF, const Geometry& gC, const Layout& lC, const AbecCoef& cF, const DomainBC* bcs, int nbc, int ncomp);
 void abec_tail_solve(const Geometry& gF, const AbecCoef& cF, MultiFab& corF, const MultiFab& resF, const Geometry& gC, const AbecCoef& cC,
                      const DomainBC& bc, bool singular, double eps_rel, int maxiter, int nub, int nuf, int nu1, int nu2, double omega, int* d_iters);
-// phi_is_zero: the pass may be told that phi is identically zero (the first pass on a multigrid correction) INSTEAD of phi being set to
-// zero in front of it -- it then reads no phi and writes every cell (the active colour its update, the other colour zero) -- if this returns
-// true for the same arguments (one component, one-component coefficients, one box spanning a periodic domain: no ghost cell is read)
 // restriction of the residual rhs - A phi straight onto the coarsened layout (one pass, the fine residual is not stored): usable if ..._ok
 bool abec_residual_reads_no_ghosts(const Geometry& g, const AbecCoef& c, const MultiFab& out, const MultiFab& phi, const MultiFab& rhs, bool restrict_form);
 bool abec_resid_restrict_ok(const AbecCoef& c, const MultiFab& phi, const MultiFab& rhs);
 void abec_resid_restrict(const Geometry& g, const AbecCoef& c, MultiFab& crse, const MultiFab& phi, const MultiFab& rhs);
-bool abec_gsrb_zero_ok(const AbecCoef& c, const MultiFab& phi, int nbc, bool wrap, bool has_cf);
-// one red + black sweep in ONE launch, out of place (pin -> pout), on a level that is one box spanning a periodic domain (k_abec_gsrb_rb: the
-// doubles of the two colour passes, a third of their HBM traffic); zero: pin is identically zero and is not read
-bool abec_gsrb_rb_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi, int nbc, const DomainBC* bcs = nullptr);
-// cf: the level is a refined box strictly inside its domain (abec_gsrb_rb_cf_ok): its coarse/fine ghost formula, evaluated inside the kernel
-void abec_gsrb_rb(const Geometry& g, const AbecCoef& c, const MultiFab& pin, MultiFab& pout, const MultiFab& rhs, double omega, bool zero,
-                  const DomainBC* bcs = nullptr, int nbc = 0, const CfTab* cf = nullptr, bool acc = false);
+// one red + black sweep in ONE launch, out of place (pin -> pout), on a level that is one box spanning its domain (k_abec_gsrb_rb: the
+// doubles of the two colour passes, a third of their HBM traffic); zero: pin is identically zero and is not read.  p: RB_BOX, or RB_CF
+// with cf, the level's coarse/fine ghost formula, evaluated inside the kernel (a refined box strictly inside its domain)
 // (acc: pout is the SOLUTION of the running solve and receives pout + the swept correction -- the last sweep of a V-cycle, k_abec.hip ACC)
+void abec_gsrb_rb(const Geometry& g, const AbecCoef& c, const AbecSmoothPlan& p, const MultiFab& pin, MultiFab& pout, const MultiFab& rhs, double omega,
+                  bool zero, const DomainBC* bcs = nullptr, int nbc = 0, const CfTab* cf = nullptr, bool acc = false);
+// the same sweep on a level of several boxes that covers its domain (RB_NBR: a chopped level, the boxes of a sharded level): k_abec_rb_ghost +
+// k_abec_gsrb_rb<.., NBR>, one two-layer ghost fill of phi per sweep in front of it (the caller's).
+// sel 0: the whole sweep; 1: only the tiles that read no ghost cell (no k_abec_rb_ghost launch); 2: k_abec_rb_ghost + the other tiles
+// (p.nbr_splits: parts 1 and 2 are both non-empty and the level has no ghost columns in x); on: the stream (null: the context's)
+void abec_gsrb_rb_nbr(const Geometry& g, const AbecCoef& c, const AbecSmoothPlan& p, MultiFab& pin, MultiFab& pout, const MultiFab& rhs, double omega,
+                      bool zero, const DomainBC* bcs, int nbc, int sel = 0, hipStream_t on = nullptr, bool acc = false);
+// the planner's answer for the arrays at hand (the finest level of a hierarchy).  level_ok: for the widths the sweep on several boxes wants
+// (phi two ghost layers, rhs and the a-term one, the density two), before the arrays exist
+bool abec_gsrb_rb_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi, int nbc, const DomainBC* bcs = nullptr);
 bool abec_gsrb_rb_cf_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi);
-// the same sweep on a level of several boxes that covers its domain (a chopped level, the boxes of a sharded level): k_abec_rb_ghost +
-// k_abec_gsrb_rb<.., NBR>, one two-layer ghost fill of phi per sweep in front of it (the caller's).  level_ok: the layout / boundary
-// conditions admit it (the caller then gives phi two ghost layers, rhs and the a-term one, the density two); ok: these arrays do
-bool abec_gsrb_rb_nbr_level_ok(const Geometry& g, const Layout& l, int ncomp, bool sig_form, bool has_a, int nbc, const DomainBC* bcs);
 bool abec_gsrb_rb_nbr_ok(const Geometry& g, const AbecCoef& c, const MultiFab& phi, const MultiFab& rhs, int nbc, const DomainBC* bcs);
-// sel 0: the whole sweep; 1: only the tiles that read no ghost cell (no k_abec_rb_ghost launch); 2: k_abec_rb_ghost + the other tiles;
-// on: the stream (null: the context's).  splits: parts 1 and 2 are both non-empty (and the level has no ghost columns in x)
-void abec_gsrb_rb_nbr(const Geometry& g, const AbecCoef& c, MultiFab& pin, MultiFab& pout, const MultiFab& rhs, double omega, bool zero,
-                      const DomainBC* bcs, int nbc, int sel = 0, hipStream_t on = nullptr, bool acc = false);
-bool abec_gsrb_rb_nbr_splits(const Geometry& g, const Layout& l);
+bool abec_gsrb_rb_nbr_level_ok(const Geometry& g, const Layout& l, int ncomp, bool sig_form, bool has_a, int nbc, const DomainBC* bcs);
 // fused red+black sweep, out of place; see k_abec.hip (the caller refreshes the ghosts of phi_out and finishes the black cells
 // on box surfaces with abec_gsrb(..., 1, ..., shell_only = true))
 void abec_gsrb_fused(const Geometry& g, const AbecCoef& c, const MultiFab& phi_in, MultiFab& phi_out, const MultiFab& rhs, double omega,

@@ -159,16 +159,14 @@ public:
     AbecCoef smoother_coef(int l) const;   // the smoother acts on the ABec part; cross terms enter through the residual
     const Geometry& geom(int l) const { return m_lev[l].g; }
     void applyBC(int l, MultiFab& phi, bool inhomog, const MultiFab* bcval, bool corners = true);
-    // cf_ghosts_current: the coarse/fine ghost cells are already what a fill would write (kept so by the passes themselves, k_abec.hip cf_maintain)
-    void smooth(int l, MultiFab& sol, const MultiFab& rhs, bool skip_fill, bool cf_ghosts_current = false, bool sol_is_zero = false);
-    bool zero_first_pass_ok(int l, const MultiFab& sol) const;   // the first colour pass can take the place of sol.setVal(0) (abec_gsrb_zero_ok)
-    // nsweeps red+black sweeps; uses the fused out-of-place kernel (ping-pong with a level buffer) where it applies
+    // The smoothing calls act on the level's own correction and residual (cor, res), by the level's plan (Level::plan: prepare()).
+    // smooth: one sweep of two colour passes.  cf_ghosts_current: the coarse/fine ghost cells are already what a fill would write (kept so
+    // by the passes themselves, k_abec.hip cf_maintain)
+    void smooth(int l, bool skip_fill, bool cf_ghosts_current = false, bool sol_is_zero = false);
+    // nsweeps red+black sweeps; the out-of-place kernels ping-pong with a level buffer
     // acc (finest level, the last smoothing call of a V-cycle): the solution of the running solve; where the sweep kernel runs its last sweep
-    // stores acc + correction into acc (m_acc_done is set: the caller skips its `sol += cor`; sol is then one sweep behind and unused)
-    void smooth_n(int l, MultiFab& sol, const MultiFab& rhs, int nsweeps, bool skip_first_fill, bool sol_is_zero = false, MultiFab* acc = nullptr);
-    bool fused_smoother_ok(int l) const;
-    bool nbr_sweep_ok(int l, const MultiFab& sol, const MultiFab& rhs) const;
-    bool cf_sweep_ok(int l, const MultiFab& sol) const;
+    // stores acc + correction into acc (m_acc_done is set: the caller skips its `sol += cor`; cor is then one sweep behind and unused)
+    void smooth_n(int l, int nsweeps, bool skip_first_fill, bool sol_is_zero = false, MultiFab* acc = nullptr);
     void vcycle(MGStats& st);
     MultiFab& res(int l) { return m_lev[l].res; }
     MultiFab& cor(int l) { return m_lev[l].cor; }
@@ -178,7 +176,7 @@ private:
         MultiFab a, b[3];          // owned (coarse levels)
         MultiFab cor, res, rescor;
         MultiFab buf;              // second buffer of the fused (out-of-place) GSRB sweeps
-        int wk_flag = -1;          // the colour passes of this level apply the domain walls themselves (abec_gsrb_walls_inkernel_ok; -1: not asked yet)
+        AbecSmoothPlan plan;       // how a smoothing call on this level runs: decided in prepare(), once per solve
         MultiFab cfm;              // coarse/fine mask (levels that do not cover the domain), see cf_build_mask
         CfTab cftab;
     };

@@ -260,6 +260,8 @@ void CellMG::prepare()
                 coarsen_into(L.b[d], face_type(d), fb->ncomp, [&](MultiFab& c) { face_avgdown(c, *fb, d); });
             }
         }
+        // everything a smoothing call on this level depends on is known now: its path is chosen here, once per solve (coef: with the tensor flag)
+        L.plan = abec_smooth_plan(L.g, abec_level(coef(l), L.cor, L.res.ngrow, (int)m_bcn.size(), m_bcn.data(), m_cf, l == 0));
     }
     bottom_direct_prepare();
 }
@@ -304,86 +306,27 @@ static double dd_omega()
     return tune("MG_DD_OMEGA", 1.0);
 }
 
-// one-component coarse/fine levels: the colour passes keep the coarse/fine ghost cells current themselves (cf_maintain, k_abec.hip), so only
-// the first pass of a smoothing call needs the k_cf_fill launch; IAMRX_CF_MAINTAIN=0: a fill in front of every pass
-static bool cf_maintain_on()
+void CellMG::smooth(int l, bool skip_fill, bool cf_ghosts_current, bool sol_is_zero)
 {
-    return tune("CF_MAINTAIN", 1) != 0;
-}
-
-bool CellMG::zero_first_pass_ok(int l, const MultiFab& sol) const
-{
-    if (m_dd_sweeps > 0 || fused_smoother_ok(l)) return false;
-    const AbecCoef c = smoother_coef(l);
-    const bool wrap = !m_cf && periodic_wrap_ok(m_lev[l].g, *m_lev[l].layout, 2);
-    // (walls applied inside the colour passes: the first pass from zero reads no ghost cell either)
-    const bool wk = !wrap && abec_gsrb_walls_inkernel_ok(m_lev[l].g, c, sol, (int)m_bcn.size(), m_bcn.data(), m_cf);
-    return abec_gsrb_zero_ok(c, sol, (int)m_bcn.size(), wrap || wk, m_cf);
-}
-
-void CellMG::smooth(int l, MultiFab& sol, const MultiFab& rhs, bool skip_fill, bool cf_ghosts_current, bool sol_is_zero)
-{
-    const AbecCoef c = smoother_coef(l);
-    // one box spanning a fully periodic domain: the kernel reads the periodic images from the valid cells, no ghost fills
-    const bool wrap = !m_cf && periodic_wrap_ok(m_lev[l].g, *m_lev[l].layout, 2);
-    const bool maint = m_cf && m_ncomp == 1 && !m_tensor && cf_maintain_on();
-    // one box spanning a domain with walls: the colour passes apply the wall conditions themselves (WallK, k_abec.hip) -- no k_abec_bc launch
-    // in front of a pass; periodic directions (if any) keep their ghost fill
-    if (m_lev[l].wk_flag < 0) m_lev[l].wk_flag = (!wrap && abec_gsrb_walls_inkernel_ok(m_lev[l].g, c, sol, (int)m_bcn.size(), m_bcn.data(), m_cf)) ? 1 : 0;
-    const bool wk = m_lev[l].wk_flag == 1;
-    const bool wk_per = wk && (m_lev[l].g.periodic[0] || m_lev[l].g.periodic[1] || m_lev[l].g.periodic[2]);
+    Level& L = m_lev[l];
+    MultiFab& sol = L.cor;
+    const AbecColourForm& f = L.plan.colour;
+    const bool periodic_fill = L.g.periodic[0] || L.g.periodic[1] || L.g.periodic[2];
     for (int rb = 0; rb < 2; ++rb) {
-        if (wk) { if (!skip_fill && wk_per) sol.FillBoundary(m_lev[l].g); }
-        else if (!skip_fill && !wrap) {
-            if (maint && (cf_ghosts_current || rb == 1)) {        // everything but the coarse/fine ghost cells
-                sol.FillBoundary(m_lev[l].g);
-                abec_apply_domain_bc(m_lev[l].g, sol, m_bcn[0], false, nullptr);
+        // in-kernel walls: no k_abec_bc launch in front of a pass; periodic directions (if any) keep their ghost fill.  wrap: no fill at all
+        if (f.walls_inkernel) { if (!skip_fill && periodic_fill) sol.FillBoundary(L.g); }
+        else if (!skip_fill && !f.wrap) {
+            if (f.maintain && (cf_ghosts_current || rb == 1)) {        // everything but the coarse/fine ghost cells
+                sol.FillBoundary(L.g);
+                abec_apply_domain_bc(L.g, sol, m_bcn[0], false, nullptr);
             } else applyBC(l, sol, false, nullptr, false);
         }
         // diagonally dominant shortcut: plain Gauss-Seidel -- over-relaxation leaves a (1 - omega) = 0.15 floor per sweep on an operator
         // that is almost its diagonal, where omega = 1 contracts by the square of the Jacobi factor
-        abec_gsrb(m_lev[l].g, c, sol, rhs, rb, m_dd_sweeps > 0 ? dd_omega() : m_o.omega, m_bcn.data(), (int)m_bcn.size(), false, wrap, m_cf ? &m_lev[l].cfm : nullptr,
-                  m_cf ? &m_lev[l].cftab : nullptr, maint, sol_is_zero && rb == 0, wk);
+        abec_gsrb(L.g, smoother_coef(l), f, sol, L.res, rb, m_dd_sweeps > 0 ? dd_omega() : m_o.omega, m_bcn.data(), (int)m_bcn.size(), false, sol_is_zero && rb == 0,
+                  m_cf ? &L.cfm : nullptr, m_cf ? &L.cftab : nullptr);
         skip_fill = false;
     }
-}
-
-// The fused sweep refreshes the ghost cells once per sweep, from a state in which the black cells off the box surfaces are
-// already updated.  That equals the reference sequence (ghost fill in front of each colour) only if a ghost value depends on
-// nothing but the first cell inside the box: periodic / neighbour images, Neumann, and Dirichlet extrapolation of order <= 2.
-bool CellMG::fused_smoother_ok(int l) const
-{
-    // opt-in: on MI355X the single-pass kernel (62 B/cell of HBM traffic instead of 130) is still slower than the two colour
-    // passes (233 VGPRs -> 2 waves/SIMD with three barriers per plane: 0.41 ms vs 2 x 0.18 ms at 256^3)
-    const bool on = tune("GSRB_FUSED", 0) != 0;
-    if (!on || m_cf) return false;
-    const Level& L = m_lev[l];
-    for (int d = 0; d < 3; ++d) {
-        if (L.layout->max_len[d] < 16) return false;
-        if (L.g.periodic[d]) continue;
-        for (const auto& b : m_bcn)
-            for (int side = 0; side < 2; ++side) {
-                const int t = side == 0 ? b.lo[d] : b.hi[d];
-                if (t == lo_neumann) continue;
-                if (t == lo_dirichlet && std::min(L.g.domain.len(d) + 1, b.maxorder) <= 2) continue;
-                return false;
-            }
-    }
-    return true;
-}
-
-// smooth_n runs the multi-box sweep kernel on this level (the finest level of a hierarchy prepared for it, arrays with its ghost widths)
-bool CellMG::nbr_sweep_ok(int l, const MultiFab& sol, const MultiFab& rhs) const
-{
-    if (l != 0 || !m_nbr || m_cf) return false;
-    return abec_gsrb_rb_nbr_ok(m_lev[l].g, smoother_coef(l), sol, rhs, (int)m_bcn.size(), m_bcn.data());
-}
-
-// smooth_n runs the sweep kernel with in-kernel coarse/fine faces on this level (a refined box strictly inside its domain, finest level)
-bool CellMG::cf_sweep_ok(int l, const MultiFab& sol) const
-{
-    if (l != 0 || !m_cf) return false;
-    return abec_gsrb_rb_cf_ok(m_lev[l].g, smoother_coef(l), sol);
 }
 
 // Out-of-place sweeps ping-pong between sol and buf.  From a zero start the first sweep reads no input: an odd number of sweeps starts
@@ -403,74 +346,74 @@ void CellMG::pingpong(MultiFab& sol, MultiFab& buf, int nsweeps, bool sol_is_zer
     if (a != &sol) MultiFab::Copy(sol, *a, 0, 0, m_ncomp, 0);
 }
 
-void CellMG::smooth_n(int l, MultiFab& sol, const MultiFab& rhs, int nsweeps, bool skip_first_fill, bool sol_is_zero, MultiFab* acc)
+void CellMG::smooth_n(int l, int nsweeps, bool skip_first_fill, bool sol_is_zero, MultiFab* acc)
 {
+    Level& L = m_lev[l];
+    MultiFab& sol = L.cor;
+    const MultiFab& rhs = L.res;
+    const AbecSmoothPlan& plan = L.plan;
+    IAMRX_ASSERT(plan.made_for(sol, rhs));
     if (l != 0) acc = nullptr;
     if (nsweeps <= 0) { if (sol_is_zero) sol.setVal(0.0); return; }
-    Level& L = m_lev[l];
     const AbecCoef c = smoother_coef(l);
     const DomainBC* bcs = m_bcn.data();
     const int nbc = (int)m_bcn.size();
-    // Red + black in one out-of-place launch per sweep (k_abec_gsrb_rb), on the finest level only (on a coarser level of 128 cells in x a
-    // march of a few planes does not beat two colour passes): a refined box strictly inside its domain -- the coarse/fine ghost values are
-    // formed inside the kernel (no k_cf_fill, no ghost maintenance; sol's ghost cells are left stale: every reader behind a smoothing call
-    // fills them) -- or one box spanning a periodic domain
-    const bool cfs = cf_sweep_ok(l, sol);
-    if (cfs || (!m_cf && l == 0 && abec_gsrb_rb_ok(L.g, c, sol, nbc, bcs))) {
-        if (!L.buf.defined()) L.buf.define(L.layout, cell_type(), m_ncomp, 1);
-        const double om = m_dd_sweeps > 0 ? dd_omega() : m_o.omega;
+    const double om = m_dd_sweeps > 0 ? dd_omega() : m_o.omega;
+    if (plan.path != AbecSmoothPlan::COLOUR && (!L.buf.defined() || L.buf.ngrow != sol.ngrow)) L.buf.define(L.layout, cell_type(), m_ncomp, sol.ngrow);
+    switch (plan.path) {
+    case AbecSmoothPlan::COLOUR:
+        for (int i = 0; i < nsweeps; ++i) smooth(l, skip_first_fill && i == 0, i > 0, sol_is_zero && i == 0);
+        return;
+    case AbecSmoothPlan::RB_BOX:
+    case AbecSmoothPlan::RB_CF:
         pingpong(sol, L.buf, nsweeps, sol_is_zero, acc, [&](MultiFab& in, MultiFab& out, bool zero, bool last) {
-            abec_gsrb_rb(L.g, c, in, out, rhs, om, zero, bcs, nbc, cfs ? &L.cftab : nullptr, last);
+            abec_gsrb_rb(L.g, c, plan, in, out, rhs, om, zero, bcs, nbc, plan.path == AbecSmoothPlan::RB_CF ? &L.cftab : nullptr, last);
         });
         return;
-    }
-    // several boxes covering the domain: the same sweep per box, one two-layer exchange of the correction in front of it (none in
-    // front of a sweep from zero), the ghost layer of the right-hand side once per V-cycle
-    if (!m_cf && nbr_sweep_ok(l, sol, rhs)) {
-        if (!L.buf.defined() || L.buf.ngrow != sol.ngrow) L.buf.define(L.layout, cell_type(), m_ncomp, sol.ngrow);
-        if (!(&rhs == &L.res && L.res_filled)) {
+    case AbecSmoothPlan::RB_NBR: {
+        // one two-layer exchange of the correction in front of a sweep (none in front of a sweep from zero), the ghost layer of the
+        // right-hand side once per V-cycle
+        if (!L.res_filled) {
             const int one[3] = {1, 1, 1};
-            const_cast<MultiFab&>(rhs).FillBoundary(L.g, 0, m_ncomp, one);
-            if (&rhs == &L.res) L.res_filled = true;
+            L.res.FillBoundary(L.g, 0, m_ncomp, one);
+            L.res_filled = true;
         }
-        const double om = m_dd_sweeps > 0 ? dd_omega() : m_o.omega;
         // Overlap (IAMRX_HALO_OVERLAP, 1: on where the level exchanges with other ranks; 2: always; 0: off): the exchange of the two ghost
         // layers, k_abec_rb_ghost and the tiles next to box faces are issued on the context's side stream, the tiles that read no
         // ghost cell on the main stream in front of them -- the messages travel while the interior of the box is swept
         auto& ctx = Context::get();
         const int ov_mode = (int)tune("HALO_OVERLAP", 1);
         const CopyPlan& fplan = fill_boundary_plan(*L.layout, cell_type(), sol.ngrow, L.g);      // (built and uploaded in front of any fork)
-        const bool overlap = ov_mode != 0 && (ov_mode == 2 || !fplan.peers.empty()) && abec_gsrb_rb_nbr_splits(L.g, *L.layout);
+        const bool overlap = ov_mode != 0 && (ov_mode == 2 || !fplan.peers.empty()) && plan.nbr_splits;
         pingpong(sol, L.buf, nsweeps, sol_is_zero, acc, [&](MultiFab& in, MultiFab& out, bool z, bool last) {
             if (z || !overlap) {
                 if (!z) in.FillBoundary(L.g);
-                abec_gsrb_rb_nbr(L.g, c, in, out, rhs, om, z, bcs, nbc, 0, nullptr, last);
+                abec_gsrb_rb_nbr(L.g, c, plan, in, out, rhs, om, z, bcs, nbc, 0, nullptr, last);
             } else {
                 ctx.fork_side();
-                abec_gsrb_rb_nbr(L.g, c, in, out, rhs, om, false, bcs, nbc, 1, ctx.stream, last);
+                abec_gsrb_rb_nbr(L.g, c, plan, in, out, rhs, om, false, bcs, nbc, 1, ctx.stream, last);
                 in.FillBoundary(L.g, 0, m_ncomp, nullptr, -1, ctx.side);
-                abec_gsrb_rb_nbr(L.g, c, in, out, rhs, om, false, bcs, nbc, 2, ctx.side, last);
+                abec_gsrb_rb_nbr(L.g, c, plan, in, out, rhs, om, false, bcs, nbc, 2, ctx.side, last);
                 ctx.join_side();
             }
         });
         return;
     }
-    if (!fused_smoother_ok(l)) {
-        for (int i = 0; i < nsweeps; ++i) smooth(l, sol, rhs, skip_first_fill && i == 0, i > 0, sol_is_zero && i == 0);
+    case AbecSmoothPlan::FUSED_SHELL: {
+        IAMRX_ASSERT(!sol_is_zero);
+        MultiFab* a = &sol;
+        MultiFab* b = &L.buf;
+        for (int i = 0; i < nsweeps; ++i) {
+            if (!(skip_first_fill && i == 0)) applyBC(l, *a, false, nullptr);
+            abec_gsrb_fused(L.g, c, *a, *b, rhs, m_o.omega, bcs, nbc);
+            applyBC(l, *b, false, nullptr);
+            abec_gsrb(L.g, c, plan.colour, *b, rhs, 1, m_o.omega, bcs, nbc, true);
+            std::swap(a, b);
+        }
+        if (a != &sol) MultiFab::Copy(sol, *a, 0, 0, m_ncomp, 0);
         return;
     }
-    IAMRX_ASSERT(!sol_is_zero);
-    if (!L.buf.defined()) L.buf.define(L.layout, cell_type(), m_ncomp, 1);
-    MultiFab* a = &sol;
-    MultiFab* b = &L.buf;
-    for (int i = 0; i < nsweeps; ++i) {
-        if (!(skip_first_fill && i == 0)) applyBC(l, *a, false, nullptr);
-        abec_gsrb_fused(L.g, c, *a, *b, rhs, m_o.omega, bcs, nbc);
-        applyBC(l, *b, false, nullptr);
-        abec_gsrb(L.g, c, *b, rhs, 1, m_o.omega, bcs, nbc, true);
-        std::swap(a, b);
     }
-    if (a != &sol) MultiFab::Copy(sol, *a, 0, 0, m_ncomp, 0);
 }
 
 void CellMG::subtract_mean(int l, MultiFab& mf)
@@ -643,20 +586,15 @@ void CellMG::bottom_solve(MGStats& st)
     const int l = (int)m_lev.size() - 1;
     Level& L = m_lev[l];
     if (m_dd_sweeps > 0) {                 // diagonally dominant operator: no hierarchy, see prepare()
-        const AbecCoef c = smoother_coef(l);
-        if ((!m_cf && (abec_gsrb_rb_ok(L.g, c, L.cor, (int)m_bcn.size(), m_bcn.data()) ||
-                       nbr_sweep_ok(l, L.cor, L.res))) || cf_sweep_ok(l, L.cor)) {
-            smooth_n(l, L.cor, L.res, m_dd_sweeps, true, true, m_acc);      // the first sweep takes the correction as zero: no fill, nothing read
-            return;
-        }
-        L.cor.setVal(0.0);
-        smooth_n(l, L.cor, L.res, m_dd_sweeps, true);
+        const bool z = L.plan.sweep_kernel();       // the first sweep takes the correction as zero: no fill, nothing read
+        if (!z) L.cor.setVal(0.0);
+        smooth_n(l, m_dd_sweeps, true, z, z ? m_acc : nullptr);
         return;
     }
     if (m_bottom_direct) { bottom_direct_solve(); return; }
     L.cor.setVal(0.0);
     if (m_o.bottom_smoother_only) {
-        smooth_n(l, L.cor, L.res, m_o.nuf, true);
+        smooth_n(l, m_o.nuf, true);
         return;
     }
     if (m_bottom_dev) {
@@ -673,10 +611,10 @@ void CellMG::bottom_solve(MGStats& st)
     st.bottom_iters_total += nit;
     if (ret != 0) {
         L.cor.setVal(0.0);
-        smooth_n(l, L.cor, L.res, m_o.nuf, true);
+        smooth_n(l, m_o.nuf, true);
     }
     const int nn = (ret == 0) ? m_o.nub : m_o.nuf;
-    smooth_n(l, L.cor, L.res, nn, false);
+    smooth_n(l, nn, false);
 }
 
 // the last two levels run as one launch (k_abec_tail): the bottom level is the device bottom solver's and the level above it a single box of
@@ -687,7 +625,7 @@ bool CellMG::tail_fused() const
     if (nl < 2 || !m_bottom_dev || m_cf || m_dd_sweeps > 0 || m_o.nu1 <= 0) return false;
     const Level& F = m_lev[nl - 2];
     const Level& C = m_lev[nl - 1];
-    if (C.agg || C.slab || F.slab || fused_smoother_ok(nl - 2)) return false;
+    if (C.agg || C.slab || F.slab || F.plan.path == AbecSmoothPlan::FUSED_SHELL) return false;
     AbecCoef cF = coef(nl - 2);
     return abec_tail_ok(F.g, *F.layout, C.g, *C.layout, cF, m_bcn.data(), (int)m_bcn.size(), m_ncomp);
 }
@@ -700,13 +638,10 @@ void CellMG::vcycle(MGStats& st)
     const int nsm = tail ? nl - 2 : nl - 1;          // levels smoothed by the loops below
     for (int l = 0; l < nsm; ++l) {
         Level& L = m_lev[l];
-        // zero initial guess of the correction: where the first colour pass reads no ghost cell it also takes the place of the fill
-        // (the sweep kernel takes "zero" per component: the three components of a tensor solve start from zero too)
-        bool rb_zero = false;
-        if (l == 0 && !m_cf && m_ncomp > 1) rb_zero = abec_gsrb_rb_ok(L.g, smoother_coef(l), L.cor, (int)m_bcn.size(), m_bcn.data());
-        const bool z = m_o.nu1 > 0 && (zero_first_pass_ok(l, L.cor) || nbr_sweep_ok(l, L.cor, L.res) || cf_sweep_ok(l, L.cor) || rb_zero);
+        // zero initial guess of the correction: where the first sweep reads no ghost cell it also takes the place of the fill
+        const bool z = m_o.nu1 > 0 && L.plan.zero_first;
         if (!z) L.cor.setVal(0.0);
-        smooth_n(l, L.cor, L.res, m_o.nu1, true, z);
+        smooth_n(l, m_o.nu1, true, z);
         const AbecCoef cl = coef(l);
         // (one box spanning a periodic domain: the fused residual + restriction reads the periodic images itself)
         if (m_cf || !abec_residual_reads_no_ghosts(L.g, cl, L.rescor, L.cor, L.res, true)) applyBC(l, L.cor, false, nullptr);
@@ -730,7 +665,7 @@ void CellMG::vcycle(MGStats& st)
     for (int l = nsm - 1; l >= 0; --l) {
         Level& L = m_lev[l];
         cc_prolong_add(L.cor, mg_correction_of(m_lev[l + 1], m_lev[l + 1].cor, 0));
-        smooth_n(l, L.cor, L.res, m_o.nu2, false, false, l == 0 ? m_acc : nullptr);
+        smooth_n(l, m_o.nu2, false, false, l == 0 ? m_acc : nullptr);
     }
 }
 

@@ -413,6 +413,24 @@ def average_down(fine, crse, scomp=0, ncomp=None, ratio=2):
     check(lib().iamrx_average_down(fine.h, crse.h, scomp, crse.ncomp if ncomp is None else ncomp, ratio))
 
 
+SMOOTHER_PATHS = ("COLOUR", "RB_BOX", "RB_CF", "RB_NBR", "FUSED_SHELL")
+SMOOTHER_KERNELS = ("general", "gsrb1", "gsrb2", "gsrb2_per_comp")
+
+
+def host_abec_smoother_plan(geom, boxes, ncomp=1, coef=1, has_a=False, has_cf=False, finest=True, ngrow=(1, 0, 1, 0), lobc=(0, 0, 0), hibc=(0, 0, 0),
+                            maxorder=3):
+    """host-only: the smoother path of a cell-centred multigrid level (include/iamrx.h: iamrx_host_abec_smoother_plan) as a dict;
+    boxes: [(lo, hi), ...], the level's global box list"""
+    arr = (C.c_int * (6 * len(boxes)))(*[int(v) for lo, hi in boxes for v in tuple(lo) + tuple(hi)])
+    out = (C.c_int * 12)()
+    check(lib().iamrx_host_abec_smoother_plan(len(boxes), arr, C.byref(geom), i3(lobc), i3(hibc), int(maxorder), int(ncomp), int(coef), int(has_a),
+                                              int(has_cf), int(finest), (C.c_int * 4)(*[int(v) for v in ngrow]), out))
+    keys = ("path", "nw", "nbr_splits", "zero_first", "kernel", "mode", "np", "maintain", "allcf", "wrap", "walls_inkernel", "zero_ok")
+    d = dict(zip(keys, out[:]))
+    d["path"], d["kernel"] = SMOOTHER_PATHS[d["path"]], SMOOTHER_KERNELS[d["kernel"]]
+    return d
+
+
 def abec_form(geom, coef, op, phi, rhs, out=None, rho=None, rho_comp=0, scale=1.0, bu=(1.0, 1.0, 1.0), beta=1.0, omega=1.15, lobc=(0, 0, 0), hibc=(0, 0, 0),
               maxorder=3):
     """one operation of the multigrid's finest-level kernel forms (include/iamrx.h: iamrx_abec_form)"""

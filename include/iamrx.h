@@ -191,6 +191,19 @@ int iamrx_host_fill_plan(int nboxes, const int* lo_hi, const int* owner, int ran
 int iamrx_host_fill_plan_wall_ext(int nboxes, const int* lo_hi, const int* owner, int rank, const int type[3], int ngrow, const iamrx_geom* g,
                                   int wall_ext, int max_desc, int* desc, int* ndesc);
 
+/* host-only (works without a GPU): how a smoothing call of the cell-centred multigrid (MLMG::mgVcycle's smooth on MLABecLaplacian /
+ * MLTensorOp, as set up at MacProj.cpp:1150-1183 and Diffusion.cpp:715-923) runs on a level -- decided once per level per solve, from the
+ * level's global box list.  lo_hi: 6 ints per box; lobc / hibc: LinOpBC codes; coef 0: stored face coefficients, 1: recomputed from the
+ * density, 2: uniform; has_cf: the level has coarse/fine faces; finest: level 0 of its hierarchy; ngrow: ghost widths of the correction,
+ * the right-hand side, the density and the a-term.  out[0] path (0 two colour passes, 1 one-launch sweep on a box spanning the domain,
+ * 2 on a refined box strictly inside it, 3 on several boxes covering it, 4 the opt-in fused sweep + shell pass), out[1] wavefronts of a
+ * sweep workgroup (12 / 16), out[2] sweep issued in two parts, out[3] the first sweep may start from zero; the colour pass: out[4] kernel
+ * (0 general, 1 plane-pipelined, 2 pair-marching, 3 pair-marching per component), out[5] coefficient mode, out[6] planes in flight,
+ * out[7] coarse/fine ghost cells maintained, out[8] all ghost cells coarse/fine, out[9] periodic index wrap, out[10] walls applied in the
+ * kernel, out[11] first pass from zero allowed.  No counterpart upstream (amrex picks nothing: one smoother kernel). */
+int iamrx_host_abec_smoother_plan(int nboxes, const int* lo_hi, const iamrx_geom* g, const int lobc[3], const int hibc[3], int maxorder, int ncomp,
+                                  int coef, int has_a, int has_cf, int finest, const int ngrow[4], int out[12]);
+
 /* ---- cell-centred linear operator primitives (amrex::MLABecLaplacian role) ---- */
 /* one red or black Gauss-Seidel pass of (alpha*a - beta div b grad) phi = rhs; ghost cells of phi must be filled */
 int iamrx_abec_gsrb(const iamrx_geom* g, double alpha, double beta, iamrx_mf a /* may be NULL */, iamrx_mf bx, iamrx_mf by, iamrx_mf bz,
