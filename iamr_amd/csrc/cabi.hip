@@ -795,6 +795,39 @@ int iamrx_tensor_solve_cf(const iamrx_geom* g, iamrx_mf soln, iamrx_mf rhs, doub
     IAMRX_CATCH
 }
 
+// ---- LES eddy viscosity (k_les.hip, projection.hip: calc_mut_les) ----------------------------------------------------------------------
+int iamrx_les_mut(const iamrx_geom* g, iamrx_mf vel, int vcomp, int model, double Cs, double base, iamrx_mf mu_x, iamrx_mf mu_y, iamrx_mf mu_z)
+{
+    IAMRX_TRY
+    MultiFab* mu[3] = {&mu_x->mf, &mu_y->mf, &mu_z->mf};
+    les_mut(to_geom(g), vel->mf, vcomp, model, Cs, base, mu);
+    IAMRX_CATCH
+}
+
+int iamrx_calc_mut_les(const iamrx_geom* g, iamrx_mf vel, const int* lobc, const int* hibc, int maxorder, int model, double Cs, iamrx_mf mu_x,
+                       iamrx_mf mu_y, iamrx_mf mu_z)
+{
+    IAMRX_TRY
+    MultiFab* mu[3] = {&mu_x->mf, &mu_y->mf, &mu_z->mf};
+    DomainBC bcs[3];
+    for (int n = 0; n < 3; ++n) bcs[n] = to_bc(lobc + 3 * n, hibc + 3 * n, maxorder);
+    calc_mut_les(to_geom(g), vel->mf, bcs, model, Cs, 0.0, mu);
+    IAMRX_CATCH
+}
+
+int iamrx_calc_mut_les_cf(const iamrx_geom* g, iamrx_mf vel, const int* lobc, const int* hibc, int maxorder, int model, double Cs, iamrx_mf mu_x,
+                          iamrx_mf mu_y, iamrx_mf mu_z, iamrx_mf crse_vel, const iamrx_geom* cgeom, int ratio)
+{
+    IAMRX_TRY
+    MultiFab* mu[3] = {&mu_x->mf, &mu_y->mf, &mu_z->mf};
+    DomainBC bcs[3];
+    for (int n = 0; n < 3; ++n) bcs[n] = to_bc(lobc + 3 * n, hibc + 3 * n, maxorder);
+    Geometry cg = to_geom(cgeom);
+    TensorCF cf{crse_vel ? &crse_vel->mf : nullptr, &cg, ratio};
+    calc_mut_les(to_geom(g), vel->mf, bcs, model, Cs, 0.0, mu, &cf);
+    IAMRX_CATCH
+}
+
 // ---- Diffusion operator entries on caller-owned data (diffusion.hip) -----------------------------------------------------------------
 namespace {
 struct CrseArgs { DiffusionCrse dc; Geometry cg; bool on = false; };
@@ -924,6 +957,7 @@ void iamrx_ns_default_params(iamrx_ns_params* p)
     p->do_trac2 = d.do_trac2; p->do_cons_trac2 = d.do_cons_trac2; p->tracer2_diff_coef = d.tracer2_diff_coef; p->do_temp = d.do_temp; p->temp_cond_coef = d.temp_cond_coef;
     p->use_ppm = d.use_ppm;
     p->avg_interval = d.avg_interval; p->compute_fluctuations = d.compute_fluctuations; p->sum_interval = d.sum_interval;
+    p->do_LES = d.do_LES; p->LES_model = d.LES_model; p->smago_Cs_cst = d.smago_Cs_cst; p->sigma_Cs_cst = d.sigma_Cs_cst;
 }
 
 static NSParams to_params(const iamrx_ns_params* p)
@@ -944,6 +978,8 @@ static NSParams to_params(const iamrx_ns_params* p)
     q.use_ppm = p->use_ppm;
     q.avg_interval = p->avg_interval; q.compute_fluctuations = p->compute_fluctuations; q.sum_interval = p->sum_interval;
     if (q.avg_interval < 0) throw Error("iamrx_ns_params: avg_interval must be >= 0");
+    q.do_LES = p->do_LES != 0; q.LES_model = p->LES_model; q.smago_Cs_cst = p->smago_Cs_cst; q.sigma_Cs_cst = p->sigma_Cs_cst;
+    if (q.do_LES && q.LES_model != 0 && q.LES_model != 1) throw Error("iamrx_ns_params: LES_model must be 0 (Smagorinsky) or 1 (Sigma)");
     return q;
 }
 
@@ -993,7 +1029,7 @@ int iamrx_ns_data(iamrx_ns ns, int which, iamrx_mf* out)
 {
     IAMRX_TRY
     NavierStokes& n = *ns->ns;
-    MultiFab* m = nullptr;
+    const MultiFab* m = nullptr;
     switch (which) {
     case 0: m = &n.get_new_data(0); break;
     case 1: m = &n.get_old_data(0); break;
@@ -1005,6 +1041,8 @@ int iamrx_ns_data(iamrx_ns ns, int which, iamrx_mf* out)
     case 9: m = &n.Aofs(); break;
     case 10: case 11: m = &n.mac_phi_history(which - 10); break;
     case 12: m = &n.average_data(); break;
+    case 13: case 14: case 15: m = &n.les_viscosity(0, which - 13); break;
+    case 16: case 17: case 18: m = &n.les_viscosity(1, which - 16); break;
     default: throw Error("iamrx_ns_data: bad selector");
     }
     // copy the current contents into a library-owned MultiFab of the same shape (old/new swap every step,

@@ -5,6 +5,7 @@
 // :858-923 (implicit solve); SURVEY a10, a11.
 #include "kernels.h"
 #include "launch.h"
+#include "tensor_lds.h"
 #include <cstring>
 #include <type_traits>
 #include <vector>
@@ -109,19 +110,6 @@ __global__ void __launch_bounds__(256) k_tensor_cross(Tiling t, const BoxD* __re
 // through a chunk of planes with a three-plane ring of the 3-component velocity tile (one ghost cell in x and y) in LDS; the five face
 // fluxes of a cell read their 80 velocity values from LDS instead of L1 / L2 (k_tensor_cross: 0.62 ms per 256^3 launch, load-issue
 // bound).  Same expressions (cross_flux), same results.
-template <int TX, int TY>
-struct LdsVel {
-    static constexpr int W = TX + 2, H = TY + 2, PS = W * H;
-    const double *pm, *p0, *pp;      // planes kc-1, kc, kc+1 (3 components each, component stride PS)
-    int kc, i0, j0;
-    __device__ __forceinline__ double operator()(int i, int j, int k, int n) const
-    {
-        const int d = k - kc;
-        const double* p = d < 0 ? pm : (d > 0 ? pp : p0);
-        return p[(i - i0) + W * (j - j0) + PS * n];
-    }
-};
-
 struct EtaUni { double v[3]; };
 // UNI (with ETA1): the three face viscosities are the constants eu (the arrays are not read)
 // FUSE (with UNI): the whole tensor residual / apply in this pass -- the 7-point part of the operator (k_abec_residual's expression for

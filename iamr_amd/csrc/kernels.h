@@ -240,4 +240,10 @@ void tensor_extensive_flux(const Geometry& g, const MultiFab& vel, const MultiFa
 void tensor_cross_terms_sub(const Geometry& g, const AbecCoef& c, MultiFab& out, const MultiFab& vel, double sign, unsigned long long* normout = nullptr);
 void fill_tensor_corners(const Geometry& g, MultiFab& phi, const DomainBC& bc, bool inhomog, const MultiFab* bcval, int comp0 = 0, int ncomp = -1);
 
+// ---- k_les.hip ----------------------------------------------------------------------------
+// LES eddy viscosity on faces, one launch: mu[d] (face d, comp 0) = base + mu_t of model 0 (Smagorinsky) / 1 (Sigma) with constant Cs, from
+// the velocity in vel(vcomp .. vcomp + 2) and its ghost cells as they are (one layer, face and edge cells): the model loops of
+// NavierStokesBase::calc_mut_LES (Source/NS_LES.cpp:105-222) on the gradients of MLTensorOp::compVelGrad (:97)
+void les_mut(const Geometry& g, const MultiFab& vel, int vcomp, int model, double Cs, double base, MultiFab* const mu[3]);
+
 }  // namespace iamrx

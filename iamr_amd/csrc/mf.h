@@ -245,6 +245,10 @@ public:
     void mark_uniform(double v) { uniform_marked = true; uniform_value = v; }
     bool uniform_marked = false;
     double uniform_value = 0.0;
+    // the opposite statement of the owner: the array varies in space (the LES face viscosities) -- consumers take their array-coefficient
+    // paths without scanning it for uniformity.  Never wrong for the result (the array holds the data either way); dropped like the mark above.
+    void mark_varying() { varying_marked = true; uniform_marked = false; }
+    bool varying_marked = false;
     // max norms of nc components in ONE reduction / host synchronisation: out[n] = max |comp + n|
     void norm0_comps(int comp, int nc, int ng, double* out, bool local = false) const;
     void setVal(double v, int comp, int nc, int ng);

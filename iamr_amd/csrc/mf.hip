@@ -505,6 +505,7 @@ MultiFab& MultiFab::operator=(MultiFab&& o) noexcept
         layout = std::move(o.layout); type = o.type; ncomp = o.ncomp; ngrow = o.ngrow;
         base = o.base; total_doubles = o.total_doubles; h_tab = std::move(o.h_tab); d_tab = o.d_tab; is_alias = o.is_alias;
         uniform_marked = o.uniform_marked; uniform_value = o.uniform_value;       // the mark describes the data: it travels with them
+        varying_marked = o.varying_marked; o.varying_marked = false;
         o.base = nullptr; o.d_tab = nullptr; o.total_doubles = 0; o.is_alias = false; o.uniform_marked = false;
     }
     return *this;
@@ -537,6 +538,7 @@ void MultiFab::release()
     if (is_alias) { if (d_tab) ctx.free(d_tab); }         // the data belong to the caller, the table to this object
     else if (base) ctx.free(base);
     base = nullptr; d_tab = nullptr; total_doubles = 0; h_tab.clear(); is_alias = false;      // d_tab of an owning MultiFab belongs to the table cache
+    varying_marked = false;
     uniform_marked = false;             // (define / alias / view_of / clear / move-assignment all come through here: new data, no promise)
 }
 

@@ -150,6 +150,12 @@ public:
     // the coarse level's own layout), cgeom its geometry.  crse == nullptr: homogeneous coarse/fine data.  Call before prepare().
     void setCoarseFineBC(const MultiFab* crse, const Geometry& cgeom, int ratio) { m_cf = true; m_crse = crse; m_cgeom = cgeom; m_ratio = ratio; }
     void prepare();   // build the coarse hierarchy (coefficient averaging)
+    // the finest level's boundary machinery alone (no coefficients, no hierarchy): enough for fillBoundaryData
+    void prepareBoundary();
+    // the operator's boundary step in front of an apply (setLevelBC + applyBC): the ghost cells of phi hold the level's boundary data on
+    // entry (domain faces; coarse/fine faces are taken from setCoarseFineBC's array) and what the stencil reads on exit, edge cells of
+    // the tensor operator included
+    void fillBoundaryData(MultiFab& phi);
     MGStats solve(MultiFab& phi, const MultiFab& rhs, double rtol, double atol);
     // out = L(phi) with inhomogeneous BC taken from phi's ghost cells
     void apply(MultiFab& out, MultiFab& phi);
@@ -186,6 +192,7 @@ private:
     template <class Sweep> void pingpong(MultiFab& sol, MultiFab& buf, int nsweeps, bool sol_is_zero, MultiFab* acc, Sweep sweep);
     bool tail_fused() const;
     void cf_bcval(MultiFab& bcval);
+    void prepare_cf(int l);
     void subtract_mean(int l, MultiFab& mf);
     Geometry m_g;
     int m_ncomp;

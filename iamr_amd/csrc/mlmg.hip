@@ -132,6 +132,24 @@ AbecCoef CellMG::smoother_coef(int l) const
     return c;
 }
 
+void CellMG::prepare_cf(int l)
+{
+    if (!m_cf) return;
+    Level& L = m_lev[l];
+    // the Dirichlet data sit half a coarse cell (of the AMR level below) behind the face on every MG level
+    double loc[3];
+    for (int d = 0; d < 3; ++d) loc[d] = 0.5 * m_ratio * m_g.dx[d];
+    L.cftab = cf_make_tab(loc, L.g.dx, m_o.maxorder);
+    L.cfm.define(L.layout, cell_type(), 1, l == 0 ? 2 : 1);
+    cf_build_mask(L.g, L.cfm);
+}
+
+void CellMG::prepareBoundary()
+{
+    m_lev.resize(1);
+    prepare_cf(0);
+}
+
 void CellMG::prepare()
 {
     ProfScope ps_prof_("cmg_prepare");
@@ -159,6 +177,7 @@ void CellMG::prepare()
                     if (!mf_uniform_value(*m_b0[d], &v) || v != m_bu[d]) throw Error("iamrx: an array marked uniform is not (MultiFab::mark_uniform)");
                 }
             }
+            else if (m_b0[d]->varying_marked) m_buni = false;      // the owner says it varies (MultiFab::mark_varying): no scan either
             else m_buni = mf_uniform_value(*m_b0[d], &m_bu[d]);
         }
     }
@@ -229,14 +248,7 @@ void CellMG::prepare()
         L.cor.define(L.layout, cell_type(), m_ncomp, (l == 0 && m_nbr) ? 2 : 1);
         L.res.define(L.layout, cell_type(), m_ncomp, (l == 0 && m_nbr) ? 1 : 0);
         L.rescor.define(L.layout, cell_type(), m_ncomp, 0);
-        if (m_cf) {
-            // the Dirichlet data sit half a coarse cell (of the AMR level below) behind the face on every MG level
-            double loc[3];
-            for (int d = 0; d < 3; ++d) loc[d] = 0.5 * m_ratio * m_g.dx[d];
-            L.cftab = cf_make_tab(loc, L.g.dx, m_o.maxorder);
-            L.cfm.define(L.layout, cell_type(), 1, l == 0 ? 2 : 1);
-            cf_build_mask(L.g, L.cfm);
-        }
+        prepare_cf(l);
         if (l > 0) {
             AbecCoef fc = coef(l - 1);
             if (L.agg) L.tmp_d.define(L.dist, cell_type(), m_ncomp, 0);
@@ -669,7 +681,7 @@ void CellMG::vcycle(MGStats& st)
     }
 }
 
-void CellMG::apply(MultiFab& out, MultiFab& phi)
+void CellMG::fillBoundaryData(MultiFab& phi)
 {
     const Geometry& g0 = m_lev[0].g;
     if (m_cf || !(g0.periodic[0] && g0.periodic[1] && g0.periodic[2])) {
@@ -678,6 +690,11 @@ void CellMG::apply(MultiFab& out, MultiFab& phi)
         cf_bcval(bcval);
         applyBC(0, phi, true, &bcval);
     } else applyBC(0, phi, true, nullptr);         // fully periodic, no coarse/fine faces: no boundary data to keep
+}
+
+void CellMG::apply(MultiFab& out, MultiFab& phi)
+{
+    fillBoundaryData(phi);
     level_residual(m_lev[0].g, coef(0), out, phi, nullptr);
 }
 

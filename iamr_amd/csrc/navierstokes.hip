@@ -237,7 +237,7 @@ void NavierStokes::set_restart_state(const double v[16])
     dt_prev_mac = v[9]; m_have_mac_prev = v[10] != 0.0; m_have_mac_prev2 = v[11] != 0.0; dt_min_adv = v[12]; m_stop_time = v[13];
     // inew / pnew are not restored: the arrays were handed over as "new" / "old" data, whichever buffers hold them now
     initial_step = false; initial_iter = false;
-    m_visc_old_valid = false;
+    m_visc_old_valid = false; m_eta_n_valid = false;
     make_rho_curr_time();
 }
 MultiFab& NavierStokes::mac_phi_history(int which)
@@ -450,7 +450,9 @@ void NavierStokes::compute_visc_terms_vel(MultiFab& visc, MultiFab& Sdata)
     if (!is_diffusive_vel()) { visc.setVal(0.0); return; }
     MultiFab stmp(layout, cell_type(), 3, 1);
     fillpatch(stmp, Sdata, Xvel, 3, bc_vel);
-    const MultiFab* ep[3] = {&eta[0], &eta[1], &eta[2]};
+    const MultiFab* ep[3];
+    MultiFab eta_les[3];
+    get_viscosity(ep, eta_les, Sdata);
     MultiFab cdata;
     TensorCF cf{&cdata, level > 0 ? &crse->g : nullptr, ratio};
     if (level > 0) crse_state_at(cdata, state_time(Sdata), Xvel, 3);        // Diffusion.cpp:1725-1736
@@ -458,6 +460,44 @@ void NavierStokes::compute_visc_terms_vel(MultiFab& visc, MultiFab& Sdata)
     tensor_apply(g, visc, stmp, 0.0, -1.0, nullptr, ep, bc_visc, 3, level > 0 ? &cf : nullptr);   // a = 0, b = -1 (Diffusion.cpp:1697-1698)
     visc.FillBoundary(g);
     first_order_extrap(visc);
+}
+
+// NavierStokesBase::calc_mut_LES (NS_LES.cpp:22-225) + the setVal / Add of getViscosity: out[d] = visc_coef + mu_t
+void NavierStokes::calc_mut_LES(MultiFab out[3], MultiFab& Sdata)
+{
+    MultiFab vel(layout, cell_type(), 3, 1);
+    fillpatch(vel, Sdata, Xvel, 3, bc_vel);                       // NS_LES.cpp:40-42, 86
+    MultiFab cdata;
+    TensorCF cf{&cdata, level > 0 ? &crse->g : nullptr, ratio};
+    if (level > 0) crse_state_at(cdata, state_time(Sdata), Xvel, 3);        // :76-84
+    DomainBC bl[3];
+    for (int n = 0; n < 3; ++n) { bl[n] = bc_visc[n]; bl[n].maxorder = 3; }  // LES_setDomainBC = linop_of; no setMaxOrder: MLLinOp's default
+    MultiFab* mp[3];
+    for (int d = 0; d < 3; ++d) {
+        if (!out[d].defined() || out[d].layout.get() != layout.get()) out[d].define(layout, face_type(d), 1, 0);
+        out[d].mark_varying();                                    // never uniform-marked, never scanned: the array paths of the operator
+        mp[d] = &out[d];
+    }
+    calc_mut_les(g, vel, bl, p.LES_model, p.LES_model == 0 ? p.smago_Cs_cst : p.sigma_Cs_cst, p.visc_coef, mp, level > 0 ? &cf : nullptr);
+}
+
+void NavierStokes::get_viscosity(const MultiFab* ep[3], MultiFab store[3], MultiFab& Sdata)
+{
+    if (!p.do_LES) { for (int d = 0; d < 3; ++d) ep[d] = &eta[d]; return; }
+    if (m_in_advance && &Sdata == &S[1 - inew]) {
+        if (!m_eta_n_valid) { calc_mut_LES(m_eta_n, Sdata); m_eta_n_valid = true; }
+        for (int d = 0; d < 3; ++d) ep[d] = &m_eta_n[d];
+        return;
+    }
+    calc_mut_LES(store, Sdata);
+    for (int d = 0; d < 3; ++d) ep[d] = &store[d];
+}
+
+const MultiFab& NavierStokes::les_viscosity(int which, int d) const
+{
+    if (!p.do_LES) throw Error("iamrx NavierStokes: no eddy viscosity (do_LES = 0)");
+    if (!m_eta_have) throw Error("iamrx NavierStokes: no velocity_diffusion_update has run yet");
+    return which == 0 ? m_eta_n[d] : m_eta_np1[d];
 }
 
 void NavierStokes::get_visc_terms_vel(MultiFab& visc, MultiFab& Sdata)
@@ -1074,7 +1114,14 @@ void NavierStokes::velocity_diffusion_update(double dt_)
     const double theta = p.be_cn_theta;
     MultiFab& Sn = S[inew];
     MultiFab& So = S[1 - inew];
-    const MultiFab* ep[3] = {&eta[0], &eta[1], &eta[2]};
+    // getViscosity(prevTime) / getViscosity(curTime): the new state holds U* here (NavierStokes.cpp:1022-1031)
+    const MultiFab *en[3], *ep[3];
+    if (p.do_LES) {
+        get_viscosity(en, m_eta_n, So);                          // (inside an advance: the cached arrays, which are m_eta_n as well)
+        calc_mut_LES(m_eta_np1, Sn);
+        for (int d = 0; d < 3; ++d) ep[d] = &m_eta_np1[d];
+        m_eta_have = true;
+    } else { get_viscosity(ep, nullptr, Sn); for (int d = 0; d < 3; ++d) en[d] = ep[d]; }
     // viscous fluxes for the registers of the interfaces above and below (do_reflux && (level < finest_level || level > 0), Diffusion.cpp:790-796, 932-956)
     const bool want_flux = fine != nullptr || level > 0;
     MultiFab tflux[3];
@@ -1101,7 +1148,7 @@ void NavierStokes::velocity_diffusion_update(double dt_)
         if (theta != 1.0 && !reuse) { crse_state_at(co, st_old, Xvel, 3); dc.crse_old = &co; }
         crse_state_at(cn, st_new, Xvel, 3); dc.crse_new = &cn;
     }
-    st_visc = diffuse_tensor_velocity(g, &So, Sn, Density, dt_, theta, rho_half, p.do_mom_diff ? 3 : 1, reuse ? &m_visc_old : nullptr, ep, ep, bc_visc,
+    st_visc = diffuse_tensor_velocity(g, &So, Sn, Density, dt_, theta, rho_half, p.do_mom_diff ? 3 : 1, reuse ? &m_visc_old : nullptr, en, ep, bc_visc,
                                       level > 0 ? &dc : nullptr, want_flux ? tfp : nullptr, p.visc_tol, o, [&](MultiFab& U) { refill(U, U); });
     if (want_flux)
         for (int d = 0; d < 3; ++d) {
@@ -1271,7 +1318,7 @@ void NavierStokes::initial_sync_project(double dt_)
 double NavierStokes::advance(double dt_, int iteration_, int ncycle_)
 {
     advance_setup(dt_, iteration_, ncycle_);
-    m_in_advance = true; m_visc_old_valid = false;
+    m_in_advance = true; m_visc_old_valid = false; m_eta_n_valid = false;
     const double dt_test = predict_velocity(dt_);
     mac_project(dt_);
     const bool fused_adv = tune("FUSED_ADVECTION", 1) != 0;
@@ -1294,7 +1341,7 @@ double NavierStokes::advance(double dt_, int iteration_, int ncycle_)
         level_project(dt_);
         if (level > 0 && iteration == 1) p_avg.setVal(0.0);      // :670-671
     }
-    m_in_advance = false; m_visc_old_valid = false;
+    m_in_advance = false; m_visc_old_valid = false; m_eta_n_valid = false;
     return dt_test;
 }
 

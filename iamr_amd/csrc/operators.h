@@ -52,6 +52,13 @@ inline MGStats tensor_solve(const Geometry& g, MultiFab& soln, const MultiFab& r
                             const MultiFab* const eta[3], const DomainBC& bc, double tol_rel, double tol_abs, const MGOpts& opts)
 { return tensor_solve(g, soln, rhs, a_scalar, b_scalar, acoef, eta, &bc, 1, tol_rel, tol_abs, opts); }
 
+// NavierStokesBase::calc_mut_LES (Source/NS_LES.cpp:22-225) on caller-owned data: the ghost cells of vel (3 comps, 1 ghost, the level's
+// boundary data in them as for tensor_apply) are filled by the tensor operator's own boundary step (CellMG::fillBoundaryData: setDomainBC
+// with LES_setDomainBC's per-component codes :59-68, 230-285, setCoarseFineBC :76-84, setLevelBC :88), then mu[d] = base + mu_t (les_mut,
+// k_les.hip).  bcs[n].maxorder: NS_LES.cpp sets none, MLLinOp's default applies (3 as far as is known: DESIGN.md section 2).
+void calc_mut_les(const Geometry& g, MultiFab& vel, const DomainBC bcs[3], int model, double Cs, double base, MultiFab* const mu[3],
+                  const TensorCF* cf = nullptr);
+
 // ---- Diffusion operator entries on caller-owned data (diffusion.hip; reference Source/Diffusion.H:53-225) -------------------
 // the coarse level's state at the old / new time (valid cells on its own layout; the same component numbering as the fine arrays);
 // crse_new == nullptr: homogeneous coarse/fine data (the sync solves)
@@ -250,6 +257,9 @@ struct NSParams {
     // ns.avg_interval / ns.compute_fluctuations (NS_average.cpp, NavierStokesBase.cpp:487-488): time averages of the velocity, sampled
     // every avg_interval level-0 steps (0: off); ns.sum_interval (NavierStokesBase.cpp:452, 2589-2592): integrated quantities (<= 0: off)
     int avg_interval = 0, compute_fluctuations = 0, sum_interval = 0;
+    // ns.do_LES / ns.LES_model (0 Smagorinsky, 1 Sigma) / ns.smago_Cs_cst / ns.sigma_Cs_cst (NavierStokesBase.cpp:142-146, 481-485)
+    int do_LES = 0, LES_model = 0;
+    double smago_Cs_cst = 0.18, sigma_Cs_cst = 1.5;
 };
 
 enum StateComp { Xvel = 0, Yvel = 1, Zvel = 2, Density = 3, Tracer = 4, MAXSCAL = 4, MAXSTATE = 3 + MAXSCAL, MAXSLOT = MAXSCAL + 2 };   // Tracer2 / Temp: NavierStokes::Tracer2 / Temp (-1: absent)
@@ -322,6 +332,8 @@ public:
     void set_stop_time(double t) { m_stop_time = t; }      // amr.restart: stop_time comes from the inputs file
     void set_restart_state(const double v[16]);            // call after the arrays are set; also leaves the initial-step state
     MultiFab& mac_phi_history(int which);                  // 0: last MAC potential, 1: the one before (defined on demand)
+    // ns.do_LES: the face viscosities of the last velocity_diffusion_update, which 0 eta_n / 1 eta_np1, direction d
+    const MultiFab& les_viscosity(int which, int d) const;
     const Geometry& geom() const { return g; }
     const LayoutP& lay() const { return layout; }
     const NSParams& params() const { return p; }
@@ -355,6 +367,10 @@ private:
     // (times (1 - theta) dt) by the Crank-Nicolson right-hand side -- one tensor apply instead of three (valid only inside advance())
     MultiFab m_visc_old;
     bool m_visc_old_valid = false, m_in_advance = false;
+    // ns.do_LES: the face viscosity visc_coef + mu_t of the old state, computed once per advance (the old state does not change inside
+    // one; validity as m_visc_old), and that of the new state as velocity_diffusion_update last saw it.  Not allocated without LES.
+    MultiFab m_eta_n[3], m_eta_np1[3];
+    bool m_eta_n_valid = false, m_eta_have = false;
     MultiFab m_cf_mask;
     MultiFab m_mac_phi_prev, m_mac_phi_prev2;  // initial guess of the next MAC solve (last two potentials)
     bool m_have_mac_prev = false, m_have_mac_prev2 = false;
@@ -373,6 +389,12 @@ private:
     double m_stop_time = -1.0;
     void initial_sync_project(double dt);
     void get_visc_terms_vel(MultiFab& visc, MultiFab& Sdata);
+    // NavierStokes::getViscosity (NavierStokes.cpp:2119-2153) at the time of Sdata (the level's old or new state): ep[d] = the face
+    // viscosity.  Without LES the level's constant arrays (nothing computed); with LES visc_coef + mu_t in store[d] (calc_mut_LES:
+    // FillPatch of the velocity, the coarse level's velocity on a refined level, the operator's boundary step, k_les_mut) -- or the
+    // advance's cached old-time arrays
+    void get_viscosity(const MultiFab* ep[3], MultiFab store[3], MultiFab& Sdata);
+    void calc_mut_LES(MultiFab out[3], MultiFab& Sdata);
     void compute_visc_terms_vel(MultiFab& visc, MultiFab& Sdata);
     const MultiFab& visc_terms_vel_old(MultiFab& scratch);
     const MultiFab& old_visc_or_zero(MultiFab& scratch);

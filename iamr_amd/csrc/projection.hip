@@ -158,4 +158,19 @@ MGStats tensor_solve(const Geometry& g, MultiFab& soln, const MultiFab& rhs, dou
     return st;
 }
 
+void calc_mut_les(const Geometry& g, MultiFab& vel, const DomainBC bcs[3], int model, double Cs, double base, MultiFab* const mu[3], const TensorCF* cf)
+{
+    IAMRX_ASSERT(vel.ncomp == 3 && vel.ngrow >= 1);
+    MGOpts o;
+    o.max_coarsening_level = 0;
+    o.maxorder = bcs[0].maxorder;
+    CellMG mg(g, vel.layout, 3, bcs[0], o);
+    mg.setDomainBCs(bcs, 3);
+    mg.setTensor(true);
+    if (cf) mg.setCoarseFineBC(cf->crse, *cf->cgeom, cf->ratio);
+    mg.prepareBoundary();
+    mg.fillBoundaryData(vel);
+    les_mut(g, vel, 0, model, Cs, base, mu);
+}
+
 }  // namespace iamrx

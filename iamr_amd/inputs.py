@@ -328,9 +328,12 @@ class Inputs:
         scheme = self.string("ns.advection_scheme", "Godunov_PLM")
         if scheme not in ("Godunov_PLM", "Godunov_PPM", "BDS"):      # NavierStokesBase.cpp:548-553
             raise NotImplementedError(f"inputs: ns.advection_scheme = {scheme}; Godunov_PLM, Godunov_PPM and BDS are implemented")
-        for k in ("ns.do_LES", "particles.do_nspc_particles", "eb2.geom_type"):
+        for k in ("particles.do_nspc_particles", "eb2.geom_type"):
             if self.has(k) and self.string(k) not in ("0", "all_regular"):
                 raise NotImplementedError(f"inputs: {k} = {self.string(k)} is not implemented")
+        if self.has("ns.do_LES") and self.string("ns.do_LES") != "0":
+            raise NotImplementedError("inputs: ns.do_LES = 1 is not switched on from an inputs file yet: the library implements LES (Smagorinsky "
+                                      "and Sigma eddy viscosity) through iamrx_ns_params.do_LES -- set params['do_LES'] = 1 on the parsed problem")
         do_trac2, do_temp = self.integer("ns.do_trac2", 0), self.integer("ns.do_temp", 0)
         ntrac = 2 if do_trac2 else 1
         # NavierStokes.cpp:268-282: n_scal_diff_coefs + n_temp_cond_coef must equal NUM_SCALARS - 1
@@ -380,6 +383,15 @@ class Inputs:
         p["compute_fluctuations"] = self.integer("ns.compute_fluctuations", 0)
         p["avg_in_checkpoint"] = self.integer("ns.avg_in_checkpoint", 1)
         p["sum_interval"] = self.integer("ns.sum_interval", -1)
+        # LES closure (NavierStokesBase.cpp:142-146, 481-485): the model and its constants are read in every run; ns.do_LES itself: above
+        les_model = self.string("ns.LES_model", "Smagorinsky")
+        if les_model not in ("Smagorinsky", "Sigma"):            # NS_LES.cpp:214-218 aborts
+            raise ValueError(f"inputs: ns.LES_model = {les_model}: Smagorinsky or Sigma")
+        p["do_LES"] = 0
+        p["LES_model"] = {"Smagorinsky": 0, "Sigma": 1}[les_model]
+        p["smago_Cs_cst"] = self.real("ns.smago_Cs_cst", 0.18)
+        p["sigma_Cs_cst"] = self.real("ns.sigma_Cs_cst", 1.5)
+        self.integer("ns.getLESVerbose", 0)                      # printing only
         if p["avg_interval"] < 0:
             raise ValueError(f"inputs: ns.avg_interval = {p['avg_interval']} must be >= 0")
         if slab and p["avg_interval"] > 0:

@@ -15,7 +15,8 @@ class NsParams(C.Structure):
                 ("wall_vel_lo", C.c_double * 9), ("wall_vel_hi", C.c_double * 9),
                 ("scal_bc_lo", C.c_double * 12), ("scal_bc_hi", C.c_double * 12), ("do_cons_trac", C.c_int), ("do_denminmax", C.c_int), ("do_scalminmax", C.c_int),
                 ("do_trac2", C.c_int), ("do_cons_trac2", C.c_int), ("tracer2_diff_coef", C.c_double), ("do_temp", C.c_int), ("temp_cond_coef", C.c_double), ("use_ppm", C.c_int),
-                ("avg_interval", C.c_int), ("compute_fluctuations", C.c_int), ("sum_interval", C.c_int)]
+                ("avg_interval", C.c_int), ("compute_fluctuations", C.c_int), ("sum_interval", C.c_int),
+                ("do_LES", C.c_int), ("LES_model", C.c_int), ("smago_Cs_cst", C.c_double), ("sigma_Cs_cst", C.c_double)]
 
 
 def ns_params(**kw):
@@ -130,14 +131,37 @@ def tensor_solve_cf(geom, soln, rhs, a, b, acoef, eta, crse_vel, cgeom, ratio=2,
     return st
 
 
+SMAGORINSKY, SIGMA = 0, 1        # ns.LES_model
+
+
+def les_mut(geom, vel, mu, model, Cs, base=0.0, vcomp=0):
+    """k_les_mut alone: mu[d] = base + mu_t from vel(vcomp..vcomp+2) and its ghost cells as they are (the model loops of
+    NavierStokesBase::calc_mut_LES, Source/NS_LES.cpp:105-222)"""
+    check(lib().iamrx_les_mut(C.byref(geom), vel.h, int(vcomp), int(model), C.c_double(Cs), C.c_double(base), mu[0].h, mu[1].h, mu[2].h))
+
+
+def calc_mut_les(geom, vel, mu, model, Cs, lobc=((0, 0, 0),) * 3, hibc=((0, 0, 0),) * 3, maxorder=3, crse_vel=None, cgeom=None, ratio=2):
+    """NavierStokesBase::calc_mut_LES (Source/NS_LES.cpp:22-225) on caller data: the tensor operator's boundary step on vel (3 comps, 1 ghost),
+    then the kernel; cgeom given: a refined level (crse_vel None: homogeneous coarse/fine data)"""
+    lo, hi, nbc = _bcn(lobc, hibc)
+    assert nbc == 3
+    if cgeom is None:
+        check(lib().iamrx_calc_mut_les(C.byref(geom), vel.h, lo, hi, int(maxorder), int(model), C.c_double(Cs), mu[0].h, mu[1].h, mu[2].h))
+    else:
+        check(lib().iamrx_calc_mut_les_cf(C.byref(geom), vel.h, lo, hi, int(maxorder), int(model), C.c_double(Cs), mu[0].h, mu[1].h, mu[2].h,
+                                          _h(crse_vel), C.byref(cgeom), int(ratio)))
+
+
 class NavierStokes:
     """level object with the reference's method names (NavierStokes::advance, post_init, ...)"""
     S_NEW, S_OLD, P_NEW, P_OLD, GP_NEW, GP_OLD, UMAC_X, UMAC_Y, UMAC_Z, AOFS = range(10)
+    ETA_N, ETA_NP1 = 13, 16   # + direction: the face viscosities visc_coef + mu_t of the last velocity_diffusion_update (do_LES = 1)
     AVERAGE = 12          # the time-average accumulators (Average_Type, NS_setup.cpp:389-405): 6 components, no ghost cells
     VEL_AVG_NAMES = ["x_vel_average", "y_vel_average", "z_vel_average", "x_vel_rms", "y_vel_rms", "z_vel_rms"]   # NS_setup.cpp:417-427
     _types = {0: ((0, 0, 0), 5, 1), 1: ((0, 0, 0), 5, 1), 2: ((1, 1, 1), 1, 1), 3: ((1, 1, 1), 1, 1), 4: ((0, 0, 0), 3, 1),
               5: ((0, 0, 0), 3, 1), 6: ((1, 0, 0), 1, 1), 7: ((0, 1, 0), 1, 1), 8: ((0, 0, 1), 1, 1), 9: ((0, 0, 0), 5, 0),
-              12: ((0, 0, 0), 6, 0)}
+              12: ((0, 0, 0), 6, 0), 13: ((1, 0, 0), 1, 0), 14: ((0, 1, 0), 1, 0), 15: ((0, 0, 1), 1, 0), 16: ((1, 0, 0), 1, 0),
+              17: ((0, 1, 0), 1, 0), 18: ((0, 0, 1), 1, 0)}
 
     def __init__(self, geom, layout, params=None, opts=None):
         self.geom = geom

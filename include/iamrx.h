@@ -349,6 +349,23 @@ int iamrx_tensor_solve_cf(const iamrx_geom* g, iamrx_mf soln, iamrx_mf rhs, doub
                           iamrx_mf eta_y, iamrx_mf eta_z, const int* lobc, const int* hibc, int nbc, iamrx_mf crse_vel,
                           const iamrx_geom* cgeom, int ratio, double tol_rel, double tol_abs, const iamrx_mg_opts* o, iamrx_mg_stats* st);
 
+/* ---- large-eddy simulation: eddy viscosity on faces (Source/NS_LES.cpp) -------------------------------------------------- */
+/* The model loops of NavierStokesBase::calc_mut_LES (Source/NS_LES.cpp:105-222) on the face gradients of MLTensorOp::compVelGrad (:97), and
+ * the setVal + Add of NavierStokes::getViscosity (Source/NavierStokes.cpp:2136, 2150), in one launch: mu_d (face d, 1 comp, the layout of vel)
+ * = base + mu_t.  vel: cells, velocity in components vcomp .. vcomp + 2, >= 1 ghost layer whose face and edge cells are read AS THE CALLER
+ * LEFT THEM.  model: 0 Smagorinsky (:122-136), 1 Sigma (:150-212); Cs: ns.smago_Cs_cst / ns.sigma_Cs_cst; filter width dx[d]. */
+int iamrx_les_mut(const iamrx_geom* g, iamrx_mf vel, int vcomp, int model, double Cs, double base, iamrx_mf mu_x, iamrx_mf mu_y, iamrx_mf mu_z);
+/* NavierStokesBase::calc_mut_LES (Source/NS_LES.cpp:22-225) behind its FillPatch: vel (3 comps, 1 ghost layer) carries the level's boundary
+ * data in its ghost cells (what FillPatch left there, :86-88), the tensor operator's boundary step fills them (tensorop.setDomainBC with the
+ * per-component codes of LES_setDomainBC, :59-68, 230-285; setLevelBC, :88), then mu_d = mu_t.  lobc / hibc: 9 LinOpBC codes, [n*3+d].
+ * maxorder: NS_LES.cpp sets none on its operator; MLLinOp's default is 3 as far as is known.  vel's ghost cells are overwritten. */
+int iamrx_calc_mut_les(const iamrx_geom* g, iamrx_mf vel, const int* lobc, const int* hibc, int maxorder, int model, double Cs,
+                       iamrx_mf mu_x, iamrx_mf mu_y, iamrx_mf mu_z);
+/* the same on a refined level that does not cover the domain (tensorop.setCoarseFineBC(&crsedata, crse_ratio[0]), Source/NS_LES.cpp:76-84);
+ * crse_vel: the coarse level's velocity (3 comps, valid data on its own layout) at the same time, NULL: homogeneous */
+int iamrx_calc_mut_les_cf(const iamrx_geom* g, iamrx_mf vel, const int* lobc, const int* hibc, int maxorder, int model, double Cs,
+                          iamrx_mf mu_x, iamrx_mf mu_y, iamrx_mf mu_z, iamrx_mf crse_vel, const iamrx_geom* cgeom, int ratio);
+
 /* ---- inter-level data motion (first building blocks) ------------------------------------------------------ */
 /* amrex::MultiFab::ParallelCopy: dst(valid + dst_ng) <- src(valid + src_ng) wherever they intersect; dst and src may live on
  * different layouts of the same index space (same index type); periodic_geom != NULL adds the periodic images of src */
@@ -464,6 +481,10 @@ typedef struct iamrx_ns_params {
     int avg_interval;            /* ns.avg_interval (Source/NavierStokesBase.cpp:487, Source/NS_average.cpp:8-17): > 0: time averages of the velocity, a sample every avg_interval level-0 steps; 0: off */
     int compute_fluctuations;    /* ns.compute_fluctuations (Source/NavierStokesBase.cpp:488): 1 = also the time integral of the squared velocity fluctuation */
     int sum_interval;            /* ns.sum_interval (Source/NavierStokesBase.cpp:452, 2589-2592): > 0: a hierarchy forms its integrated quantities every sum_interval level-0 steps; <= 0: off */
+    int do_LES;                  /* ns.do_LES (Source/NavierStokesBase.cpp:142, 481): 1 = the face viscosity of every viscous apply / solve is visc_coef + mu_t (NavierStokes::getViscosity, Source/NavierStokes.cpp:2139-2152) */
+    int LES_model;               /* ns.LES_model (Source/NavierStokesBase.cpp:143, 482): 0 = "Smagorinsky", 1 = "Sigma" */
+    double smago_Cs_cst;         /* ns.smago_Cs_cst (Source/NavierStokesBase.cpp:144, 483), default 0.18 */
+    double sigma_Cs_cst;         /* ns.sigma_Cs_cst (Source/NavierStokesBase.cpp:145, 484), default 1.5 */
 } iamrx_ns_params;
 void iamrx_ns_default_params(iamrx_ns_params* p);     /* defaults of Source/NavierStokesBase.cpp:96-170 */
 int iamrx_ns_create(const iamrx_geom* g, iamrx_layout l, const iamrx_ns_params* p, const iamrx_mg_opts* o, iamrx_ns* out);
@@ -480,7 +501,10 @@ int iamrx_ns_time(iamrx_ns ns, double* time, double* dt, int* nstep);
  * 3 P_old, 4 Gp_new, 5 Gp_old, 6..8 u_mac, 9 aofs  (get_new_data/get_old_data role); 10, 11: the last two MAC potentials (the
  * initial-guess history of the MAC solve, part of a checkpoint);
  * 12: the time-average accumulators (the reference's Average_Type, Source/NS_setup.cpp:389-405; only with avg_interval > 0): 6 components,
- * no ghost cells -- 0..2 the time integral of u, v, w, 3..5 the time integral of the squared fluctuation (Source/NS_average.cpp:45-55) */
+ * no ghost cells -- 0..2 the time integral of u, v, w, 3..5 the time integral of the squared fluctuation (Source/NS_average.cpp:45-55);
+ * 13..15: the face viscosity visc_coef + mu_t (x, y, z faces, 1 comp, no ghost cells) of the OLD state, 16..18: of the new state (which held
+ * U*), as the last velocity_diffusion_update formed them (loc_viscn / loc_viscnp1, Source/NavierStokes.cpp:1022-1028); an error with
+ * do_LES = 0 or before the first step */
 int iamrx_ns_data(iamrx_ns ns, int which, iamrx_mf* out);
 /* Derived quantities of the plotfile (derive_lst, Source/NS_setup.cpp:436-449; amr.derive_plot_vars): "energy" = rho |u|^2 / 2 (derkeng,
  * Source/NS_derive.cpp:266-295), "mag_vort" = |curl u| (dermgvort, :86-264, ghost cells by FillPatch), "avg_pressure" = mean of the eight
