@@ -698,6 +698,13 @@ int iamrx_nodal_divu(const iamrx_geom* g, iamrx_mf rhs, iamrx_mf vel, int vcomp)
     nodal_divu(gg, rhs->mf, vel->mf, vcomp, &bc);
     IAMRX_CATCH
 }
+int iamrx_nodal_divu_bc(const iamrx_geom* g, iamrx_mf rhs, iamrx_mf vel, int vcomp, const int lobc[3], const int hibc[3])
+{
+    IAMRX_TRY
+    const DomainBC bc = to_bc(lobc, hibc, 2);
+    nodal_divu(to_geom(g), rhs->mf, vel->mf, vcomp, &bc);
+    IAMRX_CATCH
+}
 int iamrx_nodal_compgrad(const iamrx_geom* g, iamrx_mf gp, iamrx_mf phi)
 {
     IAMRX_TRY nodal_mknewu(to_geom(g), nullptr, 0, phi->mf, nullptr, &gp->mf, false); IAMRX_CATCH

@@ -3,6 +3,7 @@
 // Role: amrex MultiFab::{setVal,Copy,Saxpy,Xpay,mult,norm0}, FillBoundary pack/unpack.
 #include "kernels.h"
 #include "launch.h"
+#include <algorithm>
 
 namespace iamrx {
 
@@ -540,6 +541,49 @@ void mf_mult(MultiFab& y, double a, int comp, int nc, int ng)
     for_each_2ph(*y.layout, y.type, ng, nc, Context::get().stream,
         [=] __device__(int i, int j, int k, int f, int n) { return yt[f](i, j, k, comp + n) * a; },
         [=] __device__(int i, int j, int k, int f, int n, double v) { yt[f](i, j, k, comp + n) = v; });
+}
+
+// y *= a on the ghost shell: per box two z-slabs (whole grown planes), two y-slabs (grown rows of the valid planes) and two x-slabs
+__global__ void __launch_bounds__(256) k_mult_shell(const BoxD* __restrict__ boxes, const FabD* __restrict__ yt, int t0, int t1, int t2, int ng, int comp, int nc, double a)
+{
+    const int fab = blockIdx.y;
+    BoxD b = boxes[fab];
+    b.hi[0] += t0; b.hi[1] += t1; b.hi[2] += t2;
+    const FabD y = yt[fab];
+    const long nx = b.len(0), ny = b.len(1), nz = b.len(2), gx = nx + 2 * ng, gy = ny + 2 * ng;
+    const long nA = gx * gy * ng, nB = gx * ng * nz, nC = ng * ny * nz;
+    const long total = 2 * (nA + nB + nC);
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        long r = idx;
+        int i, j, k;
+        if (r < 2 * nA) {
+            const int side = (int)(r / nA); r -= side * nA;
+            i = b.lo[0] - ng + (int)(r % gx); j = b.lo[1] - ng + (int)((r / gx) % gy);
+            k = (side ? b.hi[2] + 1 : b.lo[2] - ng) + (int)(r / (gx * gy));
+        } else if ((r -= 2 * nA) < 2 * nB) {
+            const int side = (int)(r / nB); r -= side * nB;
+            i = b.lo[0] - ng + (int)(r % gx); k = b.lo[2] + (int)(r / (gx * ng));
+            j = (side ? b.hi[1] + 1 : b.lo[1] - ng) + (int)((r / gx) % ng);
+        } else {
+            r -= 2 * nB;
+            const int side = (int)(r / nC); r -= side * nC;
+            j = b.lo[1] + (int)((r / ng) % ny); k = b.lo[2] + (int)(r / (ng * ny));
+            i = (side ? b.hi[0] + 1 : b.lo[0] - ng) + (int)(r % ng);
+        }
+        for (int n = 0; n < nc; ++n) y(i, j, k, comp + n) = y(i, j, k, comp + n) * a;
+    }
+}
+
+void mf_mult_ghosts(MultiFab& y, double a, int comp, int nc, int ng)
+{
+    if (!y.base || ng <= 0 || y.nlocal() == 0) return;
+    IAMRX_ASSERT(ng <= y.ngrow);
+    const Layout& l = *y.layout;
+    const long nx = l.max_len[0] + y.type.t[0], ny = l.max_len[1] + y.type.t[1], nz = l.max_len[2] + y.type.t[2];
+    const long total = 2 * ((nx + 2 * ng) * (ny + 2 * ng) * ng + (nx + 2 * ng) * ng * nz + ng * ny * nz);
+    const long nb = std::min<long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_mult_shell, dim3((unsigned)nb, (unsigned)l.nlocal()), dim3(256), 0, Context::get().stream, l.d_boxes, y.d_tab, y.type.t[0], y.type.t[1],
+                       y.type.t[2], ng, comp, nc, a);
 }
 
 // slab levels (mf.h): every y-plane of dst takes the single y-plane of src

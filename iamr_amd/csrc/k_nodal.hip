@@ -1580,11 +1580,109 @@ void nodal_build_dmask(const Geometry& g, MultiFab& dm, const MultiFab& cov, con
     });
 }
 
+// Tiled form of the restriction below (IAMRX_NODAL_RESTRICT_TILE): a workgroup owns CTX x CTY coarse nodes and marches KC coarse planes.  The
+// three fine planes 2k-1, 2k, 2k+1 of its (2 CTX + 1) x (2 CTY + 1) footprint live in LDS -- rows read from HBM with unit stride, every
+// fine plane once per tile column (plane 2k+1 stays for the next coarse plane), the two planes of the next coarse plane in flight while
+// the current one is summed.  Rows are stored parity-split (column c at (c & 1) * HX + (c >> 1)): the stride-2 reads of the sum are then
+// unit-stride in LDS.  The 27 terms are added in the order of the per-node form: the same doubles.
+template <int CTX, int CTY>
+__global__ void __launch_bounds__(CTX * CTY) k_nodal_restrict_tile(const BoxD* __restrict__ cboxes, const FabD* __restrict__ ct, const FabD* __restrict__ ft,
+    int ntx, int nty, int kc)
+{
+    constexpr int FX = 2 * CTX + 1, FY = 2 * CTY + 1, HX = CTX + 1, PX = 2 * HX, NT = CTX * CTY, NLD = (FX * FY + NT - 1) / NT;
+    __shared__ double F[3][FY][PX];
+    const int fab = blockIdx.y;
+    const BoxD cb = cboxes[fab];
+    const int bid = blockIdx.x;
+    const int tix = bid % ntx, r1 = bid / ntx, tiy = r1 % nty, ck = r1 / nty;
+    const int nhi0 = cb.hi[0] + 1, nhi1 = cb.hi[1] + 1, nhi2 = cb.hi[2] + 1;    // last valid coarse node
+    const int i0 = cb.lo[0] + tix * CTX, j0 = cb.lo[1] + tiy * CTY, k0 = cb.lo[2] + ck * kc;
+    if (i0 > nhi0 || j0 > nhi1 || k0 > nhi2) return;
+    const int k1 = min(k0 + kc - 1, nhi2);
+    const FabD fa = ft[fab], c = ct[fab];
+    const int ox = 2 * i0 - 1, oy = 2 * j0 - 1;                                 // fine node of footprint point (0, 0)
+    const int tid = threadIdx.x;
+    // footprint points of this thread: offset in plane 0 of the fine array (< 0: outside the array or beyond the fine nodes the tile's
+    // valid coarse nodes read -- not loaded, never used) and LDS slot
+    long foff[NLD];
+    int lslot[NLD];
+    const int fhi0 = min(2 * nhi0 + 1, fa.lo[0] + fa.n[0] - 1), fhi1 = min(2 * nhi1 + 1, fa.lo[1] + fa.n[1] - 1);
+#pragma unroll
+    for (int it = 0; it < NLD; ++it) {
+        const int idx = tid + it * NT;
+        const int lx = idx % FX, ly = idx / FX;
+        const int gi = ox + lx, gj = oy + ly;
+        const bool on = idx < FX * FY && gi >= fa.lo[0] && gi <= fhi0 && gj >= fa.lo[1] && gj <= fhi1;
+        foff[it] = on ? fa.off(gi, gj, fa.lo[2]) : -1;
+        lslot[it] = idx < FX * FY ? ly * PX + (lx & 1) * HX + (lx >> 1) : -1;
+    }
+    const long fpl = (long)fa.n[0] * fa.n[1];
+    const FabD::gdouble* fp = (const FabD::gdouble*)fa.p;
+    const int fklo = fa.lo[2], fkhi = fa.lo[2] + fa.n[2] - 1;
+    auto ldf = [&](int it, int k) { return (foff[it] >= 0 && k >= fklo && k <= fkhi) ? (double)fp[foff[it] + fpl * (k - fklo)] : 0.0; };
+    double* Fl = &F[0][0][0];
+    constexpr int PL = FY * PX;
+    int sm = 0, s0 = 1, sp = 2;          // LDS planes of the fine planes 2k-1, 2k, 2k+1
+    double v0[NLD], v1[NLD];
+#pragma unroll
+    for (int it = 0; it < NLD; ++it) {
+        const double vm = ldf(it, 2 * k0 - 1);
+        v0[it] = ldf(it, 2 * k0); v1[it] = ldf(it, 2 * k0 + 1);
+        if (lslot[it] >= 0) Fl[sm * PL + lslot[it]] = vm;
+    }
+    const int tx = tid % CTX, ty = tid / CTX;
+    const int i = i0 + tx, j = j0 + ty;
+    const bool valid = i <= nhi0 && j <= nhi1;
+    // fine columns 2 tx, 2 tx + 1, 2 tx + 2 of the footprint (di = -1, 0, 1) in a parity-split row
+    const int cxm = tx, cx0 = HX + tx, cxp = tx + 1;
+    for (int k = k0; k <= k1; ++k) {
+#pragma unroll
+        for (int it = 0; it < NLD; ++it)
+            if (lslot[it] >= 0) { Fl[s0 * PL + lslot[it]] = v0[it]; Fl[sp * PL + lslot[it]] = v1[it]; }
+        __syncthreads();
+        if (k < k1) {
+#pragma unroll
+            for (int it = 0; it < NLD; ++it) { v0[it] = ldf(it, 2 * k + 2); v1[it] = ldf(it, 2 * k + 3); }
+        }
+        if (valid) {
+            const int pl[3] = {sm, s0, sp};
+            double s = 0.0;
+#pragma unroll
+            for (int dk = 0; dk < 3; ++dk)
+#pragma unroll
+                for (int dj = 0; dj < 3; ++dj) {
+                    const double* row = Fl + pl[dk] * PL + (2 * ty + dj) * PX;
+                    const double wjk = (dj == 1 ? 2. : 1.) * (dk == 1 ? 2. : 1.);
+                    s += (1. * wjk) * row[cxm];
+                    s += (2. * wjk) * row[cx0];
+                    s += (1. * wjk) * row[cxp];
+                }
+            c(i, j, k) = s * (1. / 64.);
+        }
+        __syncthreads();
+        const int t = sm; sm = sp; sp = s0; s0 = t;
+    }
+}
+
 // full weighting (1,2,1)^3/64; the fine array needs one filled ghost-node layer
 void nodal_restrict(MultiFab& crse, const MultiFab& fine)
 {
     if (crse.nlocal() == 0) return;
     const FabD *ct = crse.d_tab, *ft = fine.d_tab;
+    const Layout& cl = *crse.layout;
+    // (measured on MI355X, coarse 128^3 / 64^3 / 32^3: 38 / 12 / 8 us against 50 / 15 / 5 us of the per-node form -- small levels are launch
+    // latency, not traffic, and few workgroups of 256 threads: IAMRX_NODAL_RESTRICT_MIN coarse cells in x, at least 16)
+    const int min_x = std::max(16, (int)tune("NODAL_RESTRICT_MIN", 48));
+    if (tune("NODAL_RESTRICT_TILE", 1) != 0 && cl.max_len[0] >= min_x && cl.max_len[1] >= 8 && fine.ngrow >= 1) {
+        constexpr int CTX = 32, CTY = 8;
+        const int ntx = (cl.max_len[0] + 1 + CTX - 1) / CTX, nty = (cl.max_len[1] + 1 + CTY - 1) / CTY;
+        const int nk = cl.max_len[2] + 1;
+        const int kc = nk >= 64 ? 8 : 4;
+        const int nck = (nk + kc - 1) / kc;
+        dim3 grid((unsigned)(ntx * nty * nck), (unsigned)cl.nlocal());
+        hipLaunchKernelGGL((k_nodal_restrict_tile<CTX, CTY>), grid, dim3(CTX * CTY), 0, Context::get().stream, cl.d_boxes, ct, ft, ntx, nty, kc);
+        return;
+    }
     for_each(*crse.layout, node_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
         const FabD fa = ft[f];
         const int ii = 2 * i, jj = 2 * j, kk = 2 * k;
@@ -1709,7 +1807,9 @@ __global__ void __launch_bounds__(256) k_nodal_interp_lds(const BoxD* __restrict
     // (sigma of the tile in LDS -- one unit-stride pass, parity-split rows, no bank conflicts -- was measured twice: 230 / 235 us against 177 us.
     // The side weights' 8 sigma loads per node and class ARE 103 of the 177 us (constant weights: 74 us, tools/r5_interp_exp.sh), but 27 KB more
     // LDS per workgroup take the occupancy from 7 to 3 workgroups per CU, and the phases between the barriers are too short to do without it.
-    // What would work is one coarse cell per thread with its 27 sigma values in registers for all four phases -- not built.)
+    // One coarse cell per thread with its 27 sigma values in registers for all four phases -- a 33 x 9 thread column tile marching in z, 18
+    // sigma loads per eight nodes -- was built and measured as well: 114 VGPRs (4 wavefronts per SIMD; held to 96 / 80 it spills 20 / 38) and
+    // five barriers per pair of planes, 212 / 31 / 23 us at 257^3 / 129^3 / 65^3 against 176 / 28 / 13 us here, same doubles.  Not adopted.)
     const FabD& s = sg;
 #define IAMRX_ICLS(PX, PY, PZ) interp_class<PX, PY, PZ, CX, CY, CZ>(T, c, s, fi0, fj0, fk0, nhi0, nhi1, nhi2, tid)
     IAMRX_ICLS(0, 0, 0);
@@ -1781,6 +1881,116 @@ void nodal_interp_add(MultiFab& fine, const MultiFab& crse, const MultiFab& sig_
     });
 }
 
+// what the two forms of nodal_divu share: wall / inflow flags per face, the domain and the scale factors
+struct DivuGeom {
+    int wl[3], wh[3], il[3], ih[3];     // Neumann wall flags, inflow flags
+    int dl[3], dh[3];
+    double f[3];
+};
+
+// the divergence at node (i, j, k) from its eight cells, v(ci, cj, ck, n) = component n of the velocity: the expression of both forms
+template <class V>
+__device__ __forceinline__ double divu_node(const DivuGeom& G, int i, int j, int k, const V& v)
+{
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+#pragma unroll
+    for (int cz = 0; cz < 2; ++cz)
+#pragma unroll
+        for (int cy = 0; cy < 2; ++cy)
+#pragma unroll
+            for (int cx = 0; cx < 2; ++cx) {
+                const int ci = i - 1 + cx, cj = j - 1 + cy, ck = k - 1 + cz;
+                const bool outside = (G.wl[0] && ci < G.dl[0]) || (G.wh[0] && ci > G.dh[0]) || (G.wl[1] && cj < G.dl[1]) || (G.wh[1] && cj > G.dh[1]) ||
+                                     (G.wl[2] && ck < G.dl[2]) || (G.wh[2] && ck > G.dh[2]);
+                const bool in0 = (G.il[0] && ci < G.dl[0]) || (G.ih[0] && ci > G.dh[0]), in1 = (G.il[1] && cj < G.dl[1]) || (G.ih[1] && cj > G.dh[1]),
+                           in2 = (G.il[2] && ck < G.dl[2]) || (G.ih[2] && ck > G.dh[2]);
+                sx += (cx ? 1.0 : -1.0) * ((outside || in1 || in2) ? 0.0 : v(ci, cj, ck, 0));
+                sy += (cy ? 1.0 : -1.0) * ((outside || in0 || in2) ? 0.0 : v(ci, cj, ck, 1));
+                sz += (cz ? 1.0 : -1.0) * ((outside || in0 || in1) ? 0.0 : v(ci, cj, ck, 2));
+            }
+    double r = 0.0;
+    r += G.f[0] * sx; r += G.f[1] * sy; r += G.f[2] * sz;
+    if ((G.wl[0] || G.il[0]) && i == G.dl[0]) r *= 2.0;
+    if ((G.wh[0] || G.ih[0]) && i == G.dh[0] + 1) r *= 2.0;
+    if ((G.wl[1] || G.il[1]) && j == G.dl[1]) r *= 2.0;
+    if ((G.wh[1] || G.ih[1]) && j == G.dh[1] + 1) r *= 2.0;
+    if ((G.wl[2] || G.il[2]) && k == G.dl[2]) r *= 2.0;
+    if ((G.wh[2] || G.ih[2]) && k == G.dh[2] + 1) r *= 2.0;
+    return r;
+}
+
+// z-marching form of nodal_divu (IAMRX_NODAL_DIVU_ZM): a workgroup owns TX x TY nodes and walks KC node planes; the two cell planes k-1, k
+// of the three velocity components on its (TX + 1) x (TY + 1) cell footprint live in LDS (rolling), so a cell is read from HBM once per
+// tile column instead of eight times from cache, and the loads of cell plane k+1 are in flight while plane k is evaluated.
+template <int TX, int TY>
+__global__ void __launch_bounds__(TX * TY) k_nodal_divu_zm(const BoxD* __restrict__ boxes, const FabD* __restrict__ rt, const FabD* __restrict__ vt, int vcomp,
+    DivuGeom G, int ntx, int nty, int kc)
+{
+    constexpr int RX = TX + 1, RY = TY + 1, NT = TX * TY, NLD = (RX * RY + NT - 1) / NT;
+    __shared__ double V[2][3][RY][RX];
+    const int fab = blockIdx.y;
+    const BoxD cb = boxes[fab];
+    const int bid = blockIdx.x;
+    const int tix = bid % ntx, r1 = bid / ntx, tiy = r1 % nty, ck = r1 / nty;
+    const int nhi0 = cb.hi[0] + 1, nhi1 = cb.hi[1] + 1, nhi2 = cb.hi[2] + 1;
+    const int tx0 = cb.lo[0] + tix * TX, ty0 = cb.lo[1] + tiy * TY, k0 = cb.lo[2] + ck * kc;
+    if (tx0 > nhi0 || ty0 > nhi1 || k0 > nhi2) return;
+    const int k1 = min(k0 + kc - 1, nhi2);
+    const FabD v = vt[fab], o = rt[fab];
+    const int ox = tx0 - 1, oy = ty0 - 1;                    // cell of footprint point (0, 0)
+    const int tid = threadIdx.x;
+    // footprint cells of this thread: offset in plane 0 of component vcomp (< 0: outside the array or beyond the cells the tile's valid
+    // nodes read -- not loaded, never used)
+    long voff[NLD];
+    int lidx[NLD];
+    const int chi0 = min(nhi0, v.lo[0] + v.n[0] - 1), chi1 = min(nhi1, v.lo[1] + v.n[1] - 1);
+#pragma unroll
+    for (int it = 0; it < NLD; ++it) {
+        const int idx = tid + it * NT;
+        const int gi = ox + idx % RX, gj = oy + idx / RX;
+        const bool on = idx < RX * RY && gi >= v.lo[0] && gi <= chi0 && gj >= v.lo[1] && gj <= chi1;
+        voff[it] = on ? v.off(gi, gj, v.lo[2]) + v.cs * vcomp : -1;
+        lidx[it] = idx < RX * RY ? idx : -1;
+    }
+    const long vpl = (long)v.n[0] * v.n[1];
+    const FabD::gdouble* vp = (const FabD::gdouble*)v.p;
+    const int vklo = v.lo[2], vkhi = v.lo[2] + v.n[2] - 1;
+    auto ldv = [&](int it, int n, int k) { return (voff[it] >= 0 && k >= vklo && k <= vkhi) ? (double)vp[voff[it] + v.cs * n + vpl * (k - vklo)] : 0.0; };
+    double* Vl = &V[0][0][0][0];
+    constexpr int PC = RY * RX, PL = 3 * PC;
+    double nv[NLD][3];
+#pragma unroll
+    for (int it = 0; it < NLD; ++it)
+#pragma unroll
+        for (int n = 0; n < 3; ++n) {
+            const double vm = ldv(it, n, k0 - 1);
+            nv[it][n] = ldv(it, n, k0);
+            if (lidx[it] >= 0) Vl[((k0 + 1) & 1) * PL + n * PC + lidx[it]] = vm;
+        }
+    const int lx = tid % TX + 1, ly = tid / TX + 1;
+    const int i = ox + lx, j = oy + ly;
+    const bool valid = i <= nhi0 && j <= nhi1;
+    for (int k = k0; k <= k1; ++k) {
+#pragma unroll
+        for (int it = 0; it < NLD; ++it)
+#pragma unroll
+            for (int n = 0; n < 3; ++n)
+                if (lidx[it] >= 0) Vl[(k & 1) * PL + n * PC + lidx[it]] = nv[it][n];
+        __syncthreads();
+        if (k < k1) {
+#pragma unroll
+            for (int it = 0; it < NLD; ++it)
+#pragma unroll
+                for (int n = 0; n < 3; ++n) nv[it][n] = ldv(it, n, k + 1);
+        }
+        if (valid) {
+            // cell (ci, cj, ck) of the footprint: plane ck & 1, row cj - oy, column ci - ox
+            o(i, j, k) = divu_node(G, i, j, k, [&](int ci, int cj, int ck, int n) { return Vl[(ck & 1) * PL + n * PC + (cj - oy) * RX + (ci - ox)]; });
+        }
+        __syncthreads();
+    }
+}
+
 // rhs(node) = FE divergence of the cell-centred velocity (mlndlap_divu); vel needs 1 filled ghost cell
 // bc (may be null = periodic / interior only): cells outside a Neumann wall contribute zero velocity and the rhs of
 // wall nodes is doubled per wall direction (mlndlap_divu + mlndlap_impose_neumann_bc)
@@ -1788,44 +1998,37 @@ void nodal_divu(const Geometry& g, MultiFab& rhs, const MultiFab& vel, int vcomp
 {
     if (rhs.nlocal() == 0) return;
     const FabD *rt = rhs.d_tab, *vt = vel.d_tab;
-    const double fx = 0.25 / g.dx[0], fy = 0.25 / g.dx[1], fz = 0.25 / g.dx[2];
     // set_boundary_velocity (Source/Projection.cpp:2570-2663) + mlndlap_divu: cells outside a Neumann wall carry no velocity,
     // outside an inflow face only the normal component (the inflow value) survives; the rhs of wall / inflow nodes is doubled
-    int wl[3], wh[3], il[3], ih[3];     // Neumann wall flags, inflow flags
+    DivuGeom G;
     for (int d = 0; d < 3; ++d) {
-        wl[d] = (bc && !g.periodic[d] && bc->lo[d] == lo_neumann) ? 1 : 0;
-        wh[d] = (bc && !g.periodic[d] && bc->hi[d] == lo_neumann) ? 1 : 0;
-        il[d] = (bc && !g.periodic[d] && bc->lo[d] == lo_inflow) ? 1 : 0;
-        ih[d] = (bc && !g.periodic[d] && bc->hi[d] == lo_inflow) ? 1 : 0;
+        G.wl[d] = (bc && !g.periodic[d] && bc->lo[d] == lo_neumann) ? 1 : 0;
+        G.wh[d] = (bc && !g.periodic[d] && bc->hi[d] == lo_neumann) ? 1 : 0;
+        G.il[d] = (bc && !g.periodic[d] && bc->lo[d] == lo_inflow) ? 1 : 0;
+        G.ih[d] = (bc && !g.periodic[d] && bc->hi[d] == lo_inflow) ? 1 : 0;
+        G.dl[d] = g.domain.lo[d]; G.dh[d] = g.domain.hi[d];
+        G.f[d] = 0.25 / g.dx[d];
     }
-    const int wl0 = wl[0], wl1 = wl[1], wl2 = wl[2], wh0 = wh[0], wh1 = wh[1], wh2 = wh[2];
-    const int il0 = il[0], il1 = il[1], il2 = il[2], ih0 = ih[0], ih1 = ih[1], ih2 = ih[2];
-    const int dl0 = g.domain.lo[0], dl1 = g.domain.lo[1], dl2 = g.domain.lo[2], dh0 = g.domain.hi[0], dh1 = g.domain.hi[1], dh2 = g.domain.hi[2];
-    for_each(*rhs.layout, node_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
+    const Layout& l = *rhs.layout;
+    if (tune("NODAL_DIVU_ZM", 1) != 0 && l.max_len[0] >= 16 && l.max_len[1] >= 8 && vel.ngrow >= 1) {
+        constexpr int TX = 32, TY = 8;
+        const int ntx = (l.max_len[0] + 1 + TX - 1) / TX, nty = (l.max_len[1] + 1 + TY - 1) / TY;
+        const int nk = l.max_len[2] + 1;
+        const int kc = nk >= 128 ? 32 : (nk >= 32 ? 16 : nk);
+        const int nck = (nk + kc - 1) / kc;
+        dim3 grid((unsigned)(ntx * nty * nck), (unsigned)l.nlocal());
+        hipLaunchKernelGGL((k_nodal_divu_zm<TX, TY>), grid, dim3(TX * TY), 0, Context::get().stream, l.d_boxes, rt, vt, vcomp, G, ntx, nty, kc);
+        return;
+    }
+    for_each(l, node_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
         const FabD v = vt[f];
-        double sx = 0.0, sy = 0.0, sz = 0.0;
-        for (int cz = 0; cz < 2; ++cz) for (int cy = 0; cy < 2; ++cy) for (int cx = 0; cx < 2; ++cx) {
-            const int ci = i - 1 + cx, cj = j - 1 + cy, ck = k - 1 + cz;
-            const bool outside = (wl0 && ci < dl0) || (wh0 && ci > dh0) || (wl1 && cj < dl1) || (wh1 && cj > dh1) || (wl2 && ck < dl2) || (wh2 && ck > dh2);
-            const bool in0 = (il0 && ci < dl0) || (ih0 && ci > dh0), in1 = (il1 && cj < dl1) || (ih1 && cj > dh1), in2 = (il2 && ck < dl2) || (ih2 && ck > dh2);
-            sx += (cx ? 1.0 : -1.0) * ((outside || in1 || in2) ? 0.0 : v(ci, cj, ck, vcomp));
-            sy += (cy ? 1.0 : -1.0) * ((outside || in0 || in2) ? 0.0 : v(ci, cj, ck, vcomp + 1));
-            sz += (cz ? 1.0 : -1.0) * ((outside || in0 || in1) ? 0.0 : v(ci, cj, ck, vcomp + 2));
-        }
-        double r = 0.0;
-        r += fx * sx; r += fy * sy; r += fz * sz;
-        if ((wl0 || il0) && i == dl0) r *= 2.0;
-        if ((wh0 || ih0) && i == dh0 + 1) r *= 2.0;
-        if ((wl1 || il1) && j == dl1) r *= 2.0;
-        if ((wh1 || ih1) && j == dh1 + 1) r *= 2.0;
-        if ((wl2 || il2) && k == dl2) r *= 2.0;
-        if ((wh2 || ih2) && k == dh2 + 1) r *= 2.0;
-        rt[f](i, j, k) = r;
+        rt[f](i, j, k) = divu_node(G, i, j, k, [&](int ci, int cj, int ck, int n) { return (double)v(ci, cj, ck, vcomp + n); });
     });
 }
 
 // vel -= sig * grad(phi) (mlndlap_mknewu_aa); gp (optional) = grad(phi) stored or accumulated (compGrad)
-void nodal_mknewu(const Geometry& g, MultiFab* vel, int vcomp, const MultiFab& phi, const MultiFab* sig, MultiFab* gp, bool gp_increment)
+// vel_scale != 1: the new velocity is stored times vel_scale -- the product the caller's mf_mult over the valid cells would form from it
+void nodal_mknewu(const Geometry& g, MultiFab* vel, int vcomp, const MultiFab& phi, const MultiFab* sig, MultiFab* gp, bool gp_increment, double vel_scale)
 {
     if (phi.nlocal() == 0) return;
     const FabD* pt = phi.d_tab;
@@ -1847,7 +2050,12 @@ void nodal_mknewu(const Geometry& g, MultiFab* vel, int vcomp, const MultiFab& p
         if (vt) {
             const double sg = st[f](i, j, k);
             const double fc[3] = {f0, f1, f2};
-            for (int d = 0; d < 3; ++d) vt[f](i, j, k, vcomp + d) -= sg * fc[d] * s[d];
+            for (int d = 0; d < 3; ++d) {
+                double u = vt[f](i, j, k, vcomp + d);
+                u -= sg * fc[d] * s[d];
+                if (vel_scale != 1.0) u = u * vel_scale;
+                vt[f](i, j, k, vcomp + d) = u;
+            }
         }
         if (gt) for (int d = 0; d < 3; ++d) { if (gp_increment) gt[f](i, j, k, d) += gr[d]; else gt[f](i, j, k, d) = gr[d]; }
     });

@@ -40,6 +40,8 @@ void mf_lincomb(MultiFab& dst, double a, const MultiFab& x, double b, const Mult
 void mf_saxpy(MultiFab& y, double a, const MultiFab& x, int xcomp, int ycomp, int nc, int ng);                          // y += a*x
 void mf_add_scalar(MultiFab& y, double a, int comp, int nc, int ng);
 void mf_mult(MultiFab& y, double a, int comp, int nc, int ng);
+// the same on the ng ghost layers only (the valid region is not touched): one launch over the shell of every box
+void mf_mult_ghosts(MultiFab& y, double a, int comp, int nc, int ng);
 
 // ---- k_stats.hip: on-the-fly velocity statistics (NS_average.cpp, NS_derive.cpp:11-45) ------
 // avg(0..2) += dt_avg * vel; fluct: avg(3..5) += dt_avg * (vel - avg(0..2) / t_sum)^2 with the updated avg(0..2); vel = S(vcomp..)
@@ -231,7 +233,8 @@ void nodal_restrict(MultiFab& crse, const MultiFab& fine);
 void nodal_interp_add(MultiFab& fine, const MultiFab& crse, const MultiFab& sig_fine);
 void nodal_divu(const Geometry& g, MultiFab& rhs, const MultiFab& vel, int vcomp, const DomainBC* bc);
 // vel(vcomp..) -= sig*grad(phi) (vel may be null); gp (may be null) = or += grad(phi)
-void nodal_mknewu(const Geometry& g, MultiFab* vel, int vcomp, const MultiFab& phi, const MultiFab* sig, MultiFab* gp, bool gp_increment);
+// vel_scale: the velocity is stored times this factor (the caller's scaling pass over the valid cells, folded in)
+void nodal_mknewu(const Geometry& g, MultiFab* vel, int vcomp, const MultiFab& phi, const MultiFab* sig, MultiFab* gp, bool gp_increment, double vel_scale = 1.0);
 
 // ---- k_tensor.hip -------------------------------------------------------------------------
 void tensor_bcoef(MultiFab& b3, const MultiFab& eta, int dir);

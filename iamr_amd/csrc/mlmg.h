@@ -242,7 +242,9 @@ public:
     NodalMG(const Geometry& g, LayoutP layout, const DomainBC& bc, const MGOpts& o);
     // sigma: cell centred, valid region used (ghost cells are filled internally, as MLNodeLaplacian does)
     void setSigma(const MultiFab& sig, int comp);
-    MGStats solve(MultiFab& phi, const MultiFab& rhs, double rtol, double atol);
+    // rhs_is_temporary: the caller does not read rhs again -- the solve works on it in place (Dirichlet nodes zeroed, mean removed) instead
+    // of on a copy (IAMRX_NODAL_RHS_INPLACE)
+    MGStats solve(MultiFab& phi, const MultiFab& rhs, double rtol, double atol, bool rhs_is_temporary = false);
     int nlevels() const { return (int)m_lev.size(); }
     bool masked() const { return m_masked; }
     const MultiFab* dmask(int l) const { return m_lev[l].dmask(); }

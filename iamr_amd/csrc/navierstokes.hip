@@ -1231,7 +1231,11 @@ void NavierStokes::level_project(double dt_)
         rhcc = make_rhcc(g, rhv, 0, 1.0, nullptr);
     }
     const MultiFab* rv = have_divu ? &rhv : nullptr;
-    st_nodal = nodal_projection(g, Sn, Xvel, Pn, sig, 0, bc_nodal, p.proj_tol, p.proj_abs_tol, o, &Gp[pnew], false, have_divu ? &rhcc : nullptr);
+    // U_new *= dt (:438, below): the valid cells by nodal_mknewu, which holds the value, the ghost cells by a launch over the shell
+    // (IAMRX_PROJ_SCALE_FUSED; nothing between the projection and that scaling reads U_new)
+    const bool fused_scale = tune("PROJ_SCALE_FUSED", 1) != 0;
+    st_nodal = nodal_projection(g, Sn, Xvel, Pn, sig, 0, bc_nodal, p.proj_tol, p.proj_abs_tol, o, &Gp[pnew], false, have_divu ? &rhcc : nullptr,
+                                fused_scale ? dt_ : 1.0);
     fill_gradp_bc();
     if (want_crse) {                                             // crse_sync_reg->CrseInit(sync_resid_crse, geom, 1.0), Projection.cpp:401-410
         MultiFab r = amr_sync_resid(*this, vold, Pn, sig, true, rv);
@@ -1241,7 +1245,8 @@ void NavierStokes::level_project(double dt_)
         MultiFab r = amr_sync_resid(*this, vold, Pn, sig, false, rv);
         sync_reg->FineAdd(r, 1.0 / (double)ncycle);
     }
-    mf_mult(Sn, dt_, Xvel, 3, 1);                                // U_new *= dt (:438)
+    if (fused_scale) mf_mult_ghosts(Sn, dt_, Xvel, 3, 1);        // U_new *= dt (:438)
+    else mf_mult(Sn, dt_, Xvel, 3, 1);
 }
 
 // Ghost cells outside an inflow face hold the boundary value of the field being projected (setPhysBoundaryValues before the

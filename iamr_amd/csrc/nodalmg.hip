@@ -59,25 +59,34 @@ NodalMG::NodalMG(const Geometry& g, LayoutP layout, const DomainBC& bc_in, const
         if (!mg_coarsen_level(f, m_o, c)) break;     // (mlmg.hip: isotropic, slab or agglomerated level)
         m_lev.push_back(std::move(c));
     }
+    // Dirichlet nodes: on Dirichlet (outflow) domain faces and on the boundary of a level that does not cover the domain
+    // (coarse/fine boundary of an AMR level).  They keep their value, carry no residual and take no correction.
+    bool need_mask = false;
+    for (int d = 0; d < 3; ++d) if (!g.periodic[d] && (bc.lo[d] == lo_dirichlet || bc.hi[d] == lo_dirichlet)) need_mask = true;
+    if (m_lev[0].layout->total_cells() != g.domain.npts()) need_mask = true;
     for (auto& L : m_lev) {
         if (L.agg) L.tmp_d.define(L.dist, node_type(), 1, 1);
         if (L.slab) L.vres.define(L.virt, node_type(), 1, 0);
         // 4 ghost layers: the plane-fused Gauss-Seidel recomputes its halo instead of exchanging it per colour
         const int ng = nodal_fused() ? 4 : 1;
         L.sig.define(L.layout, cell_type(), 1, ng);
-        // ghost cells beyond a coarse/fine boundary are never filled (setSigma: valid cells, neighbours / periodic images, wall mirrors);
-        // the prolongation forms sigma-weighted averages at the (masked) boundary nodes before they are zeroed: keep them finite
-        L.sig.setVal(0.0);
         L.cor.define(L.layout, node_type(), 1, ng);
         L.res.define(L.layout, node_type(), 1, ng);
         L.rescor.define(L.layout, node_type(), 1, 1);
+        // The zero fills below give a value to what nobody writes: ghost cells beyond a coarse/fine boundary (setSigma fills valid cells,
+        // neighbours / periodic images and wall mirrors; the prolongation forms sigma-weighted averages at the masked boundary nodes before
+        // they are zeroed: keep them finite) and ghost nodes outside the level.  A level without Dirichlet nodes that is one box spanning
+        // its domain (smooth(): `wrap`) and goes to k_nodal_gsr has neither: its kernels read valid data and the ghost layers fillbc /
+        // setSigma fill completely; sig and res are written (copy / residual / restriction) before they are read, rescor by the residual,
+        // and cor starts from zero inside the first sweep or is zeroed by smooth() / vcycle().  There the four fills are skipped
+        // (IAMRX_NODAL_SKIP_FILLS; IAMRX_POISON_ALLOC = 1 / 2 must not change a result).
+        int refl = 0;
+        const bool written_first = tune("NODAL_SKIP_FILLS", 1) != 0 && !need_mask && m_o.nodal_smoother == 0 && nodal_fused() &&
+                                   nodal_wrap_or_reflect_ok(L.g, *L.layout, m_bc, 4, &refl) && nodal_gsr_applies(L.cor, L.res, nullptr);
+        if (written_first) continue;
+        L.sig.setVal(0.0);
         L.cor.setVal(0.0); L.res.setVal(0.0); L.rescor.setVal(0.0);
     }
-    // Dirichlet nodes: on Dirichlet (outflow) domain faces and on the boundary of a level that does not cover the domain
-    // (coarse/fine boundary of an AMR level).  They keep their value, carry no residual and take no correction.
-    bool need_mask = false;
-    for (int d = 0; d < 3; ++d) if (!g.periodic[d] && (bc.lo[d] == lo_dirichlet || bc.hi[d] == lo_dirichlet)) need_mask = true;
-    if (m_lev[0].layout->total_cells() != g.domain.npts()) need_mask = true;
     for (auto& L : m_lev) {
         if (!need_mask) break;
         MultiFab cov(L.layout, cell_type(), 1, 1);
@@ -355,15 +364,21 @@ void NodalMG::vcycle_correction_inplace(MGStats& st)
     nodal_reflect_bc(L0.g, L0.cor, m_bc);
 }
 
-MGStats NodalMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, double atol)
+MGStats NodalMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, double atol, bool rhs_is_temporary)
 {
     ProfScope ps_prof_("nmg_solve");
     auto& ctx = Context::get();
     MGStats st;
     st.nlevels = (int)m_lev.size();
     Level& L0 = m_lev[0];
-    MultiFab rhs(L0.layout, node_type(), 1, 0);
-    MultiFab::Copy(rhs, rhs_in, 0, 0, 1, 0);
+    // the solve changes its right-hand side (Dirichlet nodes, mean): on a copy, unless the caller gives its array away
+    const bool inplace = rhs_is_temporary && tune("NODAL_RHS_INPLACE", 1) != 0;
+    MultiFab rhs_copy;
+    if (!inplace) {
+        rhs_copy.define(L0.layout, node_type(), 1, 0);
+        MultiFab::Copy(rhs_copy, rhs_in, 0, 0, 1, 0);
+    }
+    MultiFab& rhs = inplace ? const_cast<MultiFab&>(rhs_in) : rhs_copy;
     if (L0.dmask()) nodal_zero_masked(rhs, L0.dm);
     if (m_singular) subtract_mean(0, rhs);
     residual(0, L0.res, phi, rhs, &st.resnorm0);

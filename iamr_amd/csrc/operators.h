@@ -21,7 +21,8 @@ MGStats mlmg_mac_solve(const Geometry& g, MultiFab* const umac[3], const MultiFa
 // rhs = div(vel) at nodes, solve div(sig grad phi) = rhs, vel -= sig grad phi, Gp = / += grad phi.
 MGStats nodal_projection(const Geometry& g, MultiFab& vel, int vcomp, MultiFab& phi, const MultiFab& sig, int sig_comp,
                          const DomainBC& bc, double rel_tol, double abs_tol, const MGOpts& opts, MultiFab* gp, bool increment_gp,
-                         const MultiFab* rhcc = nullptr /* cell-centred source prepared by make_rhcc: div(sig grad phi) = div(vel) + <rhcc> */);
+                         const MultiFab* rhcc = nullptr /* cell-centred source prepared by make_rhcc: div(sig grad phi) = div(vel) + <rhcc> */,
+                         double vel_scale = 1.0 /* the valid cells of the projected velocity are stored times this factor (nodal_mknewu) */);
 void nodal_rhcc_add(const Geometry& g, MultiFab& rhs, const MultiFab& rc, const DomainBC& bc);
 MultiFab make_rhcc(const Geometry& g, const MultiFab& src, int comp, double scale, const MultiFab* drop);
 void mask_mult(MultiFab& y, int ycomp, int nc, const MultiFab& m, bool keep_where_zero, int ng);   // y *= (m == 0) or (m != 0), amrns.hip

@@ -54,7 +54,8 @@ MultiFab make_rhcc(const Geometry& g, const MultiFab& src, int comp, double scal
 }
 
 MGStats nodal_projection(const Geometry& g, MultiFab& vel, int vcomp, MultiFab& phi, const MultiFab& sig, int sig_comp,
-                         const DomainBC& bc, double rel_tol, double abs_tol, const MGOpts& opts, MultiFab* gp, bool increment_gp, const MultiFab* rhcc)
+                         const DomainBC& bc, double rel_tol, double abs_tol, const MGOpts& opts, MultiFab* gp, bool increment_gp, const MultiFab* rhcc,
+                         double vel_scale)
 {
     LayoutP layout = phi.layout;
     // caller-owned arrays on a level chopped at amr.max_grid_size: project on the merged boxes (see mlmg_mac_solve); a level with a
@@ -68,6 +69,7 @@ MGStats nodal_projection(const Geometry& g, MultiFab& vel, int vcomp, MultiFab& 
         if (rhcc) { rh_m.define(ml, cell_type(), 1, rhcc->ngrow); relayout_copy(rh_m, *rhcc, 1); }
         MGStats st = nodal_projection(g, vel_m, 0, phi_m, sig_m, 0, bc, rel_tol, abs_tol, opts, gp ? &gp_m : nullptr, increment_gp, rhcc ? &rh_m : nullptr);
         relayout_copy(vel, vel_m, 3, 0, vcomp);
+        if (vel_scale != 1.0) mf_mult(vel, vel_scale, vcomp, 3, 0);
         relayout_copy(phi, phi_m, 1);
         if (gp) relayout_copy(*gp, gp_m, 3);
         return st;
@@ -79,8 +81,8 @@ MGStats nodal_projection(const Geometry& g, MultiFab& vel, int vcomp, MultiFab& 
     MultiFab rhs(layout, node_type(), 1, 0);
     nodal_divu(g, rhs, vel, vcomp, &bc);
     if (rhcc) nodal_rhcc_add(g, rhs, *rhcc, bc);
-    MGStats st = mg.solve(phi, rhs, rel_tol, abs_tol);
-    nodal_mknewu(g, &vel, vcomp, phi, &mg.sigma(0), gp, increment_gp);
+    MGStats st = mg.solve(phi, rhs, rel_tol, abs_tol, true);     // (rhs is this function's own array)
+    nodal_mknewu(g, &vel, vcomp, phi, &mg.sigma(0), gp, increment_gp, vel_scale);
     if (gp) gp->FillBoundary(g);
     return st;
 }
@@ -101,8 +103,11 @@ MGStats level_project_single(const Geometry& g, double dt, MultiFab& U_new, int 
             st[f](i, j, k, 0) = 1.0 / rh;                                                            // scaleVar
         });
     }
-    MGStats st = nodal_projection(g, U_new, vcomp, P_new, sig, 0, bc, proj_tol, proj_abs_tol, opts, &Gp_new, false);
-    mf_mult(U_new, dt, vcomp, 3, 1);                             // :438
+    // U_new *= dt (:438): the valid cells by nodal_mknewu, which holds the value, the ghost cells by a launch over the shell (IAMRX_PROJ_SCALE_FUSED)
+    const bool fused_scale = tune("PROJ_SCALE_FUSED", 1) != 0;
+    MGStats st = nodal_projection(g, U_new, vcomp, P_new, sig, 0, bc, proj_tol, proj_abs_tol, opts, &Gp_new, false, nullptr, fused_scale ? dt : 1.0);
+    if (fused_scale) mf_mult_ghosts(U_new, dt, vcomp, 3, 1);
+    else mf_mult(U_new, dt, vcomp, 3, 1);
     return st;
 }
 

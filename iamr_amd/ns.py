@@ -61,8 +61,12 @@ def nodal_interp_add(fine, crse, sig_fine):
     check(lib().iamrx_nodal_interp_add(fine.h, crse.h, sig_fine.h))
 
 
-def nodal_divu(geom, rhs, vel, vcomp=0):
-    check(lib().iamrx_nodal_divu(C.byref(geom), rhs.h, vel.h, vcomp))
+def nodal_divu(geom, rhs, vel, vcomp=0, lobc=None, hibc=None):
+    """lobc / hibc: LinOp codes of the non-periodic faces (Neumann wall, inflow); None: every non-periodic face is a wall"""
+    if lobc is None and hibc is None:
+        check(lib().iamrx_nodal_divu(C.byref(geom), rhs.h, vel.h, vcomp))
+    else:
+        check(lib().iamrx_nodal_divu_bc(C.byref(geom), rhs.h, vel.h, vcomp, i3(lobc), i3(hibc)))
 
 
 def nodal_compgrad(geom, gp, phi):

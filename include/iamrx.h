@@ -296,6 +296,9 @@ int iamrx_nodal_gs_sweep(const iamrx_geom* g, iamrx_mf phi, iamrx_mf rhs, iamrx_
 int iamrx_nodal_restrict(iamrx_mf crse, iamrx_mf fine);
 int iamrx_nodal_interp_add(iamrx_mf fine, iamrx_mf crse, iamrx_mf sig_fine);
 int iamrx_nodal_divu(const iamrx_geom* g, iamrx_mf rhs, iamrx_mf vel, int vcomp);
+/* the same with the boundary codes of the non-periodic faces (LinOpBC codes: 102 Neumann wall, 103 inflow -- only the normal velocity
+   outside the face counts); periodic directions ignore theirs */
+int iamrx_nodal_divu_bc(const iamrx_geom* g, iamrx_mf rhs, iamrx_mf vel, int vcomp, const int lobc[3], const int hibc[3]);
 /* MLNodeLaplacian::compGrad as used by NavierStokesBase::computeGradP (Source/NavierStokesBase.cpp:4102-4122) */
 int iamrx_nodal_compgrad(const iamrx_geom* g, iamrx_mf gp, iamrx_mf phi);
 /* Projection::doMLMGNodalProjection, one level (Source/Projection.cpp:2385-2567; declaration Source/Projection.H:244-254):

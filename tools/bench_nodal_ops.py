@@ -1,5 +1,6 @@
-"""nodal residual and interpolation at n^3 nodes + 1 (periodic box, variable sigma) through the C-ABI; run under rocprofv3 --kernel-trace --stats for
-the per-kernel times.  NODAL_RES_TILE / NODAL_INTERP_TILE variants are looped over.  python tools/bench_nodal_ops.py [n]"""
+"""nodal residual, interpolation, restriction and divergence at n^3 cells (periodic box, variable sigma) through the C-ABI; run under
+rocprofv3 --kernel-trace --stats for the per-kernel times.  The forms behind NODAL_RES_TILE, NODAL_INTERP_LDS (0: per coarse node, 1: LDS
+tile), NODAL_RESTRICT_TILE and NODAL_DIVU_ZM are looped over, ten calls each.  python tools/bench_nodal_ops.py [n]"""
 import sys, os
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,11 +28,31 @@ for tile in (0, 1, 2, 3):
     if ref is None: ref = got
     print("residual tile", tile, "identical to tile 0:", bool(np.array_equal(got, ref)), flush=True)
 f0 = None
-for tile in (0, 1):
-    lib.tuning_set("NODAL_INTERP_TILE", tile)
+for form in (0, 1):
+    lib.tuning_set("NODAL_INTERP_LDS", form)
     f = lib.MultiFab(lay, lib.NODE, 1, 1); f.setval(0.0)
     for _ in range(10): N.nodal_interp_add(f, c, sig)
     lib.sync()
     got = f.gather_valid(tuple(v + 1 for v in n))
     if f0 is None: f0 = got
-    print("interp tile", tile, "identical:", bool(np.array_equal(got, f0)), flush=True)
+    print("interp form", form, "identical to form 0:", bool(np.array_equal(got, f0)), flush=True)
+lib.tuning_set("NODAL_INTERP_LDS", 1)
+c0 = None
+lib.tuning_set("NODAL_RESTRICT_MIN", 16)
+for form in (0, 1):
+    lib.tuning_set("NODAL_RESTRICT_TILE", form)
+    for _ in range(10): N.nodal_restrict(c, x)
+    lib.sync()
+    got = c.gather_valid(tuple(v + 1 for v in nc))
+    if c0 is None: c0 = got
+    print("restrict form", form, "identical to form 0:", bool(np.array_equal(got, c0)), flush=True)
+vel = lib.MultiFab(lay, lib.CELL, 3, 1)
+vel.set_from_global(rng.standard_normal(tuple(v + 2 for v in n) + (3,)), (-1, -1, -1))
+d0 = None
+for form in (0, 1):
+    lib.tuning_set("NODAL_DIVU_ZM", form)
+    for _ in range(10): N.nodal_divu(g, r, vel, 0)
+    lib.sync()
+    got = r.gather_valid(tuple(v + 1 for v in n))
+    if d0 is None: d0 = got
+    print("divu form", form, "identical to form 0:", bool(np.array_equal(got, d0)), flush=True)
