@@ -555,6 +555,17 @@ def godunov_compute_aofs(geom, aofs, acomp, S, ncomp, force, divu, umac, iconser
                                            _h(e[0]), _h(e[1]), _h(e[2]), _h(f[0]), _h(f[1]), _h(f[2]), int(scheme)))
 
 
+def godunov_compute_aofs_sync(geom, sync, acomp, S, ncomp, force, divu, umac, ucorr, iconserv, dt, bc=None, is_velocity=0,
+                              use_forces_in_trans=0, flux=None, scheme=0):
+    """NavierStokesBase::ComputeAofs with is_sync = true (reference Source/MacProj.cpp:700-731): edge states traced with umac, fluxes
+    formed with ucorr, sync(acomp..) -= -div(F)/vol; flux: all three face arrays or None"""
+    ic = (C.c_int * ncomp)(*[int(x) for x in iconserv])
+    f = [None] * 3 if flux is None else flux
+    check(lib().iamrx_godunov_compute_aofs_sync(C.byref(geom), sync.h, acomp, S.h, ncomp, _h(force), _h(divu), umac[0].h, umac[1].h,
+                                                umac[2].h, ucorr[0].h, ucorr[1].h, ucorr[2].h, ic, C.c_double(dt), _bcrec(ncomp, bc),
+                                                is_velocity, use_forces_in_trans, _h(f[0]), _h(f[1]), _h(f[2]), int(scheme)))
+
+
 # ---- Diffusion operator entries on caller-owned data (include/iamrx.h; reference Source/Diffusion.H:53-225) ----------------------------
 class DiffusionCrse(C.Structure):
     _fields_ = [("crse_old", C.c_void_p), ("crse_new", C.c_void_p), ("cgeom", C.c_void_p), ("ratio", C.c_int)]
