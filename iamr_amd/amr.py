@@ -36,6 +36,12 @@ class Amr:
         check(lib().iamrx_amr_create(C.byref(geom0), len(self.layouts), arr, int(ratio), C.byref(self.params), C.byref(self.opts), C.byref(self.h)))
         self.levels = []
         self._refresh(keep_layouts=True)
+        if getattr(self.params, "turb_forcing", 0):
+            self.set_turb_forcing(self.params.turb_nmodes, self.params.turb_mode_start, self.params.turb_div_free)
+
+    def set_turb_forcing(self, nmodes=4, mode_start=0, div_free=1, on=1):
+        """switch the turbulent forcing on for every level, with upstream's mode table for the level-0 domain (iamrx_amr_set_turb_forcing)"""
+        check(lib().iamrx_amr_set_turb_forcing(self.h, int(on), int(nmodes), int(mode_start), int(div_free)))
 
     def _refresh(self, keep_layouts=False):
         """(re)build the Python views of the levels; after a regrid the layouts are re-created from the hierarchy's box lists"""
@@ -60,6 +66,12 @@ class Amr:
             hl = C.c_void_p()
             check(lib().iamrx_amr_level(self.h, l, C.byref(hl)))
             self.levels.append(_Level(hl, self.level_geom(l), self.layouts[l], self.params, self.opts))
+
+    def set_turb_modes(self, kxyz, data, div_free=1):
+        """switch the turbulent forcing on for every level with the caller's table (NavierStokes.set_turb_modes for the hierarchy)"""
+        from .lib import _turb_table
+        M, k, d = _turb_table(kxyz, data)
+        check(lib().iamrx_amr_set_turb_modes(self.h, M, k, d, int(div_free)))
 
     def set_regrid(self, max_level, regrid_int, rules, blocking_factor=8, max_grid_size=32, grid_eff=0.7, n_error_buf=1, compute_new_dt_on_regrid=0,
                    do_refine_outflow=0, do_derefine_outflow=1, nbuf_outflow=1):

@@ -75,6 +75,10 @@ public:
     void set_restart_state(const double* dt_lev, const double* dt_mn, const int* ncyc, const int counters[2], double stop);
     void get_level_counts(int* counts, int n) const;
     void set_level_counts(const int* counts, int n);
+    // turbulent forcing: the mode table is built once from the level-0 domain (set_turb_forcing: upstream's table) or handed in
+    // (set_turb_modes: a caller's; null: off) and shared by every level, also by the levels a regrid creates
+    void set_turb_modes(TurbTableP t) { turb = t; for (auto& s : lev) s->set_turb_modes(t); }
+    void set_turb_forcing(int nmodes, int mode_start, int div_free) { set_turb_modes(turb_make_table(lev[0]->geom(), nmodes, mode_start, div_free)); }
     uint64_t grid_generation() const { return m_grid_gen; }   // incremented whenever the grids change
     uint64_t m_grid_gen = 0;
     // section profile of the coarse step (host clock around stream syncs, only while profile_on): [0] reflux, [1] avgDown,
@@ -93,6 +97,7 @@ private:
     int level_steps = 0;
     double stop_time = -1.0;
     RegridOpts rg;
+    TurbTableP turb;
     int m_ratio = 2;
     void link_level(int l);
     void check_nesting(const std::vector<BoxD>& fine, const std::vector<BoxD>& crse, const Geometry& cgeom, int l) const;

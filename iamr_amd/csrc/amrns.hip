@@ -202,7 +202,7 @@ void godunov_compute_aofs_sync(const Geometry& g, MultiFab& sync, int acomp, con
 void mac_sync_compute(const Geometry& g, MultiFab* const ucorr[3], MultiFab& Vsync, MultiFab& Ssync, const MultiFab& Svel, const MultiFab& Sscal, int nscal,
                       const MultiFab* visc_vel, const MultiFab* tf_scal, const MultiFab& gradp, const MultiFab* divu, MultiFab* const umac[3],
                       const int* iconserv_scal, bool do_mom_diff, double gravity, double dt, const BCRec* bc_vel, const BCRec* bc_scal,
-                      bool use_forces_in_trans, int scheme, MultiFab* const flux_vel[3], MultiFab* const flux_scal[3])
+                      bool use_forces_in_trans, int scheme, MultiFab* const flux_vel[3], MultiFab* const flux_scal[3], const MultiFab* turb_f)
 {
     auto& ctx = Context::get();
     const LayoutP& layout = Svel.layout;
@@ -212,10 +212,13 @@ void mac_sync_compute(const Geometry& g, MultiFab* const ucorr[3], MultiFab& Vsy
         const FabD *tt = tfv.d_tab, *gt = gradp.d_tab, *st = Sscal.d_tab, *vt = visc_vel ? visc_vel->d_tab : nullptr;
         const bool mom = do_mom_diff;
         const double grav = gravity;
+        const FabD* ft = turb_f ? turb_f->d_tab : nullptr;          // the turbulent forcing's acceleration at prev_time (1 ghost cell), getForce of MacProj.cpp:587
         for_each(*layout, cell_type(), 1, ctx.stream, [=] __device__(int i, int j, int k, int fb) {
             const double rho = st[fb](i, j, k, 0);
             for (int n = 0; n < 3; ++n) {
-                double t = ((fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0) + (vt ? (double)vt[fb](i, j, k, n) : 0.0) - gt[fb](i, j, k, n);
+                double t = ((fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0);
+                if (ft) t += rho * ft[fb](i, j, k, n);
+                t = t + (vt ? (double)vt[fb](i, j, k, n) : 0.0) - gt[fb](i, j, k, n);
                 if (!mom) t /= rho;
                 tt[fb](i, j, k, n) = t;
             }
@@ -864,9 +867,10 @@ AmrNS::AmrNS(const Geometry& g0, const std::vector<LayoutP>& layouts, int ratio,
         if (l > 0) {
             for (int d = 0; d < 3; ++d) { g.domain.lo[d] *= ratio; g.domain.hi[d] = (g.domain.hi[d] + 1) * ratio - 1; g.dx[d] /= (double)ratio; }
         }
-        lev.push_back(std::make_unique<NavierStokes>(g, layouts[l], p, o));
+        lev.push_back(std::make_unique<NavierStokes>(g, layouts[l], p, o, turb));
         NavierStokes& s = *lev.back();
         s.level = (int)l; s.ratio = l > 0 ? ratio : 1;
+        s.amr_times = true;
         n_cycle.push_back(l > 0 ? ratio : 1);
         dt_level.push_back(0.0); dt_min.push_back(1.e200);
         if (l > 0) {
@@ -1031,7 +1035,7 @@ void AmrNS::mac_sync(int l)
         MultiFab *flvp[3], *flsp[3];
         for (int d = 0; d < 3; ++d) { flv[d].define(c.layout, face_type(d), 3, 0); fls[d].define(c.layout, face_type(d), c.nscal, 0); flvp[d] = &flv[d]; flsp[d] = &fls[d]; }
         mac_sync_compute(c.g, uc, c.Vsync, c.Ssync, Smf, Sc, c.nscal, &vvisc, &tfs, c.Gp[1 - c.pnew], &divu, um, c.scal_cons, mom, c.p.gravity, dt, c.bc_vel,
-                         c.bc_scal, c.p.use_forces_in_trans != 0, c.p.use_ppm, flvp, flsp);
+                         c.bc_scal, c.p.use_forces_in_trans != 0, c.p.use_ppm, flvp, flsp, c.turb_force_at(c.prev_time()));
         for (int d = 0; d < 3; ++d) {            // NavierStokesBase.cpp:5083-5096 with sync_factor = -1
             f.reg_adv->CrseInit(flv[d], d, 0, 0, 3, dt, true);
             f.reg_adv->CrseInit(fls[d], d, 0, Density, c.nscal, dt, true);

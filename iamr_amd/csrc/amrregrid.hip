@@ -283,9 +283,10 @@ bool AmrNS::install_grids(const std::vector<std::vector<BoxD>>& grids, int lbase
         std::unique_ptr<ProfScope> pri;
         PROF_NEXT(pri, "ri_level_object");
         LayoutP nl = std::make_shared<Layout>(grids[l - lbase - 1], distribute_boxes(grids[l - lbase - 1], ctx.comm->nranks), ctx.comm->rank);
-        lev.push_back(std::make_unique<NavierStokes>(g, nl, p, o));
+        lev.push_back(std::make_unique<NavierStokes>(g, nl, p, o, turb));
         NavierStokes& s = *lev.back();
         s.level = l; s.ratio = m_ratio;
+        s.amr_times = true;
         NavierStokes* ol = (l <= old_finest) ? old[l - lbase - 1].get() : nullptr;
         link_level(l);
         // ---- times (init(old): setTimeLevel(cur_time, dt_old, dt_new); init(): dt = dt_crse / ratio, dt_old = (coarse dt_old) / ratio)

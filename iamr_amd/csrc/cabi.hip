@@ -835,6 +835,33 @@ int iamrx_calc_mut_les_cf(const iamrx_geom* g, iamrx_mf vel, const int* lobc, co
     IAMRX_CATCH
 }
 
+// ---- turbulent forcing (k_turb.hip) ----------------------------------------------------------------------------------------------------
+// host-only (no device needed): the mode table of TurbulentForcing::init_turbulent_forcing for a domain
+int iamrx_host_turb_modes(const double prob_lo[3], const double prob_hi[3], int nmodes, int mode_start, int div_free, int cap, int* M, int* kxyz, double* data)
+{
+    IAMRX_TRY
+    std::vector<int> k;
+    std::vector<double> d;
+    turb_host_modes(prob_lo, prob_hi, nmodes, mode_start, div_free, k, d);
+    const int n = (int)(k.size() / 3);
+    if (M) *M = n;
+    if (kxyz && data) {
+        if (n > cap) throw Error("iamrx_host_turb_modes: the table has " + std::to_string(n) + " modes, the caller's arrays hold " + std::to_string(cap));
+        std::copy(k.begin(), k.end(), kxyz);
+        std::copy(d.begin(), d.end(), data);
+    }
+    IAMRX_CATCH
+}
+
+int iamrx_turb_force(const iamrx_geom* g, int M, const int* kxyz, const double* data, int div_free, double time, iamrx_mf out, int ocomp)
+{
+    IAMRX_TRY
+    if (ocomp < 0 || ocomp + 3 > out->mf.ncomp || !out->mf.type.cell()) throw Error("iamrx_turb_force: out must be cell-centred with components ocomp .. ocomp + 2");
+    TurbTableP t = turb_make_table(M, kxyz, data, div_free);
+    turb_force(to_geom(g), *t, time, out->mf, ocomp);       // (the table's device copy goes back to the stream-ordered cache with t)
+    IAMRX_CATCH
+}
+
 // ---- Diffusion operator entries on caller-owned data (diffusion.hip) -----------------------------------------------------------------
 namespace {
 struct CrseArgs { DiffusionCrse dc; Geometry cg; bool on = false; };
@@ -1002,6 +1029,18 @@ int iamrx_ns_create(const iamrx_geom* g, iamrx_layout l, const iamrx_ns_params* 
     IAMRX_CATCH
 }
 int iamrx_ns_destroy(iamrx_ns ns) { IAMRX_TRY delete ns; IAMRX_CATCH }
+int iamrx_ns_set_turb_modes(iamrx_ns ns, int M, const int* kxyz, const double* data, int div_free)
+{
+    IAMRX_TRY
+    ns->ns->set_turb_modes(turb_make_table(M, kxyz, data, div_free));
+    IAMRX_CATCH
+}
+int iamrx_ns_set_turb_forcing(iamrx_ns ns, int on, int nmodes, int mode_start, int div_free)
+{
+    IAMRX_TRY
+    if (on) ns->ns->set_turb_forcing(nmodes, mode_start, div_free); else ns->ns->set_turb_modes(nullptr);
+    IAMRX_CATCH
+}
 int iamrx_ns_init_rayleightaylor(iamrx_ns ns, double rho_1, double rho_2, double tra_1, double tra_2, double pertamp, double interface_width)
 {
     IAMRX_TRY ns->ns->init_rayleightaylor(rho_1, rho_2, tra_1, tra_2, pertamp, interface_width); IAMRX_CATCH
@@ -1392,6 +1431,16 @@ int iamrx_amr_create(const iamrx_geom* g0, int nlev, const iamrx_layout* layouts
     IAMRX_CATCH
 }
 int iamrx_amr_destroy(iamrx_amr a) { IAMRX_TRY delete a; IAMRX_CATCH }
+int iamrx_amr_set_turb_modes(iamrx_amr a, int M, const int* kxyz, const double* data, int div_free)
+{
+    IAMRX_TRY a->amr->set_turb_modes(turb_make_table(M, kxyz, data, div_free)); IAMRX_CATCH
+}
+int iamrx_amr_set_turb_forcing(iamrx_amr a, int on, int nmodes, int mode_start, int div_free)
+{
+    IAMRX_TRY
+    if (on) a->amr->set_turb_forcing(nmodes, mode_start, div_free); else a->amr->set_turb_modes(nullptr);
+    IAMRX_CATCH
+}
 static void amr_refresh_levels(iamrx_amr a)
 {
     // the level handles given out so far stay valid objects (retired: every iamrx_ns_* entry returns an error on them) but the

@@ -249,4 +249,23 @@ void fill_tensor_corners(const Geometry& g, MultiFab& phi, const DomainBC& bc, b
 // NavierStokesBase::calc_mut_LES (Source/NS_LES.cpp:105-222) on the gradients of MLTensorOp::compVelGrad (:97)
 void les_mut(const Geometry& g, const MultiFab& vel, int vcomp, int model, double Cs, double base, MultiFab* const mu[3]);
 
+// ---- k_turb.hip ---------------------------------------------------------------------------
+// Turbulent forcing (Tutorials/HIT): the table of M Fourier modes -- integer wavevector and the 17 values FTX, TAT, FPX, FPY, FPZ, FAX, FAY,
+// FAZ, FPXX, FPXY, FPXZ, FPYX, FPYY, FPYZ, FPZX, FPZY, FPZZ per mode -- shared by the levels of a hierarchy
+struct TurbTable {
+    int M = 0, div_free = 1;
+    std::vector<int> kxyz;                      // [3 m + d]
+    std::vector<double> data;                   // [17 m + q]
+    mutable int* d_kxyz = nullptr;              // device copy, made by the first evaluation
+    mutable double* d_data = nullptr;
+    ~TurbTable();
+};
+using TurbTableP = std::shared_ptr<const TurbTable>;
+// host only: TurbulentForcing::init_turbulent_forcing (Tutorials/HIT/TurbulentForcing_def.H:21-366) as the list of the modes its loops write
+void turb_host_modes(const double problo[3], const double probhi[3], int nmodes, int mode_start, int div_free, std::vector<int>& kxyz, std::vector<double>& data);
+TurbTableP turb_make_table(const Geometry& g, int nmodes, int mode_start, int div_free);
+TurbTableP turb_make_table(int M, const int* kxyz, const double* data, int div_free);      // a caller's table
+// out(ocomp .. ocomp + 2) = the acceleration f(x, time) of NS_getForce.cpp:553-686 on the cells and every ghost cell of out
+void turb_force(const Geometry& g, const TurbTable& tt, double time, MultiFab& out, int ocomp);
+
 }  // namespace iamrx

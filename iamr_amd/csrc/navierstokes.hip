@@ -57,9 +57,10 @@ static LayoutP level_work_layout(const Geometry& geom, const LayoutP& lay)
     return (lay && lay->total_cells() == geom.domain.npts()) ? coalesce_layout(lay) : lay;
 }
 
-NavierStokes::NavierStokes(const Geometry& geom, LayoutP lay, const NSParams& par, const MGOpts& opts)
+NavierStokes::NavierStokes(const Geometry& geom, LayoutP lay, const NSParams& par, const MGOpts& opts, TurbTableP turb_)
     : user_layout(lay), g(geom), layout(level_work_layout(geom, lay)), p(par), o(opts)
 {
+    turb = std::move(turb_);
     nstate = Tracer + 1;
     if (p.do_trac2) Tracer2 = nstate++;
     if (p.do_temp) Temp = nstate++;
@@ -213,6 +214,19 @@ void NavierStokes::init_rayleightaylor(double rho_1, double rho_2, double tra_1,
     });
     for (int q = 0; q < 2; ++q) { P[q].setVal(0.0); Gp[q].setVal(0.0); }
     time = 0.0; nstep = 0;
+}
+
+// the turbulent forcing's acceleration at time t (null: no forcing); see operators.h
+const MultiFab* NavierStokes::turb_force_at(double t)
+{
+    if (!turb) return nullptr;
+    for (int q = 0; q < 2; ++q)
+        if (m_turb_have[q] && m_turb_t[q] == t && m_turb_f[q].layout.get() == layout.get()) { m_turb_last = q; return &m_turb_f[q]; }
+    const int q = 1 - m_turb_last;
+    if (!m_turb_f[q].defined() || m_turb_f[q].layout.get() != layout.get()) m_turb_f[q].define(layout, cell_type(), 3, 1);
+    turb_force(g, *turb, t, m_turb_f[q], 0);
+    m_turb_t[q] = t; m_turb_have[q] = true; m_turb_last = q;
+    return &m_turb_f[q];
 }
 
 // NavierStokesBase::setTimeLevel (NavierStokesBase.cpp:2978-2996) with amrex::StateData::setTimeLevel semantics
@@ -587,12 +601,15 @@ double NavierStokes::estTimeStep()
     {
         const FabD *st = Sn.d_tab, *gt = G.d_tab;
         const double grav = p.gravity;
+        const MultiFab* tfm = turb_force_at(cur_time());                 // getForce(cur_time), NavierStokesBase.cpp:1410
+        const FabD* ft = tfm ? tfm->d_tab : nullptr;
         double mx[6];
         reduce_max_f<6>(*layout, cell_type(), 0, [=] __device__(int i, int j, int k, int f, double (&m)[6]) {
             const double rho = st[f](i, j, k, Density);
             const double rho_inv = 1.0 / rho;
             for (int n = 0; n < 3; ++n) {
                 double fr = (fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0;
+                if (ft) fr += rho * ft[f](i, j, k, n);
                 fr -= gt[f](i, j, k, n);
                 fr *= rho_inv;
                 const double u = fabs(st[f](i, j, k, Xvel + n)), a = fabs(fr);
@@ -682,10 +699,13 @@ double NavierStokes::predict_velocity(double dt_)
     {
         const FabD *tt = tf.d_tab, *vt = visc.d_tab, *gt = Gp[1 - pnew].d_tab, *st = rho_ptime.d_tab;
         const double grav = p.gravity;
+        const MultiFab* tfm = turb_force_at(prev_time());                // getForce(prev_time) on one ghost layer, NavierStokesBase.cpp:4456
+        const FabD* ft = tfm ? tfm->d_tab : nullptr;
         for_each(*layout, cell_type(), 1, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
             const double rho = st[f](i, j, k, 0);
             for (int n = 0; n < 3; ++n) {
-                const double fr = (fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0;
+                double fr = (fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0;
+                if (ft) fr += rho * ft[f](i, j, k, n);
                 tt[f](i, j, k, n) = (fr + vt[f](i, j, k, n) - gt[f](i, j, k, n)) / rho;
             }
         });
@@ -823,10 +843,13 @@ void NavierStokes::velocity_advection(double dt_)
     {
         const FabD *tt = tf.d_tab, *vt = visc.d_tab, *gt = Gp[1 - pnew].d_tab, *st = Smf.d_tab;
         const double grav = p.gravity;
+        const MultiFab* tfm = turb_force_at(prev_time());                // getForce(prev_time), NavierStokesBase.cpp:3448
+        const FabD* ft = tfm ? tfm->d_tab : nullptr;
         for_each(*layout, cell_type(), 1, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
             const double rho = st[f](i, j, k, 0);
             for (int n = 0; n < 3; ++n) {
-                const double fr = (fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0;
+                double fr = (fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0;
+                if (ft) fr += rho * ft[f](i, j, k, n);
                 double t = fr + vt[f](i, j, k, n) - gt[f](i, j, k, n);
                 if (!mom) t /= rho;                     // NavierStokesBase.cpp:3459-3466: convective form only
                 tt[f](i, j, k, n) = t;
@@ -927,10 +950,13 @@ void NavierStokes::advection_all(double dt_)
         // the density of the forcing (velocity_advection's one-ghost-cell FillPatch of the old density) = rho_ptime (make_rho_prev_time)
         const FabD *tt = tf.d_tab, *vt = visc.d_tab, *wt = svisc.d_tab, *gt = Gp[1 - pnew].d_tab, *rt = rho_ptime.d_tab, *qt = Q.d_tab;
         const double grav = p.gravity;
+        const MultiFab* tfm = turb_force_at(prev_time());                // getForce(prev_time), NavierStokesBase.cpp:3448
+        const FabD* ft = tfm ? tfm->d_tab : nullptr;
         for_each(*layout, cell_type(), 1, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
             const double rho = rt[f](i, j, k, 0);
             for (int n = 0; n < 3; ++n) {
-                const double fr = (fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0;
+                double fr = (fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0;
+                if (ft) fr += rho * ft[f](i, j, k, n);
                 double t = fr + vt[f](i, j, k, n) - gt[f](i, j, k, n);
                 if (!mom) t /= rho;
                 tt[f](i, j, k, n) = t;
@@ -1065,12 +1091,16 @@ void NavierStokes::velocity_advection_update(double dt_)
     const double grav = p.gravity;
     const bool zero_force = initial_iter && is_diffusive_vel();
     const bool mom = p.do_mom_diff != 0;
+    // getForce(half_time) with the half-time density, NavierStokesBase.cpp:3580-3583; half_time = (prevTime + curTime) / 2
+    const MultiFab* tfm = turb_force_at(0.5 * (prev_time() + (amr_times ? st_new : time + dt_)));
+    const FabD* ft = tfm ? tfm->d_tab : nullptr;
     for_each(*layout, cell_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
         const double ro = ot[f](i, j, k, Density), rn = nt[f](i, j, k, Density);
         const double scal_rho = 0.5 * (ro + rn);
         const double rh = rt[f](i, j, k, 0);
         for (int n = 0; n < 3; ++n) {
             double force = (fabs(grav) > 0.0001 && n == 2) ? grav * scal_rho : 0.0;
+            if (ft) force += scal_rho * ft[f](i, j, k, n);
             if (zero_force) force = 0.0;
             double velold = ot[f](i, j, k, n);
             if (mom) {                                  // NavierStokesBase.cpp:3609-3616
@@ -1093,9 +1123,12 @@ void NavierStokes::initial_velocity_diffusion_update(double dt_)
     const FabD *nt = S[inew].d_tab, *ot = So.d_tab, *at = aofs.d_tab, *gt = Gp[1 - pnew].d_tab, *rt = rho_half.d_tab, *vt = visc.d_tab;
     const double grav = p.gravity;
     const bool mom = p.do_mom_diff != 0;
+    const MultiFab* tfm = turb_force_at(prev_time());                    // getForce(prev_time), NavierStokesBase.cpp:3696
+    const FabD* ft = tfm ? tfm->d_tab : nullptr;
     for_each(*layout, cell_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
         for (int n = 0; n < 3; ++n) {
             double force = (fabs(grav) > 0.0001 && n == 2) ? grav * ot[f](i, j, k, Density) : 0.0;
+            if (ft) force += ot[f](i, j, k, Density) * ft[f](i, j, k, n);
             force += vt[f](i, j, k, n) - gt[f](i, j, k, n);
             if (!mom) force /= rt[f](i, j, k, 0);
             force -= at[f](i, j, k, n);

@@ -171,7 +171,7 @@ void godunov_compute_aofs_sync(const Geometry& g, MultiFab& sync, int acomp, con
 void mac_sync_compute(const Geometry& g, MultiFab* const ucorr[3], MultiFab& Vsync, MultiFab& Ssync, const MultiFab& Svel, const MultiFab& Sscal, int nscal,
                       const MultiFab* visc_vel, const MultiFab* tf_scal, const MultiFab& gradp, const MultiFab* divu, MultiFab* const umac[3],
                       const int* iconserv_scal, bool do_mom_diff, double gravity, double dt, const BCRec* bc_vel, const BCRec* bc_scal,
-                      bool use_forces_in_trans, int scheme, MultiFab* const flux_vel[3], MultiFab* const flux_scal[3]);
+                      bool use_forces_in_trans, int scheme, MultiFab* const flux_vel[3], MultiFab* const flux_scal[3], const MultiFab* turb_f = nullptr);
 void mac_sync_compute_edge(const Geometry& g, MultiFab* const ucorr[3], MultiFab& Sync, int sync_indx, MultiFab* const edgestate[3], int edge_comp,
                            MultiFab* const flux_out[3]);
 
@@ -273,7 +273,8 @@ class NavierStokes {
 public:
     // the boxes as the caller (or the grid generator) gave them; `layout` below is coalesce_layout(user_layout): what the level works on
     LayoutP user_layout;
-    NavierStokes(const Geometry& g, LayoutP layout, const NSParams& p, const MGOpts& o);
+    // turb: the mode table of the turbulent forcing a hierarchy hands to the levels a regrid creates (null: no forcing until set_turb_modes)
+    NavierStokes(const Geometry& g, LayoutP layout, const NSParams& p, const MGOpts& o, TurbTableP turb = nullptr);
     ~NavierStokes();
     void init_taylorgreen(double vfac, double a, double b, double c, double rho0);   // Source/prob/prob_init.cpp:509-560
     // probtype 10 (Source/prob/prob_init.cpp:407-488, 3-D branch): fluid at rest, tanh density / tracer interface at mid height,
@@ -335,6 +336,19 @@ public:
     MultiFab& mac_phi_history(int which);                  // 0: last MAC potential, 1: the one before (defined on demand)
     // ns.do_LES: the face viscosities of the last velocity_diffusion_update, which 0 eta_n / 1 eta_np1, direction d
     const MultiFab& les_viscosity(int which, int d) const;
+    // ---- turbulent forcing (k_turb.hip; getForce of Tutorials/HIT/NS_getForce.cpp:205-707).  The acceleration f(x, t) of the mode table
+    // on the cells and one ghost layer, evaluated once per time value and kept (two arrays: the f(t^n+1) estTimeStep asks for is the
+    // f(t^n) of the next step); null without forcing.  Every site that forms gravity * rho adds rho * f.  The forcing is on exactly while the
+    // level holds a mode table: set_turb_forcing builds upstream's (TurbulentForcing::init_turbulent_forcing for the level's domain, from
+    // turb.nmodes / turb.mode_start / turb.div_free_force, TurbulentForcing_def.H:39-49), set_turb_modes takes a caller's (null: off)
+    void set_turb_forcing(int nmodes, int mode_start, int div_free) { set_turb_modes(turb_make_table(g, nmodes, mode_start, div_free)); }
+    const MultiFab* turb_force_at(double t);
+    void set_turb_modes(TurbTableP t) { turb = std::move(t); m_turb_have[0] = m_turb_have[1] = false; }
+    const TurbTableP& turb_modes() const { return turb; }
+    // the times getForce is called with: the level's own state times in a hierarchy (which keeps them), the level's clock otherwise
+    bool amr_times = false;
+    double prev_time() const { return amr_times ? st_old : time; }
+    double cur_time() const { return amr_times ? st_new : time; }
     const Geometry& geom() const { return g; }
     const LayoutP& lay() const { return layout; }
     const NSParams& params() const { return p; }
@@ -372,6 +386,11 @@ private:
     // one; validity as m_visc_old), and that of the new state as velocity_diffusion_update last saw it.  Not allocated without LES.
     MultiFab m_eta_n[3], m_eta_np1[3];
     bool m_eta_n_valid = false, m_eta_have = false;
+    TurbTableP turb;
+    MultiFab m_turb_f[2];
+    double m_turb_t[2] = {0.0, 0.0};
+    bool m_turb_have[2] = {false, false};
+    int m_turb_last = 0;                       // the array handed out last: the other one is overwritten by a new time
     MultiFab m_cf_mask;
     MultiFab m_mac_phi_prev, m_mac_phi_prev2;  // initial guess of the next MAC solve (last two potentials)
     bool m_have_mac_prev = false, m_have_mac_prev2 = false;

@@ -9,7 +9,9 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   ns.be_cn_theta, ns.do_mom_diff, ns.do_cons_trac, ns.vel_visc_coef, ns.scal_diff_coefs, ns.lo_bc, ns.hi_bc, ns.advection_scheme,
   ns.visc_tol, ns.avg_interval, ns.compute_fluctuations, ns.avg_in_checkpoint, ns.sum_interval, godunov.use_forces_in_trans, mac_proj.mac_tol / mac_abs_tol, proj.proj_tol / proj_abs_tol,
   {x,y,z}{lo,hi}.velocity / .density / .tracer, prob.probtype (1: fluid at rest, 4: constant velocity + blob, 5: DoubleShearLayer, 7: Euler, 10: RayleighTaylor, 11: TaylorGreen), prob.velocity_factor, prob.a/b/c,
-  prob.density_ic, prob.rho_1 / rho_2 / tra_1 / tra_2 / interface_width / perturbation_amplitude (probtype 10), max_step, stop_time
+  prob.density_ic, prob.rho_1 / rho_2 / tra_1 / tra_2 / interface_width / perturbation_amplitude (probtype 10), max_step, stop_time,
+  turb.nmodes (its presence switches the turbulent forcing of Tutorials/HIT on) / turb.div_free_force / turb.mode_start, prob.probtype 100 with
+  prob.turb_scale (Tutorials/HIT/TurbulentForcing_def.H:36-52, Tutorials/HIT/prob_init.cpp:58-134)
 (reference: Source/NavierStokesBase.cpp:431-557, Source/NavierStokes.cpp:250-310, Source/MacProj.cpp:62-75,
 Source/Projection.cpp:49-65, Source/Diffusion.cpp:98-118, Source/prob/prob_init.cpp:8-60, Source/main.cpp:60-145).
 Keys that select features this library does not have (AMR levels, EB, particles, inflow/outflow ...) raise; keys that only
@@ -349,7 +351,9 @@ class Inputs:
                  use_forces_in_trans=self.integer("godunov.use_forces_in_trans", 0), do_mom_diff=self.integer("ns.do_mom_diff", 0), do_cons_trac=self.integer("ns.do_cons_trac", 0), use_ppm={"Godunov_PLM": 0, "Godunov_PPM": 1, "BDS": 2}[scheme],
                  do_denminmax=self.integer("ns.do_denminmax", 0), do_scalminmax=self.integer("ns.do_scalminmax", 0),
                  mac_tol=self.real("mac_proj.mac_tol", 1.0e-12), mac_abs_tol=self.real("mac_proj.mac_abs_tol", 1.0e-16),
-                 proj_tol=self.real("proj.proj_tol", 1.0e-12), proj_abs_tol=self.real("proj.proj_abs_tol", 1.0e-16),
+                 # the nodal projection's tolerances under upstream's current prefix nodal_proj (Projection.cpp:49-54) or the older proj
+                 proj_tol=self.real("nodal_proj.proj_tol", self.real("proj.proj_tol", 1.0e-12)),
+                 proj_abs_tol=self.real("nodal_proj.proj_abs_tol", self.real("proj.proj_abs_tol", 1.0e-16)),
                  phys_lo=lo_bc, phys_hi=hi_bc)
         wlo, whi = [0.0] * 9, [0.0] * 9
         # NavierStokes.cpp:113-160: a no-slip wall takes the tangential components of its .velocity (the wall does not move along its
@@ -392,6 +396,21 @@ class Inputs:
         p["smago_Cs_cst"] = self.real("ns.smago_Cs_cst", 0.18)
         p["sigma_Cs_cst"] = self.real("ns.sigma_Cs_cst", 1.5)
         self.integer("ns.getLESVerbose", 0)                      # printing only
+        # Turbulent forcing (Tutorials/HIT).  Upstream switches it on at compile time (USE_TURBULENT_FORCING, NS_getForce.cpp:205, with a
+        # FIXME asking for a run-time switch) and then REQUIRES turb.nmodes (pp.get, TurbulentForcing_def.H:40): here the presence of
+        # turb.nmodes is the switch, so the tutorial's inputs file is enough.  turb.verbose prints only; turb.ff_factor belongs to the
+        # USE_FAST_FORCE interpolation (off in the tutorial's build, not built here); turb.force_file is never read upstream.
+        p["turb_forcing"] = 1 if self.has("turb.nmodes") else 0
+        p["turb_nmodes"] = self.integer("turb.nmodes", 4)
+        p["turb_div_free"] = self.integer("turb.div_free_force", 1)
+        p["turb_mode_start"] = self.integer("turb.mode_start", 0)
+        for k in ("turb.verbose", "turb.ff_factor", "turb.force_file"):
+            if self.has(k):
+                self.string(k)
+                self.ignored.append(k)
+        if slab and any(k.startswith("turb.") for k in self.table):
+            raise NotImplementedError("inputs: turbulent forcing (turb.*) in a two-dimensional run: the forcing is three-dimensional only "
+                                      "(TurbulentForcing_def.H:28)")
         if p["avg_interval"] < 0:
             raise ValueError(f"inputs: ns.avg_interval = {p['avg_interval']} must be >= 0")
         if slab and p["avg_interval"] > 0:
@@ -407,13 +426,18 @@ class Inputs:
             prob = dict(probtype=10, rho_1=self.real("prob.rho_1"), rho_2=self.real("prob.rho_2"), tra_1=self.real("prob.tra_1", 0.0),
                         tra_2=self.real("prob.tra_2", 0.0), pertamp=self.real("prob.perturbation_amplitude", 0.0),
                         interface_width=self.real("prob.interface_width", 1.0))
+        elif probtype == 100:                 # Tutorials/HIT/prob_init.cpp:58-134, host-side initial data (iamr_amd/probinit.py)
+            if slab:
+                raise NotImplementedError("inputs: prob.probtype = 100 (forced turbulence) in a two-dimensional run")
+            prob = dict(probtype=100, turb_scale=self.real("prob.turb_scale", 1.0), density_ic=self.real("prob.density_ic", 1.0),
+                        prob_lo=list(prob_lo), prob_hi=list(prob_hi))
         elif probtype in (2, 4, 5, 6, 7):     # host-side initial data (iamr_amd/probinit.py)
             prob = dict(probtype=probtype, density_ic=self.real("prob.density_ic", 1.0), direction=self.integer("prob.direction", 0),
                         interface_width=self.real("prob.interface_width", 1.0), blob_radius=self.real("prob.blob_radius", 0.1),
                         blob_center=self.reals("prob.blob_center", 3, [0.0, 0.0, 0.0]), velocity_ic=self.reals("prob.velocity_ic", 3, [0.0, 0.0, 0.0]))
         else:
             raise NotImplementedError(f"inputs: prob.probtype = {probtype}; implemented: 1 (fluid at rest, LidDrivenCavity), 2 / 6 (bubble / hot spot), 4 (constant "
-                                      "velocity + tracer blob), 5 (DoubleShearLayer), 7 (Euler), 10 (RayleighTaylor), 11 (TaylorGreen)")
+                                      "velocity + tracer blob), 5 (DoubleShearLayer), 7 (Euler), 10 (RayleighTaylor), 11 (TaylorGreen), 100 (forced turbulence)")
         if slab:
             prob["dim"] = 2
         out = dict(n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,

@@ -431,6 +431,39 @@ def host_abec_smoother_plan(geom, boxes, ncomp=1, coef=1, has_a=False, has_cf=Fa
     return d
 
 
+# the 17 values of a forcing mode, in the order of upstream's arrays (Tutorials/HIT/NS_getForce.cpp:249-281)
+TURB_FIELDS = ("FTX", "TAT", "FPX", "FPY", "FPZ", "FAX", "FAY", "FAZ", "FPXX", "FPXY", "FPXZ", "FPYX", "FPYY", "FPYZ", "FPZX", "FPZY", "FPZZ")
+
+
+def host_turb_modes(prob_lo, prob_hi, nmodes=4, mode_start=0, div_free=1):
+    """host-only: the mode table of the turbulent forcing for a domain (include/iamrx.h: iamrx_host_turb_modes) -> (kxyz (M, 3) int32,
+    data (M, 17) float64, columns TURB_FIELDS)"""
+    lo, hi = (C.c_double * 3)(*[float(v) for v in prob_lo]), (C.c_double * 3)(*[float(v) for v in prob_hi])
+    M = C.c_int()
+    check(lib().iamrx_host_turb_modes(lo, hi, int(nmodes), int(mode_start), int(div_free), 0, C.byref(M), None, None))
+    k = np.zeros((M.value, 3), dtype=np.int32)
+    d = np.zeros((M.value, 17))
+    check(lib().iamrx_host_turb_modes(lo, hi, int(nmodes), int(mode_start), int(div_free), M.value, C.byref(M), k.ctypes.data_as(C.POINTER(C.c_int)),
+                                      d.ctypes.data_as(C.POINTER(C.c_double))))
+    return k, d
+
+
+def _turb_table(kxyz, data):
+    k = np.ascontiguousarray(kxyz, dtype=np.int32).reshape(-1, 3)
+    d = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 17)
+    if len(k) != len(d):
+        raise ValueError("turbulent forcing table: kxyz (M, 3) and data (M, 17) must have the same number of modes")
+    _turb_table.keep = (k, d)              # the pointers below are read during the call only
+    return len(k), k.ctypes.data_as(C.POINTER(C.c_int)), d.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def turb_force(geom, kxyz, data, div_free, time, out, ocomp=0):
+    """k_turb_force alone: out(ocomp .. ocomp + 2) = the forcing's acceleration f(x, time) on the cells and every ghost cell of out
+    (include/iamrx.h: iamrx_turb_force)"""
+    M, k, d = _turb_table(kxyz, data)
+    check(lib().iamrx_turb_force(C.byref(geom), M, k, d, int(div_free), C.c_double(float(time)), out.h, int(ocomp)))
+
+
 def abec_form(geom, coef, op, phi, rhs, out=None, rho=None, rho_comp=0, scale=1.0, bu=(1.0, 1.0, 1.0), beta=1.0, omega=1.15, lobc=(0, 0, 0), hibc=(0, 0, 0),
               maxorder=3):
     """one operation of the multigrid's finest-level kernel forms (include/iamrx.h: iamrx_abec_form)"""

@@ -25,6 +25,10 @@ def ns_params(**kw):
     # ns.avg_in_checkpoint (NavierStokesBase.cpp:539) only steers amr.restart (checkpoint.restart): it travels with the parameters as a
     # plain attribute, the library's struct does not hold it
     p.avg_in_checkpoint = int(kw.pop("avg_in_checkpoint", 1))
+    # the turbulent forcing (Tutorials/HIT) is set on the level or the hierarchy after its creation (iamrx_ns_set_turb_forcing /
+    # iamrx_amr_set_turb_forcing; the library's struct keeps its layout): the four values travel the same way and NavierStokes / Amr apply them
+    p.turb_forcing, p.turb_nmodes = int(kw.pop("turb_forcing", 0)), int(kw.pop("turb_nmodes", 4))
+    p.turb_mode_start, p.turb_div_free = int(kw.pop("turb_mode_start", 0)), int(kw.pop("turb_div_free", 1))
     for k, v in kw.items():
         if k in ("phys_lo", "phys_hi"):
             setattr(p, k, (C.c_int * 3)(*[int(x) for x in v]))
@@ -174,6 +178,12 @@ class NavierStokes:
         self.opts = opts if opts is not None else mg_opts()
         self.h = C.c_void_p()
         check(lib().iamrx_ns_create(C.byref(geom), layout.h, C.byref(self.params), C.byref(self.opts), C.byref(self.h)))
+        if getattr(self.params, "turb_forcing", 0):
+            self.set_turb_forcing(self.params.turb_nmodes, self.params.turb_mode_start, self.params.turb_div_free)
+
+    def set_turb_forcing(self, nmodes=4, mode_start=0, div_free=1, on=1):
+        """switch the turbulent forcing on with upstream's mode table for the level's domain (include/iamrx.h: iamrx_ns_set_turb_forcing)"""
+        check(lib().iamrx_ns_set_turb_forcing(self.h, int(on), int(nmodes), int(mode_start), int(div_free)))
 
     def init_rayleightaylor(self, rho_1, rho_2, tra_1=0.0, tra_2=0.0, pertamp=0.0, interface_width=1.0):
         check(lib().iamrx_ns_init_rayleightaylor(self.h, C.c_double(rho_1), C.c_double(rho_2), C.c_double(tra_1), C.c_double(tra_2),
@@ -184,6 +194,13 @@ class NavierStokes:
 
     def init_rest(self, rho0=1.0):
         check(lib().iamrx_ns_init_rest(self.h, C.c_double(rho0)))
+
+    def set_turb_modes(self, kxyz, data, div_free=1):
+        """switch the turbulent forcing on with the caller's table of modes: kxyz (M, 3) integer wavevectors, data (M, 17) in
+        the order of lib.TURB_FIELDS (include/iamrx.h: iamrx_ns_set_turb_modes)"""
+        from .lib import _turb_table
+        M, k, d = _turb_table(kxyz, data)
+        check(lib().iamrx_ns_set_turb_modes(self.h, M, k, d, int(div_free)))
 
     def set_data(self, which, mf):
         check(lib().iamrx_ns_set_data(self.h, int(which), mf.h))

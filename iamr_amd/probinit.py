@@ -3,6 +3,8 @@ handed to the library once through iamrx_ns_set_data).  Restates Source/prob/pro
   probtype 4  constant velocity + tanh tracer blob        (init_constant_vel_rho, :232-281; the Poiseuille / channel regtests)
   probtype 5  DoubleShearLayer, uniform in z              (init_DoubleShearLayer, :346-405)
   probtype 7  Euler: vortex tube along x with a wobble    (init_Euler, :562-610)
+and Tutorials/HIT/prob_init.cpp for
+  probtype 100  cosine waves, the start of a forced-turbulence run (init_forced, :86-134)
 Cell centres x = prob_lo + (i + 1/2) dx as in the reference; components (u, v, w, rho, tracer)."""
 import numpy as np
 
@@ -66,6 +68,16 @@ def initial_state(prob, X, Y, Z, nstate=5):
         dist = np.sqrt((X - bc[0]) ** 2 + (Y - bc[1]) ** 2 + (Z - bc[2]) ** 2)
         S[..., 3] = prob["density_ic"]
         S[..., 4] = np.where(dist < prob["blob_radius"], 1.0, 0.0)
+    elif pt == 100:
+        lo, hi = prob["prob_lo"], prob["prob_hi"]
+        Lx, Ly = hi[0] - lo[0], hi[1] - lo[1]
+        Lz = hi[2] - lo[1]                   # as written upstream (Tutorials/HIT/prob_init.cpp:112): prob_lo[1], immaterial when prob_lo[1] = prob_lo[2]
+        TwoPi, s = 2.0 * np.pi, prob["turb_scale"]
+        S[..., 0] = s * np.cos(TwoPi * Y / Ly) * np.cos(TwoPi * Z / Lz)
+        S[..., 1] = s * np.cos(TwoPi * X / Lx) * np.cos(TwoPi * Z / Lz)
+        S[..., 2] = s * np.cos(TwoPi * X / Lx) * np.cos(TwoPi * Y / Ly)
+        S[..., 3] = prob["density_ic"]
+        S[..., 4] = 1.0                      # every tracer is 1 (:129-132), like the `extra` components
     elif pt == 7:
         eps, rho_in, beta, delta, kappa = 0.05, 0.15, 15.0, 0.0333, 500.0
         x, y, z = X - 0.5, Y - 0.5, Z - 0.5

@@ -15,7 +15,7 @@ def init_level(ns, lay, lib, N, pr, n):
     pb = pr["prob"]
     if pb["probtype"] == 1:
         ns.init_rest(pb["rho0"])
-    elif pb["probtype"] in (2, 4, 5, 6, 7):
+    elif pb["probtype"] in (2, 4, 5, 6, 7, 100):
         from .probinit import set_initial_state
         ns.init_rest(pb["density_ic"])
         set_initial_state(ns, lay, lib, N, pb, n, pr["prob_lo"], pr["prob_hi"])
@@ -247,7 +247,7 @@ def build(inp, lib, N, nranks=1, pr=None):
     pb = pr["prob"]
     if pb["probtype"] == 1:
         ns.init_rest(pb["rho0"])
-    elif pb["probtype"] in (2, 4, 5, 6, 7):
+    elif pb["probtype"] in (2, 4, 5, 6, 7, 100):
         from .probinit import set_initial_state
         ns.init_rest(pb["density_ic"])
         set_initial_state(ns, lay, lib, N, pb, pr["n"], pr["prob_lo"], pr["prob_hi"])

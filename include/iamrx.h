@@ -358,6 +358,20 @@ int iamrx_tensor_solve_cf(const iamrx_geom* g, iamrx_mf soln, iamrx_mf rhs, doub
  * = base + mu_t.  vel: cells, velocity in components vcomp .. vcomp + 2, >= 1 ghost layer whose face and edge cells are read AS THE CALLER
  * LEFT THEM.  model: 0 Smagorinsky (:122-136), 1 Sigma (:150-212); Cs: ns.smago_Cs_cst / ns.sigma_Cs_cst; filter width dx[d]. */
 int iamrx_les_mut(const iamrx_geom* g, iamrx_mf vel, int vcomp, int model, double Cs, double base, iamrx_mf mu_x, iamrx_mf mu_y, iamrx_mf mu_z);
+
+/* ---- turbulent forcing of forced homogeneous isotropic turbulence (Tutorials/HIT) ----
+ * HOST ONLY, no device needed: the mode table of TurbulentForcing::init_turbulent_forcing (Tutorials/HIT/TurbulentForcing_def.H:21-366; seed
+ * 111397, generator Tutorials/HIT/depRand.cpp: MT19937, draws in upstream's order, the zero mode's included) for the domain prob_lo .. prob_hi,
+ * as the compact list of the modes upstream's two loops write (:142-239 and the 1 <= kz < zstep set :244-341) instead of its 17 arrays of
+ * 33^3 entries: kxyz[3 m + d] the integer wavevector, data[17 m + q] the values FTX, TAT, FPX, FPY, FPZ, FAX, FAY, FAZ, FPXX, FPXY, FPXZ, FPYX,
+ * FPYY, FPYZ, FPZX, FPZY, FPZZ of mode m (the nine FPab are zero with div_free = 0, where upstream leaves them unwritten).  *M: the number
+ * of modes; kxyz / data may be NULL to ask for it, else they hold cap modes.  Refused: Lx != Ly (:34), Lz < Lx (only z may be the long
+ * direction), nmodes * zstep > 32 (array_size = 33, Tutorials/HIT/TurbulentForcing_params.H:19). */
+int iamrx_host_turb_modes(const double prob_lo[3], const double prob_hi[3], int nmodes, int mode_start, int div_free, int cap, int* M, int* kxyz, double* data);
+/* k_turb_force alone: out(ocomp .. ocomp + 2) = the acceleration f(x, time) of the forcing block of NavierStokesBase::getForce
+ * (Tutorials/HIT/NS_getForce.cpp:553-686: both forms :570-616 by div_free, every mode of the table -- upstream's two mode loops) on the cells
+ * and EVERY ghost cell of the cell-centred array out, at x = prob_lo + (i - dom_lo + 0.5) dx (upstream: from the box's corner, :544-546). */
+int iamrx_turb_force(const iamrx_geom* g, int M, const int* kxyz, const double* data, int div_free, double time, iamrx_mf out, int ocomp);
 /* NavierStokesBase::calc_mut_LES (Source/NS_LES.cpp:22-225) behind its FillPatch: vel (3 comps, 1 ghost layer) carries the level's boundary
  * data in its ghost cells (what FillPatch left there, :86-88), the tensor operator's boundary step fills them (tensorop.setDomainBC with the
  * per-component codes of LES_setDomainBC, :59-68, 230-285; setLevelBC, :88), then mu_d = mu_t.  lobc / hibc: 9 LinOpBC codes, [n*3+d].
@@ -492,6 +506,14 @@ typedef struct iamrx_ns_params {
 void iamrx_ns_default_params(iamrx_ns_params* p);     /* defaults of Source/NavierStokesBase.cpp:96-170 */
 int iamrx_ns_create(const iamrx_geom* g, iamrx_layout l, const iamrx_ns_params* p, const iamrx_mg_opts* o, iamrx_ns* out);
 int iamrx_ns_destroy(iamrx_ns ns);
+/* The turbulent forcing of Tutorials/HIT (upstream: the compile-time switch USE_TURBULENT_FORCING, Tutorials/HIT/NS_getForce.cpp:205) is a
+ * property set on the level after iamrx_ns_create and before iamrx_ns_post_init -- iamrx_ns_params keeps its layout.  on = 1: the level builds
+ * the mode table of TurbulentForcing::init_turbulent_forcing (Tutorials/HIT/TurbulentForcing_def.H:21-366) for its domain from turb.nmodes
+ * (upstream's default 4), turb.mode_start (0) and turb.div_free_force (1) (:39-49), and getForce adds rho f(x, t) from then on; on = 0: off,
+ * the state of a new level (nothing allocated, no launch added, every result what it is without the forcing). */
+int iamrx_ns_set_turb_forcing(iamrx_ns ns, int on, int nmodes, int mode_start, int div_free);
+/* the same with a caller's table (custom spectra); layout as iamrx_host_turb_modes.  Switches the forcing on. */
+int iamrx_ns_set_turb_modes(iamrx_ns ns, int M, const int* kxyz, const double* data, int div_free);
 int iamrx_ns_init_taylorgreen(iamrx_ns ns, double vfac, double a, double b, double c, double rho0);  /* Source/prob/prob_init.cpp:509-560 */
 /* prob.probtype = 10, RayleighTaylor (Source/prob/prob_init.cpp:407-488) */
 int iamrx_ns_init_rayleightaylor(iamrx_ns ns, double rho_1, double rho_2, double tra_1, double tra_2, double pertamp, double interface_width);
@@ -648,6 +670,10 @@ int iamrx_initial_sync_project(int nlev, const iamrx_proj_level* levels, const i
  * iamrx_ns_data / iamrx_ns_set_data / iamrx_ns_time / iamrx_ns_stats, do not destroy them. */
 int iamrx_amr_create(const iamrx_geom* g0, int nlev, const iamrx_layout* layouts, int ratio, const iamrx_ns_params* p, const iamrx_mg_opts* o, iamrx_amr* out);
 int iamrx_amr_destroy(iamrx_amr a);
+/* iamrx_ns_set_turb_forcing / iamrx_ns_set_turb_modes for a hierarchy: the table is built once from the level-0 domain and shared by every level
+ * (levels made by later regrids included) */
+int iamrx_amr_set_turb_forcing(iamrx_amr a, int on, int nmodes, int mode_start, int div_free);
+int iamrx_amr_set_turb_modes(iamrx_amr a, int M, const int* kxyz, const double* data, int div_free);
 /* ---- regridding: Amr::regrid from level 0 with IAMR's error estimation (amr.refinement_indicators, Source/NS_error.cpp:10-145) and
  * NavierStokesBase::init(AmrLevel&) / init() for the data of the new levels (Source/NavierStokesBase.cpp:1713-1806).
  * comp: state component 0..4 (velocity, density, tracer) or -1 = mag_vort; mode: 0 value_greater, 1 value_less, 2 vorticity_greater
