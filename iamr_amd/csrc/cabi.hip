@@ -651,6 +651,31 @@ int iamrx_nodal_residual(const iamrx_geom* g, iamrx_mf out, iamrx_mf phi, iamrx_
 {
     IAMRX_TRY nodal_residual(to_geom(g), out->mf, phi->mf, sig->mf, rhs ? &rhs->mf : nullptr); IAMRX_CATCH
 }
+// the image-reading kernel forms on a caller's level (NodalMG uses them on the levels whose smoothers read images)
+static NodalImages images_of(const Geometry& g, const MultiFab& mf, const int lobc[3], const int hibc[3], const char* who)
+{
+    NodalImages img;
+    img.on = nodal_wrap_or_reflect_ok(g, *mf.layout, to_bc(lobc, hibc, 2), 4, &img.refl);
+    if (!img.on) throw Error(std::string(who) + ": the level is not one box of at least 4 cells per direction spanning a domain that is periodic or ends on Neumann walls");
+    return img;
+}
+int iamrx_nodal_residual_images(const iamrx_geom* g, iamrx_mf out, iamrx_mf phi, iamrx_mf sig, iamrx_mf rhs, const int lobc[3], const int hibc[3],
+                                double* norm)
+{
+    IAMRX_TRY
+    const Geometry gg = to_geom(g);
+    const NodalImages img = images_of(gg, phi->mf, lobc, hibc, "iamrx_nodal_residual_images");
+    if (!nodal_residual(gg, out->mf, phi->mf, sig->mf, rhs ? &rhs->mf : nullptr, norm, img) && norm) *norm = out->mf.norm0(0, 1, 0);
+    IAMRX_CATCH
+}
+int iamrx_nodal_restrict_images(const iamrx_geom* g, iamrx_mf c, iamrx_mf f, const int lobc[3], const int hibc[3])
+{
+    IAMRX_TRY
+    const NodalImages img = images_of(to_geom(g), f->mf, lobc, hibc, "iamrx_nodal_restrict_images");
+    if (c->mf.layout->boxes.size() != 1 || c->mf.nlocal() != 1) throw Error("iamrx_nodal_restrict_images: the coarse level is not one box");
+    nodal_restrict(c->mf, f->mf, img);
+    IAMRX_CATCH
+}
 int iamrx_nodal_gs_color(const iamrx_geom* g, iamrx_mf phi, iamrx_mf rhs, iamrx_mf sig, int color)
 {
     IAMRX_TRY nodal_gs_color(to_geom(g), phi->mf, rhs->mf, sig->mf, color); IAMRX_CATCH

@@ -32,7 +32,8 @@ static NodeW make_w(const Geometry& g)
     return w;
 }
 
-// A x at node (i,j,k) and the diagonal coefficient s0.  s = sigma fab (cell centred, 1 ghost).
+// A x at node (i,j,k) and the diagonal coefficient s0.  s = sigma fab (cell centred, 1 ghost).  (node_Ax_at below is the same expression
+// with free x indices: a change here is made there too, term by term -- the two are compared to the bit.)
 __device__ __forceinline__ double node_Ax(const FabD& x, const FabD& s, const NodeW& w, int i, int j, int k, double& s0)
 {
     // sigma of the 8 cells around the node: s_{abc}, a,b,c in {m,p} for cell index node-1 / node
@@ -50,11 +51,58 @@ __device__ __forceinline__ double node_Ax(const FabD& x, const FabD& s, const No
     y += w.fz * (x(i, j, k - 1) * (smmm + spmm + smpm + sppm) + x(i, j, k + 1) * (smmp + spmp + smpp + sppp));
     return y;
 }
+// the same with x read at the given indices: the images of the node's neighbours inside a box that spans its domain (image_node below);
+// sigma at the cells around the node as above.  (node_Ax keeps its own body: with compile-time neighbour offsets the per-node
+// kernels take 72 registers, written through this form 98.  The two bodies are kept equal term by term.)
+__device__ __forceinline__ double node_Ax_at(const FabD& x, const FabD& s, const NodeW& w, int im, int i, int ip, int jm, int j, int jp, int km, int k, int kp,
+                                             double& s0)
+{
+    const double smmm = s(i - 1, j - 1, k - 1), spmm = s(i, j - 1, k - 1), smpm = s(i - 1, j, k - 1), sppm = s(i, j, k - 1);
+    const double smmp = s(i - 1, j - 1, k), spmp = s(i, j - 1, k), smpp = s(i - 1, j, k), sppp = s(i, j, k);
+    s0 = w.c * (smmm + spmm + smpm + sppm + smmp + spmp + smpp + sppp);
+    double y = x(i, j, k) * s0;
+    y += w.corner * (x(im, jm, km) * smmm + x(ip, jm, km) * spmm + x(im, jp, km) * smpm + x(ip, jp, km) * sppm
+                   + x(im, jm, kp) * smmp + x(ip, jm, kp) * spmp + x(im, jp, kp) * smpp + x(ip, jp, kp) * sppp);
+    y += w.ex * (x(i, jm, km) * (smmm + spmm) + x(i, jp, km) * (smpm + sppm) + x(i, jm, kp) * (smmp + spmp) + x(i, jp, kp) * (smpp + sppp));
+    y += w.ey * (x(im, j, km) * (smmm + smpm) + x(ip, j, km) * (spmm + sppm) + x(im, j, kp) * (smmp + smpp) + x(ip, j, kp) * (spmp + sppp));
+    y += w.ez * (x(im, jm, k) * (smmm + smmp) + x(ip, jm, k) * (spmm + spmp) + x(im, jp, k) * (smpm + smpp) + x(ip, jp, k) * (sppm + sppp));
+    y += w.fx * (x(im, j, k) * (smmm + smpm + smmp + smpp) + x(ip, j, k) * (spmm + sppm + spmp + sppp));
+    y += w.fy * (x(i, jm, k) * (smmm + spmm + smmp + spmp) + x(i, jp, k) * (smpm + sppm + smpp + sppp));
+    y += w.fz * (x(i, j, km) * (smmm + spmm + smpm + sppm) + x(i, j, kp) * (smmp + spmp + smpp + sppp));
+    return y;
+}
+
+// periodic image of a node / cell index inside the one box [lo, hi] (cells) that spans the periodic domain
+__device__ __forceinline__ int wrap_node(int g, int lo, int hi)
+{
+    // the staging halo is 4 nodes wide and the box has >= 4 cells (periodic_wrap_ok(g, l, 4)): one conditional shift is enough
+    const int n = hi - lo + 1;
+    return g < lo ? g + n : (g > hi + 1 ? g - n : g);
+}
+__device__ __forceinline__ int wrap_cell(int g, int lo, int hi)
+{
+    const int n = hi - lo + 1;
+    return g < lo ? g + n : (g > hi ? g - n : g);
+}
+// ... or, in a direction that ends on Neumann walls (refl): the mirror image -- what nodal_reflect_bc / cc_mirror_bc write into the ghost
+// nodes / cells (even reflection about the wall node lo resp. hi + 1; sigma mirrored about the wall face): the index-wrap variants then
+// read the valid data of a wall-bounded box directly as well, no ghost fill in front of a pass
+__device__ __forceinline__ int image_node(int g, int lo, int hi, bool refl)
+{
+    if (refl) return g < lo ? 2 * lo - g : (g > hi + 1 ? 2 * (hi + 1) - g : g);
+    return wrap_node(g, lo, hi);
+}
+__device__ __forceinline__ int image_cell(int g, int lo, int hi, bool refl)
+{
+    if (refl) return g < lo ? 2 * lo - 1 - g : (g > hi ? 2 * hi + 1 - g : g);
+    return wrap_cell(g, lo, hi);
+}
 
 // out = rhs - A x   (rhs null: out = A x).  z-marching: a workgroup owns a TXxTY column of nodes and walks KC planes; the
 // three x-planes and two sigma-planes it needs live in LDS (rolling), every plane is fetched from HBM once per column
 // (+ the 1-node halo ring), and the loads of plane k+2 are in flight while plane k is being evaluated.
-void nodal_residual_launch(const Geometry& g, MultiFab& out, const MultiFab& x, const MultiFab& sig, const MultiFab* rhs, unsigned long long* d_norm);
+void nodal_residual_launch(const Geometry& g, MultiFab& out, const MultiFab& x, const MultiFab& sig, const MultiFab* rhs, unsigned long long* d_norm,
+                           const NodalImages& img);
 // normout != null: the launch also reduces the max norm of what it writes (wave maximum, one atomicMax per wavefront on the bit pattern of
 // the non-negative value, NaN -> +inf: order independent, hence deterministic; k_abec.hip's norm_commit)
 __device__ __forceinline__ void nodal_norm_commit(double mx, unsigned long long* out)
@@ -68,7 +116,7 @@ __device__ __forceinline__ void nodal_norm_commit(double mx, unsigned long long*
 template <int TX, int TY>
 __global__ void __launch_bounds__(TX * TY) k_nodal_residual_zm(const BoxD* __restrict__ boxes, const FabD* __restrict__ ot, const FabD* __restrict__ xt,
     const FabD* __restrict__ st, const FabD* __restrict__ rt, NodeW w, int ntx, int nty, int kc, unsigned long long* __restrict__ normout,
-    const int4* __restrict__ list)
+    const int4* __restrict__ list, int images, int refl)
 {
     double mx = 0.0;
     constexpr int RX = TX + 2, RY = TY + 2, NT = TX * TY, NLD = (RX * RY + NT - 1) / NT;
@@ -87,7 +135,9 @@ __global__ void __launch_bounds__(TX * TY) k_nodal_residual_zm(const BoxD* __res
     const FabD x = xt[fab], s = st[fab], o = ot[fab];
     const int ox = tx0 - 1, oy = ty0 - 1;
     const int tid = threadIdx.x;
-    // footprint addressing (clamped into the arrays; clamped entries are never used by a valid node)
+    // footprint addressing (clamped into the arrays; clamped entries are never used by a valid node).  images (NodalImages: the box spans its
+    // domain): a footprint node of x outside the box is read at its image inside it -- the node a ghost fill would have copied -- and the
+    // ghost nodes of x are not read at all; sigma keeps its ghost cells (filled once per solve).  The offsets are loop invariants.
     long xoff[NLD], soff[NLD];
     int lidx[NLD];
 #pragma unroll
@@ -95,7 +145,8 @@ __global__ void __launch_bounds__(TX * TY) k_nodal_residual_zm(const BoxD* __res
         const int idx = min(tid + it * NT, RX * RY - 1);
         lidx[it] = idx;
         const int gi = ox + idx % RX, gj = oy + idx / RX;
-        const int xi = min(max(gi, x.lo[0]), x.lo[0] + x.n[0] - 1), xj = min(max(gj, x.lo[1]), x.lo[1] + x.n[1] - 1);
+        const int mi = images ? image_node(gi, cb.lo[0], cb.hi[0], refl & 1) : gi, mj = images ? image_node(gj, cb.lo[1], cb.hi[1], refl & 2) : gj;
+        const int xi = min(max(mi, x.lo[0]), x.lo[0] + x.n[0] - 1), xj = min(max(mj, x.lo[1]), x.lo[1] + x.n[1] - 1);
         const int si = min(max(gi, s.lo[0]), s.lo[0] + s.n[0] - 1), sj = min(max(gj, s.lo[1]), s.lo[1] + s.n[1] - 1);
         xoff[it] = x.off(xi, xj, x.lo[2]);
         soff[it] = s.off(si, sj, s.lo[2]);
@@ -103,7 +154,8 @@ __global__ void __launch_bounds__(TX * TY) k_nodal_residual_zm(const BoxD* __res
     const long xpl = (long)x.n[0] * x.n[1], spl = (long)s.n[0] * s.n[1];
     const FabD::gdouble* xp = (const FabD::gdouble*)x.p;
     const FabD::gdouble* sp = (const FabD::gdouble*)s.p;
-    auto ldx = [&](int it, int k) { return xp[xoff[it] + xpl * (k - x.lo[2])]; };
+    // (planes k0 - 1 .. k1 + 1: at most one node outside the box)
+    auto ldx = [&](int it, int k) { return xp[xoff[it] + xpl * ((images ? image_node(k, cb.lo[2], cb.hi[2], refl & 4) : k) - x.lo[2])]; };
     auto lds_ = [&](int it, int k) { return sp[soff[it] + spl * (k - s.lo[2])]; };
     // prologue: planes k0-1, k0 of x and cell plane k0-1 of sigma
 #pragma unroll
@@ -156,7 +208,7 @@ __global__ void __launch_bounds__(TX * TY) k_nodal_residual_zm(const BoxD* __res
 }
 
 // norm_out != null: *norm_out = max norm of out over all ranks if the z-marching kernel ran (returns true); false: the caller computes it
-bool nodal_residual(const Geometry& g, MultiFab& out, const MultiFab& x, const MultiFab& sig, const MultiFab* rhs, double* norm_out)
+bool nodal_residual(const Geometry& g, MultiFab& out, const MultiFab& x, const MultiFab& sig, const MultiFab* rhs, double* norm_out, const NodalImages& img)
 {
     auto& ctx = Context::get();
     static unsigned long long* d_norm = nullptr;
@@ -165,7 +217,7 @@ bool nodal_residual(const Geometry& g, MultiFab& out, const MultiFab& x, const M
     const bool zm = tune("NODAL_RES_ZM", 1) != 0 && lay.max_len[0] >= 16 && lay.max_len[1] >= 8 && x.ngrow >= 1 && sig.ngrow >= 1;
     const bool fused = norm_out && zm && tune("NODAL_RES_NORM", 1) != 0;
     if (fused) IAMRX_HIP_CHECK(hipMemsetAsync(d_norm, 0, sizeof(unsigned long long), ctx.stream));
-    nodal_residual_launch(g, out, x, sig, rhs, fused ? d_norm : nullptr);
+    nodal_residual_launch(g, out, x, sig, rhs, fused ? d_norm : nullptr, img);
     if (!fused) return false;
     const bool global = !lay.replicated && ctx.comm->nranks > 1;
     if (global) ctx.comm->allreduce_device(reinterpret_cast<double*>(d_norm), 1, ReduceOp::Max, ctx.stream);
@@ -178,9 +230,11 @@ bool nodal_residual(const Geometry& g, MultiFab& out, const MultiFab& x, const M
     return true;
 }
 
-void nodal_residual_launch(const Geometry& g, MultiFab& out, const MultiFab& x, const MultiFab& sig, const MultiFab* rhs, unsigned long long* d_norm)
+void nodal_residual_launch(const Geometry& g, MultiFab& out, const MultiFab& x, const MultiFab& sig, const MultiFab* rhs, unsigned long long* d_norm,
+                           const NodalImages& img)
 {
     if (x.nlocal() == 0) return;
+    IAMRX_ASSERT(!img.on || (x.layout->boxes.size() == 1 && x.nlocal() == 1));
     const NodeW w = make_w(g);
     const FabD *ot = out.d_tab, *xt = x.d_tab, *st = sig.d_tab;
     const FabD* rt = rhs ? rhs->d_tab : nullptr;
@@ -190,8 +244,21 @@ void nodal_residual_launch(const Geometry& g, MultiFab& out, const MultiFab& x, 
         constexpr int TX = 32, TY = 8;
         const int ntx = (l.max_len[0] + 1 + TX - 1) / TX, nty = (l.max_len[1] + 1 + TY - 1) / TY;
         const int nk = l.max_len[2] + 1;
-        const int kc = nk >= 128 ? 32 : (nk >= 32 ? 16 : nk);
+        // Planes per workgroup (any value gives the same doubles).  Long chunks save the two-plane prologue, but a level of few tiles then
+        // launches a handful of workgroups that each march a long chain of barrier-separated planes: the chunks are shortened (to a power of
+        // two, not below 2) until the launch has about 2048 workgroups (256 CUs x 8).  Isolated loop on MI355X (tools/bench_nodal_ops.py kc), us
+        // per launch at 17^3 / 33^3 / 65^3 / 129^3 / 257^3 nodes: 18.8 / 24.5 / 18.9 / 45.6 / 170.7 with kc = nk, 16, 16, 32, 32 (the long-chunk
+        // rule alone), 4.8 / 5.2 / 8.4 / 28.8 / 169.5 with kc = 2, 2, 2, 4, 32 (this rule; kc = 1: 4.7 / 4.7 / 9.4).  One-box levels only: that
+        // is what the scan measured, levels of several boxes keep the long chunks.  IAMRX_NODAL_RES_KC > 0 sets kc.
+        const int kc_set = (int)tune("NODAL_RES_KC", 0);
+        int kc = nk >= 128 ? 32 : (nk >= 32 ? 16 : nk);
+        if (l.boxes.size() == 1) {
+            const long fit = (long)ntx * nty * nk / 2048;
+            while (kc > 2 && kc > fit) kc = (kc & (kc - 1)) ? (1 << (31 - __builtin_clz((unsigned)kc))) : kc / 2;
+        }
+        if (kc_set > 0) kc = std::min(kc_set, nk);
         const int nck = (nk + kc - 1) / kc;
+        const int images = img.on ? 1 : 0, refl = img.refl;
         if (l.nlocal() >= 4 && tune("TILE_LISTS", 1) != 0) {
             int n = 0;
             const int4* lst = layout_int4_list(l, {3, TX, TY, kc, 0}, [&](std::vector<int4>& h) {
@@ -203,13 +270,25 @@ void nodal_residual_launch(const Geometry& g, MultiFab& out, const MultiFab& x, 
             }, &n);
             if (lst && 4L * n <= 3L * ntx * nty * nck * l.nlocal()) {
                 hipLaunchKernelGGL((k_nodal_residual_zm<TX, TY>), dim3((unsigned)n), dim3(TX * TY), 0, Context::get().stream, l.d_boxes, ot, xt, st, rt, w, ntx, nty, kc,
-                                   d_norm, lst);
+                                   d_norm, lst, images, refl);
                 return;
             }
         }
         dim3 grid((unsigned)(ntx * nty * nck), (unsigned)l.nlocal());
         hipLaunchKernelGGL((k_nodal_residual_zm<TX, TY>), grid, dim3(TX * TY), 0, Context::get().stream, l.d_boxes, ot, xt, st, rt, w, ntx, nty, kc, d_norm,
-                           (const int4*)nullptr);
+                           (const int4*)nullptr, images, refl);
+        return;
+    }
+    if (img.on) {
+        const BoxD b = l.boxes[0];
+        const int refl = img.refl;
+        for_each(*x.layout, node_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
+            double s0;
+            const double y = node_Ax_at(xt[f], st[f], w, image_node(i - 1, b.lo[0], b.hi[0], refl & 1), i, image_node(i + 1, b.lo[0], b.hi[0], refl & 1),
+                                        image_node(j - 1, b.lo[1], b.hi[1], refl & 2), j, image_node(j + 1, b.lo[1], b.hi[1], refl & 2),
+                                        image_node(k - 1, b.lo[2], b.hi[2], refl & 4), k, image_node(k + 1, b.lo[2], b.hi[2], refl & 4), s0);
+            ot[f](i, j, k) = rt ? rt[f](i, j, k) - y : y;
+        });
         return;
     }
     for_each(*x.layout, node_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
@@ -270,32 +349,6 @@ void nodal_gs_color(const Geometry& g, MultiFab& x, const MultiFab& rhs, const M
 // to xo.  In place, a workgroup could read halo nodes of plane k that a neighbouring workgroup has already updated (not
 // all workgroups of a large level are resident together), which would silently change the Gauss-Seidel ordering.
 // HBM traffic per sweep drops from 8 full-array passes to 2; kernel launches from 8+8 fills to 2+2.
-// periodic image of a node / cell index inside the one box [lo, hi] (cells) that spans the periodic domain
-__device__ __forceinline__ int wrap_node(int g, int lo, int hi)
-{
-    // the staging halo is 4 nodes wide and the box has >= 4 cells (periodic_wrap_ok(g, l, 4)): one conditional shift is enough
-    const int n = hi - lo + 1;
-    return g < lo ? g + n : (g > hi + 1 ? g - n : g);
-}
-__device__ __forceinline__ int wrap_cell(int g, int lo, int hi)
-{
-    const int n = hi - lo + 1;
-    return g < lo ? g + n : (g > hi ? g - n : g);
-}
-// ... or, in a direction that ends on Neumann walls (refl): the mirror image -- what nodal_reflect_bc / cc_mirror_bc write into the ghost
-// nodes / cells (even reflection about the wall node lo resp. hi + 1; sigma mirrored about the wall face): the index-wrap variants then
-// read the valid data of a wall-bounded box directly as well, no ghost fill in front of a pass
-__device__ __forceinline__ int image_node(int g, int lo, int hi, bool refl)
-{
-    if (refl) return g < lo ? 2 * lo - g : (g > hi + 1 ? 2 * (hi + 1) - g : g);
-    return wrap_node(g, lo, hi);
-}
-__device__ __forceinline__ int image_cell(int g, int lo, int hi, bool refl)
-{
-    if (refl) return g < lo ? 2 * lo - 1 - g : (g > hi ? 2 * hi + 1 - g : g);
-    return wrap_cell(g, lo, hi);
-}
-
 template <int TX, int TY, int NT, bool WRAP, bool MASK, bool CSIG>
 // no minimum-occupancy bound: measured at 256^3 on MI355X (profiles/round2_b_*), forcing 4 waves/SIMD on the variable-sigma variant (168 VGPRs
 // -> 128 + 41 spilled) costs 2x (325 us against 165 us per launch), 5-6 on the constant-sigma one (104 VGPRs) gains nothing / loses 35 %
@@ -1587,7 +1640,7 @@ void nodal_build_dmask(const Geometry& g, MultiFab& dm, const MultiFab& cov, con
 // unit-stride in LDS.  The 27 terms are added in the order of the per-node form: the same doubles.
 template <int CTX, int CTY>
 __global__ void __launch_bounds__(CTX * CTY) k_nodal_restrict_tile(const BoxD* __restrict__ cboxes, const FabD* __restrict__ ct, const FabD* __restrict__ ft,
-    int ntx, int nty, int kc)
+    int ntx, int nty, int kc, int images, int refl, BoxD fb)
 {
     constexpr int FX = 2 * CTX + 1, FY = 2 * CTY + 1, HX = CTX + 1, PX = 2 * HX, NT = CTX * CTY, NLD = (FX * FY + NT - 1) / NT;
     __shared__ double F[3][FY][PX];
@@ -1611,15 +1664,21 @@ __global__ void __launch_bounds__(CTX * CTY) k_nodal_restrict_tile(const BoxD* _
     for (int it = 0; it < NLD; ++it) {
         const int idx = tid + it * NT;
         const int lx = idx % FX, ly = idx / FX;
-        const int gi = ox + lx, gj = oy + ly;
-        const bool on = idx < FX * FY && gi >= fa.lo[0] && gi <= fhi0 && gj >= fa.lo[1] && gj <= fhi1;
+        // images (NodalImages; fb = the fine box, which spans its domain): a fine node outside the box is read at its image inside it and
+        // the ghost nodes of the fine array are not read at all
+        const bool in_reach = ox + lx <= 2 * nhi0 + 1 && oy + ly <= 2 * nhi1 + 1;
+        const int gi = images ? image_node(ox + lx, fb.lo[0], fb.hi[0], refl & 1) : ox + lx, gj = images ? image_node(oy + ly, fb.lo[1], fb.hi[1], refl & 2) : oy + ly;
+        const bool on = idx < FX * FY && in_reach && gi >= fa.lo[0] && gi <= fhi0 && gj >= fa.lo[1] && gj <= fhi1;
         foff[it] = on ? fa.off(gi, gj, fa.lo[2]) : -1;
         lslot[it] = idx < FX * FY ? ly * PX + (lx & 1) * HX + (lx >> 1) : -1;
     }
     const long fpl = (long)fa.n[0] * fa.n[1];
     const FabD::gdouble* fp = (const FabD::gdouble*)fa.p;
     const int fklo = fa.lo[2], fkhi = fa.lo[2] + fa.n[2] - 1;
-    auto ldf = [&](int it, int k) { return (foff[it] >= 0 && k >= fklo && k <= fkhi) ? (double)fp[foff[it] + fpl * (k - fklo)] : 0.0; };
+    auto ldf = [&](int it, int k_) {
+        const int k = images ? image_node(k_, fb.lo[2], fb.hi[2], refl & 4) : k_;
+        return (foff[it] >= 0 && k >= fklo && k <= fkhi) ? (double)fp[foff[it] + fpl * (k - fklo)] : 0.0;
+    };
     double* Fl = &F[0][0][0];
     constexpr int PL = FY * PX;
     int sm = 0, s0 = 1, sp = 2;          // LDS planes of the fine planes 2k-1, 2k, 2k+1
@@ -1664,10 +1723,14 @@ __global__ void __launch_bounds__(CTX * CTY) k_nodal_restrict_tile(const BoxD* _
     }
 }
 
-// full weighting (1,2,1)^3/64; the fine array needs one filled ghost-node layer
-void nodal_restrict(MultiFab& crse, const MultiFab& fine)
+// full weighting (1,2,1)^3/64; the fine array needs one filled ghost-node layer -- or img (the fine level is one box spanning its domain):
+// the fine nodes outside the box are read at their images inside it
+void nodal_restrict(MultiFab& crse, const MultiFab& fine, const NodalImages& img)
 {
     if (crse.nlocal() == 0) return;
+    IAMRX_ASSERT(!img.on || (fine.layout->boxes.size() == 1 && fine.nlocal() == 1 && crse.nlocal() == 1));
+    const BoxD fb = fine.layout->boxes[0];
+    const int images = img.on ? 1 : 0, refl = img.refl;
     const FabD *ct = crse.d_tab, *ft = fine.d_tab;
     const Layout& cl = *crse.layout;
     // (measured on MI355X, coarse 128^3 / 64^3 / 32^3: 38 / 12 / 8 us against 50 / 15 / 5 us of the per-node form -- small levels are launch
@@ -1680,7 +1743,7 @@ void nodal_restrict(MultiFab& crse, const MultiFab& fine)
         const int kc = nk >= 64 ? 8 : 4;
         const int nck = (nk + kc - 1) / kc;
         dim3 grid((unsigned)(ntx * nty * nck), (unsigned)cl.nlocal());
-        hipLaunchKernelGGL((k_nodal_restrict_tile<CTX, CTY>), grid, dim3(CTX * CTY), 0, Context::get().stream, cl.d_boxes, ct, ft, ntx, nty, kc);
+        hipLaunchKernelGGL((k_nodal_restrict_tile<CTX, CTY>), grid, dim3(CTX * CTY), 0, Context::get().stream, cl.d_boxes, ct, ft, ntx, nty, kc, images, refl, fb);
         return;
     }
     for_each(*crse.layout, node_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
@@ -1691,7 +1754,9 @@ void nodal_restrict(MultiFab& crse, const MultiFab& fine)
             for (int dj = -1; dj <= 1; ++dj)
                 for (int di = -1; di <= 1; ++di) {
                     const double w = (di == 0 ? 2. : 1.) * (dj == 0 ? 2. : 1.) * (dk == 0 ? 2. : 1.);
-                    s += w * fa(ii + di, jj + dj, kk + dk);
+                    int fi = ii + di, fj = jj + dj, fk = kk + dk;
+                    if (images) { fi = image_node(fi, fb.lo[0], fb.hi[0], refl & 1); fj = image_node(fj, fb.lo[1], fb.hi[1], refl & 2); fk = image_node(fk, fb.lo[2], fb.hi[2], refl & 4); }
+                    s += w * fa(fi, fj, fk);
                 }
         ct[f](i, j, k) = s * (1. / 64.);
     });

@@ -208,7 +208,12 @@ void godunov_compute_aofs(const Geometry& g, MultiFab& aofs, int acomp, const Mu
 
 
 // ---- k_nodal.hip --------------------------------------------------------------------------
-bool nodal_residual(const Geometry& g, MultiFab& out, const MultiFab& x, const MultiFab& sig, const MultiFab* rhs, double* norm_out = nullptr);
+// Image reading (residual: x, restriction: fine): the array's level is one box spanning its domain (nodal_wrap_or_reflect_ok), so a node
+// outside the box is the periodic image -- in the directions of refl (bit d): the mirror image about the Neumann wall -- of a valid node.
+// on: the kernel reads that node instead of the ghost node, which then needs no fill (FillBoundary + nodal_reflect_bc); the same doubles.
+struct NodalImages { bool on = false; int refl = 0; };
+bool nodal_residual(const Geometry& g, MultiFab& out, const MultiFab& x, const MultiFab& sig, const MultiFab* rhs, double* norm_out = nullptr,
+                    const NodalImages& img = NodalImages());
 void nodal_gs_color(const Geometry& g, MultiFab& x, const MultiFab& rhs, const MultiFab& sig, int color, const MultiFab* dmask = nullptr);
 // one k-parity pass of the plane-fused 8-colour GS (arrays need ngrow >= 4 / 3), out of place: plane k from xc, planes
 // k+-1 from xn, result to xo (xo != xc; xn may be either)
@@ -229,7 +234,7 @@ bool nodal_wrap_or_reflect_ok(const Geometry& g, const Layout& l, const DomainBC
 // all sweeps x 8 colours of a small single-box periodic level in one single-workgroup launch (false: not applicable)
 bool nodal_smooth_small(const Geometry& g, MultiFab& x, const MultiFab& rhs, const MultiFab& sig, int nsweeps);
 void nodal_jacobi(const Geometry& g, MultiFab& xnew, const MultiFab& x, const MultiFab& rhs, const MultiFab& sig, const MultiFab* dmask = nullptr);
-void nodal_restrict(MultiFab& crse, const MultiFab& fine);
+void nodal_restrict(MultiFab& crse, const MultiFab& fine, const NodalImages& img = NodalImages());
 void nodal_interp_add(MultiFab& fine, const MultiFab& crse, const MultiFab& sig_fine);
 void nodal_divu(const Geometry& g, MultiFab& rhs, const MultiFab& vel, int vcomp, const DomainBC* bc);
 // vel(vcomp..) -= sig*grad(phi) (vel may be null); gp (may be null) = or += grad(phi)

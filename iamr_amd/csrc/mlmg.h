@@ -270,6 +270,7 @@ private:
         MultiFab xb;               // second buffer of the out-of-place fused Gauss-Seidel sweeps
         MultiFab dm;               // Dirichlet node mask (defined only if the level has Dirichlet nodes, see NodalMG ctor)
         const MultiFab* dmask() const { return dm.defined() ? &dm : nullptr; }
+        NodalImages img;           // the level's residual and restriction read images instead of ghost nodes (NodalMG ctor): no ghost fills inside a cycle
     };
     int bicgstab(int l, MultiFab& sol, const MultiFab& rhs, double eps_rel, double eps_abs, int& niters);
     bool bottom_on_device();     // the coarsest level is solved by k_nodal_bottom (single-workgroup launch, no host synchronisation)

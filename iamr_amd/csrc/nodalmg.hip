@@ -11,7 +11,6 @@
 namespace iamrx {
 
 // kernels (k_nodal.hip)
-void nodal_restrict(MultiFab& crse, const MultiFab& fine);
 void nodal_interp_add(MultiFab& fine, const MultiFab& crse, const MultiFab& sig_fine);
 
 // plane-fused sweep (2 launches + 2 fills instead of 8 + 8): measured per sweep on MI355X 0.69 vs 0.79 ms at 256^3,
@@ -108,6 +107,15 @@ NodalMG::NodalMG(const Geometry& g, LayoutP layout, const DomainBC& bc_in, const
         m_singular = false;
         for (auto& L : m_lev) IAMRX_ASSERT(L.dm.defined());
     }
+    // Image readers (IAMRX_NODAL_IMAGE_READERS, 1; 0: every fill below and the ghost-reading kernels): on a level the smoothers take with
+    // index wrap / reflection (smooth(): `wrap` -- one box spanning its domain, no Dirichlet nodes) the residual and the restriction read the
+    // images of the nodes outside the box from the valid nodes as well, so nobody reads a ghost node of cor, xb, rescor or res inside a
+    // cycle and the fills behind the smoothing calls and in front of the residual, the restriction and the interpolation are not issued.
+    const bool img_on = tune("NODAL_IMAGE_READERS", 1) != 0 && m_o.nodal_smoother == 0 && nodal_fused();
+    for (auto& L : m_lev) {
+        L.img.on = img_on && !L.dmask() && nodal_wrap_or_reflect_ok(L.g, *L.layout, m_bc, 4, &L.img.refl);
+        if (!L.img.on) L.img.refl = 0;
+    }
 }
 
 void NodalMG::setSigma(const MultiFab& sig, int comp)
@@ -166,7 +174,7 @@ void NodalMG::smooth(int l, MultiFab& x, const MultiFab& rhs, bool x_is_zero, bo
     // small single-box periodic levels: all sweeps x colours in one single-workgroup launch
     const MultiFab* dmk = L.dmask();
     if (!dmk && m_o.nodal_smoother == 0 && nodal_small() && nodal_smooth_small(L.g, x, rhs, L.sig, m_o.nodal_sweeps)) {
-        fillbc(l, x);
+        if (!L.img.on) fillbc(l, x);          // (the kernel writes the periodic duplicates itself)
         return;
     }
     if (m_o.nodal_smoother == 0 && nodal_fused()) {
@@ -225,7 +233,8 @@ void NodalMG::smooth(int l, MultiFab& x, const MultiFab& rhs, bool x_is_zero, bo
             std::swap(a, b);
         }
         if (a != &x) MultiFab::Copy(x, *a, 0, 0, 1, 0);
-        if (!leave_ghosts) fillbc(l, x);
+        // (a level of image readers: every later reader of x takes images; without index wrap each pass above fills what it reads)
+        if (!leave_ghosts && !L.img.on) fillbc(l, x);
         return;
     }
     for (int ns = 0; ns < m_o.nodal_sweeps; ++ns) {
@@ -247,9 +256,10 @@ void NodalMG::smooth(int l, MultiFab& x, const MultiFab& rhs, bool x_is_zero, bo
 
 void NodalMG::residual(int l, MultiFab& r, MultiFab& x, const MultiFab& b, double* norm, bool x_filled)
 {
-    if (!x_filled) fillbc(l, x);
+    const NodalImages& img = m_lev[l].img;
+    if (!x_filled && !img.on) fillbc(l, x);
     const bool masked = (bool)m_lev[l].dmask();
-    const bool have = nodal_residual(m_lev[l].g, r, x, m_lev[l].sig, &b, (norm && !masked) ? norm : nullptr);
+    const bool have = nodal_residual(m_lev[l].g, r, x, m_lev[l].sig, &b, (norm && !masked) ? norm : nullptr, img);
     if (masked) nodal_zero_masked(r, m_lev[l].dm);
     if (norm && !have) *norm = r.norm0(0, 1, 0);
 }
@@ -290,10 +300,11 @@ void NodalMG::vcycle(MGStats& st)
         Level& L = m_lev[l];
         if (m_o.nodal_nu1 <= 0) L.cor.setVal(0.0);
         for (int i = 0; i < m_o.nodal_nu1; ++i) smooth(l, L.cor, L.res, i == 0);
-        residual(l, L.rescor, L.cor, L.res, nullptr, m_o.nodal_nu1 > 0);          // (smooth() has just filled the ghost nodes)
-        fillbc(l, L.rescor);
+        residual(l, L.rescor, L.cor, L.res, nullptr, m_o.nodal_nu1 > 0);          // (smooth() has just filled the ghost nodes, or the level reads images: no fill)
         Level& C = m_lev[l + 1];
-        mg_restrict_to(C, C.res, C.tmp_d, C.vres, [&](MultiFab& target) { nodal_restrict(target, L.rescor); });
+        const NodalImages rimg = (!C.slab && !C.agg) ? L.img : NodalImages();
+        if (!rimg.on) fillbc(l, L.rescor);
+        mg_restrict_to(C, C.res, C.tmp_d, C.vres, [&](MultiFab& target) { nodal_restrict(target, L.rescor, rimg); });
         m_lev[l + 1].res_filled = false;
         if (m_lev[l + 1].dmask()) nodal_zero_masked(m_lev[l + 1].res, m_lev[l + 1].dm);   // mlndlap_restriction: 0 on Dirichlet nodes
     }
@@ -329,7 +340,8 @@ void NodalMG::vcycle(MGStats& st)
     for (int l = nl - 2; l >= 0; --l) {
         Level& L = m_lev[l];
         // (a level that was smoothed on the way up comes with its ghost nodes filled; the bottom level comes from its solver)
-        if (l + 1 == nl - 1 || m_o.nodal_nu2 <= 0) fillbc(l + 1, m_lev[l + 1].cor);
+        // (the interpolation reads valid coarse nodes only, periodic duplicates included: the smoothers and the bottom kernels write them)
+        if ((l + 1 == nl - 1 || m_o.nodal_nu2 <= 0) && !m_lev[l + 1].img.on) fillbc(l + 1, m_lev[l + 1].cor);
         nodal_interp_add(L.cor, mg_correction_of(m_lev[l + 1], m_lev[l + 1].cor, 1), L.sig);
         if (L.dmask()) nodal_zero_masked(L.cor, L.dm);                  // mlndlap_interpadd: Dirichlet nodes take no correction
         // the finest level's correction is added to the solution node by node: nobody reads its ghost nodes

@@ -48,6 +48,13 @@ def nodal_residual(geom, out, phi, sig, rhs=None):
     check(lib().iamrx_nodal_residual(C.byref(geom), out.h, phi.h, sig.h, _h(rhs)))
 
 
+def nodal_residual_images(geom, out, phi, sig, rhs=None, lobc=(0, 0, 0), hibc=(0, 0, 0)):
+    """nodal_residual with image reads instead of phi's ghost nodes (one box spanning a periodic / Neumann-walled domain); returns max |out|"""
+    norm = C.c_double()
+    check(lib().iamrx_nodal_residual_images(C.byref(geom), out.h, phi.h, sig.h, _h(rhs), i3(lobc), i3(hibc), C.byref(norm)))
+    return norm.value
+
+
 def nodal_gs_color(geom, phi, rhs, sig, color):
     check(lib().iamrx_nodal_gs_color(C.byref(geom), phi.h, rhs.h, sig.h, color))
 
@@ -59,6 +66,11 @@ def nodal_gs_sweep(geom, phi, rhs, sig, fused=1):
 
 def nodal_restrict(crse, fine):
     check(lib().iamrx_nodal_restrict(crse.h, fine.h))
+
+
+def nodal_restrict_images(geom, crse, fine, lobc=(0, 0, 0), hibc=(0, 0, 0)):
+    """nodal_restrict with image reads instead of fine's ghost nodes; geom: the fine level's"""
+    check(lib().iamrx_nodal_restrict_images(C.byref(geom), crse.h, fine.h, i3(lobc), i3(hibc)))
 
 
 def nodal_interp_add(fine, crse, sig_fine):

@@ -287,13 +287,20 @@ int iamrx_godunov_compute_aofs(const iamrx_geom* g, iamrx_mf aofs, int acomp, ia
 /* ---- nodal projection (amrex::MLNodeLaplacian / Hydro::NodalProjector role) ------- */
 /* out = rhs - div(sig grad phi) at nodes (rhs == NULL: out = div(sig grad phi)); phi and sig need 1 filled ghost */
 int iamrx_nodal_residual(const iamrx_geom* g, iamrx_mf out, iamrx_mf phi, iamrx_mf sig, iamrx_mf rhs);
+/* the same on a level that is one box spanning its domain, every direction periodic or between Neumann walls (lobc / hibc: LinOpBC codes):
+   the nodes outside the box are read at their periodic / mirror images inside it, so the ghost nodes of phi need no fill (sig: as above);
+   norm != NULL: the max norm of out.  The same doubles as iamrx_nodal_residual on filled ghost nodes; an error where the level does not qualify */
+int iamrx_nodal_residual_images(const iamrx_geom* g, iamrx_mf out, iamrx_mf phi, iamrx_mf sig, iamrx_mf rhs, const int lobc[3], const int hibc[3],
+                                double* norm);
 /* one colour (0..7) of the 8-colour Gauss-Seidel sweep */
 int iamrx_nodal_gs_color(const iamrx_geom* g, iamrx_mf phi, iamrx_mf rhs, iamrx_mf sig, int color);
 /* one full 8-colour Gauss-Seidel sweep incl. its ghost fills.  fused = 0: eight colour passes (8 fills);
  * fused = 1: plane-fused variant, two passes (2 fills), identical arithmetic; needs phi/sig ngrow >= 4, rhs >= 3
  * (rhs ghosts must be filled by the caller) */
 int iamrx_nodal_gs_sweep(const iamrx_geom* g, iamrx_mf phi, iamrx_mf rhs, iamrx_mf sig, int fused);
-int iamrx_nodal_restrict(iamrx_mf crse, iamrx_mf fine);
+int iamrx_nodal_restrict(iamrx_mf crse, iamrx_mf fine);      /* full weighting; fine needs 1 filled ghost */
+/* the same with image reads of the fine level (g: its geometry; conditions as for iamrx_nodal_residual_images): no fill of fine's ghost nodes */
+int iamrx_nodal_restrict_images(const iamrx_geom* g, iamrx_mf crse, iamrx_mf fine, const int lobc[3], const int hibc[3]);
 int iamrx_nodal_interp_add(iamrx_mf fine, iamrx_mf crse, iamrx_mf sig_fine);
 int iamrx_nodal_divu(const iamrx_geom* g, iamrx_mf rhs, iamrx_mf vel, int vcomp);
 /* the same with the boundary codes of the non-periodic faces (LinOpBC codes: 102 Neumann wall, 103 inflow -- only the normal velocity
