@@ -169,6 +169,33 @@ int iamrx_host_abec_smoother_plan(int nboxes, const int* lo_hi, const iamrx_geom
     IAMRX_CATCH
 }
 
+// host-only (no device needed): how a smoothing call and the bottom solve of the nodal multigrid run on a level (nodal_smooth_plan, k_nodal.hip).
+// out (11 ints): path (0 JACOBI, 1 COLOUR8, 2 SMALL, 3 GS4, 4 GSR), ngrow, wrap, refl, images, written_first, zero_start, par_fill, splits,
+// bottom (0 NONE, 1 SMOOTHER_ONLY, 2 DEVICE_PERIODIC, 3 DEVICE_GENERAL, 4 HOST_KRYLOV), sweeps
+int iamrx_host_nodal_smoother_plan(int nboxes, const int* lo_hi, const iamrx_geom* g, const int lobc[3], const int hibc[3], int has_mask,
+                                   int nodal_smoother, int bottom_smoother_only, int device_bottom, int nodal_sweeps, int coarsest, const int ngrow[2],
+                                   int out[11])
+{
+    IAMRX_TRY
+    if (nboxes < 1) throw Error("iamrx_host_nodal_smoother_plan: at least one box");
+    std::vector<BoxD> b(nboxes);
+    NodalLevel lv;
+    for (int i = 0; i < nboxes; ++i)
+        for (int d = 0; d < 3; ++d) { b[i].lo[d] = lo_hi[6 * i + d]; b[i].hi[d] = lo_hi[6 * i + 3 + d]; lv.max_len[d] = std::max(lv.max_len[d], b[i].len(d)); }
+    // (NodalMG's operator codes: inflow faces are Neumann walls)
+    DomainBC bc = to_bc(lobc, hibc, 2);
+    for (int d = 0; d < 3; ++d) { if (bc.lo[d] == lo_inflow) bc.lo[d] = lo_neumann; if (bc.hi[d] == lo_inflow) bc.hi[d] = lo_neumann; }
+    lv.boxes = &b; lv.nlocal = nboxes; lv.bc = &bc;
+    lv.cor_ngrow = ngrow[0]; lv.rhs_ngrow = ngrow[1];
+    lv.has_mask = has_mask != 0;
+    lv.nodal_smoother = nodal_smoother; lv.bottom_smoother_only = bottom_smoother_only; lv.device_bottom = device_bottom; lv.nodal_sweeps = nodal_sweeps;
+    lv.coarsest = coarsest != 0;
+    const NodalSmoothPlan p = nodal_smooth_plan(to_geom(g), lv);
+    const int v[11] = {(int)p.path, p.ngrow, p.wrap, p.refl, p.images, p.written_first, p.zero_start, p.par_fill, p.splits, (int)p.bottom, p.sweeps};
+    std::copy(v, v + 11, out);
+    IAMRX_CATCH
+}
+
 static hipEvent_t g_ev0 = nullptr, g_ev1 = nullptr;
 int iamrx_timer_start(void)
 {
@@ -694,17 +721,19 @@ int iamrx_nodal_gs_sweep(const iamrx_geom* g, iamrx_mf phi, iamrx_mf rhs, iamrx_
         if (wrap && !periodic_wrap_ok(gg, *phi->mf.layout, 4)) throw Error("iamrx_nodal_gs_sweep(4): not a single box spanning a periodic domain");
         // IAMRX_BENCH_CSIG = c != 0: the constant-sigma variant with sigma = c (the caller's sigma array holds that constant)
         const double cs = tune("BENCH_CSIG", 0.0);
-        nodal_gs_fused_pass(gg, phi->mf, phi->mf, xb, rhs->mf, sig->mf, 0, wrap, nullptr, cs != 0.0 ? &cs : nullptr);
-        nodal_gs_fused_pass(gg, phi->mf, xb, xb, rhs->mf, sig->mf, 1, wrap, nullptr, cs != 0.0 ? &cs : nullptr);
+        const NodalSmoothPlan p = nodal_pass_form(phi->mf, rhs->mf, wrap);
+        nodal_gs_fused_pass(gg, p, phi->mf, phi->mf, xb, rhs->mf, sig->mf, 0, nullptr, cs != 0.0 ? &cs : nullptr);
+        nodal_gs_fused_pass(gg, p, phi->mf, xb, xb, rhs->mf, sig->mf, 1, nullptr, cs != 0.0 ? &cs : nullptr);
     } else if (fused == 2) {
         if (!nodal_smooth_small(gg, phi->mf, rhs->mf, sig->mf, 1)) throw Error("level does not qualify for the single-workgroup smoother");
         phi->mf.FillBoundary(gg);
     } else if (fused) {
         MultiFab xb(phi->mf.layout, node_type(), 1, phi->mf.ngrow);
+        const NodalSmoothPlan p = nodal_pass_form(phi->mf, rhs->mf);
         phi->mf.FillBoundary(gg);
-        nodal_gs_fused_pass(gg, phi->mf, phi->mf, xb, rhs->mf, sig->mf, 0);
+        nodal_gs_fused_pass(gg, p, phi->mf, phi->mf, xb, rhs->mf, sig->mf, 0);
         xb.FillBoundary(gg);
-        nodal_gs_fused_pass(gg, phi->mf, xb, xb, rhs->mf, sig->mf, 1);
+        nodal_gs_fused_pass(gg, p, phi->mf, xb, xb, rhs->mf, sig->mf, 1);
         MultiFab::Copy(phi->mf, xb, 0, 0, 1, 0);
     } else {
         for (int c = 0; c < 8; ++c) { phi->mf.FillBoundary(gg); nodal_gs_color(gg, phi->mf, rhs->mf, sig->mf, c); }

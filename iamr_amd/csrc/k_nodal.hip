@@ -1090,26 +1090,27 @@ static void gsr_launch(const Layout& l, const Geometry& g, const MultiFab& xc, c
 // one k-parity pass (kpar = 0: colours 0-3, kpar = 1: colours 4-7); wrap: see periodic_wrap_ok; needs x.ngrow >= 4, sig.ngrow >= 4, rhs.ngrow >= 3
 // true if the level is one box that spans a fully periodic domain: the smoother kernels can then read periodic images straight from
 // the valid data (wrap = true) and the ghost fills of x / rhs in front of it can be skipped
-bool periodic_wrap_ok(const Geometry& g, const Layout& l, int min_len)
+static bool periodic_wrap_boxes(const Geometry& g, const std::vector<BoxD>& boxes, int nlocal, int min_len)
 {
     const bool on = tune("PERIODIC_WRAP", 1) != 0;
-    if (!on || l.boxes.size() != 1 || l.nlocal() != 1) return false;
+    if (!on || boxes.size() != 1 || nlocal != 1) return false;
     for (int d = 0; d < 3; ++d)
-        if (!g.periodic[d] || l.boxes[0].lo[d] != g.domain.lo[d] || l.boxes[0].hi[d] != g.domain.hi[d] || l.boxes[0].len(d) < min_len) return false;
+        if (!g.periodic[d] || boxes[0].lo[d] != g.domain.lo[d] || boxes[0].hi[d] != g.domain.hi[d] || boxes[0].len(d) < min_len) return false;
     return true;
 }
+bool periodic_wrap_ok(const Geometry& g, const Layout& l, int min_len) { return periodic_wrap_boxes(g, l.boxes, l.nlocal(), min_len); }
 
 // ... or one box that spans a domain whose non-periodic directions end on Neumann walls on both sides (the pressure of a closed or
 // channel-like domain: LidDrivenCavity): the same kernels with mirror images in those directions (refl: bit d).  No Dirichlet mask (the
 // caller checks).  IAMRX_NODAL_REFLECT_WRAP (1): 0 = ghost fills (nodal_reflect_bc) in front of every pass.
-bool nodal_wrap_or_reflect_ok(const Geometry& g, const Layout& l, const DomainBC& bc, int min_len, int* refl)
+static bool wrap_or_reflect_boxes(const Geometry& g, const std::vector<BoxD>& boxes, int nlocal, const DomainBC& bc, int min_len, int* refl)
 {
     *refl = 0;
-    if (periodic_wrap_ok(g, l, min_len)) return true;
-    if (tune("PERIODIC_WRAP", 1) == 0 || tune("NODAL_REFLECT_WRAP", 1) == 0 || l.boxes.size() != 1 || l.nlocal() != 1) return false;
+    if (periodic_wrap_boxes(g, boxes, nlocal, min_len)) return true;
+    if (tune("PERIODIC_WRAP", 1) == 0 || tune("NODAL_REFLECT_WRAP", 1) == 0 || boxes.size() != 1 || nlocal != 1) return false;
     int r = 0;
     for (int d = 0; d < 3; ++d) {
-        if (l.boxes[0].lo[d] != g.domain.lo[d] || l.boxes[0].hi[d] != g.domain.hi[d] || l.boxes[0].len(d) < min_len) return false;
+        if (boxes[0].lo[d] != g.domain.lo[d] || boxes[0].hi[d] != g.domain.hi[d] || boxes[0].len(d) < min_len) return false;
         if (g.periodic[d]) continue;
         if (bc.lo[d] != lo_neumann || bc.hi[d] != lo_neumann) return false;
         r |= 1 << d;
@@ -1117,30 +1118,94 @@ bool nodal_wrap_or_reflect_ok(const Geometry& g, const Layout& l, const DomainBC
     *refl = r;
     return true;
 }
-
-// the register-resident kernel takes this level (and honours zero_flags: bit 0 / 1 = xc / xn is identically zero and need not be read)
-bool nodal_gsr_applies(const MultiFab& x, const MultiFab& rhs, const MultiFab* dmask)
+bool nodal_wrap_or_reflect_ok(const Geometry& g, const Layout& l, const DomainBC& bc, int min_len, int* refl)
 {
-    const Layout& l = *x.layout;
-    const bool mask_shapes_ok = !dmask || (dmask->ngrow == x.ngrow && rhs.ngrow == x.ngrow);
-    return tune("GSR", 1) != 0 && l.max_len[0] >= tune("GSR_MIN", 48) && l.max_len[1] >= tune("GSR_MIN", 48) && mask_shapes_ok;
+    return wrap_or_reflect_boxes(g, l.boxes, l.nlocal(), bc, min_len, refl);
+}
+
+// the register-resident kernel takes this level (and honours zero_flags): boxes of at least GSR_MIN cells in x and y (IAMRX_GSR=0:
+// k_nodal_gs4 everywhere); a mask must have the shape of x, and so must rhs then
+static bool nodal_gsr_applies(const NodalLevel& lv)
+{
+    const bool mask_shapes_ok = !lv.has_mask || lv.rhs_ngrow == lv.cor_ngrow;
+    return tune("GSR", 1) != 0 && lv.max_len[0] >= tune("GSR_MIN", 48) && lv.max_len[1] >= tune("GSR_MIN", 48) && mask_shapes_ok;
 }
 
 // the level is smoothed by k_nodal_gsr and its boxes hold tiles whose footprint lies inside the box (>= 3 tiles in x and y: 113 nodes)
-bool nodal_gsr_splits(const MultiFab& x, const MultiFab& rhs, const MultiFab* dmask)
+static bool nodal_gsr_splits(const NodalLevel& lv)
 {
-    if (x.nlocal() == 0 || !nodal_gsr_applies(x, rhs, dmask)) return false;
-    const Layout& l = *x.layout;
+    if (lv.nlocal == 0 || !nodal_gsr_applies(lv)) return false;
     int ntx, nty, p;
-    gsr_tiles(l.max_len[0] + 1, ntx, p);
-    gsr_tiles(l.max_len[1] + 1, nty, p);
-    return ntx >= 3 && nty >= 3 && l.max_len[2] >= 16;
+    gsr_tiles(lv.max_len[0] + 1, ntx, p);
+    gsr_tiles(lv.max_len[1] + 1, nty, p);
+    return ntx >= 3 && nty >= 3 && lv.max_len[2] >= 16;
 }
 
-void nodal_gs_fused_pass(const Geometry& g, const MultiFab& xc, const MultiFab& xn, MultiFab& xo, const MultiFab& rhs, const MultiFab& sig, int kpar, bool wrap,
-                         const MultiFab* dmask, const double* csig, int zero_flags, int refl, int sel, hipStream_t on)
+static bool nodal_small_ok(const Geometry& g, const std::vector<BoxD>& boxes, int nlocal);
+static bool nodal_bottom_boxes_ok(const Geometry& g, const std::vector<BoxD>& boxes);
+static bool nodal_bottom_boxes_ok_general(const Geometry& g, const std::vector<BoxD>& boxes);
+
+// plane-fused sweep (2 launches + 2 fills instead of 8 + 8): measured per sweep on MI355X 0.69 vs 0.79 ms at 256^3,
+// 0.11 vs 0.20 ms at 128^3, 0.03 vs 0.09 ms at <= 64^3.  IAMRX_NODAL_FUSED=0 selects the 8 colour passes.
+static bool nodal_fused_on() { return tune("NODAL_FUSED", 1) != 0; }
+// 4 ghost layers: the plane-fused Gauss-Seidel recomputes its halo instead of exchanging it per colour
+int nodal_plan_ngrow() { return nodal_fused_on() ? 4 : 1; }
+
+NodalSmoothPlan::Bottom nodal_bottom_kind(const Geometry& g, const NodalLevel& lv)
 {
-    IAMRX_ASSERT(refl == 0 || wrap);
+    if (lv.bottom_smoother_only) return NodalSmoothPlan::SMOOTHER_ONLY;
+    if (!(lv.device_bottom && lv.nodal_smoother == 0)) return NodalSmoothPlan::HOST_KRYLOV;
+    if (!lv.has_mask && nodal_bottom_boxes_ok(g, *lv.boxes)) return NodalSmoothPlan::DEVICE_PERIODIC;           // fully periodic: the wrap-only kernel
+    if (nodal_bottom_boxes_ok_general(g, *lv.boxes)) return NodalSmoothPlan::DEVICE_GENERAL;                    // walls / Dirichlet mask / refined patch
+    return NodalSmoothPlan::HOST_KRYLOV;
+}
+
+NodalSmoothPlan nodal_smooth_plan(const Geometry& g, const NodalLevel& lv)
+{
+    NodalSmoothPlan p;
+    p.cor_ngrow = lv.cor_ngrow; p.rhs_ngrow = lv.rhs_ngrow; p.sweeps = lv.nodal_sweeps;
+    p.ngrow = nodal_plan_ngrow();
+    const bool gs = lv.nodal_smoother == 0, fused = gs && nodal_fused_on();
+    const bool gsr = nodal_gsr_applies(lv);
+    p.wrap = fused && !lv.has_mask && wrap_or_reflect_boxes(g, *lv.boxes, lv.nlocal, *lv.bc, 4, &p.refl);
+    if (!p.wrap) p.refl = 0;
+    // small single-box periodic levels: all sweeps x colours in one single-workgroup launch
+    if (!gs) p.path = NodalSmoothPlan::JACOBI;
+    else if (!lv.has_mask && tune("NODAL_SMALL", 1) != 0 && nodal_small_ok(g, *lv.boxes, lv.nlocal)) p.path = NodalSmoothPlan::SMALL;
+    else if (fused) p.path = gsr ? NodalSmoothPlan::GSR : NodalSmoothPlan::GS4;
+    else p.path = NodalSmoothPlan::COLOUR8;
+    p.images = p.wrap && tune("NODAL_IMAGE_READERS", 1) != 0;
+    p.written_first = p.wrap && gsr && tune("NODAL_SKIP_FILLS", 1) != 0;
+    // (gsr: boxes >= 48 cells -- never the single-workgroup smoother's level; IAMRX_NODAL_ZERO_START = 2: index-wrap levels only)
+    const int zs_mode = (int)tune("NODAL_ZERO_START", 1);
+    p.zero_start = fused && gsr && zs_mode != 0 && (zs_mode != 2 || p.wrap);
+    p.par_fill = tune("NODAL_PARITY_FILL", 1) != 0;
+    // (without the parity fill the exchange in front of the odd pass would read, on the side stream, nodes of the array the interior tiles
+    // write on the main stream: one piece)
+    p.splits = fused && !p.wrap && p.par_fill && nodal_gsr_splits(lv);
+    if (lv.coarsest) p.bottom = nodal_bottom_kind(g, lv);
+    return p;
+}
+
+NodalSmoothPlan nodal_pass_form(const MultiFab& x, const MultiFab& rhs, bool wrap)
+{
+    NodalLevel lv;
+    const Layout& l = *x.layout;
+    for (int d = 0; d < 3; ++d) lv.max_len[d] = l.max_len[d];
+    lv.cor_ngrow = x.ngrow; lv.rhs_ngrow = rhs.ngrow;
+    NodalSmoothPlan p;
+    p.path = nodal_gsr_applies(lv) ? NodalSmoothPlan::GSR : NodalSmoothPlan::GS4;
+    p.wrap = wrap;
+    p.cor_ngrow = x.ngrow; p.rhs_ngrow = rhs.ngrow;
+    return p;
+}
+
+void nodal_gs_fused_pass(const Geometry& g, const NodalSmoothPlan& p, const MultiFab& xc, const MultiFab& xn, MultiFab& xo, const MultiFab& rhs,
+                         const MultiFab& sig, int kpar, const MultiFab* dmask, const double* csig, int zero_flags, int sel, hipStream_t on)
+{
+    const bool wrap = p.wrap;
+    const int refl = p.refl;
+    IAMRX_ASSERT(p.fused() && p.made_for(xc, rhs) && (refl == 0 || wrap) && (p.path != NodalSmoothPlan::GSR || !dmask || dmask->ngrow == xc.ngrow));
     const MultiFab& x = xc;
     if (x.nlocal() == 0) return;
     IAMRX_ASSERT(x.ngrow >= 4 && sig.ngrow >= 4 && rhs.ngrow >= 3 && xn.ngrow == x.ngrow && xo.ngrow == x.ngrow && xo.d_tab != xc.d_tab);
@@ -1148,8 +1213,7 @@ void nodal_gs_fused_pass(const Geometry& g, const MultiFab& xc, const MultiFab& 
     // tile shape: 32x16 nodes / 256 threads (40x24 footprint, 40 KB of LDS: 4 workgroups = 16 waves per CU).  Measured at 256^3
     // on MI355X: 0.151 ms per launch against 0.179 ms for 32x32 / 512 threads (IAMRX_GS4_TILE=1; fewer redundant loads and
     // updates but 8-wave barriers)
-    // levels whose boxes are at least GSR_MIN cells long in x and y: the register-resident kernel (IAMRX_GSR=0: k_nodal_gs4 everywhere)
-    if (nodal_gsr_applies(x, rhs, dmask)) {
+    if (p.path == NodalSmoothPlan::GSR) {
         if (tune("GSR_PB", 4) == 8) gsr_launch<8>(l, g, xc, xn, xo, rhs, sig, kpar, wrap, dmask, csig, zero_flags, refl, sel, on);
         else gsr_launch<4>(l, g, xc, xn, xo, rhs, sig, kpar, wrap, dmask, csig, zero_flags, refl, sel, on);
         return;
@@ -1219,18 +1283,25 @@ __global__ void __launch_bounds__(1024) k_nodal_smooth_small(const FabD* __restr
     }
 }
 
-// returns false if the level does not qualify (then the caller uses the general path)
-bool nodal_smooth_small(const Geometry& g, MultiFab& x, const MultiFab& rhs, const MultiFab& sig, int nsweeps)
+// the level qualifies: one box spanning a fully periodic domain, even lengths, at most 8^3 cells
+static bool nodal_small_ok(const Geometry& g, const std::vector<BoxD>& boxes, int nlocal)
 {
-    const Layout& l = *x.layout;
-    if (l.boxes.size() != 1 || l.nlocal() != 1) return false;
-    const BoxD& b = l.boxes[0];
+    if (boxes.size() != 1 || nlocal != 1) return false;
+    const BoxD& b = boxes[0];
     long cells = 1;
     for (int d = 0; d < 3; ++d) {
         if (!g.periodic[d] || b.lo[d] != g.domain.lo[d] || b.hi[d] != g.domain.hi[d] || (b.len(d) & 1)) return false;
         cells *= b.len(d);
     }
-    if (cells > 8L * 8 * 8) return false;     // measured: one workgroup wins up to 8^3 (13 us/sweep), loses from 32^3 on
+    return cells <= 8L * 8 * 8;     // measured: one workgroup wins up to 8^3 (13 us/sweep), loses from 32^3 on
+}
+
+// returns false if the level does not qualify (NodalSmoothPlan::SMALL: it does)
+bool nodal_smooth_small(const Geometry& g, MultiFab& x, const MultiFab& rhs, const MultiFab& sig, int nsweeps)
+{
+    const Layout& l = *x.layout;
+    if (!nodal_small_ok(g, l.boxes, l.nlocal())) return false;
+    const BoxD& b = l.boxes[0];
     hipLaunchKernelGGL(k_nodal_smooth_small, dim3(1), dim3(1024), 0, Context::get().stream, x.d_tab, rhs.d_tab, sig.d_tab, make_w(g),
                        b.len(0), b.len(1), b.len(2), b.lo[0], b.lo[1], b.lo[2], nsweeps);
     return true;
@@ -1360,11 +1431,11 @@ __global__ void __launch_bounds__(NBOT_NT) k_nodal_bottom(const FabD* __restrict
     }
 }
 
-bool nodal_bottom_device_ok(const Geometry& g, const Layout& l)
+static bool nodal_bottom_boxes_ok(const Geometry& g, const std::vector<BoxD>& boxes)
 {
     const bool enabled = tune("MG_DEVICE_BOTTOM", 1) != 0;
-    if (!enabled || l.boxes.size() != 1) return false;      // global information only: every rank must build the same hierarchy
-    const BoxD& b = l.boxes[0];
+    if (!enabled || boxes.size() != 1) return false;      // global information only: every rank must build the same hierarchy
+    const BoxD& b = boxes[0];
     long cells = 1;
     for (int d = 0; d < 3; ++d) {
         if (!g.periodic[d] || b.lo[d] != g.domain.lo[d] || b.hi[d] != g.domain.hi[d] || b.len(d) < 2) return false;
@@ -1377,7 +1448,7 @@ void nodal_bottom_solve(const Geometry& g, MultiFab& cor, const MultiFab& res, c
                         int nsweeps, int nub, int nuf, int* d_iters)
 {
     const Layout& l = *cor.layout;
-    IAMRX_ASSERT(nodal_bottom_device_ok(g, l));
+    IAMRX_ASSERT(nodal_bottom_boxes_ok(g, l.boxes));
     if (l.nlocal() == 0) return;
     const BoxD& b = l.boxes[0];
     hipLaunchKernelGGL(k_nodal_bottom, dim3(1), dim3(NBOT_NT), 0, Context::get().stream, cor.d_tab, res.d_tab, sig.d_tab, make_w(g),
@@ -1540,10 +1611,10 @@ __global__ void __launch_bounds__(NBG_NT) k_nodal_bottom_g(const FabD* __restric
     }
 }
 
-static bool nbg_geom(const Geometry& g, const Layout& l, NBotGeom& G)
+static bool nbg_geom(const Geometry& g, const std::vector<BoxD>& boxes, NBotGeom& G)
 {
-    if (l.boxes.size() != 1) return false;                      // global information only: every rank must build the same hierarchy
-    const BoxD& b = l.boxes[0];
+    if (boxes.size() != 1) return false;                      // global information only: every rank must build the same hierarchy
+    const BoxD& b = boxes[0];
     long M = 1;
     for (int d = 0; d < 3; ++d) {
         if (b.len(d) < 2 || b.len(d) > 8) return false;
@@ -1556,11 +1627,11 @@ static bool nbg_geom(const Geometry& g, const Layout& l, NBotGeom& G)
     return M <= NBG_NT;
 }
 
-bool nodal_bottom_device_ok_general(const Geometry& g, const Layout& l)
+static bool nodal_bottom_boxes_ok_general(const Geometry& g, const std::vector<BoxD>& boxes)
 {
     const bool enabled = tune("MG_DEVICE_BOTTOM", 1) != 0 && tune("MG_DEVICE_BOTTOM_GENERAL", 1) != 0;
     NBotGeom G;
-    return enabled && nbg_geom(g, l, G);
+    return enabled && nbg_geom(g, boxes, G);
 }
 
 void nodal_bottom_solve_general(const Geometry& g, MultiFab& cor, const MultiFab& res, const MultiFab& sig, const MultiFab* dmask, bool singular,
@@ -1568,7 +1639,7 @@ void nodal_bottom_solve_general(const Geometry& g, MultiFab& cor, const MultiFab
 {
     const Layout& l = *cor.layout;
     NBotGeom G;
-    IAMRX_ASSERT(nbg_geom(g, l, G) && sig.ngrow >= 1);
+    IAMRX_ASSERT(nbg_geom(g, l.boxes, G) && sig.ngrow >= 1);
     if (l.nlocal() == 0) return;
     double cnt = 1.0;
     for (int d = 0; d < 3; ++d) cnt *= (double)g.domain.len(d);

@@ -215,18 +215,57 @@ struct NodalImages { bool on = false; int refl = 0; };
 bool nodal_residual(const Geometry& g, MultiFab& out, const MultiFab& x, const MultiFab& sig, const MultiFab* rhs, double* norm_out = nullptr,
                     const NodalImages& img = NodalImages());
 void nodal_gs_color(const Geometry& g, MultiFab& x, const MultiFab& rhs, const MultiFab& sig, int color, const MultiFab* dmask = nullptr);
+// ---- the smoother and bottom path of a nodal multigrid level ----
+// What the choice rests on, as host data (no array, no device).  boxes is the level's GLOBAL box list; max_len / nlocal: Layout's (max_len
+// is the largest LOCAL extent).  has_mask: the level has a Dirichlet mask, as wide as the correction.
+struct NodalLevel {
+    const std::vector<BoxD>* boxes = nullptr;
+    int nlocal = 0, max_len[3] = {0, 0, 0};
+    const DomainBC* bc = nullptr;
+    int cor_ngrow = 0, rhs_ngrow = 0;                      // ghost widths: correction, right-hand side (the level's residual)
+    bool has_mask = false;
+    int nodal_smoother = 0, bottom_smoother_only = 0, device_bottom = 1, nodal_sweeps = 2;      // MGOpts
+    bool coarsest = false;
+};
+struct NodalSmoothPlan {
+    // JACOBI; COLOUR8: eight colour passes, each behind a ghost fill; SMALL: every sweep of the call in one single-workgroup launch
+    // (k_nodal_smooth_small); GS4 / GSR: two plane-fused passes per sweep (k_nodal_gs4 / the register-resident k_nodal_gsr)
+    enum Path { JACOBI, COLOUR8, SMALL, GS4, GSR } path = COLOUR8;
+    // how the coarsest level is solved (NONE: not the coarsest): nuf smoothing calls; k_nodal_bottom (fully periodic); k_nodal_bottom_g
+    // (walls / Dirichlet mask / refined patch); BiCGStab driven from the host
+    enum Bottom { NONE, SMOOTHER_ONLY, DEVICE_PERIODIC, DEVICE_GENERAL, HOST_KRYLOV } bottom = NONE;
+    int ngrow = 1;                // what the correction, the residual, sigma and the mask are allocated with (4: the fused passes recompute their halo)
+    bool wrap = false;            // one box spanning its domain, no Dirichlet nodes: the fused passes read images instead of ghost nodes -- periodic
+    int refl = 0;                 // ones, or mirror images about Neumann walls in the directions of refl (bit d); no ghost fill in front of a pass
+    bool images = false;          // ... and so do the residual and the restriction: no ghost fill inside a cycle (NodalImages)
+    bool written_first = false;   // every array of the level is written before it is read: no zero fill behind the allocation
+    bool zero_start = false;      // the first sweep of a call on a zero correction is told so instead of the correction being set to zero
+    bool par_fill = false;        // in front of a pass, only the ghost nodes of the planes of the parity it reads are refreshed
+    bool splits = false;          // GSR: a pass behind a ghost fill can be issued in two parts (tiles that read no ghost node / the others)
+    int sweeps = 2;               // Gauss-Seidel sweeps (Jacobi steps) per smoothing call
+    int cor_ngrow = 0, rhs_ngrow = 0;      // what the plan was made for (the launchers assert it)
+    bool fused() const { return path == GS4 || path == GSR; }
+    static bool on_device(Bottom b) { return b == DEVICE_PERIODIC || b == DEVICE_GENERAL; }       // single-workgroup launch, no host synchronisation
+    NodalImages img() const { return NodalImages{images, images ? refl : 0}; }
+    bool made_for(const MultiFab& x, const MultiFab& rhs) const { return x.ngrow == cor_ngrow && rhs.ngrow == rhs_ngrow; }
+};
+// THE decision: how a smoothing call and the bottom solve run on this level, made once per level per solve
+NodalSmoothPlan nodal_smooth_plan(const Geometry& g, const NodalLevel& lv);
+// the ghost width every plan asks for (IAMRX_NODAL_FUSED), before a level's arrays and mask exist
+int nodal_plan_ngrow();
+// the bottom part alone (what the plan of a coarsest level says): the hierarchy stops coarsening at the first level whose kind, without a
+// mask, is a device kind
+NodalSmoothPlan::Bottom nodal_bottom_kind(const Geometry& g, const NodalLevel& lv);
+// the fused-pass part alone (GS4 or GSR), for a caller that fills the ghost nodes itself or vouches for the index wrap
+NodalSmoothPlan nodal_pass_form(const MultiFab& x, const MultiFab& rhs, bool wrap = false);
 // one k-parity pass of the plane-fused 8-colour GS (arrays need ngrow >= 4 / 3), out of place: plane k from xc, planes
-// k+-1 from xn, result to xo (xo != xc; xn may be either)
-void nodal_gs_fused_pass(const Geometry& g, const MultiFab& xc, const MultiFab& xn, MultiFab& xo, const MultiFab& rhs, const MultiFab& sig, int kpar,
-                         bool wrap = false, const MultiFab* dmask = nullptr, const double* csig = nullptr, int zero_flags = 0, int refl = 0,
+// k+-1 from xn, result to xo (xo != xc; xn may be either).  p: the level's plan (GS4 / GSR, wrap, refl).  zero_flags (GSR only): bit 0: xc,
+// bit 1: xn is identically zero and is not read
+// sel (GSR only): 1 = the tiles that read no ghost node of x (footprint and planes inside the box), 2 = the others, 0 = all; on: the
+// stream of the launch (null: the context's)
+void nodal_gs_fused_pass(const Geometry& g, const NodalSmoothPlan& p, const MultiFab& xc, const MultiFab& xn, MultiFab& xo, const MultiFab& rhs,
+                         const MultiFab& sig, int kpar, const MultiFab* dmask = nullptr, const double* csig = nullptr, int zero_flags = 0,
                          int sel = 0, hipStream_t on = nullptr);
-// sel (k_nodal_gsr only): 1 = the tiles that read no ghost node of x (footprint and planes inside the box), 2 = the others, 0 = all; on: the
-// stream of the launch (null: the context's).  nodal_gsr_splits: the level has tiles of the first kind
-bool nodal_gsr_splits(const MultiFab& x, const MultiFab& rhs, const MultiFab* dmask);
-// (wrap: one box spanning its domain, images instead of ghost nodes -- periodic ones, or mirror images in the directions of refl (bit d):
-// nodal_wrap_or_reflect_ok)
-// k_nodal_gsr takes the level: then zero_flags (bit 0: xc, bit 1: xn is identically zero and is not read) may be passed
-bool nodal_gsr_applies(const MultiFab& x, const MultiFab& rhs, const MultiFab* dmask);
 void nodal_zero_masked(MultiFab& mf, const MultiFab& dmask);
 void nodal_build_dmask(const Geometry& g, MultiFab& dm, const MultiFab& cov, const DomainBC& bc);
 bool periodic_wrap_ok(const Geometry& g, const Layout& l, int min_len);

@@ -250,9 +250,10 @@ public:
     const MultiFab* dmask(int l) const { return m_lev[l].dmask(); }
     const MultiFab& sigma(int l) const { return m_lev[l].sig; }
     const Geometry& geom(int l) const { return m_lev[l].g; }
-    // x_is_zero: x is to be taken as zero whatever it holds (the first smooth call on a correction); the call leaves x fully defined
-    // leave_ghosts: the caller reads no ghost node of x afterwards (the fill behind the last sweep is skipped); x_filled: x comes straight from smooth()
-    void smooth(int l, MultiFab& x, const MultiFab& rhs, bool x_is_zero = false, bool leave_ghosts = false);
+    // one smoothing call on the level's correction cor(l) with its residual res(l) as right-hand side, along the level's plan
+    // x_is_zero: cor is to be taken as zero whatever it holds (the first smooth call on a correction); the call leaves it fully defined
+    // leave_ghosts: the caller reads no ghost node of cor afterwards (the fill behind the last sweep is skipped); x_filled: x comes straight from smooth()
+    void smooth(int l, bool x_is_zero = false, bool leave_ghosts = false);
     void residual(int l, MultiFab& r, MultiFab& x, const MultiFab& b, double* norm = nullptr, bool x_filled = false);   // norm: max norm of r (by the residual launch itself where it can)
     void vcycle(MGStats& st);
     // one V-cycle for the residual equation A e = r, zero initial guess; e is zero on Dirichlet nodes, its ghost nodes are filled.
@@ -270,10 +271,11 @@ private:
         MultiFab xb;               // second buffer of the out-of-place fused Gauss-Seidel sweeps
         MultiFab dm;               // Dirichlet node mask (defined only if the level has Dirichlet nodes, see NodalMG ctor)
         const MultiFab* dmask() const { return dm.defined() ? &dm : nullptr; }
-        NodalImages img;           // the level's residual and restriction read images instead of ghost nodes (NodalMG ctor): no ghost fills inside a cycle
+        NodalSmoothPlan plan;      // how a smoothing call and the bottom solve run on the level (nodal_smooth_plan; NodalMG ctor, once the masks exist)
+        bool overlap = false;      // plan.splits and IAMRX_HALO_OVERLAP: a pass behind a ghost fill is issued in two parts around the exchange
     };
+    NodalLevel describe(const Level& L, bool coarsest, bool has_mask, int ng) const;
     int bicgstab(int l, MultiFab& sol, const MultiFab& rhs, double eps_rel, double eps_abs, int& niters);
-    bool bottom_on_device();     // the coarsest level is solved by k_nodal_bottom (single-workgroup launch, no host synchronisation)
     void subtract_mean(int l, MultiFab& mf);
     void fillbc(int l, MultiFab& x, int kpar = -1, hipStream_t on = nullptr);   // kpar = 0 / 1: refresh the ghost nodes of the z-planes of that parity only
     Geometry m_g;

@@ -13,15 +13,8 @@ namespace iamrx {
 // kernels (k_nodal.hip)
 void nodal_interp_add(MultiFab& fine, const MultiFab& crse, const MultiFab& sig_fine);
 
-// plane-fused sweep (2 launches + 2 fills instead of 8 + 8): measured per sweep on MI355X 0.69 vs 0.79 ms at 256^3,
-// 0.11 vs 0.20 ms at 128^3, 0.03 vs 0.09 ms at <= 64^3.  IAMRX_NODAL_FUSED=0 selects the 8 colour passes.
-static bool nodal_fused() { return tune("NODAL_FUSED", 1) != 0; }
-static bool nodal_small() { return tune("NODAL_SMALL", 1) != 0; }
-bool nodal_smooth_small(const Geometry& g, MultiFab& x, const MultiFab& rhs, const MultiFab& sig, int nsweeps);
-bool nodal_bottom_device_ok(const Geometry& g, const Layout& l);
 void nodal_bottom_solve(const Geometry& g, MultiFab& cor, const MultiFab& res, const MultiFab& sig, bool singular, double eps_rel, int maxiter,
                         int nsweeps, int nub, int nuf, int* d_iters);
-bool nodal_bottom_device_ok_general(const Geometry& g, const Layout& l);
 void nodal_bottom_solve_general(const Geometry& g, MultiFab& cor, const MultiFab& res, const MultiFab& sig, const MultiFab* dmask, bool singular,
                                 double eps_rel, int maxiter, int nsweeps, int nub, int nuf, int* d_iters);
 // unique nodes of a level: the unknowns behind the Krylov iteration cap (krylov_maxiter)
@@ -51,9 +44,9 @@ NodalMG::NodalMG(const Geometry& g, LayoutP layout, const DomainBC& bc_in, const
     m_lev[0].layout = std::move(layout);
     while ((int)m_lev.size() <= m_o.max_coarsening_level) {
         Level& f = m_lev.back();
-        // a fully periodic single box of at most 8^3 cells is solved by the single-workgroup device bottom solver (k_nodal_bottom)
-        if (m_o.device_bottom && m_o.nodal_smoother == 0 && !m_o.bottom_smoother_only &&
-            (nodal_bottom_device_ok(f.g, *f.layout) || nodal_bottom_device_ok_general(f.g, *f.layout))) break;
+        // a single box of at most 8^3 cells is solved by a single-workgroup device bottom solver (k_nodal_bottom / k_nodal_bottom_g): the
+        // coarsest level (the Dirichlet masks do not exist yet: the kind without one)
+        if (NodalSmoothPlan::on_device(nodal_bottom_kind(f.g, describe(f, true, false, 0)))) break;
         Level c;
         if (!mg_coarsen_level(f, m_o, c)) break;     // (mlmg.hip: isotropic, slab or agglomerated level)
         m_lev.push_back(std::move(c));
@@ -63,28 +56,15 @@ NodalMG::NodalMG(const Geometry& g, LayoutP layout, const DomainBC& bc_in, const
     bool need_mask = false;
     for (int d = 0; d < 3; ++d) if (!g.periodic[d] && (bc.lo[d] == lo_dirichlet || bc.hi[d] == lo_dirichlet)) need_mask = true;
     if (m_lev[0].layout->total_cells() != g.domain.npts()) need_mask = true;
+    // (4 ghost layers where the plane-fused Gauss-Seidel is on: it recomputes its halo instead of exchanging it per colour)
+    const int ng = nodal_plan_ngrow();
     for (auto& L : m_lev) {
         if (L.agg) L.tmp_d.define(L.dist, node_type(), 1, 1);
         if (L.slab) L.vres.define(L.virt, node_type(), 1, 0);
-        // 4 ghost layers: the plane-fused Gauss-Seidel recomputes its halo instead of exchanging it per colour
-        const int ng = nodal_fused() ? 4 : 1;
         L.sig.define(L.layout, cell_type(), 1, ng);
         L.cor.define(L.layout, node_type(), 1, ng);
         L.res.define(L.layout, node_type(), 1, ng);
         L.rescor.define(L.layout, node_type(), 1, 1);
-        // The zero fills below give a value to what nobody writes: ghost cells beyond a coarse/fine boundary (setSigma fills valid cells,
-        // neighbours / periodic images and wall mirrors; the prolongation forms sigma-weighted averages at the masked boundary nodes before
-        // they are zeroed: keep them finite) and ghost nodes outside the level.  A level without Dirichlet nodes that is one box spanning
-        // its domain (smooth(): `wrap`) and goes to k_nodal_gsr has neither: its kernels read valid data and the ghost layers fillbc /
-        // setSigma fill completely; sig and res are written (copy / residual / restriction) before they are read, rescor by the residual,
-        // and cor starts from zero inside the first sweep or is zeroed by smooth() / vcycle().  There the four fills are skipped
-        // (IAMRX_NODAL_SKIP_FILLS; IAMRX_POISON_ALLOC = 1 / 2 must not change a result).
-        int refl = 0;
-        const bool written_first = tune("NODAL_SKIP_FILLS", 1) != 0 && !need_mask && m_o.nodal_smoother == 0 && nodal_fused() &&
-                                   nodal_wrap_or_reflect_ok(L.g, *L.layout, m_bc, 4, &refl) && nodal_gsr_applies(L.cor, L.res, nullptr);
-        if (written_first) continue;
-        L.sig.setVal(0.0);
-        L.cor.setVal(0.0); L.res.setVal(0.0); L.rescor.setVal(0.0);
     }
     for (auto& L : m_lev) {
         if (!need_mask) break;
@@ -92,7 +72,6 @@ NodalMG::NodalMG(const Geometry& g, LayoutP layout, const DomainBC& bc_in, const
         cov.setVal(0.0);
         mf_add_scalar(cov, 1.0, 0, 1, 0);
         cov.FillBoundary(L.g);
-        const int ng = L.cor.ngrow;
         L.dm.define(L.layout, node_type(), 1, ng);
         L.dm.setVal(1.0);                                  // ghost nodes outside the level: never updated
         nodal_build_dmask(L.g, L.dm, cov, m_bc);
@@ -107,15 +86,49 @@ NodalMG::NodalMG(const Geometry& g, LayoutP layout, const DomainBC& bc_in, const
         m_singular = false;
         for (auto& L : m_lev) IAMRX_ASSERT(L.dm.defined());
     }
-    // Image readers (IAMRX_NODAL_IMAGE_READERS, 1; 0: every fill below and the ghost-reading kernels): on a level the smoothers take with
-    // index wrap / reflection (smooth(): `wrap` -- one box spanning its domain, no Dirichlet nodes) the residual and the restriction read the
-    // images of the nodes outside the box from the valid nodes as well, so nobody reads a ghost node of cor, xb, rescor or res inside a
-    // cycle and the fills behind the smoothing calls and in front of the residual, the restriction and the interpolation are not issued.
-    const bool img_on = tune("NODAL_IMAGE_READERS", 1) != 0 && m_o.nodal_smoother == 0 && nodal_fused();
+    const int ov_mode = (int)tune("HALO_OVERLAP", 1);
     for (auto& L : m_lev) {
-        L.img.on = img_on && !L.dmask() && nodal_wrap_or_reflect_ok(L.g, *L.layout, m_bc, 4, &L.img.refl);
-        if (!L.img.on) L.img.refl = 0;
+        // how the level is smoothed and -- the coarsest -- solved: decided here, once the masks exist (kernels.h)
+        L.plan = nodal_smooth_plan(L.g, describe(L, &L == &m_lev.back(), L.dm.defined(), ng));
+        const NodalSmoothPlan& p = L.plan;
+        IAMRX_ASSERT(p.ngrow == ng && p.made_for(L.cor, L.res));
+        // Overlap (IAMRX_HALO_OVERLAP as for the cell-centred sweep, CellMG::smooth_n; round 6): a pass of k_nodal_gsr whose ghost nodes have
+        // to be refreshed first is issued in two parts -- the tiles whose footprint and planes lie inside their box on the main stream; the
+        // exchange, the wall reflection and the remaining tiles on the context's side stream behind a fork -- and joined: the messages
+        // travel while the interior tiles run.  The two parts write disjoint nodes; the same doubles as the one-piece pass.
+        if (p.splits && ov_mode != 0) {
+            const int ngv[3] = {ng, ng, 1};
+            // (the plans are built and uploaded here, in front of any fork)
+            bool peers = false;
+            for (int kp = -1; kp <= 1; ++kp) peers = !fill_boundary_plan(*L.layout, node_type(), ng, L.g, ngv, kp).peers.empty() || peers;
+            L.overlap = ov_mode == 2 || peers;
+        }
+        // The zero fills below give a value to what nobody writes: ghost cells beyond a coarse/fine boundary (setSigma fills valid cells,
+        // neighbours / periodic images and wall mirrors; the prolongation forms sigma-weighted averages at the masked boundary nodes before
+        // they are zeroed: keep them finite) and ghost nodes outside the level.  A level without Dirichlet nodes that is one box spanning
+        // its domain (plan.wrap) and goes to k_nodal_gsr has neither: its kernels read valid data and the ghost layers fillbc /
+        // setSigma fill completely; sig and res are written (copy / residual / restriction) before they are read, rescor by the residual,
+        // and cor starts from zero inside the first sweep or is zeroed by smooth() / vcycle().  There the four fills are skipped
+        // (plan.written_first, IAMRX_NODAL_SKIP_FILLS; IAMRX_POISON_ALLOC = 1 / 2 must not change a result).
+        if (p.written_first) continue;
+        L.sig.setVal(0.0);
+        L.cor.setVal(0.0); L.res.setVal(0.0); L.rescor.setVal(0.0);
     }
+}
+
+// the level as nodal_smooth_plan / nodal_bottom_kind see it
+NodalLevel NodalMG::describe(const Level& L, bool coarsest, bool has_mask, int ng) const
+{
+    NodalLevel lv;
+    lv.boxes = &L.layout->boxes; lv.nlocal = L.layout->nlocal();
+    for (int d = 0; d < 3; ++d) lv.max_len[d] = L.layout->max_len[d];
+    lv.bc = &m_bc;
+    lv.cor_ngrow = lv.rhs_ngrow = ng;
+    lv.has_mask = has_mask;
+    lv.nodal_smoother = m_o.nodal_smoother; lv.bottom_smoother_only = m_o.bottom_smoother_only; lv.device_bottom = m_o.device_bottom;
+    lv.nodal_sweeps = m_o.nodal_sweeps;
+    lv.coarsest = coarsest;
+    return lv;
 }
 
 void NodalMG::setSigma(const MultiFab& sig, int comp)
@@ -159,87 +172,67 @@ void NodalMG::fillbc(int l, MultiFab& x, int kpar, hipStream_t on)
     nodal_reflect_bc(m_lev[l].g, x, m_bc, on);
 }
 
-void NodalMG::smooth(int l, MultiFab& x, const MultiFab& rhs, bool x_is_zero, bool leave_ghosts)
+// one smoothing call (plan.sweeps sweeps) on the level's correction with its residual as right-hand side, as the level's plan says
+void NodalMG::smooth(int l, bool x_is_zero, bool leave_ghosts)
 {
     Level& L = m_lev[l];
-    // a correction that starts from zero: on a level the register-resident kernel smooths with index wrap (no ghost nodes are read) the
-    // first sweep is told so and reads no x -- the zero fill and a third of the first sweep's traffic; everywhere else x is zeroed here
-    // (with index wrap or on ghost-filled boxes, with or without a Dirichlet mask: the ghost nodes of a zero array are zero as well --
-    // images, reflections at walls -- so the fill in front of the first pass goes too; IAMRX_NODAL_ZERO_START = 2: index-wrap levels only)
-    const int zs_mode = (int)tune("NODAL_ZERO_START", 1);
-    int zs_refl = 0;
-    const bool zero_start = x_is_zero && m_o.nodal_smoother == 0 && nodal_fused() && zs_mode != 0 && nodal_gsr_applies(x, rhs, L.dmask()) &&
-                            (zs_mode != 2 || (!L.dmask() && nodal_wrap_or_reflect_ok(L.g, *L.layout, m_bc, 4, &zs_refl)));       // (gsr_applies: boxes >= 48 cells -- never the single-workgroup smoother's level)
-    if (x_is_zero && !zero_start) x.setVal(0.0);
-    // small single-box periodic levels: all sweeps x colours in one single-workgroup launch
+    const NodalSmoothPlan& p = L.plan;
+    MultiFab& x = L.cor;
+    const MultiFab& rhs = L.res;
     const MultiFab* dmk = L.dmask();
-    if (!dmk && m_o.nodal_smoother == 0 && nodal_small() && nodal_smooth_small(L.g, x, rhs, L.sig, m_o.nodal_sweeps)) {
-        if (!L.img.on) fillbc(l, x);          // (the kernel writes the periodic duplicates itself)
+    // a correction that starts from zero: on a level the register-resident kernel smooths (plan.zero_start) the first sweep is told so and
+    // reads no x -- the zero fill and a third of the first sweep's traffic; everywhere else x is zeroed here (with index wrap or on
+    // ghost-filled boxes, with or without a Dirichlet mask: the ghost nodes of a zero array are zero as well -- images, reflections at
+    // walls -- so the fill in front of the first pass goes too)
+    const bool zero_start = x_is_zero && p.zero_start;
+    if (x_is_zero && !zero_start) x.setVal(0.0);
+    if (p.path == NodalSmoothPlan::SMALL) {
+        const bool took = nodal_smooth_small(L.g, x, rhs, L.sig, p.sweeps);
+        IAMRX_ASSERT(took);
+        if (!p.images) fillbc(l, x);          // (the kernel writes the periodic duplicates itself)
         return;
     }
-    if (m_o.nodal_smoother == 0 && nodal_fused()) {
+    if (p.fused()) {
         // colours 0-3 (k even) in one pass, colours 4-7 (k odd) in a second one: identical arithmetic to the eight
         // sequential colour passes below.  Each sweep goes from one buffer to the other (see k_nodal_gs4).
-        if (!L.xb.defined() || L.xb.ngrow != x.ngrow) L.xb.define(L.layout, node_type(), 1, x.ngrow);
-        // one box spanning a fully periodic domain: the kernel takes periodic images from the valid data, no ghost fills
-        // ... or a domain whose non-periodic directions end on Neumann walls: mirror images in those directions (k_nodal.hip image_node)
-        int refl = 0;
-        const bool wrap = !dmk && nodal_wrap_or_reflect_ok(L.g, *L.layout, m_bc, 4, &refl);
-        if (!wrap) {
-            // the right-hand side of the level's smooth calls is its residual array, unchanged within a V-cycle: fill its ghosts once
-            if (&rhs == &L.res) { if (!L.res_filled) { fillbc(l, L.res); L.res_filled = true; } }
-            else fillbc(l, const_cast<MultiFab&>(rhs));
-        }
+        if (!L.xb.defined()) L.xb.define(L.layout, node_type(), 1, x.ngrow);
+        // the right-hand side is unchanged within a V-cycle: fill its ghosts once (plan.wrap: the kernel takes images from the valid data)
+        if (!p.wrap && !L.res_filled) { fillbc(l, L.res); L.res_filled = true; }
         MultiFab* a = &x;
         MultiFab* b = &L.xb;
         // Ghost traffic: the even pass changes even planes only and reads the odd planes next to them, the odd pass the reverse.
         // After the first (full) fill it is therefore enough to refresh the ghost nodes of the planes of ONE parity in front of each
-        // pass: the odd planes before the even pass, the even planes before the odd pass (half the halo volume; on boxes stacked in
-        // z, where one ghost plane is exchanged, every second message disappears).
-        const bool par_fill = tune("NODAL_PARITY_FILL", 1) != 0;
-        // Overlap (IAMRX_HALO_OVERLAP as for the cell-centred sweep, CellMG::smooth_n; round 6): a pass of k_nodal_gsr whose ghost nodes have
-        // to be refreshed first is issued in two parts -- the tiles whose footprint and planes lie inside their box on the main stream; the
-        // exchange, the wall reflection and the remaining tiles on the context's side stream behind a fork -- and joined: the messages
-        // travel while the interior tiles run.  The two parts write disjoint nodes; the same doubles as the one-piece pass.
+        // pass (plan.par_fill): the odd planes before the even pass, the even planes before the odd pass (half the halo volume; on boxes
+        // stacked in z, where one ghost plane is exchanged, every second message disappears).
         auto& ctx = Context::get();
-        const int ov_mode = (int)tune("HALO_OVERLAP", 1);
-        bool overlap = false;
-        if (!wrap && ov_mode != 0 && nodal_gsr_splits(x, rhs, dmk)) {
-            const int ngv[3] = {x.ngrow, x.ngrow, 1};
-            // (the plans are built and uploaded in front of any fork)
-            bool peers = false;
-            for (int kp = -1; kp <= 1; ++kp) peers = !fill_boundary_plan(*L.layout, node_type(), x.ngrow, L.g, ngv, kp).peers.empty() || peers;
-            overlap = ov_mode == 2 || peers;
-        }
         auto pass = [&](MultiFab& filled, int fill_kpar, bool do_fill, const MultiFab& xc_, const MultiFab& xn_, MultiFab& xo_, int kpar, int zf) {
             const double* cs = m_csig ? &m_csig_val : nullptr;
-            if (do_fill && overlap) {
+            if (do_fill && L.overlap) {          // in two parts around the exchange (NodalMG ctor)
                 ctx.fork_side();
-                nodal_gs_fused_pass(L.g, xc_, xn_, xo_, rhs, L.sig, kpar, wrap, dmk, cs, zf, refl, 1, ctx.stream);
+                nodal_gs_fused_pass(L.g, p, xc_, xn_, xo_, rhs, L.sig, kpar, dmk, cs, zf, 1, ctx.stream);
                 fillbc(l, filled, fill_kpar, ctx.side);
-                nodal_gs_fused_pass(L.g, xc_, xn_, xo_, rhs, L.sig, kpar, wrap, dmk, cs, zf, refl, 2, ctx.side);
+                nodal_gs_fused_pass(L.g, p, xc_, xn_, xo_, rhs, L.sig, kpar, dmk, cs, zf, 2, ctx.side);
                 ctx.join_side();
                 return;
             }
             if (do_fill) fillbc(l, filled, fill_kpar);
-            nodal_gs_fused_pass(L.g, xc_, xn_, xo_, rhs, L.sig, kpar, wrap, dmk, cs, zf, refl);
+            nodal_gs_fused_pass(L.g, p, xc_, xn_, xo_, rhs, L.sig, kpar, dmk, cs, zf);
         };
-        for (int ns = 0; ns < m_o.nodal_sweeps; ++ns) {
+        for (int ns = 0; ns < p.sweeps; ++ns) {
             const bool z = zero_start && ns == 0;
             // even planes: a -> b (ghost nodes of a refreshed first: all planes in front of the first sweep, then the odd ones)
-            pass(*a, (ns == 0 || !par_fill) ? -1 : 1, !wrap && !z, *a, *a, *b, 0, z ? 3 : 0);
+            pass(*a, (ns == 0 || !p.par_fill) ? -1 : 1, !p.wrap && !z, *a, *a, *b, 0, z ? 3 : 0);
             // odd planes: centre from a, neighbours from b (the ghost images of b's new even planes first)
-            pass(*b, par_fill ? 0 : -1, !wrap, *a, *b, *b, 1, z ? 1 : 0);
+            pass(*b, p.par_fill ? 0 : -1, !p.wrap, *a, *b, *b, 1, z ? 1 : 0);
             std::swap(a, b);
         }
         if (a != &x) MultiFab::Copy(x, *a, 0, 0, 1, 0);
         // (a level of image readers: every later reader of x takes images; without index wrap each pass above fills what it reads)
-        if (!leave_ghosts && !L.img.on) fillbc(l, x);
+        if (!leave_ghosts && !p.images) fillbc(l, x);
         return;
     }
-    for (int ns = 0; ns < m_o.nodal_sweeps; ++ns) {
-        if (false) {
-        } else if (m_o.nodal_smoother == 0) {
+    for (int ns = 0; ns < p.sweeps; ++ns) {
+        if (p.path == NodalSmoothPlan::COLOUR8) {
             for (int color = 0; color < 8; ++color) {
                 fillbc(l, x);
                 nodal_gs_color(L.g, x, rhs, L.sig, color, dmk);
@@ -256,7 +249,7 @@ void NodalMG::smooth(int l, MultiFab& x, const MultiFab& rhs, bool x_is_zero, bo
 
 void NodalMG::residual(int l, MultiFab& r, MultiFab& x, const MultiFab& b, double* norm, bool x_filled)
 {
-    const NodalImages& img = m_lev[l].img;
+    const NodalImages img = m_lev[l].plan.img();
     if (!x_filled && !img.on) fillbc(l, x);
     const bool masked = (bool)m_lev[l].dmask();
     const bool have = nodal_residual(m_lev[l].g, r, x, m_lev[l].sig, &b, (norm && !masked) ? norm : nullptr, img);
@@ -286,23 +279,16 @@ int NodalMG::bicgstab(int l, MultiFab& sol, const MultiFab& rhs, double eps_rel,
                            }, niters);
 }
 
-bool NodalMG::bottom_on_device()
-{
-    Level& B = m_lev.back();
-    if (!(m_o.device_bottom && m_o.nodal_smoother == 0 && !m_o.bottom_smoother_only)) return false;
-    return (!B.dmask() && nodal_bottom_device_ok(B.g, *B.layout)) || nodal_bottom_device_ok_general(B.g, *B.layout);
-}
-
 void NodalMG::vcycle(MGStats& st)
 {
     const int nl = (int)m_lev.size();
     for (int l = 0; l < nl - 1; ++l) {
         Level& L = m_lev[l];
         if (m_o.nodal_nu1 <= 0) L.cor.setVal(0.0);
-        for (int i = 0; i < m_o.nodal_nu1; ++i) smooth(l, L.cor, L.res, i == 0);
+        for (int i = 0; i < m_o.nodal_nu1; ++i) smooth(l, i == 0);
         residual(l, L.rescor, L.cor, L.res, nullptr, m_o.nodal_nu1 > 0);          // (smooth() has just filled the ghost nodes, or the level reads images: no fill)
         Level& C = m_lev[l + 1];
-        const NodalImages rimg = (!C.slab && !C.agg) ? L.img : NodalImages();
+        const NodalImages rimg = (!C.slab && !C.agg) ? L.plan.img() : NodalImages();
         if (!rimg.on) fillbc(l, L.rescor);
         mg_restrict_to(C, C.res, C.tmp_d, C.vres, [&](MultiFab& target) { nodal_restrict(target, L.rescor, rimg); });
         m_lev[l + 1].res_filled = false;
@@ -312,17 +298,20 @@ void NodalMG::vcycle(MGStats& st)
         const int l = nl - 1;
         Level& B = m_lev[l];
         B.cor.setVal(0.0);
-        if (m_o.bottom_smoother_only) {
-            for (int i = 0; i < m_o.nuf; ++i) smooth(l, B.cor, B.res);
-        } else if (bottom_on_device()) {
-            const int maxiter = krylov_maxiter(m_o.bottom_maxiter, nodal_unknowns(B.g));
-            if (!B.dmask() && nodal_bottom_device_ok(B.g, *B.layout))           // fully periodic: the wrap-only kernel
-                nodal_bottom_solve(B.g, B.cor, B.res, B.sig, m_singular, m_o.bottom_reltol, maxiter, m_o.nodal_sweeps, m_o.nub, m_o.nuf,
-                                   mg_bottom_iters_dev());
-            else                                                                // walls / Dirichlet mask / refined patch
-                nodal_bottom_solve_general(B.g, B.cor, B.res, B.sig, B.dmask(), m_singular, m_o.bottom_reltol, maxiter, m_o.nodal_sweeps, m_o.nub,
-                                           m_o.nuf, mg_bottom_iters_dev());
-        } else {
+        const int maxiter = krylov_maxiter(m_o.bottom_maxiter, nodal_unknowns(B.g));
+        switch (B.plan.bottom) {
+        case NodalSmoothPlan::SMOOTHER_ONLY:
+            for (int i = 0; i < m_o.nuf; ++i) smooth(l);
+            break;
+        case NodalSmoothPlan::DEVICE_PERIODIC:          // fully periodic: the wrap-only kernel
+            nodal_bottom_solve(B.g, B.cor, B.res, B.sig, m_singular, m_o.bottom_reltol, maxiter, m_o.nodal_sweeps, m_o.nub, m_o.nuf,
+                               mg_bottom_iters_dev());
+            break;
+        case NodalSmoothPlan::DEVICE_GENERAL:           // walls / Dirichlet mask / refined patch
+            nodal_bottom_solve_general(B.g, B.cor, B.res, B.sig, B.dmask(), m_singular, m_o.bottom_reltol, maxiter, m_o.nodal_sweeps, m_o.nub,
+                                       m_o.nuf, mg_bottom_iters_dev());
+            break;
+        default: {
             MultiFab rb(B.layout, node_type(), 1, 0);
             MultiFab::Copy(rb, B.res, 0, 0, 1, 0);
             if (m_singular) subtract_mean(l, rb);
@@ -331,21 +320,22 @@ void NodalMG::vcycle(MGStats& st)
             st.bottom_iters_total += nit;
             if (ret != 0) {
                 B.cor.setVal(0.0);
-                for (int i = 0; i < m_o.nuf; ++i) smooth(l, B.cor, B.res);
+                for (int i = 0; i < m_o.nuf; ++i) smooth(l);
             }
             const int nn = ret == 0 ? m_o.nub : m_o.nuf;
-            for (int i = 0; i < nn; ++i) smooth(l, B.cor, B.res);
+            for (int i = 0; i < nn; ++i) smooth(l);
+        }
         }
     }
     for (int l = nl - 2; l >= 0; --l) {
         Level& L = m_lev[l];
         // (a level that was smoothed on the way up comes with its ghost nodes filled; the bottom level comes from its solver)
         // (the interpolation reads valid coarse nodes only, periodic duplicates included: the smoothers and the bottom kernels write them)
-        if ((l + 1 == nl - 1 || m_o.nodal_nu2 <= 0) && !m_lev[l + 1].img.on) fillbc(l + 1, m_lev[l + 1].cor);
+        if ((l + 1 == nl - 1 || m_o.nodal_nu2 <= 0) && !m_lev[l + 1].plan.images) fillbc(l + 1, m_lev[l + 1].cor);
         nodal_interp_add(L.cor, mg_correction_of(m_lev[l + 1], m_lev[l + 1].cor, 1), L.sig);
         if (L.dmask()) nodal_zero_masked(L.cor, L.dm);                  // mlndlap_interpadd: Dirichlet nodes take no correction
         // the finest level's correction is added to the solution node by node: nobody reads its ghost nodes
-        for (int i = 0; i < m_o.nodal_nu2; ++i) smooth(l, L.cor, L.res, false, l == 0 && i == m_o.nodal_nu2 - 1);
+        for (int i = 0; i < m_o.nodal_nu2; ++i) smooth(l, false, l == 0 && i == m_o.nodal_nu2 - 1);
     }
 }
 
@@ -402,11 +392,11 @@ MGStats NodalMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, doubl
     if (!std::isfinite(max_norm)) throw Error("iamrx nodal MLMG: the right-hand side or the initial residual is not finite");
     const double res_target = std::max(atol, std::max(rtol, 1.e-16) * max_norm);
     st.resnorm = st.resnorm0;
-    if (m_o.verbose) printf("iamrx nodal MLMG: rhs %.6e resid0 %.6e levels %d (fused sweep %d, single-workgroup coarse smoother %d, ghost width %d)\n",
-                            st.rhsnorm0, st.resnorm0, st.nlevels, (int)nodal_fused(), (int)nodal_small(), L0.cor.ngrow);
+    if (m_o.verbose) printf("iamrx nodal MLMG: rhs %.6e resid0 %.6e levels %d (smoother path of the finest level %d, ghost width %d)\n",
+                            st.rhsnorm0, st.resnorm0, st.nlevels, (int)L0.plan.path, L0.cor.ngrow);
     double vc_ms = 0.0;
     cycle_timer().used = 0;
-    const bool bdev = bottom_on_device();
+    const bool bdev = NodalSmoothPlan::on_device(m_lev.back().plan.bottom);
     if (bdev) IAMRX_HIP_CHECK(hipMemsetAsync(mg_bottom_iters_dev(), 0, sizeof(int), ctx.stream));
     if (m_o.fixed_iters <= 0 && st.resnorm0 <= res_target) st.converged = 1;
     else {

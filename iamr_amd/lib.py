@@ -431,6 +431,25 @@ def host_abec_smoother_plan(geom, boxes, ncomp=1, coef=1, has_a=False, has_cf=Fa
     return d
 
 
+NODAL_SMOOTHER_PATHS = ("JACOBI", "COLOUR8", "SMALL", "GS4", "GSR")
+NODAL_BOTTOM_KINDS = ("NONE", "SMOOTHER_ONLY", "DEVICE_PERIODIC", "DEVICE_GENERAL", "HOST_KRYLOV")
+
+
+def host_nodal_smoother_plan(geom, boxes, has_mask=False, nodal_smoother=0, bottom_smoother_only=False, device_bottom=True, nodal_sweeps=2,
+                             coarsest=False, ngrow=(4, 4), lobc=(0, 0, 0), hibc=(0, 0, 0)):
+    """host-only: the smoother and bottom path of a nodal multigrid level (include/iamrx.h: iamrx_host_nodal_smoother_plan) as a dict;
+    boxes: [(lo, hi), ...], the level's global box list; ngrow: ghost widths of correction and right-hand side"""
+    arr = (C.c_int * (6 * len(boxes)))(*[int(v) for lo, hi in boxes for v in tuple(lo) + tuple(hi)])
+    out = (C.c_int * 11)()
+    check(lib().iamrx_host_nodal_smoother_plan(len(boxes), arr, C.byref(geom), i3(lobc), i3(hibc), int(has_mask), int(nodal_smoother),
+                                               int(bottom_smoother_only), int(device_bottom), int(nodal_sweeps), int(coarsest),
+                                               (C.c_int * 2)(*[int(v) for v in ngrow]), out))
+    keys = ("path", "ngrow", "wrap", "refl", "images", "written_first", "zero_start", "par_fill", "splits", "bottom", "sweeps")
+    d = dict(zip(keys, out[:]))
+    d["path"], d["bottom"] = NODAL_SMOOTHER_PATHS[d["path"]], NODAL_BOTTOM_KINDS[d["bottom"]]
+    return d
+
+
 # the 17 values of a forcing mode, in the order of upstream's arrays (Tutorials/HIT/NS_getForce.cpp:249-281)
 TURB_FIELDS = ("FTX", "TAT", "FPX", "FPY", "FPZ", "FAX", "FAY", "FAZ", "FPXX", "FPXY", "FPXZ", "FPYX", "FPYY", "FPYZ", "FPZX", "FPZY", "FPZZ")
 

@@ -203,6 +203,21 @@ int iamrx_host_fill_plan_wall_ext(int nboxes, const int* lo_hi, const int* owner
  * kernel, out[11] first pass from zero allowed.  No counterpart upstream (amrex picks nothing: one smoother kernel). */
 int iamrx_host_abec_smoother_plan(int nboxes, const int* lo_hi, const iamrx_geom* g, const int lobc[3], const int hibc[3], int maxorder, int ncomp,
                                   int coef, int has_a, int has_cf, int finest, const int ngrow[4], int out[12]);
+/* host-only (works without a GPU): how a smoothing call and the bottom solve of the nodal multigrid (MLMG::mgVcycle on MLNodeLaplacian, as set
+ * up at Projection.cpp:2512-2542) run on a level -- decided once per level per solve, from the level's global box list (a single rank's view).
+ * lo_hi: 6 ints per box; lobc / hibc: LinOpBC codes; has_mask: the level has Dirichlet nodes (outflow faces, the boundary of a refined
+ * level); nodal_smoother, bottom_smoother_only, device_bottom, nodal_sweeps: iamrx_mg_opts; coarsest: the last level of its hierarchy;
+ * ngrow: ghost widths of the correction and of the right-hand side (the solver allocates both with out[1]).  out[0] path (0 weighted Jacobi,
+ * 1 eight colour passes, each behind a ghost fill, 2 every sweep in one single-workgroup launch, 3 two plane-fused passes per sweep staged
+ * in LDS, 4 the same register-resident), out[1] ghost width the solver allocates, out[2] images read by index wrap instead of ghost nodes,
+ * out[3] directions with mirror images about Neumann walls (bit d), out[4] the residual and the restriction read images too (no ghost fill
+ * inside a cycle), out[5] no zero fill behind the allocation, out[6] the first sweep on a zero correction is told so, out[7] ghost fills
+ * of one plane parity, out[8] a pass behind a ghost fill can be issued in two parts, out[9] bottom solve (0 not the coarsest level,
+ * 1 smoothing calls only, 2 single-workgroup device solver of a periodic box, 3 the same with walls / Dirichlet nodes, 4 BiCGStab driven
+ * from the host), out[10] sweeps per smoothing call.  No counterpart upstream (amrex picks nothing: one smoother kernel). */
+int iamrx_host_nodal_smoother_plan(int nboxes, const int* lo_hi, const iamrx_geom* g, const int lobc[3], const int hibc[3], int has_mask,
+                                   int nodal_smoother, int bottom_smoother_only, int device_bottom, int nodal_sweeps, int coarsest, const int ngrow[2],
+                                   int out[11]);
 
 /* ---- cell-centred linear operator primitives (amrex::MLABecLaplacian role) ---- */
 /* one red or black Gauss-Seidel pass of (alpha*a - beta div b grad) phi = rhs; ghost cells of phi must be filled */

@@ -196,3 +196,20 @@ def test_pass_issued_in_two_parts_on_two_streams_gives_the_same_doubles(gpu, cas
             lib.tuning_set("HALO_OVERLAP", 1)
     for a, b in zip(out[0], out[2]):
         assert np.isfinite(a).all() and np.array_equal(a, b), float(np.abs(a - b).max())
+
+
+@pytest.mark.boxes_kept
+def test_without_the_parity_fill_a_pass_is_issued_in_one_piece(gpu):
+    """IAMRX_NODAL_PARITY_FILL = 0: the full exchange in front of the odd pass reads nodes of the array the interior tiles of a two-part pass
+    would be writing on the other stream, so the level's plan does not split (nodal_smooth_plan: `splits` needs `par_fill`).  Two boxes of
+    112 x 112 x 16 cells (3 x 3 tiles each -- the smallest level that splits with the parity fill on), HALO_OVERLAP = 2 against 0: the same
+    doubles, all finite."""
+    lib = gpu
+    kw = dict(n=(224, 112, 16), per=(1, 1, 1), lobc=(PERIODIC,) * 3, hibc=(PERIODIC,) * 3, boxes=[((0, 0, 0), (111, 111, 15)), ((112, 0, 0), (223, 111, 15))])
+    out = {}
+    with tuning(lib, NODAL_PARITY_FILL=(0, 1)):
+        for ov in (0, 2):
+            with tuning(lib, HALO_OVERLAP=(ov, 1)):
+                out[ov] = solve_case(lib, seed=5, sigma_const=False, iters=2, **kw)
+    for a, b in zip(out[0], out[2]):
+        assert np.isfinite(a).all() and np.isfinite(b).all() and np.array_equal(a, b), float(np.abs(a - b).max())
