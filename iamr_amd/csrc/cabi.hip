@@ -169,6 +169,28 @@ int iamrx_host_abec_smoother_plan(int nboxes, const int* lo_hi, const iamrx_geom
     IAMRX_CATCH
 }
 
+// host-only (no device needed): whether level `level` of a cell-centred hierarchy runs its down leg and its up leg as one launch each
+// (abec_leg_plan, k_abec_legs.hip).  out (9 ints): legs, tile lengths of the down leg, tile lengths of the up leg, halo widths of the two
+int iamrx_host_abec_leg_plan(int nboxes, const int* lo_hi, const iamrx_geom* g, const int lobc[3], const int hibc[3], int maxorder, int ncomp,
+                             int coef, int has_a, int has_cf, int finest, const int ngrow[4], int level, int nu1, int nu2, int slab_transition,
+                             int agg_transition, int out[9])
+{
+    IAMRX_TRY
+    if (nboxes < 1 || coef < 0 || coef > 2) throw Error("iamrx_host_abec_leg_plan: at least one box; coef is 0 (stored), 1 (density) or 2 (uniform)");
+    std::vector<BoxD> b(nboxes);
+    AbecLevel lv;
+    for (int i = 0; i < nboxes; ++i)
+        for (int d = 0; d < 3; ++d) { b[i].lo[d] = lo_hi[6 * i + d]; b[i].hi[d] = lo_hi[6 * i + 3 + d]; lv.max_len[d] = std::max(lv.max_len[d], b[i].len(d)); }
+    const DomainBC bc = to_bc(lobc, hibc, maxorder);
+    lv.boxes = &b; lv.nlocal = nboxes; lv.ncomp = ncomp;
+    lv.phi_ngrow = ngrow[0]; lv.rhs_ngrow = ngrow[1]; lv.sig_ngrow = ngrow[2]; lv.a_ngrow = ngrow[3];
+    lv.sig = coef == 1; lv.b_uniform = coef == 2; lv.has_a = has_a != 0; lv.nbc = 1; lv.bcs = &bc; lv.has_cf = has_cf != 0; lv.finest = finest != 0;
+    const AbecLegPlan p = abec_leg_plan(to_geom(g), lv, level, nu1, nu2, slab_transition != 0, agg_transition != 0);
+    const int v[9] = {p.on ? 1 : 0, p.tile_down[0], p.tile_down[1], p.tile_down[2], p.tile_up[0], p.tile_up[1], p.tile_up[2], p.halo_down, p.halo_up};
+    std::copy(v, v + 9, out);
+    IAMRX_CATCH
+}
+
 // host-only (no device needed): how a smoothing call and the bottom solve of the nodal multigrid run on a level (nodal_smooth_plan, k_nodal.hip).
 // out (11 ints): path (0 JACOBI, 1 COLOUR8, 2 SMALL, 3 GS4, 4 GSR), ngrow, wrap, refl, images, written_first, zero_start, par_fill, splits,
 // bottom (0 NONE, 1 SMOOTHER_ONLY, 2 DEVICE_PERIODIC, 3 DEVICE_GENERAL, 4 HOST_KRYLOV), sweeps

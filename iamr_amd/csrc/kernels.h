@@ -152,6 +152,26 @@ void abec_gsrb(const Geometry& g, const AbecCoef& c, const AbecColourForm& f, Mu
 bool abec_tail_ok(const Geometry& gF, const Layout& lF, const Geometry& gC, const Layout& lC, const AbecCoef& cF, const DomainBC* bcs, int nbc, int ncomp);
 void abec_tail_solve(const Geometry& gF, const AbecCoef& cF, MultiFab& corF, const MultiFab& resF, const Geometry& gC, const AbecCoef& cC,
                      const DomainBC& bc, bool singular, double eps_rel, int maxiter, int nub, int nuf, int nu1, int nu2, double omega, int* d_iters);
+// ---- k_abec_legs.hip: a coarse level of the cell-centred V-cycle in two launches ----
+// Down leg: nu1 red-black sweeps from zero, the residual and its restriction; up leg: prolongation and nu2 sweeps (the doubles of the
+// launches they replace).  A workgroup holds a tile grown by a halo of 2 nu cells in an LDS array of LEG_R^3 cells.
+constexpr int LEG_R = 16;
+struct AbecLegPlan {
+    bool on = false;              // the level takes legs
+    int mode = 0;                 // coefficients: 0 stored face arrays, 2 the constants bu
+    int tile_down[3] = {0, 0, 0}, tile_up[3] = {0, 0, 0};     // tile lengths of the two launches
+    int halo_down = 0, halo_up = 0;                           // 2 nu1, 2 nu2
+};
+// THE decision for level `level` (>= 1) of a hierarchy, a sibling of abec_smooth_plan (host data only): one component, no tensor solve, no
+// coarse/fine faces, one box spanning a fully periodic domain and held by this rank, stored or uniform coefficients, no slab /
+// agglomeration transition to the next level, nu1, nu2 >= 1 with the grown tile inside the LDS array, at most IAMRX_MG_LEGS_MAX_CELLS
+// cells, IAMRX_MG_LEGS (1) on.  The caller adds what only the hierarchy knows (not the coarsest level, no fused tail, no sweep-only solve).
+AbecLegPlan abec_leg_plan(const Geometry& g, const AbecLevel& lv, int level, int nu1, int nu2, bool slab_transition, bool agg_transition);
+// buf = S^nu1(0) on the level, crse_rhs = R(rhs - A buf); c: the level's coefficients
+void abec_leg_down(const Geometry& g, const AbecCoef& c, const AbecLegPlan& p, MultiFab& buf, const MultiFab& rhs, MultiFab& crse_rhs, int nu1, double omega);
+// cor = S^nu2(buf + P crse_cor)
+void abec_leg_up(const Geometry& g, const AbecCoef& c, const AbecLegPlan& p, MultiFab& cor, const MultiFab& buf, const MultiFab& rhs, const MultiFab& crse_cor, int nu2,
+                 double omega);
 // restriction of the residual rhs - A phi straight onto the coarsened layout (one pass, the fine residual is not stored): usable if ..._ok
 bool abec_residual_reads_no_ghosts(const Geometry& g, const AbecCoef& c, const MultiFab& out, const MultiFab& phi, const MultiFab& rhs, bool restrict_form);
 bool abec_resid_restrict_ok(const AbecCoef& c, const MultiFab& phi, const MultiFab& rhs);

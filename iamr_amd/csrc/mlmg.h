@@ -183,6 +183,7 @@ private:
         MultiFab cor, res, rescor;
         MultiFab buf;              // second buffer of the fused (out-of-place) GSRB sweeps
         AbecSmoothPlan plan;       // how a smoothing call on this level runs: decided in prepare(), once per solve
+        AbecLegPlan legs;          // legs.on: the level's down leg and up leg are one launch each (k_abec_legs.hip; buf: allocated in prepare())
         MultiFab cfm;              // coarse/fine mask (levels that do not cover the domain), see cf_build_mask
         CfTab cftab;
     };

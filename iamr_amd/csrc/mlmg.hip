@@ -275,6 +275,21 @@ void CellMG::prepare()
         // everything a smoothing call on this level depends on is known now: its path is chosen here, once per solve (coef: with the tensor flag)
         L.plan = abec_smooth_plan(L.g, abec_level(coef(l), L.cor, L.res.ngrow, (int)m_bcn.size(), m_bcn.data(), m_cf, l == 0));
     }
+    // ... and whether a coarse level's down leg and up leg run as one launch each (abec_leg_plan: IAMRX_MG_LEGS); never the coarsest level
+    // (the bottom solver's) nor the level the opt-in fused tail claims
+    for (int l = 0; l < nl; ++l) {
+        Level& L = m_lev[l];
+        L.legs = AbecLegPlan();
+        if (l < 1 || l + 1 >= nl || m_dd_sweeps > 0) continue;
+        const Level& C = m_lev[l + 1];
+        L.legs = abec_leg_plan(L.g, abec_level(coef(l), L.cor, L.res.ngrow, (int)m_bcn.size(), m_bcn.data(), m_cf, false), l, m_o.nu1, m_o.nu2,
+                               L.slab || C.slab, C.agg);
+    }
+    if (nl >= 2 && m_lev[nl - 2].legs.on && tail_fused()) m_lev[nl - 2].legs.on = false;
+    for (int l = 0; l < nl; ++l) {
+        Level& L = m_lev[l];
+        if (L.legs.on && (!L.buf.defined() || L.buf.ngrow != L.cor.ngrow)) L.buf.define(L.layout, cell_type(), m_ncomp, L.cor.ngrow);
+    }
     bottom_direct_prepare();
 }
 
@@ -650,6 +665,10 @@ void CellMG::vcycle(MGStats& st)
     const int nsm = tail ? nl - 2 : nl - 1;          // levels smoothed by the loops below
     for (int l = 0; l < nsm; ++l) {
         Level& L = m_lev[l];
+        if (L.legs.on) {         // sweeps from zero, residual and restriction in one launch: the smoothed correction goes to L.buf
+            abec_leg_down(L.g, coef(l), L.legs, L.buf, L.res, m_lev[l + 1].res, m_o.nu1, m_o.omega);
+            continue;
+        }
         // zero initial guess of the correction: where the first sweep reads no ghost cell it also takes the place of the fill
         const bool z = m_o.nu1 > 0 && L.plan.zero_first;
         if (!z) L.cor.setVal(0.0);
@@ -676,6 +695,10 @@ void CellMG::vcycle(MGStats& st)
     bottom_solve(st);
     for (int l = nsm - 1; l >= 0; --l) {
         Level& L = m_lev[l];
+        if (L.legs.on) {         // cor = S^nu2(buf + P cor_coarse) in one launch
+            abec_leg_up(L.g, smoother_coef(l), L.legs, L.cor, L.buf, L.res, m_lev[l + 1].cor, m_o.nu2, m_o.omega);
+            continue;
+        }
         cc_prolong_add(L.cor, mg_correction_of(m_lev[l + 1], m_lev[l + 1].cor, 0));
         smooth_n(l, m_o.nu2, false, false, l == 0 ? m_acc : nullptr);
     }

@@ -431,6 +431,19 @@ def host_abec_smoother_plan(geom, boxes, ncomp=1, coef=1, has_a=False, has_cf=Fa
     return d
 
 
+def host_abec_leg_plan(geom, boxes, level, nu1=2, nu2=2, ncomp=1, coef=0, has_a=False, has_cf=False, ngrow=(1, 0, 0, 0), lobc=(0, 0, 0), hibc=(0, 0, 0),
+                       maxorder=3, slab_transition=False, agg_transition=False):
+    """host-only: whether a coarse level of the cell-centred V-cycle runs its down leg and its up leg as one launch each
+    (include/iamrx.h: iamrx_host_abec_leg_plan) as a dict; boxes: [(lo, hi), ...], the level's global box list"""
+    arr = (C.c_int * (6 * len(boxes)))(*[int(v) for lo, hi in boxes for v in tuple(lo) + tuple(hi)])
+    out = (C.c_int * 9)()
+    check(lib().iamrx_host_abec_leg_plan(len(boxes), arr, C.byref(geom), i3(lobc), i3(hibc), int(maxorder), int(ncomp), int(coef), int(has_a),
+                                         int(has_cf), int(level == 0), (C.c_int * 4)(*[int(v) for v in ngrow]), int(level), int(nu1), int(nu2),
+                                         int(slab_transition), int(agg_transition), out))
+    v = out[:]
+    return dict(legs=bool(v[0]), tile_down=tuple(v[1:4]), tile_up=tuple(v[4:7]), halo_down=v[7], halo_up=v[8])
+
+
 NODAL_SMOOTHER_PATHS = ("JACOBI", "COLOUR8", "SMALL", "GS4", "GSR")
 NODAL_BOTTOM_KINDS = ("NONE", "SMOOTHER_ONLY", "DEVICE_PERIODIC", "DEVICE_GENERAL", "HOST_KRYLOV")
 

@@ -203,6 +203,14 @@ int iamrx_host_fill_plan_wall_ext(int nboxes, const int* lo_hi, const int* owner
  * kernel, out[11] first pass from zero allowed.  No counterpart upstream (amrex picks nothing: one smoother kernel). */
 int iamrx_host_abec_smoother_plan(int nboxes, const int* lo_hi, const iamrx_geom* g, const int lobc[3], const int hibc[3], int maxorder, int ncomp,
                                   int coef, int has_a, int has_cf, int finest, const int ngrow[4], int out[12]);
+/* host-only (works without a GPU): whether level `level` (0 = finest) of a cell-centred hierarchy runs the down leg of a V-cycle (nu1
+ * sweeps from zero, residual, restriction) and its up leg (prolongation, nu2 sweeps) as ONE launch each instead of ten.  Inputs as for
+ * iamrx_host_abec_smoother_plan, plus the level, the cycle shape and whether the step to the next coarser level goes through a slab or an
+ * agglomerated level.  out[0] legs (0 / 1); out[1..3] tile lengths of the down leg, out[4..6] of the up leg (zero without legs); out[7],
+ * out[8] the halo widths 2 nu1, 2 nu2 by which a workgroup grows its tile.  No counterpart upstream. */
+int iamrx_host_abec_leg_plan(int nboxes, const int* lo_hi, const iamrx_geom* g, const int lobc[3], const int hibc[3], int maxorder, int ncomp,
+                             int coef, int has_a, int has_cf, int finest, const int ngrow[4], int level, int nu1, int nu2, int slab_transition,
+                             int agg_transition, int out[9]);
 /* host-only (works without a GPU): how a smoothing call and the bottom solve of the nodal multigrid (MLMG::mgVcycle on MLNodeLaplacian, as set
  * up at Projection.cpp:2512-2542) run on a level -- decided once per level per solve, from the level's global box list (a single rank's view).
  * lo_hi: 6 ints per box; lobc / hibc: LinOpBC codes; has_mask: the level has Dirichlet nodes (outflow faces, the boundary of a refined
