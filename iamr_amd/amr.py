@@ -43,6 +43,17 @@ class Amr:
         """switch the turbulent forcing on for every level, with upstream's mode table for the level-0 domain (iamrx_amr_set_turb_forcing)"""
         check(lib().iamrx_amr_set_turb_forcing(self.h, int(on), int(nmodes), int(mode_start), int(div_free)))
 
+    def set_particles(self, pc):
+        """attach ONE tracer-particle container to the hierarchy (particles.Particles; None: detach): it is rebound to the levels' boxes,
+        now and after every regrid; every level moves its particles at the end of its advance, post_timestep and post_regrid redistribute
+        (NavierStokes::advance, post_timestep_particle, post_regrid; include/iamrx.h: iamrx_amr_set_particles)"""
+        check(lib().iamrx_amr_set_particles(self.h, None if pc is None else pc.h))
+        self._particles = pc
+
+    @property
+    def particles(self):
+        return getattr(self, "_particles", None)
+
     def _refresh(self, keep_layouts=False):
         """(re)build the Python views of the levels; after a regrid the layouts are re-created from the hierarchy's box lists"""
         from .lib import Layout

@@ -19,6 +19,8 @@ writer produces them, iamr_amd/plotfile.py, which is pinned byte for byte on the
                               initial-guess history of the MAC solve (two potentials per level + the dt they belong to), the step counter of
                               every level, the single-level driver's dt estimate, the box owners and (if more than one) the number of ranks that wrote
   Level_<l>/MacPhiHist_<q>_*  the two MAC potentials
+  Particles/                  with tracer particles attached to the run: this project's own particle files (iamr_amd/particles.py:
+                              write_particles_dir; NOT AMReX's binary particle format); run.py restores them on amr.restart
 
 Old data are always written: the pressure of two steps ago seeds the initial guess of the next level projection (navierstokes.hip), so a
 restart from new data alone would converge to the same answer along a different path -- equal to solver tolerance, not to the bit.
@@ -243,6 +245,10 @@ def write(run, root, step, max_level=None):
             json.dump(extra, f)
         with open(os.path.join(path, "Header"), "w") as f:
             f.write("\n".join(H) + "\n")
+    pc = getattr(run, "particles", None)
+    if pc is not None:                          # NavierStokesBase::checkPoint: NSPC->Checkpoint(dir, "Particles"); single-rank runs only
+        from .particles import save
+        save(path, pc)
     barrier()
     return path
 

@@ -2,6 +2,7 @@
 // NavierStokes levels, NavierStokesBase::post_timestep and the multi-level projections of Projection.
 #pragma once
 #include "operators.h"
+#include "particles.h"
 #include <vector>
 #include <memory>
 
@@ -79,6 +80,11 @@ public:
     // (set_turb_modes: a caller's; null: off) and shared by every level, also by the levels a regrid creates
     void set_turb_modes(TurbTableP t) { turb = t; for (auto& s : lev) s->set_turb_modes(t); }
     void set_turb_forcing(int nmodes, int mode_start, int div_free) { set_turb_modes(turb_make_table(lev[0]->geom(), nmodes, mode_start, div_free)); }
+    // tracer particles: ONE container for the hierarchy (NSPC, NavierStokesBase.cpp:198-222), bound to the levels' working boxes and bound
+    // again after every regrid (post_regrid: Redistribute(lbase), :2448-2452); post_timestep(l) redistributes the levels l .. finest
+    // (post_timestep_particle, :3866-3879).  Null: off
+    void set_particles(ParticlesP pc);
+    const ParticlesP& particle_container() const { return particles; }
     uint64_t grid_generation() const { return m_grid_gen; }   // incremented whenever the grids change
     uint64_t m_grid_gen = 0;
     // section profile of the coarse step (host clock around stream syncs, only while profile_on): [0] reflux, [1] avgDown,
@@ -98,6 +104,8 @@ private:
     double stop_time = -1.0;
     RegridOpts rg;
     TurbTableP turb;
+    ParticlesP particles;
+    void bind_particles();
     int m_ratio = 2;
     void link_level(int l);
     void check_nesting(const std::vector<BoxD>& fine, const std::vector<BoxD>& crse, const Geometry& cgeom, int l) const;

@@ -1232,12 +1232,33 @@ void AmrNS::post_timestep(int l, int crse_iteration)
         sum_integrated_quantities(last_sum);
         last_sum_step = level_steps; last_sum_time = lev[0]->time;
     }
+    // post_timestep_particle (NavierStokesBase.cpp:3866-3879): not on the last sub-step of a refined level -- the coarser level's follows
+    if (particles && (l == 0 || crse_iteration < n_cycle[l])) {
+        if (l > 0 && crse_iteration < 0) throw Error("AmrNS::post_timestep: the particles need the level's iteration");
+        particles->redistribute(l, (int)lev.size() - 1, l == 0 ? 0 : crse_iteration);
+    }
     lev[l]->time_average(dt_level[l], level_steps);                                                       // :2630-2634
     // The levels above l have just reached level l's time through their own sub-steps, and have summed the same interval in smaller pieces:
     // their three scalars equal level l's up to the rounding of those sums.  They take level l's, so that at the end of a coarse step ONE
     // time_avg / time_avg_fluct describes the hierarchy -- what <chk>/TimeAverage holds and what a regrid hands to a new level.
     if (lev[l]->has_average())
         for (size_t k = l + 1; k < lev.size(); ++k) { lev[k]->time_avg = lev[l]->time_avg; lev[k]->time_avg_fluct = lev[l]->time_avg_fluct; lev[k]->dt_avg = lev[l]->dt_avg; }
+}
+
+void AmrNS::bind_particles()
+{
+    std::vector<Geometry> gs;
+    std::vector<LayoutP> ls;
+    for (auto& s : lev) { gs.push_back(s->g); ls.push_back(s->layout); s->particles = particles; }
+    particles->define(gs, ls, m_ratio);
+}
+
+void AmrNS::set_particles(ParticlesP pc)
+{
+    particles = std::move(pc);
+    if (!particles) { for (auto& s : lev) { s->particles = nullptr; for (auto& m : s->m_part_umac) m.clear(); } return; }
+    bind_particles();
+    particles->redistribute(0, (int)lev.size() - 1, 0);
 }
 
 void AmrNS::sum_integrated_quantities(double out[3])

@@ -345,6 +345,8 @@ bool AmrNS::install_grids(const std::vector<std::vector<BoxD>>& grids, int lbase
     for (auto& o_ : old) if (o_ && o_->layout) dead_ids.push_back(o_->layout->id);
     old.clear();                                   // the old levels' arrays go first, then what the caches hold for their layouts
     for (uint64_t id_ : dead_ids) evict_layout_caches(id_);
+    // post_regrid (NavierStokesBase.cpp:2448-2452): the particles go to the new boxes
+    if (particles) { bind_particles(); particles->redistribute(lbase, (int)lev.size() - 1, 0); }
     return true;
 }
 

@@ -13,6 +13,7 @@ using namespace iamrx;
 
 struct iamrx_layout_s { LayoutP p; };
 struct iamrx_mf_s { MultiFab mf; };
+struct iamrx_particles_s { ParticlesP pc; };
 
 static thread_local std::string g_err;
 
@@ -1683,6 +1684,79 @@ int iamrx_amr_sync_stats(iamrx_amr a, iamrx_mg_stats* sync, iamrx_mg_stats* mac_
     from_stats(a->amr->st_sync, sync); from_stats(a->amr->st_mac_sync, mac_sync);
     IAMRX_CATCH
 }
+
+// ---- tracer particles (k_particles.hip) -------------------------------------------------------------------------------------------------
+// the handle the caller created is the one get_particles gives back: the container remembers it
+static std::map<Particles*, iamrx_particles>& particle_handles() { static auto* m = new std::map<Particles*, iamrx_particles>(); return *m; }
+int iamrx_particles_create(int nlev, const iamrx_geom* geoms, const iamrx_layout* layouts, int ratio, iamrx_particles* out)
+{
+    IAMRX_TRY
+    std::vector<Geometry> gs;
+    std::vector<LayoutP> ls;
+    for (int l = 0; l < nlev; ++l) { gs.push_back(to_geom(&geoms[l])); ls.push_back(layouts[l]->p); }
+    auto* h = new iamrx_particles_s;
+    h->pc = std::make_shared<Particles>(gs, ls, ratio);
+    particle_handles()[h->pc.get()] = h;
+    *out = h;
+    IAMRX_CATCH
+}
+int iamrx_particles_destroy(iamrx_particles pc) { IAMRX_TRY if (pc) { particle_handles().erase(pc->pc.get()); delete pc; } IAMRX_CATCH }
+int iamrx_particles_add(iamrx_particles pc, long n, const double* xyz, const double* r, const int* ids, const int* cpus, long* removed)
+{
+    IAMRX_TRY
+    if (n > 0 && !xyz) throw Error("iamrx_particles_add: null positions");
+    const long rm = pc->pc->add(n, xyz, r, ids, cpus);
+    if (removed) *removed = rm;
+    IAMRX_CATCH
+}
+int iamrx_particles_count(iamrx_particles pc, long* per_level, long* total, int* next_id, long* removed_total)
+{
+    IAMRX_TRY
+    if (per_level) for (int l = 0; l < pc->pc->nlevels(); ++l) per_level[l] = pc->pc->count_at_level(l);
+    if (total) *total = pc->pc->size();
+    if (next_id) *next_id = pc->pc->next_id;
+    if (removed_total) *removed_total = pc->pc->n_removed;
+    IAMRX_CATCH
+}
+int iamrx_particles_set_next_id(iamrx_particles pc, int next_id) { IAMRX_TRY if (next_id < 1) throw Error("iamrx_particles_set_next_id: ids start at 1"); pc->pc->next_id = next_id; IAMRX_CATCH }
+int iamrx_particles_set_fixed_dir(iamrx_particles pc, int dir) { IAMRX_TRY if (dir < -1 || dir > 2) throw Error("iamrx_particles_set_fixed_dir: -1 .. 2"); pc->pc->fixed_dir = dir; IAMRX_CATCH }
+int iamrx_particles_read(iamrx_particles pc, double* xyz, double* r, int* id, int* cpu, int* level, int* box)
+{
+    IAMRX_TRY pc->pc->read(xyz, r, id, cpu, level, box); IAMRX_CATCH
+}
+int iamrx_particles_set_positions(iamrx_particles pc, const double* xyz) { IAMRX_TRY if (!xyz) throw Error("iamrx_particles_set_positions: null positions"); pc->pc->set_positions(xyz); IAMRX_CATCH }
+int iamrx_particles_advect(iamrx_particles pc, int lev, iamrx_mf umac_x, iamrx_mf umac_y, iamrx_mf umac_z, double dt)
+{
+    IAMRX_TRY
+    const MultiFab* um[3] = {&umac_x->mf, &umac_y->mf, &umac_z->mf};
+    pc->pc->advect(lev, um, dt);
+    IAMRX_CATCH
+}
+int iamrx_particles_redistribute(iamrx_particles pc, int lev_min, int lev_max, int ngrow, long* removed)
+{
+    IAMRX_TRY
+    const long rm = pc->pc->redistribute(lev_min, lev_max, ngrow);
+    if (removed) *removed = rm;
+    IAMRX_CATCH
+}
+int iamrx_particles_derive_count(iamrx_particles pc, int which, int lev, iamrx_mf out, int ocomp)
+{
+    IAMRX_TRY
+    if (which == 0) pc->pc->particle_count(lev, out->mf, ocomp);
+    else if (which == 1) pc->pc->total_particle_count(lev, out->mf, ocomp);
+    else throw Error("iamrx_particles_derive_count: which = 0 (particle_count) or 1 (total_particle_count)");
+    IAMRX_CATCH
+}
+int iamrx_ns_set_particles(iamrx_ns ns, iamrx_particles pc) { IAMRX_TRY ns->ns->set_particles(pc ? pc->pc : nullptr); IAMRX_CATCH }
+int iamrx_amr_set_particles(iamrx_amr a, iamrx_particles pc) { IAMRX_TRY a->amr->set_particles(pc ? pc->pc : nullptr); IAMRX_CATCH }
+static iamrx_particles handle_of(const ParticlesP& p)
+{
+    if (!p) return nullptr;
+    auto it = particle_handles().find(p.get());
+    return it == particle_handles().end() ? nullptr : it->second;
+}
+int iamrx_ns_get_particles(iamrx_ns ns, iamrx_particles* pc) { IAMRX_TRY *pc = handle_of(ns->ns->particle_container()); IAMRX_CATCH }
+int iamrx_amr_get_particles(iamrx_amr a, iamrx_particles* pc) { IAMRX_TRY *pc = handle_of(a->amr->particle_container()); IAMRX_CATCH }
 
 int iamrx_ns_stats(iamrx_ns ns, iamrx_mg_stats* mac, iamrx_mg_stats* nodal, iamrx_mg_stats* visc)
 {

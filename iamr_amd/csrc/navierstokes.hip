@@ -25,6 +25,7 @@
 // through xlo.velocity ... zhi.velocity); constant viscosity / tracer diffusivity, divu = 0; nstate = 5 + do_trac2 + do_temp
 // (u,v,w,rho,tracer), do_mom_diff = 0 or 1, Godunov_PLM.
 #include "operators.h"
+#include "particles.h"
 #include "launch.h"
 #include <cmath>
 #include <chrono>
@@ -296,7 +297,12 @@ void NavierStokes::derive(const std::string& name, MultiFab& out, int ocomp)
     } else if (name == "velocity_average" && has_average()) {  // der_vel_avg, NS_derive.cpp:11-45: 6 components
         IAMRX_ASSERT(ocomp + 6 <= out.ncomp);
         stats_derive_vel_avg(out, ocomp, Savg, time_avg, time_avg_fluct);
-    } else throw Error("NavierStokes::derive: unknown derived quantity '" + name + "' (energy, mag_vort, avg_pressure" + (has_average() ? ", velocity_average)" : ")"));
+    } else if (name == "particle_count" && particles) {        // NavierStokesBase::ParticleDerive, NavierStokesBase.cpp:3996-4048
+        particles->particle_count(level, out, ocomp);
+    } else if (name == "total_particle_count" && particles) {
+        particles->total_particle_count(level, out, ocomp);
+    } else throw Error("NavierStokes::derive: unknown derived quantity '" + name + "' (energy, mag_vort, avg_pressure" + (has_average() ? ", velocity_average" : "") +
+                       (particles ? ", particle_count, total_particle_count)" : ")"));
 }
 
 // NavierStokesBase::time_average (NS_average.cpp:19-69), statement by statement
@@ -1379,6 +1385,7 @@ double NavierStokes::advance(double dt_, int iteration_, int ncycle_)
         level_project(dt_);
         if (level > 0 && iteration == 1) p_avg.setVal(0.0);      // :670-671
     }
+    if (particles && !initial_step) advect_particles(dt_);       // AdvectWithUmac(u_mac, level, dt), NavierStokes.cpp:672-677
     m_in_advance = false; m_visc_old_valid = false; m_eta_n_valid = false;
     return dt_test;
 }
@@ -1536,6 +1543,29 @@ void NavierStokes::post_init(double stop_time)
     dt_min_adv = 1.e200;
 }
 
+void NavierStokes::set_particles(std::shared_ptr<Particles> pc)
+{
+    if (pc && (crse || fine || amr_times)) throw Error("NavierStokes::set_particles: a level of a hierarchy takes its particles from the hierarchy");
+    particles = std::move(pc);
+    if (!particles) { for (auto& m : m_part_umac) m.clear(); return; }
+    particles->define({g}, {layout}, 1);
+    particles->redistribute(0, 0, 0);
+}
+
+// the level's particles move with its u_mac: level 0 has the one ghost face the stencils reach; a refined level that sub-cycles keeps
+// particles up to ncycle - 1 cells outside its boxes between sub-steps and reads ncycle ghost faces (umac_n_grow = ncycle,
+// NavierStokesBase.cpp:625-628), built in scratch arrays so that the level's own u_mac stays what it is
+void NavierStokes::advect_particles(double dt_)
+{
+    const MultiFab* um[3] = {&u_mac[0], &u_mac[1], &u_mac[2]};
+    if (level == 0 || ncycle <= 1) { particles->advect(level, um, dt_); return; }
+    if (particles->count_at_level(level) == 0) return;
+    const MultiFab* uc[3] = {&crse->u_mac[0], &crse->u_mac[1], &crse->u_mac[2]};
+    particles_grow_umac(m_part_umac, um, uc, crse->g, g, ratio, ncycle);
+    const MultiFab* ug[3] = {&m_part_umac[0], &m_part_umac[1], &m_part_umac[2]};
+    particles->advect(level, ug, dt_);
+}
+
 double NavierStokes::step()
 {
     double dt_ = dt;
@@ -1552,6 +1582,7 @@ double NavierStokes::step()
     dt_min_adv = advance(dt_);
     time += dt_;
     nstep += 1;
+    if (particles) particles->redistribute(0, 0, 0);
     return dt_;
 }
 

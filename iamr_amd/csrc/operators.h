@@ -269,6 +269,7 @@ struct ScalForm { int form[MAXSCAL]; };   // captured by device lambdas
 void scale_by(MultiFab& y, const MultiFab& x, int xcomp, int ng, bool divide);   // y (comp 0) *= or /= x(xcomp) on ng ghost cells
 class SyncRegister;
 class AmrNS;
+class Particles;
 class NavierStokes {
 public:
     // the boxes as the caller (or the grid generator) gave them; `layout` below is coalesce_layout(user_layout): what the level works on
@@ -345,6 +346,12 @@ public:
     const MultiFab* turb_force_at(double t);
     void set_turb_modes(TurbTableP t) { turb = std::move(t); m_turb_have[0] = m_turb_have[1] = false; }
     const TurbTableP& turb_modes() const { return turb; }
+    // ---- tracer particles (k_particles.hip; theNSPC() of NavierStokesBase.cpp:198-222).  A level on its own takes the container over
+    // (set_particles: the container is rebound to the level's working boxes and redistributed); a hierarchy binds it and hands every
+    // level the pointer (AmrNS::set_particles).  advance() moves the level's particles with u_mac at its end, except in the initial
+    // step (NavierStokes.cpp:672-677); step() then redistributes.  Null: nothing is allocated and no launch is added.
+    void set_particles(std::shared_ptr<Particles> pc);
+    const std::shared_ptr<Particles>& particle_container() const { return particles; }
     // the times getForce is called with: the level's own state times in a hierarchy (which keeps them), the level's clock otherwise
     bool amr_times = false;
     double prev_time() const { return amr_times ? st_old : time; }
@@ -386,6 +393,9 @@ private:
     // one; validity as m_visc_old), and that of the new state as velocity_diffusion_update last saw it.  Not allocated without LES.
     MultiFab m_eta_n[3], m_eta_np1[3];
     bool m_eta_n_valid = false, m_eta_have = false;
+    std::shared_ptr<Particles> particles;
+    MultiFab m_part_umac[3];                   // u_mac on ncycle ghost layers (refined levels with particles only)
+    void advect_particles(double dt);
     TurbTableP turb;
     MultiFab m_turb_f[2];
     double m_turb_t[2] = {0.0, 0.0};

@@ -11,10 +11,12 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   {x,y,z}{lo,hi}.velocity / .density / .tracer, prob.probtype (1: fluid at rest, 4: constant velocity + blob, 5: DoubleShearLayer, 7: Euler, 10: RayleighTaylor, 11: TaylorGreen), prob.velocity_factor, prob.a/b/c,
   prob.density_ic, prob.rho_1 / rho_2 / tra_1 / tra_2 / interface_width / perturbation_amplitude (probtype 10), max_step, stop_time,
   turb.nmodes (its presence switches the turbulent forcing of Tutorials/HIT on) / turb.div_free_force / turb.mode_start, prob.probtype 100 with
-  prob.turb_scale (Tutorials/HIT/TurbulentForcing_def.H:36-52, Tutorials/HIT/prob_init.cpp:58-134)
+  prob.turb_scale (Tutorials/HIT/TurbulentForcing_def.H:36-52, Tutorials/HIT/prob_init.cpp:58-134),
+  particles.particle_init_file / particle_restart_file / particle_output_file / restart_from_nonparticle_chkfile / particles_in_plotfile /
+  verbose / do_nspc_particles (NavierStokesBase.cpp:3751-3806; particles.timestamp_* are accepted and ignored)
 (reference: Source/NavierStokesBase.cpp:431-557, Source/NavierStokes.cpp:250-310, Source/MacProj.cpp:62-75,
 Source/Projection.cpp:49-65, Source/Diffusion.cpp:98-118, Source/prob/prob_init.cpp:8-60, Source/main.cpp:60-145).
-Keys that select features this library does not have (AMR levels, EB, particles, inflow/outflow ...) raise; keys that only
+Keys that select features this library does not have (EB, refinement ratio 4 ...) raise; keys that only
 concern I/O or verbosity are ignored and listed in `Inputs.ignored`.  Host-only code: no GPU needed to parse."""
 import os
 import re
@@ -200,6 +202,38 @@ class Inputs:
                     do_refine_outflow=self.integer("ns.do_refine_outflow", 0), do_derefine_outflow=self.integer("ns.do_derefine_outflow", 1),
                     nbuf_outflow=self.integer("ns.Nbuf_outflow", 1))
 
+    def particles(self, slab=None):
+        """particles.* (NavierStokesBase::read_particle_params, NavierStokesBase.cpp:3751-3806) -> None (no particles) or a dict.  Upstream
+        builds particles in or out at compile time and then defaults do_nspc_particles to true; here they are ON when an init or restart
+        file is named or particles.do_nspc_particles = 1 is given, and do_nspc_particles = 0 switches them off whatever else is named (as
+        upstream returns before reading the other keys).  File names are relative to the inputs file.  particles.timestamp_dir /
+        timestamp_indices are accepted and ignored: timestamp files are not written."""
+        if self.has("particles.pverbose"):                       # :3786-3788 aborts
+            raise ValueError("inputs: particles.pverbose found in inputs. Please use particles.verbose")
+        keys = [k for k in self.table if k.startswith("particles.")]
+        known = ("do_nspc_particles", "timestamp_dir", "timestamp_indices", "verbose", "particle_init_file", "particle_restart_file",
+                 "restart_from_nonparticle_chkfile", "particle_output_file", "particles_in_plotfile")
+        for k in keys:
+            if k.split(".", 1)[1] not in known:
+                raise KeyError(f"inputs: key {k} is not understood by this library (not silently ignored)")
+            self.used.add(k)
+        for k in ("particles.timestamp_dir", "particles.timestamp_indices"):
+            if self.has(k):
+                self.ignored.append(k)
+        do_nspc = self.integer("particles.do_nspc_particles", -1)
+
+        def fname(k):
+            v = self.string(k, "")
+            if v and not os.path.isabs(v) and self.files:
+                v = os.path.join(os.path.dirname(os.path.abspath(self.files[0])), v)
+            return v
+        out = dict(init_file=fname("particles.particle_init_file"), restart_file=fname("particles.particle_restart_file"),
+                   output_file=self.string("particles.particle_output_file", ""),
+                   restart_from_nonparticle_chkfile=self.integer("particles.restart_from_nonparticle_chkfile", 0),
+                   in_plotfile=self.integer("particles.particles_in_plotfile", 0), verbose=self.integer("particles.verbose", 0))
+        on = do_nspc == 1 or (do_nspc != 0 and bool(out["init_file"] or out["restart_file"]))
+        return out if on else None
+
     # two-dimensional inputs ---------------------------------------------------------------------------------------------
     def lift_2d(self):
         """A 2-D inputs file (amr.n_cell with two entries; AMREX_SPACEDIM == 2 builds of the reference, Exec/run2d) runs as a slab of the
@@ -330,9 +364,10 @@ class Inputs:
         scheme = self.string("ns.advection_scheme", "Godunov_PLM")
         if scheme not in ("Godunov_PLM", "Godunov_PPM", "BDS"):      # NavierStokesBase.cpp:548-553
             raise NotImplementedError(f"inputs: ns.advection_scheme = {scheme}; Godunov_PLM, Godunov_PPM and BDS are implemented")
-        for k in ("particles.do_nspc_particles", "eb2.geom_type"):
+        for k in ("eb2.geom_type",):
             if self.has(k) and self.string(k) not in ("0", "all_regular"):
                 raise NotImplementedError(f"inputs: {k} = {self.string(k)} is not implemented")
+        particles = self.particles(slab)
         if self.has("ns.do_LES") and self.string("ns.do_LES") != "0":
             raise NotImplementedError("inputs: ns.do_LES = 1 is not switched on from an inputs file yet: the library implements LES (Smagorinsky "
                                       "and Sigma eddy viscosity) through iamrx_ns_params.do_LES -- set params['do_LES'] = 1 on the parsed problem")
@@ -445,7 +480,7 @@ class Inputs:
                    plot_int=self.integer("amr.plot_int", -1), plot_file=self.string("amr.plot_file", "plt"), plot_vars=self.name_list("amr.plot_vars", "ALL"),
                    derive_plot_vars=self.name_list("amr.derive_plot_vars", "NONE"), fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,
                    check_int=self.integer("amr.check_int", -1), check_file=self.string("amr.check_file", "chk"),
-                   restart=self.string("amr.restart", "") if self.has("amr.restart") else "")
+                   restart=self.string("amr.restart", "") if self.has("amr.restart") else "", particles=particles)
         for k, dflt in _UNIMPLEMENTED_UNLESS.items():
             if self.has(k) and self.string(k) != dflt:
                 raise NotImplementedError(f"inputs: {k} = {self.string(k)} is not implemented (only {dflt})")

@@ -214,6 +214,17 @@ class NavierStokes:
         M, k, d = _turb_table(kxyz, data)
         check(lib().iamrx_ns_set_turb_modes(self.h, M, k, d, int(div_free)))
 
+    def set_particles(self, pc):
+        """attach a tracer-particle container (particles.Particles; None: detach).  The container is rebound to this level's boxes; the
+        level moves its particles at the end of every advance but the initial one and redistributes them in step().  derive() knows
+        "particle_count" and "total_particle_count" while one is attached (include/iamrx.h: iamrx_ns_set_particles)."""
+        check(lib().iamrx_ns_set_particles(self.h, None if pc is None else pc.h))
+        self._particles = pc
+
+    @property
+    def particles(self):
+        return getattr(self, "_particles", None)
+
     def set_data(self, which, mf):
         check(lib().iamrx_ns_set_data(self.h, int(which), mf.h))
 

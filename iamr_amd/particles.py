@@ -1,0 +1,235 @@
+"""Tracer particles: the ctypes view of iamrx_particles_* (include/iamrx.h; csrc/k_particles.hip) and the host-side particle files.
+
+The container follows AMReX's AmrTracerParticleContainer as IAMR uses it (reference Source/NavierStokesBase.cpp:198-222, 3751-4057).  AMReX
+is not part of the reference tree, so the container's arithmetic is UNPINNED; tests/particles_numpy.py restates
+what is implemented.
+
+Files (no device needed):
+  read_particle_file   the reference's ASCII `particle_file`: a count on the first line, then one position per line
+  write_ascii          particles.particle_output_file: the count, then `x y z id cpu` per line, %.17g, sorted by id
+  write_particles_dir / read_particles_dir
+                       the `Particles/` directory of a checkpoint or plotfile -- THIS project's own format,
+                       not AMReX's binary particle format: a text `Header` and raw little-endian arrays
+"""
+import ctypes as C
+import os
+import numpy as np
+from .lib import lib, check
+
+PARTICLES_DIR = "Particles"          # the_ns_particle_file_name, NavierStokesBase.cpp:209
+_HEADER_MAGIC = "iamr_amd-particles-1"
+_FILES = (("xyz.f64", "<f8", 3), ("r.f64", "<f8", 3), ("id.i32", "<i4", 1), ("cpu.i32", "<i4", 1))
+
+
+def _dp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _ip(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+class Particles:
+    """device-resident tracer particles on the levels (geoms[l], layouts[l]), coarsest first; attach with NavierStokes.set_particles or
+    Amr.set_particles, which rebinds the container to that object's boxes"""
+
+    def __init__(self, geoms, layouts, ratio=2):
+        geoms, layouts = list(geoms), list(layouts)
+        if len(geoms) != len(layouts) or not geoms:
+            raise ValueError("Particles: one geometry per layout, at least one level")
+        from .lib import Geom
+        ga = (Geom * len(geoms))(*geoms)
+        la = (C.c_void_p * len(layouts))(*[l.h for l in layouts])
+        self._keep = (geoms, layouts)
+        self.h = C.c_void_p()
+        check(lib().iamrx_particles_create(len(geoms), ga, la, int(ratio), C.byref(self.h)))
+
+    @staticmethod
+    def for_level(ns):
+        return Particles([ns.geom], [ns.layout], 1)
+
+    @staticmethod
+    def for_hierarchy(amr):
+        return Particles([amr.level_geom(l) for l in range(amr.nlev)], amr.layouts, amr.ratio)
+
+    def add(self, xyz, ids=None, r=None, cpus=None):
+        """add particles at the positions xyz (n, 3); ids default to the container's counter (from 1).  Returns the number of particles
+        removed because they lie outside a non-periodic domain."""
+        x = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+        n = x.shape[0]
+        i = None if ids is None else np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(n))
+        c = None if cpus is None else np.ascontiguousarray(np.asarray(cpus, dtype=np.int32).reshape(n))
+        rr = None if r is None else np.ascontiguousarray(np.asarray(r, dtype=np.float64).reshape(n, 3))
+        rm = C.c_long()
+        check(lib().iamrx_particles_add(self.h, C.c_long(n), _dp(x), _dp(rr), _ip(i), _ip(c), C.byref(rm)))
+        return rm.value
+
+    def _counts(self):
+        per = (C.c_long * 8)()
+        tot, rm, nid = C.c_long(), C.c_long(), C.c_int()
+        check(lib().iamrx_particles_count(self.h, per, C.byref(tot), C.byref(nid), C.byref(rm)))
+        return list(per), tot.value, nid.value, rm.value
+
+    def count(self, lev=None):
+        """number of particles (on level lev)"""
+        per, tot, _, _ = self._counts()
+        return tot if lev is None else per[lev]
+
+    @property
+    def next_id(self):
+        return self._counts()[2]
+
+    @next_id.setter
+    def next_id(self, v):
+        check(lib().iamrx_particles_set_next_id(self.h, int(v)))
+
+    @property
+    def removed(self):
+        """particles removed beyond non-periodic domain faces so far"""
+        return self._counts()[3]
+
+    def set_fixed_dir(self, d):
+        check(lib().iamrx_particles_set_fixed_dir(self.h, int(d)))
+
+    def read(self):
+        """-> dict(xyz (n, 3), r (n, 3), id, cpu, level, box) in storage order (grouped by level and box)"""
+        n = self.count()
+        out = dict(xyz=np.zeros((n, 3)), r=np.zeros((n, 3)), id=np.zeros(n, np.int32), cpu=np.zeros(n, np.int32), level=np.zeros(n, np.int32),
+                   box=np.zeros(n, np.int32))
+        if n:
+            check(lib().iamrx_particles_read(self.h, _dp(out["xyz"]), _dp(out["r"]), _ip(out["id"]), _ip(out["cpu"]), _ip(out["level"]), _ip(out["box"])))
+        return out
+
+    def read_sorted(self):
+        """read(), sorted by id"""
+        d = self.read()
+        o = np.argsort(d["id"], kind="stable")
+        return {k: v[o] for k, v in d.items()}
+
+    def set_positions(self, xyz):
+        """overwrite the positions, in the storage order of read(); follow with redistribute()"""
+        x = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+        if x.shape[0] != self.count():
+            raise ValueError("set_positions: one position per particle")
+        check(lib().iamrx_particles_set_positions(self.h, _dp(x)))
+
+    def advect(self, lev, umac, dt):
+        """AdvectWithUmac for the particles of level lev on the caller's face MultiFabs umac[0..2]"""
+        check(lib().iamrx_particles_advect(self.h, int(lev), umac[0].h, umac[1].h, umac[2].h, C.c_double(dt)))
+
+    def redistribute(self, lev_min=0, lev_max=None, ngrow=0):
+        rm = C.c_long()
+        check(lib().iamrx_particles_redistribute(self.h, int(lev_min), 1000 if lev_max is None else int(lev_max), int(ngrow), C.byref(rm)))
+        return rm.value
+
+    def particle_count(self, lev, out, ocomp=0):
+        check(lib().iamrx_particles_derive_count(self.h, 0, int(lev), out.h, int(ocomp)))
+
+    def total_particle_count(self, lev, out, ocomp=0):
+        check(lib().iamrx_particles_derive_count(self.h, 1, int(lev), out.h, int(ocomp)))
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().iamrx_particles_destroy(self.h)
+        except Exception:
+            pass
+
+
+# ---- files (host only) --------------------------------------------------------------------------------------------------------------------
+def read_particle_file(path, slab_y=None):
+    """positions of the reference's ASCII particle file (InitFromAsciiFile with no extra data): the count, then one position per line.
+    Three numbers per line, or two for a two-dimensional file: (x, y) lifts to (x, slab_y, y) like inputs.lift_2d (slab_y: the mid-slab
+    coordinate).  -> (n, 3) float64"""
+    with open(path) as f:
+        tok = f.read().split("\n")
+    lines = [t.split() for t in tok if t.strip()]
+    if not lines or len(lines[0]) != 1:
+        raise ValueError(f"{path}: the first line must hold the number of particles")
+    n = int(lines[0][0])
+    if len(lines) - 1 < n:
+        raise ValueError(f"{path}: {n} particles announced, {len(lines) - 1} lines follow")
+    rows = lines[1:1 + n]
+    dim = {len(r) for r in rows}
+    if n and dim not in ({2}, {3}):
+        raise ValueError(f"{path}: every line must hold two or three coordinates")
+    out = np.zeros((n, 3))
+    for q, r in enumerate(rows):
+        v = [float(s) for s in r]
+        if len(v) == 2:
+            if slab_y is None:
+                raise ValueError(f"{path}: two-dimensional positions in a three-dimensional run")
+            out[q] = (v[0], slab_y, v[1])
+        else:
+            if slab_y is not None:
+                raise ValueError(f"{path}: three-dimensional positions in a two-dimensional run")
+            out[q] = v
+    return out
+
+
+def write_ascii(path, xyz, ids, cpus):
+    """particles.particle_output_file: the count, then `x y z id cpu` per particle with %.17g, sorted by id"""
+    xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    ids, cpus = np.asarray(ids).reshape(-1), np.asarray(cpus).reshape(-1)
+    o = np.argsort(ids, kind="stable")
+    with open(path, "w") as f:
+        f.write(f"{len(ids)}\n")
+        for q in o:
+            f.write("%.17g %.17g %.17g %d %d\n" % (xyz[q, 0], xyz[q, 1], xyz[q, 2], ids[q], cpus[q]))
+
+
+def read_ascii(path):
+    """what write_ascii wrote -> (xyz, ids, cpus)"""
+    with open(path) as f:
+        n = int(f.readline())
+        rows = [f.readline().split() for _ in range(n)]
+    xyz = np.array([[float(v) for v in r[:3]] for r in rows], dtype=np.float64).reshape(n, 3)
+    return xyz, np.array([int(r[3]) for r in rows], np.int32), np.array([int(r[4]) for r in rows], np.int32)
+
+
+def write_particles_dir(parent, xyz, r, ids, cpus, next_id):
+    """<parent>/Particles/: `Header` (text: magic, count, next id, then one line `file dtype columns` per array) and the raw little-endian
+    arrays, sorted by id.  This project's own format."""
+    d = os.path.join(parent, PARTICLES_DIR)
+    os.makedirs(d, exist_ok=True)
+    ids = np.asarray(ids, np.int32).reshape(-1)
+    o = np.argsort(ids, kind="stable")
+    arrs = (np.asarray(xyz, np.float64).reshape(-1, 3)[o], np.asarray(r, np.float64).reshape(-1, 3)[o], ids[o], np.asarray(cpus, np.int32).reshape(-1)[o])
+    with open(os.path.join(d, "Header"), "w") as f:
+        f.write(f"{_HEADER_MAGIC}\n{len(ids)}\n{int(next_id)}\n")
+        for name, dt, nc in _FILES:
+            f.write(f"{name} {dt} {nc}\n")
+    for (name, dt, nc), a in zip(_FILES, arrs):
+        np.ascontiguousarray(a).astype(dt).tofile(os.path.join(d, name))
+    return d
+
+
+def read_particles_dir(parent):
+    """-> dict(xyz, r, id, cpu, next_id) of <parent>/Particles/"""
+    d = os.path.join(parent, PARTICLES_DIR)
+    with open(os.path.join(d, "Header")) as f:
+        lines = [l.strip() for l in f if l.strip()]
+    if lines[0] != _HEADER_MAGIC:
+        raise ValueError(f"{d}/Header: not a particle directory of this project ({lines[0]!r})")
+    n, next_id = int(lines[1]), int(lines[2])
+    out = {"next_id": next_id}
+    for line, key in zip(lines[3:], ("xyz", "r", "id", "cpu")):
+        name, dt, nc = line.split()
+        a = np.fromfile(os.path.join(d, name), dtype=dt)
+        if a.size != n * int(nc):
+            raise ValueError(f"{d}/{name}: {a.size} values, the header announces {n} x {nc}")
+        out[key] = a.reshape(n, 3).astype(np.float64) if int(nc) == 3 else a.astype(np.int32)
+    return out
+
+
+def save(parent, pc):
+    """the container's particles into <parent>/Particles/"""
+    p = pc.read()
+    return write_particles_dir(parent, p["xyz"], p["r"], p["id"], p["cpu"], pc.next_id)
+
+
+def restore(parent, pc):
+    """add the particles of <parent>/Particles/ to the (empty) container, bit for bit, with the id counter"""
+    d = read_particles_dir(parent)
+    pc.add(d["xyz"], ids=d["id"], r=d["r"], cpus=d["cpu"])
+    pc.next_id = d["next_id"]

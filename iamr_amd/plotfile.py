@@ -345,7 +345,9 @@ def state_names(do_trac2=0, do_temp=0):
     return STATE_NAMES_3D + (["tracer2"] if do_trac2 else []) + (["temp", "divu", "dsdt"] if do_temp else [])
 
 
-DERIVE_NAMES = ["energy", "mag_vort", "avg_pressure"]          # derive_lst order (NS_setup.cpp:436-449; no particles, no time averages)
+DERIVE_NAMES = ["energy", "mag_vort", "avg_pressure"]          # derive_lst order (NS_setup.cpp:436-449; without particles and time averages)
+# with tracer particles (do_nspc, NS_setup.cpp:452-466): the two counts follow avg_pressure
+PARTICLE_DERIVE_NAMES = ["particle_count", "total_particle_count"]
 
 
 # "velocity_average" (NS_setup.cpp:412-431): one derived quantity of six plotfile components; declared only with ns.avg_interval > 0, and
@@ -353,12 +355,13 @@ DERIVE_NAMES = ["energy", "mag_vort", "avg_pressure"]          # derive_lst orde
 VEL_AVG_NAMES = ["x_vel_average", "y_vel_average", "z_vel_average", "x_vel_rms", "y_vel_rms", "z_vel_rms"]
 
 
-def plot_selection(state, plot_vars="ALL", derive_plot_vars="NONE", averaging=False):
+def plot_selection(state, plot_vars="ALL", derive_plot_vars="NONE", averaging=False, particles=False):
     """(indices of the state components, names of the derived quantities) a plotfile holds: amr.plot_vars picks state variables (ALL: every
     one), amr.derive_plot_vars derived ones (ALL: the derive list in its order; default NONE) -- Amr::initPltAndChk / fillDerivePlotVarList.
     Unknown names raise, as amrex::Amr aborts on them.  averaging (ns.avg_interval > 0): "velocity_average" exists, first in the derive
-    list; it is returned as its six component names VEL_AVG_NAMES (run.level_arrays derives them together)."""
-    known = (["velocity_average"] if averaging else []) + DERIVE_NAMES
+    list; it is returned as its six component names VEL_AVG_NAMES (run.level_arrays derives them together).  particles: a run with tracer
+    particles also knows PARTICLE_DERIVE_NAMES, after avg_pressure."""
+    known = (["velocity_average"] if averaging else []) + DERIVE_NAMES + (PARTICLE_DERIVE_NAMES if particles else [])
 
     def expand(names):
         return [c for nm in names for c in (VEL_AVG_NAMES if nm == "velocity_average" else [nm])]

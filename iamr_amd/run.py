@@ -85,7 +85,8 @@ def plot_names_and_filter(pr):
     pv = pr.get("plot_vars", "ALL")
     if pr.get("slab") and isinstance(pv, list):          # a 2-D inputs file names the plane's velocities x_velocity, y_velocity: y is the slab's z
         pv = ["z_velocity" if v == "y_velocity" else v for v in pv]
-    keep, der = plot_selection(state, pv, pr.get("derive_plot_vars", "NONE"), averaging=pr["params"].get("avg_interval", 0) > 0)
+    keep, der = plot_selection(state, pv, pr.get("derive_plot_vars", "NONE"), averaging=pr["params"].get("avg_interval", 0) > 0,
+                               particles=bool(pr.get("particles")))
     kept = {state[q] for q in keep} | set(der)
     return state + der, der, kept
 
@@ -101,17 +102,27 @@ def _plane(boxes, arrs, names):
     """the (x, z) plane of a 2-D run lifted onto a y-periodic slab (inputs.Inputs.lift_2d) as 2-D boxes / arrays / names: the boxes that
     start at y = 0, their first y-plane, the y-velocity (identically zero) dropped, z_velocity renamed"""
     import numpy as np
+    from .plotfile import PARTICLE_DERIVE_NAMES
     keep = [q for q, (lo, hi) in enumerate(boxes) if lo[1] == 0]
     comps = [0, 2] + list(range(3, len(names)))
+    # the particle counts are the one thing that varies across the slab (the particles sit in its middle): the plane holds their sum
+    cnt = [q for q, nm in enumerate(names) if nm in PARTICLE_DERIVE_NAMES]
+    flat = [q for q in range(len(names)) if q not in cnt]
     # what makes the slab a 2-D run: no variation across it, no flow along it (checked on everything written; enforce_plane keeps it so)
     for a in arrs:
-        scale = max(1.0, float(np.abs(a).max()))
-        dev = max(float(np.abs(a - a[:, :1]).max()), float(np.abs(a[..., 1]).max()))
+        scale = max(1.0, float(np.abs(a[..., flat]).max()))
+        dev = max(float(np.abs(a[..., flat] - a[:, :1][..., flat]).max()), float(np.abs(a[..., 1]).max()))
         if dev > 1e-8 * scale:
             raise RuntimeError(f"iamr_amd.run: the slab of a two-dimensional run lost its uniformity (deviation {dev:.3e}, scale {scale:.3e})")
     n2 = ["x_velocity", "y_velocity"] + list(names[3:])
-    return ([((boxes[q][0][0], boxes[q][0][2]), (boxes[q][1][0], boxes[q][1][2])) for q in keep],
-            [arrs[q][:, 0, :, :][..., comps].copy() for q in keep], n2)
+    planes = []
+    for q in keep:
+        pl = arrs[q][:, 0, :, :].copy()
+        if cnt:
+            foot = lambda b: (b[0][0], b[0][2], b[1][0], b[1][2])
+            pl[..., cnt] = sum(arrs[s][..., cnt].sum(axis=1) for s in range(len(boxes)) if foot(boxes[s]) == foot(boxes[q]))
+        planes.append(pl[..., comps].copy())
+    return ([((boxes[q][0][0], boxes[q][0][2]), (boxes[q][1][0], boxes[q][1][2])) for q in keep], planes, n2)
 
 
 def sum_lines(time, sums, pr=None):
@@ -156,6 +167,50 @@ def enforce_plane(levels, pr):
             lev.set_data(which, mf)
 
 
+def setup_particles(run, pr, say, restart_dir=None):
+    """tracer particles of a run with particles.* keys (NavierStokesBase::initParticleData / post_restart_particle,
+    NavierStokesBase.cpp:3808-3864): one container for the level or the hierarchy; at start-up the positions of particles.particle_init_file;
+    on a restart the checkpoint's Particles/ (unless particles.restart_from_nonparticle_chkfile), then particles.particle_restart_file is
+    added and particles.particle_output_file written.  A two-dimensional file lifts (x, y) to (x, mid-slab, y) and the particles never move
+    across the slab.  Returns the container or None."""
+    pp = pr.get("particles")
+    if not pp:
+        return None
+    from .lib import comm_rank
+    if comm_rank()[1] > 1:
+        raise NotImplementedError("iamr_amd.run: tracer particles (particles.*) on more than one rank are not implemented")
+    from . import particles as P
+    pc = P.Particles.for_hierarchy(run) if hasattr(run, "levels") else P.Particles.for_level(run)
+    slab_y = None
+    if pr.get("slab"):
+        pc.set_fixed_dir(1)
+        slab_y = 0.5 * (pr["prob_lo"][1] + pr["prob_hi"][1])
+    run.set_particles(pc)
+    if restart_dir is None:
+        if pp["init_file"]:
+            pc.add(P.read_particle_file(pp["init_file"], slab_y))
+    else:
+        if not pp["restart_from_nonparticle_chkfile"]:
+            P.restore(restart_dir, pc)
+        if pp["restart_file"]:
+            pc.add(P.read_particle_file(pp["restart_file"], slab_y))
+        if pp["output_file"]:
+            d = pc.read()
+            P.write_ascii(pp["output_file"], d["xyz"], d["id"], d["cpu"])
+    if pp["verbose"]:
+        say(f"PARTICLES: {pc.count()} (removed outside the domain: {pc.removed})")
+    return pc
+
+
+def plot_particles(run, pr, path):
+    """particles.particles_in_plotfile (NavierStokes.cpp:1201-1205): the plotfile gets the Particles/ directory of a checkpoint"""
+    pc = getattr(run, "particles", None)
+    if pc is not None and pr["particles"]["in_plotfile"]:
+        from .particles import save
+        save(path, pc)
+    return path
+
+
 def write_plot_amr(amr, lays, pr, N, step, root):
     """NavierStokesBase::writePlotFile role for the hierarchy: one AMReX plotfile with every level (the five state components).
     Collective: every rank calls it and writes the boxes it owns (plotfile.write_collective)."""
@@ -182,7 +237,7 @@ def write_plot_amr(amr, lays, pr, N, step, root):
         PlotFile(out_names, amr.time, [pr["prob_lo"][0], pr["prob_lo"][2]], [pr["prob_hi"][0], pr["prob_hi"][2]], levels).write(path)
     else:
         write_collective(PlotFile(out_names, amr.time, pr["prob_lo"], pr["prob_hi"], levels), path, [lay.owners for lay in lays], rank, world)
-    return path
+    return plot_particles(amr, pr, path)
 
 
 def main_amr(pr, inp, lib, N, rank=0, world=1, observe=None):
@@ -195,15 +250,19 @@ def main_amr(pr, inp, lib, N, rank=0, world=1, observe=None):
         # amr.restart (Amr::restart): grids, data, times and step counters come from the checkpoint, parameters from the inputs file
         from . import checkpoint
         g0 = lib.Geom.make(pr["n"], prob_lo=pr["prob_lo"], prob_hi=pr["prob_hi"], periodic=pr["periodic"])
-        amr = checkpoint.restart(pr["restart"], g0, N.ns_params(**pr["params"]), stop_time=pr["stop_time"], rank=rank, world=world)
+        # (the solvers' options are the run's, not the checkpoint's: a two-dimensional run restarts with its slab multigrid, see build_amr)
+        amr = checkpoint.restart(pr["restart"], g0, N.ns_params(**pr["params"]), opts=lib.mg_opts(slab=1 if pr.get("slab") else 0),
+                                 stop_time=pr["stop_time"], rank=rank, world=world)
         if pr.get("regrid"):
             amr.set_regrid(**pr["regrid"])
         lays = amr.layouts
         step = checkpoint.read_header(pr["restart"])["level_steps"][0]
         say(f"RESTART from {pr['restart']}: step {step}, time {amr.time:.12g}, levels {amr.nlev}")
+        setup_particles(amr, pr, say, pr["restart"])
     else:
         amr, lays, g0 = build_amr(pr, lib, N, world)
         amr.post_init(pr["stop_time"])
+        setup_particles(amr, pr, say)               # (nothing moves them during the initial iterations: NavierStokes.cpp:672-677)
         step = 0
         if amr.last_sum() is not None:          # ns.sum_interval > 0: the hierarchy summed its initial data (NavierStokes.cpp:1284-1285)
             say_sums(say, amr.last_sum()[1], amr.last_sum()[2], pr)
@@ -277,7 +336,7 @@ def write_plot(ns, lay, pr, N, step, root):
         pf = from_level_data(tuple(pr["n"]), tuple(pr["prob_lo"]), tuple(pr["prob_hi"]), lay.boxes, arrs, ns.time, step, names=out_names)
         pf.levels[0].owned = local_indices(lay)
         write_collective(pf, path, [lay.owners], rank, world)
-    return path
+    return plot_particles(ns, pr, path)
 
 
 def main(argv, observe=None):
@@ -332,13 +391,16 @@ def main(argv, observe=None):
     if pr.get("restart"):
         from . import checkpoint
         g = lib.Geom.make(pr["n"], prob_lo=pr["prob_lo"], prob_hi=pr["prob_hi"], periodic=pr["periodic"])
-        ns = checkpoint.restart(pr["restart"], g, N.ns_params(**pr["params"]), single_level=True, stop_time=pr["stop_time"], rank=rank, world=world)
+        ns = checkpoint.restart(pr["restart"], g, N.ns_params(**pr["params"]), opts=lib.mg_opts(slab=1 if pr.get("slab") else 0), single_level=True,
+                                stop_time=pr["stop_time"], rank=rank, world=world)
         lay = ns.layout
         step = checkpoint.read_header(pr["restart"])["level_steps"][0]
         say(f"RESTART from {pr['restart']}: step {step}, time {ns.time:.12g}")
+        setup_particles(ns, pr, say, pr["restart"])
     else:
         ns, lay, g, pr = build(inp, lib, N, world, pr)
         ns.post_init(pr["stop_time"])
+        setup_particles(ns, pr, say)
         step = 0
         # NavierStokes::post_init, NavierStokes.cpp:1284-1297: the sums of the initial data, which are also the first sample of the averages
         if sum_int > 0:

@@ -28,6 +28,7 @@ typedef struct iamrx_fluxreg_s* iamrx_fluxreg; /* amrex::FluxRegister of one coa
 typedef struct iamrx_mf_s* iamrx_mf;           /* MultiFab (device resident) */
 typedef struct iamrx_ns_s* iamrx_ns;           /* NavierStokes level object */
 typedef struct iamrx_syncreg_s* iamrx_syncreg; /* SyncRegister of one coarse/fine interface */
+typedef struct iamrx_particles_s* iamrx_particles; /* tracer particles of a level or a hierarchy (see below) */
 typedef struct iamrx_amr_s* iamrx_amr;         /* hierarchy of NavierStokes levels (the Amr / AmrLevel role for the hot path) */
 
 typedef struct iamrx_geom {
@@ -771,6 +772,47 @@ int iamrx_amr_sync_stats(iamrx_amr a, iamrx_mg_stats* sync_project, iamrx_mg_sta
  * (mac_sync_compute, viscous / scalar sync solves, SyncInterp), [4] level_sync (MLsyncProject), [5] regrid, [8 + l] advance of level l;
  * level_sections_ms[8 * l + i]: the sections of iamrx_ns_profile of level l (may be NULL). */
 int iamrx_amr_profile(iamrx_amr a, int enable, double sections_ms[16], double level_sections_ms[]);
+
+/* ---- tracer particles (k_particles.hip): the role of AMReX's AmrTracerParticleContainer as IAMR uses it (reference
+ * Source/NavierStokesBase.cpp:198-222, 3751-4057; Source/NavierStokes.cpp:672-677).  AMReX is not part of the reference tree, so the
+ * container's arithmetic is UNPINNED; tests/particles_numpy.py restates what is implemented.  One process only.
+ * A container lives on nlev levels (coarsest first, level 0 covers the domain, refined by `ratio`); particles are device resident and kept
+ * grouped by (level, box).  Attached to a level or a hierarchy (iamrx_ns_set_particles / iamrx_amr_set_particles) it is REBOUND to that
+ * object's own boxes, and again after every regrid; box indices then refer to those (merged) boxes. */
+int iamrx_particles_create(int nlev, const iamrx_geom* geoms /* [nlev] */, const iamrx_layout* layouts /* [nlev] */, int ratio, iamrx_particles* out);
+int iamrx_particles_destroy(iamrx_particles pc);
+/* n particles from host arrays: xyz[3 n]; r[3 n], ids[n], cpus[n] may be NULL (zeros; ids from the container's counter, which starts at 1; 0).
+ * They are placed by a redistribution over all levels; *removed (may be NULL): how many of all particles fell outside a non-periodic domain. */
+int iamrx_particles_add(iamrx_particles pc, long n, const double* xyz, const double* r, const int* ids, const int* cpus, long* removed);
+/* count[l] (l < nlev of the container; may be NULL), *total, *next_id, *removed_total (any may be NULL) */
+int iamrx_particles_count(iamrx_particles pc, long* per_level, long* total, int* next_id, long* removed_total);
+int iamrx_particles_set_next_id(iamrx_particles pc, int next_id);
+/* a coordinate the particles never move in (the slab direction of a lifted two-dimensional run); -1: none */
+int iamrx_particles_set_fixed_dir(iamrx_particles pc, int dir);
+/* every particle to host arrays of `total` entries (any may be NULL): xyz[3 n], r[3 n], id, cpu, level, box; in storage order */
+int iamrx_particles_read(iamrx_particles pc, double* xyz, double* r, int* id, int* cpu, int* level, int* box);
+/* overwrite the positions from xyz[3 n], in the storage order iamrx_particles_read reports (a caller that moves the particles itself);
+ * follow with iamrx_particles_redistribute */
+int iamrx_particles_set_positions(iamrx_particles pc, const double* xyz);
+/* TracerParticleContainer::AdvectWithUmac for the particles of level lev on caller-owned face arrays (on the level's boxes, the ghost faces
+ * the stencils reach filled): pass 1  r = x, x += dt/2 v(x);  pass 2  x = r + dt v(x), r = v;  v_d trilinear in u_mac[d].  Nothing moves between
+ * boxes and no periodic wrap is applied between the passes.  At non-periodic domain faces the stencil indices are clamped to the domain. */
+int iamrx_particles_advect(iamrx_particles pc, int lev, iamrx_mf umac_x, iamrx_mf umac_y, iamrx_mf umac_z, double dt);
+/* Redistribute(lev_min, lev_max, ngrow) for the particles of the levels >= lev_min: periodic wrap; the finest level <= lev_max whose boxes hold
+ * the particle's cell; failing that and with ngrow > 0 the box of lev_min with the lowest index whose ngrow-grown region holds it (or a periodic
+ * image of it, which the particle then takes; of several images the one shifted in the fewest directions); a particle outside a non-periodic domain is removed and counted in *removed; a particle that
+ * cannot be placed is an error (the container stays as it was). */
+int iamrx_particles_redistribute(iamrx_particles pc, int lev_min, int lev_max, int ngrow, long* removed);
+/* which = 0: particle_count (particles of level lev per valid cell); 1: total_particle_count (plus the finer levels' counts coarsened onto
+ * lev, NavierStokesBase.cpp:3996-4048); out: cell-centred on the container's boxes of level lev */
+int iamrx_particles_derive_count(iamrx_particles pc, int which, int lev, iamrx_mf out, int ocomp);
+/* attach (pc = NULL: detach).  A level on its own advects its particles at the end of every advance but the initial one and redistributes in
+ * iamrx_ns_step; a hierarchy follows NavierStokes::advance / post_timestep_particle / post_regrid.  iamrx_ns_derive knows "particle_count"
+ * and "total_particle_count" while a container is attached.  The container must outlive the attachment or be detached first. */
+int iamrx_ns_set_particles(iamrx_ns ns, iamrx_particles pc);
+int iamrx_amr_set_particles(iamrx_amr a, iamrx_particles pc);
+int iamrx_ns_get_particles(iamrx_ns ns, iamrx_particles* pc /* NULL handle: none; not to be destroyed by the caller unless it created it */);
+int iamrx_amr_get_particles(iamrx_amr a, iamrx_particles* pc);
 
 #ifdef __cplusplus
 }
