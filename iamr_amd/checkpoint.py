@@ -246,7 +246,7 @@ def write(run, root, step, max_level=None):
         with open(os.path.join(path, "Header"), "w") as f:
             f.write("\n".join(H) + "\n")
     pc = getattr(run, "particles", None)
-    if pc is not None:                          # NavierStokesBase::checkPoint: NSPC->Checkpoint(dir, "Particles"); single-rank runs only
+    if pc is not None:                          # NavierStokesBase::checkPoint: NSPC->Checkpoint(dir, "Particles"); collective (particles.save)
         from .particles import save
         save(path, pc)
     barrier()

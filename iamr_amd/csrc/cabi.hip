@@ -1704,8 +1704,7 @@ int iamrx_particles_destroy(iamrx_particles pc) { IAMRX_TRY if (pc) { particle_h
 int iamrx_particles_add(iamrx_particles pc, long n, const double* xyz, const double* r, const int* ids, const int* cpus, long* removed)
 {
     IAMRX_TRY
-    if (n > 0 && !xyz) throw Error("iamrx_particles_add: null positions");
-    const long rm = pc->pc->add(n, xyz, r, ids, cpus);
+    const long rm = pc->pc->add(n, xyz, r, ids, cpus);          // (refuses null positions itself: on several ranks every rank has to)
     if (removed) *removed = rm;
     IAMRX_CATCH
 }
@@ -1718,6 +1717,7 @@ int iamrx_particles_count(iamrx_particles pc, long* per_level, long* total, int*
     if (removed_total) *removed_total = pc->pc->n_removed;
     IAMRX_CATCH
 }
+int iamrx_particles_count_global(iamrx_particles pc, long* per_level, long* total) { IAMRX_TRY pc->pc->global_count(per_level, total); IAMRX_CATCH }
 int iamrx_particles_set_next_id(iamrx_particles pc, int next_id) { IAMRX_TRY if (next_id < 1) throw Error("iamrx_particles_set_next_id: ids start at 1"); pc->pc->next_id = next_id; IAMRX_CATCH }
 int iamrx_particles_set_fixed_dir(iamrx_particles pc, int dir) { IAMRX_TRY if (dir < -1 || dir > 2) throw Error("iamrx_particles_set_fixed_dir: -1 .. 2"); pc->pc->fixed_dir = dir; IAMRX_CATCH }
 int iamrx_particles_read(iamrx_particles pc, double* xyz, double* r, int* id, int* cpu, int* level, int* box)

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <numeric>
 #include <cmath>
+#include <cstring>
 
 namespace iamrx {
 
@@ -66,8 +67,12 @@ __device__ __forceinline__ int wave_add_one(int* ctr, int k)
     return slot;
 }
 
-// the new group of particle p (written to key[p]; -1: leaves) -> the counter it adds to
-__device__ int place_one(const PHierD& H, const PArrays& a, long p, int lev_min, int lev_max, int ngrow, int nkeys, int* __restrict__ key)
+// the new group of particle p (written to key[p]; -1: leaves) -> the counter it adds to.  MR (several ranks): the box found is one of the
+// level's global list; a particle whose box rank q owns gets key -2 - q, its level and global box go to dlev / dbox (the record that
+// travels), and it counts under nkeys + 3 + q
+template <bool MR>
+__device__ int place_one(const PHierD& H, const PArrays& a, long p, int lev_min, int lev_max, int ngrow, int nkeys, int* __restrict__ key, int me,
+                         int* __restrict__ dlev, int* __restrict__ dbox)
 {
     double x[3] = {a.x[0][p], a.x[1][p], a.x[2][p]};
     bool out = false;
@@ -76,12 +81,12 @@ __device__ int place_one(const PHierD& H, const PArrays& a, long p, int lev_min,
         if (!(x[e] >= H.plo[e] && x[e] < H.phi[e])) out = true;          // also a NaN
     }
     if (out) { key[p] = -1; return nkeys; }
-    int found = -1;
+    int found = -1, flev = lev_min;                         // found: index in the global box list of level flev
     for (int L = lev_max; L >= lev_min && found < 0; --L) {
         int c[3];
         cell_of(H, L, x, c);
         const int b = box_at(H.L[L], c[0], c[1], c[2]);
-        if (b >= 0) found = H.L[L].key0 + b;
+        if (b >= 0) { found = b; flev = L; }
     }
     if (found < 0 && ngrow > 0) {
         // a box of lev_min whose ngrow-grown region holds the cell, or a periodic image of it: the lowest box index.  Every such box
@@ -107,7 +112,7 @@ __device__ int place_one(const PHierD& H, const PArrays& a, long p, int lev_min,
                     const int b = box_at(lv, q[0], q[1], q[2]);
                     const int ns = (sh[0] != 0) + (sh[1] != 0) + (sh[2] != 0);
                     if (b < 0 || (best >= 0 && (b > best || (b == best && ns >= best_ns)))) continue;
-                    const BoxD bx = lv.boxes[b];
+                    const BoxD bx = lv.gboxes[b];
                     bool in = true;
                     for (int e = 0; e < 3; ++e) {
                         const int ci = c[e] + sh[e] * lv.n[e] + lv.dlo[e];
@@ -116,21 +121,29 @@ __device__ int place_one(const PHierD& H, const PArrays& a, long p, int lev_min,
                     if (in) { best = b; best_ns = ns; bs[0] = sh[0]; bs[1] = sh[1]; bs[2] = sh[2]; }
                 }
         if (best >= 0) {
-            found = lv.key0 + best;
+            found = best;
             for (int e = 0; e < 3; ++e) if (bs[e] != 0) x[e] = x[e] + (double)bs[e] * (H.phi[e] - H.plo[e]);    // the image next to the box
         }
     }
     for (int e = 0; e < 3; ++e) a.x[e][p] = x[e];
     if (found < 0) { key[p] = -1; return nkeys + 1; }
+    if (MR) {
+        const int q = H.L[flev].owner[found];
+        if (q != me) { key[p] = -2 - q; dlev[p] = flev; dbox[p] = found; return nkeys + 3 + q; }
+        found = H.L[flev].lidx[found];
+    }
+    found += H.L[flev].key0;
     key[p] = found;
     return found;
 }
 
 
 // key: group of the particle after the redistribution (level's key0 + box), -1 removed.  counts: [nkeys] group sizes, then
-// [nkeys] removed beyond a non-periodic face, [nkeys + 1] could not be placed, [nkeys + 2] invalid (id <= 0, dropped)
+// [nkeys] removed beyond a non-periodic face, [nkeys + 1] could not be placed, [nkeys + 2] invalid (id <= 0, dropped); MR: then
+// [nkeys + 3 + q] leaves for rank q
+template <bool MR>
 __global__ void __launch_bounds__(PB) k_part_place(PHierD H, PArrays a, long n, int lev_min, int lev_max, int ngrow, int nkeys, int* __restrict__ key,
-                                                   int* __restrict__ counts)
+                                                   int* __restrict__ counts, int me, int* __restrict__ dlev, int* __restrict__ dbox)
 {
     const long p = (long)blockIdx.x * PB + threadIdx.x;
     if (p >= n) return;
@@ -139,7 +152,7 @@ __global__ void __launch_bounds__(PB) k_part_place(PHierD H, PArrays a, long n, 
     const int l0 = a.lev[p];
     if (a.id[p] <= 0) { key[p] = -1; cidx = nkeys + 2; }
     else if (l0 < lev_min) { cidx = H.L[l0].key0 + a.box[p]; key[p] = cidx; }      // not this call's business
-    else cidx = place_one(H, a, p, lev_min, lev_max, ngrow, nkeys, key);
+    else cidx = place_one<MR>(H, a, p, lev_min, lev_max, ngrow, nkeys, key, me, dlev, dbox);
     wave_add_one(counts, cidx);
 }
 
@@ -170,6 +183,82 @@ __global__ void __launch_bounds__(PB) k_part_scatter(PHierD H, PArrays a, PArray
     while (L + 1 < H.nlev && k >= H.L[L + 1].key0) ++L;
     for (int e = 0; e < 3; ++e) { o.x[e][q] = a.x[e][p]; o.r[e][q] = a.r[e][p]; }
     o.id[q] = a.id[p]; o.cpu[q] = a.cpu[p];
+    o.lev[q] = L; o.box[q] = k - H.L[L].key0;
+}
+
+// ---- migration (several ranks) ----------------------------------------------------------------------------------------------------------
+// A record is NREC doubles: x, y, z, r0, r1, r2, id, cpu, level, global box (32-bit integers are exact as doubles).  The buffer for / from
+// one peer holds its cnt records field by field (field f of record i at f * cnt + i), the peers' parts one after another in rank order.
+constexpr int NREC = 10;
+
+// the leavers (key <= -2) into the send buffer; sendcnt[q]: how many leave for rank q (the place kernel's counters), scursor[q] = 0
+__global__ void __launch_bounds__(PB) k_part_pack(PArrays a, long n, const int* __restrict__ key, const int* __restrict__ dlev, const int* __restrict__ dbox,
+                                                  const int* __restrict__ sendcnt, int* __restrict__ scursor, double* __restrict__ buf)
+{
+    const long p = (long)blockIdx.x * PB + threadIdx.x;
+    if (p >= n) return;
+    const int k = key[p];
+    if (k > -2) return;
+    const int q = -2 - k;
+    const int slot = wave_add_one(scursor, q);
+    long start = 0;
+    for (int u = 0; u < q; ++u) start += sendcnt[u];
+    const long cnt = sendcnt[q];
+    double* b = buf + start * NREC + slot;
+    for (int e = 0; e < 3; ++e) { b[e * cnt] = a.x[e][p]; b[(3 + e) * cnt] = a.r[e][p]; }
+    b[6 * cnt] = (double)a.id[p]; b[7 * cnt] = (double)a.cpu[p];
+    b[8 * cnt] = (double)dlev[p]; b[9 * cnt] = (double)dbox[p];
+}
+
+// arrival j of nrecv -> the part of the receive buffer it lies in (rstart[q]: first arrival from rank q, rstart[nranks] = nrecv) and its
+// index there
+__device__ __forceinline__ const double* arrival(const double* __restrict__ rbuf, const int* __restrict__ rstart, int nranks, long j, long& cnt)
+{
+    int q = 0;
+    while (q + 1 < nranks && j >= rstart[q + 1]) ++q;
+    cnt = rstart[q + 1] - rstart[q];
+    return rbuf + (long)rstart[q] * NREC + (j - rstart[q]);
+}
+
+// files the arrivals: akey[j] = the group of arrival j, from the level and the global box its sender found (nothing is placed a second
+// time: the sender may have moved the particle to the periodic image next to its box); counts[group] += 1.  A record that names no box of
+// this rank counts under nkeys + 1 and gets key -1
+__global__ void __launch_bounds__(PB) k_part_file(PHierD H, const double* __restrict__ rbuf, const int* __restrict__ rstart, int nranks, long nrecv, int me,
+                                                  int nkeys, int* __restrict__ akey, int* __restrict__ counts)
+{
+    const long j = (long)blockIdx.x * PB + threadIdx.x;
+    if (j >= nrecv) return;
+    long cnt;
+    const double* b = arrival(rbuf, rstart, nranks, j, cnt);
+    const int L = (int)b[8 * cnt], gb = (int)b[9 * cnt];
+    int k = -1;
+    if (L >= 0 && L < H.nlev && gb >= 0 && gb < H.L[L].ngbox && H.L[L].owner[gb] == me) k = H.L[L].key0 + H.L[L].lidx[gb];
+    akey[j] = k;
+    wave_add_one(counts, k < 0 ? nkeys + 1 : k);
+}
+
+// the one scatter of a redistribution over ranks: threads 0 .. n - 1 the particles held (leavers and removed ones have a negative key),
+// n .. n + nrecv - 1 the arrivals
+__global__ void __launch_bounds__(PB) k_part_scatter_ranks(PHierD H, PArrays a, PArrays o, long n, const int* __restrict__ key, const double* __restrict__ rbuf,
+                                                           const int* __restrict__ rstart, int nranks, long nrecv, const int* __restrict__ akey,
+                                                           const int* __restrict__ offs, int* __restrict__ cursor)
+{
+    const long t = (long)blockIdx.x * PB + threadIdx.x;
+    if (t >= n + nrecv) return;
+    const int k = t < n ? key[t] : akey[t - n];
+    if (k < 0) return;
+    const long q = (long)offs[k] + wave_add_one(cursor, k);
+    int L = 0;
+    while (L + 1 < H.nlev && k >= H.L[L + 1].key0) ++L;
+    if (t < n) {
+        for (int e = 0; e < 3; ++e) { o.x[e][q] = a.x[e][t]; o.r[e][q] = a.r[e][t]; }
+        o.id[q] = a.id[t]; o.cpu[q] = a.cpu[t];
+    } else {
+        long cnt;
+        const double* b = arrival(rbuf, rstart, nranks, t - n, cnt);
+        for (int e = 0; e < 3; ++e) { o.x[e][q] = b[e * cnt]; o.r[e][q] = b[(3 + e) * cnt]; }
+        o.id[q] = (int)b[6 * cnt]; o.cpu[q] = (int)b[7 * cnt];
+    }
     o.lev[q] = L; o.box[q] = k - H.L[L].key0;
 }
 
@@ -329,7 +418,7 @@ void Particles::reserve(long cap)
 void Particles::define(const std::vector<Geometry>& geoms, const std::vector<LayoutP>& layouts, int ratio)
 {
     auto& ctx = Context::get();
-    if (ctx.comm->nranks > 1) throw Error("iamrx Particles: particles across ranks are not implemented");
+    const bool ranks = ctx.comm->nranks > 1;
     const int nl = (int)layouts.size();
     if (nl < 1 || nl > PHierD::MAXLEV || geoms.size() != layouts.size()) throw Error("iamrx Particles: 1 .. 8 levels, one geometry per level");
     if (nl > 1 && ratio < 2) throw Error("iamrx Particles: bad refinement ratio");
@@ -351,15 +440,16 @@ void Particles::define(const std::vector<Geometry>& geoms, const std::vector<Lay
         PLevelD& lv = m_h.L[l];
         int gr = 0;
         for (int e = 0; e < 3; ++e) gr = std::gcd(gr, g.domain.len(e));
-        for (int q = 0; q < lay.nlocal(); ++q)
-            for (int e = 0; e < 3; ++e) { gr = std::gcd(gr, lay.lbox(q).lo[e] - g.domain.lo[e]); gr = std::gcd(gr, lay.lbox(q).len(e)); }
+        const int nb = (int)lay.boxes.size();                 // the global list: what is built here is the same on every rank
+        for (int q = 0; q < nb; ++q)
+            for (int e = 0; e < 3; ++e) { gr = std::gcd(gr, lay.boxes[q].lo[e] - g.domain.lo[e]); gr = std::gcd(gr, lay.boxes[q].len(e)); }
         gr = std::max(gr, 1);
         lv.gran = gr;
         size_t nt = 1;
         for (int e = 0; e < 3; ++e) { lv.dlo[e] = g.domain.lo[e]; lv.n[e] = g.domain.len(e); lv.tn[e] = lv.n[e] / gr; lv.dx[e] = g.dx[e]; nt *= (size_t)lv.tn[e]; }
         std::vector<int> tab(nt, -1);
-        for (int q = 0; q < lay.nlocal(); ++q) {
-            const BoxD& b = lay.lbox(q);
+        for (int q = 0; q < nb; ++q) {
+            const BoxD& b = lay.boxes[q];
             for (int e = 0; e < 3; ++e)
                 if (b.lo[e] < g.domain.lo[e] || b.hi[e] > g.domain.hi[e]) throw Error("iamrx Particles: a box reaches outside its level's domain");
             for (int k = (b.lo[2] - lv.dlo[2]) / gr; k <= (b.hi[2] - lv.dlo[2]) / gr; ++k)
@@ -372,6 +462,24 @@ void Particles::define(const std::vector<Geometry>& geoms, const std::vector<Lay
         IAMRX_HIP_CHECK(hipMemcpy(dt, tab.data(), nt * sizeof(int), hipMemcpyHostToDevice));
         m_tabs.push_back(dt);
         lv.tab = dt; lv.boxes = lay.d_boxes; lv.key0 = key0; lv.nbox = lay.nlocal();
+        lv.gboxes = lay.d_boxes; lv.owner = nullptr; lv.lidx = nullptr; lv.ngbox = nb;
+        if (ranks) {                                          // one block: owner[nb], lidx[nb], then the nb global boxes
+            static_assert(sizeof(BoxD) % sizeof(int) == 0, "BoxD is made of ints");
+            std::vector<int> h((size_t)2 * nb + (size_t)nb * (sizeof(BoxD) / sizeof(int)));
+            // (Layout::local_of is this rank's view; the local index ON THE OWNER is the box's place among its owner's boxes)
+            std::vector<int> seen(ctx.comm->nranks, 0);
+            for (int q = 0; q < nb; ++q) {
+                if (lay.owner[q] < 0 || lay.owner[q] >= ctx.comm->nranks) throw Error("iamrx Particles: a box is owned by no rank of the communicator");
+                h[q] = lay.owner[q];
+                h[(size_t)nb + q] = seen[lay.owner[q]]++;
+            }
+            if (nb > 0) std::memcpy(h.data() + 2 * (size_t)nb, lay.boxes.data(), (size_t)nb * sizeof(BoxD));
+            int* dg = nullptr;
+            IAMRX_HIP_CHECK(hipMalloc(&dg, std::max<size_t>(h.size(), 1) * sizeof(int)));
+            IAMRX_HIP_CHECK(hipMemcpy(dg, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+            m_tabs.push_back(dg);
+            lv.owner = dg; lv.lidx = dg + nb; lv.gboxes = (const BoxD*)(dg + 2 * (size_t)nb);
+        }
         key0 += lay.nlocal();
     }
     m_nkeys = key0;
@@ -383,7 +491,47 @@ void Particles::define(const std::vector<Geometry>& geoms, const std::vector<Lay
 
 long Particles::add(long n, const double* xyz, const double* r, const int* ids, const int* cpus)
 {
-    if (n < 0) throw Error("iamrx Particles::add: negative count");
+    auto& ctx = Context::get();
+    const int nr = ctx.comm->nranks, me = ctx.comm->rank;
+    bool bad = n < 0 || (n > 0 && !xyz);
+    if (nr > 1) {
+        // one allreduce (max): slot q the number of particles rank q adds without ids, then the id counter the ranks' ids ask for, then
+        // whether a rank was called with arguments it must refuse (every rank then throws)
+        std::vector<double> v((size_t)nr + 2, 0.0);
+        if (!bad) {
+            if (!ids) v[me] = (double)n;
+            else for (long p = 0; p < n; ++p) v[nr] = std::max(v[nr], (double)ids[p] + 1.0);
+        }
+        v[(size_t)nr + 1] = bad ? 1.0 : 0.0;
+        ctx.comm->allreduce(v.data(), nr + 2, ReduceOp::Max);
+        bad = v[(size_t)nr + 1] > 0.0;
+        if (!bad) {
+            // without ids the new ids continue the counter in rank order: rank q's follow rank q - 1's
+            long before = 0, all = 0;
+            for (int q = 0; q < nr; ++q) { if (q < me) before += (long)v[q]; all += (long)v[q]; }
+            const int first = next_id + (int)before;
+            next_id = std::max(next_id + (int)all, (int)v[nr]);
+            if (n > 0 && !ids) {
+                std::vector<int> mine((size_t)n);
+                std::iota(mine.begin(), mine.end(), first);
+                const int keep = next_id;
+                add_local(n, xyz, r, mine.data(), cpus);
+                next_id = keep;
+            } else if (n > 0) {
+                const int keep = next_id;
+                add_local(n, xyz, r, ids, cpus);
+                next_id = keep;
+            }
+        }
+    }
+    if (bad) throw Error(n < 0 ? "iamrx Particles::add: negative count" : "iamrx Particles::add: null positions, or a call another rank had to refuse");
+    if (nr == 1) add_local(n, xyz, r, ids, cpus);
+    return redistribute(0, nlevels() - 1, 0);
+}
+
+// the caller's particles onto the end of this rank's arrays (level 0, box 0 until the redistribution that follows)
+void Particles::add_local(long n, const double* xyz, const double* r, const int* ids, const int* cpus)
+{
     if (n > 0) {
         auto& ctx = Context::get();
         reserve(m_np + n);
@@ -405,9 +553,8 @@ long Particles::add(long n, const double* xyz, const double* r, const int* ids, 
         IAMRX_HIP_CHECK(hipMemcpyAsync(m_a.box + m_np, hi.data() + 3 * (size_t)n, n * sizeof(int), hipMemcpyHostToDevice, ctx.stream));
         ctx.sync();                                            // the host vectors go
         m_np += n;
-        m_lev_n[0] += n;                                       // provisional: level 0, box 0 until the redistribution below
+        m_lev_n[0] += n;                                       // provisional: level 0, box 0 until the redistribution
     }
-    return redistribute(0, nlevels() - 1, 0);
 }
 
 void Particles::read(double* xyz, double* r, int* id, int* cpu, int* lev, int* box) const
@@ -475,18 +622,20 @@ long Particles::redistribute(int lev_min, int lev_max, int ngrow)
     if (ngrow < 0) throw Error("iamrx Particles::redistribute: negative ngrow");
     if (ngrow > 0) {
         const Layout& lay = *m_layouts[lev_min];
-        for (int q = 0; q < lay.nlocal(); ++q)
+        for (auto& b : lay.boxes)                              // the global list: every rank decides alike
             for (int e = 0; e < 3; ++e)
-                if (lay.lbox(q).len(e) < ngrow) throw Error("iamrx Particles::redistribute: ngrow exceeds the length of a box");
+                if (b.len(e) < ngrow) throw Error("iamrx Particles::redistribute: ngrow exceeds the length of a box");
     }
-    if (m_np == 0) return 0;
     auto& ctx = Context::get();
+    if (ctx.comm->nranks > 1) return redistribute_ranks(lev_min, lev_max, ngrow);
+    if (m_np == 0) return 0;
     const long n = m_np;
     const int nk = m_nkeys;
     int* ws = (int*)ctx.alloc(((size_t)n + 3 * (size_t)nk + 3) * sizeof(int));
     int *key = ws, *counts = ws + n, *offs = counts + nk + 3, *cursor = offs + nk;
     IAMRX_HIP_CHECK(hipMemsetAsync(counts, 0, (nk + 3) * sizeof(int), ctx.stream));
-    hipLaunchKernelGGL(k_part_place, dim3(nblocks(n)), dim3(PB), 0, ctx.stream, m_h, m_a, n, lev_min, lev_max, ngrow, nk, key, counts);
+    hipLaunchKernelGGL(k_part_place<false>, dim3(nblocks(n)), dim3(PB), 0, ctx.stream, m_h, m_a, n, lev_min, lev_max, ngrow, nk, key, counts, 0,
+                       (int*)nullptr, (int*)nullptr);
     hipLaunchKernelGGL(k_part_prefix, dim3(1), dim3(PB), 0, ctx.stream, nk, counts, offs, cursor);
     std::vector<int> hc(nk + 3);
     IAMRX_HIP_CHECK(hipMemcpyAsync(hc.data(), counts, (nk + 3) * sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
@@ -515,6 +664,113 @@ long Particles::redistribute(int lev_min, int lev_max, int ngrow)
     return hc[nk];
 }
 
+// Several ranks.  Collectives: ONE allreduce (the nranks x nranks matrix of send counts, each rank its row, with the numbers of particles
+// that cannot be placed and that were removed) and ONE exchange, whatever the number of particles; a rank without particles or boxes
+// takes part in both.  Read-backs: the place kernel's counters, and the group counters again once the arrivals are filed.
+long Particles::redistribute_ranks(int lev_min, int lev_max, int ngrow)
+{
+    auto& ctx = Context::get();
+    const int nr = ctx.comm->nranks, me = ctx.comm->rank, fin = nlevels() - 1;
+    const long n = m_np;
+    const int nk = m_nkeys, nc = nk + 3 + nr;
+    // ints: key[n], dlev[n], dbox[n], counts[nc], offs[nk], cursor[nk], scursor[nr], rstart[nr + 1]; then the positions as they were
+    const size_t nint = 3 * (size_t)n + (size_t)nc + 2 * (size_t)nk + 2 * (size_t)nr + 1;
+    const size_t ioff = (nint * sizeof(int) + 7) / 8 * 8;
+    char* ws = (char*)ctx.alloc(ioff + 3 * (size_t)n * sizeof(double) + 8);
+    int *key = (int*)ws, *dlev = key + n, *dbox = dlev + n, *counts = dbox + n, *offs = counts + nc, *cursor = offs + nk, *scursor = cursor + nk,
+        *rstart = scursor + nr;
+    double* xkeep = (double*)(ws + ioff);
+    IAMRX_HIP_CHECK(hipMemsetAsync(counts, 0, ((size_t)nc + 2 * (size_t)nk + nr) * sizeof(int), ctx.stream));      // counts, offs, cursor, scursor
+    if (n > 0) {
+        // the place kernel writes the wrapped / image position in place: kept aside so that a collective error leaves the container as it was
+        for (int e = 0; e < 3; ++e) IAMRX_HIP_CHECK(hipMemcpyAsync(xkeep + (size_t)e * n, m_a.x[e], n * sizeof(double), hipMemcpyDeviceToDevice, ctx.stream));
+        hipLaunchKernelGGL(k_part_place<true>, dim3(nblocks(n)), dim3(PB), 0, ctx.stream, m_h, m_a, n, lev_min, lev_max, ngrow, nk, key, counts, me, dlev, dbox);
+    }
+    std::vector<int> hc(nc);
+    IAMRX_HIP_CHECK(hipMemcpyAsync(hc.data(), counts, nc * sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+    ctx.sync();
+    std::vector<double> M((size_t)nr * nr + 2, 0.0);
+    for (int q = 0; q < nr; ++q) M[(size_t)me * nr + q] = (double)hc[nk + 3 + q];
+    M[(size_t)nr * nr] = (double)hc[nk + 1];
+    M[(size_t)nr * nr + 1] = (double)hc[nk];
+    ctx.comm->allreduce(M.data(), nr * nr + 2, ReduceOp::Sum);
+    const long nbad = (long)M[(size_t)nr * nr], removed = (long)M[(size_t)nr * nr + 1];
+    if (nbad > 0) {
+        for (int e = 0; e < 3 && n > 0; ++e) IAMRX_HIP_CHECK(hipMemcpyAsync(m_a.x[e], xkeep + (size_t)e * n, n * sizeof(double), hipMemcpyDeviceToDevice, ctx.stream));
+        ctx.free(ws);
+        throw Error("iamrx Particles::redistribute(" + std::to_string(lev_min) + ", " + std::to_string(lev_max) + ", " + std::to_string(ngrow) + "): " +
+                    std::to_string(nbad) + " particles are in no box of levels " + std::to_string(lev_min) + " .. " + std::to_string(lev_max));
+    }
+    long nsend = 0, nrecv = 0;
+    std::vector<int> hr(nr + 1, 0);
+    for (int q = 0; q < nr; ++q) { nsend += hc[nk + 3 + q]; hr[q + 1] = hr[q] + (int)M[(size_t)q * nr + me]; }
+    nrecv = hr[nr];
+    double *sbuf = nullptr, *rbuf = nullptr;
+    int* akey = nullptr;
+    if (nsend > 0) {
+        sbuf = (double*)ctx.alloc((size_t)nsend * NREC * sizeof(double));
+        hipLaunchKernelGGL(k_part_pack, dim3(nblocks(n)), dim3(PB), 0, ctx.stream, m_a, n, key, dlev, dbox, counts + nk + 3, scursor, sbuf);
+    }
+    if (nrecv > 0) {
+        rbuf = (double*)ctx.alloc((size_t)nrecv * NREC * sizeof(double));
+        akey = (int*)ctx.alloc((size_t)nrecv * sizeof(int));
+    }
+    // a peer appears on both sides exactly where the matrix says so: every rank read the same matrix
+    std::vector<Message> sends, recvs;
+    size_t so = 0;
+    for (int q = 0; q < nr; ++q) {
+        const size_t sc = (size_t)hc[nk + 3 + q], rc = (size_t)(hr[q + 1] - hr[q]);
+        if (sc > 0) sends.push_back({q, sbuf + so * NREC, sc * NREC});
+        if (rc > 0) recvs.push_back({q, rbuf + (size_t)hr[q] * NREC, rc * NREC});
+        so += sc;
+    }
+    if (!sends.empty() || !recvs.empty()) ctx.comm->exchange(sends, recvs, ctx.stream);
+    if (nrecv > 0) {
+        ctx.upload_async(rstart, hr.data(), (nr + 1) * sizeof(int));
+        hipLaunchKernelGGL(k_part_file, dim3(nblocks(nrecv)), dim3(PB), 0, ctx.stream, m_h, rbuf, rstart, nr, nrecv, me, nk, akey, counts);
+        IAMRX_HIP_CHECK(hipMemcpyAsync(hc.data(), counts, (nk + 2) * sizeof(int), hipMemcpyDeviceToHost, ctx.stream));      // the groups with the arrivals
+    }
+    if (nk > 0) hipLaunchKernelGGL(k_part_prefix, dim3(1), dim3(PB), 0, ctx.stream, nk, counts, offs, cursor);
+    if (nrecv > 0) ctx.sync();
+    const long misfiled = nrecv > 0 ? hc[nk + 1] : 0;          // (the place kernel's count there was zero, or the error above was thrown)
+    long total = 0;
+    for (int l = 0; l <= fin; ++l) {
+        long s = 0;
+        for (int q = 0; q < m_h.L[l].nbox; ++q) s += hc[m_h.L[l].key0 + q];
+        m_lev_start[l] = total; m_lev_n[l] = s;
+        total += s;
+    }
+    const long cap = std::max(m_cap, total > m_cap ? std::max(total, std::max(1024L, 2 * m_cap)) : 0L);
+    if (cap > 0 && (n > 0 || nrecv > 0)) {
+        void* nb = ctx.alloc(block_bytes(cap));
+        PArrays na;
+        carve(na, nb, cap);
+        hipLaunchKernelGGL(k_part_scatter_ranks, dim3(nblocks(n + nrecv)), dim3(PB), 0, ctx.stream, m_h, m_a, na, n, key, rbuf, rstart, nr, nrecv, akey, offs, cursor);
+        if (m_block) ctx.free(m_block);
+        m_block = nb; m_a = na; m_cap = cap;
+    }
+    ctx.free(ws);
+    if (sbuf) ctx.free(sbuf);
+    if (rbuf) ctx.free(rbuf);
+    if (akey) ctx.free(akey);
+    m_np = total;
+    n_removed += removed;
+    if (misfiled > 0) throw Error("iamrx Particles::redistribute: " + std::to_string(misfiled) + " arriving particles name no box of this rank");
+    return removed;
+}
+
+void Particles::global_count(long* per_level, long* total) const
+{
+    auto& ctx = Context::get();
+    const int nl = nlevels();
+    std::vector<double> v((size_t)nl + 1, 0.0);
+    for (int l = 0; l < nl; ++l) v[l] = (double)m_lev_n[l];
+    v[nl] = (double)m_np;
+    if (ctx.comm->nranks > 1) ctx.comm->allreduce(v.data(), nl + 1, ReduceOp::Sum);
+    if (per_level) for (int l = 0; l < nl; ++l) per_level[l] = (long)v[l];
+    if (total) *total = (long)v[nl];
+}
+
 void Particles::particle_count(int lev, MultiFab& out, int ocomp)
 {
     if (lev < 0 || lev >= nlevels()) throw Error("iamrx Particles::particle_count: no such level");
@@ -531,10 +787,51 @@ void Particles::total_particle_count(int lev, MultiFab& out, int ocomp)
     particle_count(lev, out, ocomp);
     const int fin = nlevels() - 1;
     if (lev == fin) return;
+    if (Context::get().comm->nranks > 1) { add_finer_counts_ranks(lev, out, ocomp); return; }
     const long p0 = m_lev_start[lev + 1], n = m_np - p0;        // the groups are ordered by level: everything finer than lev
     if (n <= 0) return;
     auto& ctx = Context::get();
     hipLaunchKernelGGL(k_part_count, dim3(nblocks(n)), dim3(PB), 0, ctx.stream, m_h, m_a, p0, n, lev, out.d_tab, ocomp);
+}
+
+// Several ranks: a fine box and the coarse box under it may have different owners.  From the finest level down to lev + 1: the level's
+// own count plus what the finer levels handed down, summed onto the level's boxes coarsened by the ratio (same owners: no communication),
+// then copied to the boxes of the next coarser level wherever they are (parallel_copy).  Counts are small integers: every sum is exact.
+void Particles::add_finer_counts_ranks(int lev, MultiFab& out, int ocomp)
+{
+    auto& ctx = Context::get();
+    const int fin = nlevels() - 1, r = m_ratio;
+    MultiFab carry;                                           // on the coarsened boxes of level lf + 1: the counts of the levels > lf
+    for (int lf = fin; lf > lev; --lf) {
+        const LayoutP& fl = m_layouts[lf];
+        for (auto& b : fl->boxes)
+            for (int e = 0; e < 3; ++e)
+                if (b.lo[e] % r != 0 || b.len(e) % r != 0) throw Error("iamrx Particles::total_particle_count: a box of a refined level is not aligned to the ratio");
+        MultiFab cur(fl, cell_type(), 1, 0);
+        particle_count(lf, cur, 0);
+        if (carry.defined()) {
+            MultiFab below(fl, cell_type(), 1, 0);
+            below.setVal(0.0);
+            parallel_copy(below, carry, 0, 0, 1, 0, 0, nullptr);
+            mf_saxpy(cur, 1.0, below, 0, 0, 1, 0);
+        }
+        LayoutP cl = fl->coarsened(r);
+        MultiFab sum(cl, cell_type(), 1, 0);
+        const FabD *ct = sum.d_tab, *ft = cur.d_tab;
+        for_each(*cl, cell_type(), 0, ctx.stream, [=] __device__(int i, int j, int k, int f) {
+            const FabD F = ft[f];
+            double s = 0.0;
+            for (int kk = 0; kk < r; ++kk)
+                for (int jj = 0; jj < r; ++jj)
+                    for (int ii = 0; ii < r; ++ii) s += F(r * i + ii, r * j + jj, r * k + kk);
+            ct[f](i, j, k) = s;
+        });
+        carry = std::move(sum);
+    }
+    MultiFab below(m_layouts[lev], cell_type(), 1, 0);
+    below.setVal(0.0);
+    parallel_copy(below, carry, 0, 0, 1, 0, 0, nullptr);
+    mf_saxpy(out, 1.0, below, 0, ocomp, 1, 0);
 }
 
 // ---- ghost faces of a refined level for its particles ------------------------------------------------------------------------------------

@@ -1554,12 +1554,15 @@ void NavierStokes::set_particles(std::shared_ptr<Particles> pc)
 
 // the level's particles move with its u_mac: level 0 has the one ghost face the stencils reach; a refined level that sub-cycles keeps
 // particles up to ncycle - 1 cells outside its boxes between sub-steps and reads ncycle ghost faces (umac_n_grow = ncycle,
-// NavierStokesBase.cpp:625-628), built in scratch arrays so that the level's own u_mac stays what it is
+// NavierStokesBase.cpp:625-628), built in scratch arrays so that the level's own u_mac stays what it is.  Several ranks: level 0's ghost
+// face comes from the FillBoundary that follows the MAC projection (mac_project), which crosses ranks and periodic images and after which
+// nothing writes u_mac; a refined level builds its faces on every rank, whether or not the rank holds particles there -- the build is
+// collective and the count is a local one
 void NavierStokes::advect_particles(double dt_)
 {
     const MultiFab* um[3] = {&u_mac[0], &u_mac[1], &u_mac[2]};
     if (level == 0 || ncycle <= 1) { particles->advect(level, um, dt_); return; }
-    if (particles->count_at_level(level) == 0) return;
+    if (Context::get().comm->nranks == 1 && particles->count_at_level(level) == 0) return;
     const MultiFab* uc[3] = {&crse->u_mac[0], &crse->u_mac[1], &crse->u_mac[2]};
     particles_grow_umac(m_part_umac, um, uc, crse->g, g, ratio, ncycle);
     const MultiFab* ug[3] = {&m_part_umac[0], &m_part_umac[1], &m_part_umac[2]};

@@ -7,6 +7,14 @@
 // position between the two passes of advect), id, cpu, level and local box index -- kept grouped by (level, box), so that ONE launch per
 // level serves all its boxes through the level's FabD table.  Grouping is a count / prefix / scatter with integer vector atomics; the
 // order inside a box is not part of the contract.
+//
+// Several ranks (Context::comm->nranks > 1): every rank holds the particles of the boxes it owns.  A particle is placed against the
+// level's GLOBAL box list (Layout::boxes), so every rank finds the same (level, box) for it; redistribute() then sends the particles
+// whose box another rank owns to that rank (one allreduce of the send counts, one pack kernel, one Comm::exchange, one filing kernel)
+// and scatters stayers and arrivals together.  Collective on several ranks: define, add, redistribute, total_particle_count,
+// global_count -- every rank calls them, also one without particles or boxes; an error one rank finds is thrown on all of them.  Local:
+// read, set_positions, size, count_at_level, advect, particle_count.  One rank: no collective is issued and the launches are the ones
+// of the single-process container.
 #pragma once
 #include "mf.h"
 #include <vector>
@@ -15,8 +23,12 @@
 namespace iamrx {
 
 struct PLevelD {
-    const int* tab;          // box lookup: local box index (or -1) of every block of gran^3 cells of the level's domain
+    const int* tab;          // box lookup: index in the level's global box list (or -1) of every block of gran^3 cells of the level's domain
     const BoxD* boxes;       // the level's local valid boxes (Layout::d_boxes)
+    const BoxD* gboxes;      // all boxes of the level (Layout::boxes); one rank: the same array as `boxes`
+    const int* owner;        // [ngbox] owner rank of a global box; one rank: null (every box is local and global index == local index)
+    const int* lidx;         // [ngbox] local index of a global box on its owner
+    int ngbox;
     int tn[3];               // blocks per direction
     int gran;                // cells per block and direction: divides every box corner and length of the level
     int dlo[3], n[3];        // domain low corner and extent (cells)
@@ -53,7 +65,10 @@ public:
     long size() const { return m_np; }
     long count_at_level(int l) const { return m_lev_n.at(l); }
     // n particles from host arrays: xyz (n x 3); r (n x 3), ids, cpus may be null (zeros, ids from the container's counter, 0).  They are
-    // placed by redistribute(0, finest, 0); returns what that returns
+    // placed by redistribute(0, finest, 0); returns what that returns.  Several ranks: collective -- every rank passes its own list, possibly
+    // none (n = 0, null arrays), and the particles go to the owners of their boxes.  Without ids the new ids continue the counter in rank
+    // order (rank q's after rank q - 1's), so all positions on rank 0 give the ids of a one-rank run; with ids the counter becomes the
+    // largest id + 1 over the ranks
     long add(long n, const double* xyz, const double* r, const int* ids, const int* cpus);
     // every particle to host arrays of size() entries (any may be null): xyz, r (n x 3), id, cpu, level, box
     void read(double* xyz, double* r, int* id, int* cpu, int* lev, int* box) const;
@@ -62,12 +77,17 @@ public:
     // TracerParticleContainer::AdvectWithUmac for the particles of level `lev`: umac[d] face-centred in d on the level's layout, with the
     // ghost faces the particles' stencils reach already filled (one layer on level 0; see particles_grow_umac)
     void advect(int lev, const MultiFab* const umac[3], double dt);
-    // returns the number of particles removed beyond non-periodic domain faces; throws when a particle cannot be placed
+    // returns the number of particles removed beyond non-periodic domain faces (summed over the ranks); throws -- on every rank -- when a
+    // particle of any rank cannot be placed, and the container then holds what it held
     long redistribute(int lev_min, int lev_max, int ngrow);
     void particle_count(int lev, MultiFab& out, int ocomp);
+    // several ranks: collective; the finer levels' counts reach coarse boxes of other owners (level by level: counted on the finer level,
+    // summed onto its coarsened boxes, copied across; a fine cell counts where every level in between has a box under it)
     void total_particle_count(int lev, MultiFab& out, int ocomp);
-    int next_id = 1;
-    long n_removed = 0;           // removed beyond non-periodic faces since creation
+    // collective: the counts summed over the ranks (per_level: nlevels() entries, may be null)
+    void global_count(long* per_level, long* total) const;
+    int next_id = 1;              // equal on all ranks
+    long n_removed = 0;           // removed beyond non-periodic faces since creation, summed over the ranks
     int fixed_dir = -1;           // a coordinate advect leaves alone (the slab direction of a lifted two-dimensional run), -1: none
     int ratio() const { return m_ratio; }
 
@@ -85,6 +105,9 @@ private:
     static void carve(PArrays& a, void* block, long cap);
     void reserve(long cap);
     void free_tables();
+    long redistribute_ranks(int lev_min, int lev_max, int ngrow);
+    void add_local(long n, const double* xyz, const double* r, const int* ids, const int* cpus);
+    void add_finer_counts_ranks(int lev, MultiFab& out, int ocomp);
 };
 using ParticlesP = std::shared_ptr<Particles>;
 

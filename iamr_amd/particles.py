@@ -9,7 +9,11 @@ Files (no device needed):
   write_ascii          particles.particle_output_file: the count, then `x y z id cpu` per line, %.17g, sorted by id
   write_particles_dir / read_particles_dir
                        the `Particles/` directory of a checkpoint or plotfile -- THIS project's own format,
-                       not AMReX's binary particle format: a text `Header` and raw little-endian arrays
+                       not AMReX's binary particle format: a text `Header` and raw little-endian arrays.  One rank writes format 1
+                       (`iamr_amd-particles-1`); several ranks write format 2: every rank its own arrays, rank 0 the Header last
+
+Several ranks: Particles.add / redistribute / count_global / total_particle_count and save / restore / gather_sorted below are COLLECTIVE
+(every rank calls them); count / read / set_positions speak of this rank's particles (include/iamrx.h).
 """
 import ctypes as C
 import os
@@ -18,6 +22,7 @@ from .lib import lib, check
 
 PARTICLES_DIR = "Particles"          # the_ns_particle_file_name, NavierStokesBase.cpp:209
 _HEADER_MAGIC = "iamr_amd-particles-1"
+_HEADER_MAGIC_2 = "iamr_amd-particles-2"          # several writers: the arrays of writer q are <name>.<q:05d>
 _FILES = (("xyz.f64", "<f8", 3), ("r.f64", "<f8", 3), ("id.i32", "<i4", 1), ("cpu.i32", "<i4", 1))
 
 
@@ -53,10 +58,13 @@ class Particles:
         return Particles([amr.level_geom(l) for l in range(amr.nlev)], amr.layouts, amr.ratio)
 
     def add(self, xyz, ids=None, r=None, cpus=None):
-        """add particles at the positions xyz (n, 3); ids default to the container's counter (from 1).  Returns the number of particles
-        removed because they lie outside a non-periodic domain."""
+        """add particles at the positions xyz (n, 3) -- an empty list is fine; ids default to the container's counter (from 1).  Returns the
+        number of particles removed because they lie outside a non-periodic domain.  Several ranks: collective; every rank passes its own
+        list and the particles go to the owners of their boxes; without ids rank q's new ids follow rank q - 1's."""
         x = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
         n = x.shape[0]
+        if n == 0:
+            x, ids, cpus, r = None, None, None, None
         i = None if ids is None else np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(n))
         c = None if cpus is None else np.ascontiguousarray(np.asarray(cpus, dtype=np.int32).reshape(n))
         rr = None if r is None else np.ascontiguousarray(np.asarray(r, dtype=np.float64).reshape(n, 3))
@@ -74,6 +82,13 @@ class Particles:
         """number of particles (on level lev)"""
         per, tot, _, _ = self._counts()
         return tot if lev is None else per[lev]
+
+    def count_global(self, lev=None):
+        """number of particles on all ranks (on level lev); collective"""
+        per = (C.c_long * 8)()
+        tot = C.c_long()
+        check(lib().iamrx_particles_count_global(self.h, per, C.byref(tot)))
+        return tot.value if lev is None else per[lev]
 
     @property
     def next_id(self):
@@ -187,49 +202,142 @@ def read_ascii(path):
     return xyz, np.array([int(r[3]) for r in rows], np.int32), np.array([int(r[4]) for r in rows], np.int32)
 
 
-def write_particles_dir(parent, xyz, r, ids, cpus, next_id):
-    """<parent>/Particles/: `Header` (text: magic, count, next id, then one line `file dtype columns` per array) and the raw little-endian
-    arrays, sorted by id.  This project's own format."""
-    d = os.path.join(parent, PARTICLES_DIR)
-    os.makedirs(d, exist_ok=True)
+def _sorted_arrays(xyz, r, ids, cpus):
     ids = np.asarray(ids, np.int32).reshape(-1)
     o = np.argsort(ids, kind="stable")
-    arrs = (np.asarray(xyz, np.float64).reshape(-1, 3)[o], np.asarray(r, np.float64).reshape(-1, 3)[o], ids[o], np.asarray(cpus, np.int32).reshape(-1)[o])
-    with open(os.path.join(d, "Header"), "w") as f:
-        f.write(f"{_HEADER_MAGIC}\n{len(ids)}\n{int(next_id)}\n")
-        for name, dt, nc in _FILES:
-            f.write(f"{name} {dt} {nc}\n")
+    return (np.asarray(xyz, np.float64).reshape(-1, 3)[o], np.asarray(r, np.float64).reshape(-1, 3)[o], ids[o], np.asarray(cpus, np.int32).reshape(-1)[o])
+
+
+def write_particles_dir(parent, xyz, r, ids, cpus, next_id, rank=0, world=1, counts=None):
+    """<parent>/Particles/, this project's own format.  world 1: `Header` (text: magic, count, next id, then one line `file dtype columns`
+    per array) and the raw little-endian arrays, sorted by id.  world > 1 (format 2): the caller is writer `rank` of `world` and passes its
+    own particles; it writes them, sorted by id, to <file>.<rank:05d>; counts: the number of particles of every writer, which rank 0 needs
+    for the Header (magic, total count, next id, the number of writers, their counts on one line, then the array lines) -- to be called by
+    rank 0 LAST, after every other writer has finished (save() below does that through the communicator; a caller without one calls the
+    writers one after another, rank 0 at the end)."""
+    d = os.path.join(parent, PARTICLES_DIR)
+    os.makedirs(d, exist_ok=True)
+    arrs = _sorted_arrays(xyz, r, ids, cpus)
+    n = len(arrs[2])
+    if world == 1:
+        with open(os.path.join(d, "Header"), "w") as f:
+            f.write(f"{_HEADER_MAGIC}\n{n}\n{int(next_id)}\n")
+            for name, dt, nc in _FILES:
+                f.write(f"{name} {dt} {nc}\n")
+        for (name, dt, nc), a in zip(_FILES, arrs):
+            np.ascontiguousarray(a).astype(dt).tofile(os.path.join(d, name))
+        return d
+    if not 0 <= rank < world:
+        raise ValueError(f"write_particles_dir: writer {rank} of {world}")
     for (name, dt, nc), a in zip(_FILES, arrs):
-        np.ascontiguousarray(a).astype(dt).tofile(os.path.join(d, name))
+        np.ascontiguousarray(a).astype(dt).tofile(os.path.join(d, f"{name}.{rank:05d}"))
+    if rank == 0:
+        counts = [int(c) for c in counts]
+        if len(counts) != world or counts[0] != n:
+            raise ValueError(f"write_particles_dir: {world} writers, counts {counts}, writer 0 holds {n}")
+        with open(os.path.join(d, "Header"), "w") as f:
+            f.write(f"{_HEADER_MAGIC_2}\n{sum(counts)}\n{int(next_id)}\n{world}\n{' '.join(str(c) for c in counts)}\n")
+            for name, dt, nc in _FILES:
+                f.write(f"{name} {dt} {nc}\n")
     return d
 
 
-def read_particles_dir(parent):
-    """-> dict(xyz, r, id, cpu, next_id) of <parent>/Particles/"""
-    d = os.path.join(parent, PARTICLES_DIR)
-    with open(os.path.join(d, "Header")) as f:
-        lines = [l.strip() for l in f if l.strip()]
-    if lines[0] != _HEADER_MAGIC:
-        raise ValueError(f"{d}/Header: not a particle directory of this project ({lines[0]!r})")
-    n, next_id = int(lines[1]), int(lines[2])
-    out = {"next_id": next_id}
-    for line, key in zip(lines[3:], ("xyz", "r", "id", "cpu")):
+def _read_arrays(d, lines, n, suffix=""):
+    out = {}
+    for line, key in zip(lines, ("xyz", "r", "id", "cpu")):
         name, dt, nc = line.split()
-        a = np.fromfile(os.path.join(d, name), dtype=dt)
+        a = np.fromfile(os.path.join(d, name + suffix), dtype=dt)
         if a.size != n * int(nc):
-            raise ValueError(f"{d}/{name}: {a.size} values, the header announces {n} x {nc}")
+            raise ValueError(f"{d}/{name}{suffix}: {a.size} values, the header announces {n} x {nc}")
         out[key] = a.reshape(n, 3).astype(np.float64) if int(nc) == 3 else a.astype(np.int32)
     return out
 
 
+def read_particles_dir(parent, rank=0, world=1):
+    """-> dict(xyz, r, id, cpu, next_id) of <parent>/Particles/, either format: the share of reader `rank` of `world`.  Format 2: the files
+    of the writers q with q % world == rank, one after another; format 1: the rank-th of `world` contiguous slices.  The shares of all
+    readers are disjoint and together they are everything; world 1 reads everything."""
+    if not 0 <= rank < world:
+        raise ValueError(f"read_particles_dir: reader {rank} of {world}")
+    d = os.path.join(parent, PARTICLES_DIR)
+    with open(os.path.join(d, "Header")) as f:
+        lines = [l.strip() for l in f if l.strip()]
+    if lines[0] not in (_HEADER_MAGIC, _HEADER_MAGIC_2):
+        raise ValueError(f"{d}/Header: not a particle directory of this project ({lines[0]!r})")
+    n, next_id = int(lines[1]), int(lines[2])
+    if lines[0] == _HEADER_MAGIC:
+        out = _read_arrays(d, lines[3:], n)
+        lo, hi = (n * rank) // world, (n * (rank + 1)) // world
+        out = {k: v[lo:hi] for k, v in out.items()}
+    else:
+        writers, counts = int(lines[3]), [int(v) for v in lines[4].split()]
+        if len(counts) != writers or sum(counts) != n:
+            raise ValueError(f"{d}/Header: {writers} writers with counts {counts}, {n} particles announced")
+        parts = [_read_arrays(d, lines[5:], counts[q], f".{q:05d}") for q in range(writers) if q % world == rank]
+        empty = dict(xyz=np.zeros((0, 3)), r=np.zeros((0, 3)), id=np.zeros(0, np.int32), cpu=np.zeros(0, np.int32))
+        out = {k: np.concatenate([p[k] for p in parts]) if parts else empty[k] for k in empty}
+    out["next_id"] = next_id
+    return out
+
+
+def _rank_counts(n):
+    """(rank, world, the number n of every rank); the allreduce is also the barrier between the ranks' file writes"""
+    from .lib import comm_rank, comm_allreduce
+    rank, world = comm_rank()
+    v = np.zeros(world)
+    v[rank] = float(n)
+    if world > 1:
+        v = comm_allreduce(v, 0)
+    return rank, world, [int(c) for c in v]
+
+
 def save(parent, pc):
-    """the container's particles into <parent>/Particles/"""
+    """the container's particles into <parent>/Particles/.  Several ranks: collective -- every rank writes its own, rank 0 the Header once
+    all have written (plotfile.write_collective's order)."""
+    from .lib import comm_barrier
     p = pc.read()
-    return write_particles_dir(parent, p["xyz"], p["r"], p["id"], p["cpu"], pc.next_id)
+    next_id = pc.next_id
+    rank, world, counts = _rank_counts(len(p["id"]))
+    if world == 1:
+        return write_particles_dir(parent, p["xyz"], p["r"], p["id"], p["cpu"], next_id)
+    if rank == 0:
+        os.makedirs(os.path.join(parent, PARTICLES_DIR), exist_ok=True)
+    comm_barrier()                                      # the directory exists
+    if rank != 0:
+        write_particles_dir(parent, p["xyz"], p["r"], p["id"], p["cpu"], next_id, rank, world)
+    comm_barrier()                                      # the others have written
+    if rank == 0:
+        write_particles_dir(parent, p["xyz"], p["r"], p["id"], p["cpu"], next_id, 0, world, counts)
+    comm_barrier()                                      # the Header is there
+    return os.path.join(parent, PARTICLES_DIR)
 
 
 def restore(parent, pc):
-    """add the particles of <parent>/Particles/ to the (empty) container, bit for bit, with the id counter"""
-    d = read_particles_dir(parent)
+    """add the particles of <parent>/Particles/ to the (empty) container, bit for bit, with the id counter.  Several ranks: collective;
+    every rank adds its share (read_particles_dir) and the container sends the particles to the owners of their boxes, so a directory
+    written on any number of ranks restores on any other."""
+    from .lib import comm_rank
+    rank, world = comm_rank()
+    d = read_particles_dir(parent, rank, world)
     pc.add(d["xyz"], ids=d["id"], r=d["r"], cpus=d["cpu"])
     pc.next_id = d["next_id"]
+
+
+def gather_sorted(pc):
+    """-> (xyz, id, cpu) of ALL particles, sorted by id, on every rank; collective.  Every rank puts its rows at its offset into a zero
+    array and the arrays are summed (exact: every entry has one non-zero term; ids and cpus are 32-bit integers held as doubles).  For
+    small sets: every rank holds everything."""
+    from .lib import comm_allreduce
+    p = pc.read()
+    rank, world, counts = _rank_counts(len(p["id"]))
+    if world == 1:
+        o = np.argsort(p["id"], kind="stable")
+        return p["xyz"][o], p["id"][o], p["cpu"][o]
+    off = sum(counts[:rank])
+    a = np.zeros((sum(counts), 5))
+    a[off:off + counts[rank], :3] = p["xyz"]
+    a[off:off + counts[rank], 3] = p["id"]
+    a[off:off + counts[rank], 4] = p["cpu"]
+    a = comm_allreduce(a, 0) if a.size else a
+    o = np.argsort(a[:, 3], kind="stable")
+    return a[o, :3].copy(), a[o, 3].astype(np.int32), a[o, 4].astype(np.int32)

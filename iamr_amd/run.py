@@ -172,14 +172,17 @@ def setup_particles(run, pr, say, restart_dir=None):
     NavierStokesBase.cpp:3808-3864): one container for the level or the hierarchy; at start-up the positions of particles.particle_init_file;
     on a restart the checkpoint's Particles/ (unless particles.restart_from_nonparticle_chkfile), then particles.particle_restart_file is
     added and particles.particle_output_file written.  A two-dimensional file lifts (x, y) to (x, mid-slab, y) and the particles never move
-    across the slab.  Returns the container or None."""
+    across the slab.  Several ranks: every call below is collective; rank 0 passes a file's positions and the other ranks none (the ids are
+    then those of a one-rank run), the checkpoint's particles are read in shares, and the PARTICLES: line speaks of all ranks.  Returns
+    the container or None."""
     pp = pr.get("particles")
     if not pp:
         return None
     from .lib import comm_rank
-    if comm_rank()[1] > 1:
-        raise NotImplementedError("iamr_amd.run: tracer particles (particles.*) on more than one rank are not implemented")
+    import numpy as np
     from . import particles as P
+    rank = comm_rank()[0]
+    from_file = lambda name: P.read_particle_file(name, slab_y) if rank == 0 else np.zeros((0, 3))
     pc = P.Particles.for_hierarchy(run) if hasattr(run, "levels") else P.Particles.for_level(run)
     slab_y = None
     if pr.get("slab"):
@@ -188,17 +191,18 @@ def setup_particles(run, pr, say, restart_dir=None):
     run.set_particles(pc)
     if restart_dir is None:
         if pp["init_file"]:
-            pc.add(P.read_particle_file(pp["init_file"], slab_y))
+            pc.add(from_file(pp["init_file"]))
     else:
         if not pp["restart_from_nonparticle_chkfile"]:
             P.restore(restart_dir, pc)
         if pp["restart_file"]:
-            pc.add(P.read_particle_file(pp["restart_file"], slab_y))
+            pc.add(from_file(pp["restart_file"]))
         if pp["output_file"]:
-            d = pc.read()
-            P.write_ascii(pp["output_file"], d["xyz"], d["id"], d["cpu"])
+            xyz, ids, cpus = P.gather_sorted(pc)
+            if rank == 0:
+                P.write_ascii(pp["output_file"], xyz, ids, cpus)
     if pp["verbose"]:
-        say(f"PARTICLES: {pc.count()} (removed outside the domain: {pc.removed})")
+        say(f"PARTICLES: {pc.count_global()} (removed outside the domain: {pc.removed})")
     return pc
 
 
@@ -361,13 +365,16 @@ def main(argv, observe=None):
         raise ValueError(f"IAMRX_RUN_TRANSPORT={transport!r}: only 'gloo' (or unset: RCCL) is known")
     if world > 1:
         import torch.distributed as dist
+        from datetime import timedelta
+        # IAMRX_RUN_TIMEOUT (seconds; unset: torch's default): how long a collective waits for a rank that never calls it
+        kw = {"timeout": timedelta(seconds=float(os.environ["IAMRX_RUN_TIMEOUT"]))} if os.environ.get("IAMRX_RUN_TIMEOUT") else {}
         if transport == "gloo":
             local_rank = 0
-            dist.init_process_group("gloo", rank=rank, world_size=world)
+            dist.init_process_group("gloo", rank=rank, world_size=world, **kw)
         else:
             import torch
             torch.cuda.set_device(local_rank)
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank), **kw)
     lib.init(local_rank)
     if world > 1:
         from . import comm

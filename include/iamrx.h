@@ -775,17 +775,35 @@ int iamrx_amr_profile(iamrx_amr a, int enable, double sections_ms[16], double le
 
 /* ---- tracer particles (k_particles.hip): the role of AMReX's AmrTracerParticleContainer as IAMR uses it (reference
  * Source/NavierStokesBase.cpp:198-222, 3751-4057; Source/NavierStokes.cpp:672-677).  AMReX is not part of the reference tree, so the
- * container's arithmetic is UNPINNED; tests/particles_numpy.py restates what is implemented.  One process only.
+ * container's arithmetic is UNPINNED; tests/particles_numpy.py restates what is implemented.
  * A container lives on nlev levels (coarsest first, level 0 covers the domain, refined by `ratio`); particles are device resident and kept
  * grouped by (level, box).  Attached to a level or a hierarchy (iamrx_ns_set_particles / iamrx_amr_set_particles) it is REBOUND to that
- * object's own boxes, and again after every regrid; box indices then refer to those (merged) boxes. */
+ * object's own boxes, and again after every regrid; box indices then refer to those (merged) boxes.
+ *
+ * Several ranks (one process per GPU): every rank holds the particles that lie in the boxes it owns; a redistribution sends the others to
+ * their owners (one allreduce and one exchange through the installed communicator, whatever the number of particles).
+ *   COLLECTIVE -- every rank calls them, also a rank with no particle and no box, with the same level arguments; an error that one rank
+ *   finds (a particle that cannot be placed, refused arguments) is returned on every rank and every rank's container stays as it was:
+ *     create, add, redistribute, derive_count with which = 1, count_global, iamrx_ns_set_particles / iamrx_amr_set_particles, and the
+ *     steps, regrids and derives of the object the container is attached to.
+ *   LOCAL -- this rank's particles only, in this rank's storage order; box indices are local ones:
+ *     count (per_level, total), read, set_positions, advect, derive_count with which = 0, set_next_id, set_fixed_dir.
+ *   GLOBAL VALUES, equal on every rank: *removed of add and redistribute and *removed_total (sums over the ranks), *next_id, and what
+ *     count_global returns.
+ * On one rank nothing is collective and every call is what it was. */
 int iamrx_particles_create(int nlev, const iamrx_geom* geoms /* [nlev] */, const iamrx_layout* layouts /* [nlev] */, int ratio, iamrx_particles* out);
 int iamrx_particles_destroy(iamrx_particles pc);
 /* n particles from host arrays: xyz[3 n]; r[3 n], ids[n], cpus[n] may be NULL (zeros; ids from the container's counter, which starts at 1; 0).
- * They are placed by a redistribution over all levels; *removed (may be NULL): how many of all particles fell outside a non-periodic domain. */
+ * They are placed by a redistribution over all levels; *removed (may be NULL): how many of all particles fell outside a non-periodic domain.
+ * Several ranks: every rank passes its own list, possibly none (n = 0, NULL arrays); the particles go to the owners of their boxes.  Without
+ * ids the new ids continue the counter in rank order (rank q's follow rank q - 1's: all positions on rank 0 and none elsewhere give the ids
+ * of a one-rank run); with ids the counter becomes the largest id + 1 over the ranks. */
 int iamrx_particles_add(iamrx_particles pc, long n, const double* xyz, const double* r, const int* ids, const int* cpus, long* removed);
 /* count[l] (l < nlev of the container; may be NULL), *total, *next_id, *removed_total (any may be NULL) */
 int iamrx_particles_count(iamrx_particles pc, long* per_level, long* total, int* next_id, long* removed_total);
+/* collective: the counts summed over the ranks; per_level[l] (l < nlev; may be NULL), *total (may be NULL) */
+int iamrx_particles_count_global(iamrx_particles pc, long* per_level, long* total);
+/* (several ranks: to be given the same value on every rank) */
 int iamrx_particles_set_next_id(iamrx_particles pc, int next_id);
 /* a coordinate the particles never move in (the slab direction of a lifted two-dimensional run); -1: none */
 int iamrx_particles_set_fixed_dir(iamrx_particles pc, int dir);

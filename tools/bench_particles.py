@@ -1,4 +1,4 @@
-"""Tracer particles: time of the advect kernel and its share of the level step.
+"""Tracer particles: time of the advect kernel, of a redistribution, and their share of the level step.
   python tools/bench_particles.py [out.json]
 1. Particles.advect (k_part_advect, both passes) for 2^20 particles on one 128^3 periodic box with a smooth velocity: HIP events on the
    library's launch stream around each call, median of the repeats, once with the particles in random order and once grouped by cell
@@ -6,7 +6,8 @@
    Reported as particles per second and as effective gather bandwidth: per particle and pass 24 face values of 8 B are gathered, and
    pass 1 reads 3 + writes 6, pass 2 reads 6 + writes 6 doubles of particle data plus the id and box words (2 x 4 B per pass):
    bytes = 2 x 24 x 8 + (9 + 12) x 8 + 16 = 568 B per particle.
-2. a 128^3 TaylorGreen viscous step with one particle per 8 cells attached against the same step without particles, interleaved: host
+2. Particles.redistribute of the same two sets, host clock around a synchronised call, median.
+3. a 128^3 TaylorGreen viscous step with one particle per 8 cells attached against the same step without particles, interleaved: host
    clock around a synchronised step, median.
 Writes one JSON document (default profiles/particles.json)."""
 import ctypes as C
@@ -80,6 +81,20 @@ for name, (pc, ms) in cases.items():
     res["kernel"][name] = {"particles": npart, "box": nn, "ms_median": med, "ms_min": min(ms), "ms_max": max(ms),
                            "particles_per_s": npart / (med * 1e-3), "effective_GB_per_s": npart * BYTES_PER_PARTICLE / (med * 1e-3) / 1e9}
     print("advect", name, res["kernel"][name], flush=True)
+# 2. the redistribution of the same sets (nothing moves between boxes: placement, prefix, the one read-back, scatter), host clock around a
+#    synchronised call
+res["redistribute"] = {}
+for _ in range(12):
+    for name, (pc, ms) in cases.items():
+        lib.sync()
+        t0 = time.perf_counter()
+        pc.redistribute()
+        lib.sync()
+        res["redistribute"].setdefault(name, []).append((time.perf_counter() - t0) * 1e3)
+for name, ts in list(res["redistribute"].items()):
+    ts = ts[2:]
+    res["redistribute"][name] = {"particles": npart, "ms_median": statistics.median(ts), "ms_min": min(ts), "ms_max": max(ts)}
+    print("redistribute", name, res["redistribute"][name], flush=True)
 del cases, um
 
 runs = {}
