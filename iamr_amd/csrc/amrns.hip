@@ -1235,7 +1235,16 @@ void AmrNS::post_timestep(int l, int crse_iteration)
     // post_timestep_particle (NavierStokesBase.cpp:3866-3879): not on the last sub-step of a refined level -- the coarser level's follows
     if (particles && (l == 0 || crse_iteration < n_cycle[l])) {
         if (l > 0 && crse_iteration < 0) throw Error("AmrNS::post_timestep: the particles need the level's iteration");
-        particles->redistribute(l, (int)lev.size() - 1, l == 0 ? 0 : crse_iteration);
+        const int ngrow = l == 0 ? 0 : crse_iteration, fin = (int)lev.size() - 1;
+        particles->redistribute(l, fin, ngrow);
+        if (particles->timestamps_on()) {                                                                 // :3881-3951
+            // a level without particles is skipped: on several ranks by the global count, so that every rank enters a level's fill or none
+            std::vector<long> per(lev.size(), 0);
+            if (Context::get().comm->nranks > 1) particles->global_count(per.data(), nullptr);
+            else for (int q = l; q <= fin; ++q) per[q] = particles->count_at_level(q);
+            for (int q = l; q <= fin; ++q)
+                if (per[q] > 0) lev[q]->timestamp_particles(q == l ? ngrow + 1 : 1);
+        }
     }
     lev[l]->time_average(dt_level[l], level_steps);                                                       // :2630-2634
     // The levels above l have just reached level l's time through their own sub-steps, and have summed the same interval in smaller pieces:

@@ -1747,6 +1747,21 @@ int iamrx_particles_derive_count(iamrx_particles pc, int which, int lev, iamrx_m
     else throw Error("iamrx_particles_derive_count: which = 0 (particle_count) or 1 (total_particle_count)");
     IAMRX_CATCH
 }
+int iamrx_particles_sample(iamrx_particles pc, int lev, iamrx_mf mf, int ncomp, const int* comps, double* vals, int* id, int* cpu)
+{
+    IAMRX_TRY
+    if (!mf) throw Error("iamrx_particles_sample: null array");
+    pc->pc->sample(lev, mf->mf, comps, ncomp, vals, id, cpu);
+    IAMRX_CATCH
+}
+int iamrx_particles_set_timestamp(iamrx_particles pc, const char* basename, int n, const int* indices)
+{
+    IAMRX_TRY
+    if (n < 0 || (n > 0 && !indices)) throw Error("iamrx_particles_set_timestamp: n indices");
+    pc->pc->set_timestamp(basename ? basename : "", std::vector<int>(indices, indices + n));
+    IAMRX_CATCH
+}
+int iamrx_particles_timestamp(iamrx_particles pc, int lev, iamrx_mf mf, double time) { IAMRX_TRY pc->pc->timestamp(lev, mf ? &mf->mf : nullptr, time); IAMRX_CATCH }
 int iamrx_ns_set_particles(iamrx_ns ns, iamrx_particles pc) { IAMRX_TRY ns->ns->set_particles(pc ? pc->pc : nullptr); IAMRX_CATCH }
 int iamrx_amr_set_particles(iamrx_amr a, iamrx_particles pc) { IAMRX_TRY a->amr->set_particles(pc ? pc->pc : nullptr); IAMRX_CATCH }
 static iamrx_particles handle_of(const ParticlesP& p)

@@ -1,6 +1,7 @@
 // iamr_amd/csrc/k_particles.hip -- tracer particles: the container of particles.h and its kernels (advect with the MAC velocity,
-// redistribute over levels and boxes, the two particle counts).  UNPINNED against AMReX; the scheme as
-// implemented is restated in numpy by tests/particles_numpy.py.
+// redistribute over levels and boxes, the two particle counts, cell-centred state sampled at the particles and the timestamp files written
+// from it).  UNPINNED against AMReX, whose source is not in the reference tree; the scheme as implemented is
+// restated in numpy by tests/particles_numpy.py and tests/timestamp_numpy.py.
 #include "particles.h"
 #include "launch.h"
 #include "operators.h"
@@ -8,6 +9,7 @@
 #include <numeric>
 #include <cmath>
 #include <cstring>
+#include <cstdio>
 
 namespace iamrx {
 
@@ -320,6 +322,58 @@ __global__ void __launch_bounds__(PB) k_part_advect(AdvGeom G, PArrays a, long p
         for (int e = 0; e < 3; ++e) { a.r[e][p] = x[e]; a.x[e][p] = x[e] + (0.5 * dt) * v[e]; }
     } else {
         for (int e = 0; e < 3; ++e) { a.x[e][p] = a.r[e][p] + dt * v[e]; a.r[e][p] = v[e]; }
+    }
+}
+
+// ---- sample -----------------------------------------------------------------------------------------------------------------------------
+// Cell-centred components at the particles: AMReX's cic_interpolate for cell data as the timestamp files use it (AMReX's source is not in
+// the reference tree: UNPINNED like the rest of the container; tests/timestamp_numpy.py restates these expressions in this order).
+struct SampleGeom {
+    double plo[3], dx[3];
+    int dlo[3];
+};
+struct SampleComps {
+    int n;
+    int c[Particles::MAX_SAMPLE];
+};
+
+// out[m * n + t] = component C.c[m] of the particle's box FAB, trilinear between the cell centres around particle p0 + t.  Per direction
+// l = (x - plo) / dx - 0.5, i = floor(l), w = l - i, cells i and i + 1, clamped to the FAB's own index range ONLY: the array arrives
+// FillPatched and its ghost cells hold the boundary values, so there is no clamp to the domain (unlike interp_face).  Nothing is read
+// outside the array whatever the position is (a NaN takes the lower bound, as in interp_face).  The stencil and the weights are formed
+// once per particle; a component costs its eight loads.  Particles with id <= 0 are skipped (the caller zeroed `out`)
+__global__ void __launch_bounds__(PB) k_part_sample(SampleGeom G, PArrays a, long p0, long n, const FabD* __restrict__ tab, int nfab, SampleComps C,
+                                                    double* __restrict__ out)
+{
+    const long t = (long)blockIdx.x * PB + threadIdx.x;
+    if (t >= n) return;
+    const long p = p0 + t;
+    if (a.id[p] <= 0) return;
+    const int f = a.box[p];
+    if (f < 0 || f >= nfab) return;
+    const FabD F = tab[f];
+    const double x[3] = {a.x[0][p], a.x[1][p], a.x[2][p]};
+    int i0[3], i1[3];
+    double w[3];
+    for (int e = 0; e < 3; ++e) {
+        double l = (x[e] - G.plo[e]) / G.dx[e] - 0.5;
+        l = fmin(fmax(l, -1.0e9), 1.0e9);                      // (a NaN takes the lower bound)
+        const double fl = floor(l);
+        w[e] = l - fl;
+        const int ia = (int)fl + G.dlo[e], ib = ia + 1;
+        const int flo = F.lo[e], fhi = F.lo[e] + F.n[e] - 1;
+        i0[e] = min(max(ia, flo), fhi); i1[e] = min(max(ib, flo), fhi);
+    }
+    const long o000 = F.off(i0[0], i0[1], i0[2]), o100 = F.off(i1[0], i0[1], i0[2]), o010 = F.off(i0[0], i1[1], i0[2]), o110 = F.off(i1[0], i1[1], i0[2]);
+    const long o001 = F.off(i0[0], i0[1], i1[2]), o101 = F.off(i1[0], i0[1], i1[2]), o011 = F.off(i0[0], i1[1], i1[2]), o111 = F.off(i1[0], i1[1], i1[2]);
+    const double wx = w[0], wy = w[1], wz = w[2];
+    for (int m = 0; m < C.n; ++m) {
+        const auto* q = F.gp() + F.cs * C.c[m];
+        const double f000 = q[o000], f100 = q[o100], f010 = q[o010], f110 = q[o110], f001 = q[o001], f101 = q[o101], f011 = q[o011], f111 = q[o111];
+        // a + w (b - a): a uniform field is reproduced to the bit, whatever the weights
+        const double a00 = f000 + wx * (f100 - f000), a10 = f010 + wx * (f110 - f010), a01 = f001 + wx * (f101 - f001), a11 = f011 + wx * (f111 - f011);
+        const double b0 = a00 + wy * (a10 - a00), b1 = a01 + wy * (a11 - a01);
+        out[(long)m * n + t] = b0 + wz * (b1 - b0);
     }
 }
 
@@ -832,6 +886,102 @@ void Particles::add_finer_counts_ranks(int lev, MultiFab& out, int ocomp)
     below.setVal(0.0);
     parallel_copy(below, carry, 0, 0, 1, 0, 0, nullptr);
     mf_saxpy(out, 1.0, below, 0, ocomp, 1, 0);
+}
+
+// ---- state at the particles; timestamp files ------------------------------------------------------------------------------------------------
+void Particles::sample(int lev, const MultiFab& mf, const int* comps, int M, double* host_vals, int* id, int* cpu)
+{
+    if (lev < 0 || lev >= nlevels()) throw Error("iamrx Particles::sample: no such level");
+    if (!mf.layout || mf.layout->id != m_layouts[lev]->id || !mf.type.cell()) throw Error("iamrx Particles::sample: mf must be cell-centred on the level's boxes");
+    if (M < 1 || M > MAX_SAMPLE || !comps) throw Error("iamrx Particles::sample: 1 .. " + std::to_string(MAX_SAMPLE) + " components");
+    SampleComps C;
+    C.n = M;
+    for (int m = 0; m < MAX_SAMPLE; ++m) C.c[m] = 0;
+    for (int m = 0; m < M; ++m) {
+        if (comps[m] < 0 || comps[m] >= mf.ncomp) throw Error("iamrx Particles::sample: component " + std::to_string(comps[m]) + " of an array of " + std::to_string(mf.ncomp));
+        C.c[m] = comps[m];
+    }
+    const long n = m_lev_n[lev], p0 = m_lev_start[lev];
+    if (n == 0) return;
+    auto& ctx = Context::get();
+    const Geometry& g = m_geoms[lev];
+    SampleGeom G;
+    for (int e = 0; e < 3; ++e) { G.plo[e] = g.problo[e]; G.dx[e] = g.dx[e]; G.dlo[e] = g.domain.lo[e]; }
+    double* d_out = (double*)ctx.alloc((size_t)M * n * sizeof(double));
+    IAMRX_HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t)M * n * sizeof(double), ctx.stream));
+    hipLaunchKernelGGL(k_part_sample, dim3(nblocks(n)), dim3(PB), 0, ctx.stream, G, m_a, p0, n, mf.d_tab, m_layouts[lev]->nlocal(), C, d_out);
+    if (!host_vals && !id && !cpu) { ctx.free(d_out); return; }
+    std::vector<double> h;
+    if (host_vals) {
+        h.resize((size_t)M * n);
+        IAMRX_HIP_CHECK(hipMemcpyAsync(h.data(), d_out, (size_t)M * n * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
+    }
+    if (id) IAMRX_HIP_CHECK(hipMemcpyAsync(id, m_a.id + p0, n * sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+    if (cpu) IAMRX_HIP_CHECK(hipMemcpyAsync(cpu, m_a.cpu + p0, n * sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+    ctx.sync();
+    ctx.free(d_out);
+    if (host_vals)
+        for (long p = 0; p < n; ++p)
+            for (int m = 0; m < M; ++m) host_vals[(size_t)p * M + m] = h[(size_t)m * n + p];
+}
+
+void Particles::set_timestamp(const std::string& basename, std::vector<int> indices)
+{
+    if ((int)indices.size() > MAX_SAMPLE) throw Error("iamrx Particles::set_timestamp: at most " + std::to_string(MAX_SAMPLE) + " indices");
+    for (int i : indices) if (i < 0) throw Error("iamrx Particles::set_timestamp: negative index");
+    // upstream caps the number of files at 64 and lets the ranks that share one take turns; here every rank has a file of its own
+    if (!basename.empty() && Context::get().comm->nranks > 64) throw Error("iamrx Particles::set_timestamp: more than 64 ranks would share timestamp files");
+    m_ts_base = basename;
+    m_ts_indices = basename.empty() ? std::vector<int>() : std::move(indices);
+}
+
+void Particles::timestamp(int lev, const MultiFab* mf, double time)
+{
+    if (lev < 0 || lev >= nlevels()) throw Error("iamrx Particles::timestamp: no such level");
+    if (m_ts_base.empty()) throw Error("iamrx Particles::timestamp: no basename set (set_timestamp)");
+    const int M = mf ? (int)m_ts_indices.size() : 0;
+    if (mf && M > mf->ncomp) throw Error("iamrx Particles::timestamp: mf holds fewer components than there are indices");
+    const long n = m_lev_n[lev], p0 = m_lev_start[lev];
+    if (n == 0) return;
+    auto& ctx = Context::get();
+    std::vector<double> vals((size_t)M * n), xr((size_t)6 * n);
+    std::vector<int> id(n), cpu(n);
+    for (int e = 0; e < 3; ++e) {
+        IAMRX_HIP_CHECK(hipMemcpyAsync(xr.data() + (size_t)e * n, m_a.x[e] + p0, n * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
+        IAMRX_HIP_CHECK(hipMemcpyAsync(xr.data() + (size_t)(3 + e) * n, m_a.r[e] + p0, n * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
+    }
+    if (M > 0) {
+        int comps[MAX_SAMPLE];
+        for (int m = 0; m < M; ++m) comps[m] = m;
+        sample(lev, *mf, comps, M, vals.data(), id.data(), cpu.data());      // (synchronises: the copies above have arrived too)
+    } else {
+        IAMRX_HIP_CHECK(hipMemcpyAsync(id.data(), m_a.id + p0, n * sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+        IAMRX_HIP_CHECK(hipMemcpyAsync(cpu.data(), m_a.cpu + p0, n * sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+        ctx.sync();
+    }
+    // the order inside a box is not part of the container's contract: the lines of one call go out sorted by (id, cpu)
+    std::vector<long> ord;
+    for (long p = 0; p < n; ++p) if (id[p] > 0) ord.push_back(p);
+    if (ord.empty()) return;
+    std::sort(ord.begin(), ord.end(), [&](long a, long b) { return id[a] != id[b] ? id[a] < id[b] : (cpu[a] != cpu[b] ? cpu[a] < cpu[b] : a < b); });
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "_%02d", ctx.comm->rank % 64);
+    const std::string path = m_ts_base + buf;
+    std::FILE* f = std::fopen(path.c_str(), "a");
+    if (!f) throw Error("iamrx Particles::timestamp: cannot open " + path);
+    std::string line;
+    auto real = [&](double v) { std::snprintf(buf, sizeof buf, " %.10e", v); line += buf; };
+    for (long p : ord) {
+        std::snprintf(buf, sizeof buf, "%d %d", id[p], cpu[p]);
+        line = buf;
+        for (int e = 0; e < 3; ++e) if (e != fixed_dir) real(xr[(size_t)e * n + p]);
+        real(time);
+        for (int e = 0; e < 3; ++e) if (e != fixed_dir) real(xr[(size_t)(3 + e) * n + p]);
+        for (int m = 0; m < M; ++m) real(vals[(size_t)p * M + m]);
+        line += '\n';
+        std::fputs(line.c_str(), f);
+    }
+    if (std::fclose(f) != 0) throw Error("iamrx Particles::timestamp: writing " + path + " failed");
 }
 
 // ---- ghost faces of a refined level for its particles ------------------------------------------------------------------------------------

@@ -1569,6 +1569,37 @@ void NavierStokes::advect_particles(double dt_)
     particles->advect(level, ug, dt_);
 }
 
+void NavierStokes::timestamp_particles(int ng)
+{
+    const std::vector<int>& idx = particles->timestamp_indices();
+    const int M = (int)idx.size();
+    if (M == 0) { particles->timestamp(level, nullptr, cur_time()); return; }
+    MultiFab tmf(layout, cell_type(), M, ng);
+    MultiFab vel;
+    for (int m = 0; m < M; ++m) {
+        const int c = idx[m];
+        if (c < 0 || c >= nstate) throw Error("NavierStokes::timestamp_particles: index " + std::to_string(c) + " of a state of " + std::to_string(nstate) + " components");
+        if (c < Density) {
+            if (!vel.defined()) { vel.define(layout, cell_type(), 3, ng); fillpatch(vel, S[inew], Xvel, 3, bc_vel); }
+            MultiFab::Copy(tmf, vel, c - Xvel, m, 1, ng);
+        } else {
+            MultiFab one(layout, cell_type(), 1, ng);
+            fillpatch(one, S[inew], c, 1, &bc_scal[c - Density]);
+            MultiFab::Copy(tmf, one, 0, m, 1, ng);
+        }
+    }
+    particles->timestamp(level, &tmf, cur_time());
+}
+
+// true where a rank holds particles of the level: every rank decides alike (the fill of timestamp_particles is collective)
+static bool any_particles_at(Particles& pc, int lev)
+{
+    if (Context::get().comm->nranks == 1) return pc.count_at_level(lev) > 0;
+    std::vector<long> per(pc.nlevels(), 0);
+    pc.global_count(per.data(), nullptr);
+    return per[lev] > 0;
+}
+
 double NavierStokes::step()
 {
     double dt_ = dt;
@@ -1585,7 +1616,10 @@ double NavierStokes::step()
     dt_min_adv = advance(dt_);
     time += dt_;
     nstep += 1;
-    if (particles) particles->redistribute(0, 0, 0);
+    if (particles) {
+        particles->redistribute(0, 0, 0);
+        if (particles->timestamps_on() && any_particles_at(*particles, 0)) timestamp_particles(1);     // the l = 0, ngrow = 0 case
+    }
     return dt_;
 }
 

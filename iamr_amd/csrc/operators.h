@@ -352,6 +352,11 @@ public:
     // step (NavierStokes.cpp:672-677); step() then redistributes.  Null: nothing is allocated and no launch is added.
     void set_particles(std::shared_ptr<Particles> pc);
     const std::shared_ptr<Particles>& particle_container() const { return particles; }
+    // the level's share of the timestamp files (NavierStokesBase::post_timestep_particle, NavierStokesBase.cpp:3908-3951): the state
+    // components the container was given (Particles::set_timestamp), FillPatched from the new state on ng ghost layers -- one fill per
+    // boundary-condition group: the velocity, each scalar slot -- sampled at the level's particles and appended at the level's new time.
+    // Collective on several ranks (the fill); the callers (step, AmrNS::post_timestep) skip a level without particles on any rank
+    void timestamp_particles(int ng);
     // the times getForce is called with: the level's own state times in a hierarchy (which keeps them), the level's clock otherwise
     bool amr_times = false;
     double prev_time() const { return amr_times ? st_old : time; }

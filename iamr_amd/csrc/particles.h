@@ -19,6 +19,7 @@
 #include "mf.h"
 #include <vector>
 #include <memory>
+#include <string>
 
 namespace iamrx {
 
@@ -86,6 +87,27 @@ public:
     void total_particle_count(int lev, MultiFab& out, int ocomp);
     // collective: the counts summed over the ranks (per_level: nlevels() entries, may be null)
     void global_count(long* per_level, long* total) const;
+    // ---- state sampled at the particles, and the timestamp files (NavierStokesBase::post_timestep_particle, NavierStokesBase.cpp:3881-3951,
+    // and AMReX's cell-centred cic_interpolate / Timestamp: not in the reference tree, UNPINNED like the rest; tests/timestamp_numpy.py
+    // restates what is implemented).  All three are LOCAL to the rank.
+    static constexpr int MAX_SAMPLE = 16;
+    // the components comps[0 .. M) (any order, 1 <= M <= 16) of the cell-centred mf on the level's boxes, trilinearly interpolated between
+    // cell centres to the particles of level lev, in storage order: host_vals[p * M + m], id[p], cpu[p] for p < count_at_level(lev) (any
+    // may be null; a particle with id <= 0 gets zeros).  The stencil is clamped to the array only: mf arrives with its ghost cells filled
+    // (FillPatch), and they hold what the boundary conditions say.  host_vals, id and cpu all null: the kernel is launched and nothing is
+    // read back or waited for (tools/bench_particles.py times that)
+    void sample(int lev, const MultiFab& mf, const int* comps, int M, double* host_vals, int* id, int* cpu);
+    // basename empty: off (the default).  indices: the state components the step samples (AmrNS::post_timestep, NavierStokes::step); the
+    // container itself only needs their number
+    void set_timestamp(const std::string& basename, std::vector<int> indices);
+    bool timestamps_on() const { return !m_ts_base.empty(); }
+    const std::vector<int>& timestamp_indices() const { return m_ts_indices; }
+    // appends one line per particle of level lev with id > 0, sorted by (id, cpu), to basename + "_" + two digits of rank % 64 (opened in
+    // append mode per call, as upstream: a restart continues the file; no particle: no file is touched):
+    //   id cpu x y z time r0 r1 r2 v_0 .. v_{M-1}      reals %.10e (scientific, precision 10), single blanks
+    // v_m: component m of mf (the first indices.size() components) at the particle; mf null: no values.  With fixed_dir = d the
+    // coordinate d and r_d are left out
+    void timestamp(int lev, const MultiFab* mf, double time);
     int next_id = 1;              // equal on all ranks
     long n_removed = 0;           // removed beyond non-periodic faces since creation, summed over the ranks
     int fixed_dir = -1;           // a coordinate advect leaves alone (the slab direction of a lifted two-dimensional run), -1: none
@@ -102,6 +124,8 @@ private:
     long m_np = 0, m_cap = 0;
     int m_nkeys = 0;
     std::vector<long> m_lev_n, m_lev_start;
+    std::string m_ts_base;
+    std::vector<int> m_ts_indices;
     static void carve(PArrays& a, void* block, long cap);
     void reserve(long cap);
     void free_tables();

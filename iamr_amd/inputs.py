@@ -13,7 +13,8 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   turb.nmodes (its presence switches the turbulent forcing of Tutorials/HIT on) / turb.div_free_force / turb.mode_start, prob.probtype 100 with
   prob.turb_scale (Tutorials/HIT/TurbulentForcing_def.H:36-52, Tutorials/HIT/prob_init.cpp:58-134),
   particles.particle_init_file / particle_restart_file / particle_output_file / restart_from_nonparticle_chkfile / particles_in_plotfile /
-  verbose / do_nspc_particles (NavierStokesBase.cpp:3751-3806; particles.timestamp_* are accepted and ignored)
+  verbose / do_nspc_particles (NavierStokesBase.cpp:3751-3806); particles.timestamp_dir / timestamp_indices are used when this library's
+  own particles.do_timestamps = 1 is given, and accepted and ignored without it
 (reference: Source/NavierStokesBase.cpp:431-557, Source/NavierStokes.cpp:250-310, Source/MacProj.cpp:62-75,
 Source/Projection.cpp:49-65, Source/Diffusion.cpp:98-118, Source/prob/prob_init.cpp:8-60, Source/main.cpp:60-145).
 Keys that select features this library does not have (EB, refinement ratio 4 ...) raise; keys that only
@@ -206,20 +207,39 @@ class Inputs:
         """particles.* (NavierStokesBase::read_particle_params, NavierStokesBase.cpp:3751-3806) -> None (no particles) or a dict.  Upstream
         builds particles in or out at compile time and then defaults do_nspc_particles to true; here they are ON when an init or restart
         file is named or particles.do_nspc_particles = 1 is given, and do_nspc_particles = 0 switches them off whatever else is named (as
-        upstream returns before reading the other keys).  File names are relative to the inputs file.  particles.timestamp_dir /
-        timestamp_indices are accepted and ignored: timestamp files are not written."""
+        upstream returns before reading the other keys).  File names are relative to the inputs file.
+        Timestamp files (NavierStokesBase.cpp:3881-3951) are switched on by this library's own key particles.do_timestamps (default 0):
+        upstream's default timestamp_dir is the non-empty "Timestamps", so every particle run would otherwise write into its working
+        directory.  0: particles.timestamp_dir / timestamp_indices are accepted, ignored and reported.  1: they are used -- the directory
+        (default Timestamps; relative to the working directory, as upstream) and any number of State_Type indices, each checked against
+        the number of state components; out["timestamp"] = dict(dir, indices) with the indices of the library's state: in a
+        two-dimensional (lifted) run the file's indices are the 2-D state's (0 x-velocity, 1 y-velocity, 2 density, 3 tracer, ..) and
+        map to the slab's as 0 -> 0, i -> i + 1."""
         if self.has("particles.pverbose"):                       # :3786-3788 aborts
             raise ValueError("inputs: particles.pverbose found in inputs. Please use particles.verbose")
         keys = [k for k in self.table if k.startswith("particles.")]
-        known = ("do_nspc_particles", "timestamp_dir", "timestamp_indices", "verbose", "particle_init_file", "particle_restart_file",
+        known = ("do_nspc_particles", "do_timestamps", "timestamp_dir", "timestamp_indices", "verbose", "particle_init_file", "particle_restart_file",
                  "restart_from_nonparticle_chkfile", "particle_output_file", "particles_in_plotfile")
         for k in keys:
             if k.split(".", 1)[1] not in known:
                 raise KeyError(f"inputs: key {k} is not understood by this library (not silently ignored)")
             self.used.add(k)
-        for k in ("particles.timestamp_dir", "particles.timestamp_indices"):
-            if self.has(k):
-                self.ignored.append(k)
+        timestamp = None
+        if self.integer("particles.do_timestamps", 0):
+            nstate = 5 + (1 if self.integer("ns.do_trac2", 0) else 0) + (1 if self.integer("ns.do_temp", 0) else 0) - (1 if slab else 0)
+            idx = [int(v) for v in self._get("particles.timestamp_indices")] if self.has("particles.timestamp_indices") else []
+            for i in idx:
+                if not 0 <= i < nstate:
+                    raise ValueError(f"inputs: particles.timestamp_indices = {i}: the state has {nstate} components (0 .. {nstate - 1})")
+            if len(idx) > 16:
+                raise ValueError(f"inputs: particles.timestamp_indices: {len(idx)} indices, at most 16")
+            timestamp = dict(dir=self.string("particles.timestamp_dir", "Timestamps"), indices=[i + 1 if slab and i > 0 else i for i in idx])
+            if not timestamp["dir"]:
+                timestamp = None                                 # an empty directory switches them off upstream too (:3881)
+        else:
+            for k in ("particles.timestamp_dir", "particles.timestamp_indices"):
+                if self.has(k):
+                    self.ignored.append(k)
         do_nspc = self.integer("particles.do_nspc_particles", -1)
 
         def fname(k):
@@ -230,7 +250,8 @@ class Inputs:
         out = dict(init_file=fname("particles.particle_init_file"), restart_file=fname("particles.particle_restart_file"),
                    output_file=self.string("particles.particle_output_file", ""),
                    restart_from_nonparticle_chkfile=self.integer("particles.restart_from_nonparticle_chkfile", 0),
-                   in_plotfile=self.integer("particles.particles_in_plotfile", 0), verbose=self.integer("particles.verbose", 0))
+                   in_plotfile=self.integer("particles.particles_in_plotfile", 0), verbose=self.integer("particles.verbose", 0),
+                   timestamp=timestamp)
         on = do_nspc == 1 or (do_nspc != 0 and bool(out["init_file"] or out["restart_file"]))
         return out if on else None
 

@@ -13,7 +13,11 @@ Files (no device needed):
                        (`iamr_amd-particles-1`); several ranks write format 2: every rank its own arrays, rank 0 the Header last
 
 Several ranks: Particles.add / redistribute / count_global / total_particle_count and save / restore / gather_sorted below are COLLECTIVE
-(every rank calls them); count / read / set_positions speak of this rank's particles (include/iamrx.h).
+(every rank calls them); count / read / set_positions / sample / timestamp speak of this rank's particles (include/iamrx.h).
+
+Timestamp files (NavierStokesBase::post_timestep_particle, NavierStokesBase.cpp:3881-3951): after set_timestamp(basename, indices) the steps of
+the level or hierarchy the container is attached to append `id cpu x y z time r0 r1 r2 v..` per particle to <basename>_NN (NN: the rank),
+v the state components `indices` interpolated to the particle (Particles.sample; tests/timestamp_numpy.py restates it).
 """
 import ctypes as C
 import os
@@ -142,6 +146,24 @@ class Particles:
 
     def total_particle_count(self, lev, out, ocomp=0):
         check(lib().iamrx_particles_derive_count(self.h, 1, int(lev), out.h, int(ocomp)))
+
+    def sample(self, lev, mf, comps):
+        """the components `comps` of the cell-centred MultiFab mf (on the level's boxes, ghost cells filled) at the particles of level lev,
+        this rank's, in storage order -> dict(id, cpu, values (n, M)); trilinear between cell centres (include/iamrx.h)"""
+        c = np.ascontiguousarray(np.asarray(comps, dtype=np.int32).reshape(-1))
+        n = self.count(lev)
+        out = dict(id=np.zeros(n, np.int32), cpu=np.zeros(n, np.int32), values=np.zeros((n, len(c))))
+        check(lib().iamrx_particles_sample(self.h, int(lev), mf.h, len(c), _ip(c), _dp(out["values"]), _ip(out["id"]), _ip(out["cpu"])))
+        return out
+
+    def set_timestamp(self, basename, indices=()):
+        """timestamp files <basename>_NN with the state components `indices` sampled at the particles; basename None or "": off"""
+        c = np.ascontiguousarray(np.asarray(list(indices), dtype=np.int32).reshape(-1))
+        check(lib().iamrx_particles_set_timestamp(self.h, os.fsencode(basename) if basename else None, len(c), _ip(c) if len(c) else None))
+
+    def timestamp(self, lev, mf, time):
+        """append the records of this rank's particles of level lev (mf: the sampled components, or None)"""
+        check(lib().iamrx_particles_timestamp(self.h, int(lev), None if mf is None else mf.h, C.c_double(time)))
 
     def __del__(self):
         try:

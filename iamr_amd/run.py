@@ -172,7 +172,8 @@ def setup_particles(run, pr, say, restart_dir=None):
     NavierStokesBase.cpp:3808-3864): one container for the level or the hierarchy; at start-up the positions of particles.particle_init_file;
     on a restart the checkpoint's Particles/ (unless particles.restart_from_nonparticle_chkfile), then particles.particle_restart_file is
     added and particles.particle_output_file written.  A two-dimensional file lifts (x, y) to (x, mid-slab, y) and the particles never move
-    across the slab.  Several ranks: every call below is collective; rank 0 passes a file's positions and the other ranks none (the ids are
+    across the slab.  With particles.do_timestamps = 1 the timestamp directory is made and the container told to write its records
+    there (<dir>/Timestamp_NN, appended to: a restart continues them).  Several ranks: every call below is collective; rank 0 passes a file's positions and the other ranks none (the ids are
     then those of a one-rank run), the checkpoint's particles are read in shares, and the PARTICLES: line speaks of all ranks.  Returns
     the container or None."""
     pp = pr.get("particles")
@@ -189,6 +190,14 @@ def setup_particles(run, pr, say, restart_dir=None):
         pc.set_fixed_dir(1)
         slab_y = 0.5 * (pr["prob_lo"][1] + pr["prob_hi"][1])
     run.set_particles(pc)
+    ts = pp.get("timestamp")
+    if ts:
+        from .lib import comm_barrier
+        if rank == 0:
+            os.makedirs(ts["dir"], exist_ok=True)
+        comm_barrier()                                  # the directory exists
+        pc.set_timestamp(os.path.join(ts["dir"], "Timestamp"), ts["indices"])
+        say(f"PARTICLES: timestamp records of state components {ts['indices']} go to {os.path.join(ts['dir'], 'Timestamp')}_NN")
     if restart_dir is None:
         if pp["init_file"]:
             pc.add(from_file(pp["init_file"]))

@@ -787,7 +787,8 @@ int iamrx_amr_profile(iamrx_amr a, int enable, double sections_ms[16], double le
  *     create, add, redistribute, derive_count with which = 1, count_global, iamrx_ns_set_particles / iamrx_amr_set_particles, and the
  *     steps, regrids and derives of the object the container is attached to.
  *   LOCAL -- this rank's particles only, in this rank's storage order; box indices are local ones:
- *     count (per_level, total), read, set_positions, advect, derive_count with which = 0, set_next_id, set_fixed_dir.
+ *     count (per_level, total), read, set_positions, advect, derive_count with which = 0, set_next_id, set_fixed_dir, sample,
+ *     set_timestamp, timestamp.
  *   GLOBAL VALUES, equal on every rank: *removed of add and redistribute and *removed_total (sums over the ranks), *next_id, and what
  *     count_global returns.
  * On one rank nothing is collective and every call is what it was. */
@@ -824,6 +825,22 @@ int iamrx_particles_redistribute(iamrx_particles pc, int lev_min, int lev_max, i
 /* which = 0: particle_count (particles of level lev per valid cell); 1: total_particle_count (plus the finer levels' counts coarsened onto
  * lev, NavierStokesBase.cpp:3996-4048); out: cell-centred on the container's boxes of level lev */
 int iamrx_particles_derive_count(iamrx_particles pc, int which, int lev, iamrx_mf out, int ocomp);
+/* The components comps[0 .. ncomp) (1 <= ncomp <= 16, any order, repeats allowed) of the cell-centred mf on the container's boxes of level
+ * lev at the particles of that level, in storage order: vals[p * ncomp + m], id[p], cpu[p] for p < count[lev] (any may be NULL; all three
+ * NULL: the kernel is launched and nothing is read back or waited for).  Trilinear between cell centres: per direction
+ * l = (x - prob_lo) / dx - 0.5, cells floor(l) and floor(l) + 1 with the weights 1 - w and w = l - floor(l), nested as a + w (b - a) in x,
+ * then y, then z.  The stencil is clamped to the array's own index range and NOT to the domain: fill the ghost cells the particles'
+ * stencils reach (one layer for particles inside their boxes) with what the boundary conditions say.  A particle with id <= 0 gets zeros. */
+int iamrx_particles_sample(iamrx_particles pc, int lev, iamrx_mf mf, int ncomp, const int* comps, double* vals, int* id, int* cpu);
+/* Timestamp files (NavierStokesBase::post_timestep_particle, NavierStokesBase.cpp:3881-3951).  basename NULL or "": off (the default).
+ * indices[n] (n <= 16): the State_Type components that the steps of the object the container is attached to sample after each of their
+ * redistributions (FillPatched from the new state); they then call iamrx_particles_timestamp for every level that holds particles. */
+int iamrx_particles_set_timestamp(iamrx_particles pc, const char* basename, int n, const int* indices);
+/* appends one line per particle of level lev with id > 0, sorted by (id, cpu), to <basename>_<two digits of rank % 64> (append mode; a rank
+ * without such particles touches no file):   id cpu x y z time r0 r1 r2 v_0 .. v_{n-1}   -- single blanks, reals as %.10e; v_m is
+ * component m of mf at the particle (mf: cell-centred on the level's boxes, at least n components; NULL: the line ends after r2).  With a
+ * fixed direction d (iamrx_particles_set_fixed_dir) the coordinate d and r_d are left out. */
+int iamrx_particles_timestamp(iamrx_particles pc, int lev, iamrx_mf mf, double time);
 /* attach (pc = NULL: detach).  A level on its own advects its particles at the end of every advance but the initial one and redistributes in
  * iamrx_ns_step; a hierarchy follows NavierStokes::advance / post_timestep_particle / post_regrid.  iamrx_ns_derive knows "particle_count"
  * and "total_particle_count" while a container is attached.  The container must outlive the attachment or be detached first. */

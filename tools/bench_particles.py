@@ -1,4 +1,4 @@
-"""Tracer particles: time of the advect kernel, of a redistribution, and their share of the level step.
+"""Tracer particles: time of the advect kernel, of the sample kernel, of a redistribution, and their share of the level step.
   python tools/bench_particles.py [out.json]
 1. Particles.advect (k_part_advect, both passes) for 2^20 particles on one 128^3 periodic box with a smooth velocity: HIP events on the
    library's launch stream around each call, median of the repeats, once with the particles in random order and once grouped by cell
@@ -6,6 +6,10 @@
    Reported as particles per second and as effective gather bandwidth: per particle and pass 24 face values of 8 B are gathered, and
    pass 1 reads 3 + writes 6, pass 2 reads 6 + writes 6 doubles of particle data plus the id and box words (2 x 4 B per pass):
    bytes = 2 x 24 x 8 + (9 + 12) x 8 + 16 = 568 B per particle.
+1b. Particles.sample (k_part_sample, launch only: nothing read back) of M = 1 and M = 5 components of a smooth 5-component cell array with
+   one ghost layer, on the same two populations and in the same alternation, HIP events as in 1.  Per particle 8 M cell values are
+   gathered and M written, and 3 position doubles, the id and the box word are read: bytes = 32 + 72 M.  Reported next to the advect
+   kernel's time on the same population.
 2. Particles.redistribute of the same two sets, host clock around a synchronised call, median.
 3. a 128^3 TaylorGreen viscous step with one particle per 8 cells attached against the same step without particles, interleaved: host
    clock around a synchronised step, median.
@@ -81,6 +85,30 @@ for name, (pc, ms) in cases.items():
     res["kernel"][name] = {"particles": npart, "box": nn, "ms_median": med, "ms_min": min(ms), "ms_max": max(ms),
                            "particles_per_s": npart / (med * 1e-3), "effective_GB_per_s": npart * BYTES_PER_PARTICLE / (med * 1e-3) / 1e9}
     print("advect", name, res["kernel"][name], flush=True)
+# 1b. the sample kernel on the same sets
+idx = [np.mod(np.arange(-1, nn + 1) + 0.5, nn) * (2 * np.pi / nn) for e in range(3)]
+X, Y, Z = np.meshgrid(*idx, indexing="ij")
+cell = lib.MultiFab(lay, lib.CELL, 5, 1)
+cell.from_numpy(np.stack([0.3 * np.cos(X + 2 * Y + c) * np.sin(Z - Y) + 0.2 * c for c in range(5)], axis=-1), 0)
+res["sample"] = {}
+for M in (1, 5):
+    comps = (C.c_int * M)(*range(M))
+    launch = lambda pc: lib.check(lib.lib().iamrx_particles_sample(pc.h, 0, cell.h, M, comps, None, None, None))
+    times = {name: [] for name in cases}
+    for name, (pc, _) in cases.items():
+        for _ in range(5):
+            launch(pc)
+    for _ in range(30):
+        for name, (pc, _) in cases.items():
+            times[name].append(event_ms(lambda: launch(pc)))
+    for name, ms in times.items():
+        med = statistics.median(ms)
+        adv = res["kernel"][name]["ms_median"]
+        res["sample"][f"{name}_M{M}"] = {"particles": npart, "box": nn, "components": M, "ms_median": med, "ms_min": min(ms), "ms_max": max(ms),
+                                         "ns_per_particle": med * 1e6 / npart, "advect_ns_per_particle": adv * 1e6 / npart,
+                                         "effective_GB_per_s": npart * (32 + 72 * M) / (med * 1e-3) / 1e9}
+        print("sample", name, "M =", M, res["sample"][f"{name}_M{M}"], flush=True)
+del cell
 # 2. the redistribution of the same sets (nothing moves between boxes: placement, prefix, the one read-back, scatter), host clock around a
 #    synchronised call
 res["redistribute"] = {}
