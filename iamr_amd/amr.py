@@ -203,6 +203,18 @@ class Amr:
         check(lib().iamrx_amr_last_sum(self.h, C.byref(st), C.byref(tm), v))
         return None if st.value < 0 else (st.value, tm.value, tuple(v))
 
+    def plane_profile(self, dir, bin_level=0):
+        """plane-averaged profile of the composite state along dir (0, 1, 2) in the slabs of level bin_level (0 .. finest), over the cells
+        no finer level covers (include/iamrx.h: iamrx_amr_plane_profile) -> dict name -> array of nbins for the 14 names of
+        profile.NAMES, plus "coord" (bin centres in physical units) and "names"; the same on every rank.  (`profile` is the section timer.)"""
+        import numpy as np
+        from . import profile as _p
+        ok = 0 <= int(dir) <= 2 and 0 <= int(bin_level) < 30
+        cap = int(self.geom0.n[dir]) * self.ratio ** int(bin_level) if ok else 1
+        out, n = np.zeros(len(_p.NAMES) * cap), C.c_int()
+        check(lib().iamrx_amr_plane_profile(self.h, int(dir), int(bin_level), cap, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+        return _p.as_dict(out, n.value, self.geom0.prob_lo[dir], self.geom0.prob_hi[dir], dir, bin_level)
+
     def profile(self, enable):
         """-> (hierarchy sections [16], per-level sections [nlev][8]) accumulated so far; then enable: 1 reset + start, 0 stop, -1 keep"""
         sec = (C.c_double * 16)()

@@ -1283,6 +1283,24 @@ void AmrNS::sum_integrated_quantities(double out[3])
     }
 }
 
+int AmrNS::plane_profile(int dir, int bin_level, double* out, int cap)
+{
+    const int fin = (int)lev.size() - 1;
+    if (dir < 0 || dir > 2) throw Error("AmrNS::plane_profile: dir must be 0, 1 or 2, not " + std::to_string(dir));
+    if (bin_level < 0 || bin_level > fin) throw Error("AmrNS::plane_profile: bin_level " + std::to_string(bin_level) + " outside 0 .. " + std::to_string(fin));
+    const int nbins = profile_nbins(lev[0]->g, dir, bin_level);
+    if (cap < nbins) throw Error("AmrNS::plane_profile: the profile has " + std::to_string(nbins) + " bins, the caller's array holds " + std::to_string(cap));
+    std::vector<MultiFab> fc(fin);
+    std::vector<ProfileLevel> L;
+    for (int l = 0; l <= fin; ++l) {
+        NavierStokes& s = *lev[l];
+        if (l < fin) fc[l] = fine_coverage(s.layout, lev[l + 1]->layout, s.g, lev[l + 1]->ratio);
+        L.push_back(ProfileLevel{&s.get_new_data(0), l < fin ? &fc[l] : nullptr, &s.g});
+    }
+    profile_reduce((int)L.size(), L.data(), dir, bin_level, Density, Tracer, out);
+    return nbins;
+}
+
 // Amr::timeStep
 // Amr::timeStep's regrid block (upstream AMReX_Amr.cpp): at the start of a step of level l every level i = l .. min(finest, max_level - 1)
 // whose own step count since the last rebuild has reached regrid_int rebuilds the levels above it

@@ -1206,6 +1206,14 @@ int iamrx_ns_average_state(iamrx_ns ns, int set, double v[3])
     IAMRX_CATCH
 }
 int iamrx_ns_sum_integrated(iamrx_ns ns, double sums[3]) { IAMRX_TRY ns->ns->sum_integrated(nullptr, sums); IAMRX_CATCH }
+int iamrx_profile_nq(void) { return PROFILE_NQ; }
+int iamrx_ns_plane_profile(iamrx_ns ns, int dir, int nbins_cap, double* out, int* nbins)
+{
+    IAMRX_TRY
+    const int n = ns->ns->plane_profile(dir, out, nbins_cap);
+    if (nbins) *nbins = n;
+    IAMRX_CATCH
+}
 
 int iamrx_ns_set_data(iamrx_ns ns, int which, iamrx_mf src)
 {
@@ -1637,6 +1645,13 @@ int iamrx_amr_coarse_step(iamrx_amr a, double* dt0)
     IAMRX_CATCH
 }
 int iamrx_amr_sum_integrated(iamrx_amr a, double sums[3]) { IAMRX_TRY a->amr->sum_integrated_quantities(sums); IAMRX_CATCH }
+int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, double* out, int* nbins)
+{
+    IAMRX_TRY
+    const int n = a->amr->plane_profile(dir, bin_level, out, nbins_cap);
+    if (nbins) *nbins = n;
+    IAMRX_CATCH
+}
 int iamrx_amr_last_sum(iamrx_amr a, int* step, double* time, double sums[3])
 {
     IAMRX_TRY

@@ -49,6 +49,18 @@ void stats_accumulate(MultiFab& avg, const MultiFab& S, int vcomp, double dt_avg
 // out(ocomp..ocomp+2) = avg(0..2) / t_mean, out(ocomp+3..ocomp+5) = sqrt(avg(3..5) / t_fluct); a zero divisor counts as 1
 void stats_derive_vel_avg(MultiFab& out, int ocomp, const MultiFab& avg, double t_mean, double t_fluct);
 
+// ---- k_profile.hip: plane-averaged profiles of the state along one axis ----------------------
+// the quantities, in this order: 1, u, v, w, rho, c, uu, vv, ww, uv, uw, vw, rho rho, c c
+constexpr int PROFILE_NQ = 14;
+// one level of the hierarchy: its state, the mask of the cells a finer level covers (cov != 0 there; null: none) and its geometry
+struct ProfileLevel { const MultiFab* S; const MultiFab* cov; const Geometry* g; };
+int profile_nbins(const Geometry& g0, int dir, int bin_level);      // cells of level 0 along dir, times 2^bin_level
+// out[q * nbins + b] = volume-weighted mean of quantity q over the uncovered cells of levels 0 .. nlev - 1 (ratio 2) that meet slab b of
+// the index space of level bin_level along dir; a cell coarser than the bins counts in every bin it spans.  One launch per level, sums in
+// a fixed order (the same call gives the same bits), one all-reduce of the bins over the ranks (a replicated level counts once); every
+// rank receives the result.  A NaN in a counted cell reaches the bins of that cell only; a covered cell is skipped.
+void profile_reduce(int nlev, const ProfileLevel* L, int dir, int bin_level, int rho_comp, int trac_comp, double* out);
+
 struct DomainBC;
 // ---- k_bc.hip -----------------------------------------------------------------------------
 // physical-BC fill of cell-centred ghost cells outside the domain; extdir_lo/hi[n*3+d] constant ext_dir values

@@ -329,6 +329,16 @@ void NavierStokes::sum_integrated(const MultiFab* fine_cov, double out[3])
     if (comm && comm->nranks > 1 && !layout->replicated) comm->allreduce(out, 3, ReduceOp::Sum);
 }
 
+int NavierStokes::plane_profile(int dir, double* out, int cap)
+{
+    if (dir < 0 || dir > 2) throw Error("NavierStokes::plane_profile: dir must be 0, 1 or 2, not " + std::to_string(dir));
+    const int nbins = profile_nbins(g, dir, 0);
+    if (cap < nbins) throw Error("NavierStokes::plane_profile: the profile has " + std::to_string(nbins) + " bins, the caller's array holds " + std::to_string(cap));
+    const ProfileLevel L{&S[inew], nullptr, &g};
+    profile_reduce(1, &L, dir, 0, Density, Tracer, out);
+    return nbins;
+}
+
 void NavierStokes::fillpatch(MultiFab& dst, const MultiFab& src, int scomp, int ncomp, const BCRec* bc)
 {
     const bool is_vel = (bc == bc_vel);

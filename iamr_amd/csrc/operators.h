@@ -309,6 +309,9 @@ public:
     // this level's part of NavierStokes::sum_integrated_quantities (NavierStokes.cpp:1046-1079): volume-weighted sums of density, tracer and
     // kinetic energy over the cells where fine_cov (this level's layout; null: none) is zero, summed over the ranks
     void sum_integrated(const MultiFab* fine_cov, double out[3]);
+    // plane-averaged profile of this level alone along dir (k_profile.hip; nothing masked): out[q * nbins + b], PROFILE_NQ quantities of the
+    // new-time state, nbins = cells of the domain along dir.  Collective; every rank receives the result.  Returns nbins.
+    int plane_profile(int dir, double* out, int cap);
     double time = 0.0, dt = 0.0;
     int nstep = 0;
     MGStats st_mac, st_nodal, st_visc, st_scal;

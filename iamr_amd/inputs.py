@@ -14,7 +14,9 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   prob.turb_scale (Tutorials/HIT/TurbulentForcing_def.H:36-52, Tutorials/HIT/prob_init.cpp:58-134),
   particles.particle_init_file / particle_restart_file / particle_output_file / restart_from_nonparticle_chkfile / particles_in_plotfile /
   verbose / do_nspc_particles (NavierStokesBase.cpp:3751-3806); particles.timestamp_dir / timestamp_indices are used when this library's
-  own particles.do_timestamps = 1 is given, and accepted and ignored without it
+  own particles.do_timestamps = 1 is given, and accepted and ignored without it,
+  ns.profile_interval (-1: off) / ns.profile_dir (the last coordinate) / ns.profile_level (0) / ns.profile_file ("prof"): this library's own
+  keys for the plane-averaged profiles of iamr_amd/profile.py, carried under "profile" of the parsed problem, not in its params
 (reference: Source/NavierStokesBase.cpp:431-557, Source/NavierStokes.cpp:250-310, Source/MacProj.cpp:62-75,
 Source/Projection.cpp:49-65, Source/Diffusion.cpp:98-118, Source/prob/prob_init.cpp:8-60, Source/main.cpp:60-145).
 Keys that select features this library does not have (EB, refinement ratio 4 ...) raise; keys that only
@@ -496,7 +498,17 @@ class Inputs:
                                       "velocity + tracer blob), 5 (DoubleShearLayer), 7 (Euler), 10 (RayleighTaylor), 11 (TaylorGreen), 100 (forced turbulence)")
         if slab:
             prob["dim"] = 2
-        out = dict(n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
+        # plane-averaged profiles (this library's own keys, like particles.do_timestamps): every profile_interval-th level-0 step and once for
+        # the initial data; the axis of a two-dimensional file is the 2-D direction, lifted as gravity is (x -> x, y -> z: the slab's
+        # thickness direction cannot be named); a profile_level above the finest level of the moment is clamped at each output
+        pdir = self.integer("ns.profile_dir", 1 if slab else 2)
+        if pdir < 0 or pdir > (1 if slab else 2):
+            raise ValueError(f"inputs: ns.profile_dir = {pdir}: the directions are 0 .. {1 if slab else 2}")
+        profile = dict(interval=self.integer("ns.profile_interval", -1), dir=2 if slab and pdir == 1 else pdir,
+                       level=self.integer("ns.profile_level", 0), file=self.string("ns.profile_file", "prof"))
+        if profile["level"] < 0:
+            raise ValueError(f"inputs: ns.profile_level = {profile['level']} must be >= 0")
+        out = dict(profile=profile, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
                    max_step=self.integer("max_step", -1), stop_time=self.real("stop_time", -1.0),
                    plot_int=self.integer("amr.plot_int", -1), plot_file=self.string("amr.plot_file", "plt"), plot_vars=self.name_list("amr.plot_vars", "ALL"),
                    derive_plot_vars=self.name_list("amr.derive_plot_vars", "NONE"), fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,

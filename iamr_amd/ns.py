@@ -306,6 +306,17 @@ class NavierStokes:
         check(lib().iamrx_ns_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a, b, c
 
+    def plane_profile(self, dir):
+        """plane-averaged profile of this level along dir (0, 1, 2), nothing masked (include/iamrx.h: iamrx_ns_plane_profile) -> dict
+        name -> array of nbins for the 14 names of profile.NAMES, plus "coord" (bin centres in physical units) and "names"; the same
+        on every rank.  (`profile` is the section timer.)"""
+        import numpy as np
+        from . import profile as _p
+        cap = int(self.geom.n[dir]) if 0 <= int(dir) <= 2 else 1
+        out, n = np.zeros(len(_p.NAMES) * cap), C.c_int()
+        check(lib().iamrx_ns_plane_profile(self.h, int(dir), cap, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+        return _p.as_dict(out, n.value, self.geom.prob_lo[dir], self.geom.prob_hi[dir], dir, 0)
+
     def profile(self, enable):
         arr = (C.c_double * 8)()
         check(lib().iamrx_ns_profile(self.h, int(enable), arr))

@@ -140,6 +140,21 @@ def say_sums(say, time, sums, pr):
         say(line)
 
 
+def take_profile(run, pr, step, rank, say):
+    """ns.profile_interval > 0: every that many level-0 steps (and for the initial data, step 0) the plane-averaged profile of the level or
+    the hierarchy (profile.py) goes to <ns.profile_file><step:05d>.  Collective: every rank takes part in the reduction, rank 0 writes.
+    A bin level above the finest level of the moment is clamped to it (a regrid changes the finest level)."""
+    pf = pr.get("profile") or {}
+    if pf.get("interval", -1) <= 0 or step % pf["interval"] != 0:
+        return
+    from .profile import write_profile
+    p = run.plane_profile(pf["dir"], min(pf["level"], run.nlev - 1)) if hasattr(run, "levels") else run.plane_profile(pf["dir"])
+    if rank == 0:
+        path = f"{pf['file']}{step:05d}"
+        write_profile(path, p, step, run.time)
+        say("PROFILE:", path)
+
+
 def enforce_plane(levels, pr):
     """a two-dimensional run on its y-periodic slab (inputs.Inputs.lift_2d) after every coarse time step: the state, the pressure and its
     gradient become their means across the slab, the velocity / gradient component along it zero.  Upstream's 2-D build has no third
@@ -279,6 +294,7 @@ def main_amr(pr, inp, lib, N, rank=0, world=1, observe=None):
         step = 0
         if amr.last_sum() is not None:          # ns.sum_interval > 0: the hierarchy summed its initial data (NavierStokes.cpp:1284-1285)
             say_sums(say, amr.last_sum()[1], amr.last_sum()[2], pr)
+        take_profile(amr, pr, 0, rank, say)
         if observe:
             observe(amr, 0, None)
         if plot_int > 0:
@@ -298,6 +314,7 @@ def main_amr(pr, inp, lib, N, rank=0, world=1, observe=None):
         ls = amr.last_sum()                     # level 0's post_timestep summed in this step (NavierStokesBase.cpp:2589-2592)
         if ls is not None and ls[0] == step:    # (a slab was flattened after the step: what is reported is what is kept)
             say_sums(say, ls[1], amr.sum_integrated() if pr.get("slab") else ls[2], pr)
+        take_profile(amr, pr, step, rank, say)
         if observe:
             observe(amr, step, dt)
         if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports
@@ -423,6 +440,7 @@ def main(argv, observe=None):
             say_sums(say, ns.time, ns.sum_integrated(), pr)
         if avg_int > 0:
             ns.time_average(ns.dt, 0)
+        take_profile(ns, pr, 0, rank, say)
         if observe:
             observe(ns, 0, None)
         if plot_int > 0:
@@ -444,6 +462,7 @@ def main(argv, observe=None):
             say_sums(say, ns.time, ns.sum_integrated(), pr)
         if avg_int > 0:
             ns.time_average(dt, step)
+        take_profile(ns, pr, step, rank, say)
         if observe:
             observe(ns, step, dt)
         if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports

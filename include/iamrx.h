@@ -581,6 +581,14 @@ int iamrx_ns_average_state(iamrx_ns ns, int set, double v[3]);
 /* One level's part of NavierStokes::sum_integrated_quantities (Source/NavierStokes.cpp:1046-1079): sums[3] = volume-weighted sums of
  * density (MASS), tracer (TRAC) and rho |u|^2 / 2 (KINETIC ENERGY) over ALL cells of the level, on all ranks.  One fused reduction. */
 int iamrx_ns_sum_integrated(iamrx_ns ns, double sums[3]);
+/* Plane-averaged profiles along one axis (this library's own diagnostic, no upstream counterpart; k_profile.hip; not to be confused with
+ * the section timers iamrx_ns_profile / iamrx_amr_profile below).  iamrx_profile_nq: the
+ * number of quantities, 14, in this order: 1, u, v, w, rho, c, uu, vv, ww, uv, uw, vw, rho rho, c c (c: the first tracer; new-time
+ * state).  iamrx_ns_plane_profile: one level, nothing masked; *nbins = cells of the domain along dir (0, 1, 2), out[q * nbins + b] = mean of
+ * quantity q over plane b.  Sums in a fixed order: the same call gives the same bits.  A NaN in a cell reaches the bin of that cell only.
+ * Collective on several ranks, every rank receives the result.  Error: dir outside 0..2, nbins_cap smaller than *nbins. */
+int iamrx_profile_nq(void);
+int iamrx_ns_plane_profile(iamrx_ns ns, int dir, int nbins_cap, double* out, int* nbins);
 
 /* overwrite state (0,1), pressure (2,3) or grad p (4,5) with src (same layout and ngrow; ncomp at most the array's: the leading
  * components are set): the role of NavierStokes::initData for caller-supplied initial data (Source/NavierStokes.cpp:318-420).
@@ -759,6 +767,13 @@ int iamrx_amr_time(iamrx_amr a, double* time, double* dt_levels /* [nlev] or NUL
  * (Source/NavierStokesBase.cpp:2589-2592; *step = that step count); *step = -1: nothing yet. */
 int iamrx_amr_sum_integrated(iamrx_amr a, double sums[3]);
 int iamrx_amr_last_sum(iamrx_amr a, int* step, double* time /* or NULL */, double sums[3]);
+/* Plane-averaged profile of the composite state along dir (see iamrx_ns_plane_profile for the quantities and the layout of out).  The bins are
+ * the slabs, one cell thick, of the index space of level bin_level (0 .. finest): *nbins = cells of level 0 along dir times 2^bin_level.
+ * The value of a bin is the volume-weighted mean over the cells that no finer level covers and that meet the slab: a cell of a level at
+ * or above bin_level lies in one bin, a coarser cell counts in each of the 2^(bin_level - l) bins it spans with that share of its volume
+ * (piecewise constant; the sum over the bins stays conservative).  Quantity 0, the uncovered volume fraction of the slab, is 1.  Covered
+ * cells are skipped, not multiplied by zero.  Error: dir outside 0..2, bin_level outside 0..finest, nbins_cap too small. */
+int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, double* out, int* nbins);
 /* the pieces of NavierStokesBase::post_timestep(lev) one by one (lev < finest), for a caller that drives the loop itself:
  * NavierStokes::reflux, avgDown, mac_sync (= MacProj::mac_sync_solve + mac_sync_compute + the state update and SyncInterp),
  * NavierStokesBase::level_sync (= SyncInterp + Projection::MLsyncProject) */
