@@ -215,6 +215,12 @@ class Amr:
         check(lib().iamrx_amr_plane_profile(self.h, int(dir), int(bin_level), cap, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
         return _p.as_dict(out, n.value, self.geom0.prob_lo[dir], self.geom0.prob_hi[dir], dir, bin_level)
 
+    def spectrum(self):
+        """shell-summed spectra of LEVEL 0 of the hierarchy (after avgDown its covered cells hold the average of the finer data;
+        include/iamrx.h: iamrx_amr_spectrum) -> the dict of NavierStokes.spectrum; the same bits on every rank.  Collective."""
+        from . import spectrum as _s
+        return _s.level_spectrum(lib().iamrx_amr_spectrum, self.h, self.geom0)
+
     def profile(self, enable):
         """-> (hierarchy sections [16], per-level sections [nlev][8]) accumulated so far; then enable: 1 reset + start, 0 stop, -1 keep"""
         sec = (C.c_double * 16)()

@@ -1214,6 +1214,26 @@ int iamrx_ns_plane_profile(iamrx_ns ns, int dir, int nbins_cap, double* out, int
     if (nbins) *nbins = n;
     IAMRX_CATCH
 }
+int iamrx_spectrum_nq(void) { return SPECTRUM_NQ; }
+int iamrx_mf_spectrum(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, int nbins_cap, double* out, long* count, int* nbins)
+{
+    IAMRX_TRY
+    if (!g || !mf) throw Error("iamrx_mf_spectrum: null geometry or array");
+    if (ncomp < 1 || comp < 0 || comp + ncomp > mf->mf.ncomp)
+        throw Error("iamrx_mf_spectrum: components " + std::to_string(comp) + " .. " + std::to_string(comp + ncomp - 1) + " outside the array's " + std::to_string(mf->mf.ncomp));
+    std::vector<int> comps(ncomp);
+    for (int q = 0; q < ncomp; ++q) comps[q] = comp + q;
+    spectrum_of(to_geom(g), mf->mf, ncomp, comps.data(), nbins_cap, out, count, nbins);
+    IAMRX_CATCH
+}
+int iamrx_ns_spectrum(iamrx_ns ns, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY ns->ns->spectrum(nbins_cap, out, count, nbins); IAMRX_CATCH }
+int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, float* ms)
+{
+    IAMRX_TRY
+    if (!g || !mf || !ms) throw Error("iamrx_spectrum_bench: null argument");
+    spectrum_bench(to_geom(g), mf->mf, comp, reps, ms);
+    IAMRX_CATCH
+}
 
 int iamrx_ns_set_data(iamrx_ns ns, int which, iamrx_mf src)
 {
@@ -1652,6 +1672,7 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
     if (nbins) *nbins = n;
     IAMRX_CATCH
 }
+int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY a->amr->level(0).spectrum(nbins_cap, out, count, nbins); IAMRX_CATCH }
 int iamrx_amr_last_sum(iamrx_amr a, int* step, double* time, double sums[3])
 {
     IAMRX_TRY

@@ -1,0 +1,458 @@
+// iamr_amd/csrc/k_spectrum.hip -- shell-summed power spectra of cell-centred fields on a triply periodic level (this library's own
+// diagnostic; the role of the external plotfile post-processor Tutorials/HIT/README sends the reader to, settings derivespect-inputs).
+//
+// Definition (include/iamrx.h): F(m) = (1/N) sum_x f(x) exp(-2 pi i sum_d m_d x_d / n_d); shell s = (int)(kappa + 0.5) with
+// kappa = sqrt((m_x r_x)^2 + (m_y r_y)^2 + (m_z r_z)^2), r_d = L_max / L_d; P(s) = sum over the modes of shell s of |F(m)|^2.
+//
+// One component at a time through one complex work array W (16 B per cell, x fastest) from the arena:
+//   k_spec_pack    valid cells of every local box -> (f, 0) at the cell's place in the level's index space (ghost cells are never read)
+//   k_spec_fft<X>  batched 1-D transforms staged in LDS, in place: radix-2 decimation in time, two stages at a time through registers, the
+//                  bit reversal done by the load into LDS, twiddles from a table the host makes with libm (extended precision) on an octant-reduced angle, no recurrence.
+//                    X = true   a workgroup owns whole contiguous x pencils (LDS: pencil after pencil, one pad element per 32)
+//                    X = false  y or z: a workgroup owns a tile of TW adjacent x columns times the whole pencil, so that every global
+//                               load and store runs along x (LDS: element of the pencil major, x column minor)
+//   k_spec_bin<T>  a wavefront walks a row along k_x in chunks that lie inside one half of the row, where the shell index is monotone:
+//                  a segmented wave scan, the last lane of each run adds into the wavefront's own LDS bins; the four wavefronts of a
+//                  workgroup combine in a fixed order into the workgroup's slots.  T = double: |F|^2; T = unsigned long long: the count.
+//   k_spec_finish  adds the slots of a shell in slot order (one wavefront per shell) and applies 1 / N^2.
+// No floating-point atomics anywhere: the same call gives the same bits, and the result does not depend on how the level is cut into
+// boxes (only the pack sees the boxes).  Several ranks: every rank packs its own boxes into a zeroed real array, the arrays are summed
+// (exact: every cell has one owner), every rank transforms the whole field -- a gather, it does not scale.
+#include "kernels.h"
+#include "launch.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+namespace iamrx {
+
+namespace {
+
+constexpr int SPEC_THREADS = 256;
+constexpr int SPEC_MAXBINS = 2048;       // 4 wavefronts x nbins x 8 B of LDS in k_spec_bin: 64 KiB
+constexpr int SPEC_MAXWG = 1024;         // workgroups (= slots per shell) of k_spec_bin
+
+int ilog2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
+
+// ---------------------------------------------------------------------------------------------------------------- pack
+// grid (chunks, local boxes): cell p of the box -> W[dense index] = (f, 0) (CPLX) or R[dense index] = f
+template <bool CPLX>
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_pack(const BoxD* __restrict__ boxes, const FabD* __restrict__ st, int comp, BoxD dom,
+                                                            double* __restrict__ dst)
+{
+    const BoxD b = boxes[blockIdx.y];
+    const FabD s = st[blockIdx.y];
+    const auto sp = s.gp() + (long)comp * s.cs;
+    const int bx = b.len(0), by = b.len(1);
+    const long np = b.npts(), nx = dom.len(0), ny = dom.len(1);
+    for (long p = (long)blockIdx.x * SPEC_THREADS + threadIdx.x; p < np; p += (long)gridDim.x * SPEC_THREADS) {
+        const int i = (int)(p % bx);
+        const long r = p / bx;
+        const int j = (int)(r % by), k = (int)(r / by);
+        const double v = sp[s.off(b.lo[0] + i, b.lo[1] + j, b.lo[2] + k)];
+        const long o = (long)(b.lo[0] - dom.lo[0] + i) + nx * ((long)(b.lo[1] - dom.lo[1] + j) + ny * (long)(b.lo[2] - dom.lo[2] + k));
+        if (CPLX) { dst[2 * o] = v; dst[2 * o + 1] = 0.0; }
+        else dst[o] = v;
+    }
+}
+
+// the summed real array of several ranks -> (f, 0)
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_expand(const double* __restrict__ R, double2* __restrict__ W, long N)
+{
+    for (long p = (long)blockIdx.x * SPEC_THREADS + threadIdx.x; p < N; p += (long)gridDim.x * SPEC_THREADS) W[p] = make_double2(R[p], 0.0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- transform
+// One pass: every workgroup transforms `tw_` pencils of length n = 2^ln in place.  Element e of pencil t of workgroup g lies at
+//   X:  W[(g * tw_ + t) * n + e]                                          (whole x pencils, contiguous)
+//   !X: W[(g % ntile) * tw_ + t + (g / ntile) * ostride + e * estride]    (tw_ adjacent x columns; y: estride = nx, ostride = nx ny;
+//                                                                          z: estride = nx ny, ostride = nx)
+// twid[q] = exp(-2 pi i q / n), q < n / 2.  LDS: tw_ * (n + n / 32) (X) or tw_ * n (!X) double2.
+template <bool X>
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_fft(double2* __restrict__ W, const double2* __restrict__ twid, int ln, int ltw,
+                                                           int ntile, long estride, long ostride, int pair)
+{
+    extern __shared__ double2 spec_lds[];
+    double2* s = spec_lds;
+    const int n = 1 << ln, tw_ = 1 << ltw, tid = threadIdx.x;
+    const int pstride = n + (n >> 5);                  // X: LDS stride of a pencil (one pad element per 32)
+    const long base = X ? (long)blockIdx.x * tw_ * n : (long)(blockIdx.x % ntile) * tw_ + (long)(blockIdx.x / ntile) * ostride;
+    const int total = n << ltw;
+    // load, element e to the bit-reversed place
+    for (int q = tid; q < total; q += SPEC_THREADS) {
+        if (X) {
+            const int e = q & (n - 1), t = q >> ln;
+            const int r = (int)(__brev((unsigned)e) >> (32 - ln));
+            s[t * pstride + r + (r >> 5)] = W[base + q];
+        } else {
+            const int t = q & (tw_ - 1), e = q >> ltw;
+            const int r = (int)(__brev((unsigned)e) >> (32 - ln));
+            s[(r << ltw) + t] = W[base + t + e * estride];
+        }
+    }
+    __syncthreads();
+    // ln stages of n / 2 butterflies per pencil, (a, c) -> (a + w c, a - w c) with w = exp(-2 pi i pos / (2 h)), two stages at a time:
+    // a thread takes the four elements i0 + {0, h, 2h, 3h} that stages stg and stg + 1 combine among themselves through registers
+    // (the arithmetic of the two radix-2 stages, half the LDS traffic and half the barriers); an odd ln leaves one single stage, and
+    // pair = 0 (SPECTRUM_PAIR_STAGES, the measurement of tools/bench_spectrum.py) leaves them all single: the same bits either way
+    const int quarter = total >> 2;
+    int stg = 0;
+    for (; pair && stg + 1 < ln; stg += 2) {
+        const int h = 1 << stg;
+        for (int q = tid; q < quarter; q += SPEC_THREADS) {
+            int t, b;
+            if (X) { b = q & ((n >> 2) - 1); t = q >> (ln - 2); }
+            else { t = q & (tw_ - 1); b = q >> ltw; }
+            const int pos = b & (h - 1);
+            const int i0 = ((b >> stg) << (stg + 2)) + pos, i1 = i0 + h, i2 = i1 + h, i3 = i2 + h;
+            const int a0 = X ? t * pstride + i0 + (i0 >> 5) : (i0 << ltw) + t;
+            const int a1 = X ? t * pstride + i1 + (i1 >> 5) : (i1 << ltw) + t;
+            const int a2 = X ? t * pstride + i2 + (i2 >> 5) : (i2 << ltw) + t;
+            const int a3 = X ? t * pstride + i3 + (i3 >> 5) : (i3 << ltw) + t;
+            const double2 w = twid[pos << (ln - 1 - stg)];
+            const double2 wa = twid[pos << (ln - 2 - stg)], wb = twid[(pos + h) << (ln - 2 - stg)];
+            const double2 e0 = s[a0], e1 = s[a1], e2 = s[a2], e3 = s[a3];
+            // stage stg: (e0, e1) and (e2, e3)
+            const double c1r = e1.x * w.x - e1.y * w.y, c1i = e1.x * w.y + e1.y * w.x;
+            const double c3r = e3.x * w.x - e3.y * w.y, c3i = e3.x * w.y + e3.y * w.x;
+            const double f0r = e0.x + c1r, f0i = e0.y + c1i, f1r = e0.x - c1r, f1i = e0.y - c1i;
+            const double f2r = e2.x + c3r, f2i = e2.y + c3i, f3r = e2.x - c3r, f3i = e2.y - c3i;
+            // stage stg + 1: (f0, f2) at pos, (f1, f3) at pos + h
+            const double g2r = f2r * wa.x - f2i * wa.y, g2i = f2r * wa.y + f2i * wa.x;
+            const double g3r = f3r * wb.x - f3i * wb.y, g3i = f3r * wb.y + f3i * wb.x;
+            s[a0] = make_double2(f0r + g2r, f0i + g2i);
+            s[a2] = make_double2(f0r - g2r, f0i - g2i);
+            s[a1] = make_double2(f1r + g3r, f1i + g3i);
+            s[a3] = make_double2(f1r - g3r, f1i - g3i);
+        }
+        __syncthreads();
+    }
+    for (; stg < ln; ++stg) {
+        const int h = 1 << stg, half = total >> 1;
+        for (int q = tid; q < half; q += SPEC_THREADS) {
+            int t, b;
+            if (X) { b = q & ((n >> 1) - 1); t = q >> (ln - 1); }
+            else { t = q & (tw_ - 1); b = q >> ltw; }
+            const int pos = b & (h - 1);
+            const int i0 = ((b >> stg) << (stg + 1)) + pos, i1 = i0 + h;
+            const int a0 = X ? t * pstride + i0 + (i0 >> 5) : (i0 << ltw) + t;
+            const int a1 = X ? t * pstride + i1 + (i1 >> 5) : (i1 << ltw) + t;
+            const double2 w = twid[pos << (ln - 1 - stg)];
+            const double2 a = s[a0], c = s[a1];
+            const double cr = c.x * w.x - c.y * w.y, ci = c.x * w.y + c.y * w.x;
+            s[a0] = make_double2(a.x + cr, a.y + ci);
+            s[a1] = make_double2(a.x - cr, a.y - ci);
+        }
+        __syncthreads();
+    }
+    // store, natural order
+    for (int q = tid; q < total; q += SPEC_THREADS) {
+        if (X) {
+            const int e = q & (n - 1), t = q >> ln;
+            W[base + q] = s[t * pstride + e + (e >> 5)];
+        } else {
+            const int t = q & (tw_ - 1), e = q >> ltw;
+            W[base + t + e * estride] = s[(e << ltw) + t];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- shell sums
+struct SpecShape {
+    int nx, ny, nz, nbins;
+    int lcw;                // log2 of the chunk width: min(64, nx / 2) lanes walk one half of a row
+    int rows_per_wg;        // rows (j, k) of a workgroup
+    double rx, ry, rz;      // L_max / L_d
+};
+
+// T = double: val = |F|^2; T = unsigned long long: val = 1.  slots[wg * nbins + s]
+template <typename T>
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_bin(const double2* __restrict__ W, SpecShape sh, T* __restrict__ slots)
+{
+    extern __shared__ double2 spec_lds[];
+    T* bins = (T*)spec_lds;                                  // [4][nbins]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int q = tid; q < 4 * sh.nbins; q += SPEC_THREADS) bins[q] = (T)0;
+    __syncthreads();
+    T* mine = bins + wv * sh.nbins;
+    const int cw = 1 << sh.lcw, nchunk = sh.nx >> sh.lcw, nrows = sh.ny * sh.nz;
+    const int r0 = blockIdx.x * sh.rows_per_wg, r1 = min(r0 + sh.rows_per_wg, nrows);
+    for (int r = r0 + wv; r < r1; r += 4) {
+        const int j = r % sh.ny, k = r / sh.ny;
+        const int my = j < sh.ny / 2 ? j : j - sh.ny, mz = k < sh.nz / 2 ? k : k - sh.nz;
+        const double ay = (double)my * sh.ry, az = (double)mz * sh.rz;
+        const double ay2 = ay * ay, az2 = az * az;
+        for (int c = 0; c < nchunk; ++c) {
+            const int i = (c << sh.lcw) + lane;
+            const bool act = lane < cw;
+            int s = -1;
+            T v = (T)0;
+            if (act) {
+                const int mx = i < sh.nx / 2 ? i : i - sh.nx;
+                const double ax = (double)mx * sh.rx;
+                s = (int)(sqrt((ax * ax + ay2) + az2) + 0.5);        // the squares added left to right (built without FMA contraction)
+                s = min(s, sh.nbins - 1);                            // (never past the LDS bins, whatever a square root rounds to)
+                if constexpr (std::is_floating_point_v<T>) {
+                    const double2 f = W[(long)r * sh.nx + i];
+                    v = f.x * f.x + f.y * f.y;
+                } else {
+                    v = (T)1;
+                }
+            }
+            // inclusive segmented scan over the runs of equal s (contiguous: s is monotone inside the chunk), a fixed tree
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const T up = __shfl_up(v, off, 64);
+                const int ks = __shfl_up(s, off, 64);
+                if (lane >= off && ks == s) v += up;
+            }
+            const int sn = __shfl_down(s, 1, 64);
+            if (act && (lane == cw - 1 || sn != s)) mine[s] += v;        // one lane per shell of the chunk: no two lanes share a bin
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < sh.nbins; q += SPEC_THREADS)
+        slots[(long)blockIdx.x * sh.nbins + q] = ((bins[q] + bins[sh.nbins + q]) + bins[2 * sh.nbins + q]) + bins[3 * sh.nbins + q];
+}
+
+// one wavefront per shell: lane l adds the slots l, l + 64, ... in order, then the lanes combine in a fixed tree; out = sum * scale
+template <typename T>
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_finish(const T* __restrict__ slots, int nwg, int nbins, double scale, T* __restrict__ out)
+{
+    const int s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (s >= nbins) return;
+    T v = (T)0;
+    for (int g = lane; g < nwg; g += 64) v += slots[(long)g * nbins + s];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) {
+        if constexpr (std::is_floating_point_v<T>) out[s] = v * scale;
+        else out[s] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+// exp(-2 pi i q / n), q < n / 2, each part within an ulp: libm in extended precision on the angle reduced to the first octant (the
+// reduction acts on the integer q, so it is exact), rounded once to double; no recurrence
+std::vector<double2> spec_twiddles(int n)
+{
+    std::vector<double2> w(std::max(n / 2, 1));
+    const long double two_pi = 6.283185307179586476925286766559L;
+    for (int q = 0; q < n / 2; ++q) {
+        int m = q;                                  // angle = 2 pi m / n in [0, pi)
+        const bool second = 4 * m > n;              // beyond pi / 2: cos -> -cos(pi - a), sin -> sin(pi - a)
+        if (second) m = n / 2 - m;
+        const bool swap = 8 * m > n;                // beyond pi / 4: cos a = sin(pi / 2 - a), sin a = cos(pi / 2 - a)
+        const long double a = swap ? two_pi * (long double)(n - 4 * m) / (long double)(4 * n) : two_pi * (long double)m / (long double)n;
+        double c = (double)(swap ? std::sin(a) : std::cos(a)), sn = (double)(swap ? std::cos(a) : std::sin(a));
+        if (second) c = -c;
+        w[q] = make_double2(c, -sn);
+    }
+    return w;
+}
+
+struct SpecPlan {
+    SpecShape sh;
+    int ln[3];
+    long N;
+    int nwg;
+    double2* tw[3] = {nullptr, nullptr, nullptr};
+    int xp, ytw, ztw;       // log2 of the pencils per workgroup of the three passes
+    int pair;               // two butterfly stages at a time (1, the default) or one
+};
+
+SpecPlan spec_plan(const Geometry& g, int nbins)
+{
+    SpecPlan p;
+    const BoxD& d = g.domain;
+    p.sh.nx = d.len(0); p.sh.ny = d.len(1); p.sh.nz = d.len(2); p.sh.nbins = nbins;
+    double L[3], Lmax = 0.0;
+    for (int q = 0; q < 3; ++q) { L[q] = g.probhi[q] - g.problo[q]; Lmax = std::max(Lmax, L[q]); p.ln[q] = ilog2(d.len(q)); }
+    p.sh.rx = Lmax / L[0]; p.sh.ry = Lmax / L[1]; p.sh.rz = Lmax / L[2];
+    p.sh.lcw = std::min(6, p.ln[0] - 1);
+    p.N = (long)p.sh.nx * p.sh.ny * p.sh.nz;
+    const int nrows = p.sh.ny * p.sh.nz;
+    p.nwg = std::min(SPEC_MAXWG, std::max(1, nrows / 4));
+    p.sh.rows_per_wg = (nrows + p.nwg - 1) / p.nwg;
+    p.nwg = (nrows + p.sh.rows_per_wg - 1) / p.sh.rows_per_wg;
+    // pencils per workgroup: as many as fit the LDS image (SPECTRUM_TILE_ELEMS complex numbers for y and z, half of that for x; at most
+    // 4096 = 64 KiB), for y and z at least four x columns (64 B of a row) and at most the row
+    const int elems = std::clamp((int)tune("SPECTRUM_TILE_ELEMS", 2048), 256, 4096);
+    const int le = ilog2(elems);
+    p.pair = tune("SPECTRUM_PAIR_STAGES", 1) != 0;
+    p.xp = std::min(std::max(le - 1 - p.ln[0], 0), p.ln[1] + p.ln[2]);        // (the x pass measured fastest at half the image of y and z)
+    p.ytw = std::min(std::max(le - p.ln[1], 2), p.ln[0]);
+    p.ztw = std::min(std::max(le - p.ln[2], 2), p.ln[0]);
+    return p;
+}
+
+void spec_tables(SpecPlan& p)
+{
+    auto& ctx = Context::get();
+    for (int q = 0; q < 3; ++q) {
+        const int n = 1 << p.ln[q];
+        const std::vector<double2> w = spec_twiddles(n);
+        p.tw[q] = (double2*)ctx.alloc(w.size() * sizeof(double2));
+        ctx.upload_async(p.tw[q], w.data(), w.size() * sizeof(double2));
+    }
+}
+
+void spec_pack(const SpecPlan& p, const Geometry& g, const MultiFab& S, int comp, double2* W)
+{
+    auto& ctx = Context::get();
+    const Layout& lay = *S.layout;
+    const int nranks = ctx.comm ? ctx.comm->nranks : 1;
+    const bool gather = nranks > 1 && !lay.replicated;
+    long big = 1;
+    for (int f = 0; f < lay.nlocal(); ++f) big = std::max(big, lay.lbox(f).npts());
+    const dim3 grid((unsigned)std::min<long>((big + 4 * SPEC_THREADS - 1) / (4 * SPEC_THREADS), 65535), (unsigned)std::max(lay.nlocal(), 1));
+    if (!gather) {
+        if (lay.nlocal() > 0)
+            hipLaunchKernelGGL((k_spec_pack<true>), grid, dim3(SPEC_THREADS), 0, ctx.stream, lay.d_boxes, S.d_tab, comp, g.domain, (double*)W);
+        return;
+    }
+    double* R = (double*)ctx.alloc((size_t)p.N * sizeof(double));
+    IAMRX_HIP_CHECK(hipMemsetAsync(R, 0, (size_t)p.N * sizeof(double), ctx.stream));
+    if (lay.nlocal() > 0)
+        hipLaunchKernelGGL((k_spec_pack<false>), grid, dim3(SPEC_THREADS), 0, ctx.stream, lay.d_boxes, S.d_tab, comp, g.domain, R);
+    ctx.comm->allreduce_device(R, (int)p.N, ReduceOp::Sum, ctx.stream);
+    hipLaunchKernelGGL(k_spec_expand, dim3((unsigned)std::min<long>((p.N + 4 * SPEC_THREADS - 1) / (4 * SPEC_THREADS), 65535)), dim3(SPEC_THREADS), 0,
+                       ctx.stream, R, W, p.N);
+    ctx.free(R);
+}
+
+// dir = 0, 1, 2: the transform along that axis of the whole array
+void spec_fft(const SpecPlan& p, int dir, double2* W)
+{
+    auto& ctx = Context::get();
+    const long nx = p.sh.nx, ny = p.sh.ny;
+    const int ln = p.ln[dir], n = 1 << ln;
+    if (dir == 0) {
+        const int pen = 1 << p.xp;
+        const size_t lds = (size_t)pen * (n + (n >> 5)) * sizeof(double2);
+        hipLaunchKernelGGL((k_spec_fft<true>), dim3((unsigned)(p.N / ((long)pen * n))), dim3(SPEC_THREADS), lds, ctx.stream, W, p.tw[0], ln, p.xp, 1, 1L, 0L, p.pair);
+        return;
+    }
+    const int ltw = dir == 1 ? p.ytw : p.ztw;
+    const int ntile = (int)(nx >> ltw);
+    const size_t lds = ((size_t)n << ltw) * sizeof(double2);
+    const long estride = dir == 1 ? nx : nx * ny, ostride = dir == 1 ? nx * ny : nx;
+    const long other = dir == 1 ? p.sh.nz : p.sh.ny;
+    hipLaunchKernelGGL((k_spec_fft<false>), dim3((unsigned)(ntile * other)), dim3(SPEC_THREADS), lds, ctx.stream, W, p.tw[dir], ln, ltw, ntile, estride, ostride, p.pair);
+}
+
+template <typename T>
+void spec_bin(const SpecPlan& p, const double2* W, T* slots, double scale, T* out)
+{
+    auto& ctx = Context::get();
+    hipLaunchKernelGGL((k_spec_bin<T>), dim3((unsigned)p.nwg), dim3(SPEC_THREADS), (size_t)4 * p.sh.nbins * sizeof(T), ctx.stream, W, p.sh, slots);
+    hipLaunchKernelGGL((k_spec_finish<T>), dim3((unsigned)((p.sh.nbins + 3) / 4)), dim3(SPEC_THREADS), 0, ctx.stream, slots, p.nwg, p.sh.nbins, scale, out);
+}
+
+void spec_check_cover(const Geometry& g, const Layout& lay)
+{
+    long cells = 0;
+    for (const BoxD& b : lay.boxes) {
+        for (int d = 0; d < 3; ++d)
+            if (b.lo[d] < g.domain.lo[d] || b.hi[d] > g.domain.hi[d]) throw Error("spectrum: a box of the level reaches outside the domain");
+        cells += b.npts();
+    }
+    if (cells != g.domain.npts())
+        throw Error("spectrum: the boxes of the level do not cover the domain (" + std::to_string(cells) + " of " + std::to_string(g.domain.npts()) + " cells)");
+}
+
+}  // namespace
+
+int spectrum_nbins(const Geometry& g)
+{
+    static const char* axis = "xyz";
+    for (int d = 0; d < 3; ++d)
+        if (!g.periodic[d]) throw Error(std::string("spectrum: direction ") + axis[d] + " is not periodic (a spectrum needs a fully periodic domain)");
+    double Lmax = 0.0, kap2 = 0.0;
+    for (int d = 0; d < 3; ++d) {
+        const int n = g.domain.len(d);
+        if (n < 4 || n > 1024 || (n & (n - 1)) != 0)
+            throw Error(std::string("spectrum: extent n_") + axis[d] + " = " + std::to_string(n) + " is not a power of two in 4 .. 1024");
+        if (!(g.probhi[d] > g.problo[d])) throw Error(std::string("spectrum: the domain has no length along ") + axis[d]);
+        Lmax = std::max(Lmax, g.probhi[d] - g.problo[d]);
+    }
+    for (int d = 0; d < 3; ++d) {
+        const double a = (double)(-(g.domain.len(d) / 2)) * (Lmax / (g.probhi[d] - g.problo[d]));
+        kap2 = kap2 + a * a;
+    }
+    const double kap = std::sqrt(kap2) + 0.5;
+    if (!(kap < (double)SPEC_MAXBINS))
+        throw Error("spectrum: more than " + std::to_string(SPEC_MAXBINS) + " shells (the side lengths of the domain differ too much for its extents)");
+    return (int)kap + 1;
+}
+
+void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* comps, int nbins, double* out, long* count)
+{
+    IAMRX_ASSERT(nq >= 1 && nbins == spectrum_nbins(g));
+    if (!S.type.cell()) throw Error("spectrum: the array is not cell-centred");
+    for (int q = 0; q < nq; ++q)
+        if (comps[q] < 0 || comps[q] >= S.ncomp) throw Error("spectrum: component " + std::to_string(comps[q]) + " outside 0 .. " + std::to_string(S.ncomp - 1));
+    spec_check_cover(g, *S.layout);
+    auto& ctx = Context::get();
+    SpecPlan p = spec_plan(g, nbins);
+    spec_tables(p);
+    const size_t nout = (size_t)(nq + 1) * nbins;
+    ctx.ensure_scratch(nout + 16);
+    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+    double* slots = (double*)ctx.alloc((size_t)p.nwg * nbins * sizeof(double));
+    double* d_out = (double*)ctx.alloc(nout * sizeof(double));
+    const double invN = 1.0 / (double)p.N;
+    for (int q = 0; q < nq; ++q) {
+        spec_pack(p, g, S, comps[q], W);
+        for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
+        spec_bin<double>(p, W, slots, invN * invN, d_out + (size_t)q * nbins);
+    }
+    if (count) {
+        static_assert(sizeof(unsigned long long) == sizeof(double), "the counts share the slots of the sums");
+        spec_bin<unsigned long long>(p, W, (unsigned long long*)slots, 1.0, (unsigned long long*)(d_out + (size_t)nq * nbins));
+    }
+    IAMRX_HIP_CHECK(hipMemcpyAsync(ctx.h_scratch, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
+    ctx.sync();
+    for (size_t q = 0; q < (size_t)nq * nbins; ++q) out[q] = ctx.h_scratch[q];
+    if (count) {
+        for (int s = 0; s < nbins; ++s) {
+            unsigned long long c;
+            std::memcpy(&c, ctx.h_scratch + (size_t)nq * nbins + s, sizeof c);
+            count[s] = (long)c;
+        }
+    }
+    ctx.free(d_out); ctx.free(slots); ctx.free(W);
+    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+}
+
+void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, float* ms)
+{
+    const int nbins = spectrum_nbins(g);
+    spec_check_cover(g, *S.layout);
+    IAMRX_ASSERT(S.type.cell() && comp >= 0 && comp < S.ncomp && reps >= 1);
+    auto& ctx = Context::get();
+    SpecPlan p = spec_plan(g, nbins);
+    spec_tables(p);
+    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+    double* slots = (double*)ctx.alloc((size_t)p.nwg * nbins * sizeof(double));
+    double* d_out = (double*)ctx.alloc((size_t)nbins * sizeof(double));
+    hipEvent_t ev[6];
+    for (auto& e : ev) IAMRX_HIP_CHECK(hipEventCreate(&e));
+    const double invN = 1.0 / (double)p.N;
+    for (int r = 0; r < reps; ++r) {
+        IAMRX_HIP_CHECK(hipEventRecord(ev[0], ctx.stream));
+        spec_pack(p, g, S, comp, W);
+        IAMRX_HIP_CHECK(hipEventRecord(ev[1], ctx.stream));
+        for (int d = 0; d < 3; ++d) { spec_fft(p, d, W); IAMRX_HIP_CHECK(hipEventRecord(ev[2 + d], ctx.stream)); }
+        spec_bin<double>(p, W, slots, invN * invN, d_out);
+        IAMRX_HIP_CHECK(hipEventRecord(ev[5], ctx.stream));
+        IAMRX_HIP_CHECK(hipEventSynchronize(ev[5]));
+        for (int q = 0; q < 5; ++q) IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[5 * r + q], ev[q], ev[q + 1]));
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    ctx.free(d_out); ctx.free(slots); ctx.free(W);
+    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+}
+
+}  // namespace iamrx

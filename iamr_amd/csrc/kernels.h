@@ -61,6 +61,21 @@ int profile_nbins(const Geometry& g0, int dir, int bin_level);      // cells of 
 // rank receives the result.  A NaN in a counted cell reaches the bins of that cell only; a covered cell is skipped.
 void profile_reduce(int nlev, const ProfileLevel* L, int dir, int bin_level, int rho_comp, int trac_comp, double* out);
 
+// ---- k_spectrum.hip: shell-summed power spectra of a triply periodic level -------------------
+// the columns the level and hierarchy entries return: P_u, P_v, P_w, P_c (c: the first tracer)
+constexpr int SPECTRUM_NQ = 4;
+// the number of shells of the geometry (include/iamrx.h); throws, naming the reason, if a direction is not periodic or an extent is
+// not a power of two in 4 .. 1024
+int spectrum_nbins(const Geometry& g);
+// out[q * nbins + s] = sum over the modes of shell s of |F(m)|^2 of component comps[q] of S (cell-centred; its boxes tile the domain of
+// g; ghost cells are never read), count[s] (or null) = modes of shell s.  nbins = spectrum_nbins(g).  One component at a time through
+// one complex work array from the arena; sums in a fixed order (the same call gives the same bits, however the level is cut into
+// boxes).  Collective on several ranks: the field is gathered on every rank, every rank transforms it and receives the same bits.
+void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* comps, int nbins, double* out, long* count);
+// measurement aid (tools/bench_spectrum.py): reps times the five passes of one component -- pack, x, y, z, shell sums -- with an event
+// between them; ms[5 * r + p] = milliseconds of pass p in repeat r
+void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, float* ms);
+
 struct DomainBC;
 // ---- k_bc.hip -----------------------------------------------------------------------------
 // physical-BC fill of cell-centred ghost cells outside the domain; extdir_lo/hi[n*3+d] constant ext_dir values

@@ -339,6 +339,22 @@ int NavierStokes::plane_profile(int dir, double* out, int cap)
     return nbins;
 }
 
+// the common part of the three C entries: *nbins first, then the capacity
+void spectrum_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int cap, double* out, long* count, int* nbins)
+{
+    const int n = spectrum_nbins(g);
+    if (nbins) *nbins = n;
+    if (cap < n) throw Error("spectrum: " + std::to_string(n) + " shells, the caller's arrays hold " + std::to_string(cap));
+    if (!out) throw Error("spectrum: null output array");
+    spectrum_compute(g, S, nq, comps, n, out, count);
+}
+
+void NavierStokes::spectrum(int cap, double* out, long* count, int* nbins)
+{
+    const int comps[SPECTRUM_NQ] = {Xvel, Yvel, Zvel, Tracer};
+    spectrum_of(g, S[inew], SPECTRUM_NQ, comps, cap, out, count, nbins);
+}
+
 void NavierStokes::fillpatch(MultiFab& dst, const MultiFab& src, int scomp, int ncomp, const BCRec* bc)
 {
     const bool is_vel = (bc == bc_vel);

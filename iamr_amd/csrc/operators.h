@@ -195,6 +195,9 @@ private:
     MultiFab m_reg, m_onreg, m_vsfine;
 };
 
+// *nbins = spectrum_nbins(g) first, then the capacity check, then spectrum_compute (kernels.h)
+void spectrum_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int cap, double* out, long* count, int* nbins);
+
 class NavierStokes;
 // sync residual of a level projection (Hydro::NodalProjector::computeSyncResidualCoarse / Fine): crse_side: on the nodes of the level
 // that touch both cells covered by the next finer level and cells that are not, rhs - L(phi) formed with the uncovered cells only;
@@ -312,6 +315,10 @@ public:
     // plane-averaged profile of this level alone along dir (k_profile.hip; nothing masked): out[q * nbins + b], PROFILE_NQ quantities of the
     // new-time state, nbins = cells of the domain along dir.  Collective; every rank receives the result.  Returns nbins.
     int plane_profile(int dir, double* out, int cap);
+    // shell-summed power spectra of u, v, w and the first tracer of the new-time state (k_spectrum.hip): out[q * nbins + s], SPECTRUM_NQ
+    // columns, count[s] (or null) the modes of shell s.  *nbins is set before the capacity is checked.  Collective; every rank receives the
+    // result.
+    void spectrum(int cap, double* out, long* count, int* nbins);
     double time = 0.0, dt = 0.0;
     int nstep = 0;
     MGStats st_mac, st_nodal, st_visc, st_scal;

@@ -16,7 +16,10 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   verbose / do_nspc_particles (NavierStokesBase.cpp:3751-3806); particles.timestamp_dir / timestamp_indices are used when this library's
   own particles.do_timestamps = 1 is given, and accepted and ignored without it,
   ns.profile_interval (-1: off) / ns.profile_dir (the last coordinate) / ns.profile_level (0) / ns.profile_file ("prof"): this library's own
-  keys for the plane-averaged profiles of iamr_amd/profile.py, carried under "profile" of the parsed problem, not in its params
+  keys for the plane-averaged profiles of iamr_amd/profile.py, carried under "profile" of the parsed problem, not in its params,
+  ns.spectrum_interval (-1: off) / ns.spectrum_file ("spec"): this library's own keys for the shell-summed spectra of level 0
+  (iamr_amd/spectrum.py), carried under "spectrum"; an interval > 0 needs a fully periodic three-dimensional domain whose extents are
+  powers of two in 4 .. 1024
 (reference: Source/NavierStokesBase.cpp:431-557, Source/NavierStokes.cpp:250-310, Source/MacProj.cpp:62-75,
 Source/Projection.cpp:49-65, Source/Diffusion.cpp:98-118, Source/prob/prob_init.cpp:8-60, Source/main.cpp:60-145).
 Keys that select features this library does not have (EB, refinement ratio 4 ...) raise; keys that only
@@ -508,7 +511,21 @@ class Inputs:
                        level=self.integer("ns.profile_level", 0), file=self.string("ns.profile_file", "prof"))
         if profile["level"] < 0:
             raise ValueError(f"inputs: ns.profile_level = {profile['level']} must be >= 0")
-        out = dict(profile=profile, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
+        # shell-summed spectra (this library's own keys): every spectrum_interval-th level-0 step and once for the initial data, of level 0
+        spectrum = dict(interval=self.integer("ns.spectrum_interval", -1), file=self.string("ns.spectrum_file", "spec"))
+        if spectrum["interval"] > 0:
+            from .spectrum import extent_ok
+            if slab:
+                raise NotImplementedError("inputs: ns.spectrum_interval > 0 in a two-dimensional run: the transform is three-dimensional only "
+                                          "(the slab's thickness direction has two cells)")
+            if not all(per):
+                raise ValueError(f"inputs: ns.spectrum_interval > 0 needs a fully periodic domain, geometry.is_periodic = {' '.join(str(int(v)) for v in per)}: "
+                                 f"direction {'xyz'[[bool(v) for v in per].index(False)]} is not periodic")
+            for d in range(3):
+                if not extent_ok(n[d]):
+                    raise ValueError(f"inputs: ns.spectrum_interval > 0 needs extents that are powers of two in 4 .. 1024, amr.n_cell has "
+                                     f"n_{'xyz'[d]} = {n[d]}")
+        out = dict(profile=profile, spectrum=spectrum, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
                    max_step=self.integer("max_step", -1), stop_time=self.real("stop_time", -1.0),
                    plot_int=self.integer("amr.plot_int", -1), plot_file=self.string("amr.plot_file", "plt"), plot_vars=self.name_list("amr.plot_vars", "ALL"),
                    derive_plot_vars=self.name_list("amr.derive_plot_vars", "NONE"), fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,

@@ -496,6 +496,13 @@ def turb_force(geom, kxyz, data, div_free, time, out, ocomp=0):
     check(lib().iamrx_turb_force(C.byref(geom), M, k, d, int(div_free), C.c_double(float(time)), out.h, int(ocomp)))
 
 
+def mf_spectrum(geom, mf, comp=0, ncomp=1):
+    """shell-summed power spectra of components comp .. comp + ncomp - 1 of a cell-centred MultiFab whose boxes tile the fully periodic
+    domain of geom (include/iamrx.h: iamrx_mf_spectrum) -> (P (ncomp, nbins), count (nbins,) int64)"""
+    from . import spectrum as _s
+    return _s.mf_spectrum(geom, mf, comp, ncomp)
+
+
 def abec_form(geom, coef, op, phi, rhs, out=None, rho=None, rho_comp=0, scale=1.0, bu=(1.0, 1.0, 1.0), beta=1.0, omega=1.15, lobc=(0, 0, 0), hibc=(0, 0, 0),
               maxorder=3):
     """one operation of the multigrid's finest-level kernel forms (include/iamrx.h: iamrx_abec_form)"""

@@ -317,6 +317,13 @@ class NavierStokes:
         check(lib().iamrx_ns_plane_profile(self.h, int(dir), cap, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
         return _p.as_dict(out, n.value, self.geom.prob_lo[dir], self.geom.prob_hi[dir], dir, 0)
 
+    def spectrum(self):
+        """shell-summed spectra of the new-time state on a fully periodic level (include/iamrx.h: iamrx_ns_spectrum) -> dict with "k"
+        (s 2 pi / L_max), "count" (modes per shell), "E" = (P_u + P_v + P_w) / 2, "Euu", "Evv", "Eww", "Ecc" (c: the first tracer), "n",
+        "L"; the same bits on every rank.  Collective."""
+        from . import spectrum as _s
+        return _s.level_spectrum(lib().iamrx_ns_spectrum, self.h, self.geom)
+
     def profile(self, enable):
         arr = (C.c_double * 8)()
         check(lib().iamrx_ns_profile(self.h, int(enable), arr))

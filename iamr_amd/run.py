@@ -155,6 +155,20 @@ def take_profile(run, pr, step, rank, say):
         say("PROFILE:", path)
 
 
+def take_spectrum(run, pr, step, rank, say):
+    """ns.spectrum_interval > 0: every that many level-0 steps (and for the initial data, step 0) the shell-summed spectra of the level, or
+    of level 0 of the hierarchy (spectrum.py), go to <ns.spectrum_file><step:05d>.  Collective: every rank takes part, rank 0 writes."""
+    sp = pr.get("spectrum") or {}
+    if sp.get("interval", -1) <= 0 or step % sp["interval"] != 0:
+        return
+    from .spectrum import write_spectrum
+    s = run.spectrum()
+    if rank == 0:
+        path = f"{sp['file']}{step:05d}"
+        write_spectrum(path, s, step, run.time)
+        say("SPECTRUM:", path)
+
+
 def enforce_plane(levels, pr):
     """a two-dimensional run on its y-periodic slab (inputs.Inputs.lift_2d) after every coarse time step: the state, the pressure and its
     gradient become their means across the slab, the velocity / gradient component along it zero.  Upstream's 2-D build has no third
@@ -295,6 +309,7 @@ def main_amr(pr, inp, lib, N, rank=0, world=1, observe=None):
         if amr.last_sum() is not None:          # ns.sum_interval > 0: the hierarchy summed its initial data (NavierStokes.cpp:1284-1285)
             say_sums(say, amr.last_sum()[1], amr.last_sum()[2], pr)
         take_profile(amr, pr, 0, rank, say)
+        take_spectrum(amr, pr, 0, rank, say)
         if observe:
             observe(amr, 0, None)
         if plot_int > 0:
@@ -315,6 +330,7 @@ def main_amr(pr, inp, lib, N, rank=0, world=1, observe=None):
         if ls is not None and ls[0] == step:    # (a slab was flattened after the step: what is reported is what is kept)
             say_sums(say, ls[1], amr.sum_integrated() if pr.get("slab") else ls[2], pr)
         take_profile(amr, pr, step, rank, say)
+        take_spectrum(amr, pr, step, rank, say)
         if observe:
             observe(amr, step, dt)
         if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports
@@ -441,6 +457,7 @@ def main(argv, observe=None):
         if avg_int > 0:
             ns.time_average(ns.dt, 0)
         take_profile(ns, pr, 0, rank, say)
+        take_spectrum(ns, pr, 0, rank, say)
         if observe:
             observe(ns, 0, None)
         if plot_int > 0:
@@ -463,6 +480,7 @@ def main(argv, observe=None):
         if avg_int > 0:
             ns.time_average(dt, step)
         take_profile(ns, pr, step, rank, say)
+        take_spectrum(ns, pr, step, rank, say)
         if observe:
             observe(ns, step, dt)
         if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports

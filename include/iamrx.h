@@ -589,6 +589,36 @@ int iamrx_ns_sum_integrated(iamrx_ns ns, double sums[3]);
  * Collective on several ranks, every rank receives the result.  Error: dir outside 0..2, nbins_cap smaller than *nbins. */
 int iamrx_profile_nq(void);
 int iamrx_ns_plane_profile(iamrx_ns ns, int dir, int nbins_cap, double* out, int* nbins);
+/* Shell-summed power spectra of a level on a fully periodic domain (this library's own diagnostic; k_spectrum.hip; the role of the
+ * plotfile post-processor Tutorials/HIT/README names, settings file derivespect-inputs).  For a cell-centred field f on n = (n_x, n_y,
+ * n_z) cells, N = n_x n_y n_z, side lengths L_d:
+ *   transform    F(m) = (1/N) sum_x f(x) exp(-2 pi i sum_d m_d x_d / n_d), signed mode numbers m_d in [-n_d/2, n_d/2): an index
+ *                j >= n_d/2 means j - n_d;
+ *   shell index  L_max = max_d L_d, r_d = L_max / L_d, kappa = sqrt((m_x r_x)^2 + (m_y r_y)^2 + (m_z r_z)^2) (the squares added left to
+ *                right in double, no FMA), s = (int)(kappa + 0.5); shell s stands for the wavenumber k_s = s 2 pi / L_max;
+ *   shells       *nbins = (int)(kappa(-n/2) + 0.5) + 1 with kappa(-n/2) at m_d = -n_d/2 in every direction: all N modes are counted,
+ *                none is cut off at the Nyquist sphere;
+ *   power        P_f(s) = sum over the modes of shell s of |F(m)|^2, so that sum_s P_f(s) = mean(f^2) (Parseval);
+ *   count        count(s) = number of modes of shell s (exact), sum_s count(s) = N.
+ * iamrx_spectrum_nq: the number of columns of the level and hierarchy entries, 4: P_u, P_v, P_w, P_c (c: the first tracer; new-time
+ * state); the kinetic-energy spectrum is E = (P_u + P_v + P_w) / 2.  No density weighting.
+ * iamrx_mf_spectrum: out[q * nbins + s] = P(s) of component comp + q (q < ncomp) of a caller-owned cell-centred array whose boxes tile
+ * the domain of g; ghost cells are never read; count[nbins] may be NULL.  It needs no level object.
+ * iamrx_ns_spectrum: the four columns from the level's new-time state.
+ * All of them: hand-written batched FFTs staged in LDS, one component at a time through one complex work array of 16 N bytes that
+ * returns to the library's arena; sums in a fixed order without floating-point atomics: the same call gives the same bits, and the
+ * bits do not depend on how the level is cut into boxes.  Collective on several ranks: every rank writes the cells of its own boxes
+ * into a zeroed real array, the arrays are summed through the communicator (exact: a cell has one owner), and EVERY rank then
+ * transforms the whole field and receives the same bits -- a gather that does not scale with the number of ranks (a distributed
+ * transform is not built).  Error: a direction that is not periodic; an extent that is not a power of two in 4 .. 1024 (the message
+ * names it); nbins_cap < *nbins (*nbins is set all the same); boxes that do not cover the domain; more than 2048 shells (side lengths
+ * that differ too much for the extents). */
+int iamrx_spectrum_nq(void);
+int iamrx_mf_spectrum(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, int nbins_cap, double* out, long* count, int* nbins);
+int iamrx_ns_spectrum(iamrx_ns ns, int nbins_cap, double* out, long* count, int* nbins);
+/* measurement aid (tools/bench_spectrum.py): reps times the five passes of one component (pack, x, y, z transform, shell sums) with an
+ * event between them; ms[5 * r + p] = milliseconds of pass p in repeat r.  Nothing is read back. */
+int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, float* ms);
 
 /* overwrite state (0,1), pressure (2,3) or grad p (4,5) with src (same layout and ngrow; ncomp at most the array's: the leading
  * components are set): the role of NavierStokes::initData for caller-supplied initial data (Source/NavierStokes.cpp:318-420).
@@ -774,6 +804,9 @@ int iamrx_amr_last_sum(iamrx_amr a, int* step, double* time /* or NULL */, doubl
  * (piecewise constant; the sum over the bins stays conservative).  Quantity 0, the uncovered volume fraction of the slab, is 1.  Covered
  * cells are skipped, not multiplied by zero.  Error: dir outside 0..2, bin_level outside 0..finest, nbins_cap too small. */
 int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, double* out, int* nbins);
+/* The spectra of iamrx_ns_spectrum on LEVEL 0 of the hierarchy: after avgDown its covered cells hold the average of the finer data (the
+ * role of finestLevel = 0 in derivespect-inputs).  Spectra on finer levels and composite spectra are not built. */
+int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins);
 /* the pieces of NavierStokesBase::post_timestep(lev) one by one (lev < finest), for a caller that drives the loop itself:
  * NavierStokes::reflux, avgDown, mac_sync (= MacProj::mac_sync_solve + mac_sync_compute + the state update and SyncInterp),
  * NavierStokesBase::level_sync (= SyncInterp + Projection::MLsyncProject) */
