@@ -1,5 +1,7 @@
 """Hierarchy of NavierStokes levels (ctypes view of iamrx_amr_*; include/iamrx.h): Amr::coarseTimeStep with subcycling,
-NavierStokesBase::post_timestep (reflux, avgDown, mac_sync, level_sync) and the multi-level NavierStokes::post_init."""
+NavierStokesBase::post_timestep (reflux, avgDown, mac_sync, level_sync) and the multi-level NavierStokes::post_init.  What the run driver,
+the checkpoint writer and the particle container read of a run -- levels, layouts, nlev, level_geom, ratio, time, dts, particles,
+plane_profile, spectrum -- a single NavierStokes level offers under the same names (ns.py)."""
 import ctypes as C
 from .lib import lib, check, mg_opts, MgStats
 from .ns import NavierStokes, ns_params
@@ -159,11 +161,6 @@ class Amr:
         check(lib().iamrx_amr_coarse_step(self.h, C.byref(dt)))
         n = C.c_int()
         check(lib().iamrx_amr_nlevels(self.h, C.byref(n)))
-        boxes_now = []
-        for l in range(1, n.value):
-            nb = C.c_int(0)
-            check(lib().iamrx_amr_level_boxes(self.h, l, C.byref(nb), None))
-            boxes_now.append(nb.value)
         if n.value != len(self.levels) or self._grids_changed():
             self._refresh()
         return dt.value

@@ -66,11 +66,6 @@ def _box(lo, hi, typ=(0, 0, 0)):
     return "((" + ",".join(str(v) for v in lo) + ") (" + ",".join(str(v) for v in hi) + ") (" + ",".join(str(v) for v in typ) + "))"
 
 
-def _local_indices(lay):
-    """global indices of the boxes this rank owns, in the order of its local fabs (increasing)"""
-    return [lay.local_box(li)[2] for li in range(lay.nlocal())]
-
-
 def _write_vismf_data(dirname, name, boxes, typ, arrays, ngrow, rank=0, owned=None):
     """phase A of VisMF::Write of one MultiFab, every rank: <name>_D_<rank:05d> with the fabs this rank owns; boxes: ALL valid cell boxes of
     the MultiFab, owned: the global indices (increasing) of those `arrays` belong to (None: every box); arrays: per owned box
@@ -137,20 +132,14 @@ def _geom_line(g, n):
     return "0 " + " ".join(repr(float(v)) for v in lo) + " " + " ".join(repr(float(v)) for v in hi) + " " + _box((0, 0, 0), [v - 1 for v in n])
 
 
-def _level_views(run):
-    """(levels, layouts, geoms, hierarchy or None) of an Amr hierarchy or a single NavierStokes level"""
-    if hasattr(run, "levels"):
-        return run.levels, run.layouts, [run.level_geom(l) for l in range(run.nlev)], run
-    return [run], [run.layout], [run.geom], None
-
-
 def write(run, root, step, max_level=None):
     """checkpoint of `run` (iamr_amd.amr.Amr or iamr_amd.ns.NavierStokes) into <root><step:05d>; returns the directory.  Collective: every
     rank of the library's communicator calls it and writes the fabs it owns; rank 0 writes the headers once the data are complete."""
-    from .lib import lib, check, comm_rank
+    from .lib import lib, check, comm_rank, local_indices
+    from .amr import Amr
     L = lib()
-    levels, lays, geoms, amr = _level_views(run)
-    nlev = len(levels)
+    levels, lays, nlev = run.levels, run.layouts, run.nlev
+    geoms = [run.level_geom(l) for l in range(nlev)]
     rank, world = comm_rank()
     allreduce, barrier = comm_ops(world)
     path = f"{root}{step:05d}"
@@ -163,15 +152,15 @@ def write(run, root, step, max_level=None):
     counters, stop = (C.c_int * 2)(), C.c_double(-1.0)
     nmax = max(max_level, nlev - 1) + 1
     level_count = (C.c_int * nmax)()
-    if amr is not None:
-        check(L.iamrx_amr_restart_state(amr.h, 0, dt_level, dt_min, n_cycle, counters, C.byref(stop)))
-        check(L.iamrx_amr_level_counts(amr.h, 0, level_count, nmax))
+    if isinstance(run, Amr):
+        check(L.iamrx_amr_restart_state(run.h, 0, dt_level, dt_min, n_cycle, counters, C.byref(stop)))
+        check(L.iamrx_amr_level_counts(run.h, 0, level_count, nmax))
     states = []
     for lev in levels:
         st = (C.c_double * 16)()
         check(L.iamrx_ns_restart_state(lev.h, 0, st))
         states.append(list(st))
-    if amr is None:
+    if not isinstance(run, Amr):         # a single level keeps these itself
         dt_level[0], dt_min[0], n_cycle[0] = states[0][1], states[0][12], 1
         counters[0] = counters[1] = int(states[0][2])
         level_count[0] = counters[1]
@@ -200,7 +189,7 @@ def write(run, root, step, max_level=None):
     for l, (lev, lay, g) in enumerate(zip(levels, lays, geoms)):
         ld = os.path.join(path, f"Level_{l}")
         boxes = [(list(lo), list(hi)) for lo, hi in lay.boxes]
-        owned = _local_indices(lay)
+        owned = local_indices(lay)
         n = [geoms[0].n[d] * 2 ** l for d in range(3)]
         H += [str(l), _geom_line(g, n), f"({len(boxes)} 0"] + [_box(lo, hi) for lo, hi in boxes] + [")", str(ntypes)]
         st = states[l]
@@ -245,7 +234,7 @@ def write(run, root, step, max_level=None):
             json.dump(extra, f)
         with open(os.path.join(path, "Header"), "w") as f:
             f.write("\n".join(H) + "\n")
-    pc = getattr(run, "particles", None)
+    pc = run.particles
     if pc is not None:                          # NavierStokesBase::checkPoint: NSPC->Checkpoint(dir, "Particles"); collective (particles.save)
         from .particles import save
         save(path, pc)
@@ -365,7 +354,7 @@ def restart(path, geom0, params, opts=None, single_level=False, stop_time=None, 
         levels = run.levels
     for l, lev in enumerate(levels):
         ld = os.path.join(path, f"Level_{l}")
-        mine = _local_indices(lays[l])
+        mine = Lb.local_indices(lays[l])
         for t, (name, snew, sold, typ, nc) in enumerate(STATE_TYPES):
             for tag, sel in (("New", snew), ("Old", sold)):
                 arrays = _read_vismf(ld, f"SD_{t}_{tag}_MF", mine)
@@ -399,7 +388,7 @@ def restart(path, geom0, params, opts=None, single_level=False, stop_time=None, 
         if stop_time is not None:
             st[13] = float(stop_time)
         check(L.iamrx_ns_restart_state(lev.h, 1, st))
-    if hasattr(run, "levels"):
+    if isinstance(run, Amr):
         dt_level, dt_min = (C.c_double * nlev)(*hd["dt_level"][:nlev]), (C.c_double * nlev)(*hd["dt_min"][:nlev])
         n_cycle = (C.c_int * nlev)(*hd["n_cycle"][:nlev])
         counters = (C.c_int * 2)(extra["level_steps0"], extra["level_count"])

@@ -202,6 +202,11 @@ class Layout:
             pass
 
 
+def local_indices(lay):
+    """global indices (in lay.boxes) of the boxes this rank owns, in the order of its local fabs (increasing)"""
+    return [lay.local_box(li)[2] for li in range(lay.nlocal())]
+
+
 class MultiFab:
     """device-resident multi-component array over the boxes of a Layout"""
 

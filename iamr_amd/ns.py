@@ -225,6 +225,23 @@ class NavierStokes:
     def particles(self):
         return getattr(self, "_particles", None)
 
+    # a level is a hierarchy of one: the read-only members amr.Amr offers the run driver, the checkpoint writer and the particle container
+    nlev, ratio = 1, 2
+
+    @property
+    def levels(self):
+        return [self]
+
+    @property
+    def layouts(self):
+        return [self.layout]
+
+    def level_geom(self, l):
+        return self.geom
+
+    def dts(self):
+        return [self.dt]
+
     def set_data(self, which, mf):
         check(lib().iamrx_ns_set_data(self.h, int(which), mf.h))
 
@@ -306,12 +323,14 @@ class NavierStokes:
         check(lib().iamrx_ns_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a, b, c
 
-    def plane_profile(self, dir):
+    def plane_profile(self, dir, bin_level=0):
         """plane-averaged profile of this level along dir (0, 1, 2), nothing masked (include/iamrx.h: iamrx_ns_plane_profile) -> dict
         name -> array of nbins for the 14 names of profile.NAMES, plus "coord" (bin centres in physical units) and "names"; the same
-        on every rank.  (`profile` is the section timer.)"""
+        on every rank.  bin_level: Amr.plane_profile's argument; a level bins in its own cells.  (`profile` is the section timer.)"""
         import numpy as np
         from . import profile as _p
+        if bin_level != 0:
+            raise ValueError(f"NavierStokes.plane_profile: bin_level {bin_level} on a single level")
         cap = int(self.geom.n[dir]) if 0 <= int(dir) <= 2 else 1
         out, n = np.zeros(len(_p.NAMES) * cap), C.c_int()
         check(lib().iamrx_ns_plane_profile(self.h, int(dir), cap, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))

@@ -54,12 +54,11 @@ class Particles:
         check(lib().iamrx_particles_create(len(geoms), ga, la, int(ratio), C.byref(self.h)))
 
     @staticmethod
-    def for_level(ns):
-        return Particles([ns.geom], [ns.layout], 1)
+    def for_run(run):
+        """a container on the levels of a NavierStokes level or an Amr hierarchy"""
+        return Particles([run.level_geom(l) for l in range(run.nlev)], run.layouts, run.ratio)
 
-    @staticmethod
-    def for_hierarchy(amr):
-        return Particles([amr.level_geom(l) for l in range(amr.nlev)], amr.layouts, amr.ratio)
+    for_level = for_hierarchy = for_run
 
     def add(self, xyz, ids=None, r=None, cpus=None):
         """add particles at the positions xyz (n, 3) -- an empty list is fine; ids default to the container's counter (from 1).  Returns the

@@ -1,6 +1,8 @@
 """`python -m iamr_amd.run <inputs file> [key=value ...]` -- IAMR's main loop (Source/main.cpp:60-145: ParmParse, Amr::init,
 `while (step < max_step && time < stop_time) coarseTimeStep`) driving libiamrx.so from an unmodified IAMR inputs file (SURVEY row
-f4): one level, or a hierarchy of fixed refined grids (amr.max_level > 0 with amr.regrid_file, subcycled, inviscid).  Under
+f4): one level, or a hierarchy of fixed refined grids (amr.max_level > 0 with amr.regrid_file, subcycled, inviscid).  Both go through
+ONE start-up sequence and loop (drive) and one plotfile writer (write_plot): a level offers the members of a hierarchy of one
+(ns.NavierStokes), and what the two do differently are the four small functions in front of drive.  Under
 torch.distributed.run the boxes of every level are spread over the ranks (one process per GPU); plotfiles and checkpoints are written
 by all ranks together (every rank the fabs it owns, rank 0 the headers) and amr.restart reads a checkpoint on any number of ranks.
 IAMRX_RUN_TRANSPORT=gloo: the ranks talk through torch.distributed's gloo on host buffers and all use device 0 (several ranks on the one
@@ -8,6 +10,8 @@ GPU of a test machine); unset: nccl + RCCL, one GPU per rank."""
 import os
 import sys
 import time
+
+from .lib import local_indices          # (which of a layout's boxes this rank owns: callers of level_arrays and write_plot ask here)
 
 
 def init_level(ns, lay, lib, N, pr, n):
@@ -25,15 +29,22 @@ def init_level(ns, lay, lib, N, pr, n):
         ns.init_taylorgreen(pb["vfac"], pb["a"], pb["b"], pb["c"], pb["rho0"])
 
 
+def solver_opts(pr, lib, **mg_kw):
+    """the run's multigrid options.  2-D run on its slab: the multigrid keeps the slab two cells thick (mlmg.hip mg_slab_level) -- a
+    property of THIS problem's solvers, handed over in their options (not process-wide tuning: ADVICE round 5)"""
+    return lib.mg_opts(slab=1 if pr.get("slab") else 0, **mg_kw)
+
+
+def level0_geom(pr, lib):
+    return lib.Geom.make(pr["n"], prob_lo=pr["prob_lo"], prob_hi=pr["prob_hi"], periodic=pr["periodic"])
+
+
 def build_amr(pr, lib, N, world=1, **mg_kw):
     """hierarchy of fixed grids: level 0 chopped by amr.max_grid_size, the refined levels as the grid file gives them"""
     from .amr import Amr
-    # 2-D run on its slab: the multigrid keeps the slab two cells thick (mlmg.hip mg_slab_level) -- a property of THIS problem's solvers,
-    # handed over in their options (not process-wide tuning: ADVICE round 5)
-    opts = lib.mg_opts(slab=1 if pr.get("slab") else 0, **mg_kw)
-    g0 = lib.Geom.make(pr["n"], prob_lo=pr["prob_lo"], prob_hi=pr["prob_hi"], periodic=pr["periodic"])
+    g0 = level0_geom(pr, lib)
     lays = [lib.Layout.decompose(tuple(pr["n"]), pr["max_grid_size"], world)] + [lib.Layout(b, [q % world for q in range(len(b))]) for b in pr["fine_boxes"]]
-    amr = Amr(g0, lays, N.ns_params(**pr["params"]), opts)
+    amr = Amr(g0, lays, N.ns_params(**pr["params"]), solver_opts(pr, lib, **mg_kw))
     for l, lev in enumerate(amr.levels):
         init_level(lev, lays[l], lib, N, pr, [v * 2 ** l for v in pr["n"]])
     if pr.get("regrid"):
@@ -52,9 +63,14 @@ def build_amr(pr, lib, N, world=1, **mg_kw):
     return amr, amr.layouts, g0
 
 
-def local_indices(lay):
-    """global indices (in lay.boxes) of the boxes this rank owns, in the order of its local fabs"""
-    return [lay.local_box(li)[2] for li in range(lay.nlocal())]
+def build(inp, lib, N, nranks=1, pr=None):
+    """one level: the domain chopped by amr.max_grid_size"""
+    pr = pr if pr is not None else inp.problem()
+    g = level0_geom(pr, lib)
+    lay = lib.Layout.decompose(tuple(pr["n"]), pr["max_grid_size"], nranks)
+    ns = N.NavierStokes(g, lay, N.ns_params(**pr["params"]), solver_opts(pr, lib))
+    init_level(ns, lay, lib, N, pr, pr["n"])
+    return ns, lay, g, pr
 
 
 def level_arrays(ns, lay, N, derived=()):
@@ -148,7 +164,7 @@ def take_profile(run, pr, step, rank, say):
     if pf.get("interval", -1) <= 0 or step % pf["interval"] != 0:
         return
     from .profile import write_profile
-    p = run.plane_profile(pf["dir"], min(pf["level"], run.nlev - 1)) if hasattr(run, "levels") else run.plane_profile(pf["dir"])
+    p = run.plane_profile(pf["dir"], min(pf["level"], run.nlev - 1))
     if rank == 0:
         path = f"{pf['file']}{step:05d}"
         write_profile(path, p, step, run.time)
@@ -213,7 +229,7 @@ def setup_particles(run, pr, say, restart_dir=None):
     from . import particles as P
     rank = comm_rank()[0]
     from_file = lambda name: P.read_particle_file(name, slab_y) if rank == 0 else np.zeros((0, 3))
-    pc = P.Particles.for_hierarchy(run) if hasattr(run, "levels") else P.Particles.for_level(run)
+    pc = P.Particles.for_run(run)
     slab_y = None
     if pr.get("slab"):
         pc.set_fixed_dir(1)
@@ -246,143 +262,136 @@ def setup_particles(run, pr, say, restart_dir=None):
 
 def plot_particles(run, pr, path):
     """particles.particles_in_plotfile (NavierStokes.cpp:1201-1205): the plotfile gets the Particles/ directory of a checkpoint"""
-    pc = getattr(run, "particles", None)
+    pc = run.particles
     if pc is not None and pr["particles"]["in_plotfile"]:
         from .particles import save
         save(path, pc)
     return path
 
 
-def write_plot_amr(amr, lays, pr, N, step, root):
-    """NavierStokesBase::writePlotFile role for the hierarchy: one AMReX plotfile with every level (the five state components).
-    Collective: every rank calls it and writes the boxes it owns (plotfile.write_collective)."""
+def write_plot(run, lay, pr, N, step, root):
+    """NavierStokesBase::writePlotFile role: AMReX-format plotfile <root><step:05d> with every level of `run` (a level or a hierarchy): the
+    state variables of amr.plot_vars and the derived quantities of amr.derive_plot_vars.  `lay`: the layouts of the levels (for a single
+    level its layout will do); they name all boxes and their owners.  Collective: every rank of the library's communicator calls it and
+    writes the boxes it owns (plotfile.write_collective).  A two-dimensional run (single-rank: every box is local) writes its plane."""
     from .plotfile import PlotFile, Level, write_collective
     from .lib import comm_rank
     rank, world = comm_rank()
+    lays = lay if isinstance(lay, (list, tuple)) else [lay]
     names, der, kept = plot_names_and_filter(pr)
+    slab = pr.get("slab")
+    ax = [0, 2] if slab else [0, 1, 2]                      # the directions the plotfile knows
     levels = []
-    dts = amr.dts()
-    for l, lev in enumerate(amr.levels):
+    for l, lev in enumerate(run.levels):
         n = [v * 2 ** l for v in pr["n"]]
         dx = [(pr["prob_hi"][d] - pr["prob_lo"][d]) / n[d] for d in range(3)]
         boxes, arrs = level_arrays(lev, lays[l], N, der)
-        if pr.get("slab"):
+        if slab:
             boxes, arrs, names2 = _plane(boxes, arrs, names)
-            plane_names = [nm for q, nm in enumerate(names) if q != 1]
-            out_names, arrs = select_components(plane_names, arrs, kept, names2)
-            levels.append(Level(((0, 0), (n[0] - 1, n[2] - 1)), [dx[0], dx[2]], boxes, arrs, step * 2 ** l, amr.time))
+            out_names, arrs = select_components([nm for q, nm in enumerate(names) if q != 1], arrs, kept, names2)
+            owned = None
         else:
             out_names, arrs = select_components(names, arrs, kept)
-            levels.append(Level(((0, 0, 0), tuple(v - 1 for v in n)), dx, lays[l].boxes, arrs, step * 2 ** l, amr.time, owned=local_indices(lays[l])))
+            boxes, owned = lays[l].boxes, local_indices(lays[l])
+        levels.append(Level(([0] * len(ax), [n[d] - 1 for d in ax]), [dx[d] for d in ax], boxes, arrs, step * 2 ** l, run.time, owned=owned))
+    pf = PlotFile(out_names, run.time, [pr["prob_lo"][d] for d in ax], [pr["prob_hi"][d] for d in ax], levels)
     path = f"{root}{step:05d}"
-    if pr.get("slab"):                      # single-rank runs (main): every box is local
-        PlotFile(out_names, amr.time, [pr["prob_lo"][0], pr["prob_lo"][2]], [pr["prob_hi"][0], pr["prob_hi"][2]], levels).write(path)
+    if slab:
+        pf.write(path)
     else:
-        write_collective(PlotFile(out_names, amr.time, pr["prob_lo"], pr["prob_hi"], levels), path, [lay.owners for lay in lays], rank, world)
-    return plot_particles(amr, pr, path)
+        write_collective(pf, path, [ll.owners for ll in lays], rank, world)
+    return plot_particles(run, pr, path)
 
 
-def main_amr(pr, inp, lib, N, rank=0, world=1, observe=None):
-    """hierarchy run; world > 1: the boxes of every level are spread over the ranks (level 0 by Layout.decompose, fixed refined grids
-    round-robin, regridded levels by the library's knapsack, restarted levels as checkpoint.restart says); observe: see main"""
+# ---- what a hierarchy and a single level do differently in the main loop
+def _hierarchy(run):
+    from .amr import Amr
+    return isinstance(run, Amr)
+
+
+def advance(run):
+    """one coarse time step -> its dt"""
+    return run.coarse_step() if _hierarchy(run) else run.step()
+
+
+def step_line(run, step, dt):
+    line = f"STEP = {step} TIME = {run.time:.12g} DT = {dt:.12g}"
+    return line + f" LEVELS = {run.nlev} GRIDS = {[len(l.boxes) for l in run.layouts]}" if _hierarchy(run) else line
+
+
+def report_sums(run, pr, step, say):
+    """ns.sum_interval > 0: the integrated quantities of the initial data (step 0; NavierStokes.cpp:1284-1285) and of every sum_interval-th
+    level-0 step (post_timestep, NavierStokesBase.cpp:2589-2592).  A hierarchy sums by itself and is asked for what it found; the
+    driver of a single level sums when they are due."""
+    if _hierarchy(run):
+        ls = run.last_sum()
+        if ls is not None and ls[0] == step:    # (a slab was flattened after the step: what is reported is what is kept)
+            say_sums(say, ls[1], run.sum_integrated() if pr.get("slab") and step > 0 else ls[2], pr)
+    elif pr["params"].get("sum_interval", -1) > 0 and step % pr["params"]["sum_interval"] == 0:
+        say_sums(say, run.time, run.sum_integrated(), pr)
+
+
+def take_time_average(run, pr, step, dt):
+    """ns.avg_interval > 0: a hierarchy samples by itself; the driver of a single level after post_init (step 0, dt None: the level's dt;
+    NavierStokes.cpp:1286-1297) and after every step (NavierStokesBase.cpp:2630-2634)"""
+    if not _hierarchy(run) and pr["params"].get("avg_interval", 0) > 0:
+        run.time_average(run.dt if dt is None else dt, step)
+
+
+def drive(pr, inp, lib, N, hierarchy, rank=0, world=1, observe=None):
+    """a run from amr.restart or from its initial data to max_step / stop_time: a single level, or (hierarchy) an Amr hierarchy.  world > 1:
+    the boxes of every level are spread over the ranks (level 0 by Layout.decompose, fixed refined grids round-robin, regridded levels
+    by the library's knapsack, restarted levels as checkpoint.restart says) and every rank executes the same sequence of collective
+    operations: step, enforce_plane, sums, time average, profile, spectrum, observe, plotfile, checkpoint.  observe: see main"""
+    from . import checkpoint
     say = print if rank == 0 else (lambda *a, **k: None)
-    check_int, check_root = pr.get("check_int", -1), pr.get("check_file", "chk")
     plot_int, plot_root = pr.get("plot_int", -1), pr.get("plot_file", "plt")
+    check_int, check_root = pr.get("check_int", -1), pr.get("check_file", "chk")
+
+    def post_step(step, dt):
+        """NavierStokes::post_init for the initial data (step 0, dt None), post_timestep of level 0 after a step, and the output then due"""
+        report_sums(run, pr, step, say)
+        take_time_average(run, pr, step, dt)
+        take_profile(run, pr, step, rank, say)
+        take_spectrum(run, pr, step, rank, say)
+        if observe:
+            observe(run, step, dt)
+        if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports
+            say("PLOTFILE:", write_plot(run, run.layouts, pr, N, step, plot_root))
+
     if pr.get("restart"):
         # amr.restart (Amr::restart): grids, data, times and step counters come from the checkpoint, parameters from the inputs file
-        from . import checkpoint
-        g0 = lib.Geom.make(pr["n"], prob_lo=pr["prob_lo"], prob_hi=pr["prob_hi"], periodic=pr["periodic"])
-        # (the solvers' options are the run's, not the checkpoint's: a two-dimensional run restarts with its slab multigrid, see build_amr)
-        amr = checkpoint.restart(pr["restart"], g0, N.ns_params(**pr["params"]), opts=lib.mg_opts(slab=1 if pr.get("slab") else 0),
-                                 stop_time=pr["stop_time"], rank=rank, world=world)
+        # (the solvers' options are the run's too: a two-dimensional run restarts with its slab multigrid, see solver_opts)
+        run = checkpoint.restart(pr["restart"], level0_geom(pr, lib), N.ns_params(**pr["params"]), opts=solver_opts(pr, lib),
+                                 single_level=not hierarchy, stop_time=pr["stop_time"], rank=rank, world=world)
         if pr.get("regrid"):
-            amr.set_regrid(**pr["regrid"])
-        lays = amr.layouts
+            run.set_regrid(**pr["regrid"])
         step = checkpoint.read_header(pr["restart"])["level_steps"][0]
-        say(f"RESTART from {pr['restart']}: step {step}, time {amr.time:.12g}, levels {amr.nlev}")
-        setup_particles(amr, pr, say, pr["restart"])
+        say(f"RESTART from {pr['restart']}: step {step}, time {run.time:.12g}" + (f", levels {run.nlev}" if hierarchy else ""))
+        setup_particles(run, pr, say, pr["restart"])
     else:
-        amr, lays, g0 = build_amr(pr, lib, N, world)
-        amr.post_init(pr["stop_time"])
-        setup_particles(amr, pr, say)               # (nothing moves them during the initial iterations: NavierStokes.cpp:672-677)
+        run = build_amr(pr, lib, N, world)[0] if hierarchy else build(inp, lib, N, world, pr)[0]
+        run.post_init(pr["stop_time"])
+        setup_particles(run, pr, say)               # (nothing moves them during the initial iterations: NavierStokes.cpp:672-677)
         step = 0
-        if amr.last_sum() is not None:          # ns.sum_interval > 0: the hierarchy summed its initial data (NavierStokes.cpp:1284-1285)
-            say_sums(say, amr.last_sum()[1], amr.last_sum()[2], pr)
-        take_profile(amr, pr, 0, rank, say)
-        take_spectrum(amr, pr, 0, rank, say)
-        if observe:
-            observe(amr, 0, None)
-        if plot_int > 0:
-            say("PLOTFILE:", write_plot_amr(amr, lays, pr, N, 0, plot_root))
+        post_step(0, None)
     if inp.ignored:
         say("inputs: ignored (I/O / verbosity / AMR bookkeeping) keys:", " ".join(sorted(inp.ignored)))
     t0 = time.perf_counter()
-    while (pr["max_step"] < 0 or step < pr["max_step"]) and (pr["stop_time"] < 0 or amr.time < pr["stop_time"] - 1e-14):
+    while (pr["max_step"] < 0 or step < pr["max_step"]) and (pr["stop_time"] < 0 or run.time < pr["stop_time"] - 1e-14):
         if pr["max_step"] < 0 and pr["stop_time"] < 0:
             break
-        dt = amr.coarse_step()
+        dt = advance(run)
         if pr.get("slab"):
-            enforce_plane(amr.levels, pr)
-        lays = amr.layouts                      # a regrid during the step replaces them
+            enforce_plane(run.levels, pr)
         step += 1
-        say(f"STEP = {step} TIME = {amr.time:.12g} DT = {dt:.12g} LEVELS = {amr.nlev} GRIDS = {[len(l.boxes) for l in lays]}")
-        ls = amr.last_sum()                     # level 0's post_timestep summed in this step (NavierStokesBase.cpp:2589-2592)
-        if ls is not None and ls[0] == step:    # (a slab was flattened after the step: what is reported is what is kept)
-            say_sums(say, ls[1], amr.sum_integrated() if pr.get("slab") else ls[2], pr)
-        take_profile(amr, pr, step, rank, say)
-        take_spectrum(amr, pr, step, rank, say)
-        if observe:
-            observe(amr, step, dt)
-        if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports
-            say("PLOTFILE:", write_plot_amr(amr, lays, pr, N, step, plot_root))
+        say(step_line(run, step, dt))
+        post_step(step, dt)
         if check_int > 0 and step % check_int == 0:
-            from . import checkpoint
-            say("CHECKPOINT:", checkpoint.write(amr, check_root, step, pr.get("max_level")))
+            say("CHECKPOINT:", checkpoint.write(run, check_root, step, pr.get("max_level") if hierarchy else None))
     lib.sync()
     say(f"Run time = {time.perf_counter() - t0:.6f}")
     return 0
-
-
-def build(inp, lib, N, nranks=1, pr=None):
-    pr = pr if pr is not None else inp.problem()
-    opts = lib.mg_opts(slab=1 if pr.get("slab") else 0)        # (see build_amr)
-    g = lib.Geom.make(pr["n"], prob_lo=pr["prob_lo"], prob_hi=pr["prob_hi"], periodic=pr["periodic"])
-    lay = lib.Layout.decompose(tuple(pr["n"]), pr["max_grid_size"], nranks)
-    ns = N.NavierStokes(g, lay, N.ns_params(**pr["params"]), opts)
-    pb = pr["prob"]
-    if pb["probtype"] == 1:
-        ns.init_rest(pb["rho0"])
-    elif pb["probtype"] in (2, 4, 5, 6, 7, 100):
-        from .probinit import set_initial_state
-        ns.init_rest(pb["density_ic"])
-        set_initial_state(ns, lay, lib, N, pb, pr["n"], pr["prob_lo"], pr["prob_hi"])
-    elif pb["probtype"] == 10:
-        ns.init_rayleightaylor(pb["rho_1"], pb["rho_2"], pb["tra_1"], pb["tra_2"], pb["pertamp"], pb["interface_width"])
-    else:
-        ns.init_taylorgreen(pb["vfac"], pb["a"], pb["b"], pb["c"], pb["rho0"])
-    return ns, lay, g, pr
-
-
-def write_plot(ns, lay, pr, N, step, root):
-    """NavierStokesBase::writePlotFile role (single level): AMReX-format plotfile <root><step:05d> with the state variables of
-    amr.plot_vars and the derived quantities of amr.derive_plot_vars.  Collective: every rank of the library's communicator calls it and
-    writes the boxes it owns (plotfile.write_collective); `lay` names all boxes and their owners."""
-    from .plotfile import from_level_data, write_collective
-    from .lib import comm_rank
-    rank, world = comm_rank()
-    names, der, kept = plot_names_and_filter(pr)
-    boxes, arrs = level_arrays(ns, lay, N, der)
-    path = f"{root}{step:05d}"
-    if pr.get("slab"):
-        boxes, arrs, names2 = _plane(boxes, arrs, names)
-        out_names, arrs = select_components([nm for q, nm in enumerate(names) if q != 1], arrs, kept, names2)
-        from_level_data((pr["n"][0], pr["n"][2]), (pr["prob_lo"][0], pr["prob_lo"][2]), (pr["prob_hi"][0], pr["prob_hi"][2]), boxes, arrs, ns.time, step, names=out_names).write(path)
-    else:
-        out_names, arrs = select_components(names, arrs, kept)
-        pf = from_level_data(tuple(pr["n"]), tuple(pr["prob_lo"]), tuple(pr["prob_hi"]), lay.boxes, arrs, ns.time, step, names=out_names)
-        pf.levels[0].owned = local_indices(lay)
-        write_collective(pf, path, [lay.owners], rank, world)
-    return plot_particles(ns, pr, path)
 
 
 def main(argv, observe=None):
@@ -427,74 +436,12 @@ def main(argv, observe=None):
     pr = inp.problem()
     if pr.get("slab") and world > 1:
         raise NotImplementedError("iamr_amd.run: two-dimensional inputs (run on a y-periodic slab) are single-rank runs")
-    say = print if rank == 0 else (lambda *a, **k: None)
-    if pr["fine_boxes"] or pr.get("regrid") or (pr.get("restart") and pr.get("max_level", 0) > 0):
-        rc = main_amr(pr, inp, lib, N, rank, world, observe)
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
-        return rc
-    plot_int, plot_root = pr.get("plot_int", -1), pr.get("plot_file", "plt")
-    check_int, check_root = pr.get("check_int", -1), pr.get("check_file", "chk")
-    sum_int, avg_int = pr["params"].get("sum_interval", -1), pr["params"].get("avg_interval", 0)
-    if pr.get("restart"):
-        from . import checkpoint
-        g = lib.Geom.make(pr["n"], prob_lo=pr["prob_lo"], prob_hi=pr["prob_hi"], periodic=pr["periodic"])
-        ns = checkpoint.restart(pr["restart"], g, N.ns_params(**pr["params"]), opts=lib.mg_opts(slab=1 if pr.get("slab") else 0), single_level=True,
-                                stop_time=pr["stop_time"], rank=rank, world=world)
-        lay = ns.layout
-        step = checkpoint.read_header(pr["restart"])["level_steps"][0]
-        say(f"RESTART from {pr['restart']}: step {step}, time {ns.time:.12g}")
-        setup_particles(ns, pr, say, pr["restart"])
-    else:
-        ns, lay, g, pr = build(inp, lib, N, world, pr)
-        ns.post_init(pr["stop_time"])
-        setup_particles(ns, pr, say)
-        step = 0
-        # NavierStokes::post_init, NavierStokes.cpp:1284-1297: the sums of the initial data, which are also the first sample of the averages
-        if sum_int > 0:
-            say_sums(say, ns.time, ns.sum_integrated(), pr)
-        if avg_int > 0:
-            ns.time_average(ns.dt, 0)
-        take_profile(ns, pr, 0, rank, say)
-        take_spectrum(ns, pr, 0, rank, say)
-        if observe:
-            observe(ns, 0, None)
-        if plot_int > 0:
-            say("PLOTFILE:", write_plot(ns, lay, pr, N, 0, plot_root))
-    if rank == 0 and inp.ignored:
-        print("inputs: ignored (I/O / verbosity / AMR bookkeeping) keys:", " ".join(sorted(inp.ignored)))
-    t0 = time.perf_counter()
-    while (pr["max_step"] < 0 or step < pr["max_step"]) and (pr["stop_time"] < 0 or ns.time < pr["stop_time"] - 1e-14):
-        if pr["max_step"] < 0 and pr["stop_time"] < 0:
-            break
-        dt = ns.step()
-        if pr.get("slab"):
-            enforce_plane([ns], pr)
-        step += 1
-        if rank == 0:
-            print(f"STEP = {step} TIME = {ns.time:.12g} DT = {dt:.12g}")
-        # NavierStokesBase::post_timestep on the one level (NavierStokesBase.cpp:2589-2592, 2630-2634)
-        if sum_int > 0 and step % sum_int == 0:
-            say_sums(say, ns.time, ns.sum_integrated(), pr)
-        if avg_int > 0:
-            ns.time_average(dt, step)
-        take_profile(ns, pr, step, rank, say)
-        take_spectrum(ns, pr, step, rank, say)
-        if observe:
-            observe(ns, step, dt)
-        if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports
-            say("PLOTFILE:", write_plot(ns, lay, pr, N, step, plot_root))
-        if check_int > 0 and step % check_int == 0:
-            from . import checkpoint
-            say("CHECKPOINT:", checkpoint.write(ns, check_root, step))
-    lib.sync()
-    if rank == 0:
-        print(f"Run time = {time.perf_counter() - t0:.6f}")
+    hierarchy = bool(pr["fine_boxes"] or pr.get("regrid") or (pr.get("restart") and pr.get("max_level", 0) > 0))
+    rc = drive(pr, inp, lib, N, hierarchy, rank, world, observe)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    return 0
+    return rc
 
 
 if __name__ == "__main__":
