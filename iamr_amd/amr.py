@@ -218,6 +218,18 @@ class Amr:
         from . import spectrum as _s
         return _s.level_spectrum(lib().iamrx_amr_spectrum, self.h, self.geom0)
 
+    def histogram(self, names, nbins=64, range=None):
+        """composite histograms and PDFs of named fields (include/iamrx.h: iamrx_amr_histogram; pdf.py): level l counts the cells level
+        l + 1 does not cover with the weight 8^(finest - l), so the counts are in finest-level cell volumes -> the dict of
+        NavierStokes.histogram.  range None: each field's minimum and maximum over the valid cells of all levels.  Collective."""
+        from . import pdf as _p
+        return _p.histogram(self, lib().iamrx_amr_histogram, names, nbins, range)
+
+    def histogram2(self, namex, namey, nbins=(32, 32), range=None):
+        """composite joint histogram of two named fields (include/iamrx.h: iamrx_amr_histogram2) -> the dict of NavierStokes.histogram2"""
+        from . import pdf as _p
+        return _p.histogram2(self, lib().iamrx_amr_histogram2, namex, namey, nbins, range)
+
     def profile(self, enable):
         """-> (hierarchy sections [16], per-level sections [nlev][8]) accumulated so far; then enable: 1 reset + start, 0 stop, -1 keep"""
         sec = (C.c_double * 16)()

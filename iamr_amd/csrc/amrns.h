@@ -38,6 +38,11 @@ public:
     // plane-averaged profile of the composite state along dir (k_profile.hip): the PROFILE_NQ volume-weighted means of every slab of the
     // index space of level bin_level (0 .. finest), over the cells no finer level covers; out[q * nbins + b].  Returns nbins.
     int plane_profile(int dir, int bin_level, double* out, int cap);
+    // composite histograms of named fields (k_hist.hip; the names: NavierStokes::hist_field): level l counts the cells level l + 1 does not
+    // cover, each with the weight 8^(finest - l), so the slots are in units of finest-level cell volumes and together sum to
+    // cells(level 0) * 8^finest (an error unless that stays below 2^53).  Layout of counts as NavierStokes::histogram / histogram2.
+    void histogram(int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts);
+    void histogram2(const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts);
     int last_sum_step = -1;
     // ---- regridding (Amr::regrid from level 0 at the start of a coarse step; NavierStokes::errorEst, NS_error.cpp:10-145;
     // NavierStokesBase::init(AmrLevel&) / init(), NavierStokesBase.cpp:1713-1806) ----

@@ -1301,6 +1301,56 @@ int AmrNS::plane_profile(int dir, int bin_level, double* out, int cap)
     return nbins;
 }
 
+// weights of the composite histogram: level l counts 8^(finest - l) per cell, so that the slots are in units of finest-level cell volumes
+// and together sum to cells(level 0) * 8^finest, which must stay below 2^53 (the transport between the ranks carries doubles)
+static std::vector<unsigned long long> hist_weights(int fin, long cells0, const char* who)
+{
+    if (3 * fin >= 53) throw Error(std::string(who) + ": too many levels for counts below 2^53");
+    std::vector<unsigned long long> w(fin + 1);
+    for (int l = 0; l <= fin; ++l) w[l] = 1ULL << (3 * (fin - l));
+    const double total = (double)cells0 * (double)w[0];
+    if (!(total < 9007199254740992.0)) throw Error(std::string(who) + ": cells(level 0) * 8^finest = " + std::to_string(total) + " does not stay below 2^53");
+    return w;
+}
+
+void AmrNS::histogram(int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts)
+{
+    if (n < 1) throw Error("AmrNS::histogram: no field names");
+    for (int q = 0; q < n; ++q) { lev[0]->hist_field(names[q]); hist_check_range("AmrNS::histogram", lo[q], hi[q], nbins, HIST_NBINS_MAX); }
+    const std::vector<unsigned long long> w = hist_weights((int)lev.size() - 1, lev[0]->g.domain.npts(), "AmrNS::histogram");
+    const int fin = (int)lev.size() - 1;
+    const size_t nslots = (size_t)n * (nbins + 3);
+    unsigned long long* d = hist_begin(nslots);
+    try {
+        for (int l = 0; l <= fin; ++l) {
+            NavierStokes& s = *lev[l];
+            if (l < fin) { MultiFab fc = fine_coverage(s.layout, lev[l + 1]->layout, s.g, lev[l + 1]->ratio); s.hist_add_names(n, names, &fc, lo, hi, nbins, w[l], d); }
+            else s.hist_add_names(n, names, nullptr, lo, hi, nbins, w[l], d);
+        }
+    } catch (...) { Context::get().sync(); Context::get().free(d); throw; }
+    hist_end(d, nslots, counts);
+}
+
+void AmrNS::histogram2(const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts)
+{
+    lev[0]->hist_field(namex); lev[0]->hist_field(namey);
+    for (int a = 0; a < 2; ++a) hist_check_range("AmrNS::histogram2", lo[a], hi[a], nbins[a], HIST2_SLOTS_MAX);
+    if ((long)nbins[0] * nbins[1] > HIST2_SLOTS_MAX)
+        throw Error("AmrNS::histogram2: nbins = " + std::to_string(nbins[0]) + " x " + std::to_string(nbins[1]) + " exceeds " + std::to_string(HIST2_SLOTS_MAX) + " slots");
+    const std::vector<unsigned long long> w = hist_weights((int)lev.size() - 1, lev[0]->g.domain.npts(), "AmrNS::histogram2");
+    const int fin = (int)lev.size() - 1;
+    const size_t nslots = (size_t)nbins[0] * nbins[1] + 1;
+    unsigned long long* d = hist_begin(nslots);
+    try {
+        for (int l = 0; l <= fin; ++l) {
+            NavierStokes& s = *lev[l];
+            if (l < fin) { MultiFab fc = fine_coverage(s.layout, lev[l + 1]->layout, s.g, lev[l + 1]->ratio); s.hist_add2_names(namex, namey, &fc, lo, hi, nbins, w[l], d); }
+            else s.hist_add2_names(namex, namey, nullptr, lo, hi, nbins, w[l], d);
+        }
+    } catch (...) { Context::get().sync(); Context::get().free(d); throw; }
+    hist_end(d, nslots, counts);
+}
+
 // Amr::timeStep
 // Amr::timeStep's regrid block (upstream AMReX_Amr.cpp): at the start of a step of level l every level i = l .. min(finest, max_level - 1)
 // whose own step count since the last rebuild has reached regrid_int rebuilds the levels above it

@@ -1235,6 +1235,77 @@ int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, f
     IAMRX_CATCH
 }
 
+// ---- histograms (k_hist.hip)
+static std::vector<int> hist_comps(const char* who, iamrx_mf mf, int comp, int ncomp)
+{
+    if (!mf) throw Error(std::string(who) + ": null array");
+    if (ncomp < 1 || comp < 0 || comp + ncomp > mf->mf.ncomp)
+        throw Error(std::string(who) + ": components " + std::to_string(comp) + " .. " + std::to_string(comp + ncomp - 1) + " outside the array's " + std::to_string(mf->mf.ncomp));
+    std::vector<int> c(ncomp);
+    for (int q = 0; q < ncomp; ++q) c[q] = comp + q;
+    return c;
+}
+static std::vector<std::string> hist_names(const char* who, int nnames, const char* const* names)
+{
+    if (nnames < 1 || !names) throw Error(std::string(who) + ": no field names");
+    std::vector<std::string> v;
+    for (int q = 0; q < nnames; ++q) { if (!names[q]) throw Error(std::string(who) + ": null name"); v.emplace_back(names[q]); }
+    return v;
+}
+int iamrx_mf_histogram(iamrx_mf mf, int comp, int ncomp, iamrx_mf cov, const double* lo, const double* hi, int nbins, long long weight, long long* counts)
+{
+    IAMRX_TRY
+    const std::vector<int> c = hist_comps("iamrx_mf_histogram", mf, comp, ncomp);
+    if (!lo || !hi || !counts) throw Error("iamrx_mf_histogram: null argument");
+    if (weight < 1) throw Error("iamrx_mf_histogram: weight = " + std::to_string(weight) + " must be >= 1");
+    for (int q = 0; q < ncomp; ++q) hist_check_range("iamrx_mf_histogram", lo[q], hi[q], nbins, HIST_NBINS_MAX);
+    const size_t nslots = (size_t)ncomp * (nbins + 3);
+    unsigned long long* d = hist_begin(nslots);
+    try { hist_add(mf->mf, ncomp, c.data(), cov ? &cov->mf : nullptr, lo, hi, nbins, (unsigned long long)weight, d); }
+    catch (...) { Context::get().sync(); Context::get().free(d); throw; }
+    hist_end(d, nslots, counts);
+    IAMRX_CATCH
+}
+int iamrx_mf_histogram2(iamrx_mf mf, int compx, int compy, iamrx_mf cov, const double lo[2], const double hi[2], const int nbins[2], long long weight, long long* counts)
+{
+    IAMRX_TRY
+    if (!mf || !lo || !hi || !nbins || !counts) throw Error("iamrx_mf_histogram2: null argument");
+    if (weight < 1) throw Error("iamrx_mf_histogram2: weight = " + std::to_string(weight) + " must be >= 1");
+    for (int a = 0; a < 2; ++a) hist_check_range("iamrx_mf_histogram2", lo[a], hi[a], nbins[a], HIST2_SLOTS_MAX);
+    if ((long)nbins[0] * nbins[1] > HIST2_SLOTS_MAX)
+        throw Error("iamrx_mf_histogram2: nbins = " + std::to_string(nbins[0]) + " x " + std::to_string(nbins[1]) + " exceeds " + std::to_string(HIST2_SLOTS_MAX) + " slots");
+    const size_t nslots = (size_t)nbins[0] * nbins[1] + 1;
+    unsigned long long* d = hist_begin(nslots);
+    try { hist_add2(mf->mf, compx, mf->mf, compy, cov ? &cov->mf : nullptr, lo, hi, nbins, (unsigned long long)weight, d); }
+    catch (...) { Context::get().sync(); Context::get().free(d); throw; }
+    hist_end(d, nslots, counts);
+    IAMRX_CATCH
+}
+int iamrx_ns_histogram(iamrx_ns ns, int nnames, const char* const* names, const double* lo, const double* hi, int nbins, long long* counts)
+{
+    IAMRX_TRY
+    const std::vector<std::string> v = hist_names("iamrx_ns_histogram", nnames, names);
+    if (!lo || !hi || !counts) throw Error("iamrx_ns_histogram: null argument");
+    ns->ns->histogram(nnames, v.data(), lo, hi, nbins, counts);
+    IAMRX_CATCH
+}
+int iamrx_ns_histogram2(iamrx_ns ns, const char* namex, const char* namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts)
+{
+    IAMRX_TRY
+    if (!namex || !namey || !lo || !hi || !nbins || !counts) throw Error("iamrx_ns_histogram2: null argument");
+    ns->ns->histogram2(namex, namey, lo, hi, nbins, counts);
+    IAMRX_CATCH
+}
+int iamrx_hist_bench(iamrx_mf mf, int comp, int ncomp, iamrx_mf cov, const double* lo, const double* hi, int nbins, int nby, int reps, float* ms)
+{
+    IAMRX_TRY
+    const std::vector<int> c = hist_comps("iamrx_hist_bench", mf, comp, ncomp);
+    if (!lo || !hi || !ms || reps < 1) throw Error("iamrx_hist_bench: null argument or reps < 1");
+    if (nby != 0 && ncomp != 2) throw Error("iamrx_hist_bench: the joint form (nby > 0) takes two components");
+    hist_bench(mf->mf, ncomp, c.data(), cov ? &cov->mf : nullptr, lo, hi, nbins, nby, reps, ms);
+    IAMRX_CATCH
+}
+
 int iamrx_ns_set_data(iamrx_ns ns, int which, iamrx_mf src)
 {
     IAMRX_TRY
@@ -1673,6 +1744,21 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
     IAMRX_CATCH
 }
 int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY a->amr->level(0).spectrum(nbins_cap, out, count, nbins); IAMRX_CATCH }
+int iamrx_amr_histogram(iamrx_amr a, int nnames, const char* const* names, const double* lo, const double* hi, int nbins, long long* counts)
+{
+    IAMRX_TRY
+    const std::vector<std::string> v = hist_names("iamrx_amr_histogram", nnames, names);
+    if (!lo || !hi || !counts) throw Error("iamrx_amr_histogram: null argument");
+    a->amr->histogram(nnames, v.data(), lo, hi, nbins, counts);
+    IAMRX_CATCH
+}
+int iamrx_amr_histogram2(iamrx_amr a, const char* namex, const char* namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts)
+{
+    IAMRX_TRY
+    if (!namex || !namey || !lo || !hi || !nbins || !counts) throw Error("iamrx_amr_histogram2: null argument");
+    a->amr->histogram2(namex, namey, lo, hi, nbins, counts);
+    IAMRX_CATCH
+}
 int iamrx_amr_last_sum(iamrx_amr a, int* step, double* time, double sums[3])
 {
     IAMRX_TRY

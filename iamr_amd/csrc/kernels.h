@@ -76,6 +76,27 @@ void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* c
 // between them; ms[5 * r + p] = milliseconds of pass p in repeat r
 void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, float* ms);
 
+// ---- k_hist.hip: histograms of cell-centred components (integer counts, exact) ----------------
+// The binning rule per column (lo < hi finite, inv = nbins / (hi - lo) in double): NaN -> slot nan, v < lo -> below, v > hi -> above,
+// otherwise bin min((int)((v - lo) * inv), nbins - 1).  Slots of a column: the nbins bins, then below, above, nan.
+constexpr int HIST_NBINS_MAX = 4096;        // bins of a column
+constexpr int HIST2_SLOTS_MAX = 16384;      // nbx * nby of a joint histogram
+void hist_check_range(const char* who, double lo, double hi, int nbins, int nbins_max);        // throws on what the rule excludes
+// zeroed device slots; hist_add / hist_add2 add the cells of this rank's boxes of one level to them (cov: cells with cov != 0 are skipped,
+// null: none; ghost cells are never read), every counted cell `weight`; hist_end brings them to the host, sums them over the ranks (as
+// doubles: every slot and their total must stay below 2^53), frees them.  A level every rank holds in full is counted once.
+unsigned long long* hist_begin(size_t nslots);
+// d_counts[q * (nbins + 3) + s] += ... for the columns q = 0 .. ncol - 1 = components comps[q] of S
+void hist_add(const MultiFab& S, int ncol, const int* comps, const MultiFab* cov, const double* lo, const double* hi, int nbins,
+              unsigned long long weight, unsigned long long* d_counts);
+// joint: d_counts[bx * nby + by] += ..., d_counts[nbx * nby] (`outside`) takes a cell that is NaN or out of range on either axis
+void hist_add2(const MultiFab& X, int compx, const MultiFab& Y, int compy, const MultiFab* cov, const double lo[2], const double hi[2],
+               const int nbins[2], unsigned long long weight, unsigned long long* d_counts);
+void hist_end(unsigned long long* d_counts, size_t nslots, long long* out);
+// measurement aid: ms[r] = the launches of one hist_add (nby = 0) or hist_add2 (ncol = 2, nby > 0) between two events, nothing read back
+void hist_bench(const MultiFab& S, int ncol, const int* comps, const MultiFab* cov, const double* lo, const double* hi, int nbins, int nby,
+                int reps, float* ms);
+
 struct DomainBC;
 // ---- k_bc.hip -----------------------------------------------------------------------------
 // physical-BC fill of cell-centred ghost cells outside the domain; extdir_lo/hi[n*3+d] constant ext_dir values

@@ -339,6 +339,76 @@ int NavierStokes::plane_profile(int dir, double* out, int cap)
     return nbins;
 }
 
+// ---- histograms of named fields (k_hist.hip)
+int NavierStokes::hist_field(const std::string& name) const
+{
+    if (name == "x_velocity") return Xvel;
+    if (name == "y_velocity") return Yvel;
+    if (name == "z_velocity") return Zvel;
+    if (name == "density") return Density;
+    if (name == "tracer") return Tracer;
+    if (name == "tracer2" && Tracer2 >= 0) return Tracer2;
+    if (name == "temp" && Temp >= 0) return Temp;
+    if (name == "energy" || name == "mag_vort" || name == "avg_pressure") return -1;
+    throw Error("NavierStokes::histogram: unknown field '" + name + "' (x_velocity, y_velocity, z_velocity, density, tracer" +
+                (Tracer2 >= 0 ? ", tracer2" : "") + (Temp >= 0 ? ", temp" : "") + ", energy, mag_vort, avg_pressure)");
+}
+
+void NavierStokes::hist_add_names(int n, const std::string* names, const MultiFab* cov, const double* lo, const double* hi, int nbins,
+                                  unsigned long long weight, unsigned long long* d_counts)
+{
+    std::vector<int> comp(n);
+    for (int q = 0; q < n; ++q) { comp[q] = hist_field(names[q]); hist_check_range("NavierStokes::histogram", lo[q], hi[q], nbins, HIST_NBINS_MAX); }
+    // consecutive state names share one pass over the state; a derived quantity is formed into a scratch array and takes a pass of its own
+    for (int q = 0; q < n;) {
+        unsigned long long* out = d_counts + (size_t)q * (nbins + 3);
+        if (comp[q] >= 0) {
+            int m = 1;
+            while (q + m < n && comp[q + m] >= 0) ++m;
+            hist_add(S[inew], m, comp.data() + q, cov, lo + q, hi + q, nbins, weight, out);
+            q += m;
+        } else {
+            MultiFab t(layout, cell_type(), 1, 0);
+            derive(names[q], t, 0);
+            const int zero = 0;
+            hist_add(t, 1, &zero, cov, lo + q, hi + q, nbins, weight, out);
+            ++q;
+        }
+    }
+}
+
+void NavierStokes::hist_add2_names(const std::string& namex, const std::string& namey, const MultiFab* cov, const double lo[2], const double hi[2],
+                                   const int nbins[2], unsigned long long weight, unsigned long long* d_counts)
+{
+    const int cx = hist_field(namex), cy = hist_field(namey);
+    MultiFab tx, ty;
+    if (cx < 0) { tx.define(layout, cell_type(), 1, 0); derive(namex, tx, 0); }
+    if (cy < 0) { ty.define(layout, cell_type(), 1, 0); derive(namey, ty, 0); }
+    hist_add2(cx < 0 ? tx : S[inew], std::max(cx, 0), cy < 0 ? ty : S[inew], std::max(cy, 0), cov, lo, hi, nbins, weight, d_counts);
+}
+
+void NavierStokes::histogram(int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts)
+{
+    if (n < 1) throw Error("NavierStokes::histogram: no field names");
+    for (int q = 0; q < n; ++q) { hist_field(names[q]); hist_check_range("NavierStokes::histogram", lo[q], hi[q], nbins, HIST_NBINS_MAX); }
+    const size_t nslots = (size_t)n * (nbins + 3);
+    unsigned long long* d = hist_begin(nslots);
+    try { hist_add_names(n, names, nullptr, lo, hi, nbins, 1ULL, d); } catch (...) { Context::get().sync(); Context::get().free(d); throw; }
+    hist_end(d, nslots, counts);
+}
+
+void NavierStokes::histogram2(const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts)
+{
+    hist_field(namex); hist_field(namey);
+    for (int a = 0; a < 2; ++a) hist_check_range("NavierStokes::histogram2", lo[a], hi[a], nbins[a], HIST2_SLOTS_MAX);
+    if ((long)nbins[0] * nbins[1] > HIST2_SLOTS_MAX)
+        throw Error("NavierStokes::histogram2: nbins = " + std::to_string(nbins[0]) + " x " + std::to_string(nbins[1]) + " exceeds " + std::to_string(HIST2_SLOTS_MAX) + " slots");
+    const size_t nslots = (size_t)nbins[0] * nbins[1] + 1;
+    unsigned long long* d = hist_begin(nslots);
+    try { hist_add2_names(namex, namey, nullptr, lo, hi, nbins, 1ULL, d); } catch (...) { Context::get().sync(); Context::get().free(d); throw; }
+    hist_end(d, nslots, counts);
+}
+
 // the common part of the three C entries: *nbins first, then the capacity
 void spectrum_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int cap, double* out, long* count, int* nbins)
 {

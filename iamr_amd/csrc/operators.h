@@ -319,6 +319,20 @@ public:
     // columns, count[s] (or null) the modes of shell s.  *nbins is set before the capacity is checked.  Collective; every rank receives the
     // result.
     void spectrum(int cap, double* out, long* count, int* nbins);
+    // histograms of named fields of the new-time data (k_hist.hip; the binning rule: kernels.h).  A name is a state component by its
+    // plotfile name (x_velocity, y_velocity, z_velocity, density, tracer, and tracer2 / temp when the run has them) or one of the
+    // single-component derived quantities energy, mag_vort, avg_pressure, formed by derive() into a scratch array that returns to the
+    // arena; anything else is an error that lists the known names.  hist_field: the state component of a name, -1 for a derived one.
+    // hist_add_names / hist_add2_names: this level's cells where cov (null: none) is zero, each with `weight`, added to device slots of
+    // hist_begin (the hierarchy's building block).  histogram: counts[q * (nbins + 3) + s], s < nbins the bins, then below, above, nan;
+    // histogram2: counts[bx * nby + by], then `outside`.  Collective; every rank receives the result.
+    int hist_field(const std::string& name) const;
+    void hist_add_names(int n, const std::string* names, const MultiFab* cov, const double* lo, const double* hi, int nbins,
+                        unsigned long long weight, unsigned long long* d_counts);
+    void hist_add2_names(const std::string& namex, const std::string& namey, const MultiFab* cov, const double lo[2], const double hi[2],
+                         const int nbins[2], unsigned long long weight, unsigned long long* d_counts);
+    void histogram(int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts);
+    void histogram2(const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts);
     double time = 0.0, dt = 0.0;
     int nstep = 0;
     MGStats st_mac, st_nodal, st_visc, st_scal;

@@ -19,11 +19,15 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   keys for the plane-averaged profiles of iamr_amd/profile.py, carried under "profile" of the parsed problem, not in its params,
   ns.spectrum_interval (-1: off) / ns.spectrum_file ("spec"): this library's own keys for the shell-summed spectra of level 0
   (iamr_amd/spectrum.py), carried under "spectrum"; an interval > 0 needs a fully periodic three-dimensional domain whose extents are
-  powers of two in 4 .. 1024
+  powers of two in 4 .. 1024,
+  ns.pdf_interval (-1: off) / ns.pdf_vars (field names, required with an interval > 0) / ns.pdf_nbins (64) / ns.pdf_range (two numbers per
+  name; absent: each field's minimum and maximum at each output) / ns.pdf_file ("pdf"): this library's own keys for the histograms and
+  PDFs of iamr_amd/pdf.py, carried under "pdf"
 (reference: Source/NavierStokesBase.cpp:431-557, Source/NavierStokes.cpp:250-310, Source/MacProj.cpp:62-75,
 Source/Projection.cpp:49-65, Source/Diffusion.cpp:98-118, Source/prob/prob_init.cpp:8-60, Source/main.cpp:60-145).
 Keys that select features this library does not have (EB, refinement ratio 4 ...) raise; keys that only
 concern I/O or verbosity are ignored and listed in `Inputs.ignored`.  Host-only code: no GPU needed to parse."""
+import math
 import os
 import re
 
@@ -525,7 +529,28 @@ class Inputs:
                 if not extent_ok(n[d]):
                     raise ValueError(f"inputs: ns.spectrum_interval > 0 needs extents that are powers of two in 4 .. 1024, amr.n_cell has "
                                      f"n_{'xyz'[d]} = {n[d]}")
-        out = dict(profile=profile, spectrum=spectrum, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
+        # histograms / PDFs (this library's own keys): every pdf_interval-th level-0 step and once for the initial data, of the fields named
+        # in pdf_vars; pdf_range: two numbers per name, absent: each field's minimum and maximum at each output
+        pdf = dict(interval=self.integer("ns.pdf_interval", -1), vars=[w for v in (self._get("ns.pdf_vars") if self.has("ns.pdf_vars") else []) for w in v.split()],
+                   nbins=self.integer("ns.pdf_nbins", 64), range=None, file=self.string("ns.pdf_file", "pdf"))
+        if pdf["interval"] > 0 and not pdf["vars"]:
+            raise ValueError("inputs: ns.pdf_interval > 0 needs the names of the fields in ns.pdf_vars")
+        from .pdf import known_names, NBINS_MAX
+        known = known_names(bool(p["do_trac2"]), bool(p["do_temp"]))
+        for v in pdf["vars"]:
+            if v not in known:
+                raise ValueError(f"inputs: ns.pdf_vars names '{v}', this run knows {' '.join(known)}")
+        if not 1 <= pdf["nbins"] <= NBINS_MAX:
+            raise ValueError(f"inputs: ns.pdf_nbins = {pdf['nbins']} outside 1 .. {NBINS_MAX}")
+        if self.has("ns.pdf_range"):
+            r = [float(x) for x in self._get("ns.pdf_range")]
+            if len(r) != 2 * len(pdf["vars"]):
+                raise ValueError(f"inputs: ns.pdf_range holds {len(r)} numbers, two per name of ns.pdf_vars are {2 * len(pdf['vars'])}")
+            pdf["range"] = [(r[2 * q], r[2 * q + 1]) for q in range(len(pdf["vars"]))]
+            for (a, b), v in zip(pdf["range"], pdf["vars"]):
+                if not (math.isfinite(a) and math.isfinite(b) and a < b):
+                    raise ValueError(f"inputs: ns.pdf_range of {v} = {a} {b}: two finite numbers, the first smaller than the second")
+        out = dict(profile=profile, spectrum=spectrum, pdf=pdf, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
                    max_step=self.integer("max_step", -1), stop_time=self.real("stop_time", -1.0),
                    plot_int=self.integer("amr.plot_int", -1), plot_file=self.string("amr.plot_file", "plt"), plot_vars=self.name_list("amr.plot_vars", "ALL"),
                    derive_plot_vars=self.name_list("amr.derive_plot_vars", "NONE"), fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,

@@ -508,6 +508,20 @@ def mf_spectrum(geom, mf, comp=0, ncomp=1):
     return _s.mf_spectrum(geom, mf, comp, ncomp)
 
 
+def mf_histogram(mf, comp=0, ncomp=1, nbins=64, range=None, cov=None, weight=1):
+    """exact histograms of components comp .. comp + ncomp - 1 of a cell-centred MultiFab over the valid cells where cov (a cell array
+    on the same layout, or None) is zero (include/iamrx.h: iamrx_mf_histogram) -> int64 (ncomp, nbins + 3): the bins, then below,
+    above, nan.  range: one (lo, hi) pair for all columns or one per column.  Collective."""
+    from . import pdf as _p
+    return _p.mf_histogram(mf, comp, ncomp, nbins, range, cov, weight)
+
+
+def mf_histogram2(mf, compx, compy, nbins=(32, 32), range=None, cov=None, weight=1):
+    """exact joint histogram of two components (include/iamrx.h: iamrx_mf_histogram2) -> (int64 (nbx, nby), outside)"""
+    from . import pdf as _p
+    return _p.mf_histogram2(mf, compx, compy, nbins, range, cov, weight)
+
+
 def abec_form(geom, coef, op, phi, rhs, out=None, rho=None, rho_comp=0, scale=1.0, bu=(1.0, 1.0, 1.0), beta=1.0, omega=1.15, lobc=(0, 0, 0), hibc=(0, 0, 0),
               maxorder=3):
     """one operation of the multigrid's finest-level kernel forms (include/iamrx.h: iamrx_abec_form)"""

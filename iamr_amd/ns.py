@@ -343,6 +343,19 @@ class NavierStokes:
         from . import spectrum as _s
         return _s.level_spectrum(lib().iamrx_ns_spectrum, self.h, self.geom)
 
+    def histogram(self, names, nbins=64, range=None):
+        """histograms and PDFs of named fields of this level (include/iamrx.h: iamrx_ns_histogram; pdf.py: the names, the binning rule)
+        -> dict with "names", "range", "edges", "counts" (int64), "below", "above", "nan", "total", "pdf", one row per name.  range: one
+        (lo, hi) pair per name, or None for each field's minimum and maximum.  Collective; the same on every rank."""
+        from . import pdf as _p
+        return _p.histogram(self, lib().iamrx_ns_histogram, names, nbins, range)
+
+    def histogram2(self, namex, namey, nbins=(32, 32), range=None):
+        """joint histogram of two named fields (include/iamrx.h: iamrx_ns_histogram2) -> dict with "xedges", "yedges", "counts"
+        (nbx, nby) int64, "outside", "total", "pdf".  Collective."""
+        from . import pdf as _p
+        return _p.histogram2(self, lib().iamrx_ns_histogram2, namex, namey, nbins, range)
+
     def profile(self, enable):
         arr = (C.c_double * 8)()
         check(lib().iamrx_ns_profile(self.h, int(enable), arr))

@@ -185,6 +185,24 @@ def take_spectrum(run, pr, step, rank, say):
         say("SPECTRUM:", path)
 
 
+def take_pdf(run, pr, step, rank, say):
+    """ns.pdf_interval > 0: every that many level-0 steps (and for the initial data, step 0) the histograms and PDFs of the fields of
+    ns.pdf_vars over the level or the hierarchy (pdf.py) go to <ns.pdf_file><step:05d>.  Collective: every rank takes part, rank 0
+    writes.  A two-dimensional file names the plane's velocities x_velocity, y_velocity (y is the slab's z); the slab is uniform across
+    its thickness, so the normalised PDF is the plane's, the counts are those of slab cells."""
+    pf = pr.get("pdf") or {}
+    if pf.get("interval", -1) <= 0 or step % pf["interval"] != 0:
+        return
+    from .pdf import write_pdf
+    names = ["z_velocity" if pr.get("slab") and v == "y_velocity" else v for v in pf["vars"]]
+    h = run.histogram(names, pf["nbins"], pf["range"])
+    h["names"] = tuple(pf["vars"])
+    if rank == 0:
+        path = f"{pf['file']}{step:05d}"
+        write_pdf(path, h, step, run.time)
+        say("PDF:", path)
+
+
 def enforce_plane(levels, pr):
     """a two-dimensional run on its y-periodic slab (inputs.Inputs.lift_2d) after every coarse time step: the state, the pressure and its
     gradient become their means across the slab, the velocity / gradient component along it zero.  Upstream's 2-D build has no third
@@ -342,7 +360,7 @@ def drive(pr, inp, lib, N, hierarchy, rank=0, world=1, observe=None):
     """a run from amr.restart or from its initial data to max_step / stop_time: a single level, or (hierarchy) an Amr hierarchy.  world > 1:
     the boxes of every level are spread over the ranks (level 0 by Layout.decompose, fixed refined grids round-robin, regridded levels
     by the library's knapsack, restarted levels as checkpoint.restart says) and every rank executes the same sequence of collective
-    operations: step, enforce_plane, sums, time average, profile, spectrum, observe, plotfile, checkpoint.  observe: see main"""
+    operations: step, enforce_plane, sums, time average, profile, spectrum, pdf, observe, plotfile, checkpoint.  observe: see main"""
     from . import checkpoint
     say = print if rank == 0 else (lambda *a, **k: None)
     plot_int, plot_root = pr.get("plot_int", -1), pr.get("plot_file", "plt")
@@ -354,6 +372,7 @@ def drive(pr, inp, lib, N, hierarchy, rank=0, world=1, observe=None):
         take_time_average(run, pr, step, dt)
         take_profile(run, pr, step, rank, say)
         take_spectrum(run, pr, step, rank, say)
+        take_pdf(run, pr, step, rank, say)
         if observe:
             observe(run, step, dt)
         if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports

@@ -619,6 +619,38 @@ int iamrx_ns_spectrum(iamrx_ns ns, int nbins_cap, double* out, long* count, int*
 /* measurement aid (tools/bench_spectrum.py): reps times the five passes of one component (pack, x, y, z transform, shell sums) with an
  * event between them; ms[5 * r + p] = milliseconds of pass p in repeat r.  Nothing is read back. */
 int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, float* ms);
+/* Histograms of cell-centred fields: the counts a probability density function is made of (this library's own diagnostic, no upstream
+ * counterpart; k_hist.hip; iamr_amd/pdf.py forms the PDFs).  The counts are integers and exact: the same bits on every call, for every
+ * way the level is cut into boxes and for every number of ranks.  The binning rule, per column:
+ *   bounds       lo < hi, both finite, hi - lo finite; 1 <= nbins <= 4096; inv = nbins / (hi - lo), formed once in double;
+ *   a value v    NaN -> the slot `nan`; v < lo -> the slot `below`; v > hi -> the slot `above`;
+ *                otherwise bin b = min((int)((v - lo) * inv), nbins - 1): a subtraction, then a multiplication (never fused), then a
+ *                truncation, so that numpy reproduces it exactly;
+ *   therefore    v == hi lies in the last bin; a value on an interior edge lies in the upper bin; -0.0 with lo = 0 lies in bin 0;
+ *                -inf / +inf go to below / above;
+ *   slots        counts[q * (nbins + 3) + s] (64-bit integers) for column q: s < nbins the bins, then below, above, nan;
+ *   cells        the valid cells of the boxes; ghost cells are never read; a cell with cov != 0 (cov: a cell-centred array on the same
+ *                layout, may be NULL) is skipped, not multiplied by zero: what it holds reaches no slot; every counted cell adds the
+ *                integer `weight` (>= 1; 1 for a single level).
+ * iamrx_mf_histogram: columns q < ncomp = components comp + q of a caller-owned cell-centred array, all with nbins bins, lo[ncomp], hi[ncomp].
+ * iamrx_mf_histogram2: the joint histogram of components compx and compy, the same rule per axis with lo[2], hi[2], nbins[2] and
+ * nbins[0] * nbins[1] <= 16384: counts[bx * nby + by], followed by ONE slot `outside` for a cell that is NaN or out of range on either axis
+ * (nbx * nby + 1 slots).
+ * iamrx_ns_histogram / iamrx_ns_histogram2: fields of a level by name, weight 1, nothing masked.  The names: the state components by
+ * their plotfile names x_velocity, y_velocity, z_velocity, density, tracer (tracer2 / temp when the run has them) and the single-component
+ * derived quantities energy, mag_vort, avg_pressure (formed as iamrx_ns_derive forms them, into a scratch array that returns to the
+ * library's arena); new-time data.
+ * All of them are collective on several ranks: every rank counts its own boxes, the slots are summed through the communicator (which
+ * carries doubles: integers below 2^53 are summed exactly; a slot or a total that reaches 2^53 is an error) and every rank receives the
+ * result.  Error: hi <= lo, a bound that is not finite, nbins outside its range, an unknown name (the message lists the known ones), a
+ * coverage array on another layout, components outside the array. */
+int iamrx_mf_histogram(iamrx_mf mf, int comp, int ncomp, iamrx_mf cov /* may be NULL */, const double* lo, const double* hi, int nbins, long long weight, long long* counts);
+int iamrx_mf_histogram2(iamrx_mf mf, int compx, int compy, iamrx_mf cov /* may be NULL */, const double lo[2], const double hi[2], const int nbins[2], long long weight, long long* counts);
+int iamrx_ns_histogram(iamrx_ns ns, int nnames, const char* const* names, const double* lo, const double* hi, int nbins, long long* counts);
+int iamrx_ns_histogram2(iamrx_ns ns, const char* namex, const char* namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts);
+/* measurement aid (tools/bench_hist.py): reps times the launches of one iamrx_mf_histogram (nby = 0) or iamrx_mf_histogram2 (ncomp = 2,
+ * nbins x nby bins) between two events; ms[r] = milliseconds of repeat r.  Nothing is read back. */
+int iamrx_hist_bench(iamrx_mf mf, int comp, int ncomp, iamrx_mf cov /* may be NULL */, const double* lo, const double* hi, int nbins, int nby, int reps, float* ms);
 
 /* overwrite state (0,1), pressure (2,3) or grad p (4,5) with src (same layout and ngrow; ncomp at most the array's: the leading
  * components are set): the role of NavierStokes::initData for caller-supplied initial data (Source/NavierStokes.cpp:318-420).
@@ -807,6 +839,12 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
 /* The spectra of iamrx_ns_spectrum on LEVEL 0 of the hierarchy: after avgDown its covered cells hold the average of the finer data (the
  * role of finestLevel = 0 in derivespect-inputs).  Spectra on finer levels and composite spectra are not built. */
 int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins);
+/* Composite histograms of the hierarchy (the rule, the names and the layout of counts: iamrx_mf_histogram / iamrx_ns_histogram above).  Level l
+ * counts the cells that level l + 1 does not cover, each with the weight 8^(finest - l): the slots are in units of finest-level cell
+ * volumes, and all slots of a column together sum to cells(level 0) * 8^finest.  Covered cells are skipped, not multiplied by zero.
+ * Error: as above, and a hierarchy for which that total does not stay below 2^53. */
+int iamrx_amr_histogram(iamrx_amr a, int nnames, const char* const* names, const double* lo, const double* hi, int nbins, long long* counts);
+int iamrx_amr_histogram2(iamrx_amr a, const char* namex, const char* namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts);
 /* the pieces of NavierStokesBase::post_timestep(lev) one by one (lev < finest), for a caller that drives the loop itself:
  * NavierStokes::reflux, avgDown, mac_sync (= MacProj::mac_sync_solve + mac_sync_compute + the state update and SyncInterp),
  * NavierStokesBase::level_sync (= SyncInterp + Projection::MLsyncProject) */
