@@ -193,6 +193,16 @@ class Amr:
         check(lib().iamrx_amr_sum_integrated(self.h, v))
         return tuple(v)
 
+    def integrate(self, names):
+        """composite volume-weighted sums of named fields (include/iamrx.h: iamrx_amr_integrate; the names of histogram): every level
+        over the cells the next finer one does not cover -> float64 array, one per name.  Collective; the same on every rank."""
+        import numpy as np
+        names = [names] if isinstance(names, str) else list(names)
+        out = np.zeros(max(len(names), 1))
+        check(lib().iamrx_amr_integrate(self.h, len(names), (C.c_char_p * max(len(names), 1))(*[nm.encode() for nm in names]),
+                                        out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[:len(names)]
+
     def last_sum(self):
         """(level-0 step, time, (mass, tracer, kinetic energy)) the hierarchy last computed by itself (ns.sum_interval > 0: after post_init and
         in level 0's post_timestep), or None"""

@@ -35,6 +35,9 @@ public:
     // sum_interval-th level-0 step) call it and leave what they found in last_sum (last_sum_step: the level-0 step count then, -1: never)
     void sum_integrated_quantities(double out[3]);
     double last_sum[3] = {0.0, 0.0, 0.0}, last_sum_time = 0.0;
+    // the same for named fields (NavierStokes::integrate; the names: NavierStokes::hist_field): out[q] = composite volume-weighted sum of
+    // field names[q], every level with its own cell volume over the cells the next finer one does not cover, coarsest first
+    void integrate(int n, const std::string* names, double* out);
     // plane-averaged profile of the composite state along dir (k_profile.hip): the PROFILE_NQ volume-weighted means of every slab of the
     // index space of level bin_level (0 .. finest), over the cells no finer level covers; out[q * nbins + b].  Returns nbins.
     int plane_profile(int dir, int bin_level, double* out, int cap);

@@ -1283,6 +1283,20 @@ void AmrNS::sum_integrated_quantities(double out[3])
     }
 }
 
+void AmrNS::integrate(int n, const std::string* names, double* out)
+{
+    if (n < 1 || !names || !out) throw Error("AmrNS::integrate: no field names");
+    for (int q = 0; q < n; ++q) { lev[0]->hist_field(names[q]); out[q] = 0.0; }
+    const int fin = (int)lev.size() - 1;
+    std::vector<double> v(n);
+    for (int l = 0; l <= fin; ++l) {
+        NavierStokes& s = *lev[l];
+        if (l < fin) { MultiFab fc = fine_coverage(s.layout, lev[l + 1]->layout, s.g, lev[l + 1]->ratio); s.integrate(n, names, &fc, v.data()); }
+        else s.integrate(n, names, nullptr, v.data());
+        for (int q = 0; q < n; ++q) out[q] += v[q];
+    }
+}
+
 int AmrNS::plane_profile(int dir, int bin_level, double* out, int cap)
 {
     const int fin = (int)lev.size() - 1;

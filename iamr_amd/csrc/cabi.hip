@@ -588,6 +588,27 @@ int iamrx_mlmg_mac_solve_cf(const iamrx_geom* g, iamrx_mf ux, iamrx_mf uy, iamrx
     IAMRX_CATCH
 }
 
+int iamrx_derive_velgrad(const iamrx_geom* g, iamrx_mf out, int ocomp, int nq, const int* which, iamrx_mf vel, int vcomp, double mu, int path)
+{
+    IAMRX_TRY
+    if (!g || !out || !vel || !which) throw Error("iamrx_derive_velgrad: null argument");
+    derive_velgrad(to_geom(g), out->mf, ocomp, nq, which, vel->mf, vcomp, mu, path);
+    IAMRX_CATCH
+}
+int iamrx_velgrad_path(iamrx_mf vel, int path, int* form)
+{
+    IAMRX_TRY
+    if (!vel || !form) throw Error("iamrx_velgrad_path: null argument");
+    *form = velgrad_path(*vel->mf.layout, path);
+    IAMRX_CATCH
+}
+int iamrx_velgrad_bench(const iamrx_geom* g, iamrx_mf out, int nq, const int* which, iamrx_mf vel, int vcomp, double mu, int path, int split, int reps, float* ms)
+{
+    IAMRX_TRY
+    if (!g || !out || !vel || !which || !ms || reps < 1) throw Error("iamrx_velgrad_bench: null argument or reps < 1");
+    velgrad_bench(to_geom(g), out->mf, nq, which, vel->mf, vcomp, mu, path, split != 0, reps, ms);
+    IAMRX_CATCH
+}
 int iamrx_derive_mag_vort(const iamrx_geom* g, iamrx_mf out, int ocomp, iamrx_mf vel, int vcomp)
 {
     IAMRX_TRY derive_mag_vort(to_geom(g), out->mf, ocomp, vel->mf, vcomp); IAMRX_CATCH
@@ -1195,6 +1216,33 @@ int iamrx_ns_derive(iamrx_ns ns, const char* name, iamrx_mf out, int ocomp)
     IAMRX_CATCH
 }
 
+static std::vector<std::string> hist_names(const char* who, int nnames, const char* const* names);
+int iamrx_ns_derive_fields(iamrx_ns ns, int nnames, const char* const* names, iamrx_mf out, int ocomp)
+{
+    IAMRX_TRY
+    if (!ns || !out) throw Error("iamrx_ns_derive_fields: null argument");
+    NavierStokes& n = *ns->ns;
+    const std::vector<std::string> v = hist_names("iamrx_ns_derive_fields", nnames, names);
+    if (ocomp < 0 || ocomp + nnames > out->mf.ncomp) throw Error("iamrx_ns_derive_fields: out has too few components for " + std::to_string(nnames) + " fields");
+    if (out->mf.layout->id == n.lay()->id) n.derive_fields(nnames, v.data(), out->mf, ocomp);
+    else {
+        IAMRX_ASSERT(out->mf.layout->id == n.user_layout->id && out->mf.type.cell());
+        MultiFab t(n.lay(), cell_type(), nnames, 0), u(n.user_layout, cell_type(), nnames, 0);
+        n.derive_fields(nnames, v.data(), t, 0);
+        relayout_copy(u, t, nnames);
+        MultiFab::Copy(out->mf, u, 0, ocomp, nnames, 0);
+    }
+    IAMRX_CATCH
+}
+int iamrx_ns_integrate(iamrx_ns ns, int nnames, const char* const* names, double* out)
+{
+    IAMRX_TRY
+    if (!ns || !out) throw Error("iamrx_ns_integrate: null argument");
+    const std::vector<std::string> v = hist_names("iamrx_ns_integrate", nnames, names);
+    ns->ns->integrate(nnames, v.data(), nullptr, out);
+    IAMRX_CATCH
+}
+
 int iamrx_ns_time_average(iamrx_ns ns, double dt_level, int level0_steps) { IAMRX_TRY ns->ns->time_average(dt_level, level0_steps); IAMRX_CATCH }
 int iamrx_ns_average_state(iamrx_ns ns, int set, double v[3])
 {
@@ -1736,6 +1784,14 @@ int iamrx_amr_coarse_step(iamrx_amr a, double* dt0)
     IAMRX_CATCH
 }
 int iamrx_amr_sum_integrated(iamrx_amr a, double sums[3]) { IAMRX_TRY a->amr->sum_integrated_quantities(sums); IAMRX_CATCH }
+int iamrx_amr_integrate(iamrx_amr a, int nnames, const char* const* names, double* out)
+{
+    IAMRX_TRY
+    if (!a || !out) throw Error("iamrx_amr_integrate: null argument");
+    const std::vector<std::string> v = hist_names("iamrx_amr_integrate", nnames, names);
+    a->amr->integrate(nnames, v.data(), out);
+    IAMRX_CATCH
+}
 int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, double* out, int* nbins)
 {
     IAMRX_TRY

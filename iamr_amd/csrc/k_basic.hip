@@ -502,6 +502,57 @@ void reduce_sum_integrated(const MultiFab& S, int rho_comp, int trac_comp, const
     for (int q = 0; q < 3; ++q) out[q] = ctx.h_scratch[q];
 }
 
+// the same for named fields (NavierStokes::integrate): the sums of up to SUM_COMPS_MAX components of one array over the cells where cov
+// is zero (skipped, not multiplied by zero), in the tiling and the order of k_sum_integrated.  partials[q * np + block]
+struct SumComps { int n; int comp[SUM_COMPS_MAX]; };
+template <bool MASK>
+__global__ void __launch_bounds__(256) k_sum_comps(Tiling t, const BoxD* __restrict__ boxes, const FabD* __restrict__ at, const FabD* __restrict__ cov, SumComps c,
+                                                   double* __restrict__ partials, int np)
+{
+    const int fab = tile_fab(t);
+    const BoxD b = boxes[fab];
+    int i, j, k0, k1;
+    double s[SUM_COMPS_MAX];
+#pragma unroll
+    for (int q = 0; q < SUM_COMPS_MAX; ++q) s[q] = 0.0;
+    if (tile_ijk(t, b, i, j, k0, k1)) {
+        const FabD a = at[fab];
+        for (int k = k0; k <= k1; ++k) {
+            if (MASK && cov[fab](i, j, k) != 0.0) continue;
+#pragma unroll
+            for (int q = 0; q < SUM_COMPS_MAX; ++q) if (q < c.n) s[q] += a(i, j, k, c.comp[q]);
+        }
+    }
+    const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+#pragma unroll
+    for (int q = 0; q < SUM_COMPS_MAX; ++q)
+        if (q < c.n) {          // (uniform: every thread of the workgroup takes part in the reduction)
+            const double v = block_reduce<0>(s[q]);
+            if (threadIdx.x == 0) partials[(size_t)q * np + slot] = v;
+        }
+}
+
+void reduce_sum_comps(const MultiFab& mf, int n, const int* comps, const MultiFab* cov, double* out)
+{
+    IAMRX_ASSERT(mf.type.cell() && (!cov || (cov->type.cell() && cov->layout->id == mf.layout->id)));
+    for (int q = 0; q < n; ++q) { IAMRX_ASSERT(comps[q] >= 0 && comps[q] < mf.ncomp); out[q] = 0.0; }
+    if (mf.nlocal() == 0) return;
+    auto& ctx = Context::get();
+    Tiling t = level_tiling(*mf.layout, mf.type, 0, 8, true);
+    dim3 g = t.grid();
+    const int np = (int)(g.x * g.y);
+    for (int q0 = 0; q0 < n; q0 += SUM_COMPS_MAX) {
+        SumComps c;
+        c.n = std::min(SUM_COMPS_MAX, n - q0);
+        for (int q = 0; q < SUM_COMPS_MAX; ++q) c.comp[q] = q < c.n ? comps[q0 + q] : 0;
+        ctx.ensure_scratch((size_t)c.n * np + 16);
+        if (cov) hipLaunchKernelGGL((k_sum_comps<true>), g, Tiling::block(), 0, ctx.stream, t, mf.layout->d_boxes, mf.d_tab, cov->d_tab, c, ctx.d_scratch, np);
+        else hipLaunchKernelGGL((k_sum_comps<false>), g, Tiling::block(), 0, ctx.stream, t, mf.layout->d_boxes, mf.d_tab, (const FabD*)nullptr, c, ctx.d_scratch, np);
+        finish_to_host(0, c.n, np, false);
+        for (int q = 0; q < c.n; ++q) out[q0 + q] = ctx.h_scratch[q];
+    }
+}
+
 // ------------------------------------------------------------------ BLAS-1 style
 void mf_lincomb(MultiFab& dst, double a, const MultiFab& x, double b, const MultiFab& y, int comp, int nc, int ng)
 {

@@ -21,6 +21,10 @@ void reduce_minmax(const MultiFab& mf, int comp, int ng, double& mn, double& mx,
 double reduce_sum_unique(const MultiFab& mf, int comp, const Geometry& g, bool global = false);   // sum over owner copies
 // this rank's sums of density, tracer and kinetic energy over the valid cells where cov (may be null) is zero: one pass over the state
 void reduce_sum_integrated(const MultiFab& S, int rho_comp, int trac_comp, const MultiFab* cov, double out[3]);
+// this rank's sums of the components comps[0 .. n) of a cell-centred array over the valid cells where cov (may be null) is zero; the
+// tiling and the summation order of reduce_sum_integrated (the same call gives the same bits), SUM_COMPS_MAX components per pass
+constexpr int SUM_COMPS_MAX = 8;
+void reduce_sum_comps(const MultiFab& mf, int n, const int* comps, const MultiFab* cov, double* out);
 // nout simultaneous dot products over the valid region, owner-masked for nodal data: out[q] = <x_q, y_q>
 void reduce_dots(int nout, const MultiFab* const* x, const MultiFab* const* y, int comp, int nc, const Geometry& g, double* out, bool local = false);
 // ... with the results left on the device (no read-back): krylov.h
@@ -96,6 +100,21 @@ void hist_end(unsigned long long* d_counts, size_t nslots, long long* out);
 // measurement aid: ms[r] = the launches of one hist_add (nby = 0) or hist_add2 (ncol = 2, nby > 0) between two events, nothing read back
 void hist_bench(const MultiFab& S, int ncol, const int* comps, const MultiFab* cov, const double* lo, const double* hi, int nbins, int nby,
                 int reps, float* ms);
+
+// ---- k_velgrad.hip: derived fields of the velocity-gradient tensor ---------------------------
+// the quantity ids, in this order: diveru, vort_x, vort_y, vort_z, enstrophy, strain_rate, dissipation, q_criterion, r_invariant, helicity
+// (the definitions: k_velgrad.hip)
+constexpr int VELGRAD_NQ = 10;
+// out(ocomp + q) = quantity which[q] (q < nq <= VELGRAD_NQ) of the centred gradient of vel(vcomp .. vcomp + 2) on the valid cells; vel:
+// cell-centred, same layout, at least one FILLED ghost layer (only the face neighbours of a cell are read); mu: the dynamic viscosity of
+// "dissipation".  path 0: the marching form where the level's largest box holds a full 32 x 8 tile, else the plain form; 1 / 2 force
+// the marching / plain form (1 on a level without a full tile is an error).  The two forms give the same bits.
+void derive_velgrad(const Geometry& g, MultiFab& out, int ocomp, int nq, const int* which, const MultiFab& vel, int vcomp, double mu, int path = 0);
+int velgrad_path(const Layout& l, int path);        // the form a call takes: 1 marching, 2 plain
+// measurement aid: ms[r] = one launch of nq outputs into out(0 .. nq) (split: nq single-output launches) between two events, nothing
+// read back
+void velgrad_bench(const Geometry& g, MultiFab& out, int nq, const int* which, const MultiFab& vel, int vcomp, double mu, int path, bool split,
+                   int reps, float* ms);
 
 struct DomainBC;
 // ---- k_bc.hip -----------------------------------------------------------------------------

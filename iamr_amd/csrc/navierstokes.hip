@@ -271,9 +271,18 @@ void NavierStokes::swap_time_levels(double dt_)      // StateData::swapTimeLevel
 // FillPatch: copy the valid data, same-level + periodic ghost fill, then the physical-BC fill
 // (StateDataPhysBCFunct: FilccCell rules + the ext_dir functors of NS_bcfill.H).  On a refined level: FillPatchTwoLevels with the
 // coarse level's data interpolated in time (amr.hip); src must be the level's old or new State_Type data.
+const char* const VELGRAD_NAMES[10] = {"diveru", "vort_x", "vort_y", "vort_z", "enstrophy", "strain_rate", "dissipation", "q_criterion", "r_invariant", "helicity"};
+static const char* const VELGRAD_LIST = "diveru, vort_x, vort_y, vort_z, enstrophy, strain_rate, dissipation, q_criterion, r_invariant, helicity";
+int velgrad_id(const std::string& name)
+{
+    for (int q = 0; q < VELGRAD_NQ; ++q) if (name == VELGRAD_NAMES[q]) return q;
+    return -1;
+}
+
 void NavierStokes::derive(const std::string& name, MultiFab& out, int ocomp)
 {
     IAMRX_ASSERT(out.type.cell() && out.layout->id == layout->id && ocomp < out.ncomp);
+    if (velgrad_id(name) >= 0) { derive_fields(1, &name, out, ocomp); return; }
     auto& ctx = Context::get();
     const FabD* ot = out.d_tab;
     if (name == "energy") {                                    // derkeng, NS_derive.cpp:266-295
@@ -302,7 +311,66 @@ void NavierStokes::derive(const std::string& name, MultiFab& out, int ocomp)
     } else if (name == "total_particle_count" && particles) {
         particles->total_particle_count(level, out, ocomp);
     } else throw Error("NavierStokes::derive: unknown derived quantity '" + name + "' (energy, mag_vort, avg_pressure" + (has_average() ? ", velocity_average" : "") +
-                       (particles ? ", particle_count, total_particle_count)" : ")"));
+                       (particles ? ", particle_count, total_particle_count, " : ", ") + VELGRAD_LIST + ")");
+}
+
+void NavierStokes::derive_fields(int n, const std::string* names, MultiFab& out, int ocomp)
+{
+    if (n < 1 || !names) throw Error("NavierStokes::derive_fields: no field names");
+    IAMRX_ASSERT(out.type.cell() && out.layout->id == layout->id);
+    if (ocomp < 0 || ocomp + n > out.ncomp) throw Error("NavierStokes::derive_fields: " + std::to_string(n) + " fields from component " + std::to_string(ocomp) + " do not fit the array's " + std::to_string(out.ncomp));
+    std::vector<int> vq, vid;          // the velocity-gradient names: their places in the list and their ids
+    for (int q = 0; q < n; ++q) {
+        if (names[q] == "velocity_average") throw Error("NavierStokes::derive_fields: velocity_average has six components; ask derive() for it");
+        const int id = velgrad_id(names[q]);
+        if (id >= 0) { vq.push_back(q); vid.push_back(id); }
+    }
+    for (int q = 0; q < n; ++q) {
+        if (velgrad_id(names[q]) >= 0) continue;
+        int comp = -1;
+        try { comp = hist_field(names[q]); } catch (const Error&) { comp = -1; }          // (derive() knows names hist_field does not, and reports the unknown ones)
+        if (comp >= 0) MultiFab::Copy(out, S[inew], comp, ocomp + q, 1, 0);
+        else derive(names[q], out, ocomp + q);
+    }
+    if (vq.empty()) return;
+    const int m = (int)vq.size();
+    MultiFab vel(layout, cell_type(), 3, 1);
+    fillpatch(vel, S[inew], Xvel, 3, bc_vel);
+    if (vq.back() - vq.front() == m - 1) { derive_velgrad(g, out, ocomp + vq.front(), m, vid.data(), vel, 0, p.visc_coef, 0); return; }
+    MultiFab t(layout, cell_type(), m, 0);          // the names are scattered over the list: one launch into a scratch array, then to their places
+    derive_velgrad(g, t, 0, m, vid.data(), vel, 0, p.visc_coef, 0);
+    for (int s = 0; s < m; ++s) MultiFab::Copy(out, t, s, ocomp + vq[s], 1, 0);
+}
+
+void NavierStokes::integrate(int n, const std::string* names, const MultiFab* fine_cov, double* out)
+{
+    if (n < 1 || !names || !out) throw Error("NavierStokes::integrate: no field names");
+    std::vector<int> comp(n), sq, sc, dq;
+    std::vector<std::string> dn;
+    for (int q = 0; q < n; ++q) {
+        comp[q] = hist_field(names[q]);
+        if (comp[q] >= 0) { sq.push_back(q); sc.push_back(comp[q]); } else { dq.push_back(q); dn.push_back(names[q]); }
+    }
+    std::vector<double> v(n, 0.0);
+    if (!sq.empty()) {
+        std::vector<double> r(sq.size());
+        reduce_sum_comps(S[inew], (int)sq.size(), sc.data(), fine_cov, r.data());
+        for (size_t s = 0; s < sq.size(); ++s) v[sq[s]] = r[s];
+    }
+    if (!dq.empty()) {
+        const int m = (int)dq.size();
+        MultiFab t(layout, cell_type(), m, 0);
+        derive_fields(m, dn.data(), t, 0);
+        std::vector<int> c(m);
+        std::vector<double> r(m);
+        for (int s = 0; s < m; ++s) c[s] = s;
+        reduce_sum_comps(t, m, c.data(), fine_cov, r.data());
+        for (int s = 0; s < m; ++s) v[dq[s]] = r[s];
+    }
+    const double vol = g.dx[0] * g.dx[1] * g.dx[2];
+    for (int q = 0; q < n; ++q) out[q] = v[q] * vol;
+    auto& comm = Context::get().comm;
+    if (comm && comm->nranks > 1 && !layout->replicated) comm->allreduce(out, n, ReduceOp::Sum);
 }
 
 // NavierStokesBase::time_average (NS_average.cpp:19-69), statement by statement
@@ -350,8 +418,9 @@ int NavierStokes::hist_field(const std::string& name) const
     if (name == "tracer2" && Tracer2 >= 0) return Tracer2;
     if (name == "temp" && Temp >= 0) return Temp;
     if (name == "energy" || name == "mag_vort" || name == "avg_pressure") return -1;
+    if (velgrad_id(name) >= 0) return -2;
     throw Error("NavierStokes::histogram: unknown field '" + name + "' (x_velocity, y_velocity, z_velocity, density, tracer" +
-                (Tracer2 >= 0 ? ", tracer2" : "") + (Temp >= 0 ? ", temp" : "") + ", energy, mag_vort, avg_pressure)");
+                (Tracer2 >= 0 ? ", tracer2" : "") + (Temp >= 0 ? ", temp" : "") + ", energy, mag_vort, avg_pressure, " + VELGRAD_LIST + ")");
 }
 
 void NavierStokes::hist_add_names(int n, const std::string* names, const MultiFab* cov, const double* lo, const double* hi, int nbins,
@@ -359,13 +428,23 @@ void NavierStokes::hist_add_names(int n, const std::string* names, const MultiFa
 {
     std::vector<int> comp(n);
     for (int q = 0; q < n; ++q) { comp[q] = hist_field(names[q]); hist_check_range("NavierStokes::histogram", lo[q], hi[q], nbins, HIST_NBINS_MAX); }
-    // consecutive state names share one pass over the state; a derived quantity is formed into a scratch array and takes a pass of its own
+    // consecutive state names share one pass over the state; a derived quantity is formed into a scratch array and takes a pass of its own;
+    // consecutive velocity-gradient names are formed together (one ghost fill, one launch) and share one pass
     for (int q = 0; q < n;) {
         unsigned long long* out = d_counts + (size_t)q * (nbins + 3);
         if (comp[q] >= 0) {
             int m = 1;
             while (q + m < n && comp[q + m] >= 0) ++m;
             hist_add(S[inew], m, comp.data() + q, cov, lo + q, hi + q, nbins, weight, out);
+            q += m;
+        } else if (comp[q] == -2) {
+            int m = 1;
+            while (q + m < n && comp[q + m] == -2) ++m;
+            MultiFab t(layout, cell_type(), m, 0);
+            derive_fields(m, names + q, t, 0);
+            std::vector<int> c(m);
+            for (int s = 0; s < m; ++s) c[s] = s;
+            hist_add(t, m, c.data(), cov, lo + q, hi + q, nbins, weight, out);
             q += m;
         } else {
             MultiFab t(layout, cell_type(), 1, 0);
@@ -381,6 +460,13 @@ void NavierStokes::hist_add2_names(const std::string& namex, const std::string& 
                                    const int nbins[2], unsigned long long weight, unsigned long long* d_counts)
 {
     const int cx = hist_field(namex), cy = hist_field(namey);
+    if (cx == -2 && cy == -2) {          // two velocity-gradient names: one ghost fill, one launch
+        MultiFab t(layout, cell_type(), 2, 0);
+        const std::string nm[2] = {namex, namey};
+        derive_fields(2, nm, t, 0);
+        hist_add2(t, 0, t, 1, cov, lo, hi, nbins, weight, d_counts);
+        return;
+    }
     MultiFab tx, ty;
     if (cx < 0) { tx.define(layout, cell_type(), 1, 0); derive(namex, tx, 0); }
     if (cy < 0) { ty.define(layout, cell_type(), 1, 0); derive(namey, ty, 0); }

@@ -104,6 +104,11 @@ MGStats mac_sync_solve(const Geometry& g, FluxRegister& mr, const MultiFab& rho_
 
 // ---- regrid.hip: error estimation + grid generation
 void derive_mag_vort(const Geometry& g, MultiFab& out, int ocomp, const MultiFab& vel, int vcomp);
+// the derived fields of the velocity-gradient tensor (k_velgrad.hip; declared in kernels.h): out(ocomp + q) = quantity which[q]
+void derive_velgrad(const Geometry& g, MultiFab& out, int ocomp, int nq, const int* which, const MultiFab& vel, int vcomp, double mu, int path);
+// the names of the ten quantities in the order of their ids, and the id of a name (-1: not one of them)
+extern const char* const VELGRAD_NAMES[10];
+int velgrad_id(const std::string& name);
 void error_tag(const Geometry& g, MultiFab& tags, const MultiFab& field, int comp, int mode, double value, int level,
                const double* rb_lo, const double* rb_hi);
 // manual_tags_placement at the outflow faces (NavierStokesBase.cpp:2112-2215): mode 1 do_refine_outflow, 2 do_derefine_outflow with
@@ -293,7 +298,15 @@ public:
     // derived quantities of the plotfile (derive_lst of NS_setup.cpp:436-449): "energy" = rho |u|^2 / 2 (derkeng), "mag_vort" = |curl u|
     // (dermgvort, ghost cells by FillPatch), "avg_pressure" = mean of the 8 nodes of the cell (deravgpres); new-time data; out: cell, >= 1 comp;
     // with avg_interval > 0 also "velocity_average" (der_vel_avg, NS_derive.cpp:11-45): 6 components, mean velocity and rms fluctuation
+    // and the ten velocity-gradient names of VELGRAD_NAMES (k_velgrad.hip; "dissipation" with mu = ns.vel_visc_coef: the molecular part
+    // only, also in an LES run)
     void derive(const std::string& name, MultiFab& out, int ocomp = 0);
+    // out(ocomp + q) = field names[q]: any mix of state names (hist_field), the single-component derived names and the velocity-gradient
+    // names; ALL velocity-gradient names of the list share ONE fillpatch of the velocity and ONE derive_velgrad launch
+    void derive_fields(int n, const std::string* names, MultiFab& out, int ocomp = 0);
+    // out[q] = volume-weighted sum of field names[q] (as derive_fields forms it; state names are reduced from the state) over the cells
+    // where fine_cov (this level's layout; null: none) is zero, summed over the ranks: sum_integrated for named fields
+    void integrate(int n, const std::string* names, const MultiFab* fine_cov, double* out);
     MultiFab& get_new_data(int type) { return type == 0 ? S[inew] : (type == 1 ? P[pnew] : Gp[pnew]); }
     MultiFab& get_old_data(int type) { return type == 0 ? S[1 - inew] : (type == 1 ? P[1 - pnew] : Gp[1 - pnew]); }
     MultiFab& umac(int d) { return u_mac[d]; }
@@ -322,7 +335,9 @@ public:
     // histograms of named fields of the new-time data (k_hist.hip; the binning rule: kernels.h).  A name is a state component by its
     // plotfile name (x_velocity, y_velocity, z_velocity, density, tracer, and tracer2 / temp when the run has them) or one of the
     // single-component derived quantities energy, mag_vort, avg_pressure, formed by derive() into a scratch array that returns to the
-    // arena; anything else is an error that lists the known names.  hist_field: the state component of a name, -1 for a derived one.
+    // arena, or one of the velocity-gradient names (consecutive ones are formed by one derive_fields into one multi-component scratch
+    // array and take one pass); anything else is an error that lists the known names.  hist_field: the state component of a name, -1
+    // for a derived one, -2 for a velocity-gradient one.
     // hist_add_names / hist_add2_names: this level's cells where cov (null: none) is zero, each with `weight`, added to device slots of
     // hist_begin (the hierarchy's building block).  histogram: counts[q * (nbins + 3) + s], s < nbins the bins, then below, above, nan;
     // histogram2: counts[bx * nby + by], then `outside`.  Collective; every rank receives the result.

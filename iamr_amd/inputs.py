@@ -22,7 +22,11 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   powers of two in 4 .. 1024,
   ns.pdf_interval (-1: off) / ns.pdf_vars (field names, required with an interval > 0) / ns.pdf_nbins (64) / ns.pdf_range (two numbers per
   name; absent: each field's minimum and maximum at each output) / ns.pdf_file ("pdf"): this library's own keys for the histograms and
-  PDFs of iamr_amd/pdf.py, carried under "pdf"
+  PDFs of iamr_amd/pdf.py, carried under "pdf",
+  ns.integrate_interval (0: off) / ns.integrate_vars (field names, required with an interval > 0) / ns.integrate_file ("integ"): this
+  library's own keys for the volume integrals of named fields against time (iamr_amd/integrals.py), carried under "integrate"; the names
+  are those of ns.pdf_vars, which include the velocity-gradient fields of pdf.VELGRAD_NAMES (a two-dimensional run knows
+  pdf.VELGRAD_NAMES_2D of them; amr.derive_plot_vars may name them too)
 (reference: Source/NavierStokesBase.cpp:431-557, Source/NavierStokes.cpp:250-310, Source/MacProj.cpp:62-75,
 Source/Projection.cpp:49-65, Source/Diffusion.cpp:98-118, Source/prob/prob_init.cpp:8-60, Source/main.cpp:60-145).
 Keys that select features this library does not have (EB, refinement ratio 4 ...) raise; keys that only
@@ -550,10 +554,30 @@ class Inputs:
             for (a, b), v in zip(pdf["range"], pdf["vars"]):
                 if not (math.isfinite(a) and math.isfinite(b) and a < b):
                     raise ValueError(f"inputs: ns.pdf_range of {v} = {a} {b}: two finite numbers, the first smaller than the second")
-        out = dict(profile=profile, spectrum=spectrum, pdf=pdf, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
+        # volume integrals of named fields against time (this library's own keys): once for the initial data, then every
+        # integrate_interval-th level-0 step one row of ns.integrate_file; 0: off, nothing is launched
+        integ = dict(interval=self.integer("ns.integrate_interval", 0), vars=[w for v in (self._get("ns.integrate_vars") if self.has("ns.integrate_vars") else []) for w in v.split()],
+                     file=self.string("ns.integrate_file", "integ"))
+        if integ["interval"] < 0:
+            raise ValueError(f"inputs: ns.integrate_interval = {integ['interval']} must be >= 0; the fields ns.integrate_vars may name: {' '.join(known)}")
+        if integ["interval"] > 0 and not integ["vars"]:
+            raise ValueError(f"inputs: ns.integrate_interval > 0 needs the names of the fields in ns.integrate_vars; this run knows {' '.join(known)}")
+        for v in integ["vars"]:
+            if v not in known:
+                raise ValueError(f"inputs: ns.integrate_vars names '{v}', this run knows {' '.join(known)}")
+        dpv = self.name_list("amr.derive_plot_vars", "NONE")
+        if slab:
+            # the slab is the (x, z) plane: a name that carries a direction, or needs the third one, has no two-dimensional meaning here
+            from .pdf import VELGRAD_NAMES, VELGRAD_NAMES_2D
+            for key, vs in (("amr.derive_plot_vars", dpv if isinstance(dpv, list) else []), ("ns.pdf_vars", pdf["vars"]), ("ns.integrate_vars", integ["vars"])):
+                for v in vs:
+                    if v in VELGRAD_NAMES and v not in VELGRAD_NAMES_2D:
+                        raise NotImplementedError(f"inputs: {key} names '{v}' in a two-dimensional run: of the velocity-gradient fields a slab "
+                                                  f"knows {' '.join(VELGRAD_NAMES_2D)}")
+        out = dict(profile=profile, spectrum=spectrum, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
                    max_step=self.integer("max_step", -1), stop_time=self.real("stop_time", -1.0),
                    plot_int=self.integer("amr.plot_int", -1), plot_file=self.string("amr.plot_file", "plt"), plot_vars=self.name_list("amr.plot_vars", "ALL"),
-                   derive_plot_vars=self.name_list("amr.derive_plot_vars", "NONE"), fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,
+                   derive_plot_vars=dpv, fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,
                    check_int=self.integer("amr.check_int", -1), check_file=self.string("amr.check_file", "chk"),
                    restart=self.string("amr.restart", "") if self.has("amr.restart") else "", particles=particles)
         for k, dflt in _UNIMPLEMENTED_UNLESS.items():

@@ -579,6 +579,23 @@ def mlmg_mac_solve_cf(geom, umac, rho, rho_comp, S, mac_phi, rhs_scale, crse_phi
     return st
 
 
+def derive_velgrad(geom, out, vel, which, ocomp=0, vcomp=0, mu=0.0, path=0):
+    """derived fields of the velocity-gradient tensor (include/iamrx.h: iamrx_derive_velgrad): out(ocomp + q) = quantity which[q] -- ids or
+    names of pdf.VELGRAD_NAMES -- of the centred gradient of vel(vcomp .. vcomp + 2), vel with 1 filled ghost layer; mu: the viscosity of
+    "dissipation"; path 0: the form the layout asks for, 1 marching, 2 plain"""
+    from .pdf import VELGRAD_NAMES
+    ids = [VELGRAD_NAMES.index(w) if isinstance(w, str) else int(w) for w in ([which] if isinstance(which, (str, int)) else which)]
+    check(lib().iamrx_derive_velgrad(C.byref(geom), _h(out), int(ocomp), len(ids), (C.c_int * max(len(ids), 1))(*ids), _h(vel), int(vcomp),
+                                     C.c_double(mu), int(path)))
+
+
+def velgrad_path(vel, path=0):
+    """the form derive_velgrad takes on the layout of vel: 1 marching, 2 plain (path 1 raises where no box holds a full tile)"""
+    form = C.c_int()
+    check(lib().iamrx_velgrad_path(_h(vel), int(path), C.byref(form)))
+    return form.value
+
+
 def derive_mag_vort(geom, out, vel, ocomp=0, vcomp=0):
     """|curl u| (dermgvort, NS_derive.cpp:86-264); vel with 1 filled ghost cell"""
     check(lib().iamrx_derive_mag_vort(C.byref(geom), _h(out), ocomp, _h(vel), vcomp))

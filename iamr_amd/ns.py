@@ -279,12 +279,35 @@ class NavierStokes:
         return MultiFab(self.layout, typ, nc, ng, _handle=h, _owned=True)
 
     def derive(self, name):
-        """derived quantity of the plotfile ("energy", "mag_vort", "avg_pressure": NavierStokes::derive) as a one-component cell MultiFab;
+        """derived quantity of the plotfile ("energy", "mag_vort", "avg_pressure": NavierStokes::derive) or one of the velocity-gradient
+        fields of pdf.VELGRAD_NAMES as a one-component cell MultiFab; a list of names: derive_fields, one multi-component array;
         "velocity_average" (only with avg_interval > 0; der_vel_avg, NS_derive.cpp:11-45) has the six components VEL_AVG_NAMES"""
         from .lib import MultiFab, CELL
+        if not isinstance(name, str):
+            return self.derive_fields(name)
         out = MultiFab(self.layout, CELL, 6 if name == "velocity_average" else 1, 0)
         check(lib().iamrx_ns_derive(self.h, name.encode(), out.h, 0))
         return out
+
+    def derive_fields(self, names):
+        """one cell MultiFab with component q = field names[q]: any mix of state names (pdf.STATE_NAMES), single-component derived names
+        and the velocity-gradient names of pdf.VELGRAD_NAMES, which all share one ghost fill and one kernel launch
+        (include/iamrx.h: iamrx_ns_derive_fields).  Collective."""
+        from .lib import MultiFab, CELL
+        names = list(names)
+        out = MultiFab(self.layout, CELL, max(len(names), 1), 0)
+        check(lib().iamrx_ns_derive_fields(self.h, len(names), (C.c_char_p * max(len(names), 1))(*[nm.encode() for nm in names]), out.h, 0))
+        return out
+
+    def integrate(self, names):
+        """volume-weighted sums of named fields over ALL cells of this level (include/iamrx.h: iamrx_ns_integrate; the names of
+        histogram) -> float64 array, one per name.  Collective; the same on every rank."""
+        import numpy as np
+        names = [names] if isinstance(names, str) else list(names)
+        out = np.zeros(max(len(names), 1))
+        check(lib().iamrx_ns_integrate(self.h, len(names), (C.c_char_p * max(len(names), 1))(*[nm.encode() for nm in names]),
+                                       out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[:len(names)]
 
     def time_average(self, dt_level, level0_steps):
         """NavierStokesBase::time_average (NS_average.cpp:19-69); a hierarchy calls it itself, the driver of a single level after post_init

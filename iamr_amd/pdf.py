@@ -8,7 +8,11 @@ import ctypes as C
 import numpy as np
 
 STATE_NAMES = ("x_velocity", "y_velocity", "z_velocity", "density", "tracer")
-DERIVED_NAMES = ("energy", "mag_vort", "avg_pressure")
+# the derived fields of the velocity-gradient tensor (csrc/k_velgrad.hip), in the order of the library's quantity ids
+VELGRAD_NAMES = ("diveru", "vort_x", "vort_y", "vort_z", "enstrophy", "strain_rate", "dissipation", "q_criterion", "r_invariant", "helicity")
+# of these a two-dimensional run (on its y-periodic slab) knows the ones that do not name a direction or need the third one
+VELGRAD_NAMES_2D = ("diveru", "enstrophy", "strain_rate", "dissipation", "q_criterion")
+DERIVED_NAMES = ("energy", "mag_vort", "avg_pressure") + VELGRAD_NAMES
 NBINS_MAX, SLOTS2_MAX = 4096, 16384
 
 

@@ -346,6 +346,9 @@ def state_names(do_trac2=0, do_temp=0):
 
 
 DERIVE_NAMES = ["energy", "mag_vort", "avg_pressure"]          # derive_lst order (NS_setup.cpp:436-449; without particles and time averages)
+# this library's own derived fields of the velocity-gradient tensor (csrc/k_velgrad.hip): amr.derive_plot_vars may name them; they are
+# not part of upstream's derive list, so ALL does not expand to them
+VELGRAD_NAMES = ["diveru", "vort_x", "vort_y", "vort_z", "enstrophy", "strain_rate", "dissipation", "q_criterion", "r_invariant", "helicity"]
 # with tracer particles (do_nspc, NS_setup.cpp:452-466): the two counts follow avg_pressure
 PARTICLE_DERIVE_NAMES = ["particle_count", "total_particle_count"]
 
@@ -360,7 +363,7 @@ def plot_selection(state, plot_vars="ALL", derive_plot_vars="NONE", averaging=Fa
     one), amr.derive_plot_vars derived ones (ALL: the derive list in its order; default NONE) -- Amr::initPltAndChk / fillDerivePlotVarList.
     Unknown names raise, as amrex::Amr aborts on them.  averaging (ns.avg_interval > 0): "velocity_average" exists, first in the derive
     list; it is returned as its six component names VEL_AVG_NAMES (run.level_arrays derives them together).  particles: a run with tracer
-    particles also knows PARTICLE_DERIVE_NAMES, after avg_pressure."""
+    particles also knows PARTICLE_DERIVE_NAMES, after avg_pressure.  A list may also name the velocity-gradient fields VELGRAD_NAMES."""
     known = (["velocity_average"] if averaging else []) + DERIVE_NAMES + (PARTICLE_DERIVE_NAMES if particles else [])
 
     def expand(names):
@@ -375,13 +378,13 @@ def plot_selection(state, plot_vars="ALL", derive_plot_vars="NONE", averaging=Fa
             raise ValueError(f"amr.plot_vars: not state variables: {bad} (have {state})")
         keep = [q for q, nm in enumerate(state) if nm in plot_vars]           # plotfile order = state order (Amr::statePlotVars is a list filled in descriptor order)
     if derive_plot_vars == "ALL":
-        der = expand(known)
+        der = expand(known)                 # (upstream's derive list: without VELGRAD_NAMES)
     elif derive_plot_vars == "NONE":
         der = []
     else:
-        bad = [v for v in derive_plot_vars if v not in known]
+        bad = [v for v in derive_plot_vars if v not in known + VELGRAD_NAMES]
         if bad:
-            raise ValueError(f"amr.derive_plot_vars: unknown derived quantities {bad} (have {known})")
+            raise ValueError(f"amr.derive_plot_vars: unknown derived quantities {bad} (have {known + VELGRAD_NAMES})")
         der = expand(derive_plot_vars)
     return keep, der
 

@@ -81,14 +81,23 @@ def level_arrays(ns, lay, N, derived=()):
     S = ns.data(N.NavierStokes.S_NEW)
     # the six names of "velocity_average" (plotfile.plot_selection) are ONE derived quantity of six components
     va = N.NavierStokes.VEL_AVG_NAMES
-    D = [ns.derive("velocity_average" if name == va[0] else name) for name in derived if name not in va[1:]]
+    # all velocity-gradient names of the plotfile are formed by ONE derive call (one ghost fill, one launch)
+    from .plotfile import VELGRAD_NAMES
+    vg = [name for name in derived if name in VELGRAD_NAMES]
+    VG = ns.derive(vg) if vg else None
+    D = [(VG, vg.index(name)) if name in vg else (ns.derive("velocity_average" if name == va[0] else name), None)
+         for name in derived if name not in va[1:]]
+
+    def comps(d, li):
+        a = d[0].to_numpy(li)[0]
+        return a if d[1] is None else a[..., d[1]:d[1] + 1]
     boxes, arrs = [], []
     for li in range(S.nlocal()):
         a, lo = S.to_numpy(li)
         blo, bhi, gi = lay.local_box(li)
         ng = (a.shape[0] - (bhi[0] - blo[0] + 1)) // 2
         v = a[ng:a.shape[0] - ng, ng:a.shape[1] - ng, ng:a.shape[2] - ng, :]
-        arrs.append(np.concatenate([v] + [d.to_numpy(li)[0] for d in D], axis=-1) if D else v.copy())
+        arrs.append(np.concatenate([v] + [comps(d, li) for d in D], axis=-1) if D else v.copy())
         boxes.append((tuple(blo), tuple(bhi)))
     return boxes, arrs
 
@@ -201,6 +210,22 @@ def take_pdf(run, pr, step, rank, say):
         path = f"{pf['file']}{step:05d}"
         write_pdf(path, h, step, run.time)
         say("PDF:", path)
+
+
+def take_integrals(run, pr, step, rank, say):
+    """ns.integrate_interval > 0: every that many level-0 steps (and for the initial data, step 0) the volume integrals of the fields of
+    ns.integrate_vars over the level or the hierarchy go as one row `step time v1 ... vn` to the text file ns.integrate_file
+    (integrals.py).  Collective: every rank takes part, rank 0 writes.  A two-dimensional run on its slab reports the plane integrals: the
+    sums divided by the slab's thickness (as sum_lines does)."""
+    ig = pr.get("integrate") or {}
+    if ig.get("interval", 0) <= 0 or step % ig["interval"] != 0:
+        return
+    from .integrals import append_row
+    v = run.integrate(ig["vars"])
+    if pr.get("slab"):
+        v = v / (pr["prob_hi"][1] - pr["prob_lo"][1])
+    if rank == 0:
+        append_row(ig["file"], ig["vars"], step, run.time, v)
 
 
 def enforce_plane(levels, pr):
@@ -360,7 +385,7 @@ def drive(pr, inp, lib, N, hierarchy, rank=0, world=1, observe=None):
     """a run from amr.restart or from its initial data to max_step / stop_time: a single level, or (hierarchy) an Amr hierarchy.  world > 1:
     the boxes of every level are spread over the ranks (level 0 by Layout.decompose, fixed refined grids round-robin, regridded levels
     by the library's knapsack, restarted levels as checkpoint.restart says) and every rank executes the same sequence of collective
-    operations: step, enforce_plane, sums, time average, profile, spectrum, pdf, observe, plotfile, checkpoint.  observe: see main"""
+    operations: step, enforce_plane, sums, time average, profile, spectrum, pdf, integrals, observe, plotfile, checkpoint.  observe: see main"""
     from . import checkpoint
     say = print if rank == 0 else (lambda *a, **k: None)
     plot_int, plot_root = pr.get("plot_int", -1), pr.get("plot_file", "plt")
@@ -373,11 +398,17 @@ def drive(pr, inp, lib, N, hierarchy, rank=0, world=1, observe=None):
         take_profile(run, pr, step, rank, say)
         take_spectrum(run, pr, step, rank, say)
         take_pdf(run, pr, step, rank, say)
+        take_integrals(run, pr, step, rank, say)
         if observe:
             observe(run, step, dt)
         if plot_int > 0 and step % plot_int == 0:           # collective: every rank writes, rank 0 reports
             say("PLOTFILE:", write_plot(run, run.layouts, pr, N, step, plot_root))
 
+    ig = pr.get("integrate") or {}
+    if ig.get("interval", 0) > 0 and rank == 0:
+        # the one file of the run's integrals: started afresh (header line) by a run from initial data, appended to after amr.restart
+        from .integrals import start_file
+        start_file(ig["file"], ig["vars"], append=bool(pr.get("restart")))
     if pr.get("restart"):
         # amr.restart (Amr::restart): grids, data, times and step counters come from the checkpoint, parameters from the inputs file
         # (the solvers' options are the run's too: a two-dimensional run restarts with its slab multigrid, see solver_opts)

@@ -449,6 +449,21 @@ int iamrx_fillpatch_two_levels(iamrx_mf dst, int dcomp, double time, iamrx_mf fi
 /* ---- error estimation and grid generation ---------------------------------------------- */
 /* "mag_vort" derived quantity (dermgvort, Source/NS_derive.cpp:86-264, non-EB): out(ocomp) = |curl u|, vel needs 1 filled ghost cell */
 int iamrx_derive_mag_vort(const iamrx_geom* g, iamrx_mf out, int ocomp, iamrx_mf vel, int vcomp);
+/* Derived fields of the velocity-gradient tensor (this library's own; csrc/k_velgrad.hip).  A[n][d] = d u_n / d x_d at the cell centre is
+ * the centred difference 0.5 * (u_n(+e_d) - u_n(-e_d)) * (1 / dx_d) over vel(vcomp .. vcomp + 2), which needs at least 1 FILLED ghost
+ * layer (only the face neighbours of a cell are read).  out(ocomp + q) = quantity which[q], q < nq <= 10, on the valid cells; the ids:
+ *   0 diveru = (A00 + A11) + A22;  1 2 3 vort_x, vort_y, vort_z = A21 - A12, A02 - A20, A10 - A01;
+ *   4 enstrophy = 0.5 * (vort_x^2 + vort_y^2 + vort_z^2);  5 strain_rate = sqrt(2 SS);  6 dissipation = mu * (2 SS);
+ *   7 q_criterion = 0.5 * (enstrophy - SS) (= -A_ij A_ji / 2);  8 r_invariant = -det(A);  9 helicity = u . vort
+ * with SS = A00^2 + A11^2 + A22^2 + 0.5 * ((A01 + A10)^2 + (A02 + A20)^2 + (A12 + A21)^2).  One pass forms all of them.
+ * path 0: the marching form (velocity planes in LDS) where the level's largest box holds a full 32 x 8 tile, else the plain form; 1 / 2
+ * force the marching / plain form (1 on a level without a full tile is an error).  Both give the same bits.  iamrx_velgrad_path: the
+ * form (1 / 2) such a call takes on the layout of vel. */
+int iamrx_derive_velgrad(const iamrx_geom* g, iamrx_mf out, int ocomp, int nq, const int* which, iamrx_mf vel, int vcomp, double mu, int path);
+int iamrx_velgrad_path(iamrx_mf vel, int path, int* form);
+/* measurement aid (tools/bench_velgrad.py): reps times one launch of nq outputs into out(0 .. nq) (split != 0: nq single-output launches)
+ * between two events; ms[r] = milliseconds of repeat r.  Nothing is read back. */
+int iamrx_velgrad_bench(const iamrx_geom* g, iamrx_mf out, int nq, const int* which, iamrx_mf vel, int vcomp, double mu, int path, int split, int reps, float* ms);
 /* one amr.refinement_indicators entry (NavierStokes::error_setup / errorEst, Source/NS_error.cpp:10-145; AMRErrorTag):
  * mode 0 value_greater, 1 value_less, 2 vorticity_greater (value x 2^level), 3 adjacent_difference_greater (field with 1 ghost cell);
  * realbox_lo/hi: in_box_lo / in_box_hi or NULL.  tags: cell-centred, 1 comp; tagged cells are set to 1 */
@@ -569,6 +584,14 @@ int iamrx_ns_data(iamrx_ns ns, int which, iamrx_mf* out);
  * components from ocomp on, x/y/z_vel_average = accumulator / time_avg and x/y/z_vel_rms = sqrt(accumulator / time_avg_fluct), a zero
  * divisor counting as 1.  Without averages the name is unknown. */
 int iamrx_ns_derive(iamrx_ns ns, const char* name, iamrx_mf out, int ocomp);
+/* iamrx_ns_derive also knows the ten velocity-gradient names of iamrx_derive_velgrad (ghost cells by FillPatch as for mag_vort;
+ * "dissipation" with mu = ns.vel_visc_coef: the molecular part only, also in an LES run).
+ * iamrx_ns_derive_fields: out(ocomp + q) = field names[q] for any mix of state names (the plotfile names of iamrx_ns_histogram),
+ * single-component derived names and velocity-gradient names; ALL velocity-gradient names of the list share one ghost fill and one launch.
+ * iamrx_ns_integrate: out[q] = volume-weighted sum of field names[q] over ALL cells of the level, on all ranks (iamrx_ns_sum_integrated
+ * for named fields; the same summation order).  Unknown names are errors that list the known ones. */
+int iamrx_ns_derive_fields(iamrx_ns ns, int nnames, const char* const* names, iamrx_mf out, int ocomp);
+int iamrx_ns_integrate(iamrx_ns ns, int nnames, const char* const* names, double* out);
 /* NavierStokesBase::time_average (Source/NS_average.cpp:19-69) as NavierStokes::post_init (Source/NavierStokes.cpp:1287-1297) and
  * NavierStokesBase::post_timestep (Source/NavierStokesBase.cpp:2630-2634) call it: dt_avg += dt_level; if level0_steps is a multiple of
  * avg_interval the new-time velocity enters the accumulators with weight dt_avg, then time_avg += dt_avg, time_avg_fluct += dt_avg (or
@@ -638,7 +661,7 @@ int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, f
  * (nbx * nby + 1 slots).
  * iamrx_ns_histogram / iamrx_ns_histogram2: fields of a level by name, weight 1, nothing masked.  The names: the state components by
  * their plotfile names x_velocity, y_velocity, z_velocity, density, tracer (tracer2 / temp when the run has them) and the single-component
- * derived quantities energy, mag_vort, avg_pressure (formed as iamrx_ns_derive forms them, into a scratch array that returns to the
+ * derived quantities energy, mag_vort, avg_pressure and the ten velocity-gradient names (formed as iamrx_ns_derive forms them, into a scratch array that returns to the
  * library's arena); new-time data.
  * All of them are collective on several ranks: every rank counts its own boxes, the slots are summed through the communicator (which
  * carries doubles: integers below 2^53 are summed exactly; a slot or a total that reaches 2^53 is an error) and every rank receives the
@@ -828,6 +851,9 @@ int iamrx_amr_time(iamrx_amr a, double* time, double* dt_levels /* [nlev] or NUL
  * (Source/NavierStokes.cpp:1284-1285; *step = 0) and in level 0's post_timestep of every sum_interval-th level-0 step
  * (Source/NavierStokesBase.cpp:2589-2592; *step = that step count); *step = -1: nothing yet. */
 int iamrx_amr_sum_integrated(iamrx_amr a, double sums[3]);
+/* the same for named fields (the names of iamrx_ns_integrate): out[q] = composite volume-weighted sum of names[q], every level with its
+ * own cell volume over the cells the next finer level does not cover, the levels added coarsest first, summed over the ranks */
+int iamrx_amr_integrate(iamrx_amr a, int nnames, const char* const* names, double* out);
 int iamrx_amr_last_sum(iamrx_amr a, int* step, double* time /* or NULL */, double sums[3]);
 /* Plane-averaged profile of the composite state along dir (see iamrx_ns_plane_profile for the quantities and the layout of out).  The bins are
  * the slabs, one cell thick, of the index space of level bin_level (0 .. finest): *nbins = cells of level 0 along dir times 2^bin_level.
