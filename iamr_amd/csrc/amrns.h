@@ -8,6 +8,8 @@
 
 namespace iamrx {
 
+MultiFab fine_coverage(const LayoutP& crse, const LayoutP& fine, const Geometry& cgeom, int ratio);
+
 class AmrNS {
 public:
     // layouts[l]: boxes of level l in that level's index space (level 0 covers the domain); ratio 2 between levels
@@ -33,19 +35,20 @@ public:
     // NavierStokes::sum_integrated_quantities (NavierStokes.cpp:1046-1079): composite mass, tracer and kinetic energy -- every level over the
     // cells the next finer one does not cover, the levels added coarsest first.  post_init and level 0's post_timestep (every
     // sum_interval-th level-0 step) call it and leave what they found in last_sum (last_sum_step: the level-0 step count then, -1: never)
-    void sum_integrated_quantities(double out[3]);
+    void sum_integrated_quantities(double out[3]) { NavierStokes::sum_integrated_of(levels(), out); }
     double last_sum[3] = {0.0, 0.0, 0.0}, last_sum_time = 0.0;
-    // the same for named fields (NavierStokes::integrate; the names: NavierStokes::hist_field): out[q] = composite volume-weighted sum of
+    // the same for named fields (the names: NavierStokes::integrate): out[q] = composite volume-weighted sum of
     // field names[q], every level with its own cell volume over the cells the next finer one does not cover, coarsest first
-    void integrate(int n, const std::string* names, double* out);
+    void integrate(int n, const std::string* names, double* out) { NavierStokes::integrate_of(levels(), n, names, out); }
     // plane-averaged profile of the composite state along dir (k_profile.hip): the PROFILE_NQ volume-weighted means of every slab of the
     // index space of level bin_level (0 .. finest), over the cells no finer level covers; out[q * nbins + b].  Returns nbins.
-    int plane_profile(int dir, int bin_level, double* out, int cap);
-    // composite histograms of named fields (k_hist.hip; the names: NavierStokes::hist_field): level l counts the cells level l + 1 does not
+    int plane_profile(int dir, int bin_level, double* out, int cap) { return NavierStokes::plane_profile_of(levels(), dir, bin_level, out, cap); }
+    // composite histograms of named fields (k_hist.hip; the names: NavierStokes::integrate): level l counts the cells level l + 1 does not
     // cover, each with the weight 8^(finest - l), so the slots are in units of finest-level cell volumes and together sum to
     // cells(level 0) * 8^finest (an error unless that stays below 2^53).  Layout of counts as NavierStokes::histogram / histogram2.
-    void histogram(int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts);
-    void histogram2(const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts);
+    void histogram(int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts) { NavierStokes::histogram_of(levels(), n, names, lo, hi, nbins, counts); }
+    void histogram2(const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts)
+    { NavierStokes::histogram2_of(levels(), namex, namey, lo, hi, nbins, counts); }
     int last_sum_step = -1;
     // ---- regridding (Amr::regrid from level 0 at the start of a coarse step; NavierStokes::errorEst, NS_error.cpp:10-145;
     // NavierStokesBase::init(AmrLevel&) / init(), NavierStokesBase.cpp:1713-1806) ----
@@ -117,6 +120,8 @@ private:
     TurbTableP turb;
     ParticlesP particles;
     void bind_particles();
+    // what the diagnostics above walk (diagnostics.hip: ONE implementation of each for a level and a hierarchy)
+    std::vector<NavierStokes*> levels() const { std::vector<NavierStokes*> v; for (auto& s : lev) v.push_back(s.get()); return v; }
     int m_ratio = 2;
     void link_level(int l);
     void check_nesting(const std::vector<BoxD>& fine, const std::vector<BoxD>& crse, const Geometry& cgeom, int l) const;

@@ -32,6 +32,18 @@ namespace iamrx {
 
 // ------------------------------------------------------------------------------------------------------------------------
 // small level-wide helpers
+// cell MultiFab on the coarse layout (1 ghost): 1 on the coarse cells the fine layout covers (also for diagnostics.hip)
+MultiFab fine_coverage(const LayoutP& crse, const LayoutP& fine, const Geometry& cgeom, int ratio)
+{
+    MultiFab fc(crse, cell_type(), 1, 1);
+    fc.setVal(0.0);
+    MultiFab ones(fine, cell_type(), 1, 0);
+    ones.setVal(1.0);
+    average_down(ones, fc, 0, 1, ratio);
+    fc.FillBoundary(cgeom);
+    return fc;
+}
+
 namespace {
 
 // cell MultiFab (1 ghost): 1 on the cells of `l` (neighbour boxes and periodic images included), 0 elsewhere
@@ -42,17 +54,6 @@ MultiFab coverage(const LayoutP& l, const Geometry& g)
     mf_add_scalar(cov, 1.0, 0, 1, 0);
     cov.FillBoundary(g);
     return cov;
-}
-// cell MultiFab on the coarse layout (1 ghost): 1 on the coarse cells the fine layout covers
-MultiFab fine_coverage(const LayoutP& crse, const LayoutP& fine, const Geometry& cgeom, int ratio)
-{
-    MultiFab fc(crse, cell_type(), 1, 1);
-    fc.setVal(0.0);
-    MultiFab ones(fine, cell_type(), 1, 0);
-    ones.setVal(1.0);
-    average_down(ones, fc, 0, 1, ratio);
-    fc.FillBoundary(cgeom);
-    return fc;
 }
 // node class with respect to a cell coverage (1 ghost): 0 none of the surrounding in-domain cells covered, 1 all of them, 2 some
 void node_class(MultiFab& out, const MultiFab& cov, const Geometry& g)
@@ -1268,101 +1269,6 @@ void AmrNS::set_particles(ParticlesP pc)
     if (!particles) { for (auto& s : lev) { s->particles = nullptr; for (auto& m : s->m_part_umac) m.clear(); } return; }
     bind_particles();
     particles->redistribute(0, (int)lev.size() - 1, 0);
-}
-
-void AmrNS::sum_integrated_quantities(double out[3])
-{
-    out[0] = out[1] = out[2] = 0.0;
-    const int fin = (int)lev.size() - 1;
-    for (int l = 0; l <= fin; ++l) {
-        NavierStokes& s = *lev[l];
-        double v[3];
-        if (l < fin) { MultiFab fc = fine_coverage(s.layout, lev[l + 1]->layout, s.g, lev[l + 1]->ratio); s.sum_integrated(&fc, v); }
-        else s.sum_integrated(nullptr, v);
-        for (int q = 0; q < 3; ++q) out[q] += v[q];
-    }
-}
-
-void AmrNS::integrate(int n, const std::string* names, double* out)
-{
-    if (n < 1 || !names || !out) throw Error("AmrNS::integrate: no field names");
-    for (int q = 0; q < n; ++q) { lev[0]->hist_field(names[q]); out[q] = 0.0; }
-    const int fin = (int)lev.size() - 1;
-    std::vector<double> v(n);
-    for (int l = 0; l <= fin; ++l) {
-        NavierStokes& s = *lev[l];
-        if (l < fin) { MultiFab fc = fine_coverage(s.layout, lev[l + 1]->layout, s.g, lev[l + 1]->ratio); s.integrate(n, names, &fc, v.data()); }
-        else s.integrate(n, names, nullptr, v.data());
-        for (int q = 0; q < n; ++q) out[q] += v[q];
-    }
-}
-
-int AmrNS::plane_profile(int dir, int bin_level, double* out, int cap)
-{
-    const int fin = (int)lev.size() - 1;
-    if (dir < 0 || dir > 2) throw Error("AmrNS::plane_profile: dir must be 0, 1 or 2, not " + std::to_string(dir));
-    if (bin_level < 0 || bin_level > fin) throw Error("AmrNS::plane_profile: bin_level " + std::to_string(bin_level) + " outside 0 .. " + std::to_string(fin));
-    const int nbins = profile_nbins(lev[0]->g, dir, bin_level);
-    if (cap < nbins) throw Error("AmrNS::plane_profile: the profile has " + std::to_string(nbins) + " bins, the caller's array holds " + std::to_string(cap));
-    std::vector<MultiFab> fc(fin);
-    std::vector<ProfileLevel> L;
-    for (int l = 0; l <= fin; ++l) {
-        NavierStokes& s = *lev[l];
-        if (l < fin) fc[l] = fine_coverage(s.layout, lev[l + 1]->layout, s.g, lev[l + 1]->ratio);
-        L.push_back(ProfileLevel{&s.get_new_data(0), l < fin ? &fc[l] : nullptr, &s.g});
-    }
-    profile_reduce((int)L.size(), L.data(), dir, bin_level, Density, Tracer, out);
-    return nbins;
-}
-
-// weights of the composite histogram: level l counts 8^(finest - l) per cell, so that the slots are in units of finest-level cell volumes
-// and together sum to cells(level 0) * 8^finest, which must stay below 2^53 (the transport between the ranks carries doubles)
-static std::vector<unsigned long long> hist_weights(int fin, long cells0, const char* who)
-{
-    if (3 * fin >= 53) throw Error(std::string(who) + ": too many levels for counts below 2^53");
-    std::vector<unsigned long long> w(fin + 1);
-    for (int l = 0; l <= fin; ++l) w[l] = 1ULL << (3 * (fin - l));
-    const double total = (double)cells0 * (double)w[0];
-    if (!(total < 9007199254740992.0)) throw Error(std::string(who) + ": cells(level 0) * 8^finest = " + std::to_string(total) + " does not stay below 2^53");
-    return w;
-}
-
-void AmrNS::histogram(int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts)
-{
-    if (n < 1) throw Error("AmrNS::histogram: no field names");
-    for (int q = 0; q < n; ++q) { lev[0]->hist_field(names[q]); hist_check_range("AmrNS::histogram", lo[q], hi[q], nbins, HIST_NBINS_MAX); }
-    const std::vector<unsigned long long> w = hist_weights((int)lev.size() - 1, lev[0]->g.domain.npts(), "AmrNS::histogram");
-    const int fin = (int)lev.size() - 1;
-    const size_t nslots = (size_t)n * (nbins + 3);
-    unsigned long long* d = hist_begin(nslots);
-    try {
-        for (int l = 0; l <= fin; ++l) {
-            NavierStokes& s = *lev[l];
-            if (l < fin) { MultiFab fc = fine_coverage(s.layout, lev[l + 1]->layout, s.g, lev[l + 1]->ratio); s.hist_add_names(n, names, &fc, lo, hi, nbins, w[l], d); }
-            else s.hist_add_names(n, names, nullptr, lo, hi, nbins, w[l], d);
-        }
-    } catch (...) { Context::get().sync(); Context::get().free(d); throw; }
-    hist_end(d, nslots, counts);
-}
-
-void AmrNS::histogram2(const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts)
-{
-    lev[0]->hist_field(namex); lev[0]->hist_field(namey);
-    for (int a = 0; a < 2; ++a) hist_check_range("AmrNS::histogram2", lo[a], hi[a], nbins[a], HIST2_SLOTS_MAX);
-    if ((long)nbins[0] * nbins[1] > HIST2_SLOTS_MAX)
-        throw Error("AmrNS::histogram2: nbins = " + std::to_string(nbins[0]) + " x " + std::to_string(nbins[1]) + " exceeds " + std::to_string(HIST2_SLOTS_MAX) + " slots");
-    const std::vector<unsigned long long> w = hist_weights((int)lev.size() - 1, lev[0]->g.domain.npts(), "AmrNS::histogram2");
-    const int fin = (int)lev.size() - 1;
-    const size_t nslots = (size_t)nbins[0] * nbins[1] + 1;
-    unsigned long long* d = hist_begin(nslots);
-    try {
-        for (int l = 0; l <= fin; ++l) {
-            NavierStokes& s = *lev[l];
-            if (l < fin) { MultiFab fc = fine_coverage(s.layout, lev[l + 1]->layout, s.g, lev[l + 1]->ratio); s.hist_add2_names(namex, namey, &fc, lo, hi, nbins, w[l], d); }
-            else s.hist_add2_names(namex, namey, nullptr, lo, hi, nbins, w[l], d);
-        }
-    } catch (...) { Context::get().sync(); Context::get().free(d); throw; }
-    hist_end(d, nslots, counts);
 }
 
 // Amr::timeStep

@@ -1198,21 +1198,23 @@ int iamrx_ns_data(iamrx_ns ns, int which, iamrx_mf* out)
     IAMRX_CATCH
 }
 
-// overwrite one of the level's arrays (same selectors as iamrx_ns_data) with src: problem set-up from caller data
+// form nc derived components into out(ocomp ..): straight into it on the level's working layout, else there first and then to the caller's boxes
+static void derive_into(NavierStokes& n, MultiFab& out, int ocomp, int nc, const std::function<void(MultiFab&, int)>& form)
+{
+    if (out.layout->id == n.lay()->id) { form(out, ocomp); return; }
+    IAMRX_ASSERT(out.layout->id == n.user_layout->id && out.type.cell());
+    MultiFab t(n.lay(), cell_type(), nc, 0), u(n.user_layout, cell_type(), nc, 0);
+    form(t, 0);
+    relayout_copy(u, t, nc);
+    MultiFab::Copy(out, u, 0, ocomp, nc, 0);
+}
 int iamrx_ns_derive(iamrx_ns ns, const char* name, iamrx_mf out, int ocomp)
 {
     IAMRX_TRY
     NavierStokes& n = *ns->ns;
     const int nc = std::string(name) == "velocity_average" ? 6 : 1;      // der_vel_avg: mean and rms of the three velocities
     if (ocomp < 0 || ocomp + nc > out->mf.ncomp) throw Error("iamrx_ns_derive: out has too few components for '" + std::string(name) + "'");
-    if (out->mf.layout->id == n.lay()->id) n.derive(name, out->mf, ocomp);
-    else {
-        IAMRX_ASSERT(out->mf.layout->id == n.user_layout->id && out->mf.type.cell());
-        MultiFab t(n.lay(), cell_type(), nc, 0), u(n.user_layout, cell_type(), nc, 0);
-        n.derive(name, t, 0);
-        relayout_copy(u, t, nc);
-        MultiFab::Copy(out->mf, u, 0, ocomp, nc, 0);
-    }
+    derive_into(n, out->mf, ocomp, nc, [&](MultiFab& t, int c) { n.derive(name, t, c); });
     IAMRX_CATCH
 }
 
@@ -1224,14 +1226,7 @@ int iamrx_ns_derive_fields(iamrx_ns ns, int nnames, const char* const* names, ia
     NavierStokes& n = *ns->ns;
     const std::vector<std::string> v = hist_names("iamrx_ns_derive_fields", nnames, names);
     if (ocomp < 0 || ocomp + nnames > out->mf.ncomp) throw Error("iamrx_ns_derive_fields: out has too few components for " + std::to_string(nnames) + " fields");
-    if (out->mf.layout->id == n.lay()->id) n.derive_fields(nnames, v.data(), out->mf, ocomp);
-    else {
-        IAMRX_ASSERT(out->mf.layout->id == n.user_layout->id && out->mf.type.cell());
-        MultiFab t(n.lay(), cell_type(), nnames, 0), u(n.user_layout, cell_type(), nnames, 0);
-        n.derive_fields(nnames, v.data(), t, 0);
-        relayout_copy(u, t, nnames);
-        MultiFab::Copy(out->mf, u, 0, ocomp, nnames, 0);
-    }
+    derive_into(n, out->mf, ocomp, nnames, [&](MultiFab& t, int c) { n.derive_fields(nnames, v.data(), t, c); });
     IAMRX_CATCH
 }
 int iamrx_ns_integrate(iamrx_ns ns, int nnames, const char* const* names, double* out)
@@ -1239,7 +1234,7 @@ int iamrx_ns_integrate(iamrx_ns ns, int nnames, const char* const* names, double
     IAMRX_TRY
     if (!ns || !out) throw Error("iamrx_ns_integrate: null argument");
     const std::vector<std::string> v = hist_names("iamrx_ns_integrate", nnames, names);
-    ns->ns->integrate(nnames, v.data(), nullptr, out);
+    ns->ns->integrate(nnames, v.data(), out);
     IAMRX_CATCH
 }
 
@@ -1253,7 +1248,7 @@ int iamrx_ns_average_state(iamrx_ns ns, int set, double v[3])
     else { v[0] = n.time_avg; v[1] = n.time_avg_fluct; v[2] = n.dt_avg; }
     IAMRX_CATCH
 }
-int iamrx_ns_sum_integrated(iamrx_ns ns, double sums[3]) { IAMRX_TRY ns->ns->sum_integrated(nullptr, sums); IAMRX_CATCH }
+int iamrx_ns_sum_integrated(iamrx_ns ns, double sums[3]) { IAMRX_TRY ns->ns->sum_integrated(sums); IAMRX_CATCH }
 int iamrx_profile_nq(void) { return PROFILE_NQ; }
 int iamrx_ns_plane_profile(iamrx_ns ns, int dir, int nbins_cap, double* out, int* nbins)
 {
@@ -1307,11 +1302,9 @@ int iamrx_mf_histogram(iamrx_mf mf, int comp, int ncomp, iamrx_mf cov, const dou
     if (!lo || !hi || !counts) throw Error("iamrx_mf_histogram: null argument");
     if (weight < 1) throw Error("iamrx_mf_histogram: weight = " + std::to_string(weight) + " must be >= 1");
     for (int q = 0; q < ncomp; ++q) hist_check_range("iamrx_mf_histogram", lo[q], hi[q], nbins, HIST_NBINS_MAX);
-    const size_t nslots = (size_t)ncomp * (nbins + 3);
-    unsigned long long* d = hist_begin(nslots);
-    try { hist_add(mf->mf, ncomp, c.data(), cov ? &cov->mf : nullptr, lo, hi, nbins, (unsigned long long)weight, d); }
-    catch (...) { Context::get().sync(); Context::get().free(d); throw; }
-    hist_end(d, nslots, counts);
+    HistSlots slots((size_t)ncomp * (nbins + 3));
+    hist_add(mf->mf, ncomp, c.data(), cov ? &cov->mf : nullptr, lo, hi, nbins, (unsigned long long)weight, slots.d);
+    slots.finish(counts);
     IAMRX_CATCH
 }
 int iamrx_mf_histogram2(iamrx_mf mf, int compx, int compy, iamrx_mf cov, const double lo[2], const double hi[2], const int nbins[2], long long weight, long long* counts)
@@ -1319,14 +1312,10 @@ int iamrx_mf_histogram2(iamrx_mf mf, int compx, int compy, iamrx_mf cov, const d
     IAMRX_TRY
     if (!mf || !lo || !hi || !nbins || !counts) throw Error("iamrx_mf_histogram2: null argument");
     if (weight < 1) throw Error("iamrx_mf_histogram2: weight = " + std::to_string(weight) + " must be >= 1");
-    for (int a = 0; a < 2; ++a) hist_check_range("iamrx_mf_histogram2", lo[a], hi[a], nbins[a], HIST2_SLOTS_MAX);
-    if ((long)nbins[0] * nbins[1] > HIST2_SLOTS_MAX)
-        throw Error("iamrx_mf_histogram2: nbins = " + std::to_string(nbins[0]) + " x " + std::to_string(nbins[1]) + " exceeds " + std::to_string(HIST2_SLOTS_MAX) + " slots");
-    const size_t nslots = (size_t)nbins[0] * nbins[1] + 1;
-    unsigned long long* d = hist_begin(nslots);
-    try { hist_add2(mf->mf, compx, mf->mf, compy, cov ? &cov->mf : nullptr, lo, hi, nbins, (unsigned long long)weight, d); }
-    catch (...) { Context::get().sync(); Context::get().free(d); throw; }
-    hist_end(d, nslots, counts);
+    hist2_check("iamrx_mf_histogram2", lo, hi, nbins);
+    HistSlots slots((size_t)nbins[0] * nbins[1] + 1);
+    hist_add2(mf->mf, compx, mf->mf, compy, cov ? &cov->mf : nullptr, lo, hi, nbins, (unsigned long long)weight, slots.d);
+    slots.finish(counts);
     IAMRX_CATCH
 }
 int iamrx_ns_histogram(iamrx_ns ns, int nnames, const char* const* names, const double* lo, const double* hi, int nbins, long long* counts)
@@ -1354,6 +1343,7 @@ int iamrx_hist_bench(iamrx_mf mf, int comp, int ncomp, iamrx_mf cov, const doubl
     IAMRX_CATCH
 }
 
+// overwrite one of the level's arrays (same selectors as iamrx_ns_data) with src: problem set-up from caller data
 int iamrx_ns_set_data(iamrx_ns ns, int which, iamrx_mf src)
 {
     IAMRX_TRY

@@ -97,6 +97,16 @@ void hist_add(const MultiFab& S, int ncol, const int* comps, const MultiFab* cov
 void hist_add2(const MultiFab& X, int compx, const MultiFab& Y, int compy, const MultiFab* cov, const double lo[2], const double hi[2],
                const int nbins[2], unsigned long long weight, unsigned long long* d_counts);
 void hist_end(unsigned long long* d_counts, size_t nslots, long long* out);
+// the device slots of one histogram call: hist_begin here, hist_end in finish(); an error that unwinds past them syncs and frees them
+struct HistSlots {
+    size_t n; unsigned long long* d;
+    explicit HistSlots(size_t nslots) : n(nslots), d(hist_begin(nslots)) {}
+    HistSlots(const HistSlots&) = delete;
+    ~HistSlots() { if (d) { try { Context::get().sync(); Context::get().free(d); } catch (...) {} } }
+    void finish(long long* counts) { unsigned long long* p = d; d = nullptr; hist_end(p, n, counts); }
+};
+// the checks of a joint histogram: both ranges, and nbins[0] * nbins[1] <= HIST2_SLOTS_MAX (diagnostics.hip)
+void hist2_check(const char* who, const double lo[2], const double hi[2], const int nbins[2]);
 // measurement aid: ms[r] = the launches of one hist_add (nby = 0) or hist_add2 (ncol = 2, nby > 0) between two events, nothing read back
 void hist_bench(const MultiFab& S, int ncol, const int* comps, const MultiFab* cov, const double* lo, const double* hi, int nbins, int nby,
                 int reps, float* ms);

@@ -268,111 +268,6 @@ void NavierStokes::swap_time_levels(double dt_)      // StateData::swapTimeLevel
     pt_new[0] = pt_new[1]; pt_new[1] += dt_;
 }
 
-// FillPatch: copy the valid data, same-level + periodic ghost fill, then the physical-BC fill
-// (StateDataPhysBCFunct: FilccCell rules + the ext_dir functors of NS_bcfill.H).  On a refined level: FillPatchTwoLevels with the
-// coarse level's data interpolated in time (amr.hip); src must be the level's old or new State_Type data.
-const char* const VELGRAD_NAMES[10] = {"diveru", "vort_x", "vort_y", "vort_z", "enstrophy", "strain_rate", "dissipation", "q_criterion", "r_invariant", "helicity"};
-static const char* const VELGRAD_LIST = "diveru, vort_x, vort_y, vort_z, enstrophy, strain_rate, dissipation, q_criterion, r_invariant, helicity";
-int velgrad_id(const std::string& name)
-{
-    for (int q = 0; q < VELGRAD_NQ; ++q) if (name == VELGRAD_NAMES[q]) return q;
-    return -1;
-}
-
-void NavierStokes::derive(const std::string& name, MultiFab& out, int ocomp)
-{
-    IAMRX_ASSERT(out.type.cell() && out.layout->id == layout->id && ocomp < out.ncomp);
-    if (velgrad_id(name) >= 0) { derive_fields(1, &name, out, ocomp); return; }
-    auto& ctx = Context::get();
-    const FabD* ot = out.d_tab;
-    if (name == "energy") {                                    // derkeng, NS_derive.cpp:266-295
-        const FabD* st = S[inew].d_tab;
-        for_each(*layout, cell_type(), 0, ctx.stream, [=] __device__(int i, int j, int k, int f) {
-            const FabD s = st[f];
-            const double vx = s(i, j, k, Xvel), vy = s(i, j, k, Yvel), vz = s(i, j, k, Zvel);
-            ot[f](i, j, k, ocomp) = 0.5 * s(i, j, k, Density) * (vx * vx + vy * vy + vz * vz);
-        });
-    } else if (name == "mag_vort") {                           // dermgvort on FillPatched velocities (grow_box_by_two upstream; the stencil reads one cell)
-        MultiFab vel(layout, cell_type(), 3, 1);
-        fillpatch(vel, S[inew], Xvel, 3, bc_vel);
-        derive_mag_vort(g, out, ocomp, vel, 0);
-    } else if (name == "avg_pressure") {                       // deravgpres, NS_derive.cpp:51-80
-        const FabD* pt = P[pnew].d_tab;
-        for_each(*layout, cell_type(), 0, ctx.stream, [=] __device__(int i, int j, int k, int f) {
-            const FabD p = pt[f];
-            ot[f](i, j, k, ocomp) = 0.125 * (p(i + 1, j, k) + p(i, j, k) + p(i + 1, j + 1, k) + p(i, j + 1, k)
-                                           + p(i + 1, j, k + 1) + p(i, j, k + 1) + p(i + 1, j + 1, k + 1) + p(i, j + 1, k + 1));
-        });
-    } else if (name == "velocity_average" && has_average()) {  // der_vel_avg, NS_derive.cpp:11-45: 6 components
-        IAMRX_ASSERT(ocomp + 6 <= out.ncomp);
-        stats_derive_vel_avg(out, ocomp, Savg, time_avg, time_avg_fluct);
-    } else if (name == "particle_count" && particles) {        // NavierStokesBase::ParticleDerive, NavierStokesBase.cpp:3996-4048
-        particles->particle_count(level, out, ocomp);
-    } else if (name == "total_particle_count" && particles) {
-        particles->total_particle_count(level, out, ocomp);
-    } else throw Error("NavierStokes::derive: unknown derived quantity '" + name + "' (energy, mag_vort, avg_pressure" + (has_average() ? ", velocity_average" : "") +
-                       (particles ? ", particle_count, total_particle_count, " : ", ") + VELGRAD_LIST + ")");
-}
-
-void NavierStokes::derive_fields(int n, const std::string* names, MultiFab& out, int ocomp)
-{
-    if (n < 1 || !names) throw Error("NavierStokes::derive_fields: no field names");
-    IAMRX_ASSERT(out.type.cell() && out.layout->id == layout->id);
-    if (ocomp < 0 || ocomp + n > out.ncomp) throw Error("NavierStokes::derive_fields: " + std::to_string(n) + " fields from component " + std::to_string(ocomp) + " do not fit the array's " + std::to_string(out.ncomp));
-    std::vector<int> vq, vid;          // the velocity-gradient names: their places in the list and their ids
-    for (int q = 0; q < n; ++q) {
-        if (names[q] == "velocity_average") throw Error("NavierStokes::derive_fields: velocity_average has six components; ask derive() for it");
-        const int id = velgrad_id(names[q]);
-        if (id >= 0) { vq.push_back(q); vid.push_back(id); }
-    }
-    for (int q = 0; q < n; ++q) {
-        if (velgrad_id(names[q]) >= 0) continue;
-        int comp = -1;
-        try { comp = hist_field(names[q]); } catch (const Error&) { comp = -1; }          // (derive() knows names hist_field does not, and reports the unknown ones)
-        if (comp >= 0) MultiFab::Copy(out, S[inew], comp, ocomp + q, 1, 0);
-        else derive(names[q], out, ocomp + q);
-    }
-    if (vq.empty()) return;
-    const int m = (int)vq.size();
-    MultiFab vel(layout, cell_type(), 3, 1);
-    fillpatch(vel, S[inew], Xvel, 3, bc_vel);
-    if (vq.back() - vq.front() == m - 1) { derive_velgrad(g, out, ocomp + vq.front(), m, vid.data(), vel, 0, p.visc_coef, 0); return; }
-    MultiFab t(layout, cell_type(), m, 0);          // the names are scattered over the list: one launch into a scratch array, then to their places
-    derive_velgrad(g, t, 0, m, vid.data(), vel, 0, p.visc_coef, 0);
-    for (int s = 0; s < m; ++s) MultiFab::Copy(out, t, s, ocomp + vq[s], 1, 0);
-}
-
-void NavierStokes::integrate(int n, const std::string* names, const MultiFab* fine_cov, double* out)
-{
-    if (n < 1 || !names || !out) throw Error("NavierStokes::integrate: no field names");
-    std::vector<int> comp(n), sq, sc, dq;
-    std::vector<std::string> dn;
-    for (int q = 0; q < n; ++q) {
-        comp[q] = hist_field(names[q]);
-        if (comp[q] >= 0) { sq.push_back(q); sc.push_back(comp[q]); } else { dq.push_back(q); dn.push_back(names[q]); }
-    }
-    std::vector<double> v(n, 0.0);
-    if (!sq.empty()) {
-        std::vector<double> r(sq.size());
-        reduce_sum_comps(S[inew], (int)sq.size(), sc.data(), fine_cov, r.data());
-        for (size_t s = 0; s < sq.size(); ++s) v[sq[s]] = r[s];
-    }
-    if (!dq.empty()) {
-        const int m = (int)dq.size();
-        MultiFab t(layout, cell_type(), m, 0);
-        derive_fields(m, dn.data(), t, 0);
-        std::vector<int> c(m);
-        std::vector<double> r(m);
-        for (int s = 0; s < m; ++s) c[s] = s;
-        reduce_sum_comps(t, m, c.data(), fine_cov, r.data());
-        for (int s = 0; s < m; ++s) v[dq[s]] = r[s];
-    }
-    const double vol = g.dx[0] * g.dx[1] * g.dx[2];
-    for (int q = 0; q < n; ++q) out[q] = v[q] * vol;
-    auto& comm = Context::get().comm;
-    if (comm && comm->nranks > 1 && !layout->replicated) comm->allreduce(out, n, ReduceOp::Sum);
-}
-
 // NavierStokesBase::time_average (NS_average.cpp:19-69), statement by statement
 void NavierStokes::time_average(double dt_level, int level0_steps)
 {
@@ -384,115 +279,6 @@ void NavierStokes::time_average(double dt_level, int level0_steps)
     time_avg = time_avg + dt_avg;
     time_avg_fluct = fluct ? time_avg_fluct + dt_avg : 0.0;
     dt_avg = 0.0;
-}
-
-// the level's share of NavierStokes::sum_integrated_quantities (NavierStokes.cpp:1046-1079; amrex volumeWeightedSum: the cells under the
-// finer level do not count, the weight is the cell volume): one fused reduction (k_basic.hip), then one sum over the ranks
-void NavierStokes::sum_integrated(const MultiFab* fine_cov, double out[3])
-{
-    reduce_sum_integrated(S[inew], Density, Tracer, fine_cov, out);
-    const double vol = g.dx[0] * g.dx[1] * g.dx[2];
-    for (int q = 0; q < 3; ++q) out[q] *= vol;
-    auto& comm = Context::get().comm;
-    if (comm && comm->nranks > 1 && !layout->replicated) comm->allreduce(out, 3, ReduceOp::Sum);
-}
-
-int NavierStokes::plane_profile(int dir, double* out, int cap)
-{
-    if (dir < 0 || dir > 2) throw Error("NavierStokes::plane_profile: dir must be 0, 1 or 2, not " + std::to_string(dir));
-    const int nbins = profile_nbins(g, dir, 0);
-    if (cap < nbins) throw Error("NavierStokes::plane_profile: the profile has " + std::to_string(nbins) + " bins, the caller's array holds " + std::to_string(cap));
-    const ProfileLevel L{&S[inew], nullptr, &g};
-    profile_reduce(1, &L, dir, 0, Density, Tracer, out);
-    return nbins;
-}
-
-// ---- histograms of named fields (k_hist.hip)
-int NavierStokes::hist_field(const std::string& name) const
-{
-    if (name == "x_velocity") return Xvel;
-    if (name == "y_velocity") return Yvel;
-    if (name == "z_velocity") return Zvel;
-    if (name == "density") return Density;
-    if (name == "tracer") return Tracer;
-    if (name == "tracer2" && Tracer2 >= 0) return Tracer2;
-    if (name == "temp" && Temp >= 0) return Temp;
-    if (name == "energy" || name == "mag_vort" || name == "avg_pressure") return -1;
-    if (velgrad_id(name) >= 0) return -2;
-    throw Error("NavierStokes::histogram: unknown field '" + name + "' (x_velocity, y_velocity, z_velocity, density, tracer" +
-                (Tracer2 >= 0 ? ", tracer2" : "") + (Temp >= 0 ? ", temp" : "") + ", energy, mag_vort, avg_pressure, " + VELGRAD_LIST + ")");
-}
-
-void NavierStokes::hist_add_names(int n, const std::string* names, const MultiFab* cov, const double* lo, const double* hi, int nbins,
-                                  unsigned long long weight, unsigned long long* d_counts)
-{
-    std::vector<int> comp(n);
-    for (int q = 0; q < n; ++q) { comp[q] = hist_field(names[q]); hist_check_range("NavierStokes::histogram", lo[q], hi[q], nbins, HIST_NBINS_MAX); }
-    // consecutive state names share one pass over the state; a derived quantity is formed into a scratch array and takes a pass of its own;
-    // consecutive velocity-gradient names are formed together (one ghost fill, one launch) and share one pass
-    for (int q = 0; q < n;) {
-        unsigned long long* out = d_counts + (size_t)q * (nbins + 3);
-        if (comp[q] >= 0) {
-            int m = 1;
-            while (q + m < n && comp[q + m] >= 0) ++m;
-            hist_add(S[inew], m, comp.data() + q, cov, lo + q, hi + q, nbins, weight, out);
-            q += m;
-        } else if (comp[q] == -2) {
-            int m = 1;
-            while (q + m < n && comp[q + m] == -2) ++m;
-            MultiFab t(layout, cell_type(), m, 0);
-            derive_fields(m, names + q, t, 0);
-            std::vector<int> c(m);
-            for (int s = 0; s < m; ++s) c[s] = s;
-            hist_add(t, m, c.data(), cov, lo + q, hi + q, nbins, weight, out);
-            q += m;
-        } else {
-            MultiFab t(layout, cell_type(), 1, 0);
-            derive(names[q], t, 0);
-            const int zero = 0;
-            hist_add(t, 1, &zero, cov, lo + q, hi + q, nbins, weight, out);
-            ++q;
-        }
-    }
-}
-
-void NavierStokes::hist_add2_names(const std::string& namex, const std::string& namey, const MultiFab* cov, const double lo[2], const double hi[2],
-                                   const int nbins[2], unsigned long long weight, unsigned long long* d_counts)
-{
-    const int cx = hist_field(namex), cy = hist_field(namey);
-    if (cx == -2 && cy == -2) {          // two velocity-gradient names: one ghost fill, one launch
-        MultiFab t(layout, cell_type(), 2, 0);
-        const std::string nm[2] = {namex, namey};
-        derive_fields(2, nm, t, 0);
-        hist_add2(t, 0, t, 1, cov, lo, hi, nbins, weight, d_counts);
-        return;
-    }
-    MultiFab tx, ty;
-    if (cx < 0) { tx.define(layout, cell_type(), 1, 0); derive(namex, tx, 0); }
-    if (cy < 0) { ty.define(layout, cell_type(), 1, 0); derive(namey, ty, 0); }
-    hist_add2(cx < 0 ? tx : S[inew], std::max(cx, 0), cy < 0 ? ty : S[inew], std::max(cy, 0), cov, lo, hi, nbins, weight, d_counts);
-}
-
-void NavierStokes::histogram(int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts)
-{
-    if (n < 1) throw Error("NavierStokes::histogram: no field names");
-    for (int q = 0; q < n; ++q) { hist_field(names[q]); hist_check_range("NavierStokes::histogram", lo[q], hi[q], nbins, HIST_NBINS_MAX); }
-    const size_t nslots = (size_t)n * (nbins + 3);
-    unsigned long long* d = hist_begin(nslots);
-    try { hist_add_names(n, names, nullptr, lo, hi, nbins, 1ULL, d); } catch (...) { Context::get().sync(); Context::get().free(d); throw; }
-    hist_end(d, nslots, counts);
-}
-
-void NavierStokes::histogram2(const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts)
-{
-    hist_field(namex); hist_field(namey);
-    for (int a = 0; a < 2; ++a) hist_check_range("NavierStokes::histogram2", lo[a], hi[a], nbins[a], HIST2_SLOTS_MAX);
-    if ((long)nbins[0] * nbins[1] > HIST2_SLOTS_MAX)
-        throw Error("NavierStokes::histogram2: nbins = " + std::to_string(nbins[0]) + " x " + std::to_string(nbins[1]) + " exceeds " + std::to_string(HIST2_SLOTS_MAX) + " slots");
-    const size_t nslots = (size_t)nbins[0] * nbins[1] + 1;
-    unsigned long long* d = hist_begin(nslots);
-    try { hist_add2_names(namex, namey, nullptr, lo, hi, nbins, 1ULL, d); } catch (...) { Context::get().sync(); Context::get().free(d); throw; }
-    hist_end(d, nslots, counts);
 }
 
 // the common part of the three C entries: *nbins first, then the capacity
@@ -511,6 +297,9 @@ void NavierStokes::spectrum(int cap, double* out, long* count, int* nbins)
     spectrum_of(g, S[inew], SPECTRUM_NQ, comps, cap, out, count, nbins);
 }
 
+// FillPatch: copy the valid data, same-level + periodic ghost fill, then the physical-BC fill
+// (StateDataPhysBCFunct: FilccCell rules + the ext_dir functors of NS_bcfill.H).  On a refined level: FillPatchTwoLevels with the
+// coarse level's data interpolated in time (amr.hip); src must be the level's old or new State_Type data.
 void NavierStokes::fillpatch(MultiFab& dst, const MultiFab& src, int scomp, int ncomp, const BCRec* bc)
 {
     const bool is_vel = (bc == bc_vel);

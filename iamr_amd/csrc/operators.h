@@ -106,9 +106,6 @@ MGStats mac_sync_solve(const Geometry& g, FluxRegister& mr, const MultiFab& rho_
 void derive_mag_vort(const Geometry& g, MultiFab& out, int ocomp, const MultiFab& vel, int vcomp);
 // the derived fields of the velocity-gradient tensor (k_velgrad.hip; declared in kernels.h): out(ocomp + q) = quantity which[q]
 void derive_velgrad(const Geometry& g, MultiFab& out, int ocomp, int nq, const int* which, const MultiFab& vel, int vcomp, double mu, int path);
-// the names of the ten quantities in the order of their ids, and the id of a name (-1: not one of them)
-extern const char* const VELGRAD_NAMES[10];
-int velgrad_id(const std::string& name);
 void error_tag(const Geometry& g, MultiFab& tags, const MultiFab& field, int comp, int mode, double value, int level,
                const double* rb_lo, const double* rb_hi);
 // manual_tags_placement at the outflow faces (NavierStokesBase.cpp:2112-2215): mode 1 do_refine_outflow, 2 do_derefine_outflow with
@@ -278,6 +275,8 @@ void scale_by(MultiFab& y, const MultiFab& x, int xcomp, int ng, bool divide);  
 class SyncRegister;
 class AmrNS;
 class Particles;
+struct FieldEntry;                                            // an entry of the field table (diagnostics.hip)
+struct FieldRef { const MultiFab* mf; int comp; };            // where a single-component field is
 class NavierStokes {
 public:
     // the boxes as the caller (or the grid generator) gave them; `layout` below is coalesce_layout(user_layout): what the level works on
@@ -295,18 +294,20 @@ public:
     double advance(double dt) { return advance(dt, 1, 1); }
     double advance(double dt, int iteration, int ncycle);   // NavierStokes::advance(time, dt, iteration, ncycle); returns the dt estimate
     double estTimeStep();                      // NavierStokesBase::estTimeStep
+    // ---- diagnostics of named fields (diagnostics.hip: the field table says which names there are and which entry point takes which)
     // derived quantities of the plotfile (derive_lst of NS_setup.cpp:436-449): "energy" = rho |u|^2 / 2 (derkeng), "mag_vort" = |curl u|
     // (dermgvort, ghost cells by FillPatch), "avg_pressure" = mean of the 8 nodes of the cell (deravgpres); new-time data; out: cell, >= 1 comp;
-    // with avg_interval > 0 also "velocity_average" (der_vel_avg, NS_derive.cpp:11-45): 6 components, mean velocity and rms fluctuation
-    // and the ten velocity-gradient names of VELGRAD_NAMES (k_velgrad.hip; "dissipation" with mu = ns.vel_visc_coef: the molecular part
-    // only, also in an LES run)
+    // with avg_interval > 0 also "velocity_average" (der_vel_avg, NS_derive.cpp:11-45): 6 components, mean velocity and rms fluctuation;
+    // with particles bound the two particle counts; and the ten velocity-gradient names (k_velgrad.hip; "dissipation" with
+    // mu = ns.vel_visc_coef: the molecular part only, also in an LES run)
     void derive(const std::string& name, MultiFab& out, int ocomp = 0);
-    // out(ocomp + q) = field names[q]: any mix of state names (hist_field), the single-component derived names and the velocity-gradient
-    // names; ALL velocity-gradient names of the list share ONE fillpatch of the velocity and ONE derive_velgrad launch
+    // out(ocomp + q) = field names[q]: any mix of state names by their plotfile names (x_velocity, y_velocity, z_velocity, density, tracer,
+    // and tracer2 / temp when the run has them), the single-component derived names and the velocity-gradient names; ALL
+    // velocity-gradient names of the list share ONE fillpatch of the velocity and ONE derive_velgrad launch
     void derive_fields(int n, const std::string* names, MultiFab& out, int ocomp = 0);
-    // out[q] = volume-weighted sum of field names[q] (as derive_fields forms it; state names are reduced from the state) over the cells
-    // where fine_cov (this level's layout; null: none) is zero, summed over the ranks: sum_integrated for named fields
-    void integrate(int n, const std::string* names, const MultiFab* fine_cov, double* out);
+    // out[q] = volume-weighted sum of field names[q] (a state name, energy, mag_vort, avg_pressure or a velocity-gradient name) over all
+    // cells of the level, summed over the ranks: sum_integrated for named fields
+    void integrate(int n, const std::string* names, double* out) { integrate_of({this}, n, names, out); }
     MultiFab& get_new_data(int type) { return type == 0 ? S[inew] : (type == 1 ? P[pnew] : Gp[pnew]); }
     MultiFab& get_old_data(int type) { return type == 0 ? S[1 - inew] : (type == 1 ? P[1 - pnew] : Gp[1 - pnew]); }
     MultiFab& umac(int d) { return u_mac[d]; }
@@ -322,32 +323,22 @@ public:
     // NavierStokesBase::time_average (NS_average.cpp:19-69): dt_avg += dt_level; every avg_interval-th level-0 step the accumulation
     // kernel (k_stats.hip), then the three scalars.  Nothing happens (no launch) with avg_interval = 0.
     void time_average(double dt_level, int level0_steps);
-    // this level's part of NavierStokes::sum_integrated_quantities (NavierStokes.cpp:1046-1079): volume-weighted sums of density, tracer and
-    // kinetic energy over the cells where fine_cov (this level's layout; null: none) is zero, summed over the ranks
-    void sum_integrated(const MultiFab* fine_cov, double out[3]);
+    // NavierStokes::sum_integrated_quantities (NavierStokes.cpp:1046-1079) of this level alone: volume-weighted sums of density, tracer and
+    // kinetic energy over all its cells, summed over the ranks
+    void sum_integrated(double out[3]) { sum_integrated_of({this}, out); }
     // plane-averaged profile of this level alone along dir (k_profile.hip; nothing masked): out[q * nbins + b], PROFILE_NQ quantities of the
     // new-time state, nbins = cells of the domain along dir.  Collective; every rank receives the result.  Returns nbins.
-    int plane_profile(int dir, double* out, int cap);
+    int plane_profile(int dir, double* out, int cap) { return plane_profile_of({this}, dir, 0, out, cap); }
     // shell-summed power spectra of u, v, w and the first tracer of the new-time state (k_spectrum.hip): out[q * nbins + s], SPECTRUM_NQ
     // columns, count[s] (or null) the modes of shell s.  *nbins is set before the capacity is checked.  Collective; every rank receives the
     // result.
     void spectrum(int cap, double* out, long* count, int* nbins);
-    // histograms of named fields of the new-time data (k_hist.hip; the binning rule: kernels.h).  A name is a state component by its
-    // plotfile name (x_velocity, y_velocity, z_velocity, density, tracer, and tracer2 / temp when the run has them) or one of the
-    // single-component derived quantities energy, mag_vort, avg_pressure, formed by derive() into a scratch array that returns to the
-    // arena, or one of the velocity-gradient names (consecutive ones are formed by one derive_fields into one multi-component scratch
-    // array and take one pass); anything else is an error that lists the known names.  hist_field: the state component of a name, -1
-    // for a derived one, -2 for a velocity-gradient one.
-    // hist_add_names / hist_add2_names: this level's cells where cov (null: none) is zero, each with `weight`, added to device slots of
-    // hist_begin (the hierarchy's building block).  histogram: counts[q * (nbins + 3) + s], s < nbins the bins, then below, above, nan;
+    // histograms of named fields of the new-time data (k_hist.hip; the binning rule: kernels.h; the names: those of integrate; anything
+    // else is an error that lists the known names).  histogram: counts[q * (nbins + 3) + s], s < nbins the bins, then below, above, nan;
     // histogram2: counts[bx * nby + by], then `outside`.  Collective; every rank receives the result.
-    int hist_field(const std::string& name) const;
-    void hist_add_names(int n, const std::string* names, const MultiFab* cov, const double* lo, const double* hi, int nbins,
-                        unsigned long long weight, unsigned long long* d_counts);
-    void hist_add2_names(const std::string& namex, const std::string& namey, const MultiFab* cov, const double lo[2], const double hi[2],
-                         const int nbins[2], unsigned long long weight, unsigned long long* d_counts);
-    void histogram(int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts);
-    void histogram2(const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts);
+    void histogram(int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts) { histogram_of({this}, n, names, lo, hi, nbins, counts); }
+    void histogram2(const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts)
+    { histogram2_of({this}, namex, namey, lo, hi, nbins, counts); }
     double time = 0.0, dt = 0.0;
     int nstep = 0;
     MGStats st_mac, st_nodal, st_visc, st_scal;
@@ -407,6 +398,30 @@ public:
     friend class AmrNS;
 
 private:
+    // ---- diagnostics.hip.  find_field: the table's entry of a name this run has and the entry point `use` takes (else an error that lists
+    // those names).  resolve_fields: where each single-component field of a list is -- state names in place, the others formed into `direct`
+    // (field q at dcomp + q) or into `scratch`.  integrate_level, hist_add*_names: this level's part of a diagnostic, over the cells where cov (this
+    // level's layout; null: none) is zero; the histograms add every counted cell with `weight` to the device slots.
+    const FieldEntry& find_field(const std::string& name, unsigned use, const char* who) const;
+    int state_comp(const FieldEntry& e) const;
+    void derive_pointwise(const FieldEntry& e, MultiFab& out, int ocomp);
+    std::vector<FieldRef> resolve_fields(int n, const std::string* names, unsigned use, const char* who, MultiFab& scratch, MultiFab* direct = nullptr, int dcomp = 0);
+    void form_fields(int n, const std::string* names, unsigned use, const char* who, MultiFab& out, int ocomp);
+    void finish_sums(int n, double* out) const;
+    void integrate_level(int n, const std::string* names, const MultiFab* cov, double* out);
+    void hist_add_names(int n, const std::string* names, const MultiFab* cov, const double* lo, const double* hi, int nbins,
+                        unsigned long long weight, unsigned long long* d_counts);
+    void hist_add2_names(const std::string& namex, const std::string& namey, const MultiFab* cov, const double lo[2], const double hi[2],
+                         const int nbins[2], unsigned long long weight, unsigned long long* d_counts);
+    // the ONE implementation of each diagnostic, over the levels of a hierarchy, coarsest first (every level over the cells the next
+    // finer one does not cover, the levels added in that order); a level is a hierarchy of one and passes {this}, AmrNS its levels
+    struct Levels;
+    using LevelList = std::vector<NavierStokes*>;
+    static void sum_integrated_of(const LevelList& lev, double out[3]);
+    static void integrate_of(const LevelList& lev, int n, const std::string* names, double* out);
+    static int plane_profile_of(const LevelList& lev, int dir, int bin_level, double* out, int cap);
+    static void histogram_of(const LevelList& lev, int n, const std::string* names, const double* lo, const double* hi, int nbins, long long* counts);
+    static void histogram2_of(const LevelList& lev, const std::string& namex, const std::string& namey, const double lo[2], const double hi[2], const int nbins[2], long long* counts);
     void advance_setup(double dt, int iteration, int ncycle);
     void swap_time_levels(double dt);
     void fill_gp(MultiFab& G, double time);

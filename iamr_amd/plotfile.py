@@ -17,6 +17,7 @@ Host-side I/O (control plane): plain Python + numpy, dimension-generic (2-D file
 import os
 import re
 import numpy as np
+from . import pdf as _pdf
 
 REAL_DESC = "((8, (64 11 52 0 1 12 0 1023)),(8, (8 7 6 5 4 3 2 1)))"
 
@@ -348,7 +349,7 @@ def state_names(do_trac2=0, do_temp=0):
 DERIVE_NAMES = ["energy", "mag_vort", "avg_pressure"]          # derive_lst order (NS_setup.cpp:436-449; without particles and time averages)
 # this library's own derived fields of the velocity-gradient tensor (csrc/k_velgrad.hip): amr.derive_plot_vars may name them; they are
 # not part of upstream's derive list, so ALL does not expand to them
-VELGRAD_NAMES = ["diveru", "vort_x", "vort_y", "vort_z", "enstrophy", "strain_rate", "dissipation", "q_criterion", "r_invariant", "helicity"]
+VELGRAD_NAMES = list(_pdf.VELGRAD_NAMES)
 # with tracer particles (do_nspc, NS_setup.cpp:452-466): the two counts follow avg_pressure
 PARTICLE_DERIVE_NAMES = ["particle_count", "total_particle_count"]
 

@@ -79,25 +79,19 @@ def level_arrays(ns, lay, N, derived=()):
     every rank calls this, also one that owns nothing)"""
     import numpy as np
     S = ns.data(N.NavierStokes.S_NEW)
-    # the six names of "velocity_average" (plotfile.plot_selection) are ONE derived quantity of six components
+    # the six names of "velocity_average" (plotfile.plot_selection) are ONE derived quantity of six components; all the others are formed
+    # by ONE derive_fields call (the velocity-gradient names among them share one ghost fill and one launch)
     va = N.NavierStokes.VEL_AVG_NAMES
-    # all velocity-gradient names of the plotfile are formed by ONE derive call (one ghost fill, one launch)
-    from .plotfile import VELGRAD_NAMES
-    vg = [name for name in derived if name in VELGRAD_NAMES]
-    VG = ns.derive(vg) if vg else None
-    D = [(VG, vg.index(name)) if name in vg else (ns.derive("velocity_average" if name == va[0] else name), None)
-         for name in derived if name not in va[1:]]
-
-    def comps(d, li):
-        a = d[0].to_numpy(li)[0]
-        return a if d[1] is None else a[..., d[1]:d[1] + 1]
+    single = [name for name in derived if name not in va]
+    D = ([ns.derive(single)] if single else []) + ([ns.derive("velocity_average")] if va[0] in derived else [])
+    order = [(single + va).index(name) for name in derived]
     boxes, arrs = [], []
     for li in range(S.nlocal()):
         a, lo = S.to_numpy(li)
         blo, bhi, gi = lay.local_box(li)
         ng = (a.shape[0] - (bhi[0] - blo[0] + 1)) // 2
         v = a[ng:a.shape[0] - ng, ng:a.shape[1] - ng, ng:a.shape[2] - ng, :]
-        arrs.append(np.concatenate([v] + [comps(d, li) for d in D], axis=-1) if D else v.copy())
+        arrs.append(np.concatenate([v, np.concatenate([d.to_numpy(li)[0] for d in D], axis=-1)[..., order]], axis=-1) if D else v.copy())
         boxes.append((tuple(blo), tuple(bhi)))
     return boxes, arrs
 
