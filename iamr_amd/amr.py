@@ -1,7 +1,7 @@
 """Hierarchy of NavierStokes levels (ctypes view of iamrx_amr_*; include/iamrx.h): Amr::coarseTimeStep with subcycling,
 NavierStokesBase::post_timestep (reflux, avgDown, mac_sync, level_sync) and the multi-level NavierStokes::post_init.  What the run driver,
 the checkpoint writer and the particle container read of a run -- levels, layouts, nlev, level_geom, ratio, time, dts, particles,
-plane_profile, spectrum -- a single NavierStokes level offers under the same names (ns.py)."""
+plane_profile, spectrum, structure_functions -- a single NavierStokes level offers under the same names (ns.py)."""
 import ctypes as C
 from .lib import lib, check, mg_opts, MgStats
 from .ns import NavierStokes, ns_params
@@ -227,6 +227,12 @@ class Amr:
         include/iamrx.h: iamrx_amr_spectrum) -> the dict of NavierStokes.spectrum; the same bits on every rank.  Collective."""
         from . import spectrum as _s
         return _s.level_spectrum(lib().iamrx_amr_spectrum, self.h, self.geom0)
+
+    def structure_functions(self, pmax=4, rmax=None):
+        """structure functions and two-point correlations of LEVEL 0 of the hierarchy (as spectrum takes its level; include/iamrx.h:
+        iamrx_amr_strfn) -> the dict of NavierStokes.structure_functions; the same bits on every rank.  Collective."""
+        from . import strfn as _s
+        return _s.level_structure(lib().iamrx_amr_strfn, self.h, self.geom0, pmax, rmax)
 
     def histogram(self, names, nbins=64, range=None):
         """composite histograms and PDFs of named fields (include/iamrx.h: iamrx_amr_histogram; pdf.py): level l counts the cells level

@@ -1278,6 +1278,34 @@ int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, f
     IAMRX_CATCH
 }
 
+// ---- structure functions (k_strfn.hip)
+int iamrx_strfn_ncol(int pmax) { return pmax >= 1 && pmax <= STRFN_PMAX ? 1 + pmax + (pmax + 1) / 2 : -1; }
+int iamrx_strfn_nq(void) { return STRFN_NQ; }
+int iamrx_mf_strfn(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean)
+{
+    IAMRX_TRY
+    if (!g || !mf) throw Error("iamrx_mf_strfn: null geometry or array");
+    if (ncomp < 1 || comp < 0 || comp + ncomp > mf->mf.ncomp)
+        throw Error("iamrx_mf_strfn: components " + std::to_string(comp) + " .. " + std::to_string(comp + ncomp - 1) + " outside the array's " + std::to_string(mf->mf.ncomp));
+    std::vector<int> comps(ncomp);
+    for (int q = 0; q < ncomp; ++q) comps[q] = comp + q;
+    strfn_of(to_geom(g), mf->mf, ncomp, comps.data(), pmax, rmax, rcap, out, count, mean);
+    IAMRX_CATCH
+}
+int iamrx_ns_strfn(iamrx_ns ns, int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean)
+{
+    IAMRX_TRY ns->ns->strfn(pmax, rmax, rcap, out, count, mean); IAMRX_CATCH
+}
+int iamrx_strfn_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int pmax, const int rmax[3], int reps, float* ms)
+{
+    IAMRX_TRY
+    if (!g || !mf || !ms || !rmax) throw Error("iamrx_strfn_bench: null argument");
+    int rm[3];
+    strfn_resolve_rmax(to_geom(g), rmax, rm);
+    strfn_bench(to_geom(g), mf->mf, comp, pmax, rm, reps, ms);
+    IAMRX_CATCH
+}
+
 // ---- histograms (k_hist.hip)
 static std::vector<int> hist_comps(const char* who, iamrx_mf mf, int comp, int ncomp)
 {
@@ -1790,6 +1818,10 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
     IAMRX_CATCH
 }
 int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY a->amr->level(0).spectrum(nbins_cap, out, count, nbins); IAMRX_CATCH }
+int iamrx_amr_strfn(iamrx_amr a, int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean)
+{
+    IAMRX_TRY a->amr->level(0).strfn(pmax, rmax, rcap, out, count, mean); IAMRX_CATCH
+}
 int iamrx_amr_histogram(iamrx_amr a, int nnames, const char* const* names, const double* lo, const double* hi, int nbins, long long* counts)
 {
     IAMRX_TRY

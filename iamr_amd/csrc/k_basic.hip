@@ -637,6 +637,70 @@ void mf_mult_ghosts(MultiFab& y, double a, int comp, int nc, int ng)
                        y.type.t[2], ng, comp, nc, a);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- dense image
+constexpr int DENSE_THREADS = 256;
+
+// grid (chunks, local boxes): cell p of the box -> dst[2 * dense index] = (f, 0) (CPLX) or dst[dense index] = f
+template <bool CPLX>
+__global__ void __launch_bounds__(DENSE_THREADS) k_dense_pack(const BoxD* __restrict__ boxes, const FabD* __restrict__ st, int comp, BoxD dom,
+                                                              double* __restrict__ dst)
+{
+    const BoxD b = boxes[blockIdx.y];
+    const FabD s = st[blockIdx.y];
+    const auto sp = s.gp() + (long)comp * s.cs;
+    const int bx = b.len(0), by = b.len(1);
+    const long np = b.npts(), nx = dom.len(0), ny = dom.len(1);
+    for (long p = (long)blockIdx.x * DENSE_THREADS + threadIdx.x; p < np; p += (long)gridDim.x * DENSE_THREADS) {
+        const int i = (int)(p % bx);
+        const long r = p / bx;
+        const int j = (int)(r % by), k = (int)(r / by);
+        const double v = sp[s.off(b.lo[0] + i, b.lo[1] + j, b.lo[2] + k)];
+        const long o = (long)(b.lo[0] - dom.lo[0] + i) + nx * ((long)(b.lo[1] - dom.lo[1] + j) + ny * (long)(b.lo[2] - dom.lo[2] + k));
+        if (CPLX) { dst[2 * o] = v; dst[2 * o + 1] = 0.0; }
+        else dst[o] = v;
+    }
+}
+
+void dense_check_cover(const char* who, const Geometry& g, const Layout& lay)
+{
+    long cells = 0;
+    for (const BoxD& b : lay.boxes) {
+        for (int d = 0; d < 3; ++d)
+            if (b.lo[d] < g.domain.lo[d] || b.hi[d] > g.domain.hi[d]) throw Error(std::string(who) + ": a box of the level reaches outside the domain");
+        cells += b.npts();
+    }
+    if (cells != g.domain.npts())
+        throw Error(std::string(who) + ": the boxes of the level do not cover the domain (" + std::to_string(cells) + " of " + std::to_string(g.domain.npts()) + " cells)");
+}
+
+void dense_pack(const Geometry& g, const MultiFab& S, int comp, double* dst, bool cplx)
+{
+    const Layout& lay = *S.layout;
+    if (lay.nlocal() == 0) return;
+    long big = 1;
+    for (int f = 0; f < lay.nlocal(); ++f) big = std::max(big, lay.lbox(f).npts());
+    const dim3 grid((unsigned)std::min<long>((big + 4 * DENSE_THREADS - 1) / (4 * DENSE_THREADS), 65535), (unsigned)lay.nlocal());
+    hipStream_t s = Context::get().stream;
+    if (cplx) hipLaunchKernelGGL((k_dense_pack<true>), grid, dim3(DENSE_THREADS), 0, s, lay.d_boxes, S.d_tab, comp, g.domain, dst);
+    else hipLaunchKernelGGL((k_dense_pack<false>), grid, dim3(DENSE_THREADS), 0, s, lay.d_boxes, S.d_tab, comp, g.domain, dst);
+}
+
+bool dense_needs_gather(const MultiFab& S)
+{
+    auto& ctx = Context::get();
+    return (ctx.comm ? ctx.comm->nranks : 1) > 1 && !S.layout->replicated;
+}
+
+void dense_gather(const Geometry& g, const MultiFab& S, int comp, double* R)
+{
+    auto& ctx = Context::get();
+    if (!dense_needs_gather(S)) { dense_pack(g, S, comp, R, false); return; }
+    const long N = g.domain.npts();
+    IAMRX_HIP_CHECK(hipMemsetAsync(R, 0, (size_t)N * sizeof(double), ctx.stream));
+    dense_pack(g, S, comp, R, false);
+    ctx.comm->allreduce_device(R, (int)N, ReduceOp::Sum, ctx.stream);
+}
+
 // slab levels (mf.h): every y-plane of dst takes the single y-plane of src
 void slab_duplicate(MultiFab& dst, const MultiFab& src)
 {

@@ -5,7 +5,8 @@
 // kappa = sqrt((m_x r_x)^2 + (m_y r_y)^2 + (m_z r_z)^2), r_d = L_max / L_d; P(s) = sum over the modes of shell s of |F(m)|^2.
 //
 // One component at a time through one complex work array W (16 B per cell, x fastest) from the arena:
-//   k_spec_pack    valid cells of every local box -> (f, 0) at the cell's place in the level's index space (ghost cells are never read)
+//   k_dense_pack   (k_basic.hip, shared with k_strfn.hip) valid cells of every local box -> (f, 0) at the cell's place in the level's
+//                  index space (ghost cells are never read)
 //   k_spec_fft<X>  batched 1-D transforms staged in LDS, in place: radix-2 decimation in time, two stages at a time through registers, the
 //                  bit reversal done by the load into LDS, twiddles from a table the host makes with libm (extended precision) on an octant-reduced angle, no recurrence.
 //                    X = true   a workgroup owns whole contiguous x pencils (LDS: pencil after pencil, one pad element per 32)
@@ -37,27 +38,7 @@ constexpr int SPEC_MAXWG = 1024;         // workgroups (= slots per shell) of k_
 int ilog2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
 
 // ---------------------------------------------------------------------------------------------------------------- pack
-// grid (chunks, local boxes): cell p of the box -> W[dense index] = (f, 0) (CPLX) or R[dense index] = f
-template <bool CPLX>
-__global__ void __launch_bounds__(SPEC_THREADS) k_spec_pack(const BoxD* __restrict__ boxes, const FabD* __restrict__ st, int comp, BoxD dom,
-                                                            double* __restrict__ dst)
-{
-    const BoxD b = boxes[blockIdx.y];
-    const FabD s = st[blockIdx.y];
-    const auto sp = s.gp() + (long)comp * s.cs;
-    const int bx = b.len(0), by = b.len(1);
-    const long np = b.npts(), nx = dom.len(0), ny = dom.len(1);
-    for (long p = (long)blockIdx.x * SPEC_THREADS + threadIdx.x; p < np; p += (long)gridDim.x * SPEC_THREADS) {
-        const int i = (int)(p % bx);
-        const long r = p / bx;
-        const int j = (int)(r % by), k = (int)(r / by);
-        const double v = sp[s.off(b.lo[0] + i, b.lo[1] + j, b.lo[2] + k)];
-        const long o = (long)(b.lo[0] - dom.lo[0] + i) + nx * ((long)(b.lo[1] - dom.lo[1] + j) + ny * (long)(b.lo[2] - dom.lo[2] + k));
-        if (CPLX) { dst[2 * o] = v; dst[2 * o + 1] = 0.0; }
-        else dst[o] = v;
-    }
-}
-
+// (the pack itself and the gather of several ranks: dense_pack / dense_gather, k_basic.hip, shared with k_strfn.hip)
 // the summed real array of several ranks -> (f, 0)
 __global__ void __launch_bounds__(SPEC_THREADS) k_spec_expand(const double* __restrict__ R, double2* __restrict__ W, long N)
 {
@@ -301,22 +282,9 @@ void spec_tables(SpecPlan& p)
 void spec_pack(const SpecPlan& p, const Geometry& g, const MultiFab& S, int comp, double2* W)
 {
     auto& ctx = Context::get();
-    const Layout& lay = *S.layout;
-    const int nranks = ctx.comm ? ctx.comm->nranks : 1;
-    const bool gather = nranks > 1 && !lay.replicated;
-    long big = 1;
-    for (int f = 0; f < lay.nlocal(); ++f) big = std::max(big, lay.lbox(f).npts());
-    const dim3 grid((unsigned)std::min<long>((big + 4 * SPEC_THREADS - 1) / (4 * SPEC_THREADS), 65535), (unsigned)std::max(lay.nlocal(), 1));
-    if (!gather) {
-        if (lay.nlocal() > 0)
-            hipLaunchKernelGGL((k_spec_pack<true>), grid, dim3(SPEC_THREADS), 0, ctx.stream, lay.d_boxes, S.d_tab, comp, g.domain, (double*)W);
-        return;
-    }
+    if (!dense_needs_gather(S)) { dense_pack(g, S, comp, (double*)W, true); return; }
     double* R = (double*)ctx.alloc((size_t)p.N * sizeof(double));
-    IAMRX_HIP_CHECK(hipMemsetAsync(R, 0, (size_t)p.N * sizeof(double), ctx.stream));
-    if (lay.nlocal() > 0)
-        hipLaunchKernelGGL((k_spec_pack<false>), grid, dim3(SPEC_THREADS), 0, ctx.stream, lay.d_boxes, S.d_tab, comp, g.domain, R);
-    ctx.comm->allreduce_device(R, (int)p.N, ReduceOp::Sum, ctx.stream);
+    dense_gather(g, S, comp, R);
     hipLaunchKernelGGL(k_spec_expand, dim3((unsigned)std::min<long>((p.N + 4 * SPEC_THREADS - 1) / (4 * SPEC_THREADS), 65535)), dim3(SPEC_THREADS), 0,
                        ctx.stream, R, W, p.N);
     ctx.free(R);
@@ -350,18 +318,6 @@ void spec_bin(const SpecPlan& p, const double2* W, T* slots, double scale, T* ou
     hipLaunchKernelGGL((k_spec_finish<T>), dim3((unsigned)((p.sh.nbins + 3) / 4)), dim3(SPEC_THREADS), 0, ctx.stream, slots, p.nwg, p.sh.nbins, scale, out);
 }
 
-void spec_check_cover(const Geometry& g, const Layout& lay)
-{
-    long cells = 0;
-    for (const BoxD& b : lay.boxes) {
-        for (int d = 0; d < 3; ++d)
-            if (b.lo[d] < g.domain.lo[d] || b.hi[d] > g.domain.hi[d]) throw Error("spectrum: a box of the level reaches outside the domain");
-        cells += b.npts();
-    }
-    if (cells != g.domain.npts())
-        throw Error("spectrum: the boxes of the level do not cover the domain (" + std::to_string(cells) + " of " + std::to_string(g.domain.npts()) + " cells)");
-}
-
 }  // namespace
 
 int spectrum_nbins(const Geometry& g)
@@ -393,7 +349,7 @@ void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* c
     if (!S.type.cell()) throw Error("spectrum: the array is not cell-centred");
     for (int q = 0; q < nq; ++q)
         if (comps[q] < 0 || comps[q] >= S.ncomp) throw Error("spectrum: component " + std::to_string(comps[q]) + " outside 0 .. " + std::to_string(S.ncomp - 1));
-    spec_check_cover(g, *S.layout);
+    dense_check_cover("spectrum", g, *S.layout);
     auto& ctx = Context::get();
     SpecPlan p = spec_plan(g, nbins);
     spec_tables(p);
@@ -429,7 +385,7 @@ void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* c
 void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, float* ms)
 {
     const int nbins = spectrum_nbins(g);
-    spec_check_cover(g, *S.layout);
+    dense_check_cover("spectrum", g, *S.layout);
     IAMRX_ASSERT(S.type.cell() && comp >= 0 && comp < S.ncomp && reps >= 1);
     auto& ctx = Context::get();
     SpecPlan p = spec_plan(g, nbins);

@@ -46,6 +46,16 @@ void mf_add_scalar(MultiFab& y, double a, int comp, int nc, int ng);
 void mf_mult(MultiFab& y, double a, int comp, int nc, int ng);
 // the same on the ng ghost layers only (the valid region is not touched): one launch over the shell of every box
 void mf_mult_ghosts(MultiFab& y, double a, int comp, int nc, int ng);
+// ---- the dense image of a level (k_basic.hip): what the spectra and the structure functions work on ----
+// throws "<who>: ..." unless the boxes of the layout lie inside the domain of g and hold as many cells as it
+void dense_check_cover(const char* who, const Geometry& g, const Layout& lay);
+// the valid cells of THIS rank's boxes of component comp of a cell-centred array -> their place in the index space of the domain of g
+// (x fastest; ghost cells are never read): dst[o] = f, or with cplx dst[2 o] = f, dst[2 o + 1] = 0.  Cells of other ranks are not written.
+void dense_pack(const Geometry& g, const MultiFab& S, int comp, double* dst, bool cplx);
+// the whole field as a real array on every rank.  One rank (or a replicated layout): dense_pack.  Several: every rank packs its boxes
+// into the zeroed array and the arrays are summed through the communicator (exact: a cell has one owner) -- a gather, collective.
+void dense_gather(const Geometry& g, const MultiFab& S, int comp, double* R);
+bool dense_needs_gather(const MultiFab& S);      // several ranks and a layout that is not replicated
 
 // ---- k_stats.hip: on-the-fly velocity statistics (NS_average.cpp, NS_derive.cpp:11-45) ------
 // avg(0..2) += dt_avg * vel; fluct: avg(3..5) += dt_avg * (vel - avg(0..2) / t_sum)^2 with the updated avg(0..2); vel = S(vcomp..)
@@ -79,6 +89,27 @@ void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* c
 // measurement aid (tools/bench_spectrum.py): reps times the five passes of one component -- pack, x, y, z, shell sums -- with an event
 // between them; ms[5 * r + p] = milliseconds of pass p in repeat r
 void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, float* ms);
+
+// ---- k_strfn.hip: structure functions and two-point correlations along the axes --------------
+// the components the level and hierarchy entries take: u, v, w and the first tracer
+constexpr int STRFN_NQ = 4;
+constexpr int STRFN_PMAX = 8;               // moments 1 .. pmax <= 8
+constexpr int STRFN_MAX_EXTENT = 1024;      // cells along an axis that is not skipped
+int strfn_ncol(int pmax);                   // 1 + pmax + ceil(pmax / 2); throws on pmax outside 1 .. STRFN_PMAX
+// the separations of a call: rmax[d] = -1 -> the largest allowed (n_d / 2 periodic, n_d - 1 otherwise), 0 -> the axis is skipped;
+// throws, naming the axis, on a larger request, on one below -1 and on an extent above STRFN_MAX_EXTENT of an axis that is not skipped
+void strfn_resolve_rmax(const Geometry& g, const int rmax[3], int out[3]);
+// pairs of axis d at separation r (include/iamrx.h): N periodic, (n_d - r) N / n_d otherwise
+long long strfn_count(const Geometry& g, int d, int r);
+// out[((d * nq + c) * ncol + col) * rcap + r] = column col of component comps[c] of S (cell-centred; its boxes tile the domain of g; ghost
+// cells are never read) along axis d at separation r <= rmax[d] (resolved, <= rcap - 1), zero beyond; mean[c] (or null) = <f_c>.  One
+// component at a time through one dense real array from the arena (dense_gather: the only step that sees boxes or ranks), one pair
+// launch per axis; sums in a fixed order, no floating-point atomics: the same call gives the same bits for any box layout and any
+// number of ranks.  Collective on several ranks.
+void strfn_compute(const Geometry& g, const MultiFab& S, int nq, const int* comps, int pmax, const int rmax[3], int rcap, double* out, double* mean);
+// measurement aid (tools/bench_strfn.py): reps times the four passes of one component -- pack, x, y, z (each pair launch with its finish
+// kernel) -- with an event between them; ms[4 * r + p] = milliseconds of pass p in repeat r (0 for a skipped axis)
+void strfn_bench(const Geometry& g, const MultiFab& S, int comp, int pmax, const int rmax[3], int reps, float* ms);
 
 // ---- k_hist.hip: histograms of cell-centred components (integer counts, exact) ----------------
 // The binning rule per column (lo < hi finite, inv = nbins / (hi - lo) in double): NaN -> slot nan, v < lo -> below, v > hi -> above,

@@ -297,6 +297,29 @@ void NavierStokes::spectrum(int cap, double* out, long* count, int* nbins)
     spectrum_of(g, S[inew], SPECTRUM_NQ, comps, cap, out, count, nbins);
 }
 
+// the common part of the three C entries: every check that needs no device first, the exact counts from their formula, then the kernels
+void strfn_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int pmax, const int rmax[3], int rcap, double* out, long long* count,
+              double* mean)
+{
+    (void)strfn_ncol(pmax);                 // throws on a pmax out of range
+    if (!rmax) throw Error("strfn: null rmax");
+    int rm[3];
+    strfn_resolve_rmax(g, rmax, rm);
+    const int need = 1 + std::max(rm[0], std::max(rm[1], rm[2]));
+    if (rcap < need) throw Error("strfn: rcap = " + std::to_string(rcap) + " too small, the separations 0 .. " + std::to_string(need - 1) + " need " + std::to_string(need));
+    if (!out) throw Error("strfn: null output array");
+    strfn_compute(g, S, nq, comps, pmax, rm, rcap, out, mean);
+    if (count)
+        for (int d = 0; d < 3; ++d)
+            for (int r = 0; r < rcap; ++r) count[(size_t)d * rcap + r] = rm[d] > 0 && r <= rm[d] ? strfn_count(g, d, r) : 0;
+}
+
+void NavierStokes::strfn(int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean)
+{
+    const int comps[STRFN_NQ] = {Xvel, Yvel, Zvel, Tracer};
+    strfn_of(g, S[inew], STRFN_NQ, comps, pmax, rmax, rcap, out, count, mean);
+}
+
 // FillPatch: copy the valid data, same-level + periodic ghost fill, then the physical-BC fill
 // (StateDataPhysBCFunct: FilccCell rules + the ext_dir functors of NS_bcfill.H).  On a refined level: FillPatchTwoLevels with the
 // coarse level's data interpolated in time (amr.hip); src must be the level's old or new State_Type data.

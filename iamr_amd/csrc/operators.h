@@ -199,6 +199,10 @@ private:
 
 // *nbins = spectrum_nbins(g) first, then the capacity check, then spectrum_compute (kernels.h)
 void spectrum_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int cap, double* out, long* count, int* nbins);
+// the common part of the three structure-function entries: pmax, the separations (strfn_resolve_rmax) and the capacity are checked by
+// name, count[d * rcap + r] (or null) is filled from strfn_count, then strfn_compute (kernels.h)
+void strfn_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int pmax, const int rmax[3], int rcap, double* out, long long* count,
+              double* mean);
 
 class NavierStokes;
 // sync residual of a level projection (Hydro::NodalProjector::computeSyncResidualCoarse / Fine): crse_side: on the nodes of the level
@@ -333,6 +337,10 @@ public:
     // columns, count[s] (or null) the modes of shell s.  *nbins is set before the capacity is checked.  Collective; every rank receives the
     // result.
     void spectrum(int cap, double* out, long* count, int* nbins);
+    // structure functions and two-point correlations along the axes of u, v, w and the first tracer of the new-time state (k_strfn.hip):
+    // out[((d * STRFN_NQ + c) * ncol + col) * rcap + r], count[d * rcap + r] and mean[c] (either may be null).  Collective; every rank
+    // receives the result.
+    void strfn(int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean);
     // histograms of named fields of the new-time data (k_hist.hip; the binning rule: kernels.h; the names: those of integrate; anything
     // else is an error that lists the known names).  histogram: counts[q * (nbins + 3) + s], s < nbins the bins, then below, above, nan;
     // histogram2: counts[bx * nby + by], then `outside`.  Collective; every rank receives the result.

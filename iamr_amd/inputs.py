@@ -20,6 +20,9 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   ns.spectrum_interval (-1: off) / ns.spectrum_file ("spec"): this library's own keys for the shell-summed spectra of level 0
   (iamr_amd/spectrum.py), carried under "spectrum"; an interval > 0 needs a fully periodic three-dimensional domain whose extents are
   powers of two in 4 .. 1024,
+  ns.strfn_interval (-1: off) / ns.strfn_pmax (4; 1 .. 8) / ns.strfn_rmax (one integer or three; -1: the largest separation of the axis, 0:
+  skip it) / ns.strfn_file ("sf"): this library's own keys for the structure functions and two-point correlations of level 0 along the
+  axes (iamr_amd/strfn.py), carried under "strfn"; an interval > 0 needs a three-dimensional run, walls and any extents <= 1024 allowed,
   ns.pdf_interval (-1: off) / ns.pdf_vars (field names, required with an interval > 0) / ns.pdf_nbins (64) / ns.pdf_range (two numbers per
   name; absent: each field's minimum and maximum at each output) / ns.pdf_file ("pdf"): this library's own keys for the histograms and
   PDFs of iamr_amd/pdf.py, carried under "pdf",
@@ -533,6 +536,23 @@ class Inputs:
                 if not extent_ok(n[d]):
                     raise ValueError(f"inputs: ns.spectrum_interval > 0 needs extents that are powers of two in 4 .. 1024, amr.n_cell has "
                                      f"n_{'xyz'[d]} = {n[d]}")
+        # structure functions and two-point correlations along the axes (this library's own keys): every strfn_interval-th level-0 step and
+        # once for the initial data, of level 0; strfn_rmax: one integer for all axes or three (-1: the largest allowed, 0: skip the axis)
+        strfn = dict(interval=self.integer("ns.strfn_interval", -1), pmax=self.integer("ns.strfn_pmax", 4),
+                     rmax=[int(v) for v in self._get("ns.strfn_rmax")] if self.has("ns.strfn_rmax") else [-1], file=self.string("ns.strfn_file", "sf"))
+        from .strfn import check_request, resolve_rmax
+        try:
+            strfn["pmax"], strfn["rmax"] = check_request(strfn["pmax"], strfn["rmax"])
+        except ValueError as e:
+            raise ValueError("inputs: ns.strfn_pmax / ns.strfn_rmax: " + str(e)) from None
+        if strfn["interval"] > 0:
+            if slab:
+                raise NotImplementedError("inputs: ns.strfn_interval > 0 in a two-dimensional run: the structure functions are three-dimensional only "
+                                          "(the slab's thickness direction has two cells)")
+            try:
+                resolve_rmax(n, per, strfn["rmax"])
+            except ValueError as e:
+                raise ValueError("inputs: ns.strfn_rmax against amr.n_cell and geometry.is_periodic: " + str(e)) from None
         # histograms / PDFs (this library's own keys): every pdf_interval-th level-0 step and once for the initial data, of the fields named
         # in pdf_vars; pdf_range: two numbers per name, absent: each field's minimum and maximum at each output
         pdf = dict(interval=self.integer("ns.pdf_interval", -1), vars=[w for v in (self._get("ns.pdf_vars") if self.has("ns.pdf_vars") else []) for w in v.split()],
@@ -574,7 +594,7 @@ class Inputs:
                     if v in VELGRAD_NAMES and v not in VELGRAD_NAMES_2D:
                         raise NotImplementedError(f"inputs: {key} names '{v}' in a two-dimensional run: of the velocity-gradient fields a slab "
                                                   f"knows {' '.join(VELGRAD_NAMES_2D)}")
-        out = dict(profile=profile, spectrum=spectrum, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
+        out = dict(profile=profile, spectrum=spectrum, strfn=strfn, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
                    max_step=self.integer("max_step", -1), stop_time=self.real("stop_time", -1.0),
                    plot_int=self.integer("amr.plot_int", -1), plot_file=self.string("amr.plot_file", "plt"), plot_vars=self.name_list("amr.plot_vars", "ALL"),
                    derive_plot_vars=dpv, fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,

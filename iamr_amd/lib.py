@@ -508,6 +508,14 @@ def mf_spectrum(geom, mf, comp=0, ncomp=1):
     return _s.mf_spectrum(geom, mf, comp, ncomp)
 
 
+def mf_structure(geom, mf, comp=0, ncomp=1, pmax=4, rmax=None):
+    """structure functions and two-point correlations along the axes of components comp .. comp + ncomp - 1 of a cell-centred MultiFab
+    whose boxes tile the domain of geom (include/iamrx.h: iamrx_mf_strfn) -> the raw dict of strfn.raw_dict: "avg" (3, ncomp, ncol,
+    rcap), "count" (3, rcap) int64, "mean" (ncomp,), "r", "dx", "n", "L", "periodic", "pmax", "rmax".  Collective."""
+    from . import strfn as _s
+    return _s.mf_structure(geom, mf, comp, ncomp, pmax, rmax)
+
+
 def mf_histogram(mf, comp=0, ncomp=1, nbins=64, range=None, cov=None, weight=1):
     """exact histograms of components comp .. comp + ncomp - 1 of a cell-centred MultiFab over the valid cells where cov (a cell array
     on the same layout, or None) is zero (include/iamrx.h: iamrx_mf_histogram) -> int64 (ncomp, nbins + 3): the bins, then below,

@@ -366,6 +366,15 @@ class NavierStokes:
         from . import spectrum as _s
         return _s.level_spectrum(lib().iamrx_ns_spectrum, self.h, self.geom)
 
+    def structure_functions(self, pmax=4, rmax=None):
+        """structure functions and two-point correlations of u, v, w and the first tracer of the new-time state along the axes, with or
+        without walls (include/iamrx.h: iamrx_ns_strfn) -> the dict of strfn.derive: the raw "avg" (3, 4, ncol, rcap), "count", "mean",
+        "r", "dx", "n", "L", "periodic", and per axis "SL", "ST", "Sc" (and "...abs"), "RL", "RT", "f", "g", "integral_scale",
+        "taylor_scale".  rmax: None the largest separation of every axis, one integer or three (0 skips an axis).  The same bits on every
+        rank.  Collective."""
+        from . import strfn as _s
+        return _s.level_structure(lib().iamrx_ns_strfn, self.h, self.geom, pmax, rmax)
+
     def histogram(self, names, nbins=64, range=None):
         """histograms and PDFs of named fields of this level (include/iamrx.h: iamrx_ns_histogram; pdf.py: the names, the binning rule)
         -> dict with "names", "range", "edges", "counts" (int64), "below", "above", "nan", "total", "pdf", one row per name.  range: one

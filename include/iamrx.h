@@ -642,6 +642,38 @@ int iamrx_ns_spectrum(iamrx_ns ns, int nbins_cap, double* out, long* count, int*
 /* measurement aid (tools/bench_spectrum.py): reps times the five passes of one component (pack, x, y, z transform, shell sums) with an
  * event between them; ms[5 * r + p] = milliseconds of pass p in repeat r.  Nothing is read back. */
 int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, float* ms);
+/* Structure functions and two-point correlations along the axes (this library's own diagnostic, no upstream counterpart; k_strfn.hip).
+ * Unlike the spectra they are defined with walls and on extents that are not powers of two.  For a cell-centred component f on a level
+ * whose boxes tile the domain, n = (n_x, n_y, n_z) cells, N = n_x n_y n_z, an axis d and an integer separation r in cells:
+ *   pairs        periodic axis: x and x + r e_d with wrap-around, for all N cells x: count(d, r) = N, also for r = n_d / 2, where every
+ *                unordered pair is met twice.  Non-periodic axis: only pairs inside the domain, no wrap, no ghost cell:
+ *                count(d, r) = (n_d - r) N / n_d;
+ *   separations  r = 0 .. rmax_d.  rmax_d = -1: the largest allowed value, n_d / 2 on a periodic axis and n_d - 1 otherwise;
+ *                rmax_d = 0: the axis is skipped, nothing is launched for it; a larger request is an error that names the axis;
+ *   columns      with delta = f(x + r e_d) - f(x), every column a sum over the pairs divided by count(d, r):
+ *                column 0: R = <f(x) f(x + r e_d)>; columns 1 .. pmax: <delta^p>, signed; then one column for each odd p <= pmax:
+ *                <|delta|^p>.  1 <= pmax <= 8, ncol = 1 + pmax + ceil(pmax / 2) (iamrx_strfn_ncol; -1 for a pmax out of range).
+ *                Powers by successive multiplication in double;
+ *   mean         mean[c] = <f_c> over the N cells;
+ *   count        exact integers from the formula above (no kernel forms them);
+ *   extents      n_d <= 1024 on an axis that is not skipped; any extent, a power of two or not (an extent of 1 has rmax_d = 0).
+ * iamrx_strfn_nq: the components of the level and hierarchy entries, 4: u, v, w and the first tracer of the new-time state.
+ * iamrx_mf_strfn: components comp + c (c < ncomp) of a caller-owned cell-centred array; out[((d * ncomp + c) * ncol + col) * rcap + r],
+ * zero for r > rmax_d; count[d * rcap + r] (zero for r > rmax_d) and mean[ncomp] may be NULL; rcap >= 1 + the largest resolved rmax_d.
+ * iamrx_ns_strfn: the four components of the level's new-time state (ncomp = 4 in the indexing above).
+ * All of them: the valid cells are packed into one dense real array of 8 N bytes from the library's arena (ghost cells are never
+ * read), one component at a time; one launch per axis stages pencils in LDS and forms every separation from there; sums in a fixed
+ * order without floating-point atomics: the same call gives the same bits, for any way the level is cut into boxes and any number of
+ * ranks.  Collective on several ranks: the field is gathered on every rank as for the spectra (it does not scale with the ranks).
+ * Error, by name: an array that is not cell-centred; a bad component range; boxes that do not tile the domain; pmax outside 1 .. 8;
+ * rmax_d below -1 or beyond the axis's limit; rcap too small; an extent above 1024 on an axis that is not skipped. */
+int iamrx_strfn_ncol(int pmax);
+int iamrx_strfn_nq(void);
+int iamrx_mf_strfn(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean);
+int iamrx_ns_strfn(iamrx_ns ns, int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean);
+/* measurement aid (tools/bench_strfn.py): reps times the four passes of one component (pack, then the pair launch of x, y and z, each
+ * with its finish kernel) with an event between them; ms[4 * r + p] = milliseconds of pass p in repeat r.  Nothing is read back. */
+int iamrx_strfn_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int pmax, const int rmax[3], int reps, float* ms);
 /* Histograms of cell-centred fields: the counts a probability density function is made of (this library's own diagnostic, no upstream
  * counterpart; k_hist.hip; iamr_amd/pdf.py forms the PDFs).  The counts are integers and exact: the same bits on every call, for every
  * way the level is cut into boxes and for every number of ranks.  The binning rule, per column:
@@ -865,6 +897,8 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
 /* The spectra of iamrx_ns_spectrum on LEVEL 0 of the hierarchy: after avgDown its covered cells hold the average of the finer data (the
  * role of finestLevel = 0 in derivespect-inputs).  Spectra on finer levels and composite spectra are not built. */
 int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins);
+/* The structure functions of iamrx_ns_strfn on LEVEL 0 of the hierarchy, exactly as iamrx_amr_spectrum takes its level. */
+int iamrx_amr_strfn(iamrx_amr a, int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean);
 /* Composite histograms of the hierarchy (the rule, the names and the layout of counts: iamrx_mf_histogram / iamrx_ns_histogram above).  Level l
  * counts the cells that level l + 1 does not cover, each with the weight 8^(finest - l): the slots are in units of finest-level cell
  * volumes, and all slots of a column together sum to cells(level 0) * 8^finest.  Covered cells are skipped, not multiplied by zero.
