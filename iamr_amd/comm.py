@@ -4,12 +4,49 @@ init_rccl_from_torch(dist): production transport -- RCCL inside libiamrx.so; tor
 broadcast the 128-byte RCCL unique id.
 init_gloo_callback(dist): test transport -- torch.distributed (gloo) send/recv/all_reduce on host buffers driven
 from the library through C callbacks; lets two ranks share one GPU.
-Call after lib.init() and before creating any Layout."""
+Call after lib.init() and before creating any Layout.
+start(rank, world, ...) / stop(): the whole start-up of one rank of a run -- process group, device, library, transport -- and its end."""
 import ctypes as C
 import numpy as np
 from .lib import lib, IamrxError
 
 _keep = []
+
+
+def start(rank, world, local_rank=0, transport="", timeout_s=None):
+    """one rank of `world`: torch.distributed's process group (world > 1), the library on its device, the library's communicator.
+    transport "gloo": host-staged transport (init_gloo_callback), every rank on device 0 -- several ranks on one GPU, where RCCL cannot
+    connect two ranks; "": nccl + RCCL, rank r on GPU local_rank.  timeout_s (seconds; None: torch's default): how long a collective
+    waits for a rank that never calls it.  The rendezvous is torch's (MASTER_ADDR / MASTER_PORT of the environment)."""
+    from . import lib as L
+    if transport not in ("", "gloo"):
+        raise ValueError(f"IAMRX_RUN_TRANSPORT={transport!r}: only 'gloo' (or unset: RCCL) is known")
+    if world > 1:
+        import torch.distributed as dist
+        from datetime import timedelta
+        kw = {"timeout": timedelta(seconds=float(timeout_s))} if timeout_s is not None else {}
+        if transport == "gloo":
+            local_rank = 0
+            dist.init_process_group("gloo", rank=rank, world_size=world, **kw)
+        else:
+            import torch
+            torch.cuda.set_device(local_rank)
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank), **kw)
+    L.init(local_rank)
+    if world > 1:
+        if transport == "gloo":
+            init_gloo_callback(dist)
+        else:
+            init_rccl_from_torch(dist)
+
+
+def stop():
+    """the end of what start began: a barrier, then the process group goes (nothing where none is up: a one-rank run)"""
+    import sys
+    dist = sys.modules.get("torch.distributed")          # (a one-rank run never imported it)
+    if dist is not None and dist.is_available() and dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
 
 
 def _check(rc):

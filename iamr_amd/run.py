@@ -467,40 +467,19 @@ def main(argv, observe=None):
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    from . import lib
+    from . import comm, lib
     from . import ns as N
-    # IAMRX_RUN_TRANSPORT=gloo: host-staged transport (comm.init_gloo_callback), every rank on device 0 -- several ranks on one GPU, where
-    # RCCL cannot connect two ranks; unset: nccl + RCCL, rank r on GPU LOCAL_RANK
-    transport = os.environ.get("IAMRX_RUN_TRANSPORT", "")
-    if transport not in ("", "gloo"):
-        raise ValueError(f"IAMRX_RUN_TRANSPORT={transport!r}: only 'gloo' (or unset: RCCL) is known")
-    if world > 1:
-        import torch.distributed as dist
-        from datetime import timedelta
-        # IAMRX_RUN_TIMEOUT (seconds; unset: torch's default): how long a collective waits for a rank that never calls it
-        kw = {"timeout": timedelta(seconds=float(os.environ["IAMRX_RUN_TIMEOUT"]))} if os.environ.get("IAMRX_RUN_TIMEOUT") else {}
-        if transport == "gloo":
-            local_rank = 0
-            dist.init_process_group("gloo", rank=rank, world_size=world, **kw)
-        else:
-            import torch
-            torch.cuda.set_device(local_rank)
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank), **kw)
-    lib.init(local_rank)
-    if world > 1:
-        from . import comm
-        if transport == "gloo":
-            comm.init_gloo_callback(dist)
-        else:
-            comm.init_rccl_from_torch(dist)
+    # IAMRX_RUN_TRANSPORT=gloo: host-staged transport, every rank on device 0 -- several ranks on one GPU, where RCCL cannot connect two
+    # ranks; unset: nccl + RCCL, rank r on GPU LOCAL_RANK.  IAMRX_RUN_TIMEOUT (seconds; unset: torch's default): how long a collective
+    # waits for a rank that never calls it
+    timeout_s = float(os.environ["IAMRX_RUN_TIMEOUT"]) if os.environ.get("IAMRX_RUN_TIMEOUT") else None
+    comm.start(rank, world, local_rank, os.environ.get("IAMRX_RUN_TRANSPORT", ""), timeout_s)
     pr = inp.problem()
     if pr.get("slab") and world > 1:
         raise NotImplementedError("iamr_amd.run: two-dimensional inputs (run on a y-periodic slab) are single-rank runs")
     hierarchy = bool(pr["fine_boxes"] or pr.get("regrid") or (pr.get("restart") and pr.get("max_level", 0) > 0))
     rc = drive(pr, inp, lib, N, hierarchy, rank, world, observe)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    comm.stop()
     return rc
 
 

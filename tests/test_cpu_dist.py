@@ -10,6 +10,7 @@ import os
 import sys
 import numpy as np
 import pytest
+import ranks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = (16, 8, 8)
@@ -76,15 +77,12 @@ def reference_single_box(orc, N=N):
 
 
 def worker(rank, world, port, out_dir, case="x4"):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    ranks.rank_env(rank, world, port)
     import torch
     import torch.distributed as dist
     import orc
     from iamr_amd import lib
     from test_cpu_abi import host_plan
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     L = orc.lib()
     N, BOXES, OWNERS = layout(case)
@@ -166,13 +164,8 @@ def worker(rank, world, port, out_dir, case="x4"):
 
 
 def test_two_rank_gloo_halo_exchange_matches_single_rank(orc, tmp_path):
-    import torch.multiprocessing as mp
     ref = reference_single_box(orc)
-    import socket
-    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:        # a free port (a pid-derived one can collide with a lingering socket)
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    mp.spawn(worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    ranks.spawn(worker, 2, ranks.free_port(), str(tmp_path))
     got = np.zeros(N)
     gmax = []
     for r in range(2):
@@ -189,15 +182,10 @@ def test_eight_rank_gloo_halo_exchange_of_the_bench_layout(orc, tmp_path):
     """the layout of bench.py --gpus 8 (1 x 2 x 4 boxes of 8^3, every rank owns one box, every face of a box towards another rank or its
     periodic image) on an 8-member gloo world: the product's plans, message matching and the all-reduce give the single-box sweep bit
     for bit.  No device is opened: the eight-rank world of the GPU path is bounded by the processes a test may run on the GPU."""
-    import torch.multiprocessing as mp
     n, boxes, owners = layout("bench8")
     assert len(set(owners)) == 8 and n == (8, 16, 32)
     ref = reference_single_box(orc, n)
-    import socket
-    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    mp.spawn(worker, args=(8, port, str(tmp_path), "bench8"), nprocs=8, join=True)
+    ranks.spawn(worker, 8, ranks.free_port(), str(tmp_path), "bench8", max_ranks=8)      # (no device is opened: MAX_RANKS does not bind)
     got = np.zeros(n)
     gmax = []
     for r in range(8):

@@ -6,6 +6,7 @@ import os
 import sys
 import numpy as np
 import pytest
+import ranks
 
 # one box per rank in most cases (nothing to merge); the cases with several boxes per rank say which mode they want ("+merge"), so the
 # whole module runs with IAMRX_COALESCE = 0 in the environment of the rank processes unless a case sets it (tests/conftest.py)
@@ -14,26 +15,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = (16, 16, 16)
 BOXES = [((0, 0, 0), (15, 15, 7)), ((0, 0, 8), (15, 15, 15))]
 NSTEPS = 2
-# rank processes started at once.  The machines that run this suite stop a job in which more than 6 processes have the GPU open; the
-# pytest process holds the device as well, so 4 ranks keep a margin.  An 8-member world runs on the CPU instead
-# (tests/test_cpu_dist.py::test_eight_rank_gloo_halo_exchange_of_the_bench_layout).
-MAX_RANKS = 4
-
-
-def free_port():
-    """a TCP port nobody listens on right now (a port derived from the pid collided with a lingering socket once in round 6: the rendezvous
-    of one test then waited ten minutes inside the driver's time budget)"""
-    import socket
-    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
-        sk.bind(("127.0.0.1", 0))
-        return sk.getsockname()[1]
 
 
 def run(rank, world, port, out_dir, agg, case="tg"):
-    sys.path.insert(0, ROOT)
     global N, BOXES
-    if case.endswith("+merge"):      # the library's default: the level objects work on the boxes a rank owns MERGED (the suite otherwise keeps them)
-        os.environ["IAMRX_COALESCE"] = "1"
+    merge = case.endswith("+merge")  # the library's default: the level objects work on the boxes a rank owns MERGED (the suite otherwise keeps them)
+    if merge:
         case = case[:-6]
     if case == "slabs":              # eight 16^3 boxes, the four of a z-slab owned by one rank: each rank merges its four into one 32 x 32 x 16 box
         N = (32, 32, 32)
@@ -55,16 +42,9 @@ def run(rank, world, port, out_dir, agg, case="tg"):
             BOXES.append(((16 * ix, 16 * iy, 16 * iz), (16 * ix + 15, 16 * iy + 15, 16 * iz + 15)))
     if agg is not None:
         os.environ["IAMRX_MG_AGGLOMERATE_CELLS"] = agg
-    from iamr_amd import lib
+    lib = ranks.start_rank(rank, world, port, merge)
     from iamr_amd import ns as NS
-    lib.init(0)
     if world > 1:
-        import torch.distributed as dist
-        from iamr_amd import comm
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        comm.init_gloo_callback(dist)
         import bench
         bench.transport_selftest(lib, rank, world)   # the check bench.py runs on a freshly initialised transport
     if case == "amr":
@@ -113,9 +93,7 @@ def run(rank, world, port, out_dir, agg, case="tg"):
     sm, sn, sv = ns.stats()
     out["iters"] = np.array([sm.iters, sn.iters, sv.iters])
     np.savez(os.path.join(out_dir, f"w{world}_r{rank}.npz"), **out)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    ranks.stop_rank()
 
 
 def run_amr(rank, world, out_dir):
@@ -123,7 +101,6 @@ def run_amr(rank, world, out_dir):
     from iamr_amd import lib
     from iamr_amd import ns as NS
     from iamr_amd.amr import Amr
-    import torch.distributed as dist
     n0 = 16
     cb = [((i, j, k), (i + 7, j + 7, k + 7)) for k in (0, 8) for j in (0, 8) for i in (0, 8)]
     fb = [((8 + 8 * i, 8 + 8 * j, 8), (15 + 8 * i, 15 + 8 * j, 23)) for j in (0, 1) for i in (0, 1)]
@@ -144,9 +121,7 @@ def run_amr(rank, world, out_dir):
     st, stm = amr.sync_stats()
     out["iters"] = np.array([st.iters, stm.iters])
     np.savez(os.path.join(out_dir, f"amr_w{world}_r{rank}.npz"), **out)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    ranks.stop_rank()
 
 
 def run_amrbench(rank, world, out_dir, nbox):
@@ -166,9 +141,7 @@ def run_amrbench(rank, world, out_dir, nbox):
             blo, bhi, gi = amr.layouts[l].local_box(li)
             out[f"l{l}box{gi}"] = a[1:-1, 1:-1, 1:-1, :]
     np.savez(os.path.join(out_dir, f"amrbench_w{world}_r{rank}.npz"), **out)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    ranks.stop_rank()
 
 
 def run_regrid(rank, world, out_dir):
@@ -177,7 +150,6 @@ def run_regrid(rank, world, out_dir):
     from iamr_amd import lib
     from iamr_amd import ns as NS
     from iamr_amd.amr import Amr
-    import torch.distributed as dist
     n0 = 16
     cb = [((i, j, k), (i + 7, j + 7, k + 7)) for k in (0, 8) for j in (0, 8) for i in (0, 8)]
     fb = [((8, 8, 8), (23, 23, 23))]
@@ -218,20 +190,16 @@ def run_regrid(rank, world, out_dir):
             out["l%dbox_%d_%d_%d" % ((l,) + tuple(blo))] = a[1:-1, 1:-1, 1:-1, :]
     out["nlocal"] = np.array([amr.levels[l].data(0).nlocal() for l in range(amr.nlev)])
     np.savez(os.path.join(out_dir, f"regrid_w{world}_r{rank}.npz"), **out)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    ranks.stop_rank()
 
 
 @pytest.mark.parametrize("nr", [2, 4])
 def test_amr_bench_workload_sharded_over_ranks(tmp_path, nr):
     """the AMR workload of bench.py --gpus nr (base level and refined level each one box per GPU) on nr ranks sharing the GPU: every box of
     both levels, the time steps and the iteration counts of the sync solves equal the run of ONE rank holding the same 2 nr boxes"""
-    import torch.multiprocessing as mp
-    port = free_port()
-    mp.spawn(run, args=(1, port, str(tmp_path), None, f"amrbench{nr}"), nprocs=1, join=True)
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), None, f"amrbench{nr}")
     ref = np.load(os.path.join(str(tmp_path), "amrbench_w1_r0.npz"))
-    mp.spawn(run, args=(nr, free_port(), str(tmp_path), None, f"amrbench{nr}"), nprocs=nr, join=True)
+    ranks.spawn(run, nr, ranks.free_port(), str(tmp_path), None, f"amrbench{nr}")
     seen = set()
     for r in range(nr):
         z = np.load(os.path.join(str(tmp_path), f"amrbench_w{nr}_r{r}.npz"))
@@ -247,11 +215,9 @@ def test_amr_bench_workload_sharded_over_ranks(tmp_path, nr):
 @pytest.mark.parametrize("merge", ["", "+merge"])
 def test_regrid_on_two_ranks_matches_one_rank(tmp_path, merge):
     """Amr::regrid with the levels spread over two ranks: same grids after every regrid, same data, both ranks own boxes of the new level"""
-    import torch.multiprocessing as mp
-    port = free_port()
-    mp.spawn(run, args=(1, port, str(tmp_path), None, "regrid" + merge), nprocs=1, join=True)      # "+merge": level 0 merged per rank (the default mode)
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), None, "regrid" + merge)      # "+merge": level 0 merged per rank (the default mode)
     ref = np.load(os.path.join(str(tmp_path), "regrid_w1_r0.npz"))
-    mp.spawn(run, args=(2, free_port(), str(tmp_path), None, "regrid" + merge), nprocs=2, join=True)
+    ranks.spawn(run, 2, ranks.free_port(), str(tmp_path), None, "regrid" + merge)
     seen = set()
     for r in range(2):
         z = np.load(os.path.join(str(tmp_path), f"regrid_w2_r{r}.npz"))
@@ -268,11 +234,9 @@ def test_regrid_on_two_ranks_matches_one_rank(tmp_path, merge):
 def test_two_level_hierarchy_on_two_ranks(tmp_path):
     """the multi-level time step (subcycling, registers, MAC sync incl. the viscous solves, composite sync projection, multi-level
     initialisation) with the boxes of BOTH levels distributed over two ranks sharing the GPU: every box equals the one-rank result"""
-    import torch.multiprocessing as mp
-    port = free_port()
-    mp.spawn(run, args=(1, port, str(tmp_path), None, "amr"), nprocs=1, join=True)
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), None, "amr")
     ref = np.load(os.path.join(str(tmp_path), "amr_w1_r0.npz"))
-    mp.spawn(run, args=(2, free_port(), str(tmp_path), None, "amr"), nprocs=2, join=True)
+    ranks.spawn(run, 2, ranks.free_port(), str(tmp_path), None, "amr")
     seen = set()
     for r in range(2):
         z = np.load(os.path.join(str(tmp_path), f"amr_w2_r{r}.npz"))
@@ -288,10 +252,8 @@ def test_two_level_hierarchy_on_two_ranks(tmp_path):
 def test_two_ranks_on_one_gpu_match_single_rank(tmp_path, agg):
     """agg: multigrid agglomeration threshold in cells (None: default, every coarse level of this small problem is replicated on
     both ranks; "0": all levels stay distributed; "64": only the 4^3 and 2^3 levels are replicated)"""
-    import torch.multiprocessing as mp
-    port = free_port()
-    mp.spawn(run, args=(1, port, str(tmp_path), agg), nprocs=1, join=True)
-    mp.spawn(run, args=(2, free_port(), str(tmp_path), agg), nprocs=2, join=True)
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), agg)
+    ranks.spawn(run, 2, ranks.free_port(), str(tmp_path), agg)
     ref = np.load(os.path.join(str(tmp_path), "w1_r0.npz"))
     for r in range(2):
         z = np.load(os.path.join(str(tmp_path), f"w2_r{r}.npz"))
@@ -304,10 +266,8 @@ def test_two_ranks_on_one_gpu_match_single_rank(tmp_path, agg):
 def test_a_rank_without_boxes_takes_part_in_the_step(tmp_path):
     """more ranks than boxes (AMReX allows it; coarse AMR levels routinely have fewer grids than ranks): rank 2 owns nothing, launches
     no kernels, but joins every reduction and exchange; ranks 0 and 1 reproduce the 1-rank result"""
-    import torch.multiprocessing as mp
-    port = free_port()
-    mp.spawn(run, args=(1, port, str(tmp_path), None), nprocs=1, join=True)
-    mp.spawn(run, args=(3, free_port(), str(tmp_path), None), nprocs=3, join=True)
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), None)
+    ranks.spawn(run, 3, ranks.free_port(), str(tmp_path), None)
     ref = np.load(os.path.join(str(tmp_path), "w1_r0.npz"))
     idle = np.load(os.path.join(str(tmp_path), "w3_r2.npz"))
     assert not [k for k in idle.files if k.startswith("box")] and np.allclose(idle["dts"], ref["dts"], rtol=1e-10, atol=0)
@@ -323,10 +283,8 @@ def test_ranks_that_merge_their_boxes(tmp_path):
     """the library's default mode (IAMRX_COALESCE = 1) under several ranks: every rank owns four boxes that merge into
     one slab; the merged level objects, their data accessors (the caller's boxes) and the multigrid wrappers on merged boxes against the
     one-rank run, whose eight boxes merge into one box spanning the domain"""
-    import torch.multiprocessing as mp
-    port = free_port()
-    mp.spawn(run, args=(1, port, str(tmp_path), None, "slabs+merge"), nprocs=1, join=True)
-    mp.spawn(run, args=(2, free_port(), str(tmp_path), None, "slabs+merge"), nprocs=2, join=True)
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), None, "slabs+merge")
+    ranks.spawn(run, 2, ranks.free_port(), str(tmp_path), None, "slabs+merge")
     ref = np.load(os.path.join(str(tmp_path), "w1_r0.npz"))
     seen = 0
     for r in range(2):
@@ -345,10 +303,8 @@ def test_rows_that_span_the_domain_sharded_in_y_and_z(tmp_path, nr):
     no ghost cell run on the main stream (HALO_OVERLAP: on by itself where a level has peers); the coarse multigrid levels are agglomerated
     onto one merged box per rank.  Equal to the one-rank run (same kernels on four local boxes) to round-off: the sums of the mean
     removals and dot products are formed rank by rank."""
-    import torch.multiprocessing as mp
-    port = free_port()
-    mp.spawn(run, args=(1, port, str(tmp_path), None, "rows128"), nprocs=1, join=True)
-    mp.spawn(run, args=(nr, free_port(), str(tmp_path), None, "rows128"), nprocs=nr, join=True)
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), None, "rows128")
+    ranks.spawn(run, nr, ranks.free_port(), str(tmp_path), None, "rows128")
     ref = np.load(os.path.join(str(tmp_path), "w1_r0.npz"))
     for r in range(nr):
         z = np.load(os.path.join(str(tmp_path), f"w{nr}_r{r}.npz"))
@@ -360,10 +316,8 @@ def test_rows_that_span_the_domain_sharded_in_y_and_z(tmp_path, nr):
 
 def test_two_ranks_lid_driven_cavity(tmp_path):
     """wall BCs (physical BC fills, Neumann projections, per-component tensor BCs, tracer diffusion) across a rank boundary"""
-    import torch.multiprocessing as mp
-    port = free_port()
-    mp.spawn(run, args=(1, port, str(tmp_path), None, "ldc"), nprocs=1, join=True)
-    mp.spawn(run, args=(2, free_port(), str(tmp_path), None, "ldc"), nprocs=2, join=True)
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), None, "ldc")
+    ranks.spawn(run, 2, ranks.free_port(), str(tmp_path), None, "ldc")
     ref = np.load(os.path.join(str(tmp_path), "w1_r0.npz"))
     for r in range(2):
         z = np.load(os.path.join(str(tmp_path), f"w2_r{r}.npz"))
@@ -376,12 +330,10 @@ def test_two_ranks_lid_driven_cavity(tmp_path):
 def test_four_ranks_stacked_boxes_like_the_bench(tmp_path):
     """bench.py's weak-scaling layout (one box per rank stacked in z, domain 16 x 16 x 64) on 4 ranks sharing the GPU, with the
     default agglomeration threshold and with a threshold that keeps the first coarse level distributed: same result as one rank"""
-    import torch.multiprocessing as mp
-    port = free_port()
-    mp.spawn(run, args=(1, port, str(tmp_path), None, "stack4"), nprocs=1, join=True)
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), None, "stack4")
     ref = np.load(os.path.join(str(tmp_path), "w1_r0.npz"))
     for agg in (None, "1024"):
-        mp.spawn(run, args=(4, free_port(), str(tmp_path), agg, "stack4"), nprocs=4, join=True)
+        ranks.spawn(run, 4, ranks.free_port(), str(tmp_path), agg, "stack4")
         for r in range(4):
             z = np.load(os.path.join(str(tmp_path), f"w4_r{r}.npz"))
             assert np.allclose(z["dts"], ref["dts"], rtol=1e-10, atol=0)
@@ -396,12 +348,10 @@ def test_bench_process_grid_layouts(tmp_path, nr):
     SURVEY 8e) on ranks sharing the GPU over the callback transport: same result as one rank holding all boxes.  At most MAX_RANKS rank
     processes: the 8-box layout runs on 4 ranks that own two boxes each (box q on rank q % 4: every box still has its neighbours in y and
     z on other ranks)"""
-    import torch.multiprocessing as mp
-    port = free_port()
-    mp.spawn(run, args=(1, port, str(tmp_path), None, f"grid{nr}"), nprocs=1, join=True)
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), None, f"grid{nr}")
     ref = np.load(os.path.join(str(tmp_path), "w1_r0.npz"))
-    world = min(nr, MAX_RANKS)
-    mp.spawn(run, args=(world, free_port(), str(tmp_path), None, f"grid{nr}"), nprocs=world, join=True)
+    world = min(nr, ranks.MAX_RANKS)
+    ranks.spawn(run, world, ranks.free_port(), str(tmp_path), None, f"grid{nr}")
     seen = set()
     for r in range(world):
         z = np.load(os.path.join(str(tmp_path), f"w{world}_r{r}.npz"))
@@ -419,7 +369,7 @@ def test_bench_script_multi_rank_path(tmp_path):
     import json
     import subprocess
     env = dict(os.environ, IAMRX_BENCH_TRANSPORT="gloo", MASTER_ADDR="127.0.0.1", IAMRX_BENCH_N="32")     # "--n" would be eaten by torchrun
-    port = free_port()
+    port = ranks.free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
@@ -433,7 +383,7 @@ def test_bench_script_multi_rank_path(tmp_path):
     assert abs(d["value"] - d["config"]["cells"] * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
 
 
-def _rccl_single(rank, out_dir):
+def _rccl_single(rank, world, out_dir):
     sys.path.insert(0, ROOT)
     import ctypes as C
     from iamr_amd import lib
@@ -461,8 +411,7 @@ def test_rccl_transport_single_rank(tmp_path):
     """the RCCL back end itself (dlopen of librccl, ncclGetUniqueId / ncclCommInitRank / ncclAllReduce through the resolved
     symbols) with a 1-rank communicator: every reduction of two time steps goes through ncclAllReduce; same result as the serial
     communicator; the halo-exchange primitive (grouped ncclSend / ncclRecv) is exercised as a loop-back to the own rank."""
-    import torch.multiprocessing as mp
-    mp.spawn(_rccl_single, args=(str(tmp_path),), nprocs=1, join=True)
+    ranks.spawn(_rccl_single, 1, str(tmp_path))
     z = np.load(os.path.join(str(tmp_path), "rccl1.npz"))
     sys.path.insert(0, ROOT)
     from iamr_amd import lib
@@ -477,10 +426,11 @@ def test_rccl_transport_single_rank(tmp_path):
     assert np.array_equal(ns.data(NS.NavierStokes.S_NEW).gather_valid(n), z["S"])
 
 
-def _rccl_pair(rank, out_dir):
+def _rccl_pair(rank, world, out_dir):
     """one process per DEVICE (rank r drives device r): the RCCL transport between two GPUs -- ncclCommInitRank from a unique id handed over
     through a file, the exchange probe, bench.py's transport self-test, then two TaylorGreen steps on one 16 x 16 x 8 box per rank"""
     sys.path.insert(0, ROOT)
+    import ctypes as C
     import time
     from iamr_amd import lib
     from iamr_amd import ns as NS
@@ -524,9 +474,8 @@ def test_rccl_transport_between_two_devices(tmp_path):
                "remain untested on hardware (tests/test_gpu_dist.py::test_rccl_transport_between_two_devices runs as soon as 2 GPUs are visible)")
         print("\n*** " + msg + " ***", file=sys.stderr, flush=True)
         pytest.skip(msg)
-    import torch.multiprocessing as mp
-    mp.spawn(_rccl_pair, args=(str(tmp_path),), nprocs=2, join=True)
-    mp.spawn(run, args=(1, free_port(), str(tmp_path), None), nprocs=1, join=True)      # the same two boxes on one rank
+    ranks.spawn(_rccl_pair, 2, str(tmp_path))
+    ranks.spawn(run, 1, ranks.free_port(), str(tmp_path), None)      # the same two boxes on one rank
     one = np.load(os.path.join(str(tmp_path), "w1_r0.npz"))
     for r in range(2):
         z = np.load(os.path.join(str(tmp_path), f"rccl2_r{r}.npz"))

@@ -1,5 +1,5 @@
-"""GPU: plotfiles, checkpoints and restart of runs on several ranks (ranks sharing the one GPU over the gloo callback transport, the
-harness of tests/test_gpu_dist.py).  Two kinds of comparison: what was WRITTEN against what the ranks HELD is exact (I/O moves doubles);
+"""GPU: plotfiles, checkpoints and restart of runs on several ranks (ranks sharing the one GPU over the gloo callback transport:
+tests/ranks.py).  Two kinds of comparison: what was WRITTEN against what the ranks HELD is exact (I/O moves doubles);
 an N-rank run against a 1-rank run uses the constants tests/test_gpu_dist.py asserts (state within 1e-9 on a single level, 1e-8 for a
 hierarchy or a regridded run, dts at rtol 1e-10) on the state variables only.
 
@@ -7,10 +7,10 @@ One spawn serves several checks: the runs through iamr_amd.run.main are grouped 
 ranks call R.main several times (a fresh rendezvous port per call); the module-scoped fixtures below hold their output directories."""
 import json
 import os
-import sys
 import numpy as np
 import pytest
-from test_gpu_dist import free_port, MAX_RANKS
+import ranks
+from ranks import free_port
 
 pytestmark = [pytest.mark.gpu, pytest.mark.boxes_kept]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,41 +20,20 @@ NSTATE = 5                                               # u v w density tracer:
 
 
 # ---------------------------------------------------------------------------------------------------------------- rank processes
-def _env(rank, world, merge=False):
-    sys.path.insert(0, ROOT)
-    os.environ.update(IAMRX_COALESCE="1" if merge else "0", RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-                      IAMRX_RUN_TRANSPORT="gloo")
-
-
 def main_ranks(rank, world, ports, jobs, log_dir, group):
     """every rank: R.main once per job, the way `python -m iamr_amd.run` under torchrun calls it; stdout of every call is kept"""
-    _env(rank, world)
-    from iamr_amd import run as R
-    for q, (port, argv) in enumerate(zip(ports, jobs)):
-        os.environ["MASTER_PORT"] = str(port)
-        with open(os.path.join(log_dir, f"{group}_job{q}_r{rank}.txt"), "w") as f:
-            keep, sys.stdout = sys.stdout, f
-            try:
-                rc = R.main(argv)
-            finally:
-                sys.stdout = keep
-        assert rc == 0, (q, rc)
+    ranks.rank_env(rank, world)
+    ranks.run_jobs(rank, ports, jobs, log_dir, group)
 
 
 def plot_ranks(rank, world, port, out_dir, owners, merge):
     """case 1: TaylorGreen 16^3 in four 16 x 8 x 8 boxes, viscous, two steps; every rank dumps what level_arrays gives for its boxes, then
     all write the plotfile together.  owners None: run.build deals the boxes (Layout.decompose); a list: that deal, same construction."""
-    _env(rank, world, merge)
-    from iamr_amd import lib, comm
+    lib = ranks.start_rank(rank, world, port, merge)
     from iamr_amd import ns as N
     from iamr_amd import run as R
     from iamr_amd.inputs import Inputs
     from iamr_amd.plotfile import DERIVE_NAMES
-    import torch.distributed as dist
-    lib.init(0)
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    comm.init_gloo_callback(dist)
     inp = Inputs([os.path.join(GOLD, "inputs.3d.taylorgreen")], ["amr.n_cell=16 16 16", "amr.derive_plot_vars=ALL", "ns.vel_visc_coef=0.01"])
     pr = inp.problem()
     pr["max_grid_size"] = (16, 8, 8)
@@ -76,23 +55,16 @@ def plot_ranks(rank, world, port, out_dir, owners, merge):
              owners=np.array(lay.owners), **{f"box{q}": a for q, a in zip(idx, arrs)})
     path = R.write_plot(ns, lay, pr, N, 2, os.path.join(out_dir, "plt"))
     assert path == os.path.join(out_dir, "plt00002")
-    dist.barrier()
-    dist.destroy_process_group()
+    ranks.stop_rank()
 
 
 def allreduce_ranks(rank, world, port, out_dir):
-    _env(rank, world)
-    from iamr_amd import lib, comm
-    lib.init(0)
+    lib = ranks.start_rank(rank, world, port)
     v = np.array([1.0 + rank, 10.0 * (rank + 1), -3.0 * rank, 7.0, float(rank % 2)])
     if world == 1:
         res = [lib.comm_allreduce(v.copy(), op) for op in (0, 1, 2)]
         lib.comm_barrier()
     else:
-        import torch.distributed as dist
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        comm.init_gloo_callback(dist)
         assert lib.comm_rank() == (rank, world)
         res = [lib.comm_allreduce(v.copy(), op) for op in (0, 1, 2)]
         big = lib.comm_allreduce(np.full((40, 11), float(rank + 1)), 0)          # two-dimensional, larger than any solver reduction
@@ -103,15 +75,8 @@ def allreduce_ranks(rank, world, port, out_dir):
             raise AssertionError("a float32 array was accepted")
         except TypeError:
             pass
-        dist.barrier()
-        dist.destroy_process_group()
+    ranks.stop_rank()
     np.savez(os.path.join(out_dir, f"ar_w{world}_r{rank}.npz"), v=v, **{f"op{q}": r for q, r in enumerate(res)})
-
-
-def _spawn(fn, world, *args):
-    import torch.multiprocessing as mp
-    assert world <= MAX_RANKS
-    mp.spawn(fn, args=(world,) + args, nprocs=world, join=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------- reading back
@@ -178,7 +143,7 @@ def _rst(d, tag, frm):
 
 
 def _run_group(d, group, world, jobs):
-    _spawn(main_ranks, world, [free_port() for _ in jobs], jobs, d, group)
+    ranks.spawn(main_ranks, world, [free_port() for _ in jobs], jobs, d, group)
 
 
 @pytest.fixture(scope="module")
@@ -220,13 +185,13 @@ def other_worlds(two_ranks):
 def test_comm_allreduce(tmp_path):
     """case 6: sum / max / min of rank-dependent vectors on 3 ranks equal numpy's (small integers as doubles: exact); one rank: untouched"""
     d = str(tmp_path)
-    _spawn(allreduce_ranks, 3, free_port(), d)
+    ranks.spawn(allreduce_ranks, 3, free_port(), d)
     Z = [np.load(os.path.join(d, f"ar_w3_r{r}.npz")) for r in range(3)]
     V = np.stack([z["v"] for z in Z])
     for z in Z:
         assert np.array_equal(z["op0"], V.sum(axis=0)) and np.array_equal(z["op1"], V.max(axis=0)) and np.array_equal(z["op2"], V.min(axis=0))
         assert np.array_equal(z["op3"], np.full(440, 6.0))
-    _spawn(allreduce_ranks, 1, free_port(), d)
+    ranks.spawn(allreduce_ranks, 1, free_port(), d)
     z = np.load(os.path.join(d, "ar_w1_r0.npz"))
     for q in range(3):
         assert np.array_equal(z[f"op{q}"], z["v"])
@@ -240,7 +205,7 @@ def test_plotfile_equals_what_the_ranks_held(tmp_path, world, owners, merge):
     (two boxes per rank merged inside the level): box list, owners and data still speak the caller's four boxes."""
     from iamr_amd.plotfile import PlotFile, DERIVE_NAMES, state_names
     d = str(tmp_path)
-    _spawn(plot_ranks, world, free_port(), d, owners, merge)
+    ranks.spawn(plot_ranks, world, free_port(), d, owners, merge)
     held = [np.load(os.path.join(d, f"held_r{r}.npz")) for r in range(world)]
     own = [int(o) for o in held[0]["owners"]]
     assert own == ([0, 0, 1, 1] if owners is None else owners)

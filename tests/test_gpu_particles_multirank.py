@@ -1,5 +1,5 @@
-"""GPU: tracer particles on several ranks (ranks sharing the one GPU over the gloo callback transport, the harness of
-tests/test_gpu_multirank_io.py): placement against the global box list, migration, collective errors, counts, particle files and restart.
+"""GPU: tracer particles on several ranks (ranks sharing the one GPU over the gloo callback transport:
+tests/ranks.py): placement against the global box list, migration, collective errors, counts, particle files and restart.
 
 Two parts, ONE spawn per world size (1, 2, 3) serving both:
 A. the container on caller-owned arrays: 16^3 in eight 8^3 boxes dealt round robin, periodic in x and y, walls in z, one patch (coarse
@@ -9,10 +9,10 @@ B. runs through iamr_amd.run.main: against one rank within 1e-8 modulo the perio
    hierarchy run on several ranks; a particle moved with a stale ghost face is off by about 1e-3), restart on the same rank count to the bit.
 A fourth spawn (2 ranks) repeats one run of B in the library's default box mode (IAMRX_COALESCE=1: the level objects merge a rank's boxes)."""
 import os
-import sys
 import numpy as np
 import pytest
-from test_gpu_dist import free_port, MAX_RANKS
+import ranks
+from ranks import free_port
 
 import particles_numpy as pn
 
@@ -20,7 +20,6 @@ pytestmark = [pytest.mark.gpu, pytest.mark.boxes_kept]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 TOL_RUN = 1e-8
-TIMEOUT_S = 120
 
 # ---- part A: geometry ------------------------------------------------------------------------------------------------------------------
 N0 = (16, 16, 16)
@@ -84,13 +83,6 @@ def pushed(xyz, ids, lev):
 
 
 # ---- the rank processes ------------------------------------------------------------------------------------------------------------------
-def _env(rank, world, merge=False):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ.update(IAMRX_COALESCE="1" if merge else "0", RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-                      IAMRX_RUN_TRANSPORT="gloo", IAMRX_RUN_TIMEOUT=str(TIMEOUT_S))
-
-
 def _state(pc, lays):
     """this rank's particles with the GLOBAL box index"""
     d = pc.read()
@@ -177,37 +169,17 @@ def container_checks(rank, world, out_dir):
 
 def group_ranks(rank, world, port_a, ports, jobs, out_dir, group, with_container, merge):
     """one rank of a spawned group: part A (its own process group), then R.main once per job"""
-    _env(rank, world, merge)
-    from iamr_amd import lib
     if with_container:
-        lib.init(0)
-        if world > 1:
-            from datetime import timedelta
-            import torch.distributed as dist
-            from iamr_amd import comm
-            os.environ["MASTER_PORT"] = str(port_a)
-            dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=TIMEOUT_S))
-            comm.init_gloo_callback(dist)
+        ranks.start_rank(rank, world, port_a, merge)
         container_checks(rank, world, out_dir)
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
-    from iamr_amd import run as R
-    for q, (port, argv) in enumerate(zip(ports, jobs)):
-        os.environ["MASTER_PORT"] = str(port)
-        with open(os.path.join(out_dir, f"{group}_job{q}_r{rank}.txt"), "w") as f:
-            hold, sys.stdout = sys.stdout, f
-            try:
-                rc = R.main(argv)
-            finally:
-                sys.stdout = hold
-        assert rc == 0, (q, rc)
+        ranks.stop_rank()
+    else:
+        ranks.rank_env(rank, world, merge=merge)
+    ranks.run_jobs(rank, ports, jobs, out_dir, group)
 
 
-def _spawn(world, jobs, out_dir, group, with_container=True, merge=False):
-    import torch.multiprocessing as mp
-    assert world <= MAX_RANKS
-    mp.spawn(group_ranks, args=(world, free_port(), [free_port() for _ in jobs], jobs, out_dir, group, with_container, merge), nprocs=world, join=True)
+def run_group(world, jobs, out_dir, group, with_container=True, merge=False):
+    ranks.spawn(group_ranks, world, free_port(), [free_port() for _ in jobs], jobs, out_dir, group, with_container, merge)
 
 
 # ---- part B: the runs ----------------------------------------------------------------------------------------------------------------------
@@ -258,7 +230,7 @@ def two_ranks(out_dir):
     single-level run"""
     d = out_dir
     p512, p64 = f"{d}/p512.txt", f"{d}/p64.txt"
-    _spawn(2, [_amr(d, "C", p512), _rst(d, "D", "C", p512, [f"particles.particle_output_file={d}/ascii_D.txt"]), _regrid(d, "2", p64), _single(d, "2", p64)], d, "two")
+    run_group(2, [_amr(d, "C", p512), _rst(d, "D", "C", p512, [f"particles.particle_output_file={d}/ascii_D.txt"]), _regrid(d, "2", p64), _single(d, "2", p64)], d, "two")
     return d
 
 
@@ -266,7 +238,7 @@ def two_ranks(out_dir):
 def one_rank(two_ranks):
     d = two_ranks
     p512, p64 = f"{d}/p512.txt", f"{d}/p64.txt"
-    _spawn(1, [_amr(d, "A", p512), _rst(d, "E", "C", p512), _regrid(d, "1", p64), _single(d, "1", p64)], d, "one")
+    run_group(1, [_amr(d, "A", p512), _rst(d, "E", "C", p512), _regrid(d, "1", p64), _single(d, "1", p64)], d, "one")
     return d
 
 
@@ -274,7 +246,7 @@ def one_rank(two_ranks):
 def three_ranks(one_rank):
     d = one_rank
     p512 = f"{d}/p512.txt"
-    _spawn(3, [_amr(d, "B", p512), _rst(d, "F", "C", p512)], d, "three")
+    run_group(3, [_amr(d, "B", p512), _rst(d, "F", "C", p512)], d, "three")
     return d
 
 
@@ -507,6 +479,6 @@ def test_merged_boxes(all_worlds):
     """check 6: the two-rank hierarchy run again in the library's default box mode (the level objects merge the boxes a rank owns, so the
     particles' boxes are not the callers'): ids and positions modulo the period against the one-rank run"""
     d = all_worlds
-    _spawn(2, [_amr(d, "M", f"{d}/p512.txt")], d, "merged", with_container=False, merge=True)
+    run_group(2, [_amr(d, "M", f"{d}/p512.txt")], d, "merged", with_container=False, merge=True)
     for step in (1, 2):
         _close(_particles(f"{d}/chkM_0000{step}"), _particles(f"{d}/chkA_0000{step}"))

@@ -1,29 +1,19 @@
-"""GPU: shell-summed spectra on two ranks (ranks sharing the one GPU over the gloo callback transport, the harness of
-tests/test_gpu_profile_multirank.py): every rank writes the cells of its own boxes into a zeroed array, the arrays are summed (exact:
+"""GPU: shell-summed spectra on two ranks (ranks sharing the one GPU over the gloo callback transport:
+tests/ranks.py): every rank writes the cells of its own boxes into a zeroed array, the arrays are summed (exact:
 a cell has one owner), every rank transforms the whole field.  Both ranks return identical bytes, and those bytes are the one-rank
 result to the bit.  The two ranks are fresh child processes under a time limit of their own."""
 import os
-import time
 import numpy as np
 import pytest
-from test_gpu_dist import free_port
-from test_gpu_multirank_io import _env
+import ranks
 import spectrum_numpy as SN
 
 pytestmark = [pytest.mark.gpu, pytest.mark.boxes_kept]
 N3 = (32, 32, 32)
-LIMIT = 120.0          # seconds for the two ranks
 
 
 def spectrum_ranks(rank, world, port, out_dir):
-    _env(rank, world)
-    from iamr_amd import lib as L
-    from iamr_amd import comm
-    import torch.distributed as dist
-    L.init(0)
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    comm.init_gloo_callback(dist)
+    L = ranks.start_rank(rank, world, port)
     f = SN.noise(N3, 7, 2)
     g = L.Geom.make(list(N3), periodic=(1, 1, 1))
     lay = L.Layout.decompose(N3, 16, world)
@@ -37,26 +27,14 @@ def spectrum_ranks(rank, world, port, out_dir):
         mf.from_numpy(a, li)
     P, count = L.mf_spectrum(g, mf, 0, 2)
     np.savez(os.path.join(out_dir, f"spec_w{world}_r{rank}.npz"), P=P, count=count)
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-def _spawn(world, *args):
-    import torch.multiprocessing as mp
-    ctx = mp.spawn(spectrum_ranks, args=(world,) + args, nprocs=world, join=False)
-    end = time.monotonic() + LIMIT
-    while not ctx.join(timeout=1.0):
-        if time.monotonic() > end:
-            for p in ctx.processes:
-                p.kill()
-            raise AssertionError(f"{world} rank(s) did not finish within {LIMIT:.0f} s")
+    ranks.stop_rank()
 
 
 def test_two_ranks_against_one(gpu, tmp_path):
     """the 1-rank spectrum is taken in this process (the same eight boxes), the 2-rank one by two child processes"""
     from test_gpu_spectrum import make_mf, geom_of, check
     d = str(tmp_path)
-    _spawn(2, free_port(), d)
+    ranks.spawn(spectrum_ranks, 2, ranks.free_port(), d)
     two = [np.load(os.path.join(d, f"spec_w2_r{r}.npz")) for r in range(2)]
     f = SN.noise(N3, 7, 2)
     mf, lay = make_mf(N3, f, 16)

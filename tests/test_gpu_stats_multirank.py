@@ -1,14 +1,14 @@
-"""GPU: velocity statistics and integrated quantities of runs on several ranks (ranks sharing the one GPU over the gloo callback transport,
-the harness of tests/test_gpu_multirank_io.py).  An N-rank run against the 1-rank run uses that file's constants (single level: 1e-9;
+"""GPU: velocity statistics and integrated quantities of runs on several ranks (ranks sharing the one GPU over the gloo callback transport:
+tests/ranks.py).  An N-rank run against the 1-rank run uses that file's constants (single level: 1e-9;
 a checkpoint restarted on another number of ranks: 1e-8); the integrated quantities, summed over the ranks through the communicator's
 host all-reduce, are also held to the rounding bound of tests/test_gpu_stats.py against numpy on the state the checkpoint holds."""
 import json
 import os
-import sys
 import numpy as np
 import pytest
-from test_gpu_dist import free_port
-from test_gpu_multirank_io import _env, _spawn, _log, _dts, TOL_LEVEL, TOL_HIER, RTOL_DT
+import ranks
+from ranks import free_port
+from test_gpu_multirank_io import _log, _dts, TOL_LEVEL, TOL_HIER, RTOL_DT
 from test_gpu_stats import composite_sums
 
 pytestmark = [pytest.mark.gpu, pytest.mark.boxes_kept]
@@ -19,24 +19,18 @@ N16 = [16, 16, 16]
 
 def stats_ranks(rank, world, ports, jobs, log_dir, group):
     """every rank: R.main once per job with an observer that records the integrated quantities (full doubles) and the three scalars"""
-    _env(rank, world)
-    from iamr_amd import run as R
-    for q, (port, argv) in enumerate(zip(ports, jobs)):
-        os.environ["MASTER_PORT"] = str(port)
-        rec = []
+    ranks.rank_env(rank, world)
+    rec = []
 
-        def observe(ns, step, dt):
-            rec.append(dict(step=step, time=ns.time, sums=list(ns.sum_integrated()), avg=list(ns.average_state)))      # collective
+    def observe(ns, step, dt):
+        rec.append(dict(step=step, time=ns.time, sums=list(ns.sum_integrated()), avg=list(ns.average_state)))      # collective
 
-        with open(os.path.join(log_dir, f"{group}_job{q}_r{rank}.txt"), "w") as f:
-            keep, sys.stdout = sys.stdout, f
-            try:
-                rc = R.main(argv, observe)
-            finally:
-                sys.stdout = keep
-        assert rc == 0, (q, rc)
+    def after(q):
         with open(os.path.join(log_dir, f"{group}_job{q}_r{rank}.json"), "w") as f:
             json.dump(rec, f)
+        rec.clear()
+
+    ranks.run_jobs(rank, ports, jobs, log_dir, group, observe, after)
 
 
 def _job(d, tag, *more):
@@ -63,14 +57,17 @@ def _gathered(path, name, typ_ng=0):
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
     d = str(tmp_path_factory.mktemp("stats_multirank"))
+    # four spawns in one fixture (measured 2.4, 2.9, 2.5 and 3.2 s): four times the helper's 120 s would pass the 420 s after which pytest-timeout
+    # takes the whole test, so each gets 100 s -- the helper fires first, and ends its ranks
+    lim = 100.0
     one = [_job(d, "A")]
     two = [_job(d, "B")]
-    _spawn(stats_ranks, 1, [free_port() for _ in one], one, d, "one")
-    _spawn(stats_ranks, 2, [free_port() for _ in two], two, d, "two")
+    ranks.spawn(stats_ranks, 1, [free_port() for _ in one], one, d, "one", limit=lim)
+    ranks.spawn(stats_ranks, 2, [free_port() for _ in two], two, d, "two", limit=lim)
     rst = [_job(d, "C", f"amr.restart={d}/chkB_00002")]
-    _spawn(stats_ranks, 1, [free_port()], rst, d, "rst1")
+    ranks.spawn(stats_ranks, 1, [free_port()], rst, d, "rst1", limit=lim)
     rst3 = [_job(d, "D", f"amr.restart={d}/chkB_00002")]
-    _spawn(stats_ranks, 3, [free_port()], rst3, d, "rst3")
+    ranks.spawn(stats_ranks, 3, [free_port()], rst3, d, "rst3", limit=lim)
     return d
 
 

@@ -382,7 +382,7 @@ def test_two_ranks_write_the_records_of_one(tmp_path):
     one-rank file's -- the same (time, id) keys, positions (modulo the period) and values within the 1e-8 that
     tests/test_gpu_particles_multirank.py allows between rank counts"""
     try:
-        from test_gpu_particles_multirank import _spawn, _particle_file, TOL_RUN
+        from test_gpu_particles_multirank import run_group, _particle_file, TOL_RUN
     except Exception as e:                                                 # pragma: no cover
         pytest.skip(f"THE TWO-RANK TIMESTAMP TEST DID NOT RUN: the spawning helper of tests/test_gpu_particles_multirank.py cannot be reused ({e})")
     d = str(tmp_path)
@@ -391,8 +391,8 @@ def test_two_ranks_write_the_records_of_one(tmp_path):
     def job(tag):
         return [os.path.join(GOLD, "inputs.3d.taylorgreen_amr16"), f"particles.particle_init_file={d}/p64.txt", "max_step=1", "amr.plot_int=-1", "amr.check_int=-1",
                 "particles.do_timestamps=1", f"particles.timestamp_dir={d}/ts{tag}", "particles.timestamp_indices=0 3"]
-    _spawn(2, [job(2)], d, "ts_two", with_container=False)
-    _spawn(1, [job(1)], d, "ts_one", with_container=False)
+    run_group(2, [job(2)], d, "ts_two", with_container=False)
+    run_group(1, [job(1)], d, "ts_one", with_container=False)
     assert sorted(os.listdir(f"{d}/ts1")) == ["Timestamp_00"] and sorted(os.listdir(f"{d}/ts2")) == ["Timestamp_00", "Timestamp_01"]
     one = tn.parse_file(f"{d}/ts1/Timestamp_00")
     parts = [tn.parse_file(f"{d}/ts2/Timestamp_0{r}") for r in (0, 1)]

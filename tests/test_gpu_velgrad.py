@@ -8,12 +8,11 @@ carries about 11 roundings.  strain_rate is compared as got^2 against 2 SS.  The
 tile, one-cell remainders, a single plane, one odd box, unequal boxes off the tile grid, and 4^3 boxes (the plain form)."""
 import math
 import os
-import sys
 import numpy as np
 import pytest
 import hist_numpy as HN
 from test_gpu_profile import random_state, put_state, one_level
-from test_gpu_dist import free_port
+import ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -458,15 +457,8 @@ NAMES9 = ["q_criterion", "x_velocity", "r_invariant", "helicity", "energy", "dis
 
 
 def _two_ranks(rank, world, port, out_dir):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ.update(IAMRX_COALESCE="0", RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    from iamr_amd import lib, comm
+    lib = ranks.start_rank(rank, world, port)
     from iamr_amd import ns as N
-    import torch.distributed as dist
-    lib.init(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    comm.init_gloo_callback(dist)
     g = lib.Geom.make(list(N9), periodic=(1, 1, 1))
     lay = lib.Layout.decompose(N9, MGS9, world)
     ns = N.NavierStokes(g, lay, N.ns_params(visc_coef=0.02))
@@ -476,16 +468,14 @@ def _two_ranks(rank, world, port, out_dir):
     integ = ns.integrate(NAMES9)
     idx = [lay.local_box(li)[2] for li in range(lay.nlocal())]
     np.savez(os.path.join(out_dir, f"r{rank}.npz"), idx=np.array(idx), integ=integ, **{f"box{q}": out.to_numpy(li)[0] for li, q in enumerate(idx)})
-    dist.barrier()
-    dist.destroy_process_group()
+    ranks.stop_rank()
 
 
 @pytest.mark.merged_only
 def test_two_ranks_on_one_device(gpu, tmp_path):
     """the boxes of one level dealt to two ranks (sharing the device over the gloo callback transport): the fields of every box are the
     one-rank fields to the bit, the integrals agree within 1e-13 of the sum of magnitudes"""
-    import torch.multiprocessing as mp
-    mp.spawn(_two_ranks, args=(2, free_port(), str(tmp_path)), nprocs=2, join=True)
+    ranks.spawn(_two_ranks, 2, ranks.free_port(), str(tmp_path))
     from iamr_amd import lib as L
     from iamr_amd import ns as N
     S = random_state(N9, 91)

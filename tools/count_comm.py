@@ -7,10 +7,9 @@ import torch.distributed as dist
 from iamr_amd import lib, comm
 from iamr_amd import ns as N
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-dist.init_process_group("gloo")
-rank, world = dist.get_rank(), dist.get_world_size()
+rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
 single = os.environ.get('COUNT_SINGLE_OWNER') == '1'      # same boxes, all owned by rank 0 (run with one process)
-lib.init(0)
+comm.start(rank, world, 0, "gloo")
 cnt = {"ex": 0, "ar": 0, "bytes": 0}
 import collections
 hist = collections.Counter()
@@ -21,8 +20,7 @@ def irecv(t, *a, **k):
 def ar(t, *a, **k):
     cnt["ar"] += 1
     return orig_ar(t, *a, **k)
-dist.irecv, dist.all_reduce = irecv, ar
-comm.init_gloo_callback(dist)
+dist.irecv, dist.all_reduce = irecv, ar      # (the transport's callbacks look both up when they are called)
 boxes = [((0, 0, r * n), (n - 1, n - 1, (r + 1) * n - 1)) for r in range(world)]
 nb = int(os.environ.get('COUNT_BOXES', str(world)))
 boxes = [((0, 0, r * n), (n - 1, n - 1, (r + 1) * n - 1)) for r in range(nb)]
@@ -52,4 +50,4 @@ if rank == 0:
     print(f"exchanges per step and rank: {xd[0]} on the main stream ({xd[1] * 8 / 1e6:.1f} MB sent; exposed: in front of the kernel that reads the ghost data), "
           f"{xd[2]} on the side stream ({xd[3] * 8 / 1e6:.1f} MB sent; hidden behind the interior tiles of the multi-box red + black sweep and of the nodal passes)")
 if rank == 0: print("sizes (doubles: count):", sorted(hist.items()))
-dist.barrier(); dist.destroy_process_group()
+comm.stop()
