@@ -228,6 +228,12 @@ class Amr:
         from . import spectrum as _s
         return _s.level_spectrum(lib().iamrx_amr_spectrum, self.h, self.geom0)
 
+    def spectral_budget(self):
+        """spectral kinetic-energy budget of LEVEL 0 of the hierarchy (as spectrum takes its level; include/iamrx.h:
+        iamrx_amr_spectral_budget) -> the dict of NavierStokes.spectral_budget; the same bits on every rank.  Collective."""
+        from . import budget as _b
+        return _b.level_budget(lib().iamrx_amr_spectral_budget, self.h, self.geom0, self.params.visc_coef)
+
     def structure_functions(self, pmax=4, rmax=None):
         """structure functions and two-point correlations of LEVEL 0 of the hierarchy (as spectrum takes its level; include/iamrx.h:
         iamrx_amr_strfn) -> the dict of NavierStokes.structure_functions; the same bits on every rank.  Collective."""

@@ -1278,6 +1278,51 @@ int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, f
     IAMRX_CATCH
 }
 
+// ---- co-spectra, the nonlinear term and the spectral budget (k_spectrum.hip, k_convect.hip)
+int iamrx_mf_cospectrum(const iamrx_geom* g, iamrx_mf a, int acomp, iamrx_mf b, int bcomp, int nbins_cap, double* out, long* count, int* nbins)
+{
+    IAMRX_TRY
+    if (!g || !a || !b) throw Error("iamrx_mf_cospectrum: null geometry or array");
+    if (acomp < 0 || acomp >= a->mf.ncomp) throw Error("iamrx_mf_cospectrum: component " + std::to_string(acomp) + " outside the first array's " + std::to_string(a->mf.ncomp));
+    if (bcomp < 0 || bcomp >= b->mf.ncomp) throw Error("iamrx_mf_cospectrum: component " + std::to_string(bcomp) + " outside the second array's " + std::to_string(b->mf.ncomp));
+    cospectrum_of(to_geom(g), a->mf, acomp, b->mf, bcomp, nbins_cap, out, count, nbins);
+    IAMRX_CATCH
+}
+int iamrx_mf_spectrum_k2(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, int nbins_cap, double* out, int* nbins)
+{
+    IAMRX_TRY
+    if (!g || !mf) throw Error("iamrx_mf_spectrum_k2: null geometry or array");
+    if (ncomp < 1 || comp < 0 || comp + ncomp > mf->mf.ncomp)
+        throw Error("iamrx_mf_spectrum_k2: components " + std::to_string(comp) + " .. " + std::to_string(comp + ncomp - 1) + " outside the array's " + std::to_string(mf->mf.ncomp));
+    std::vector<int> comps(ncomp);
+    for (int q = 0; q < ncomp; ++q) comps[q] = comp + q;
+    spectrum_k2_of(to_geom(g), mf->mf, ncomp, comps.data(), nbins_cap, out, nbins);
+    IAMRX_CATCH
+}
+int iamrx_cospectrum_bench(const iamrx_geom* g, iamrx_mf a, int acomp, iamrx_mf b, int bcomp, int reps, float* ms)
+{
+    IAMRX_TRY
+    if (!g || !a || !b || !ms || reps < 1) throw Error("iamrx_cospectrum_bench: null argument or reps < 1");
+    cospectrum_bench(to_geom(g), a->mf, acomp, b->mf, bcomp, reps, ms);
+    IAMRX_CATCH
+}
+int iamrx_convective_term(const iamrx_geom* g, iamrx_mf out, int ocomp, iamrx_mf vel, int vcomp)
+{
+    IAMRX_TRY
+    if (!g || !out || !vel) throw Error("iamrx_convective_term: null argument");
+    convective_term(to_geom(g), out->mf, ocomp, vel->mf, vcomp);
+    IAMRX_CATCH
+}
+int iamrx_convective_bench(const iamrx_geom* g, iamrx_mf out, iamrx_mf vel, int vcomp, int reps, float* ms)
+{
+    IAMRX_TRY
+    if (!g || !out || !vel || !ms || reps < 1) throw Error("iamrx_convective_bench: null argument or reps < 1");
+    convective_bench(to_geom(g), out->mf, vel->mf, vcomp, reps, ms);
+    IAMRX_CATCH
+}
+int iamrx_budget_nq(void) { return BUDGET_NQ; }
+int iamrx_ns_spectral_budget(iamrx_ns ns, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY ns->ns->spectral_budget(nbins_cap, out, count, nbins); IAMRX_CATCH }
+
 // ---- structure functions (k_strfn.hip)
 int iamrx_strfn_ncol(int pmax) { return pmax >= 1 && pmax <= STRFN_PMAX ? 1 + pmax + (pmax + 1) / 2 : -1; }
 int iamrx_strfn_nq(void) { return STRFN_NQ; }
@@ -1818,6 +1863,7 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
     IAMRX_CATCH
 }
 int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY a->amr->level(0).spectrum(nbins_cap, out, count, nbins); IAMRX_CATCH }
+int iamrx_amr_spectral_budget(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY a->amr->level(0).spectral_budget(nbins_cap, out, count, nbins); IAMRX_CATCH }
 int iamrx_amr_strfn(iamrx_amr a, int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean)
 {
     IAMRX_TRY a->amr->level(0).strfn(pmax, rmax, rcap, out, count, mean); IAMRX_CATCH

@@ -640,8 +640,9 @@ void mf_mult_ghosts(MultiFab& y, double a, int comp, int nc, int ng)
 // ---------------------------------------------------------------------------------------------------------------- dense image
 constexpr int DENSE_THREADS = 256;
 
-// grid (chunks, local boxes): cell p of the box -> dst[2 * dense index] = (f, 0) (CPLX) or dst[dense index] = f
-template <bool CPLX>
+// grid (chunks, local boxes): cell p of the box -> dst[dense index] = f (MODE 0), dst[2 * dense index] = (f, 0) (MODE 1), or the
+// imaginary part dst[2 * dense index + 1] = f alone (MODE 2: the second field of a packed pair, k_spectrum.hip)
+template <int MODE>
 __global__ void __launch_bounds__(DENSE_THREADS) k_dense_pack(const BoxD* __restrict__ boxes, const FabD* __restrict__ st, int comp, BoxD dom,
                                                               double* __restrict__ dst)
 {
@@ -656,7 +657,8 @@ __global__ void __launch_bounds__(DENSE_THREADS) k_dense_pack(const BoxD* __rest
         const int j = (int)(r % by), k = (int)(r / by);
         const double v = sp[s.off(b.lo[0] + i, b.lo[1] + j, b.lo[2] + k)];
         const long o = (long)(b.lo[0] - dom.lo[0] + i) + nx * ((long)(b.lo[1] - dom.lo[1] + j) + ny * (long)(b.lo[2] - dom.lo[2] + k));
-        if (CPLX) { dst[2 * o] = v; dst[2 * o + 1] = 0.0; }
+        if (MODE == 1) { dst[2 * o] = v; dst[2 * o + 1] = 0.0; }
+        else if (MODE == 2) dst[2 * o + 1] = v;
         else dst[o] = v;
     }
 }
@@ -673,7 +675,7 @@ void dense_check_cover(const char* who, const Geometry& g, const Layout& lay)
         throw Error(std::string(who) + ": the boxes of the level do not cover the domain (" + std::to_string(cells) + " of " + std::to_string(g.domain.npts()) + " cells)");
 }
 
-void dense_pack(const Geometry& g, const MultiFab& S, int comp, double* dst, bool cplx)
+static void dense_pack_mode(const Geometry& g, const MultiFab& S, int comp, double* dst, int mode)
 {
     const Layout& lay = *S.layout;
     if (lay.nlocal() == 0) return;
@@ -681,9 +683,13 @@ void dense_pack(const Geometry& g, const MultiFab& S, int comp, double* dst, boo
     for (int f = 0; f < lay.nlocal(); ++f) big = std::max(big, lay.lbox(f).npts());
     const dim3 grid((unsigned)std::min<long>((big + 4 * DENSE_THREADS - 1) / (4 * DENSE_THREADS), 65535), (unsigned)lay.nlocal());
     hipStream_t s = Context::get().stream;
-    if (cplx) hipLaunchKernelGGL((k_dense_pack<true>), grid, dim3(DENSE_THREADS), 0, s, lay.d_boxes, S.d_tab, comp, g.domain, dst);
-    else hipLaunchKernelGGL((k_dense_pack<false>), grid, dim3(DENSE_THREADS), 0, s, lay.d_boxes, S.d_tab, comp, g.domain, dst);
+    if (mode == 1) hipLaunchKernelGGL((k_dense_pack<1>), grid, dim3(DENSE_THREADS), 0, s, lay.d_boxes, S.d_tab, comp, g.domain, dst);
+    else if (mode == 2) hipLaunchKernelGGL((k_dense_pack<2>), grid, dim3(DENSE_THREADS), 0, s, lay.d_boxes, S.d_tab, comp, g.domain, dst);
+    else hipLaunchKernelGGL((k_dense_pack<0>), grid, dim3(DENSE_THREADS), 0, s, lay.d_boxes, S.d_tab, comp, g.domain, dst);
 }
+
+void dense_pack(const Geometry& g, const MultiFab& S, int comp, double* dst, bool cplx) { dense_pack_mode(g, S, comp, dst, cplx ? 1 : 0); }
+void dense_pack_imag(const Geometry& g, const MultiFab& S, int comp, double* dst) { dense_pack_mode(g, S, comp, dst, 2); }
 
 bool dense_needs_gather(const MultiFab& S)
 {

@@ -12,9 +12,10 @@
 //                    X = true   a workgroup owns whole contiguous x pencils (LDS: pencil after pencil, one pad element per 32)
 //                    X = false  y or z: a workgroup owns a tile of TW adjacent x columns times the whole pencil, so that every global
 //                               load and store runs along x (LDS: element of the pencil major, x column minor)
-//   k_spec_bin<T>  a wavefront walks a row along k_x in chunks that lie inside one half of the row, where the shell index is monotone:
-//                  a segmented wave scan, the last lane of each run adds into the wavefront's own LDS bins; the four wavefronts of a
-//                  workgroup combine in a fixed order into the workgroup's slots.  T = double: |F|^2; T = unsigned long long: the count.
+//   k_spec_bin<V>  a wavefront walks a row along k_x in chunks that lie inside one half of the row, where the shell index is monotone:
+//                  a segmented wave scan, the last lane of each run adds into the wavefront's own LDS bins; the wavefronts of a
+//                  workgroup combine in a fixed order into the workgroup's slots.  V: the value functor -- |F|^2, the count, the
+//                  k^2-weighted power, or the four sums of a packed pair (co-spectrum; the mode is read with its mirror mode).
 //   k_spec_finish  adds the slots of a shell in slot order (one wavefront per shell) and applies 1 / N^2.
 // No floating-point atomics anywhere: the same call gives the same bits, and the result does not depend on how the level is cut into
 // boxes (only the pack sees the boxes).  Several ranks: every rank packs its own boxes into a zeroed real array, the arrays are summed
@@ -43,6 +44,12 @@ int ilog2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
 __global__ void __launch_bounds__(SPEC_THREADS) k_spec_expand(const double* __restrict__ R, double2* __restrict__ W, long N)
 {
     for (long p = (long)blockIdx.x * SPEC_THREADS + threadIdx.x; p < N; p += (long)gridDim.x * SPEC_THREADS) W[p] = make_double2(R[p], 0.0);
+}
+
+// two summed real arrays of several ranks -> (a, b)
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_expand2(const double* __restrict__ Ra, const double* __restrict__ Rb, double2* __restrict__ W, long N)
+{
+    for (long p = (long)blockIdx.x * SPEC_THREADS + threadIdx.x; p < N; p += (long)gridDim.x * SPEC_THREADS) W[p] = make_double2(Ra[p], Rb[p]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- transform
@@ -148,54 +155,114 @@ struct SpecShape {
     double rx, ry, rz;      // L_max / L_d
 };
 
-// T = double: val = |F|^2; T = unsigned long long: val = 1.  slots[wg * nbins + s]
-template <typename T>
-__global__ void __launch_bounds__(SPEC_THREADS) k_spec_bin(const double2* __restrict__ W, SpecShape sh, T* __restrict__ slots)
+// The values a mode contributes, NV of them of type T, from the transform W at (row r, column i), at the mirror mode -m (row rm,
+// column im) and from kap2 = kappa^2, which the kernel has formed for the shell index:
+//   PowerVal  |F|^2                                     CountVal  1
+//   K2Val     (c kap2) |F|^2 with c = (2 pi / L_max)^2: the spectral |grad f|^2
+//   CoVal     W = transform of Z = a + i b, a and b real: with Z = W(m), M = W(-m)
+//               C_ab = Re(F_a conj F_b) = Im(Z M) / 2,  P_a = |Z + conj M|^2 / 4,  P_b = |Z - conj M|^2 / 4,  W_a = (c kap2) P_a
+struct PowerVal {
+    using T = double;
+    static constexpr int NV = 1;
+    const double2* __restrict__ W;
+    __device__ __forceinline__ void operator()(long r, int i, long, int, int nx, double, T v[NV]) const
+    {
+        const double2 f = W[r * nx + i];
+        v[0] = f.x * f.x + f.y * f.y;
+    }
+};
+struct CountVal {
+    using T = unsigned long long;
+    static constexpr int NV = 1;
+    __device__ __forceinline__ void operator()(long, int, long, int, int, double, T v[NV]) const { v[0] = 1ull; }
+};
+struct K2Val {
+    using T = double;
+    static constexpr int NV = 1;
+    const double2* __restrict__ W;
+    double c;
+    __device__ __forceinline__ void operator()(long r, int i, long, int, int nx, double kap2, T v[NV]) const
+    {
+        const double2 f = W[r * nx + i];
+        v[0] = (c * kap2) * (f.x * f.x + f.y * f.y);
+    }
+};
+struct CoVal {
+    using T = double;
+    static constexpr int NV = 4;
+    const double2* __restrict__ W;
+    double c;
+    __device__ __forceinline__ void operator()(long r, int i, long rm, int im, int nx, double kap2, T v[NV]) const
+    {
+        const double2 z = W[r * nx + i], m = W[rm * nx + im];
+        const double sr = z.x + m.x, si = z.y - m.y, dr = z.x - m.x, di = z.y + m.y;
+        v[0] = 0.5 * (z.x * m.y + z.y * m.x);
+        v[1] = 0.25 * (sr * sr + si * si);
+        v[2] = 0.25 * (dr * dr + di * di);
+        v[3] = (c * kap2) * v[1];
+    }
+};
+
+// 64 * nw threads, nw = 4, 2 or 1 wavefronts with LDS bins [nw][NV][nbins] of their own (spec_bin: the most that fit 64 KiB);
+// slots[(q * gridDim.x + wg) * nbins + s] for value q: the slots of one value lie together, as k_spec_finish reads them
+template <class Val>
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_bin(Val val, SpecShape sh, typename Val::T* __restrict__ slots)
 {
+    using T = typename Val::T;
+    constexpr int NV = Val::NV;
     extern __shared__ double2 spec_lds[];
-    T* bins = (T*)spec_lds;                                  // [4][nbins]
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    for (int q = tid; q < 4 * sh.nbins; q += SPEC_THREADS) bins[q] = (T)0;
+    T* bins = (T*)spec_lds;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nt = blockDim.x, nw = nt >> 6;
+    const int wstride = NV * sh.nbins;
+    for (int q = tid; q < nw * wstride; q += nt) bins[q] = (T)0;
     __syncthreads();
-    T* mine = bins + wv * sh.nbins;
+    T* mine = bins + wv * wstride;
     const int cw = 1 << sh.lcw, nchunk = sh.nx >> sh.lcw, nrows = sh.ny * sh.nz;
     const int r0 = blockIdx.x * sh.rows_per_wg, r1 = min(r0 + sh.rows_per_wg, nrows);
-    for (int r = r0 + wv; r < r1; r += 4) {
+    for (int r = r0 + wv; r < r1; r += nw) {
         const int j = r % sh.ny, k = r / sh.ny;
         const int my = j < sh.ny / 2 ? j : j - sh.ny, mz = k < sh.nz / 2 ? k : k - sh.nz;
+        const long rm = (long)(j ? sh.ny - j : 0) + (long)sh.ny * (k ? sh.nz - k : 0);       // the row of the modes -m: walked with descending i
         const double ay = (double)my * sh.ry, az = (double)mz * sh.rz;
         const double ay2 = ay * ay, az2 = az * az;
         for (int c = 0; c < nchunk; ++c) {
             const int i = (c << sh.lcw) + lane;
             const bool act = lane < cw;
             int s = -1;
-            T v = (T)0;
+            T v[NV];
+#pragma unroll
+            for (int q = 0; q < NV; ++q) v[q] = (T)0;
             if (act) {
                 const int mx = i < sh.nx / 2 ? i : i - sh.nx;
                 const double ax = (double)mx * sh.rx;
-                s = (int)(sqrt((ax * ax + ay2) + az2) + 0.5);        // the squares added left to right (built without FMA contraction)
+                const double kap2 = (ax * ax + ay2) + az2;           // the squares added left to right (built without FMA contraction)
+                s = (int)(sqrt(kap2) + 0.5);
                 s = min(s, sh.nbins - 1);                            // (never past the LDS bins, whatever a square root rounds to)
-                if constexpr (std::is_floating_point_v<T>) {
-                    const double2 f = W[(long)r * sh.nx + i];
-                    v = f.x * f.x + f.y * f.y;
-                } else {
-                    v = (T)1;
-                }
+                val((long)r, i, rm, i ? sh.nx - i : 0, sh.nx, kap2, v);
             }
             // inclusive segmented scan over the runs of equal s (contiguous: s is monotone inside the chunk), a fixed tree
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
-                const T up = __shfl_up(v, off, 64);
                 const int ks = __shfl_up(s, off, 64);
-                if (lane >= off && ks == s) v += up;
+#pragma unroll
+                for (int q = 0; q < NV; ++q) {
+                    const T up = __shfl_up(v[q], off, 64);
+                    if (lane >= off && ks == s) v[q] += up;
+                }
             }
             const int sn = __shfl_down(s, 1, 64);
-            if (act && (lane == cw - 1 || sn != s)) mine[s] += v;        // one lane per shell of the chunk: no two lanes share a bin
+            if (act && (lane == cw - 1 || sn != s)) {                 // one lane per shell of the chunk: no two lanes share a bin
+#pragma unroll
+                for (int q = 0; q < NV; ++q) mine[q * sh.nbins + s] += v[q];
+            }
         }
     }
     __syncthreads();
-    for (int q = tid; q < sh.nbins; q += SPEC_THREADS)
-        slots[(long)blockIdx.x * sh.nbins + q] = ((bins[q] + bins[sh.nbins + q]) + bins[2 * sh.nbins + q]) + bins[3 * sh.nbins + q];
+    for (int q = tid; q < wstride; q += nt) {
+        T a = bins[q];
+        for (int w = 1; w < nw; ++w) a += bins[w * wstride + q];          // the wavefronts in order
+        slots[((long)(q / sh.nbins) * gridDim.x + blockIdx.x) * sh.nbins + q % sh.nbins] = a;
+    }
 }
 
 // one wavefront per shell: lane l adds the slots l, l + 64, ... in order, then the lanes combine in a fixed tree; out = sum * scale
@@ -310,12 +377,52 @@ void spec_fft(const SpecPlan& p, int dir, double2* W)
     hipLaunchKernelGGL((k_spec_fft<false>), dim3((unsigned)(ntile * other)), dim3(SPEC_THREADS), lds, ctx.stream, W, p.tw[dir], ln, ltw, ntile, estride, ostride, p.pair);
 }
 
-template <typename T>
-void spec_bin(const SpecPlan& p, const double2* W, T* slots, double scale, T* out)
+// the shell sums of the NV values of val: out[q * nbins + s] = scale * sum; slots: NV * nwg * nbins entries
+template <class Val>
+void spec_bin(const SpecPlan& p, const Val& val, typename Val::T* slots, double scale, typename Val::T* out)
+{
+    using T = typename Val::T;
+    auto& ctx = Context::get();
+    const size_t per_wave = (size_t)Val::NV * p.sh.nbins * sizeof(T);
+    int nw = SPEC_THREADS / 64;
+    while (nw > 1 && nw * per_wave > 65536) nw >>= 1;
+    hipLaunchKernelGGL((k_spec_bin<Val>), dim3((unsigned)p.nwg), dim3(64 * nw), nw * per_wave, ctx.stream, val, p.sh, slots);
+    for (int q = 0; q < Val::NV; ++q)
+        hipLaunchKernelGGL((k_spec_finish<T>), dim3((unsigned)((p.sh.nbins + 3) / 4)), dim3(SPEC_THREADS), 0, ctx.stream,
+                           slots + (size_t)q * p.nwg * p.sh.nbins, p.nwg, p.sh.nbins, scale, out + (size_t)q * p.sh.nbins);
+}
+
+// Z = a + i b of a pair of real fields, which may live on different layouts
+void spec_pack_pair(const SpecPlan& p, const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, double2* W)
 {
     auto& ctx = Context::get();
-    hipLaunchKernelGGL((k_spec_bin<T>), dim3((unsigned)p.nwg), dim3(SPEC_THREADS), (size_t)4 * p.sh.nbins * sizeof(T), ctx.stream, W, p.sh, slots);
-    hipLaunchKernelGGL((k_spec_finish<T>), dim3((unsigned)((p.sh.nbins + 3) / 4)), dim3(SPEC_THREADS), 0, ctx.stream, slots, p.nwg, p.sh.nbins, scale, out);
+    if (!dense_needs_gather(A) && !dense_needs_gather(B)) {
+        dense_pack(g, A, acomp, (double*)W, true);
+        dense_pack_imag(g, B, bcomp, (double*)W);
+        return;
+    }
+    double* R = (double*)ctx.alloc((size_t)2 * p.N * sizeof(double));
+    dense_gather(g, A, acomp, R);
+    dense_gather(g, B, bcomp, R + p.N);
+    hipLaunchKernelGGL(k_spec_expand2, dim3((unsigned)std::min<long>((p.N + 4 * SPEC_THREADS - 1) / (4 * SPEC_THREADS), 65535)), dim3(SPEC_THREADS), 0,
+                       ctx.stream, R, R + p.N, W, p.N);
+    ctx.free(R);
+}
+
+// (2 pi / L_max)^2: the factor between kappa^2 and k^2
+double spec_k2_unit(const Geometry& g)
+{
+    double Lmax = 0.0;
+    for (int q = 0; q < 3; ++q) Lmax = std::max(Lmax, g.probhi[q] - g.problo[q]);
+    const double k0 = 6.283185307179586476925286766559 / Lmax;
+    return k0 * k0;
+}
+
+void spec_check(const Geometry& g, const MultiFab& S, int comp)
+{
+    if (!S.type.cell()) throw Error("spectrum: the array is not cell-centred");
+    if (comp < 0 || comp >= S.ncomp) throw Error("spectrum: component " + std::to_string(comp) + " outside 0 .. " + std::to_string(S.ncomp - 1));
+    dense_check_cover("spectrum", g, *S.layout);
 }
 
 }  // namespace
@@ -362,11 +469,11 @@ void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* c
     for (int q = 0; q < nq; ++q) {
         spec_pack(p, g, S, comps[q], W);
         for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
-        spec_bin<double>(p, W, slots, invN * invN, d_out + (size_t)q * nbins);
+        spec_bin(p, PowerVal{W}, slots, invN * invN, d_out + (size_t)q * nbins);
     }
     if (count) {
         static_assert(sizeof(unsigned long long) == sizeof(double), "the counts share the slots of the sums");
-        spec_bin<unsigned long long>(p, W, (unsigned long long*)slots, 1.0, (unsigned long long*)(d_out + (size_t)nq * nbins));
+        spec_bin(p, CountVal{}, (unsigned long long*)slots, 1.0, (unsigned long long*)(d_out + (size_t)nq * nbins));
     }
     IAMRX_HIP_CHECK(hipMemcpyAsync(ctx.h_scratch, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
     ctx.sync();
@@ -401,7 +508,99 @@ void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, fl
         spec_pack(p, g, S, comp, W);
         IAMRX_HIP_CHECK(hipEventRecord(ev[1], ctx.stream));
         for (int d = 0; d < 3; ++d) { spec_fft(p, d, W); IAMRX_HIP_CHECK(hipEventRecord(ev[2 + d], ctx.stream)); }
-        spec_bin<double>(p, W, slots, invN * invN, d_out);
+        spec_bin(p, PowerVal{W}, slots, invN * invN, d_out);
+        IAMRX_HIP_CHECK(hipEventRecord(ev[5], ctx.stream));
+        IAMRX_HIP_CHECK(hipEventSynchronize(ev[5]));
+        for (int q = 0; q < 5; ++q) IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[5 * r + q], ev[q], ev[q + 1]));
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    ctx.free(d_out); ctx.free(slots); ctx.free(W);
+    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- co-spectra
+// A pair (a, b) of real fields goes through ONE transform as Z = a + i b (spec_pack_pair); the bin pass reads every mode with its mirror
+// mode and yields C_ab, P_a, P_b and W_a at once (CoVal).
+void cospectrum_compute(const Geometry& g, int npair, const SpecPair* pairs, int nbins, double* out, long* count)
+{
+    IAMRX_ASSERT(npair >= 1 && pairs && nbins == spectrum_nbins(g));
+    for (int q = 0; q < npair; ++q) { spec_check(g, *pairs[q].a, pairs[q].acomp); spec_check(g, *pairs[q].b, pairs[q].bcomp); }
+    auto& ctx = Context::get();
+    SpecPlan p = spec_plan(g, nbins);
+    spec_tables(p);
+    constexpr int NV = CoVal::NV;
+    static_assert(NV == COSPEC_NV, "the columns of a pair");
+    const size_t nout = (size_t)(NV * npair + 1) * nbins;
+    ctx.ensure_scratch(nout + 16);
+    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+    double* slots = (double*)ctx.alloc((size_t)NV * p.nwg * nbins * sizeof(double));
+    double* d_out = (double*)ctx.alloc(nout * sizeof(double));
+    const double invN = 1.0 / (double)p.N, k2u = spec_k2_unit(g);
+    for (int q = 0; q < npair; ++q) {
+        spec_pack_pair(p, g, *pairs[q].a, pairs[q].acomp, *pairs[q].b, pairs[q].bcomp, W);
+        for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
+        spec_bin(p, CoVal{W, k2u}, slots, invN * invN, d_out + (size_t)NV * q * nbins);
+    }
+    if (count) spec_bin(p, CountVal{}, (unsigned long long*)slots, 1.0, (unsigned long long*)(d_out + (size_t)NV * npair * nbins));
+    IAMRX_HIP_CHECK(hipMemcpyAsync(ctx.h_scratch, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
+    ctx.sync();
+    for (size_t q = 0; q < (size_t)NV * npair * nbins; ++q) out[q] = ctx.h_scratch[q];
+    if (count) {
+        for (int s = 0; s < nbins; ++s) {
+            unsigned long long c;
+            std::memcpy(&c, ctx.h_scratch + (size_t)NV * npair * nbins + s, sizeof c);
+            count[s] = (long)c;
+        }
+    }
+    ctx.free(d_out); ctx.free(slots); ctx.free(W);
+    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+}
+
+void spectrum_k2_compute(const Geometry& g, const MultiFab& S, int nq, const int* comps, int nbins, double* out)
+{
+    IAMRX_ASSERT(nq >= 1 && nbins == spectrum_nbins(g));
+    for (int q = 0; q < nq; ++q) spec_check(g, S, comps[q]);
+    auto& ctx = Context::get();
+    SpecPlan p = spec_plan(g, nbins);
+    spec_tables(p);
+    const size_t nout = (size_t)nq * nbins;
+    ctx.ensure_scratch(nout + 16);
+    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+    double* slots = (double*)ctx.alloc((size_t)p.nwg * nbins * sizeof(double));
+    double* d_out = (double*)ctx.alloc(nout * sizeof(double));
+    const double invN = 1.0 / (double)p.N, k2u = spec_k2_unit(g);
+    for (int q = 0; q < nq; ++q) {
+        spec_pack(p, g, S, comps[q], W);
+        for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
+        spec_bin(p, K2Val{W, k2u}, slots, invN * invN, d_out + (size_t)q * nbins);
+    }
+    IAMRX_HIP_CHECK(hipMemcpyAsync(ctx.h_scratch, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
+    ctx.sync();
+    for (size_t q = 0; q < nout; ++q) out[q] = ctx.h_scratch[q];
+    ctx.free(d_out); ctx.free(slots); ctx.free(W);
+    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+}
+
+void cospectrum_bench(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int reps, float* ms)
+{
+    const int nbins = spectrum_nbins(g);
+    spec_check(g, A, acomp); spec_check(g, B, bcomp);
+    IAMRX_ASSERT(reps >= 1);
+    auto& ctx = Context::get();
+    SpecPlan p = spec_plan(g, nbins);
+    spec_tables(p);
+    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+    double* slots = (double*)ctx.alloc((size_t)CoVal::NV * p.nwg * nbins * sizeof(double));
+    double* d_out = (double*)ctx.alloc((size_t)CoVal::NV * nbins * sizeof(double));
+    hipEvent_t ev[6];
+    for (auto& e : ev) IAMRX_HIP_CHECK(hipEventCreate(&e));
+    const double invN = 1.0 / (double)p.N, k2u = spec_k2_unit(g);
+    for (int r = 0; r < reps; ++r) {
+        IAMRX_HIP_CHECK(hipEventRecord(ev[0], ctx.stream));
+        spec_pack_pair(p, g, A, acomp, B, bcomp, W);
+        IAMRX_HIP_CHECK(hipEventRecord(ev[1], ctx.stream));
+        for (int d = 0; d < 3; ++d) { spec_fft(p, d, W); IAMRX_HIP_CHECK(hipEventRecord(ev[2 + d], ctx.stream)); }
+        spec_bin(p, CoVal{W, k2u}, slots, invN * invN, d_out);
         IAMRX_HIP_CHECK(hipEventRecord(ev[5], ctx.stream));
         IAMRX_HIP_CHECK(hipEventSynchronize(ev[5]));
         for (int q = 0; q < 5; ++q) IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[5 * r + q], ev[q], ev[q + 1]));

@@ -52,6 +52,8 @@ void dense_check_cover(const char* who, const Geometry& g, const Layout& lay);
 // the valid cells of THIS rank's boxes of component comp of a cell-centred array -> their place in the index space of the domain of g
 // (x fastest; ghost cells are never read): dst[o] = f, or with cplx dst[2 o] = f, dst[2 o + 1] = 0.  Cells of other ranks are not written.
 void dense_pack(const Geometry& g, const MultiFab& S, int comp, double* dst, bool cplx);
+// the same cells into the imaginary parts alone, dst[2 o + 1] = f: the second field of a packed pair (k_spectrum.hip)
+void dense_pack_imag(const Geometry& g, const MultiFab& S, int comp, double* dst);
 // the whole field as a real array on every rank.  One rank (or a replicated layout): dense_pack.  Several: every rank packs its boxes
 // into the zeroed array and the arrays are summed through the communicator (exact: a cell has one owner) -- a gather, collective.
 void dense_gather(const Geometry& g, const MultiFab& S, int comp, double* R);
@@ -89,6 +91,29 @@ void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* c
 // measurement aid (tools/bench_spectrum.py): reps times the five passes of one component -- pack, x, y, z, shell sums -- with an event
 // between them; ms[5 * r + p] = milliseconds of pass p in repeat r
 void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, float* ms);
+// ---- co-spectra: two real fields through ONE packed transform Z = a + i b ----
+// a pair of cell-centred components; the two arrays tile the domain, may be the same array and may live on different layouts
+struct SpecPair { const MultiFab* a; int acomp; const MultiFab* b; int bcomp; };
+// the columns of a pair, in this order: C_ab(s) = sum over shell s of Re(F_a conj F_b), P_a, P_b, W_a(s) = sum of k(m)^2 |F_a(m)|^2 with
+// k(m)^2 = (2 pi / L_max)^2 kappa^2 (the spectral |grad a|^2, not the solver's discrete one)
+constexpr int COSPEC_NV = 4;
+// out[(COSPEC_NV * q + v) * nbins + s] = column v of pair q; count as in spectrum_compute.  The transforms, the fixed-order sums (the
+// same call gives the same bits, whatever the box layouts) and the gather on several ranks are those of spectrum_compute.
+void cospectrum_compute(const Geometry& g, int npair, const SpecPair* pairs, int nbins, double* out, long* count);
+// out[q * nbins + s] = W(s) of component comps[q] of S alone (one plain transform per component)
+void spectrum_k2_compute(const Geometry& g, const MultiFab& S, int nq, const int* comps, int nbins, double* out);
+// measurement aid (tools/bench_budget.py): the five passes of one packed pair -- pack, x, y, z, the shell sums with the mirror read --
+// timed as spectrum_bench times its five
+void cospectrum_bench(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int reps, float* ms);
+
+// ---- k_convect.hip: the skew-symmetric centred nonlinear term ----------------------------------
+// out(ocomp + i) = N_i = 0.5 sum_d [u_d delta_d u_i + delta_d(u_d u_i)] of vel(vcomp .. vcomp + 2) on the valid cells (the evaluation
+// order: k_convect.hip); vel: cell-centred, same layout, at least one FILLED ghost layer (only the face neighbours of a cell are read)
+void convective_term(const Geometry& g, MultiFab& out, int ocomp, const MultiFab& vel, int vcomp);
+// measurement aid: ms[r] = one launch into out(0 .. 2) between two events, nothing read back
+void convective_bench(const Geometry& g, MultiFab& out, const MultiFab& vel, int vcomp, int reps, float* ms);
+// the columns of the spectral budget of a level: E, T, D, F (include/iamrx.h)
+constexpr int BUDGET_NQ = 4;
 
 // ---- k_strfn.hip: structure functions and two-point correlations along the axes --------------
 // the components the level and hierarchy entries take: u, v, w and the first tracer

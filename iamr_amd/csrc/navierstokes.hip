@@ -297,6 +297,55 @@ void NavierStokes::spectrum(int cap, double* out, long* count, int* nbins)
     spectrum_of(g, S[inew], SPECTRUM_NQ, comps, cap, out, count, nbins);
 }
 
+// the shell count first, then the capacity: the checks of spectrum_of
+static int spectrum_cap(const Geometry& g, int cap, const void* out, int* nbins)
+{
+    const int n = spectrum_nbins(g);
+    if (nbins) *nbins = n;
+    if (cap < n) throw Error("spectrum: " + std::to_string(n) + " shells, the caller's arrays hold " + std::to_string(cap));
+    if (!out) throw Error("spectrum: null output array");
+    return n;
+}
+
+void cospectrum_of(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int cap, double* out, long* count, int* nbins)
+{
+    const int n = spectrum_cap(g, cap, out, nbins);
+    const SpecPair pr{&A, acomp, &B, bcomp};
+    std::vector<double> col((size_t)COSPEC_NV * n);
+    cospectrum_compute(g, 1, &pr, n, col.data(), count);
+    for (int q = 0; q < 3 * n; ++q) out[q] = col[q];
+}
+
+void spectrum_k2_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int cap, double* out, int* nbins)
+{
+    const int n = spectrum_cap(g, cap, out, nbins);
+    spectrum_k2_compute(g, S, nq, comps, n, out);
+}
+
+void NavierStokes::spectral_budget(int cap, double* out, long* count, int* nbins)
+{
+    const int n = spectrum_cap(g, cap, out, nbins);
+    MultiFab vel(layout, cell_type(), 3, 1), N(layout, cell_type(), 3, 0), f;
+    fillpatch(vel, S[inew], Xvel, 3, bc_vel);
+    convective_term(g, N, 0, vel, 0);
+    if (turb) {
+        f.define(layout, cell_type(), 3, 0);
+        turb_force(g, *turb, cur_time(), f, 0);
+    }
+    SpecPair pr[6];
+    for (int i = 0; i < 3; ++i) { pr[i] = SpecPair{&vel, i, &N, i}; pr[3 + i] = SpecPair{&vel, i, &f, i}; }
+    const int np = turb ? 6 : 3;
+    std::vector<double> col((size_t)COSPEC_NV * np * n);
+    cospectrum_compute(g, np, pr, n, col.data(), count);
+    auto at = [&](int pair, int v, int s) { return col[((size_t)COSPEC_NV * pair + v) * n + s]; };
+    for (int s = 0; s < n; ++s) {
+        out[s] = 0.5 * ((at(0, 1, s) + at(1, 1, s)) + at(2, 1, s));
+        out[n + s] = -((at(0, 0, s) + at(1, 0, s)) + at(2, 0, s));
+        out[2 * n + s] = p.visc_coef * ((at(0, 3, s) + at(1, 3, s)) + at(2, 3, s));
+        out[3 * n + s] = turb ? (at(3, 0, s) + at(4, 0, s)) + at(5, 0, s) : 0.0;
+    }
+}
+
 // the common part of the three C entries: every check that needs no device first, the exact counts from their formula, then the kernels
 void strfn_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int pmax, const int rmax[3], int rcap, double* out, long long* count,
               double* mean)

@@ -199,6 +199,10 @@ private:
 
 // *nbins = spectrum_nbins(g) first, then the capacity check, then spectrum_compute (kernels.h)
 void spectrum_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int cap, double* out, long* count, int* nbins);
+// the same order of checks in front of cospectrum_compute: out[v * nbins + s], v = 0, 1, 2: C_ab, P_a, P_b
+void cospectrum_of(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int cap, double* out, long* count, int* nbins);
+// ... and in front of spectrum_k2_compute
+void spectrum_k2_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int cap, double* out, int* nbins);
 // the common part of the three structure-function entries: pmax, the separations (strfn_resolve_rmax) and the capacity are checked by
 // name, count[d * rcap + r] (or null) is filled from strfn_count, then strfn_compute (kernels.h)
 void strfn_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int pmax, const int rmax[3], int rcap, double* out, long long* count,
@@ -337,6 +341,11 @@ public:
     // columns, count[s] (or null) the modes of shell s.  *nbins is set before the capacity is checked.  Collective; every rank receives the
     // result.
     void spectrum(int cap, double* out, long* count, int* nbins);
+    // spectral kinetic-energy budget of the new-time state (include/iamrx.h): out[q * nbins + s], BUDGET_NQ columns E, T, D, F.  One
+    // FillPatch of the velocity (one ghost layer), the skew-symmetric nonlinear term (k_convect.hip) and, with the turbulent forcing on, its
+    // acceleration at cur_time() into arrays that return to the arena, then one packed transform per pair (u_i, N_i) and (u_i, f_i).
+    // *nbins is set before the capacity is checked.  Collective; every rank receives the result.
+    void spectral_budget(int cap, double* out, long* count, int* nbins);
     // structure functions and two-point correlations along the axes of u, v, w and the first tracer of the new-time state (k_strfn.hip):
     // out[((d * STRFN_NQ + c) * ncol + col) * rcap + r], count[d * rcap + r] and mean[c] (either may be null).  Collective; every rank
     // receives the result.

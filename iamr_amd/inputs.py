@@ -18,7 +18,8 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   ns.profile_interval (-1: off) / ns.profile_dir (the last coordinate) / ns.profile_level (0) / ns.profile_file ("prof"): this library's own
   keys for the plane-averaged profiles of iamr_amd/profile.py, carried under "profile" of the parsed problem, not in its params,
   ns.spectrum_interval (-1: off) / ns.spectrum_file ("spec"): this library's own keys for the shell-summed spectra of level 0
-  (iamr_amd/spectrum.py), carried under "spectrum"; an interval > 0 needs a fully periodic three-dimensional domain whose extents are
+  (iamr_amd/spectrum.py), carried under "spectrum"; ns.budget_interval (-1: off) / ns.budget_file ("sbud"): the spectral kinetic-energy
+  budget of level 0 (iamr_amd/budget.py), carried under "budget", with the preconditions of the spectra; an interval > 0 needs a fully periodic three-dimensional domain whose extents are
   powers of two in 4 .. 1024,
   ns.strfn_interval (-1: off) / ns.strfn_pmax (4; 1 .. 8) / ns.strfn_rmax (one integer or three; -1: the largest separation of the axis, 0:
   skip it) / ns.strfn_file ("sf"): this library's own keys for the structure functions and two-point correlations of level 0 along the
@@ -536,6 +537,20 @@ class Inputs:
                 if not extent_ok(n[d]):
                     raise ValueError(f"inputs: ns.spectrum_interval > 0 needs extents that are powers of two in 4 .. 1024, amr.n_cell has "
                                      f"n_{'xyz'[d]} = {n[d]}")
+        # spectral kinetic-energy budget (this library's own keys; budget.py): as the spectra, with the same preconditions
+        budget = dict(interval=self.integer("ns.budget_interval", -1), file=self.string("ns.budget_file", "sbud"))
+        if budget["interval"] > 0:
+            from .spectrum import extent_ok
+            if slab:
+                raise NotImplementedError("inputs: ns.budget_interval > 0 in a two-dimensional run: the transform is three-dimensional only "
+                                          "(the slab's thickness direction has two cells)")
+            if not all(per):
+                raise ValueError(f"inputs: ns.budget_interval > 0 needs a fully periodic domain, geometry.is_periodic = {' '.join(str(int(v)) for v in per)}: "
+                                 f"direction {'xyz'[[bool(v) for v in per].index(False)]} is not periodic")
+            for d in range(3):
+                if not extent_ok(n[d]):
+                    raise ValueError(f"inputs: ns.budget_interval > 0 needs extents that are powers of two in 4 .. 1024, amr.n_cell has "
+                                     f"n_{'xyz'[d]} = {n[d]}")
         # structure functions and two-point correlations along the axes (this library's own keys): every strfn_interval-th level-0 step and
         # once for the initial data, of level 0; strfn_rmax: one integer for all axes or three (-1: the largest allowed, 0: skip the axis)
         strfn = dict(interval=self.integer("ns.strfn_interval", -1), pmax=self.integer("ns.strfn_pmax", 4),
@@ -594,7 +609,7 @@ class Inputs:
                     if v in VELGRAD_NAMES and v not in VELGRAD_NAMES_2D:
                         raise NotImplementedError(f"inputs: {key} names '{v}' in a two-dimensional run: of the velocity-gradient fields a slab "
                                                   f"knows {' '.join(VELGRAD_NAMES_2D)}")
-        out = dict(profile=profile, spectrum=spectrum, strfn=strfn, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
+        out = dict(profile=profile, spectrum=spectrum, budget=budget, strfn=strfn, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
                    max_step=self.integer("max_step", -1), stop_time=self.real("stop_time", -1.0),
                    plot_int=self.integer("amr.plot_int", -1), plot_file=self.string("amr.plot_file", "plt"), plot_vars=self.name_list("amr.plot_vars", "ALL"),
                    derive_plot_vars=dpv, fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,

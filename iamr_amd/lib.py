@@ -508,6 +508,26 @@ def mf_spectrum(geom, mf, comp=0, ncomp=1):
     return _s.mf_spectrum(geom, mf, comp, ncomp)
 
 
+def mf_cospectrum(geom, a, b, acomp=0, bcomp=0):
+    """co-spectrum of component acomp of a and bcomp of b, cell-centred MultiFabs that each tile the fully periodic domain of geom
+    (include/iamrx.h: iamrx_mf_cospectrum; one packed transform) -> (C_ab, P_a, P_b, count), each (nbins,)"""
+    from . import budget as _b
+    return _b.mf_cospectrum(geom, a, b, acomp, bcomp)
+
+
+def mf_spectrum_k2(geom, mf, comp=0, ncomp=1):
+    """k^2-weighted power W (ncomp, nbins) of components comp .. comp + ncomp - 1: the spectral |grad f|^2 per shell
+    (include/iamrx.h: iamrx_mf_spectrum_k2)"""
+    from . import budget as _b
+    return _b.mf_spectrum_k2(geom, mf, comp, ncomp)
+
+
+def convective_term(geom, out, vel, ocomp=0, vcomp=0):
+    """out(ocomp .. ocomp + 2) = the skew-symmetric centred nonlinear term N_i = 0.5 sum_d [u_d delta_d u_i + delta_d(u_d u_i)] of
+    vel(vcomp .. vcomp + 2), vel with 1 filled ghost layer (include/iamrx.h: iamrx_convective_term)"""
+    check(lib().iamrx_convective_term(C.byref(geom), _h(out), int(ocomp), _h(vel), int(vcomp)))
+
+
 def mf_structure(geom, mf, comp=0, ncomp=1, pmax=4, rmax=None):
     """structure functions and two-point correlations along the axes of components comp .. comp + ncomp - 1 of a cell-centred MultiFab
     whose boxes tile the domain of geom (include/iamrx.h: iamrx_mf_strfn) -> the raw dict of strfn.raw_dict: "avg" (3, ncomp, ncol,

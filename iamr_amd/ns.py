@@ -366,6 +366,27 @@ class NavierStokes:
         from . import spectrum as _s
         return _s.level_spectrum(lib().iamrx_ns_spectrum, self.h, self.geom)
 
+    def cospectrum(self, a, b):
+        """co-spectrum of two named fields of this level -- any names derive_fields knows: the state components by plotfile name, "energy",
+        "mag_vort", "avg_pressure" and the velocity-gradient names (include/iamrx.h: iamrx_mf_cospectrum) -> dict with "k", "count",
+        "C" = C_ab, "Pa", "Pb", "n", "L"; the same bits on every rank.  Collective."""
+        from . import budget as _b
+        from . import spectrum as _s
+        import math
+        import numpy as np
+        f = self.derive_fields([a, b])
+        Cab, Pa, Pb, cnt = _b.mf_cospectrum(self.geom, f, f, 0, 1)
+        n, L = _s._geom_nL(self.geom)
+        return dict(k=np.arange(len(Cab)) * (2.0 * math.pi / max(L)), count=cnt, C=Cab, Pa=Pa, Pb=Pb, n=n, L=L)
+
+    def spectral_budget(self):
+        """spectral kinetic-energy budget of the new-time state on a fully periodic level (include/iamrx.h: iamrx_ns_spectral_budget) ->
+        dict with "k", "count", "E", "T" (nonlinear transfer, skew-symmetric centred form), "Pi" (the flux -cumsum(T)), "D" (molecular
+        dissipation spectrum), "F" (injection by the turbulent forcing; zero when it is off), "n", "L", "visc_coef"; the same bits on every
+        rank.  Collective."""
+        from . import budget as _b
+        return _b.level_budget(lib().iamrx_ns_spectral_budget, self.h, self.geom, self.params.visc_coef)
+
     def structure_functions(self, pmax=4, rmax=None):
         """structure functions and two-point correlations of u, v, w and the first tracer of the new-time state along the axes, with or
         without walls (include/iamrx.h: iamrx_ns_strfn) -> the dict of strfn.derive: the raw "avg" (3, 4, ncol, rcap), "count", "mean",

@@ -642,6 +642,46 @@ int iamrx_ns_spectrum(iamrx_ns ns, int nbins_cap, double* out, long* count, int*
 /* measurement aid (tools/bench_spectrum.py): reps times the five passes of one component (pack, x, y, z transform, shell sums) with an
  * event between them; ms[5 * r + p] = milliseconds of pass p in repeat r.  Nothing is read back. */
 int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, float* ms);
+/* Co-spectra and the spectral kinetic-energy budget dE(k)/dt = T(k) - D(k) + F(k) of a fully periodic level (this library's own
+ * diagnostic; k_spectrum.hip, k_convect.hip).  The transform F, the signed mode numbers, kappa, the shell index s, *nbins and count are
+ * those of iamrx_mf_spectrum, and so are the restrictions and the errors, checked in the same order (*nbins is set before the capacity
+ * error).  N: the number of cells.
+ *   co-spectrum    C_ab(s) = sum over the modes of shell s of Re(F_a(m) conj(F_b(m))) of two cell-centred fields a, b, so that
+ *                  sum_s C_ab(s) = mean(a b) (Parseval) and C_aa = P_a;
+ *   k^2 weighting  W_f(s) = sum over the modes of shell s of k(m)^2 |F_f(m)|^2, k(m)^2 = (2 pi / L_max)^2 ((m_x r_x)^2 + (m_y r_y)^2 +
+ *                  (m_z r_z)^2), the squares added in the order the shell index uses.  This is the SPECTRAL |grad f|^2, not the one of the
+ *                  solver's discrete operators;
+ *   nonlinear term in skew-symmetric centred form: with delta_d f(x) = (f(x + e_d) - f(x - e_d)) (0.5 / dx_d) and i = 0, 1, 2,
+ *                  N_i(x) = 0.5 sum_d [ u_d(x) delta_d u_i(x) + delta_d(u_d u_i)(x) ]  (built without FMA contraction).  Only the six face
+ *                  neighbours of a cell are read.  sum_x u_i N_i = 0 identically on a periodic grid (summation by parts), so the
+ *                  transfer below sums to zero over the shells up to rounding;
+ *   budget         of the new-time state, no density weighting (as for E): E(s) = (P_u + P_v + P_w) / 2, T(s) = -(C_{u N_0} + C_{v N_1}
+ *                  + C_{w N_2}), D(s) = visc_coef (W_u + W_v + W_w) (the molecular part only, also in an LES run, as "dissipation"),
+ *                  F(s) = C_{u f_0} + C_{v f_1} + C_{w f_2} with f the acceleration of the turbulent forcing at the level's time as
+ *                  iamrx_turb_force evaluates it, exactly zero with the forcing off.  The flux Pi(s) = -(T(0) + ... + T(s)) is left to
+ *                  the caller (iamr_amd/budget.py adds left to right).
+ * iamrx_mf_cospectrum: out[0 .. nbins) = C_ab, then P_a, then P_b, of component acomp of a and bcomp of b: caller-owned cell-centred
+ * arrays that each tile the domain of g; they may be the same array and may have different box layouts; count may be NULL.  The pair goes
+ * through ONE transform as Z = a + i b; the shell sums read every mode with its mirror mode -m, index ((n_x - i) % n_x, (n_y - j) % n_y,
+ * (n_z - k) % n_z): Re(F_a conj F_b)(m) = Im(Z(m) Z(-m)) / 2, |F_a|^2 = |Z(m) + conj Z(-m)|^2 / 4, |F_b|^2 = |Z(m) - conj Z(-m)|^2 / 4.
+ * Sums in a fixed order, no floating-point atomics: the same call gives the same bits, whatever the box layouts.  C_ab and C_ba agree
+ * within rounding, not to the bit (the packed fields differ).
+ * iamrx_mf_spectrum_k2: out[q * nbins + s] = W(s) of component comp + q, one plain transform each.
+ * iamrx_convective_term: out(ocomp + i) = N_i of vel(vcomp .. vcomp + 2) on the valid cells; out and vel on one layout, vel with at
+ * least one FILLED ghost layer.  Walls are allowed: the stencil is pointwise and a ghost cell's value is differenced like any other.
+ * iamrx_budget_nq: the columns of the level and hierarchy entries, 4: E, T, D, F.  iamrx_ns_spectral_budget: out[q * nbins + s]; the
+ * velocity is FillPatched once with one ghost layer, N (and f) are formed into arrays that return to the arena, three packed transforms
+ * (u_i, N_i) give E, T and D, three more (u_i, f_i) give F when the forcing is on.  Collective on several ranks as the spectra are (a
+ * gather).  Not built: density weighting, levels above 0, a distributed transform, time averaging, the eddy-viscosity part of D. */
+int iamrx_mf_cospectrum(const iamrx_geom* g, iamrx_mf a, int acomp, iamrx_mf b, int bcomp, int nbins_cap, double* out, long* count, int* nbins);
+int iamrx_mf_spectrum_k2(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, int nbins_cap, double* out, int* nbins);
+int iamrx_convective_term(const iamrx_geom* g, iamrx_mf out, int ocomp, iamrx_mf vel, int vcomp);
+int iamrx_budget_nq(void);
+int iamrx_ns_spectral_budget(iamrx_ns ns, int nbins_cap, double* out, long* count, int* nbins);
+/* measurement aids (tools/bench_budget.py): the five passes of one packed pair (pack, x, y, z transform, shell sums with the mirror read),
+ * ms[5 * r + p] as iamrx_spectrum_bench; one launch of the nonlinear term into out(0 .. 2), ms[r].  Nothing is read back. */
+int iamrx_cospectrum_bench(const iamrx_geom* g, iamrx_mf a, int acomp, iamrx_mf b, int bcomp, int reps, float* ms);
+int iamrx_convective_bench(const iamrx_geom* g, iamrx_mf out, iamrx_mf vel, int vcomp, int reps, float* ms);
 /* Structure functions and two-point correlations along the axes (this library's own diagnostic, no upstream counterpart; k_strfn.hip).
  * Unlike the spectra they are defined with walls and on extents that are not powers of two.  For a cell-centred component f on a level
  * whose boxes tile the domain, n = (n_x, n_y, n_z) cells, N = n_x n_y n_z, an axis d and an integer separation r in cells:
@@ -897,6 +937,8 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
 /* The spectra of iamrx_ns_spectrum on LEVEL 0 of the hierarchy: after avgDown its covered cells hold the average of the finer data (the
  * role of finestLevel = 0 in derivespect-inputs).  Spectra on finer levels and composite spectra are not built. */
 int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins);
+/* The budget of iamrx_ns_spectral_budget on LEVEL 0 of the hierarchy, exactly as iamrx_amr_spectrum takes its level. */
+int iamrx_amr_spectral_budget(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins);
 /* The structure functions of iamrx_ns_strfn on LEVEL 0 of the hierarchy, exactly as iamrx_amr_spectrum takes its level. */
 int iamrx_amr_strfn(iamrx_amr a, int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean);
 /* Composite histograms of the hierarchy (the rule, the names and the layout of counts: iamrx_mf_histogram / iamrx_ns_histogram above).  Level l
