@@ -228,6 +228,11 @@ class Amr:
         from . import spectrum as _s
         return _s.level_spectrum(lib().iamrx_amr_spectrum, self.h, self.geom0)
 
+    def filtered(self, names, kind, kc):
+        """the named fields of LEVEL 0 of the hierarchy (as spectrum takes its level) low-pass filtered into a new MultiFab on that
+        level's layout -> NavierStokes.filtered of level 0.  Collective."""
+        return self.levels[0].filtered(names, kind, kc)
+
     def spectral_budget(self):
         """spectral kinetic-energy budget of LEVEL 0 of the hierarchy (as spectrum takes its level; include/iamrx.h:
         iamrx_amr_spectral_budget) -> the dict of NavierStokes.spectral_budget; the same bits on every rank.  Collective."""

@@ -1320,6 +1320,43 @@ int iamrx_convective_bench(const iamrx_geom* g, iamrx_mf out, iamrx_mf vel, int 
     convective_bench(to_geom(g), out->mf, vel->mf, vcomp, reps, ms);
     IAMRX_CATCH
 }
+// ---- the way back from mode space: noise, filters, the solenoidal projection, the synthetic field (k_spectrum.hip)
+int iamrx_mf_noise(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, unsigned long long seed)
+{
+    IAMRX_TRY
+    if (!g || !mf) throw Error("iamrx_mf_noise: null geometry or array");
+    specop_noise(to_geom(g), mf->mf, comp, ncomp, seed);
+    IAMRX_CATCH
+}
+int iamrx_mf_filter(const iamrx_geom* g, iamrx_mf dst, int dcomp, iamrx_mf src, int scomp, int ncomp, int kind, double kc)
+{
+    IAMRX_TRY
+    if (!g || !dst || !src) throw Error("iamrx_mf_filter: null geometry or array");
+    specop_filter(to_geom(g), dst->mf, dcomp, src->mf, scomp, ncomp, kind, kc);
+    IAMRX_CATCH
+}
+int iamrx_mf_solenoidal(const iamrx_geom* g, iamrx_mf dst, int dcomp, iamrx_mf src, int scomp, int wavenumber)
+{
+    IAMRX_TRY
+    if (!g || !dst || !src) throw Error("iamrx_mf_solenoidal: null geometry or array");
+    specop_solenoidal(to_geom(g), dst->mf, dcomp, src->mf, scomp, wavenumber);
+    IAMRX_CATCH
+}
+int iamrx_mf_synthesize(const iamrx_geom* g, iamrx_mf dst, int dcomp, unsigned long long seed, int nbins, const double* E_target, int wavenumber)
+{
+    IAMRX_TRY
+    if (!g || !dst) throw Error("iamrx_mf_synthesize: null geometry or array");
+    specop_synthesize(to_geom(g), dst->mf, dcomp, seed, nbins, E_target, wavenumber);
+    IAMRX_CATCH
+}
+int iamrx_specop_bench_np(void) { return SPECOP_BENCH_NP; }
+int iamrx_specop_bench(const iamrx_geom* g, iamrx_mf dst, iamrx_mf src, int scomp, int kind, double kc, int wavenumber, int reps, float* ms)
+{
+    IAMRX_TRY
+    if (!g || !dst || !src || !ms || reps < 1) throw Error("iamrx_specop_bench: null argument or reps < 1");
+    specop_bench(to_geom(g), dst->mf, src->mf, scomp, kind, kc, wavenumber, reps, ms);
+    IAMRX_CATCH
+}
 int iamrx_budget_nq(void) { return BUDGET_NQ; }
 int iamrx_ns_spectral_budget(iamrx_ns ns, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY ns->ns->spectral_budget(nbins_cap, out, count, nbins); IAMRX_CATCH }
 

@@ -691,6 +691,34 @@ static void dense_pack_mode(const Geometry& g, const MultiFab& S, int comp, doub
 void dense_pack(const Geometry& g, const MultiFab& S, int comp, double* dst, bool cplx) { dense_pack_mode(g, S, comp, dst, cplx ? 1 : 0); }
 void dense_pack_imag(const Geometry& g, const MultiFab& S, int comp, double* dst) { dense_pack_mode(g, S, comp, dst, 2); }
 
+// grid (chunks, local boxes): the inverse of k_dense_pack<1>, cell p of the box <- scale * src[2 * dense index] (the real part)
+__global__ void __launch_bounds__(DENSE_THREADS) k_dense_unpack(const BoxD* __restrict__ boxes, const FabD* __restrict__ dt, int comp, BoxD dom,
+                                                                const double* __restrict__ src, double scale)
+{
+    const BoxD b = boxes[blockIdx.y];
+    const FabD d = dt[blockIdx.y];
+    const auto dp = d.gp() + (long)comp * d.cs;
+    const int bx = b.len(0), by = b.len(1);
+    const long np = b.npts(), nx = dom.len(0), ny = dom.len(1);
+    for (long p = (long)blockIdx.x * DENSE_THREADS + threadIdx.x; p < np; p += (long)gridDim.x * DENSE_THREADS) {
+        const int i = (int)(p % bx);
+        const long r = p / bx;
+        const int j = (int)(r % by), k = (int)(r / by);
+        const long o = (long)(b.lo[0] - dom.lo[0] + i) + nx * ((long)(b.lo[1] - dom.lo[1] + j) + ny * (long)(b.lo[2] - dom.lo[2] + k));
+        dp[d.off(b.lo[0] + i, b.lo[1] + j, b.lo[2] + k)] = src[2 * o] * scale;
+    }
+}
+
+void dense_unpack(const Geometry& g, MultiFab& S, int comp, const double* src, double scale)
+{
+    const Layout& lay = *S.layout;
+    if (lay.nlocal() == 0) return;
+    long big = 1;
+    for (int f = 0; f < lay.nlocal(); ++f) big = std::max(big, lay.lbox(f).npts());
+    const dim3 grid((unsigned)std::min<long>((big + 4 * DENSE_THREADS - 1) / (4 * DENSE_THREADS), 65535), (unsigned)lay.nlocal());
+    hipLaunchKernelGGL(k_dense_unpack, grid, dim3(DENSE_THREADS), 0, Context::get().stream, lay.d_boxes, S.d_tab, comp, g.domain, src, scale);
+}
+
 bool dense_needs_gather(const MultiFab& S)
 {
     auto& ctx = Context::get();

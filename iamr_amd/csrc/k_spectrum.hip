@@ -610,4 +610,410 @@ void cospectrum_bench(const Geometry& g, const MultiFab& A, int acomp, const Mul
     for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the way back
+// Filters, the solenoidal projection and the synthetic field (include/iamrx.h).  The inverse transform is the forward one:
+// f = conj(FFT(conj(N F))) / N, so a call is  pack, 3 x k_spec_fft, k_spec_mul<Op> (the operation, then conj and 1 / N), 3 x k_spec_fft,
+// k_dense_unpack (k_basic.hip; the real part, so the last conjugation is free).
+//   k_spec_mul<Op>  one streaming pass over the modes, x fastest: a workgroup is 2^ltx lanes along x times 256 >> ltx rows (j, k), every
+//                   index a shift or a mask (all extents are powers of two); a lane loads and stores whole 16-byte modes, a wavefront
+//                   1 KiB of a row (or 64 B pieces of several rows where n_x < 64).  The factors that need exp or sin come from per-axis
+//                   tables the host makes in extended precision, like the twiddles: a mode costs three cached 8-byte reads, not a libm call.
+//   k_spec_noise    the counter-based noise of include/iamrx.h, into the boxes of an array or into a dense complex image
+namespace {
+
+struct SpecAxes { const double* x; const double* y; const double* z; };      // one table per axis, indexed by the cell index of the mode
+
+// G(m) F(m): kind 1 compares kappa^2 with kc^2, every other kind is (g_x g_y) g_z from the tables (ones for the identity)
+struct FilterOp {
+    double2* __restrict__ W;
+    SpecAxes g;
+    int sharp;
+    double kc2;
+    __device__ __forceinline__ void operator()(long p, int i, int j, int k, double kap2, int, double sgn, double scale) const
+    {
+        const double G = sharp ? (kap2 <= kc2 ? 1.0 : 0.0) : (g.x[i] * g.y[j]) * g.z[k];
+        const double a = G * scale;
+        const double2 f = W[p];
+        W[p] = make_double2(f.x * a, sgn * (f.y * a));
+    }
+};
+
+// u <- u - q (q . u) / |q|^2 on three arrays at once, real and imaginary parts alike (q is real)
+struct SolenoidalOp {
+    double2* __restrict__ U; double2* __restrict__ V; double2* __restrict__ Wz;
+    SpecAxes q;
+    __device__ __forceinline__ void operator()(long p, int i, int j, int k, double, int, double sgn, double scale) const
+    {
+        const double qx = q.x[i], qy = q.y[j], qz = q.z[k];
+        const double q2 = (qx * qx + qy * qy) + qz * qz;
+        double2 u = U[p], v = V[p], w = Wz[p];
+        if (q2 != 0.0) {
+            const double cr = ((qx * u.x + qy * v.x) + qz * w.x) / q2, ci = ((qx * u.y + qy * v.y) + qz * w.y) / q2;
+            u.x -= qx * cr; u.y -= qx * ci;
+            v.x -= qy * cr; v.y -= qy * ci;
+            w.x -= qz * cr; w.y -= qz * ci;
+        }
+        U[p] = make_double2(u.x * scale, sgn * (u.y * scale));
+        V[p] = make_double2(v.x * scale, sgn * (v.y * scale));
+        Wz[p] = make_double2(w.x * scale, sgn * (w.y * scale));
+    }
+};
+
+// F(m) <- a[s(m)] F(m) on three arrays at once
+struct ShellScaleOp {
+    double2* __restrict__ U; double2* __restrict__ V; double2* __restrict__ Wz;
+    const double* __restrict__ a;
+    __device__ __forceinline__ void operator()(long p, int, int, int, double, int s, double sgn, double scale) const
+    {
+        const double c = a[s] * scale;
+        const double2 u = U[p], v = V[p], w = Wz[p];
+        U[p] = make_double2(u.x * c, sgn * (u.y * c));
+        V[p] = make_double2(v.x * c, sgn * (v.y * c));
+        Wz[p] = make_double2(w.x * c, sgn * (w.y * c));
+    }
+};
+
+// sgn = -1: the conjugate in front of the inverse transform, scale = 1 / N with it (a power of two: exact); sgn = 1, scale = 1 otherwise
+template <class Op>
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_mul(Op op, SpecShape sh, int lny, int ltx, double sgn, double scale)
+{
+    const int tx = 1 << ltx, i0 = threadIdx.x & (tx - 1), rsub = threadIdx.x >> ltx, rpb = SPEC_THREADS >> ltx;
+    const int nrows = sh.ny * sh.nz;
+    for (int r = blockIdx.x * rpb + rsub; r < nrows; r += gridDim.x * rpb) {
+        const int j = r & (sh.ny - 1), k = r >> lny;
+        const int my = j < sh.ny / 2 ? j : j - sh.ny, mz = k < sh.nz / 2 ? k : k - sh.nz;
+        const double ay = (double)my * sh.ry, az = (double)mz * sh.rz;
+        const double ay2 = ay * ay, az2 = az * az;
+        for (int i = i0; i < sh.nx; i += tx) {
+            const int mx = i < sh.nx / 2 ? i : i - sh.nx;
+            const double ax = (double)mx * sh.rx;
+            const double kap2 = (ax * ax + ay2) + az2;               // as k_spec_bin forms it
+            const int s = min((int)(sqrt(kap2) + 0.5), sh.nbins - 1);
+            op((long)r * sh.nx + i, i, j, k, kap2, s, sgn, scale);
+        }
+    }
+}
+
+__host__ __device__ inline unsigned long long spec_mix(unsigned long long z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// the inner mix of a component, formed once on the host
+unsigned long long spec_noise_key(unsigned long long seed, int c) { return spec_mix(seed ^ ((unsigned long long)(c + 1) * 0x9E3779B97F4A7C15ull)); }
+// h = mix(key + o); every step of the value is exact in double
+__device__ __forceinline__ double spec_noise_value(unsigned long long key, unsigned long long o)
+{
+    const unsigned long long h = spec_mix(key + o);
+    return ((double)(h >> 12) + 0.5) * 0x1p-52 - 0.5;
+}
+
+// grid (chunks, local boxes), as k_dense_pack: the valid cells of a box take the noise of their global index
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_noise(const BoxD* __restrict__ boxes, const FabD* __restrict__ dt, int comp, BoxD dom,
+                                                             unsigned long long key)
+{
+    const BoxD b = boxes[blockIdx.y];
+    const FabD d = dt[blockIdx.y];
+    const auto dp = d.gp() + (long)comp * d.cs;
+    const int bx = b.len(0), by = b.len(1);
+    const long np = b.npts(), nx = dom.len(0), ny = dom.len(1);
+    for (long p = (long)blockIdx.x * SPEC_THREADS + threadIdx.x; p < np; p += (long)gridDim.x * SPEC_THREADS) {
+        const int i = (int)(p % bx);
+        const long r = p / bx;
+        const int j = (int)(r % by), k = (int)(r / by);
+        const long o = (long)(b.lo[0] - dom.lo[0] + i) + nx * ((long)(b.lo[1] - dom.lo[1] + j) + ny * (long)(b.lo[2] - dom.lo[2] + k));
+        dp[d.off(b.lo[0] + i, b.lo[1] + j, b.lo[2] + k)] = spec_noise_value(key, (unsigned long long)o);
+    }
+}
+// the whole dense image at once, (noise, 0): every rank makes the same field, no gather
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_noise_dense(double2* __restrict__ W, long N, unsigned long long key)
+{
+    for (long p = (long)blockIdx.x * SPEC_THREADS + threadIdx.x; p < N; p += (long)gridDim.x * SPEC_THREADS)
+        W[p] = make_double2(spec_noise_value(key, (unsigned long long)p), 0.0);
+}
+
+// a(s) = sqrt(E_target(s) / E_now(s)) with E_now = ((P_u + P_v) + P_w) / 2, a = 0 for s = 0 and where E_now = 0; *bad = 1 + the first
+// shell whose target asks for energy the noise does not have (0: none)
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_coef(const double* __restrict__ P, const double* __restrict__ Et, int nbins, double* __restrict__ a,
+                                                            int* __restrict__ bad)
+{
+    const int s = blockIdx.x * SPEC_THREADS + threadIdx.x;
+    if (s >= nbins) return;
+    const double En = 0.5 * ((P[s] + P[nbins + s]) + P[2 * nbins + s]);
+    double c = 0.0;
+    if (s > 0 && En > 0.0) c = sqrt(Et[s] / En);
+    else if (s > 0 && Et[s] > 0.0) atomicMin(bad, s);
+    a[s] = c;
+}
+
+// ---- host side
+long double spec_pi() { return 3.141592653589793238462643383279502884L; }
+
+// the per-axis factor of the filter at cell index e of an axis of n cells with r = L_max / L: kinds 0 and 1 -> 1
+std::vector<double> spec_filter_axis(int n, double r, int kind, double kc)
+{
+    std::vector<double> t(n, 1.0);
+    if (kind != 2 && kind != 3) return t;
+    for (int e = 0; e < n; ++e) {
+        const int m = e < n / 2 ? e : e - n;
+        const long double x = spec_pi() * (long double)m * (long double)r / (long double)kc;      // k_d Delta
+        if (kind == 2) t[e] = (double)std::exp(-(x * x) / 24.0L);
+        else t[e] = m == 0 ? 1.0 : (double)(std::sin(0.5L * x) / (0.5L * x));
+    }
+    return t;
+}
+
+// q_d at cell index e: exact 2 pi m / L, centred sin(2 pi m / n) / dx; 0 at m = -n / 2 (the Nyquist rule) in both forms
+std::vector<double> spec_wave_axis(int n, double L, double dx, int wavenumber)
+{
+    std::vector<double> t(n, 0.0);
+    for (int e = 0; e < n; ++e) {
+        const int m = e < n / 2 ? e : e - n;
+        if (2 * m == -n) continue;
+        if (wavenumber == 0) t[e] = (double)(2.0L * spec_pi() * (long double)m / (long double)L);
+        else t[e] = (double)(std::sin(2.0L * spec_pi() * (long double)m / (long double)n) / (long double)dx);
+    }
+    return t;
+}
+
+struct SpecAxisTables {
+    double* d[3] = {nullptr, nullptr, nullptr};
+    SpecAxes axes() const { return SpecAxes{d[0], d[1], d[2]}; }
+    void upload(int q, const std::vector<double>& t)
+    {
+        auto& ctx = Context::get();
+        d[q] = (double*)ctx.alloc(t.size() * sizeof(double));
+        ctx.upload_async(d[q], t.data(), t.size() * sizeof(double));
+    }
+    void release() { for (auto& p : d) if (p) { Context::get().free(p); p = nullptr; } }
+};
+
+SpecAxisTables spec_filter_tables(const SpecPlan& p, int kind, double kc)
+{
+    SpecAxisTables t;
+    const int n[3] = {p.sh.nx, p.sh.ny, p.sh.nz};
+    const double r[3] = {p.sh.rx, p.sh.ry, p.sh.rz};
+    for (int q = 0; q < 3; ++q) t.upload(q, spec_filter_axis(n[q], r[q], kind, kc));
+    return t;
+}
+
+SpecAxisTables spec_wave_tables(const SpecPlan& p, const Geometry& g, int wavenumber)
+{
+    SpecAxisTables t;
+    const int n[3] = {p.sh.nx, p.sh.ny, p.sh.nz};
+    for (int q = 0; q < 3; ++q) t.upload(q, spec_wave_axis(n[q], g.probhi[q] - g.problo[q], g.dx[q], wavenumber));
+    return t;
+}
+
+template <class Op>
+void spec_mul(const SpecPlan& p, const Op& op, bool inverse)
+{
+    const int ltx = std::min(p.ln[0], 8), rpb = SPEC_THREADS >> ltx;
+    const long nrows = (long)p.sh.ny * p.sh.nz;
+    const unsigned grid = (unsigned)std::min<long>((nrows + rpb - 1) / rpb, 8192);
+    hipLaunchKernelGGL((k_spec_mul<Op>), dim3(grid), dim3(SPEC_THREADS), 0, Context::get().stream, op, p.sh, p.ln[1], ltx, inverse ? -1.0 : 1.0,
+                       inverse ? 1.0 / (double)p.N : 1.0);
+}
+
+unsigned spec_stream_grid(long N) { return (unsigned)std::min<long>((N + 4 * SPEC_THREADS - 1) / (4 * SPEC_THREADS), 65535); }
+
+void spec_noise_dense(const SpecPlan& p, unsigned long long seed, int c, double2* W)
+{
+    hipLaunchKernelGGL(k_spec_noise_dense, dim3(spec_stream_grid(p.N)), dim3(SPEC_THREADS), 0, Context::get().stream, W, p.N, spec_noise_key(seed, c));
+}
+
+// the checks of the spectra on one array, under the caller's name for the component range
+void specop_check(const Geometry& g, const MultiFab& S, int comp, int ncomp)
+{
+    if (!S.type.cell()) throw Error("spectrum: the array is not cell-centred");
+    if (ncomp < 1 || comp < 0 || comp + ncomp > S.ncomp)
+        throw Error("spectrum: components " + std::to_string(comp) + " .. " + std::to_string(comp + ncomp - 1) + " outside 0 .. " + std::to_string(S.ncomp - 1));
+    dense_check_cover("spectrum", g, *S.layout);
+}
+
+void specop_written(MultiFab& S) { S.uniform_marked = false; S.varying_marked = false; }
+
+// the device part of a synthesis on the work arrays W[3]: noise .. shell scale with the conjugate and 1 / N; ev (or null): the events
+// of specop_bench after each step.  d_P: 3 * nbins, d_a: nbins, d_bad: one int preset to INT_MAX
+void spec_synth_modes(const SpecPlan& p, const SpecAxisTables& qt, unsigned long long seed, double2* const W[3], double* slots, double* d_P,
+                      const double* d_Et, double* d_a, int* d_bad, hipEvent_t* ev)
+{
+    auto& ctx = Context::get();
+    const int nbins = p.sh.nbins;
+    const double invN = 1.0 / (double)p.N;
+    auto mark = [&](int q) { if (ev) IAMRX_HIP_CHECK(hipEventRecord(ev[q], ctx.stream)); };
+    for (int c = 0; c < 3; ++c) spec_noise_dense(p, seed, c, W[c]);
+    mark(0);
+    for (int c = 0; c < 3; ++c)
+        for (int d = 0; d < 3; ++d) spec_fft(p, d, W[c]);
+    mark(1);
+    spec_mul(p, SolenoidalOp{W[0], W[1], W[2], qt.axes()}, false);
+    mark(2);
+    for (int c = 0; c < 3; ++c) spec_bin(p, PowerVal{W[c]}, slots, invN * invN, d_P + (size_t)c * nbins);
+    hipLaunchKernelGGL(k_spec_coef, dim3((unsigned)((nbins + SPEC_THREADS - 1) / SPEC_THREADS)), dim3(SPEC_THREADS), 0, ctx.stream, d_P, d_Et, nbins, d_a, d_bad);
+    mark(3);
+    spec_mul(p, ShellScaleOp{W[0], W[1], W[2], d_a}, true);
+    mark(4);
+    for (int c = 0; c < 3; ++c)
+        for (int d = 0; d < 3; ++d) spec_fft(p, d, W[c]);
+    mark(5);
+}
+
+}  // namespace
+
+void specop_noise(const Geometry& g, MultiFab& S, int comp, int ncomp, unsigned long long seed)
+{
+    specop_check(g, S, comp, ncomp);
+    const Layout& lay = *S.layout;
+    if (lay.nlocal() == 0) return;
+    long big = 1;
+    for (int f = 0; f < lay.nlocal(); ++f) big = std::max(big, lay.lbox(f).npts());
+    const dim3 grid(spec_stream_grid(big), (unsigned)lay.nlocal());
+    for (int c = 0; c < ncomp; ++c)
+        hipLaunchKernelGGL(k_spec_noise, grid, dim3(SPEC_THREADS), 0, Context::get().stream, lay.d_boxes, S.d_tab, comp + c, g.domain, spec_noise_key(seed, c));
+    specop_written(S);
+}
+
+void specop_filter(const Geometry& g, MultiFab& dst, int dcomp, const MultiFab& src, int scomp, int ncomp, int kind, double kc)
+{
+    const int nbins = spectrum_nbins(g);
+    specop_check(g, src, scomp, ncomp);
+    specop_check(g, dst, dcomp, ncomp);
+    if (kind < 0 || kind >= SPECOP_NKIND) throw Error("spectrum: filter kind " + std::to_string(kind) + " outside 0 .. " + std::to_string(SPECOP_NKIND - 1));
+    if (!(kc > 0.0) || !std::isfinite(kc)) throw Error("spectrum: the filter's cut-off kc must be positive and finite");
+    auto& ctx = Context::get();
+    SpecPlan p = spec_plan(g, nbins);
+    spec_tables(p);
+    SpecAxisTables gt = spec_filter_tables(p, kind, kc);
+    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+    const bool down = &dst == &src && dcomp > scomp;        // overlapping ranges of one array: never read what was already written
+    for (int c = 0; c < ncomp; ++c) {
+        const int q = down ? ncomp - 1 - c : c;
+        spec_pack(p, g, src, scomp + q, W);
+        for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
+        spec_mul(p, FilterOp{W, gt.axes(), kind == 1, kc * kc}, true);
+        for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
+        dense_unpack(g, dst, dcomp + q, (const double*)W, 1.0);
+    }
+    specop_written(dst);
+    ctx.sync();
+    ctx.free(W); gt.release();
+    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+}
+
+void specop_solenoidal(const Geometry& g, MultiFab& dst, int dcomp, const MultiFab& src, int scomp, int wavenumber)
+{
+    const int nbins = spectrum_nbins(g);
+    specop_check(g, src, scomp, 3);
+    specop_check(g, dst, dcomp, 3);
+    if (wavenumber < 0 || wavenumber >= SPECOP_NWAVE) throw Error("spectrum: wavenumber form " + std::to_string(wavenumber) + " outside 0 .. " + std::to_string(SPECOP_NWAVE - 1));
+    auto& ctx = Context::get();
+    SpecPlan p = spec_plan(g, nbins);
+    spec_tables(p);
+    SpecAxisTables qt = spec_wave_tables(p, g, wavenumber);
+    double2* W[3];
+    for (int c = 0; c < 3; ++c) {
+        W[c] = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+        spec_pack(p, g, src, scomp + c, W[c]);
+        for (int d = 0; d < 3; ++d) spec_fft(p, d, W[c]);
+    }
+    spec_mul(p, SolenoidalOp{W[0], W[1], W[2], qt.axes()}, true);
+    for (int c = 0; c < 3; ++c) {
+        for (int d = 0; d < 3; ++d) spec_fft(p, d, W[c]);
+        dense_unpack(g, dst, dcomp + c, (const double*)W[c], 1.0);
+    }
+    specop_written(dst);
+    ctx.sync();
+    for (int c = 0; c < 3; ++c) ctx.free(W[c]);
+    qt.release();
+    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+}
+
+void specop_synthesize(const Geometry& g, MultiFab& dst, int dcomp, unsigned long long seed, int nbins, const double* E_target, int wavenumber)
+{
+    const int nb = spectrum_nbins(g);
+    specop_check(g, dst, dcomp, 3);
+    if (wavenumber < 0 || wavenumber >= SPECOP_NWAVE) throw Error("spectrum: wavenumber form " + std::to_string(wavenumber) + " outside 0 .. " + std::to_string(SPECOP_NWAVE - 1));
+    if (nbins != nb) throw Error("spectrum: " + std::to_string(nb) + " shells, the target spectrum holds " + std::to_string(nbins));
+    if (!E_target) throw Error("spectrum: null target spectrum");
+    for (int s = 0; s < nb; ++s)
+        if (!(E_target[s] >= 0.0) || !std::isfinite(E_target[s])) throw Error("spectrum: the target spectrum of shell " + std::to_string(s) + " is negative or not finite");
+    auto& ctx = Context::get();
+    SpecPlan p = spec_plan(g, nb);
+    spec_tables(p);
+    SpecAxisTables qt = spec_wave_tables(p, g, wavenumber);
+    double2* W[3];
+    for (int c = 0; c < 3; ++c) W[c] = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+    double* slots = (double*)ctx.alloc((size_t)p.nwg * nb * sizeof(double));
+    double* d_P = (double*)ctx.alloc((size_t)5 * nb * sizeof(double));            // P_u, P_v, P_w, the target, a
+    int* d_bad = (int*)ctx.alloc(sizeof(int));
+    const int none = 0x7fffffff;
+    int bad = none;
+    ctx.upload_async(d_P + (size_t)3 * nb, E_target, (size_t)nb * sizeof(double));
+    ctx.upload_async(d_bad, &none, sizeof(int));
+    spec_synth_modes(p, qt, seed, W, slots, d_P, d_P + (size_t)3 * nb, d_P + (size_t)4 * nb, d_bad, nullptr);
+    IAMRX_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+    ctx.sync();
+    if (bad == none) {
+        for (int c = 0; c < 3; ++c) dense_unpack(g, dst, dcomp + c, (const double*)W[c], 1.0);
+        specop_written(dst);
+        ctx.sync();
+    }
+    for (int c = 0; c < 3; ++c) ctx.free(W[c]);
+    ctx.free(d_bad); ctx.free(d_P); ctx.free(slots);
+    qt.release();
+    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+    if (bad != none)
+        throw Error("spectrum: the target spectrum asks for energy in shell " + std::to_string(bad) + ", where the projected noise has none");
+}
+
+void specop_bench(const Geometry& g, MultiFab& dst, const MultiFab& src, int scomp, int kind, double kc, int wavenumber, int reps, float* ms)
+{
+    const int nbins = spectrum_nbins(g);
+    specop_check(g, src, scomp, 1);
+    specop_check(g, dst, 0, 3);
+    IAMRX_ASSERT(kind >= 0 && kind < SPECOP_NKIND && kc > 0.0 && wavenumber >= 0 && wavenumber < SPECOP_NWAVE && reps >= 1);
+    auto& ctx = Context::get();
+    SpecPlan p = spec_plan(g, nbins);
+    spec_tables(p);
+    SpecAxisTables gt = spec_filter_tables(p, kind, kc), qt = spec_wave_tables(p, g, wavenumber);
+    double2* W[3];
+    for (int c = 0; c < 3; ++c) W[c] = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+    double* slots = (double*)ctx.alloc((size_t)p.nwg * nbins * sizeof(double));
+    double* d_P = (double*)ctx.alloc((size_t)5 * nbins * sizeof(double));
+    int* d_bad = (int*)ctx.alloc(sizeof(int));
+    IAMRX_HIP_CHECK(hipMemsetAsync(d_P, 0, (size_t)5 * nbins * sizeof(double), ctx.stream));      // target 0: a = 0, the passes cost the same
+    IAMRX_HIP_CHECK(hipMemsetAsync(d_bad, 0x7f, sizeof(int), ctx.stream));
+    constexpr int NP = SPECOP_BENCH_NP;
+    hipEvent_t ev[NP + 1];
+    for (auto& e : ev) IAMRX_HIP_CHECK(hipEventCreate(&e));
+    for (int r = 0; r < reps; ++r) {
+        int q = 0;
+        IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream));
+        spec_pack(p, g, src, scomp, W[0]);
+        IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream));
+        for (int d = 0; d < 3; ++d) { spec_fft(p, d, W[0]); IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream)); }
+        spec_mul(p, FilterOp{W[0], gt.axes(), kind == 1, kc * kc}, true);
+        IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream));
+        for (int d = 0; d < 3; ++d) { spec_fft(p, d, W[0]); IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream)); }
+        dense_unpack(g, dst, 0, (const double*)W[0], 1.0);
+        IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream));                                      // ev[9]: the filter ends, the synthesis begins
+        spec_synth_modes(p, qt, 42ull, W, slots, d_P, d_P + (size_t)3 * nbins, d_P + (size_t)4 * nbins, d_bad, ev + 10);
+        for (int c = 0; c < 3; ++c) dense_unpack(g, dst, c, (const double*)W[c], 1.0);
+        IAMRX_HIP_CHECK(hipEventRecord(ev[16], ctx.stream));
+        dense_pack(g, src, scomp, (double*)W[0], true);
+        IAMRX_HIP_CHECK(hipEventRecord(ev[17], ctx.stream));
+        IAMRX_HIP_CHECK(hipEventSynchronize(ev[17]));
+        for (int s = 0; s < NP; ++s) IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[NP * r + s], ev[s], ev[s + 1]));
+    }
+    specop_written(dst);
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    for (int c = 0; c < 3; ++c) ctx.free(W[c]);
+    ctx.free(d_bad); ctx.free(d_P); ctx.free(slots);
+    gt.release(); qt.release();
+    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+}
+
 }  // namespace iamrx

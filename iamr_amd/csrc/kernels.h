@@ -58,6 +58,9 @@ void dense_pack_imag(const Geometry& g, const MultiFab& S, int comp, double* dst
 // into the zeroed array and the arrays are summed through the communicator (exact: a cell has one owner) -- a gather, collective.
 void dense_gather(const Geometry& g, const MultiFab& S, int comp, double* R);
 bool dense_needs_gather(const MultiFab& S);      // several ranks and a layout that is not replicated
+// the inverse of dense_pack with cplx: the valid cells of THIS rank's boxes of component comp take scale * the real part src[2 o] of
+// their place in the complex image of the domain (the whole image is on every rank); ghost cells are not written
+void dense_unpack(const Geometry& g, MultiFab& S, int comp, const double* src, double scale);
 
 // ---- k_stats.hip: on-the-fly velocity statistics (NS_average.cpp, NS_derive.cpp:11-45) ------
 // avg(0..2) += dt_avg * vel; fluct: avg(3..5) += dt_avg * (vel - avg(0..2) / t_sum)^2 with the updated avg(0..2); vel = S(vcomp..)
@@ -105,6 +108,18 @@ void spectrum_k2_compute(const Geometry& g, const MultiFab& S, int nq, const int
 // measurement aid (tools/bench_budget.py): the five passes of one packed pair -- pack, x, y, z, the shell sums with the mirror read --
 // timed as spectrum_bench times its five
 void cospectrum_bench(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int reps, float* ms);
+// ---- the way back from mode space (include/iamrx.h): filters, the solenoidal projection, a synthetic isotropic field ----
+// f = conj(FFT(conj(N F))) / N through the forward passes; the conjugation and 1 / N ride on the mode-space pass k_spec_mul<Op>
+constexpr int SPECOP_NKIND = 4;             // identity, sharp, Gaussian, box
+constexpr int SPECOP_NWAVE = 2;             // exact, centred
+constexpr int SPECOP_BENCH_NP = 17;
+// white noise of (seed, c, global cell index) in the valid cells of S(comp + c), c < ncomp; any domain whose boxes S tiles
+void specop_noise(const Geometry& g, MultiFab& S, int comp, int ncomp, unsigned long long seed);
+// dst(dcomp + q) = G * src(scomp + q); the checks of the spectra on both arrays, then kind and kc, before anything is written
+void specop_filter(const Geometry& g, MultiFab& dst, int dcomp, const MultiFab& src, int scomp, int ncomp, int kind, double kc);
+void specop_solenoidal(const Geometry& g, MultiFab& dst, int dcomp, const MultiFab& src, int scomp, int wavenumber);
+void specop_synthesize(const Geometry& g, MultiFab& dst, int dcomp, unsigned long long seed, int nbins, const double* E_target, int wavenumber);
+void specop_bench(const Geometry& g, MultiFab& dst, const MultiFab& src, int scomp, int kind, double kc, int wavenumber, int reps, float* ms);
 
 // ---- k_convect.hip: the skew-symmetric centred nonlinear term ----------------------------------
 // out(ocomp + i) = N_i = 0.5 sum_d [u_d delta_d u_i + delta_d(u_d u_i)] of vel(vcomp .. vcomp + 2) on the valid cells (the evaluation

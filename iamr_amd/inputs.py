@@ -12,6 +12,9 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   prob.density_ic, prob.rho_1 / rho_2 / tra_1 / tra_2 / interface_width / perturbation_amplitude (probtype 10), max_step, stop_time,
   turb.nmodes (its presence switches the turbulent forcing of Tutorials/HIT on) / turb.div_free_force / turb.mode_start, prob.probtype 100 with
   prob.turb_scale (Tutorials/HIT/TurbulentForcing_def.H:36-52, Tutorials/HIT/prob_init.cpp:58-134),
+  prob.probtype 101 (this library's own: the decaying isotropic box, level 0's velocity synthesised on the device by iamr_amd/spectral.py)
+  with hit.k0 (4) / hit.urms0 (1) / hit.seed (42) / hit.wavenumber (centred | exact) / hit.spectrum_file (a two-column `k E` table in
+  place of the model spectrum) and prob.density_ic; it needs what the spectra need and amr.max_level = 0,
   particles.particle_init_file / particle_restart_file / particle_output_file / restart_from_nonparticle_chkfile / particles_in_plotfile /
   verbose / do_nspc_particles (NavierStokesBase.cpp:3751-3806); particles.timestamp_dir / timestamp_indices are used when this library's
   own particles.do_timestamps = 1 is given, and accepted and ignored without it,
@@ -504,13 +507,38 @@ class Inputs:
                 raise NotImplementedError("inputs: prob.probtype = 100 (forced turbulence) in a two-dimensional run")
             prob = dict(probtype=100, turb_scale=self.real("prob.turb_scale", 1.0), density_ic=self.real("prob.density_ic", 1.0),
                         prob_lo=list(prob_lo), prob_hi=list(prob_hi))
+        elif probtype == 101:                 # this library's own: the decaying isotropic box, velocity synthesised on the device (spectral.py)
+            from .spectrum import extent_ok
+            if slab:
+                raise NotImplementedError("inputs: prob.probtype = 101 (decaying isotropic turbulence) in a two-dimensional run: the transform is "
+                                          "three-dimensional only")
+            if max_level > 0:
+                raise NotImplementedError(f"inputs: prob.probtype = 101 with amr.max_level = {max_level}: the synthetic field is made on level 0 only "
+                                          "(filling the finer levels of a synthesised start is not built)")
+            if not all(per):
+                raise ValueError(f"inputs: prob.probtype = 101 needs a fully periodic domain, geometry.is_periodic = {' '.join(str(int(v)) for v in per)}: "
+                                 f"direction {'xyz'[[bool(v) for v in per].index(False)]} is not periodic")
+            for d in range(3):
+                if not extent_ok(n[d]):
+                    raise ValueError(f"inputs: prob.probtype = 101 needs extents that are powers of two in 4 .. 1024, amr.n_cell has "
+                                     f"n_{'xyz'[d]} = {n[d]}")
+            wn = self.string("hit.wavenumber", "centred")
+            if wn not in ("centred", "exact"):
+                raise ValueError(f"inputs: hit.wavenumber = {wn}: centred or exact")
+            sf = self.string("hit.spectrum_file", "")
+            if sf and not os.path.isabs(sf) and self.files:
+                sf = os.path.join(os.path.dirname(os.path.abspath(self.files[0])), sf)
+            prob = dict(probtype=101, k0=self.real("hit.k0", 4.0), urms0=self.real("hit.urms0", 1.0), seed=self.integer("hit.seed", 42),
+                        wavenumber=wn, spectrum_file=sf, density_ic=self.real("prob.density_ic", 1.0))
+            if not prob["k0"] > 0.0 or not prob["urms0"] > 0.0 or prob["seed"] < 0:
+                raise ValueError("inputs: hit.k0 and hit.urms0 must be positive, hit.seed non-negative")
         elif probtype in (2, 4, 5, 6, 7):     # host-side initial data (iamr_amd/probinit.py)
             prob = dict(probtype=probtype, density_ic=self.real("prob.density_ic", 1.0), direction=self.integer("prob.direction", 0),
                         interface_width=self.real("prob.interface_width", 1.0), blob_radius=self.real("prob.blob_radius", 0.1),
                         blob_center=self.reals("prob.blob_center", 3, [0.0, 0.0, 0.0]), velocity_ic=self.reals("prob.velocity_ic", 3, [0.0, 0.0, 0.0]))
         else:
             raise NotImplementedError(f"inputs: prob.probtype = {probtype}; implemented: 1 (fluid at rest, LidDrivenCavity), 2 / 6 (bubble / hot spot), 4 (constant "
-                                      "velocity + tracer blob), 5 (DoubleShearLayer), 7 (Euler), 10 (RayleighTaylor), 11 (TaylorGreen), 100 (forced turbulence)")
+                                      "velocity + tracer blob), 5 (DoubleShearLayer), 7 (Euler), 10 (RayleighTaylor), 11 (TaylorGreen), 100 (forced turbulence), 101 (decaying isotropic turbulence)")
         if slab:
             prob["dim"] = 2
         # plane-averaged profiles (this library's own keys, like particles.do_timestamps): every profile_interval-th level-0 step and once for

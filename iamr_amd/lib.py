@@ -515,6 +515,33 @@ def mf_cospectrum(geom, a, b, acomp=0, bcomp=0):
     return _b.mf_cospectrum(geom, a, b, acomp, bcomp)
 
 
+def mf_noise(geom, mf, seed, comp=0, ncomp=1):
+    """white noise of (seed, component, global cell index) in the valid cells (include/iamrx.h: iamrx_mf_noise; spectral.py)"""
+    from . import spectral as _s
+    return _s.mf_noise(geom, mf, seed, comp, ncomp)
+
+
+def mf_filter(geom, dst, src, kind, kc, dcomp=0, scomp=0, ncomp=1):
+    """dst(dcomp + q) = the low-pass filtered src(scomp + q): kind identity / sharp / gaussian / box (or 0 .. 3), cut-off kc in units of
+    2 pi / L_max (include/iamrx.h: iamrx_mf_filter; spectral.py)"""
+    from . import spectral as _s
+    return _s.mf_filter(geom, dst, src, kind, kc, dcomp, scomp, ncomp)
+
+
+def mf_solenoidal(geom, dst, src, wavenumber="centred", dcomp=0, scomp=0):
+    """dst(dcomp .. dcomp + 2) = the solenoidal part of src(scomp .. scomp + 2) for the exact or the centred wavenumber
+    (include/iamrx.h: iamrx_mf_solenoidal; spectral.py)"""
+    from . import spectral as _s
+    return _s.mf_solenoidal(geom, dst, src, wavenumber, dcomp, scomp)
+
+
+def mf_synthesize(geom, dst, E_target, seed=42, wavenumber="centred", comp=0):
+    """dst(comp .. comp + 2) = a random solenoidal field with the shell spectrum E_target (include/iamrx.h: iamrx_mf_synthesize;
+    spectral.py)"""
+    from . import spectral as _s
+    return _s.mf_synthesize(geom, dst, E_target, seed, wavenumber, comp)
+
+
 def mf_spectrum_k2(geom, mf, comp=0, ncomp=1):
     """k^2-weighted power W (ncomp, nbins) of components comp .. comp + ncomp - 1: the spectral |grad f|^2 per shell
     (include/iamrx.h: iamrx_mf_spectrum_k2)"""

@@ -379,6 +379,13 @@ class NavierStokes:
         n, L = _s._geom_nL(self.geom)
         return dict(k=np.arange(len(Cab)) * (2.0 * math.pi / max(L)), count=cnt, C=Cab, Pa=Pa, Pb=Pb, n=n, L=L)
 
+    def filtered(self, names, kind, kc):
+        """the named fields of this level -- any names derive_fields knows -- low-pass filtered in mode space into a new MultiFab on the
+        level's layout, component q = names[q] (include/iamrx.h: iamrx_mf_filter; spectral.py).  kind: "sharp", "gaussian", "box" (or
+        "identity"); kc: the cut-off in units of 2 pi / L_max.  Needs what spectrum needs.  Collective."""
+        from . import spectral as _s
+        return _s.level_filtered(self, names, kind, kc)
+
     def spectral_budget(self):
         """spectral kinetic-energy budget of the new-time state on a fully periodic level (include/iamrx.h: iamrx_ns_spectral_budget) ->
         dict with "k", "count", "E", "T" (nonlinear transfer, skew-symmetric centred form), "Pi" (the flux -cumsum(T)), "D" (molecular

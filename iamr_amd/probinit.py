@@ -5,6 +5,8 @@ handed to the library once through iamrx_ns_set_data).  Restates Source/prob/pro
   probtype 7  Euler: vortex tube along x with a wobble    (init_Euler, :562-610)
 and Tutorials/HIT/prob_init.cpp for
   probtype 100  cosine waves, the start of a forced-turbulence run (init_forced, :86-134)
+and, this library's own,
+  probtype 101  the decaying isotropic box: the velocity is synthesised on the device (set_synthetic_state, spectral.py)
 Cell centres x = prob_lo + (i + 1/2) dx as in the reference; components (u, v, w, rho, tracer)."""
 import numpy as np
 
@@ -100,4 +102,29 @@ def set_initial_state(ns, lay, lib, N, prob, n, prob_lo, prob_hi):
         lo, hi = m.fab_box(li)
         X, Y, Z = cell_centres(n, prob_lo, prob_hi, lo, hi)
         m.from_numpy(initial_state(prob, X, Y, Z, nstate), li)
+    ns.set_data(N.NavierStokes.S_NEW, m)
+
+
+def set_synthetic_state(ns, lay, lib, N, prob, n):
+    """probtype 101, the decaying isotropic box: density prob.density_ic, every tracer 1 (as probtype 100), and a velocity that
+    spectral.mf_synthesize makes on the device at the run's own resolution: random, solenoidal for the wavenumber form hit.wavenumber,
+    with the model spectrum of spectral.hit_spectrum (hit.k0, hit.urms0) or the table of hit.spectrum_file.  Collective."""
+    from . import spectral as SP
+    from .spectrum import nbins_of
+    geom = ns.geom
+    L = tuple(float(geom.prob_hi[d]) - float(geom.prob_lo[d]) for d in range(3))
+    nbins = nbins_of(n, L)
+    if prob["spectrum_file"]:
+        E = SP.read_spectrum_table(prob["spectrum_file"], nbins)
+    else:
+        E = SP.hit_spectrum(nbins, L, prob["k0"], prob["urms0"], n=n)
+    nstate = ns.nstate
+    m = lib.MultiFab(lay, lib.CELL, nstate, 1)
+    for li in range(m.nlocal()):
+        lo, hi = m.fab_box(li)
+        S = np.zeros(tuple(hi[d] - lo[d] + 1 for d in range(3)) + (nstate,), order="F")
+        S[..., 3] = prob["density_ic"]
+        S[..., 4:] = 1.0
+        m.from_numpy(S, li)
+    SP.mf_synthesize(geom, m, E, seed=prob["seed"], wavenumber=prob["wavenumber"], comp=0)
     ns.set_data(N.NavierStokes.S_NEW, m)

@@ -23,6 +23,10 @@ def init_level(ns, lay, lib, N, pr, n):
         from .probinit import set_initial_state
         ns.init_rest(pb["density_ic"])
         set_initial_state(ns, lay, lib, N, pb, n, pr["prob_lo"], pr["prob_hi"])
+    elif pb["probtype"] == 101:
+        from .probinit import set_synthetic_state
+        ns.init_rest(pb["density_ic"])
+        set_synthetic_state(ns, lay, lib, N, pb, n)
     elif pb["probtype"] == 10:
         ns.init_rayleightaylor(pb["rho_1"], pb["rho_2"], pb["tra_1"], pb["tra_2"], pb["pertamp"], pb["interface_width"])
     else:

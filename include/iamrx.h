@@ -682,6 +682,57 @@ int iamrx_ns_spectral_budget(iamrx_ns ns, int nbins_cap, double* out, long* coun
  * ms[5 * r + p] as iamrx_spectrum_bench; one launch of the nonlinear term into out(0 .. 2), ms[r].  Nothing is read back. */
 int iamrx_cospectrum_bench(const iamrx_geom* g, iamrx_mf a, int acomp, iamrx_mf b, int bcomp, int reps, float* ms);
 int iamrx_convective_bench(const iamrx_geom* g, iamrx_mf out, iamrx_mf vel, int vcomp, int reps, float* ms);
+/* The way back from mode space: spectral filters, the solenoidal projection and a synthetic isotropic field (this library's own; the role
+ * of the off-line generator Tutorials/HIT/README names; k_spectrum.hip).  The transform F, the signed mode numbers m_d, r_d, kappa, the
+ * shell index s and *nbins are those of iamrx_mf_spectrum, and so are the restrictions and the errors, checked in the same order.
+ * Physical wavenumber k_d = 2 pi m_d / L_d = k0 m_d r_d with k0 = 2 pi / L_max, so |k| = k0 kappa.  dx_d = L_d / n_d.
+ *   inverse        f = conj(FFT(conj(N F))) / N with the passes and twiddle tables of the forward transform: the conjugation and the 1 / N
+ *                  are folded into the mode-space pass in front, and the unpack takes real parts (the last conjugation is free);
+ *   filter         F(m) <- G(m) F(m); the cut-off kc is given in units of k0 and Delta = pi / (k0 kc):
+ *                    kind 0  identity  G = 1 (the round trip)
+ *                    kind 1  sharp     G = 1 where kappa^2 <= kc^2 (kappa^2 formed exactly as the shell index forms it), otherwise 0
+ *                    kind 2  Gaussian  G = exp(-|k|^2 Delta^2 / 24) = prod_d exp(-(pi m_d r_d / kc)^2 / 24)
+ *                    kind 3  box       G = prod_d sinc(k_d Delta / 2) = prod_d sinc(pi m_d r_d / (2 kc)), sinc(x) = sin(x) / x, sinc(0) = 1
+ *                  Kinds 2 and 3 are products of one factor per axis; the factors come from per-axis tables the host makes in extended
+ *                  precision (as the twiddles), multiplied as (g_x g_y) g_z;
+ *   projection     on three components at once, u(m) <- u(m) - q (q . u(m)) / |q|^2 with q . u = (q_x u_x + q_y u_y) + q_z u_z and
+ *                  |q|^2 = (q_x^2 + q_y^2) + q_z^2; modes with |q|^2 = 0 are left alone:
+ *                    wavenumber 0  exact    q_d = k_d: the continuous field becomes divergence-free
+ *                    wavenumber 1  centred  q_d = sin(2 pi m_d / n_d) / dx_d: the centred difference (f(x + e_d) - f(x - e_d)) / (2 dx_d)
+ *                                           of "diveru" and of the nonlinear term becomes divergence-free
+ *                  Nyquist rule: q_d = 0 for m_d = -n_d / 2 in both forms (the sine gives it by itself; without it the exact form is not
+ *                  Hermitian there and the real part taken at the end would break the projection in those modes);
+ *   shell scale    F(m) <- a[s(m)] F(m);
+ *   noise          depends on (seed, component c counted from 0 at `comp`, global cell index o = i + n_x (j + n_y k)) alone, in 64-bit
+ *                  wrapping arithmetic: mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *                  z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31);  h = mix(mix(seed ^ ((c + 1) * 0x9E3779B97F4A7C15)) + o);
+ *                  value = ((h >> 12) + 0.5) 2^-52 - 0.5: uniform in (-1/2, 1/2), every step exact in double, the same for every box
+ *                  layout and number of ranks.
+ * iamrx_mf_noise: the valid cells of components comp .. comp + ncomp - 1 of a cell-centred array whose boxes tile the domain of g (g
+ * gives n_x, n_y; periodicity and extents are not restricted).
+ * iamrx_mf_filter: dst(dcomp + q) = filtered src(scomp + q), q < ncomp, one component at a time; dst and src may be the same array or
+ * live on different layouts of the same domain; ghost cells are neither read nor written.  Error besides those of the spectra: kind
+ * outside 0 .. 3, kc not > 0 (any kind).
+ * iamrx_mf_solenoidal: dst(dcomp .. dcomp + 2) = the solenoidal part of src(scomp .. scomp + 2); three work arrays.  Error: wavenumber
+ * outside 0 .. 1.
+ * iamrx_mf_synthesize: dst(dcomp .. dcomp + 2) = a random solenoidal field whose kinetic-energy spectrum E(s) = (P_u + P_v + P_w) / 2 is
+ * E_target[0 .. nbins): noise(seed) for c = 0, 1, 2, three forward transforms, the projection, E_now(s) through the shell sums of the
+ * spectra, a(s) = sqrt(E_target(s) / E_now(s)) (a = 0 where E_now(s) = 0 or s = 0), the shell scale, three inverse transforms, the
+ * unpack.  nbins must be that of g.  Error: a negative or non-finite E_target(s); E_target(s) > 0 in a shell where E_now(s) = 0 (s = 0
+ * is never asked for: the field has no mean); in that case dst is not written.
+ * All of them: one 16 N byte work array per component in flight from the arena, no floating-point atomics, sums in the fixed order of
+ * the spectra: the same call gives the same bits, whatever the box layouts.  Collective on several ranks as the spectra are: a gather,
+ * every rank transforms the whole field, the unpack writes the rank's own boxes.  On any error dst is untouched. */
+int iamrx_mf_noise(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, unsigned long long seed);
+int iamrx_mf_filter(const iamrx_geom* g, iamrx_mf dst, int dcomp, iamrx_mf src, int scomp, int ncomp, int kind, double kc);
+int iamrx_mf_solenoidal(const iamrx_geom* g, iamrx_mf dst, int dcomp, iamrx_mf src, int scomp, int wavenumber);
+int iamrx_mf_synthesize(const iamrx_geom* g, iamrx_mf dst, int dcomp, unsigned long long seed, int nbins, const double* E_target, int wavenumber);
+/* measurement aid (tools/bench_filter.py): iamrx_specop_bench_np() = 17 passes with an event between them, ms[17 * r + p]: one filter of
+ * src(scomp) into dst(0) -- 0 pack, 1 2 3 forward x y z, 4 multiplier, 5 6 7 inverse x y z, 8 unpack -- then one synthesis into
+ * dst(0 .. 2) -- 9 noise, 10 nine forward passes, 11 projection, 12 shell sums and a(s), 13 shell scale, 14 nine inverse passes,
+ * 15 unpack -- and 16 one dense_pack of src(scomp) alone, the yardstick of the streaming passes.  Nothing is read back. */
+int iamrx_specop_bench_np(void);
+int iamrx_specop_bench(const iamrx_geom* g, iamrx_mf dst, iamrx_mf src, int scomp, int kind, double kc, int wavenumber, int reps, float* ms);
 /* Structure functions and two-point correlations along the axes (this library's own diagnostic, no upstream counterpart; k_strfn.hip).
  * Unlike the spectra they are defined with walls and on extents that are not powers of two.  For a cell-centred component f on a level
  * whose boxes tile the domain, n = (n_x, n_y, n_z) cells, N = n_x n_y n_z, an axis d and an integer separation r in cells:
