@@ -1258,14 +1258,20 @@ int iamrx_ns_plane_profile(iamrx_ns ns, int dir, int nbins_cap, double* out, int
     IAMRX_CATCH
 }
 int iamrx_spectrum_nq(void) { return SPECTRUM_NQ; }
+// comp .. comp + ncomp - 1, or the refusal under the entry's name
+static std::vector<int> comp_range(const char* who, const MultiFab& S, int comp, int ncomp)
+{
+    if (ncomp < 1 || comp < 0 || comp + ncomp > S.ncomp)
+        throw Error(std::string(who) + ": components " + std::to_string(comp) + " .. " + std::to_string(comp + ncomp - 1) + " outside the array's " + std::to_string(S.ncomp));
+    std::vector<int> comps(ncomp);
+    for (int q = 0; q < ncomp; ++q) comps[q] = comp + q;
+    return comps;
+}
 int iamrx_mf_spectrum(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, int nbins_cap, double* out, long* count, int* nbins)
 {
     IAMRX_TRY
     if (!g || !mf) throw Error("iamrx_mf_spectrum: null geometry or array");
-    if (ncomp < 1 || comp < 0 || comp + ncomp > mf->mf.ncomp)
-        throw Error("iamrx_mf_spectrum: components " + std::to_string(comp) + " .. " + std::to_string(comp + ncomp - 1) + " outside the array's " + std::to_string(mf->mf.ncomp));
-    std::vector<int> comps(ncomp);
-    for (int q = 0; q < ncomp; ++q) comps[q] = comp + q;
+    const std::vector<int> comps = comp_range("iamrx_mf_spectrum", mf->mf, comp, ncomp);
     spectrum_of(to_geom(g), mf->mf, ncomp, comps.data(), nbins_cap, out, count, nbins);
     IAMRX_CATCH
 }
@@ -1292,10 +1298,7 @@ int iamrx_mf_spectrum_k2(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, 
 {
     IAMRX_TRY
     if (!g || !mf) throw Error("iamrx_mf_spectrum_k2: null geometry or array");
-    if (ncomp < 1 || comp < 0 || comp + ncomp > mf->mf.ncomp)
-        throw Error("iamrx_mf_spectrum_k2: components " + std::to_string(comp) + " .. " + std::to_string(comp + ncomp - 1) + " outside the array's " + std::to_string(mf->mf.ncomp));
-    std::vector<int> comps(ncomp);
-    for (int q = 0; q < ncomp; ++q) comps[q] = comp + q;
+    const std::vector<int> comps = comp_range("iamrx_mf_spectrum_k2", mf->mf, comp, ncomp);
     spectrum_k2_of(to_geom(g), mf->mf, ncomp, comps.data(), nbins_cap, out, nbins);
     IAMRX_CATCH
 }

@@ -95,16 +95,13 @@ void convective_bench(const Geometry& g, MultiFab& out, const MultiFab& vel, int
     auto& ctx = Context::get();
     const ConvectArgs p = convect_args(g, out, 0, vel, vcomp);
     if (vel.nlocal() == 0) { for (int r = 0; r < reps; ++r) ms[r] = 0.f; return; }
-    hipEvent_t ev[2];
-    for (auto& e : ev) IAMRX_HIP_CHECK(hipEventCreate(&e));
+    PassTimer t(2);
     for (int r = 0; r < reps; ++r) {
-        IAMRX_HIP_CHECK(hipEventRecord(ev[0], ctx.stream));
+        t.mark();
         convect_launch(*vel.layout, out, vel, p);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[1], ctx.stream));
-        IAMRX_HIP_CHECK(hipEventSynchronize(ev[1]));
-        IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[r], ev[0], ev[1]));
+        t.mark();
+        t.finish(ms + r);
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
     ctx.sync();
 }
 

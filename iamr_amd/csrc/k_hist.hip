@@ -215,11 +215,10 @@ void hist_check_range(const char* who, double lo, double hi, int nbins, int nbin
     if (!std::isfinite(hi - lo)) throw Error(std::string(who) + ": hi - lo overflows");
 }
 
-unsigned long long* hist_begin(size_t nslots)
+DevBuf<unsigned long long> hist_begin(size_t nslots)
 {
-    auto& ctx = Context::get();
-    unsigned long long* d = (unsigned long long*)ctx.alloc(nslots * sizeof(unsigned long long));
-    IAMRX_HIP_CHECK(hipMemsetAsync(d, 0, nslots * sizeof(unsigned long long), ctx.stream));
+    DevBuf<unsigned long long> d(nslots);
+    IAMRX_HIP_CHECK(hipMemsetAsync(d, 0, nslots * sizeof(unsigned long long), Context::get().stream));
     return d;
 }
 
@@ -274,13 +273,12 @@ void hist_add2(const MultiFab& X, int compx, const MultiFab& Y, int compy, const
     else hipLaunchKernelGGL((k_hist2<false>), g, blk, lds, ctx.stream, tiles, ntiles, X.layout->d_boxes, X.d_tab, Y.d_tab, (const FabD*)nullptr, hc, weight, d_counts);
 }
 
-void hist_end(unsigned long long* d_counts, size_t nslots, long long* out)
+void hist_end(const unsigned long long* d_counts, size_t nslots, long long* out)
 {
     auto& ctx = Context::get();
     std::vector<unsigned long long> h(nslots);
     IAMRX_HIP_CHECK(hipMemcpyAsync(h.data(), d_counts, nslots * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx.stream));
     ctx.sync();
-    ctx.free(d_counts);
     const unsigned long long lim = 1ULL << 53;
     if (ctx.comm && ctx.comm->nranks > 1) {
         // the transport carries doubles: integers below 2^53 are summed exactly
@@ -301,21 +299,17 @@ void hist_bench(const MultiFab& S, int ncol, const int* comps, const MultiFab* c
     IAMRX_ASSERT(reps >= 1 && ms && ncol >= 1 && (nby == 0 || ncol == 2));
     auto& ctx = Context::get();
     const size_t nslots = nby > 0 ? (size_t)nbins * nby + 1 : (size_t)ncol * (nbins + 3);
-    unsigned long long* d = hist_begin(nslots);
+    const DevBuf<unsigned long long> d = hist_begin(nslots);
     const int nb2[2] = {nbins, nby};
-    hipEvent_t ev[2];
-    for (auto& e : ev) IAMRX_HIP_CHECK(hipEventCreate(&e));
+    PassTimer t(2);
     for (int r = 0; r < reps; ++r) {
-        IAMRX_HIP_CHECK(hipEventRecord(ev[0], ctx.stream));
+        t.mark();
         if (nby > 0) hist_add2(S, comps[0], S, comps[1], cov, lo, hi, nb2, 1ULL, d);
         else hist_add(S, ncol, comps, cov, lo, hi, nbins, 1ULL, d);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[1], ctx.stream));
-        IAMRX_HIP_CHECK(hipEventSynchronize(ev[1]));
-        IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[r], ev[0], ev[1]));
+        t.mark();
+        t.finish(ms + r);
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
     ctx.sync();
-    ctx.free(d);
 }
 
 }  // namespace iamrx

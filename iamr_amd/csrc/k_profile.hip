@@ -284,8 +284,7 @@ void profile_reduce(int nlev, const ProfileLevel* L, int dir, int bin_level, int
         f.w[l] = 1.0 / (double)(nperp << std::max(l - bin_level, 0));
     }
     const size_t nout = (size_t)NQ * f.nbins;
-    ctx.ensure_scratch(nout + 16);
-    double* buf = (double*)ctx.alloc((total + nout) * sizeof(double));
+    DevBuf<double> buf(total + nout);
     for (int l = 0; l < nlev; ++l) {
         const MultiFab& S = *L[l].S;
         const Layout& lay = *S.layout;
@@ -300,7 +299,8 @@ void profile_reduce(int nlev, const ProfileLevel* L, int dir, int bin_level, int
         const int* csr = (const int*)profile_list(lay, dir, 1, &n_csr);
         n_items /= 2;
         const long nslots = profile_nslots(lay, dir);
-        double* partials = (double*)ctx.alloc((size_t)NQ * nslots * sizeof(double));
+        DevBuf<double> part((size_t)NQ * nslots);           // freed behind the launches of this level that use it (DevBuf, mf.h)
+        double* partials = part;
         const FabD* cov = L[l].cov ? L[l].cov->d_tab : nullptr;
         const dim3 g((unsigned)n_items), blk(256);
         if (dir == 0) {
@@ -311,15 +311,12 @@ void profile_reduce(int nlev, const ProfileLevel* L, int dir, int bin_level, int
             else hipLaunchKernelGGL((k_profile_plane<false>), g, blk, 0, ctx.stream, items, lay.d_boxes, S.d_tab, cov, dir, rho_comp, trac_comp, partials, nslots);
         }
         hipLaunchKernelGGL(k_profile_bins, dim3((unsigned)((NQ * f.n[l] + 3) / 4)), blk, 0, ctx.stream, partials, nslots, csr, csr + f.n[l] + 1, f.n[l], lev);
-        ctx.free(partials);
     }
     double* d_out = buf + total;
     hipLaunchKernelGGL(k_profile_fold, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, ctx.stream, f, buf, d_out);
     if (nranks > 1) ctx.comm->allreduce_device(d_out, (int)nout, ReduceOp::Sum, ctx.stream);
-    IAMRX_HIP_CHECK(hipMemcpyAsync(ctx.h_scratch, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
-    ctx.sync();
-    for (size_t q = 0; q < nout; ++q) out[q] = ctx.h_scratch[q];
-    ctx.free(buf);
+    const double* h = ctx.read_back(d_out, nout);
+    std::copy(h, h + nout, out);
 }
 
 }  // namespace iamrx

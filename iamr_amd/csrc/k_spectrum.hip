@@ -305,7 +305,7 @@ struct SpecPlan {
     int ln[3];
     long N;
     int nwg;
-    double2* tw[3] = {nullptr, nullptr, nullptr};
+    DevBuf<double2> tw[3];  // exp(-2 pi i q / n_d), q < n_d / 2
     int xp, ytw, ztw;       // log2 of the pencils per workgroup of the three passes
     int pair;               // two butterfly stages at a time (1, the default) or one
 };
@@ -332,29 +332,22 @@ SpecPlan spec_plan(const Geometry& g, int nbins)
     p.xp = std::min(std::max(le - 1 - p.ln[0], 0), p.ln[1] + p.ln[2]);        // (the x pass measured fastest at half the image of y and z)
     p.ytw = std::min(std::max(le - p.ln[1], 2), p.ln[0]);
     p.ztw = std::min(std::max(le - p.ln[2], 2), p.ln[0]);
-    return p;
-}
-
-void spec_tables(SpecPlan& p)
-{
-    auto& ctx = Context::get();
     for (int q = 0; q < 3; ++q) {
-        const int n = 1 << p.ln[q];
-        const std::vector<double2> w = spec_twiddles(n);
-        p.tw[q] = (double2*)ctx.alloc(w.size() * sizeof(double2));
-        ctx.upload_async(p.tw[q], w.data(), w.size() * sizeof(double2));
+        const std::vector<double2> w = spec_twiddles(1 << p.ln[q]);
+        p.tw[q] = DevBuf<double2>(w.size());
+        Context::get().upload_async(p.tw[q], w.data(), w.size() * sizeof(double2));
     }
+    return p;
 }
 
 void spec_pack(const SpecPlan& p, const Geometry& g, const MultiFab& S, int comp, double2* W)
 {
     auto& ctx = Context::get();
     if (!dense_needs_gather(S)) { dense_pack(g, S, comp, (double*)W, true); return; }
-    double* R = (double*)ctx.alloc((size_t)p.N * sizeof(double));
+    DevBuf<double> R((size_t)p.N);          // freed behind the launch that reads it (DevBuf, mf.h)
     dense_gather(g, S, comp, R);
     hipLaunchKernelGGL(k_spec_expand, dim3((unsigned)std::min<long>((p.N + 4 * SPEC_THREADS - 1) / (4 * SPEC_THREADS), 65535)), dim3(SPEC_THREADS), 0,
-                       ctx.stream, R, W, p.N);
-    ctx.free(R);
+                       ctx.stream, R.get(), W, p.N);
 }
 
 // dir = 0, 1, 2: the transform along that axis of the whole array
@@ -366,7 +359,7 @@ void spec_fft(const SpecPlan& p, int dir, double2* W)
     if (dir == 0) {
         const int pen = 1 << p.xp;
         const size_t lds = (size_t)pen * (n + (n >> 5)) * sizeof(double2);
-        hipLaunchKernelGGL((k_spec_fft<true>), dim3((unsigned)(p.N / ((long)pen * n))), dim3(SPEC_THREADS), lds, ctx.stream, W, p.tw[0], ln, p.xp, 1, 1L, 0L, p.pair);
+        hipLaunchKernelGGL((k_spec_fft<true>), dim3((unsigned)(p.N / ((long)pen * n))), dim3(SPEC_THREADS), lds, ctx.stream, W, p.tw[0].get(), ln, p.xp, 1, 1L, 0L, p.pair);
         return;
     }
     const int ltw = dir == 1 ? p.ytw : p.ztw;
@@ -374,7 +367,13 @@ void spec_fft(const SpecPlan& p, int dir, double2* W)
     const size_t lds = ((size_t)n << ltw) * sizeof(double2);
     const long estride = dir == 1 ? nx : nx * ny, ostride = dir == 1 ? nx * ny : nx;
     const long other = dir == 1 ? p.sh.nz : p.sh.ny;
-    hipLaunchKernelGGL((k_spec_fft<false>), dim3((unsigned)(ntile * other)), dim3(SPEC_THREADS), lds, ctx.stream, W, p.tw[dir], ln, ltw, ntile, estride, ostride, p.pair);
+    hipLaunchKernelGGL((k_spec_fft<false>), dim3((unsigned)(ntile * other)), dim3(SPEC_THREADS), lds, ctx.stream, W, p.tw[dir].get(), ln, ltw, ntile, estride, ostride, p.pair);
+}
+
+// the forward transform of the whole array: the three passes; t (or null): a mark after each
+void spec_forward(const SpecPlan& p, double2* W, PassTimer* t = nullptr)
+{
+    for (int d = 0; d < 3; ++d) { spec_fft(p, d, W); PassTimer::mark(t); }
 }
 
 // the shell sums of the NV values of val: out[q * nbins + s] = scale * sum; slots: NV * nwg * nbins entries
@@ -401,12 +400,11 @@ void spec_pack_pair(const SpecPlan& p, const Geometry& g, const MultiFab& A, int
         dense_pack_imag(g, B, bcomp, (double*)W);
         return;
     }
-    double* R = (double*)ctx.alloc((size_t)2 * p.N * sizeof(double));
+    DevBuf<double> R((size_t)2 * p.N);
     dense_gather(g, A, acomp, R);
     dense_gather(g, B, bcomp, R + p.N);
     hipLaunchKernelGGL(k_spec_expand2, dim3((unsigned)std::min<long>((p.N + 4 * SPEC_THREADS - 1) / (4 * SPEC_THREADS), 65535)), dim3(SPEC_THREADS), 0,
-                       ctx.stream, R, R + p.N, W, p.N);
-    ctx.free(R);
+                       ctx.stream, R.get(), R + p.N, W, p.N);
 }
 
 // (2 pi / L_max)^2: the factor between kappa^2 and k^2
@@ -418,11 +416,62 @@ double spec_k2_unit(const Geometry& g)
     return k0 * k0;
 }
 
-void spec_check(const Geometry& g, const MultiFab& S, int comp)
+void spec_check(const Geometry& g, const MultiFab& S, int nq, const int* comps)
 {
     if (!S.type.cell()) throw Error("spectrum: the array is not cell-centred");
-    if (comp < 0 || comp >= S.ncomp) throw Error("spectrum: component " + std::to_string(comp) + " outside 0 .. " + std::to_string(S.ncomp - 1));
+    for (int q = 0; q < nq; ++q)
+        if (comps[q] < 0 || comps[q] >= S.ncomp) throw Error("spectrum: component " + std::to_string(comps[q]) + " outside 0 .. " + std::to_string(S.ncomp - 1));
     dense_check_cover("spectrum", g, *S.layout);
+}
+
+// the modes per shell ride in the slots and the output of the sums
+static_assert(sizeof(unsigned long long) == sizeof(double), "the counts share the slots of the sums");
+
+// The shell sums of n transforms.  pack(p, q, W) fills the work array with transform q (one component, or a packed pair), val(W) makes the
+// functor whose Val::NV columns land in out[(Val::NV * q + v) * nbins + s]; count (or null): the modes of every shell.
+template <class Pack, class MakeVal>
+void spec_shell_sums(const Geometry& g, int n, int nbins, const Pack& pack, const MakeVal& val, double* out, long* count)
+{
+    using Val = decltype(val((const double2*)nullptr));
+    const SpecPlan p = spec_plan(g, nbins);
+    const size_t nsum = (size_t)Val::NV * n * nbins;
+    DevBuf<double2> W((size_t)p.N);
+    DevBuf<double> slots((size_t)Val::NV * p.nwg * nbins), d_out(nsum + nbins);
+    const double invN = 1.0 / (double)p.N;
+    for (int q = 0; q < n; ++q) {
+        pack(p, q, W);
+        spec_forward(p, W);
+        spec_bin(p, val(W), slots, invN * invN, d_out + (size_t)Val::NV * q * nbins);
+    }
+    if (count) spec_bin(p, CountVal{}, (unsigned long long*)slots.get(), 1.0, (unsigned long long*)(d_out + nsum));
+    const double* h = Context::get().read_back(d_out, nsum + (count ? nbins : 0));
+    std::copy(h, h + nsum, out);
+    for (int s = 0; count && s < nbins; ++s) {
+        unsigned long long c;
+        std::memcpy(&c, h + nsum + s, sizeof c);
+        count[s] = (long)c;
+    }
+}
+
+// measurement aid: reps times the five passes of one transform -- pack, x, y, z, the shell sums -- ms[5 * r + pass]
+template <class Pack, class MakeVal>
+void spec_bench_passes(const Geometry& g, int nbins, const Pack& pack, const MakeVal& val, int reps, float* ms)
+{
+    using Val = decltype(val((const double2*)nullptr));
+    const SpecPlan p = spec_plan(g, nbins);
+    DevBuf<double2> W((size_t)p.N);
+    DevBuf<double> slots((size_t)Val::NV * p.nwg * nbins), d_out((size_t)Val::NV * nbins);
+    PassTimer t(6);
+    const double invN = 1.0 / (double)p.N;
+    for (int r = 0; r < reps; ++r) {
+        t.mark();
+        pack(p, W);
+        t.mark();
+        spec_forward(p, W, &t);
+        spec_bin(p, val(W), slots, invN * invN, d_out);
+        t.mark();
+        t.finish(ms + 5 * r);
+    }
 }
 
 }  // namespace
@@ -453,40 +502,9 @@ int spectrum_nbins(const Geometry& g)
 void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* comps, int nbins, double* out, long* count)
 {
     IAMRX_ASSERT(nq >= 1 && nbins == spectrum_nbins(g));
-    if (!S.type.cell()) throw Error("spectrum: the array is not cell-centred");
-    for (int q = 0; q < nq; ++q)
-        if (comps[q] < 0 || comps[q] >= S.ncomp) throw Error("spectrum: component " + std::to_string(comps[q]) + " outside 0 .. " + std::to_string(S.ncomp - 1));
-    dense_check_cover("spectrum", g, *S.layout);
-    auto& ctx = Context::get();
-    SpecPlan p = spec_plan(g, nbins);
-    spec_tables(p);
-    const size_t nout = (size_t)(nq + 1) * nbins;
-    ctx.ensure_scratch(nout + 16);
-    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
-    double* slots = (double*)ctx.alloc((size_t)p.nwg * nbins * sizeof(double));
-    double* d_out = (double*)ctx.alloc(nout * sizeof(double));
-    const double invN = 1.0 / (double)p.N;
-    for (int q = 0; q < nq; ++q) {
-        spec_pack(p, g, S, comps[q], W);
-        for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
-        spec_bin(p, PowerVal{W}, slots, invN * invN, d_out + (size_t)q * nbins);
-    }
-    if (count) {
-        static_assert(sizeof(unsigned long long) == sizeof(double), "the counts share the slots of the sums");
-        spec_bin(p, CountVal{}, (unsigned long long*)slots, 1.0, (unsigned long long*)(d_out + (size_t)nq * nbins));
-    }
-    IAMRX_HIP_CHECK(hipMemcpyAsync(ctx.h_scratch, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
-    ctx.sync();
-    for (size_t q = 0; q < (size_t)nq * nbins; ++q) out[q] = ctx.h_scratch[q];
-    if (count) {
-        for (int s = 0; s < nbins; ++s) {
-            unsigned long long c;
-            std::memcpy(&c, ctx.h_scratch + (size_t)nq * nbins + s, sizeof c);
-            count[s] = (long)c;
-        }
-    }
-    ctx.free(d_out); ctx.free(slots); ctx.free(W);
-    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+    spec_check(g, S, nq, comps);
+    spec_shell_sums(g, nq, nbins, [&](const SpecPlan& p, int q, double2* W) { spec_pack(p, g, S, comps[q], W); },
+                    [](const double2* W) { return PowerVal{W}; }, out, count);
 }
 
 void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, float* ms)
@@ -494,28 +512,7 @@ void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, fl
     const int nbins = spectrum_nbins(g);
     dense_check_cover("spectrum", g, *S.layout);
     IAMRX_ASSERT(S.type.cell() && comp >= 0 && comp < S.ncomp && reps >= 1);
-    auto& ctx = Context::get();
-    SpecPlan p = spec_plan(g, nbins);
-    spec_tables(p);
-    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
-    double* slots = (double*)ctx.alloc((size_t)p.nwg * nbins * sizeof(double));
-    double* d_out = (double*)ctx.alloc((size_t)nbins * sizeof(double));
-    hipEvent_t ev[6];
-    for (auto& e : ev) IAMRX_HIP_CHECK(hipEventCreate(&e));
-    const double invN = 1.0 / (double)p.N;
-    for (int r = 0; r < reps; ++r) {
-        IAMRX_HIP_CHECK(hipEventRecord(ev[0], ctx.stream));
-        spec_pack(p, g, S, comp, W);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[1], ctx.stream));
-        for (int d = 0; d < 3; ++d) { spec_fft(p, d, W); IAMRX_HIP_CHECK(hipEventRecord(ev[2 + d], ctx.stream)); }
-        spec_bin(p, PowerVal{W}, slots, invN * invN, d_out);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[5], ctx.stream));
-        IAMRX_HIP_CHECK(hipEventSynchronize(ev[5]));
-        for (int q = 0; q < 5; ++q) IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[5 * r + q], ev[q], ev[q + 1]));
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    ctx.free(d_out); ctx.free(slots); ctx.free(W);
-    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+    spec_bench_passes(g, nbins, [&](const SpecPlan& p, double2* W) { spec_pack(p, g, S, comp, W); }, [](const double2* W) { return PowerVal{W}; }, reps, ms);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- co-spectra
@@ -524,90 +521,31 @@ void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, fl
 void cospectrum_compute(const Geometry& g, int npair, const SpecPair* pairs, int nbins, double* out, long* count)
 {
     IAMRX_ASSERT(npair >= 1 && pairs && nbins == spectrum_nbins(g));
-    for (int q = 0; q < npair; ++q) { spec_check(g, *pairs[q].a, pairs[q].acomp); spec_check(g, *pairs[q].b, pairs[q].bcomp); }
-    auto& ctx = Context::get();
-    SpecPlan p = spec_plan(g, nbins);
-    spec_tables(p);
-    constexpr int NV = CoVal::NV;
-    static_assert(NV == COSPEC_NV, "the columns of a pair");
-    const size_t nout = (size_t)(NV * npair + 1) * nbins;
-    ctx.ensure_scratch(nout + 16);
-    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
-    double* slots = (double*)ctx.alloc((size_t)NV * p.nwg * nbins * sizeof(double));
-    double* d_out = (double*)ctx.alloc(nout * sizeof(double));
-    const double invN = 1.0 / (double)p.N, k2u = spec_k2_unit(g);
-    for (int q = 0; q < npair; ++q) {
-        spec_pack_pair(p, g, *pairs[q].a, pairs[q].acomp, *pairs[q].b, pairs[q].bcomp, W);
-        for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
-        spec_bin(p, CoVal{W, k2u}, slots, invN * invN, d_out + (size_t)NV * q * nbins);
-    }
-    if (count) spec_bin(p, CountVal{}, (unsigned long long*)slots, 1.0, (unsigned long long*)(d_out + (size_t)NV * npair * nbins));
-    IAMRX_HIP_CHECK(hipMemcpyAsync(ctx.h_scratch, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
-    ctx.sync();
-    for (size_t q = 0; q < (size_t)NV * npair * nbins; ++q) out[q] = ctx.h_scratch[q];
-    if (count) {
-        for (int s = 0; s < nbins; ++s) {
-            unsigned long long c;
-            std::memcpy(&c, ctx.h_scratch + (size_t)NV * npair * nbins + s, sizeof c);
-            count[s] = (long)c;
-        }
-    }
-    ctx.free(d_out); ctx.free(slots); ctx.free(W);
-    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+    for (int q = 0; q < npair; ++q) { spec_check(g, *pairs[q].a, 1, &pairs[q].acomp); spec_check(g, *pairs[q].b, 1, &pairs[q].bcomp); }
+    static_assert(CoVal::NV == COSPEC_NV, "the columns of a pair");
+    const double k2u = spec_k2_unit(g);
+    spec_shell_sums(g, npair, nbins,
+                    [&](const SpecPlan& p, int q, double2* W) { spec_pack_pair(p, g, *pairs[q].a, pairs[q].acomp, *pairs[q].b, pairs[q].bcomp, W); },
+                    [&](const double2* W) { return CoVal{W, k2u}; }, out, count);
 }
 
 void spectrum_k2_compute(const Geometry& g, const MultiFab& S, int nq, const int* comps, int nbins, double* out)
 {
     IAMRX_ASSERT(nq >= 1 && nbins == spectrum_nbins(g));
-    for (int q = 0; q < nq; ++q) spec_check(g, S, comps[q]);
-    auto& ctx = Context::get();
-    SpecPlan p = spec_plan(g, nbins);
-    spec_tables(p);
-    const size_t nout = (size_t)nq * nbins;
-    ctx.ensure_scratch(nout + 16);
-    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
-    double* slots = (double*)ctx.alloc((size_t)p.nwg * nbins * sizeof(double));
-    double* d_out = (double*)ctx.alloc(nout * sizeof(double));
-    const double invN = 1.0 / (double)p.N, k2u = spec_k2_unit(g);
-    for (int q = 0; q < nq; ++q) {
-        spec_pack(p, g, S, comps[q], W);
-        for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
-        spec_bin(p, K2Val{W, k2u}, slots, invN * invN, d_out + (size_t)q * nbins);
-    }
-    IAMRX_HIP_CHECK(hipMemcpyAsync(ctx.h_scratch, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
-    ctx.sync();
-    for (size_t q = 0; q < nout; ++q) out[q] = ctx.h_scratch[q];
-    ctx.free(d_out); ctx.free(slots); ctx.free(W);
-    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+    for (int q = 0; q < nq; ++q) spec_check(g, S, 1, &comps[q]);
+    const double k2u = spec_k2_unit(g);
+    spec_shell_sums(g, nq, nbins, [&](const SpecPlan& p, int q, double2* W) { spec_pack(p, g, S, comps[q], W); },
+                    [&](const double2* W) { return K2Val{W, k2u}; }, out, nullptr);
 }
 
 void cospectrum_bench(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int reps, float* ms)
 {
     const int nbins = spectrum_nbins(g);
-    spec_check(g, A, acomp); spec_check(g, B, bcomp);
+    spec_check(g, A, 1, &acomp); spec_check(g, B, 1, &bcomp);
     IAMRX_ASSERT(reps >= 1);
-    auto& ctx = Context::get();
-    SpecPlan p = spec_plan(g, nbins);
-    spec_tables(p);
-    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
-    double* slots = (double*)ctx.alloc((size_t)CoVal::NV * p.nwg * nbins * sizeof(double));
-    double* d_out = (double*)ctx.alloc((size_t)CoVal::NV * nbins * sizeof(double));
-    hipEvent_t ev[6];
-    for (auto& e : ev) IAMRX_HIP_CHECK(hipEventCreate(&e));
-    const double invN = 1.0 / (double)p.N, k2u = spec_k2_unit(g);
-    for (int r = 0; r < reps; ++r) {
-        IAMRX_HIP_CHECK(hipEventRecord(ev[0], ctx.stream));
-        spec_pack_pair(p, g, A, acomp, B, bcomp, W);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[1], ctx.stream));
-        for (int d = 0; d < 3; ++d) { spec_fft(p, d, W); IAMRX_HIP_CHECK(hipEventRecord(ev[2 + d], ctx.stream)); }
-        spec_bin(p, CoVal{W, k2u}, slots, invN * invN, d_out);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[5], ctx.stream));
-        IAMRX_HIP_CHECK(hipEventSynchronize(ev[5]));
-        for (int q = 0; q < 5; ++q) IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[5 * r + q], ev[q], ev[q + 1]));
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    ctx.free(d_out); ctx.free(slots); ctx.free(W);
-    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+    const double k2u = spec_k2_unit(g);
+    spec_bench_passes(g, nbins, [&](const SpecPlan& p, double2* W) { spec_pack_pair(p, g, A, acomp, B, bcomp, W); },
+                      [&](const double2* W) { return CoVal{W, k2u}; }, reps, ms);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the way back
@@ -779,15 +717,13 @@ std::vector<double> spec_wave_axis(int n, double L, double dx, int wavenumber)
 }
 
 struct SpecAxisTables {
-    double* d[3] = {nullptr, nullptr, nullptr};
+    DevBuf<double> d[3];
     SpecAxes axes() const { return SpecAxes{d[0], d[1], d[2]}; }
     void upload(int q, const std::vector<double>& t)
     {
-        auto& ctx = Context::get();
-        d[q] = (double*)ctx.alloc(t.size() * sizeof(double));
-        ctx.upload_async(d[q], t.data(), t.size() * sizeof(double));
+        d[q] = DevBuf<double>(t.size());
+        Context::get().upload_async(d[q], t.data(), t.size() * sizeof(double));
     }
-    void release() { for (auto& p : d) if (p) { Context::get().free(p); p = nullptr; } }
 };
 
 SpecAxisTables spec_filter_tables(const SpecPlan& p, int kind, double kc)
@@ -835,30 +771,39 @@ void specop_check(const Geometry& g, const MultiFab& S, int comp, int ncomp)
 
 void specop_written(MultiFab& S) { S.uniform_marked = false; S.varying_marked = false; }
 
-// the device part of a synthesis on the work arrays W[3]: noise .. shell scale with the conjugate and 1 / N; ev (or null): the events
-// of specop_bench after each step.  d_P: 3 * nbins, d_a: nbins, d_bad: one int preset to INT_MAX
-void spec_synth_modes(const SpecPlan& p, const SpecAxisTables& qt, unsigned long long seed, double2* const W[3], double* slots, double* d_P,
-                      const double* d_Et, double* d_a, int* d_bad, hipEvent_t* ev)
+// the work arrays of a synthesis.  P: P_u, P_v, P_w, the target, the shell factors a (nbins each); bad: one int, preset to INT_MAX
+struct SynthWork {
+    DevBuf<double2> W[3];
+    DevBuf<double> slots, P;
+    DevBuf<int> bad;
+    explicit SynthWork(const SpecPlan& p)
+        : W{DevBuf<double2>((size_t)p.N), DevBuf<double2>((size_t)p.N), DevBuf<double2>((size_t)p.N)}, slots((size_t)p.nwg * p.sh.nbins),
+          P((size_t)5 * p.sh.nbins), bad(1) {}
+};
+
+// the device part of a synthesis: noise .. shell scale with the conjugate and 1 / N; t (or null): the timer of specop_bench, marked
+// after each of the six steps
+void spec_synth_modes(const SpecPlan& p, const SpecAxisTables& qt, unsigned long long seed, const SynthWork& w, PassTimer* t)
 {
     auto& ctx = Context::get();
     const int nbins = p.sh.nbins;
     const double invN = 1.0 / (double)p.N;
-    auto mark = [&](int q) { if (ev) IAMRX_HIP_CHECK(hipEventRecord(ev[q], ctx.stream)); };
+    const DevBuf<double2>* W = w.W;
+    double* d_P = w.P;
     for (int c = 0; c < 3; ++c) spec_noise_dense(p, seed, c, W[c]);
-    mark(0);
-    for (int c = 0; c < 3; ++c)
-        for (int d = 0; d < 3; ++d) spec_fft(p, d, W[c]);
-    mark(1);
+    PassTimer::mark(t);
+    for (int c = 0; c < 3; ++c) spec_forward(p, W[c]);
+    PassTimer::mark(t);
     spec_mul(p, SolenoidalOp{W[0], W[1], W[2], qt.axes()}, false);
-    mark(2);
-    for (int c = 0; c < 3; ++c) spec_bin(p, PowerVal{W[c]}, slots, invN * invN, d_P + (size_t)c * nbins);
-    hipLaunchKernelGGL(k_spec_coef, dim3((unsigned)((nbins + SPEC_THREADS - 1) / SPEC_THREADS)), dim3(SPEC_THREADS), 0, ctx.stream, d_P, d_Et, nbins, d_a, d_bad);
-    mark(3);
-    spec_mul(p, ShellScaleOp{W[0], W[1], W[2], d_a}, true);
-    mark(4);
-    for (int c = 0; c < 3; ++c)
-        for (int d = 0; d < 3; ++d) spec_fft(p, d, W[c]);
-    mark(5);
+    PassTimer::mark(t);
+    for (int c = 0; c < 3; ++c) spec_bin(p, PowerVal{W[c]}, w.slots, invN * invN, d_P + (size_t)c * nbins);
+    hipLaunchKernelGGL(k_spec_coef, dim3((unsigned)((nbins + SPEC_THREADS - 1) / SPEC_THREADS)), dim3(SPEC_THREADS), 0, ctx.stream, d_P, d_P + (size_t)3 * nbins,
+                       nbins, d_P + (size_t)4 * nbins, w.bad.get());
+    PassTimer::mark(t);
+    spec_mul(p, ShellScaleOp{W[0], W[1], W[2], d_P + (size_t)4 * nbins}, true);
+    PassTimer::mark(t);
+    for (int c = 0; c < 3; ++c) spec_forward(p, W[c]);
+    PassTimer::mark(t);
 }
 
 }  // namespace
@@ -883,24 +828,20 @@ void specop_filter(const Geometry& g, MultiFab& dst, int dcomp, const MultiFab& 
     specop_check(g, dst, dcomp, ncomp);
     if (kind < 0 || kind >= SPECOP_NKIND) throw Error("spectrum: filter kind " + std::to_string(kind) + " outside 0 .. " + std::to_string(SPECOP_NKIND - 1));
     if (!(kc > 0.0) || !std::isfinite(kc)) throw Error("spectrum: the filter's cut-off kc must be positive and finite");
-    auto& ctx = Context::get();
-    SpecPlan p = spec_plan(g, nbins);
-    spec_tables(p);
-    SpecAxisTables gt = spec_filter_tables(p, kind, kc);
-    double2* W = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+    const SpecPlan p = spec_plan(g, nbins);
+    const SpecAxisTables gt = spec_filter_tables(p, kind, kc);
+    DevBuf<double2> W((size_t)p.N);
     const bool down = &dst == &src && dcomp > scomp;        // overlapping ranges of one array: never read what was already written
     for (int c = 0; c < ncomp; ++c) {
         const int q = down ? ncomp - 1 - c : c;
         spec_pack(p, g, src, scomp + q, W);
-        for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
+        spec_forward(p, W);
         spec_mul(p, FilterOp{W, gt.axes(), kind == 1, kc * kc}, true);
-        for (int d = 0; d < 3; ++d) spec_fft(p, d, W);
-        dense_unpack(g, dst, dcomp + q, (const double*)W, 1.0);
+        spec_forward(p, W);
+        dense_unpack(g, dst, dcomp + q, (const double*)W.get(), 1.0);
     }
     specop_written(dst);
-    ctx.sync();
-    ctx.free(W); gt.release();
-    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+    Context::get().sync();
 }
 
 void specop_solenoidal(const Geometry& g, MultiFab& dst, int dcomp, const MultiFab& src, int scomp, int wavenumber)
@@ -909,26 +850,21 @@ void specop_solenoidal(const Geometry& g, MultiFab& dst, int dcomp, const MultiF
     specop_check(g, src, scomp, 3);
     specop_check(g, dst, dcomp, 3);
     if (wavenumber < 0 || wavenumber >= SPECOP_NWAVE) throw Error("spectrum: wavenumber form " + std::to_string(wavenumber) + " outside 0 .. " + std::to_string(SPECOP_NWAVE - 1));
-    auto& ctx = Context::get();
-    SpecPlan p = spec_plan(g, nbins);
-    spec_tables(p);
-    SpecAxisTables qt = spec_wave_tables(p, g, wavenumber);
-    double2* W[3];
+    const SpecPlan p = spec_plan(g, nbins);
+    const SpecAxisTables qt = spec_wave_tables(p, g, wavenumber);
+    DevBuf<double2> W[3];
     for (int c = 0; c < 3; ++c) {
-        W[c] = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
+        W[c] = DevBuf<double2>((size_t)p.N);
         spec_pack(p, g, src, scomp + c, W[c]);
-        for (int d = 0; d < 3; ++d) spec_fft(p, d, W[c]);
+        spec_forward(p, W[c]);
     }
     spec_mul(p, SolenoidalOp{W[0], W[1], W[2], qt.axes()}, true);
     for (int c = 0; c < 3; ++c) {
-        for (int d = 0; d < 3; ++d) spec_fft(p, d, W[c]);
-        dense_unpack(g, dst, dcomp + c, (const double*)W[c], 1.0);
+        spec_forward(p, W[c]);
+        dense_unpack(g, dst, dcomp + c, (const double*)W[c].get(), 1.0);
     }
     specop_written(dst);
-    ctx.sync();
-    for (int c = 0; c < 3; ++c) ctx.free(W[c]);
-    qt.release();
-    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
+    Context::get().sync();
 }
 
 void specop_synthesize(const Geometry& g, MultiFab& dst, int dcomp, unsigned long long seed, int nbins, const double* E_target, int wavenumber)
@@ -941,32 +877,21 @@ void specop_synthesize(const Geometry& g, MultiFab& dst, int dcomp, unsigned lon
     for (int s = 0; s < nb; ++s)
         if (!(E_target[s] >= 0.0) || !std::isfinite(E_target[s])) throw Error("spectrum: the target spectrum of shell " + std::to_string(s) + " is negative or not finite");
     auto& ctx = Context::get();
-    SpecPlan p = spec_plan(g, nb);
-    spec_tables(p);
-    SpecAxisTables qt = spec_wave_tables(p, g, wavenumber);
-    double2* W[3];
-    for (int c = 0; c < 3; ++c) W[c] = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
-    double* slots = (double*)ctx.alloc((size_t)p.nwg * nb * sizeof(double));
-    double* d_P = (double*)ctx.alloc((size_t)5 * nb * sizeof(double));            // P_u, P_v, P_w, the target, a
-    int* d_bad = (int*)ctx.alloc(sizeof(int));
+    const SpecPlan p = spec_plan(g, nb);
+    const SpecAxisTables qt = spec_wave_tables(p, g, wavenumber);
+    const SynthWork w(p);
     const int none = 0x7fffffff;
     int bad = none;
-    ctx.upload_async(d_P + (size_t)3 * nb, E_target, (size_t)nb * sizeof(double));
-    ctx.upload_async(d_bad, &none, sizeof(int));
-    spec_synth_modes(p, qt, seed, W, slots, d_P, d_P + (size_t)3 * nb, d_P + (size_t)4 * nb, d_bad, nullptr);
-    IAMRX_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+    ctx.upload_async(w.P + (size_t)3 * nb, E_target, (size_t)nb * sizeof(double));
+    ctx.upload_async(w.bad, &none, sizeof(int));
+    spec_synth_modes(p, qt, seed, w, nullptr);
+    IAMRX_HIP_CHECK(hipMemcpyAsync(&bad, w.bad, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
     ctx.sync();
-    if (bad == none) {
-        for (int c = 0; c < 3; ++c) dense_unpack(g, dst, dcomp + c, (const double*)W[c], 1.0);
-        specop_written(dst);
-        ctx.sync();
-    }
-    for (int c = 0; c < 3; ++c) ctx.free(W[c]);
-    ctx.free(d_bad); ctx.free(d_P); ctx.free(slots);
-    qt.release();
-    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
     if (bad != none)
         throw Error("spectrum: the target spectrum asks for energy in shell " + std::to_string(bad) + ", where the projected noise has none");
+    for (int c = 0; c < 3; ++c) dense_unpack(g, dst, dcomp + c, (const double*)w.W[c].get(), 1.0);
+    specop_written(dst);
+    ctx.sync();
 }
 
 void specop_bench(const Geometry& g, MultiFab& dst, const MultiFab& src, int scomp, int kind, double kc, int wavenumber, int reps, float* ms)
@@ -976,44 +901,32 @@ void specop_bench(const Geometry& g, MultiFab& dst, const MultiFab& src, int sco
     specop_check(g, dst, 0, 3);
     IAMRX_ASSERT(kind >= 0 && kind < SPECOP_NKIND && kc > 0.0 && wavenumber >= 0 && wavenumber < SPECOP_NWAVE && reps >= 1);
     auto& ctx = Context::get();
-    SpecPlan p = spec_plan(g, nbins);
-    spec_tables(p);
-    SpecAxisTables gt = spec_filter_tables(p, kind, kc), qt = spec_wave_tables(p, g, wavenumber);
-    double2* W[3];
-    for (int c = 0; c < 3; ++c) W[c] = (double2*)ctx.alloc((size_t)p.N * sizeof(double2));
-    double* slots = (double*)ctx.alloc((size_t)p.nwg * nbins * sizeof(double));
-    double* d_P = (double*)ctx.alloc((size_t)5 * nbins * sizeof(double));
-    int* d_bad = (int*)ctx.alloc(sizeof(int));
-    IAMRX_HIP_CHECK(hipMemsetAsync(d_P, 0, (size_t)5 * nbins * sizeof(double), ctx.stream));      // target 0: a = 0, the passes cost the same
-    IAMRX_HIP_CHECK(hipMemsetAsync(d_bad, 0x7f, sizeof(int), ctx.stream));
+    const SpecPlan p = spec_plan(g, nbins);
+    const SpecAxisTables gt = spec_filter_tables(p, kind, kc), qt = spec_wave_tables(p, g, wavenumber);
+    const SynthWork w(p);
+    double2* W0 = w.W[0];
+    IAMRX_HIP_CHECK(hipMemsetAsync(w.P, 0, (size_t)5 * nbins * sizeof(double), ctx.stream));      // target 0: a = 0, the passes cost the same
+    IAMRX_HIP_CHECK(hipMemsetAsync(w.bad, 0x7f, sizeof(int), ctx.stream));
     constexpr int NP = SPECOP_BENCH_NP;
-    hipEvent_t ev[NP + 1];
-    for (auto& e : ev) IAMRX_HIP_CHECK(hipEventCreate(&e));
+    PassTimer t(NP + 1);
     for (int r = 0; r < reps; ++r) {
-        int q = 0;
-        IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream));
-        spec_pack(p, g, src, scomp, W[0]);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream));
-        for (int d = 0; d < 3; ++d) { spec_fft(p, d, W[0]); IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream)); }
-        spec_mul(p, FilterOp{W[0], gt.axes(), kind == 1, kc * kc}, true);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream));
-        for (int d = 0; d < 3; ++d) { spec_fft(p, d, W[0]); IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream)); }
-        dense_unpack(g, dst, 0, (const double*)W[0], 1.0);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[q++], ctx.stream));                                      // ev[9]: the filter ends, the synthesis begins
-        spec_synth_modes(p, qt, 42ull, W, slots, d_P, d_P + (size_t)3 * nbins, d_P + (size_t)4 * nbins, d_bad, ev + 10);
-        for (int c = 0; c < 3; ++c) dense_unpack(g, dst, c, (const double*)W[c], 1.0);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[16], ctx.stream));
-        dense_pack(g, src, scomp, (double*)W[0], true);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[17], ctx.stream));
-        IAMRX_HIP_CHECK(hipEventSynchronize(ev[17]));
-        for (int s = 0; s < NP; ++s) IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[NP * r + s], ev[s], ev[s + 1]));
+        t.mark();
+        spec_pack(p, g, src, scomp, W0);
+        t.mark();
+        spec_forward(p, W0, &t);
+        spec_mul(p, FilterOp{W0, gt.axes(), kind == 1, kc * kc}, true);
+        t.mark();
+        spec_forward(p, W0, &t);
+        dense_unpack(g, dst, 0, (const double*)W0, 1.0);
+        t.mark();                                               // the filter's nine passes end, the six of the synthesis begin
+        spec_synth_modes(p, qt, 42ull, w, &t);
+        for (int c = 0; c < 3; ++c) dense_unpack(g, dst, c, (const double*)w.W[c].get(), 1.0);
+        t.mark();
+        dense_pack(g, src, scomp, (double*)W0, true);
+        t.mark();
+        t.finish(ms + NP * r);
     }
     specop_written(dst);
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    for (int c = 0; c < 3; ++c) ctx.free(W[c]);
-    ctx.free(d_bad); ctx.free(d_P); ctx.free(slots);
-    gt.release(); qt.release();
-    for (int d = 0; d < 3; ++d) ctx.free(p.tw[d]);
 }
 
 }  // namespace iamrx

@@ -332,12 +332,8 @@ void strfn_compute(const Geometry& g, const MultiFab& S, int nq, const int* comp
     for (int d = 0; d < 3; ++d) IAMRX_ASSERT(rmax[d] >= 0 && rmax[d] < rcap && (rmax[d] == 0 || g.domain.len(d) <= STRFN_MAX_EXTENT));
     dense_check_cover("strfn", g, *S.layout);
     auto& ctx = Context::get();
-    const long N = g.domain.npts();
     const size_t nsf = (size_t)3 * nq * ncol * rcap, nout = nsf + nq;
-    ctx.ensure_scratch(nout + 16);
-    double* R = (double*)ctx.alloc((size_t)N * sizeof(double));
-    double* slots = (double*)ctx.alloc(strfn_slots(g, rmax, pmax) * sizeof(double));
-    double* d_out = (double*)ctx.alloc(nout * sizeof(double));
+    DevBuf<double> R((size_t)g.domain.npts()), slots(strfn_slots(g, rmax, pmax)), d_out(nout);
     IAMRX_HIP_CHECK(hipMemsetAsync(d_out, 0, nout * sizeof(double), ctx.stream));         // the separations beyond an axis's rmax
     for (int q = 0; q < nq; ++q) {
         dense_gather(g, S, comps[q], R);
@@ -345,11 +341,9 @@ void strfn_compute(const Geometry& g, const MultiFab& S, int nq, const int* comp
             if (rmax[d] > 0) strfn_axis(g, d, rmax[d], pmax, rcap, R, slots, d_out + ((size_t)d * nq + q) * ncol * rcap);
         strfn_mean(g, R, slots, d_out + nsf + q);
     }
-    IAMRX_HIP_CHECK(hipMemcpyAsync(ctx.h_scratch, d_out, nout * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
-    ctx.sync();
-    for (size_t q = 0; q < nsf; ++q) out[q] = ctx.h_scratch[q];
-    if (mean) for (int q = 0; q < nq; ++q) mean[q] = ctx.h_scratch[nsf + q];
-    ctx.free(d_out); ctx.free(slots); ctx.free(R);
+    const double* h = ctx.read_back(d_out, nout);
+    std::copy(h, h + nsf, out);
+    if (mean) std::copy(h + nsf, h + nout, mean);
 }
 
 void strfn_bench(const Geometry& g, const MultiFab& S, int comp, int pmax, const int rmax[3], int reps, float* ms)
@@ -359,25 +353,19 @@ void strfn_bench(const Geometry& g, const MultiFab& S, int comp, int pmax, const
     IAMRX_ASSERT(S.type.cell() && comp >= 0 && comp < S.ncomp && reps >= 1);
     int rcap = 1;
     for (int d = 0; d < 3; ++d) { IAMRX_ASSERT(rmax[d] >= 0); rcap = std::max(rcap, rmax[d] + 1); }
-    auto& ctx = Context::get();
-    double* R = (double*)ctx.alloc((size_t)g.domain.npts() * sizeof(double));
-    double* slots = (double*)ctx.alloc(strfn_slots(g, rmax, pmax) * sizeof(double));
-    double* d_out = (double*)ctx.alloc((size_t)3 * ncol * rcap * sizeof(double));
-    hipEvent_t ev[5];
-    for (auto& e : ev) IAMRX_HIP_CHECK(hipEventCreate(&e));
+    DevBuf<double> R((size_t)g.domain.npts()), slots(strfn_slots(g, rmax, pmax)), d_out((size_t)3 * ncol * rcap);
+    PassTimer t(5);
     for (int r = 0; r < reps; ++r) {
-        IAMRX_HIP_CHECK(hipEventRecord(ev[0], ctx.stream));
+        t.mark();
         dense_gather(g, S, comp, R);
-        IAMRX_HIP_CHECK(hipEventRecord(ev[1], ctx.stream));
+        t.mark();
         for (int d = 0; d < 3; ++d) {
             if (rmax[d] > 0) strfn_axis(g, d, rmax[d], pmax, rcap, R, slots, d_out + (size_t)d * ncol * rcap);
-            IAMRX_HIP_CHECK(hipEventRecord(ev[2 + d], ctx.stream));
+            t.mark();
         }
-        IAMRX_HIP_CHECK(hipEventSynchronize(ev[4]));
-        for (int q = 0; q < 4; ++q) IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[4 * r + q], ev[q], ev[q + 1]));
+        t.finish(ms + 4 * r);
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    ctx.free(d_out); ctx.free(slots); ctx.free(R);
 }
+
 
 }  // namespace iamrx

@@ -251,21 +251,18 @@ void velgrad_bench(const Geometry& g, MultiFab& out, int nq, const int* which, c
     const VelgradArgs p = velgrad_args(g, out, 0, nq, which, vel, vcomp, mu);
     const int form = velgrad_path(*vel.layout, path);
     if (vel.nlocal() == 0) { for (int r = 0; r < reps; ++r) ms[r] = 0.f; return; }
-    hipEvent_t ev[2];
-    for (auto& e : ev) IAMRX_HIP_CHECK(hipEventCreate(&e));
+    PassTimer t(2);
     for (int r = 0; r < reps; ++r) {
-        IAMRX_HIP_CHECK(hipEventRecord(ev[0], ctx.stream));
+        t.mark();
         if (!split) velgrad_launch(*vel.layout, out, vel, p, form);
         else for (int q = 0; q < nq; ++q) {
             VelgradArgs one = p;
             one.nq = 1; one.id[0] = p.id[q]; one.ocomp = q;
             velgrad_launch(*vel.layout, out, vel, one, form);
         }
-        IAMRX_HIP_CHECK(hipEventRecord(ev[1], ctx.stream));
-        IAMRX_HIP_CHECK(hipEventSynchronize(ev[1]));
-        IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[r], ev[0], ev[1]));
+        t.mark();
+        t.finish(ms + r);
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
     ctx.sync();
 }
 

@@ -159,22 +159,20 @@ constexpr int HIST2_SLOTS_MAX = 16384;      // nbx * nby of a joint histogram
 void hist_check_range(const char* who, double lo, double hi, int nbins, int nbins_max);        // throws on what the rule excludes
 // zeroed device slots; hist_add / hist_add2 add the cells of this rank's boxes of one level to them (cov: cells with cov != 0 are skipped,
 // null: none; ghost cells are never read), every counted cell `weight`; hist_end brings them to the host, sums them over the ranks (as
-// doubles: every slot and their total must stay below 2^53), frees them.  A level every rank holds in full is counted once.
-unsigned long long* hist_begin(size_t nslots);
+// doubles: every slot and their total must stay below 2^53).  A level every rank holds in full is counted once.
+DevBuf<unsigned long long> hist_begin(size_t nslots);
 // d_counts[q * (nbins + 3) + s] += ... for the columns q = 0 .. ncol - 1 = components comps[q] of S
 void hist_add(const MultiFab& S, int ncol, const int* comps, const MultiFab* cov, const double* lo, const double* hi, int nbins,
               unsigned long long weight, unsigned long long* d_counts);
 // joint: d_counts[bx * nby + by] += ..., d_counts[nbx * nby] (`outside`) takes a cell that is NaN or out of range on either axis
 void hist_add2(const MultiFab& X, int compx, const MultiFab& Y, int compy, const MultiFab* cov, const double lo[2], const double hi[2],
                const int nbins[2], unsigned long long weight, unsigned long long* d_counts);
-void hist_end(unsigned long long* d_counts, size_t nslots, long long* out);
-// the device slots of one histogram call: hist_begin here, hist_end in finish(); an error that unwinds past them syncs and frees them
+void hist_end(const unsigned long long* d_counts, size_t nslots, long long* out);
+// the device slots of one histogram call: hist_begin here, hist_end in finish(); freed with the call, also when an error unwinds past them
 struct HistSlots {
-    size_t n; unsigned long long* d;
+    size_t n; DevBuf<unsigned long long> d;
     explicit HistSlots(size_t nslots) : n(nslots), d(hist_begin(nslots)) {}
-    HistSlots(const HistSlots&) = delete;
-    ~HistSlots() { if (d) { try { Context::get().sync(); Context::get().free(d); } catch (...) {} } }
-    void finish(long long* counts) { unsigned long long* p = d; d = nullptr; hist_end(p, n, counts); }
+    void finish(long long* counts) { hist_end(d, n, counts); }
 };
 // the checks of a joint histogram: both ranges, and nbins[0] * nbins[1] <= HIST2_SLOTS_MAX (diagnostics.hip)
 void hist2_check(const char* who, const double lo[2], const double hi[2], const int nbins[2]);

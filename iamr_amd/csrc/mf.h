@@ -82,6 +82,49 @@ struct Context {
     void fork_side();
     void join_side();
     void free_on(hipStream_t s, void* p) { if (s == stream) free(p); else parked.push_back(p); }
+    // n doubles at device address d, brought to the pinned scratch behind everything `stream` has been given: valid until the next use of h_scratch
+    const double* read_back(const double* d, size_t n);
+};
+
+// ------------------------------------------------------------------ scoped owners of a call's device scratch
+// One Context::alloc block of n elements T, freed when the owner dies.  A freed block may be handed out again at once: that is safe only
+// because ALL work that touches such a block is ordered on ctx.stream (the next user's work runs behind the last reader's).  Context::free
+// is host bookkeeping and makes no HIP call, so freeing while an error unwinds is safe whatever failed, and the destructor adds no
+// synchronisation.  Never for a block that work on another stream touches (Context::free_on).
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    explicit DevBuf(size_t n) : p((T*)Context::get().alloc(n * sizeof(T))) {}
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); return *this; }
+    ~DevBuf() { Context::get().free(p); }
+    T* get() const { return p; }
+    operator T*() const { return p; }
+};
+
+// The n events around the n - 1 passes of a measurement aid: mark() records the next one on ctx.stream, finish() waits for the last and
+// writes the n - 1 times between neighbours (milliseconds), after which the next repeat marks from the first again.  A body that runs
+// timed and untimed takes a PassTimer* and marks through mark(t): null, so do not time.
+struct PassTimer {
+    std::vector<hipEvent_t> ev;
+    size_t next = 0;
+    explicit PassTimer(int n)
+    {
+        ev.reserve(n);
+        for (int q = 0; q < n; ++q) { hipEvent_t e; IAMRX_HIP_CHECK(hipEventCreate(&e)); ev.push_back(e); }
+    }
+    PassTimer(const PassTimer&) = delete;
+    ~PassTimer() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    void mark() { IAMRX_ASSERT(next < ev.size()); IAMRX_HIP_CHECK(hipEventRecord(ev[next++], Context::get().stream)); }
+    static void mark(PassTimer* t) { if (t) t->mark(); }
+    void finish(float* ms)
+    {
+        IAMRX_ASSERT(next == ev.size());
+        IAMRX_HIP_CHECK(hipEventSynchronize(ev.back()));
+        for (size_t q = 0; q + 1 < ev.size(); ++q) IAMRX_HIP_CHECK(hipEventElapsedTime(&ms[q], ev[q], ev[q + 1]));
+        next = 0;
+    }
 };
 
 // ------------------------------------------------------------------ tuning registry

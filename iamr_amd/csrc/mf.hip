@@ -67,6 +67,14 @@ void Context::ensure_scratch(size_t n)
     scratch_n = n;
 }
 
+const double* Context::read_back(const double* d, size_t n)
+{
+    ensure_scratch(n + 16);
+    IAMRX_HIP_CHECK(hipMemcpyAsync(h_scratch, d, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    sync();
+    return h_scratch;
+}
+
 // IAMRX_POISON_ALLOC=1 (debugging aid): device blocks are filled with 0xFF bytes (NaN as doubles) when they are handed out, so that a
 // kernel reading memory nobody has written shows up deterministically instead of depending on what the recycled block held before
 // (2: zeros instead -- if a result changes between 0, 1 and 2 some kernel reads memory nobody wrote)

@@ -281,23 +281,7 @@ void NavierStokes::time_average(double dt_level, int level0_steps)
     dt_avg = 0.0;
 }
 
-// the common part of the three C entries: *nbins first, then the capacity
-void spectrum_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int cap, double* out, long* count, int* nbins)
-{
-    const int n = spectrum_nbins(g);
-    if (nbins) *nbins = n;
-    if (cap < n) throw Error("spectrum: " + std::to_string(n) + " shells, the caller's arrays hold " + std::to_string(cap));
-    if (!out) throw Error("spectrum: null output array");
-    spectrum_compute(g, S, nq, comps, n, out, count);
-}
-
-void NavierStokes::spectrum(int cap, double* out, long* count, int* nbins)
-{
-    const int comps[SPECTRUM_NQ] = {Xvel, Yvel, Zvel, Tracer};
-    spectrum_of(g, S[inew], SPECTRUM_NQ, comps, cap, out, count, nbins);
-}
-
-// the shell count first, then the capacity: the checks of spectrum_of
+// the common part of the C entries of the spectra: *nbins (the shell count) first, then the capacity
 static int spectrum_cap(const Geometry& g, int cap, const void* out, int* nbins)
 {
     const int n = spectrum_nbins(g);
@@ -305,6 +289,17 @@ static int spectrum_cap(const Geometry& g, int cap, const void* out, int* nbins)
     if (cap < n) throw Error("spectrum: " + std::to_string(n) + " shells, the caller's arrays hold " + std::to_string(cap));
     if (!out) throw Error("spectrum: null output array");
     return n;
+}
+
+void spectrum_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int cap, double* out, long* count, int* nbins)
+{
+    spectrum_compute(g, S, nq, comps, spectrum_cap(g, cap, out, nbins), out, count);
+}
+
+void NavierStokes::spectrum(int cap, double* out, long* count, int* nbins)
+{
+    const int comps[SPECTRUM_NQ] = {Xvel, Yvel, Zvel, Tracer};
+    spectrum_of(g, S[inew], SPECTRUM_NQ, comps, cap, out, count, nbins);
 }
 
 void cospectrum_of(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int cap, double* out, long* count, int* nbins)
