@@ -233,6 +233,12 @@ class Amr:
         level's layout -> NavierStokes.filtered of level 0.  Collective."""
         return self.levels[0].filtered(names, kind, kc)
 
+    def sgs(self, kind, kc, fields=()):
+        """a-priori LES analysis of LEVEL 0 of the hierarchy (as spectrum takes its level; include/iamrx.h: iamrx_amr_sgs) -> the dict of
+        NavierStokes.sgs, the fields on the layout of level 0; the same bits on every rank.  Collective."""
+        from . import sgs as _g
+        return _g.level_sgs(lib().iamrx_amr_sgs, self.h, self.geom0, self.layouts[0], kind, kc, fields)
+
     def spectral_budget(self):
         """spectral kinetic-energy budget of LEVEL 0 of the hierarchy (as spectrum takes its level; include/iamrx.h:
         iamrx_amr_spectral_budget) -> the dict of NavierStokes.spectral_budget; the same bits on every rank.  Collective."""

@@ -1360,6 +1360,27 @@ int iamrx_specop_bench(const iamrx_geom* g, iamrx_mf dst, iamrx_mf src, int scom
     specop_bench(to_geom(g), dst->mf, src->mf, scomp, kind, kc, wavenumber, reps, ms);
     IAMRX_CATCH
 }
+// ---- a-priori LES analysis (the driver: k_spectrum.hip, the kernels: k_sgs.hip)
+int iamrx_sgs_nstat(void) { return SGS_NSTAT; }
+int iamrx_mf_sgs(const iamrx_geom* g, iamrx_mf vel, int vcomp, int kind, double kc, iamrx_mf out, int ocomp, int nout, const int* which, double* stats, long* counts)
+{
+    IAMRX_TRY
+    if (!g || !vel) throw Error("iamrx_mf_sgs: null geometry or array");
+    sgs_compute(to_geom(g), vel->mf, vcomp, kind, kc, out ? &out->mf : nullptr, ocomp, nout, which, stats, counts);
+    IAMRX_CATCH
+}
+int iamrx_ns_sgs(iamrx_ns ns, int kind, double kc, iamrx_mf out, int ocomp, int nout, const int* which, double* stats, long* counts)
+{
+    IAMRX_TRY ns->ns->sgs(kind, kc, out ? &out->mf : nullptr, ocomp, nout, which, stats, counts); IAMRX_CATCH
+}
+int iamrx_sgs_bench_np(void) { return SGS_BENCH_NP; }
+int iamrx_sgs_bench(const iamrx_geom* g, iamrx_mf out, iamrx_mf vel, int vcomp, int kind, double kc, int nout, const int* which, int reps, float* ms)
+{
+    IAMRX_TRY
+    if (!g || !vel || !ms || reps < 1) throw Error("iamrx_sgs_bench: null argument or reps < 1");
+    sgs_bench(to_geom(g), out ? &out->mf : nullptr, vel->mf, vcomp, kind, kc, nout, which, reps, ms);
+    IAMRX_CATCH
+}
 int iamrx_budget_nq(void) { return BUDGET_NQ; }
 int iamrx_ns_spectral_budget(iamrx_ns ns, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY ns->ns->spectral_budget(nbins_cap, out, count, nbins); IAMRX_CATCH }
 
@@ -1903,6 +1924,10 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
     IAMRX_CATCH
 }
 int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY a->amr->level(0).spectrum(nbins_cap, out, count, nbins); IAMRX_CATCH }
+int iamrx_amr_sgs(iamrx_amr a, int kind, double kc, iamrx_mf out, int ocomp, int nout, const int* which, double* stats, long* counts)
+{
+    IAMRX_TRY a->amr->level(0).sgs(kind, kc, out ? &out->mf : nullptr, ocomp, nout, which, stats, counts); IAMRX_CATCH
+}
 int iamrx_amr_spectral_budget(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY a->amr->level(0).spectral_budget(nbins_cap, out, count, nbins); IAMRX_CATCH }
 int iamrx_amr_strfn(iamrx_amr a, int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean)
 {

@@ -771,6 +771,13 @@ void specop_check(const Geometry& g, const MultiFab& S, int comp, int ncomp)
 
 void specop_written(MultiFab& S) { S.uniform_marked = false; S.varying_marked = false; }
 
+// the filter's own refusals
+void specop_check_filter(int kind, double kc)
+{
+    if (kind < 0 || kind >= SPECOP_NKIND) throw Error("spectrum: filter kind " + std::to_string(kind) + " outside 0 .. " + std::to_string(SPECOP_NKIND - 1));
+    if (!(kc > 0.0) || !std::isfinite(kc)) throw Error("spectrum: the filter's cut-off kc must be positive and finite");
+}
+
 // the work arrays of a synthesis.  P: P_u, P_v, P_w, the target, the shell factors a (nbins each); bad: one int, preset to INT_MAX
 struct SynthWork {
     DevBuf<double2> W[3];
@@ -826,8 +833,7 @@ void specop_filter(const Geometry& g, MultiFab& dst, int dcomp, const MultiFab& 
     const int nbins = spectrum_nbins(g);
     specop_check(g, src, scomp, ncomp);
     specop_check(g, dst, dcomp, ncomp);
-    if (kind < 0 || kind >= SPECOP_NKIND) throw Error("spectrum: filter kind " + std::to_string(kind) + " outside 0 .. " + std::to_string(SPECOP_NKIND - 1));
-    if (!(kc > 0.0) || !std::isfinite(kc)) throw Error("spectrum: the filter's cut-off kc must be positive and finite");
+    specop_check_filter(kind, kc);
     const SpecPlan p = spec_plan(g, nbins);
     const SpecAxisTables gt = spec_filter_tables(p, kind, kc);
     DevBuf<double2> W((size_t)p.N);
@@ -927,6 +933,131 @@ void specop_bench(const Geometry& g, MultiFab& dst, const MultiFab& src, int sco
         t.finish(ms + NP * r);
     }
     specop_written(dst);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- a-priori LES analysis
+// Subgrid stresses and the inter-scale flux from filtered products (include/iamrx.h: iamrx_mf_sgs).  Nine images -- u_i by the plain pack,
+// u_i u_j (i <= j) by the product pack of k_sgs.hip -- each through the filter's own sequence, one component per transform as in
+// specop_filter; they stay on the device, k_sgs_point (k_sgs.hip) reads them in place, and only the requested fields are unpacked.
+namespace {
+
+constexpr int SGS_PAIR[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+
+// u_i u_j where spec_pack puts u_i: straight into the image, or through the zeroed, summed real array of several ranks (exact: a cell
+// has one owner, every other rank adds 0)
+void sgs_pack(const SpecPlan& p, const Geometry& g, const MultiFab& S, int ci, int cj, double2* W)
+{
+    auto& ctx = Context::get();
+    if (!dense_needs_gather(S)) { sgs_pack_product(g, S, ci, cj, (double*)W, true); return; }
+    DevBuf<double> R((size_t)p.N);
+    IAMRX_HIP_CHECK(hipMemsetAsync(R, 0, (size_t)p.N * sizeof(double), ctx.stream));
+    sgs_pack_product(g, S, ci, cj, R, false);
+    ctx.comm->allreduce_device(R, (int)p.N, ReduceOp::Sum, ctx.stream);
+    hipLaunchKernelGGL(k_spec_expand, dim3(spec_stream_grid(p.N)), dim3(SPEC_THREADS), 0, ctx.stream, R.get(), W, p.N);
+}
+
+// the device memory of a call: images 0 .. 2 the velocities, 3 .. 8 the products; returned to the arena with the call on every path
+struct SgsWork {
+    DevBuf<double2> W[9];
+    DevBuf<double> slots, stats;
+    DevBuf<unsigned long long> neg;
+    explicit SgsWork(const SpecPlan& p) : slots((size_t)SGS_NSTAT * sgs_nwg(p.N)), stats(SGS_NSTAT + 1), neg(1)
+    {
+        for (int q = 0; q < 9; ++q) W[q] = DevBuf<double2>((size_t)p.N);
+    }
+    // where dense_unpack finds field f
+    const double* field(int f) const { return f < 6 ? (const double*)W[3 + f].get() : (const double*)W[3 + f - 6].get() + 1; }
+};
+
+// pack .. finish; t (or null): the timer of sgs_bench, marked after the plain packs, the product packs, the transforms and the point pass
+void sgs_passes(const SpecPlan& p, const SpecAxisTables& gt, const Geometry& g, const MultiFab& vel, int vcomp, int kind, double kc, int mask,
+                const SgsWork& w, PassTimer* t)
+{
+    for (int c = 0; c < 3; ++c) spec_pack(p, g, vel, vcomp + c, w.W[c]);
+    PassTimer::mark(t);
+    for (int q = 0; q < 6; ++q) sgs_pack(p, g, vel, vcomp + SGS_PAIR[q][0], vcomp + SGS_PAIR[q][1], w.W[3 + q]);
+    PassTimer::mark(t);
+    for (int q = 0; q < 9; ++q) {
+        spec_forward(p, w.W[q]);
+        spec_mul(p, FilterOp{w.W[q], gt.axes(), kind == 1, kc * kc}, true);
+        spec_forward(p, w.W[q]);
+    }
+    PassTimer::mark(t);
+    SgsPoint a;
+    for (int c = 0; c < 3; ++c) { a.U[c] = w.W[c]; a.ln[c] = p.ln[c]; a.dxi[c] = 1.0 / g.dx[c]; }
+    for (int q = 0; q < 6; ++q) a.P[q] = w.W[3 + q];
+    double Lmax = 0.0;
+    for (int d = 0; d < 3; ++d) Lmax = std::max(Lmax, g.probhi[d] - g.problo[d]);
+    const double delta = Lmax / (2.0 * kc);
+    a.delta2 = delta * delta;
+    a.mask = mask;
+    sgs_point(a, w.slots, w.neg, w.stats);
+    PassTimer::mark(t);
+}
+
+// the checks of a call, all before anything is allocated or written; returns the mask of the requested fields
+int sgs_check(const Geometry& g, const MultiFab& vel, int vcomp, int kind, double kc, const MultiFab* out, int ocomp, int nout, const int* which)
+{
+    specop_check(g, vel, vcomp, 3);
+    specop_check_filter(kind, kc);
+    if (nout < 0) throw Error("sgs: nout = " + std::to_string(nout) + " is negative");
+    if (nout > 0 && (!out || !which)) throw Error("sgs: nout > 0 with a null out or which");
+    int mask = 0;
+    for (int q = 0; q < nout; ++q) {
+        if (which[q] < 0 || which[q] >= SGS_NFIELD) throw Error("sgs: field id " + std::to_string(which[q]) + " outside 0 .. " + std::to_string(SGS_NFIELD - 1));
+        mask |= 1 << which[q];
+    }
+    if (nout > 0) {
+        if (out == &vel) throw Error("sgs: out aliases vel");
+        specop_check(g, *out, ocomp, nout);
+    }
+    return mask;
+}
+
+}  // namespace
+
+void sgs_compute(const Geometry& g, const MultiFab& vel, int vcomp, int kind, double kc, MultiFab* out, int ocomp, int nout, const int* which,
+                 double* stats, long* counts)
+{
+    const int nbins = spectrum_nbins(g);
+    const int mask = sgs_check(g, vel, vcomp, kind, kc, out, ocomp, nout, which);
+    if (!stats) throw Error("sgs: null stats");
+    const SpecPlan p = spec_plan(g, nbins);
+    const SpecAxisTables gt = spec_filter_tables(p, kind, kc);
+    const SgsWork w(p);
+    sgs_passes(p, gt, g, vel, vcomp, kind, kc, mask, w, nullptr);
+    for (int q = 0; q < nout; ++q) dense_unpack(g, *out, ocomp + q, w.field(which[q]), 1.0);
+    if (nout > 0) specop_written(*out);
+    const double* h = Context::get().read_back(w.stats, SGS_NSTAT + 1);
+    std::copy(h, h + SGS_NSTAT, stats);
+    if (counts) {
+        long long neg;
+        std::memcpy(&neg, h + SGS_NSTAT, sizeof neg);
+        counts[0] = p.N;
+        counts[1] = (long)neg;
+    }
+    Context::get().sync();
+}
+
+void sgs_bench(const Geometry& g, MultiFab* out, const MultiFab& vel, int vcomp, int kind, double kc, int nout, const int* which, int reps, float* ms)
+{
+    const int nbins = spectrum_nbins(g);
+    const int mask = sgs_check(g, vel, vcomp, kind, kc, out, 0, nout, which);
+    IAMRX_ASSERT(reps >= 1 && ms);
+    const SpecPlan p = spec_plan(g, nbins);
+    const SpecAxisTables gt = spec_filter_tables(p, kind, kc);
+    const SgsWork w(p);
+    PassTimer t(SGS_BENCH_NP + 1);
+    for (int r = 0; r < reps; ++r) {
+        t.mark();
+        sgs_passes(p, gt, g, vel, vcomp, kind, kc, mask, w, &t);
+        for (int q = 0; q < nout; ++q) dense_unpack(g, *out, q, w.field(which[q]), 1.0);
+        t.mark();
+        dense_pack(g, vel, vcomp, (double*)w.W[0].get(), true);
+        t.mark();
+        t.finish(ms + SGS_BENCH_NP * r);
+    }
+    if (nout > 0) specop_written(*out);
 }
 
 }  // namespace iamrx

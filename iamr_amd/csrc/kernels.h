@@ -120,6 +120,35 @@ void specop_filter(const Geometry& g, MultiFab& dst, int dcomp, const MultiFab& 
 void specop_solenoidal(const Geometry& g, MultiFab& dst, int dcomp, const MultiFab& src, int scomp, int wavenumber);
 void specop_synthesize(const Geometry& g, MultiFab& dst, int dcomp, unsigned long long seed, int nbins, const double* E_target, int wavenumber);
 void specop_bench(const Geometry& g, MultiFab& dst, const MultiFab& src, int scomp, int kind, double kc, int wavenumber, int reps, float* ms);
+// ---- a-priori LES analysis (include/iamrx.h: iamrx_mf_sgs): the driver beside specop_filter, its own kernels in k_sgs.hip ----
+constexpr int SGS_NSTAT = 16;               // the means of include/iamrx.h
+constexpr int SGS_NFIELD = 10;              // tau_xx tau_xy tau_xz tau_yy tau_yz tau_zz k_sgs sgs_flux filtered_strain smag_flux
+constexpr int SGS_MAXWG = 1024;             // workgroups (= slots per statistic) of k_sgs_point: a function of N alone
+constexpr int SGS_BENCH_NP = 6;
+// the nine dense images of a call after their inverse transforms.  U: the filtered velocities, read at the face neighbours; P: the
+// filtered products xx xy xz yy yz zz, read at the cell itself and overwritten by the fields of `mask` (bit f: field f; tau_ij over the
+// real part of P[ij], fields 6 .. 9 into the imaginary parts of P[0 .. 3]).  ln: log2 of the extents; dxi: 1 / dx; delta2: Delta^2
+struct SgsPoint {
+    const double2* U[3];
+    double2* P[6];
+    int ln[3];
+    double dxi[3];
+    double delta2;
+    int mask;
+};
+// the valid cells of S(ci) * S(cj) of THIS rank's boxes -> their place in the dense image: dense_pack on a product (no array of products)
+void sgs_pack_product(const Geometry& g, const MultiFab& S, int ci, int cj, double* dst, bool cplx);
+int sgs_nwg(long N);
+// k_sgs_point and its finish kernel: slots holds SGS_NSTAT * sgs_nwg(N) doubles, neg one counter (zeroed here), stats SGS_NSTAT + 1
+// doubles -- the means, then the bits of the count of cells with Pi < 0
+void sgs_point(const SgsPoint& a, double* slots, unsigned long long* neg, double* stats);
+// stats[SGS_NSTAT], counts[2] = {N, cells with Pi < 0} of vel(vcomp .. vcomp + 2) under the filter (kind, kc); out (null with nout = 0:
+// statistics only) takes field which[q] in component ocomp + q of its valid cells.  Every check before anything is written.
+void sgs_compute(const Geometry& g, const MultiFab& vel, int vcomp, int kind, double kc, MultiFab* out, int ocomp, int nout, const int* which,
+                 double* stats, long* counts);
+// measurement aid (tools/bench_sgs.py): ms[SGS_BENCH_NP * r + p], p = 0 the three plain packs, 1 the six product packs, 2 the 54 transform
+// passes and nine multipliers, 3 k_sgs_point with its finish, 4 the unpack of the nout fields, 5 one dense_pack of vel(vcomp) alone
+void sgs_bench(const Geometry& g, MultiFab* out, const MultiFab& vel, int vcomp, int kind, double kc, int nout, const int* which, int reps, float* ms);
 
 // ---- k_convect.hip: the skew-symmetric centred nonlinear term ----------------------------------
 // out(ocomp + i) = N_i = 0.5 sum_d [u_d delta_d u_i + delta_d(u_d u_i)] of vel(vcomp .. vcomp + 2) on the valid cells (the evaluation

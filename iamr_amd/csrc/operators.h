@@ -346,6 +346,12 @@ public:
     // acceleration at cur_time() into arrays that return to the arena, then one packed transform per pair (u_i, N_i) and (u_i, f_i).
     // *nbins is set before the capacity is checked.  Collective; every rank receives the result.
     void spectral_budget(int cap, double* out, long* count, int* nbins);
+    // a-priori LES analysis of the new-time velocity (include/iamrx.h: iamrx_mf_sgs; no ghost cell is read): sgs_compute on S[inew].
+    // Collective; every rank receives the same statistics.
+    void sgs(int kind, double kc, MultiFab* out, int ocomp, int nout, const int* which, double* stats, long* counts)
+    {
+        sgs_compute(g, S[inew], Xvel, kind, kc, out, ocomp, nout, which, stats, counts);
+    }
     // structure functions and two-point correlations along the axes of u, v, w and the first tracer of the new-time state (k_strfn.hip):
     // out[((d * STRFN_NQ + c) * ncol + col) * rcap + r], count[d * rcap + r] and mean[c] (either may be null).  Collective; every rank
     // receives the result.

@@ -24,6 +24,9 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   (iamr_amd/spectrum.py), carried under "spectrum"; ns.budget_interval (-1: off) / ns.budget_file ("sbud"): the spectral kinetic-energy
   budget of level 0 (iamr_amd/budget.py), carried under "budget", with the preconditions of the spectra; an interval > 0 needs a fully periodic three-dimensional domain whose extents are
   powers of two in 4 .. 1024,
+  ns.sgs_interval (-1: off) / ns.sgs_filter (sharp | gaussian | box; gaussian) / ns.sgs_kc (1 .. 8 cut-offs, required with an interval > 0) /
+  ns.sgs_file ("sgs"): this library's own keys for the a-priori LES analysis of level 0 (iamr_amd/sgs.py), carried under "sgs", with the
+  preconditions of the spectra,
   ns.strfn_interval (-1: off) / ns.strfn_pmax (4; 1 .. 8) / ns.strfn_rmax (one integer or three; -1: the largest separation of the axis, 0:
   skip it) / ns.strfn_file ("sf"): this library's own keys for the structure functions and two-point correlations of level 0 along the
   axes (iamr_amd/strfn.py), carried under "strfn"; an interval > 0 needs a three-dimensional run, walls and any extents <= 1024 allowed,
@@ -579,6 +582,30 @@ class Inputs:
                 if not extent_ok(n[d]):
                     raise ValueError(f"inputs: ns.budget_interval > 0 needs extents that are powers of two in 4 .. 1024, amr.n_cell has "
                                      f"n_{'xyz'[d]} = {n[d]}")
+        # a-priori LES analysis (this library's own keys; sgs.py): every sgs_interval-th level-0 step and once for the initial data one row
+        # per cut-off of ns.sgs_kc in the one text file ns.sgs_file, of level 0; the preconditions of the spectra
+        sgs = dict(interval=self.integer("ns.sgs_interval", -1), filter=self.string("ns.sgs_filter", "gaussian"),
+                   kc=[float(v) for v in self._get("ns.sgs_kc")] if self.has("ns.sgs_kc") else [], file=self.string("ns.sgs_file", "sgs"))
+        if sgs["interval"] > 0:
+            from .spectrum import extent_ok
+            from .sgs import FILTERS
+            if slab:
+                raise NotImplementedError("inputs: ns.sgs_interval > 0 in a two-dimensional run: the transform is three-dimensional only "
+                                          "(the slab's thickness direction has two cells)")
+            if not all(per):
+                raise ValueError(f"inputs: ns.sgs_interval > 0 needs a fully periodic domain, geometry.is_periodic = {' '.join(str(int(v)) for v in per)}: "
+                                 f"direction {'xyz'[[bool(v) for v in per].index(False)]} is not periodic")
+            for d in range(3):
+                if not extent_ok(n[d]):
+                    raise ValueError(f"inputs: ns.sgs_interval > 0 needs extents that are powers of two in 4 .. 1024, amr.n_cell has "
+                                     f"n_{'xyz'[d]} = {n[d]}")
+            if sgs["filter"] not in FILTERS:
+                raise ValueError(f"inputs: ns.sgs_filter = {sgs['filter']}: one of {' | '.join(FILTERS)}")
+            if not 1 <= len(sgs["kc"]) <= 8:
+                raise ValueError(f"inputs: ns.sgs_interval > 0 needs 1 .. 8 cut-offs in ns.sgs_kc, it holds {len(sgs['kc'])}")
+            for v in sgs["kc"]:
+                if not (v > 0.0 and math.isfinite(v)):
+                    raise ValueError(f"inputs: ns.sgs_kc = {v:g}: a cut-off must be positive and finite")
         # structure functions and two-point correlations along the axes (this library's own keys): every strfn_interval-th level-0 step and
         # once for the initial data, of level 0; strfn_rmax: one integer for all axes or three (-1: the largest allowed, 0: skip the axis)
         strfn = dict(interval=self.integer("ns.strfn_interval", -1), pmax=self.integer("ns.strfn_pmax", 4),
@@ -637,7 +664,7 @@ class Inputs:
                     if v in VELGRAD_NAMES and v not in VELGRAD_NAMES_2D:
                         raise NotImplementedError(f"inputs: {key} names '{v}' in a two-dimensional run: of the velocity-gradient fields a slab "
                                                   f"knows {' '.join(VELGRAD_NAMES_2D)}")
-        out = dict(profile=profile, spectrum=spectrum, budget=budget, strfn=strfn, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
+        out = dict(profile=profile, spectrum=spectrum, budget=budget, sgs=sgs, strfn=strfn, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
                    max_step=self.integer("max_step", -1), stop_time=self.real("stop_time", -1.0),
                    plot_int=self.integer("amr.plot_int", -1), plot_file=self.string("amr.plot_file", "plt"), plot_vars=self.name_list("amr.plot_vars", "ALL"),
                    derive_plot_vars=dpv, fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,

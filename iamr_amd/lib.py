@@ -528,6 +528,13 @@ def mf_filter(geom, dst, src, kind, kc, dcomp=0, scomp=0, ncomp=1):
     return _s.mf_filter(geom, dst, src, kind, kc, dcomp, scomp, ncomp)
 
 
+def mf_sgs(geom, vel, kind, kc, fields=(), vcomp=0, layout=None):
+    """a-priori LES analysis of vel(vcomp .. vcomp + 2) under the filter (kind, kc): subgrid stress, inter-scale flux, backscatter and the
+    Smagorinsky constants that reproduce them (include/iamrx.h: iamrx_mf_sgs) -> the dict of sgs.as_dict"""
+    from . import sgs as _s
+    return _s.mf_sgs(geom, vel, kind, kc, fields, vcomp, layout)
+
+
 def mf_solenoidal(geom, dst, src, wavenumber="centred", dcomp=0, scomp=0):
     """dst(dcomp .. dcomp + 2) = the solenoidal part of src(scomp .. scomp + 2) for the exact or the centred wavenumber
     (include/iamrx.h: iamrx_mf_solenoidal; spectral.py)"""

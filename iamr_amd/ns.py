@@ -386,6 +386,13 @@ class NavierStokes:
         from . import spectral as _s
         return _s.level_filtered(self, names, kind, kc)
 
+    def sgs(self, kind, kc, fields=()):
+        """a-priori LES analysis of the new-time velocity on a fully periodic level (include/iamrx.h: iamrx_ns_sgs; sgs.py) -> dict with
+        the 16 named statistics, "N", "negative_cells", "delta", the derived ratios per model ("strain", "gradient") and "fields": a new
+        MultiFab on the level's layout holding the requested fields (names or ids of sgs.FIELD_NAMES), or None.  Collective."""
+        from . import sgs as _g
+        return _g.level_sgs(lib().iamrx_ns_sgs, self.h, self.geom, self.layout, kind, kc, fields)
+
     def spectral_budget(self):
         """spectral kinetic-energy budget of the new-time state on a fully periodic level (include/iamrx.h: iamrx_ns_spectral_budget) ->
         dict with "k", "count", "E", "T" (nonlinear transfer, skew-symmetric centred form), "Pi" (the flux -cumsum(T)), "D" (molecular

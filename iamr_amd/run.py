@@ -207,6 +207,20 @@ def take_budget(run, pr, step, rank, say):
         say("BUDGET:", path)
 
 
+def take_sgs(run, pr, step, rank, say):
+    """ns.sgs_interval > 0: every that many level-0 steps (and for the initial data, step 0) the a-priori LES statistics of the level, or
+    of level 0 of the hierarchy (sgs.py), go as one row per cut-off of ns.sgs_kc to the text file ns.sgs_file.  Collective: every rank
+    takes part, rank 0 writes.  Off: nothing is launched or allocated."""
+    sg = pr.get("sgs") or {}
+    if sg.get("interval", -1) <= 0 or step % sg["interval"] != 0:
+        return
+    from .sgs import append_row
+    for kc in sg["kc"]:
+        s = run.sgs(sg["filter"], kc)
+        if rank == 0:
+            append_row(sg["file"], step, run.time, kc, s["stats"], (s["N"], s["negative_cells"]))
+
+
 def take_strfn(run, pr, step, rank, say):
     """ns.strfn_interval > 0: every that many level-0 steps (and for the initial data, step 0) the structure functions and two-point
     correlations of the level, or of level 0 of the hierarchy (strfn.py), go to <ns.strfn_file><step:05d>.  Collective: every rank takes
@@ -413,7 +427,7 @@ def drive(pr, inp, lib, N, hierarchy, rank=0, world=1, observe=None):
     """a run from amr.restart or from its initial data to max_step / stop_time: a single level, or (hierarchy) an Amr hierarchy.  world > 1:
     the boxes of every level are spread over the ranks (level 0 by Layout.decompose, fixed refined grids round-robin, regridded levels
     by the library's knapsack, restarted levels as checkpoint.restart says) and every rank executes the same sequence of collective
-    operations: step, enforce_plane, sums, time average, profile, spectrum, spectral budget, structure functions, pdf, integrals, observe, plotfile, checkpoint.  observe: see main"""
+    operations: step, enforce_plane, sums, time average, profile, spectrum, spectral budget, a-priori LES statistics, structure functions, pdf, integrals, observe, plotfile, checkpoint.  observe: see main"""
     from . import checkpoint
     say = print if rank == 0 else (lambda *a, **k: None)
     plot_int, plot_root = pr.get("plot_int", -1), pr.get("plot_file", "plt")
@@ -426,6 +440,7 @@ def drive(pr, inp, lib, N, hierarchy, rank=0, world=1, observe=None):
         take_profile(run, pr, step, rank, say)
         take_spectrum(run, pr, step, rank, say)
         take_budget(run, pr, step, rank, say)
+        take_sgs(run, pr, step, rank, say)
         take_strfn(run, pr, step, rank, say)
         take_pdf(run, pr, step, rank, say)
         take_integrals(run, pr, step, rank, say)
@@ -439,6 +454,11 @@ def drive(pr, inp, lib, N, hierarchy, rank=0, world=1, observe=None):
         # the one file of the run's integrals: started afresh (header line) by a run from initial data, appended to after amr.restart
         from .integrals import start_file
         start_file(ig["file"], ig["vars"], append=bool(pr.get("restart")))
+    sg = pr.get("sgs") or {}
+    if sg.get("interval", -1) > 0 and rank == 0:
+        # the one file of the run's a-priori LES statistics, by the same rule
+        from .sgs import start_file as start_sgs
+        start_sgs(sg["file"], append=bool(pr.get("restart")))
     if pr.get("restart"):
         # amr.restart (Amr::restart): grids, data, times and step counters come from the checkpoint, parameters from the inputs file
         # (the solvers' options are the run's too: a two-dimensional run restarts with its slab multigrid, see solver_opts)

@@ -733,6 +733,80 @@ int iamrx_mf_synthesize(const iamrx_geom* g, iamrx_mf dst, int dcomp, unsigned l
  * 15 unpack -- and 16 one dense_pack of src(scomp) alone, the yardstick of the streaming passes.  Nothing is read back. */
 int iamrx_specop_bench_np(void);
 int iamrx_specop_bench(const iamrx_geom* g, iamrx_mf dst, iamrx_mf src, int scomp, int kind, double kc, int wavenumber, int reps, float* ms);
+/* A-priori LES analysis: the subgrid stress of a filtered field, the energy it drains from the large scales and what the Smagorinsky
+ * operators of the closure (k_les.hip) make of the same filtered field (this library's own diagnostic; k_sgs.hip, driver in
+ * k_spectrum.hip).  The level is cell-centred and triply periodic with power-of-two extents 4 .. 1024: the conditions and the errors
+ * of the spectra.  u = vel(vcomp .. vcomp + 2); the filter is (kind, kc) of iamrx_mf_filter, written ~ below; Delta = pi / (k0 kc) =
+ * L_max / (2 kc); N = the cells of the level; <.> = the sum over all cells divided once by N.  Per cell:
+ *   filtered velocity   u~_i: the filtered u_i;
+ *   filtered product    (u_i u_j)~ for i <= j: the filtered cell-wise product, formed in double (one rounding) before the filter;
+ *   stress              tau_ij = (u_i u_j)~ - u~_i u~_j (one product, one difference);
+ *   subgrid energy      k_sgs = 0.5 ((tau_xx + tau_yy) + tau_zz);
+ *   deviatoric stress   taud_ij = tau_ij - delta_ij ((2 / 3) k_sgs);
+ *   filtered gradient   A[n][d] = 0.5 (u~_n(x + e_d) - u~_n(x - e_d)) (1 / dx_d) with periodic wrap: the centred difference of
+ *                       iamrx_derive_velgrad (the same bits as (u~_n(x + e_d) - u~_n(x - e_d)) (0.5 / dx_d));
+ *   filtered strain     S_ij = 0.5 (A[i][j] + A[j][i]); with s_ij = A[i][j] + A[j][i] for i < j,
+ *                       SS = A00^2 + A11^2 + A22^2 + 0.5 (s_01^2 + s_02^2 + s_12^2), each sum left to right as iamrx_derive_velgrad's,
+ *                       |S|^2 = 2 SS and |S| = sqrt(2 SS): "strain_rate" of u~;
+ *   inter-scale flux    Pi = -tau_ij S_ij, all nine terms (the six off-diagonal ones in pairs, tau_ij s_ij = 2 tau_ij S_ij):
+ *                       Pi = -(((tau_xx A00 + tau_yy A11) + tau_zz A22) + ((tau_xy s_01 + tau_xz s_02) + tau_yz s_12));
+ *   eddy viscosity at C_s = 1, two operators:
+ *                       m = 0 "strain"    D_0 = Delta^2 |S|, the textbook Smagorinsky form;
+ *                       m = 1 "gradient"  D_1 = Delta^2 sqrt(2 A_ij A_ij) = les_model<0>(A, Delta^2) of the closure, the expression
+ *                                         ns.smago_Cs_cst multiplies in this code (one function, les_model.h, for both);
+ *                       model stress M^m_ij = -2 D_m S_ij, model flux P_m = D_m |S|^2 = D_m (2 SS);
+ *   taud_ij taud_ij   = ((taud_xx^2 + taud_yy^2) + taud_zz^2) + 2 ((tau_xy^2 + tau_xz^2) + tau_yz^2);
+ *   taud_ij S_ij      = ((taud_xx A00 + taud_yy A11) + taud_zz A22) + ((tau_xy s_01 + tau_xz s_02) + tau_yz s_12).
+ * sgs statistics: iamrx_sgs_nstat() = 16 doubles, index name value (m = 0: strain, m = 1: gradient at 6 + 5 m .. 10 + 5 m)
+ *    0  Pi            <Pi>
+ *    1  Pi2           <Pi^2>
+ *    2  Pi_neg        <min(Pi, 0)>
+ *    3  k_sgs         <k_sgs>
+ *    4  S2            <|S|^2>
+ *    5  taud2         <taud_ij taud_ij>
+ *    6  P_strain      <P_0>
+ *    7  P2_strain     <P_0^2>
+ *    8  PiP_strain    <Pi P_0>
+ *    9  MM_strain     <D_0^2 |S|^2>           (= <M^0 M^0> / 2)
+ *   10  LM_strain     <D_0 taud_ij S_ij>      (= -<taud M^0> / 2)
+ *   11  P_gradient    <P_1>
+ *   12  P2_gradient   <P_1^2>
+ *   13  PiP_gradient  <Pi P_1>
+ *   14  MM_gradient   <D_1^2 |S|^2>
+ *   15  LM_gradient   <D_1 taud_ij S_ij>
+ * and two exact integers counts[2] = {N, the cells with Pi < 0} (counts may be null).  The sums run in a fixed order -- per thread in
+ * index order over a grid that depends on N alone, across a wavefront by a butterfly in which both partners add the same two numbers
+ * in the same order, per workgroup into its own slots, the slots in slot order -- without floating-point atomics: the same call gives
+ * the same bits for every box layout and number of ranks.
+ * sgs fields: by id, any subset in any order, field which[q] into component ocomp + q of the valid cells of `out`
+ *    0  tau_xx
+ *    1  tau_xy
+ *    2  tau_xz
+ *    3  tau_yy
+ *    4  tau_yz
+ *    5  tau_zz
+ *    6  k_sgs
+ *    7  sgs_flux          Pi
+ *    8  filtered_strain   |S|
+ *    9  smag_flux         P_0
+ * `out` is a caller-owned cell-centred array on any layout that tiles the domain (not necessarily that of vel); ghost cells are
+ * neither read nor written, of vel or of out.  out = NULL with nout = 0: statistics only, no field is stored or unpacked.
+ * One component per transform, the filter's own sequence and per-field accuracy; nine 16 N byte images from the arena for the length
+ * of the call, returned on every path.  Errors: those of the spectra (not cell-centred, component range, boxes that do not tile, not
+ * periodic, extents) and of the filter (kind, kc); a field id outside 0 .. 9; nout > 0 with a null out or which; out aliasing vel; null
+ * stats.  On any error out is untouched.  Collective on several ranks exactly as iamrx_mf_filter; every rank receives the same bits.
+ * iamrx_ns_sgs: the new-time velocity of the level's state (no ghost cell is needed).
+ * Not built: the Sigma operator (its acos of a clamped argument is ill-conditioned; a derived parity bound is a piece of work of its
+ * own), density weighting, levels above 0, a distributed transform, pair-packed transforms, time averaging. */
+int iamrx_sgs_nstat(void);
+int iamrx_mf_sgs(const iamrx_geom* g, iamrx_mf vel, int vcomp, int kind, double kc, iamrx_mf out, int ocomp, int nout, const int* which,
+                 double* stats, long* counts);
+int iamrx_ns_sgs(iamrx_ns ns, int kind, double kc, iamrx_mf out, int ocomp, int nout, const int* which, double* stats, long* counts);
+/* measurement aid (tools/bench_sgs.py): iamrx_sgs_bench_np() = 6 passes with an event between them, ms[6 * r + p]: 0 the three plain
+ * packs, 1 the six product packs, 2 the 54 transform passes and nine multipliers, 3 k_sgs_point with its finish kernel, 4 the unpack of
+ * the nout fields into out(0 .. nout - 1), 5 one dense_pack of vel(vcomp) alone.  Nothing is read back. */
+int iamrx_sgs_bench_np(void);
+int iamrx_sgs_bench(const iamrx_geom* g, iamrx_mf out, iamrx_mf vel, int vcomp, int kind, double kc, int nout, const int* which, int reps, float* ms);
 /* Structure functions and two-point correlations along the axes (this library's own diagnostic, no upstream counterpart; k_strfn.hip).
  * Unlike the spectra they are defined with walls and on extents that are not powers of two.  For a cell-centred component f on a level
  * whose boxes tile the domain, n = (n_x, n_y, n_z) cells, N = n_x n_y n_z, an axis d and an integer separation r in cells:
@@ -990,6 +1064,8 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
 int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins);
 /* The budget of iamrx_ns_spectral_budget on LEVEL 0 of the hierarchy, exactly as iamrx_amr_spectrum takes its level. */
 int iamrx_amr_spectral_budget(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins);
+/* The a-priori LES analysis of iamrx_ns_sgs on LEVEL 0 of the hierarchy, exactly as iamrx_amr_spectrum takes its level. */
+int iamrx_amr_sgs(iamrx_amr a, int kind, double kc, iamrx_mf out, int ocomp, int nout, const int* which, double* stats, long* counts);
 /* The structure functions of iamrx_ns_strfn on LEVEL 0 of the hierarchy, exactly as iamrx_amr_spectrum takes its level. */
 int iamrx_amr_strfn(iamrx_amr a, int pmax, const int rmax[3], int rcap, double* out, long long* count, double* mean);
 /* Composite histograms of the hierarchy (the rule, the names and the layout of counts: iamrx_mf_histogram / iamrx_ns_histogram above).  Level l
