@@ -211,10 +211,12 @@ void average_down(const MultiFab& fine, MultiFab& crse, int scomp, int ncomp, in
 //   1. same-level data (time-interpolated between the old and new StateData) -> dst valid + ghost cells, periodic images incl.
 //   2. the part of dst inside the (periodically extended) domain that no fine box covers is interpolated from the coarse
 //      level: the coarse data (time-interpolated, physical BC applied at the coarse domain boundary) are gathered on
-//      coarsen(region) grown by one cell and prolonged with amrex::CellConservativeLinear (linear limiting on):
-//        central slopes (one-sided 4-point formula next to an ext_dir / hoextrap domain face), limited slope
-//        s = sign(dc) min(|dc|, 2|forward|, 2|backward|) (0 at an extremum), one factor alpha_d = min_n s_n/dc_n per direction
-//        shared by ALL components (the limiter stays linear in the state), fine = crse + sum_d off_d alpha_d dc_d
+//      coarsen(region) grown by two cells and prolonged with amrex::CellConservativeLinear (linear limiting off: the
+//      per-component monotonised-central variant), for every component n by itself:
+//        central slope dc (one-sided 4-point formula next to an ext_dir / hoextrap domain face), limited slope
+//        s_d = sign(dc) min(|dc|, 2|forward|, 2|backward|) (0 at an extremum), then ONE factor alpha_n <= 1 for the three slopes of
+//        the component so that the largest excursion inside the coarse cell, sum_d |s_d| (r-1)/(2r), stays within the range of the
+//        27 coarse neighbours; fine = crse + sum_d off_d alpha_n s_d
 //   3. physical BC fill of dst at the fine domain boundary.
 // The regions of step 2 and the coarse gather layout depend only on the two fine layouts and are cached.
 namespace {
