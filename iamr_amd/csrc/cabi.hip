@@ -1284,6 +1284,50 @@ int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, f
     IAMRX_CATCH
 }
 
+// ---- the slab-decomposed transform of several ranks (k_spectrum.hip)
+// host-only (no device needed): eligibility and the scatter plan of rank `rank` of `nranks`; rows of 10 longs: kind, peer, box, lo[3], hi[3], off
+int iamrx_host_spectrum_slab_plan(const iamrx_geom* g, int nboxes, const int* lo_hi, const int* owner, int rank, int nranks, int* eligible,
+                                  char* reason, size_t reason_cap, int max_rows, long* rows, int* nrows)
+{
+    IAMRX_TRY
+    if (!g || !eligible || !nrows || nboxes < 0 || (nboxes > 0 && !lo_hi)) throw Error("iamrx_host_spectrum_slab_plan: null argument or a negative number of boxes");
+    static_assert(IAMRX_SPECTRUM_SLAB_BENCH_NP == SPEC_SLAB_BENCH_NP, "the passes of the measurement aid");
+    std::vector<BoxD> b(nboxes);
+    std::vector<int> own(nboxes);
+    for (int i = 0; i < nboxes; ++i) {
+        for (int d = 0; d < 3; ++d) { b[i].lo[d] = lo_hi[6 * i + d]; b[i].hi[d] = lo_hi[6 * i + 3 + d]; }
+        own[i] = owner ? owner[i] : 0;
+    }
+    std::string why;
+    std::vector<SpecSlabRow> r;
+    *eligible = spectrum_slab_plan(to_geom(g).domain, b, own, rank, nranks, &why, &r) ? 1 : 0;
+    if (reason && reason_cap > 0) { strncpy(reason, why.c_str(), reason_cap - 1); reason[reason_cap - 1] = 0; }
+    *nrows = (int)r.size();
+    for (int n = 0; rows && n < std::min(*nrows, max_rows); ++n) {
+        long* o = rows + 10 * n;
+        o[0] = r[n].kind; o[1] = r[n].peer; o[2] = r[n].box;
+        for (int d = 0; d < 3; ++d) { o[3 + d] = r[n].lo[d]; o[6 + d] = r[n].hi[d]; }
+        o[9] = r[n].off;
+    }
+    IAMRX_CATCH
+}
+int iamrx_spectrum_slab_info(long out[7])
+{
+    IAMRX_TRY
+    if (!out) throw Error("iamrx_spectrum_slab_info: null argument");
+    const SpecSlabInfo i = spectrum_slab_info();
+    const long v[7] = {i.path, i.ranks, i.max_image, i.per_pass, i.sent, i.received, i.transforms};
+    std::copy(v, v + 7, out);
+    IAMRX_CATCH
+}
+int iamrx_spectrum_slab_bench(const iamrx_geom* g, int nranks, int reps, float* ms)
+{
+    IAMRX_TRY
+    if (!g || !ms || reps < 1) throw Error("iamrx_spectrum_slab_bench: null argument or reps < 1");
+    spectrum_slab_bench(to_geom(g), nranks, reps, ms);
+    IAMRX_CATCH
+}
+
 // ---- co-spectra, the nonlinear term and the spectral budget (k_spectrum.hip, k_convect.hip)
 int iamrx_mf_cospectrum(const iamrx_geom* g, iamrx_mf a, int acomp, iamrx_mf b, int bcomp, int nbins_cap, double* out, long* count, int* nbins)
 {

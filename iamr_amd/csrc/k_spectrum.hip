@@ -19,7 +19,8 @@
 //   k_spec_finish  adds the slots of a shell in slot order (one wavefront per shell) and applies 1 / N^2.
 // No floating-point atomics anywhere: the same call gives the same bits, and the result does not depend on how the level is cut into
 // boxes (only the pack sees the boxes).  Several ranks: every rank packs its own boxes into a zeroed real array, the arrays are summed
-// (exact: every cell has one owner), every rank transforms the whole field -- a gather, it does not scale.
+// (exact: every cell has one owner), every rank transforms the whole field -- a gather, it does not scale.  SPECTRUM_DIST = 1: the
+// shell-summed diagnostics take the slab-decomposed form instead ("the slab form" below): no rank holds more than N / R modes.
 #include "kernels.h"
 #include "launch.h"
 #include <algorithm>
@@ -56,7 +57,8 @@ __global__ void __launch_bounds__(SPEC_THREADS) k_spec_expand2(const double* __r
 // One pass: every workgroup transforms `tw_` pencils of length n = 2^ln in place.  Element e of pencil t of workgroup g lies at
 //   X:  W[(g * tw_ + t) * n + e]                                          (whole x pencils, contiguous)
 //   !X: W[(g % ntile) * tw_ + t + (g / ntile) * ostride + e * estride]    (tw_ adjacent x columns; y: estride = nx, ostride = nx ny;
-//                                                                          z: estride = nx ny, ostride = nx)
+//                                                                          z: estride = nx ny, ostride = nx; z on a y-slab
+//                                                                          Y[jl][k][i]: estride = nx, ostride = nx nz)
 // twid[q] = exp(-2 pi i q / n), q < n / 2.  LDS: tw_ * (n + n / 32) (X) or tw_ * n (!X) double2.
 template <bool X>
 __global__ void __launch_bounds__(SPEC_THREADS) k_spec_fft(double2* __restrict__ W, const double2* __restrict__ twid, int ln, int ltw,
@@ -155,8 +157,16 @@ struct SpecShape {
     double rx, ry, rz;      // L_max / L_d
 };
 
-// The values a mode contributes, NV of them of type T, from the transform W at (row r, column i), at the mirror mode -m (row rm,
-// column im) and from kap2 = kappa^2, which the kernel has formed for the shell index:
+// The part of the shape a launch of k_spec_bin works on.  One rank: all nwg workgroups on the whole image.  The slab form: rank r launches
+// the workgroups that own the rows of its planes [k0, k0 + nkl) and reads them from its slab, whose plane 0 is plane k0.
+struct SpecPart {
+    int wg0, nwg;           // the first workgroup of the launch; the workgroups of the whole shape (the slots of a shell)
+    int k0, nkl;            // the first plane and the number of planes of the image the functor reads
+};
+
+// The values a mode contributes, NV of them of type T, from the transform at (STORAGE row r of the image, column i), at the mirror mode
+// -m (storage row rm of the mirror image, column im) and from kap2 = kappa^2, which the kernel has formed for the shell index from the
+// GLOBAL row.  One rank: image and mirror image are the whole array and a storage row is the global row.
 //   PowerVal  |F|^2                                     CountVal  1
 //   K2Val     (c kap2) |F|^2 with c = (2 pi / L_max)^2: the spectral |grad f|^2
 //   CoVal     W = transform of Z = a + i b, a and b real: with Z = W(m), M = W(-m)
@@ -190,11 +200,12 @@ struct K2Val {
 struct CoVal {
     using T = double;
     static constexpr int NV = 4;
-    const double2* __restrict__ W;
+    const double2* __restrict__ W;       // the image and
+    const double2* __restrict__ M;       // the image of the mirror planes: W itself on one rank (both only read), the received planes in the slab form
     double c;
     __device__ __forceinline__ void operator()(long r, int i, long rm, int im, int nx, double kap2, T v[NV]) const
     {
-        const double2 z = W[r * nx + i], m = W[rm * nx + im];
+        const double2 z = W[r * nx + i], m = M[rm * nx + im];
         const double sr = z.x + m.x, si = z.y - m.y, dr = z.x - m.x, di = z.y + m.y;
         v[0] = 0.5 * (z.x * m.y + z.y * m.x);
         v[1] = 0.25 * (sr * sr + si * si);
@@ -204,9 +215,10 @@ struct CoVal {
 };
 
 // 64 * nw threads, nw = 4, 2 or 1 wavefronts with LDS bins [nw][NV][nbins] of their own (spec_bin: the most that fit 64 KiB);
-// slots[(q * gridDim.x + wg) * nbins + s] for value q: the slots of one value lie together, as k_spec_finish reads them
+// slots[(q * part.nwg + wg) * nbins + s] for value q and the GLOBAL workgroup wg = part.wg0 + blockIdx.x: the slots of one value lie
+// together, as k_spec_finish reads them
 template <class Val>
-__global__ void __launch_bounds__(SPEC_THREADS) k_spec_bin(Val val, SpecShape sh, typename Val::T* __restrict__ slots)
+__global__ void __launch_bounds__(SPEC_THREADS) k_spec_bin(Val val, SpecShape sh, SpecPart part, typename Val::T* __restrict__ slots)
 {
     using T = typename Val::T;
     constexpr int NV = Val::NV;
@@ -218,11 +230,16 @@ __global__ void __launch_bounds__(SPEC_THREADS) k_spec_bin(Val val, SpecShape sh
     __syncthreads();
     T* mine = bins + wv * wstride;
     const int cw = 1 << sh.lcw, nchunk = sh.nx >> sh.lcw, nrows = sh.ny * sh.nz;
-    const int r0 = blockIdx.x * sh.rows_per_wg, r1 = min(r0 + sh.rows_per_wg, nrows);
+    const int wg = part.wg0 + blockIdx.x;
+    const int r0 = wg * sh.rows_per_wg, r1 = min(r0 + sh.rows_per_wg, nrows);
     for (int r = r0 + wv; r < r1; r += nw) {
         const int j = r % sh.ny, k = r / sh.ny;
         const int my = j < sh.ny / 2 ? j : j - sh.ny, mz = k < sh.nz / 2 ? k : k - sh.nz;
-        const long rm = (long)(j ? sh.ny - j : 0) + (long)sh.ny * (k ? sh.nz - k : 0);       // the row of the modes -m: walked with descending i
+        // the storage rows: of the mode in the image, and of the modes -m (walked with descending i) in the mirror image, where the mirror
+        // of the image's plane kl lies in plane (nkl - kl) % nkl -- one rank: plane (nz - k) % nz of the array itself
+        const int kl = k - part.k0;
+        const long rs = (long)j + (long)sh.ny * kl;
+        const long rm = (long)(j ? sh.ny - j : 0) + (long)sh.ny * (kl ? part.nkl - kl : 0);
         const double ay = (double)my * sh.ry, az = (double)mz * sh.rz;
         const double ay2 = ay * ay, az2 = az * az;
         for (int c = 0; c < nchunk; ++c) {
@@ -238,7 +255,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) k_spec_bin(Val val, SpecShape sh
                 const double kap2 = (ax * ax + ay2) + az2;           // the squares added left to right (built without FMA contraction)
                 s = (int)(sqrt(kap2) + 0.5);
                 s = min(s, sh.nbins - 1);                            // (never past the LDS bins, whatever a square root rounds to)
-                val((long)r, i, rm, i ? sh.nx - i : 0, sh.nx, kap2, v);
+                val(rs, i, rm, i ? sh.nx - i : 0, sh.nx, kap2, v);
             }
             // inclusive segmented scan over the runs of equal s (contiguous: s is monotone inside the chunk), a fixed tree
 #pragma unroll
@@ -261,7 +278,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) k_spec_bin(Val val, SpecShape sh
     for (int q = tid; q < wstride; q += nt) {
         T a = bins[q];
         for (int w = 1; w < nw; ++w) a += bins[w * wstride + q];          // the wavefronts in order
-        slots[((long)(q / sh.nbins) * gridDim.x + blockIdx.x) * sh.nbins + q % sh.nbins] = a;
+        slots[((long)(q / sh.nbins) * part.nwg + wg) * sh.nbins + q % sh.nbins] = a;
     }
 }
 
@@ -277,6 +294,85 @@ __global__ void __launch_bounds__(SPEC_THREADS) k_spec_finish(const T* __restric
     if (lane == 0) {
         if constexpr (std::is_floating_point_v<T>) out[s] = v * scale;
         else out[s] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the slab form
+// R ranks, R a power of two that divides ny and nz; nzl = nz / R, nyl = ny / R.  Rank r owns the planes [r nzl, (r + 1) nzl) as the
+// z-slab W[kl][j][i] and, between the two transposes, the rows [r nyl, (r + 1) nyl) of every plane as the y-slab Y[jl][k][i].
+//   k_slab_scatter    the boxes of the rank, cut by the slabs: a piece of the own slab goes straight into W -- (f, 0), or the imaginary part
+//                     alone for the second field of a packed pair --, a piece of another rank's slab as real doubles into that rank's
+//                     part of the send buffer (x fastest inside a piece)
+//   k_slab_place      the received pieces -> W
+//   k_slab_transpose  both transposes, PACK: an image -> the send buffer, one block of N / R^2 modes per destination in rank order with
+//                     the own block left out, which goes straight to its place in the other image; !PACK: the received blocks -> the
+//                     other image.  A row of nx modes is the unit: 2^ltx lanes along x, whole 16-byte modes, as k_spec_mul walks them.
+// a piece: the cells lo .. lo + len - 1 of local fab `fab` (scatter), off doubles into the buffer, or off < 0: into the slab
+struct SlabPiece { int fab; int lo[3], len[3]; long off; };
+
+// grid (chunks, pieces)
+__global__ void __launch_bounds__(SPEC_THREADS) k_slab_scatter(const SlabPiece* __restrict__ pieces, const FabD* __restrict__ st, int comp, BoxD dom, int k0,
+                                                               double* __restrict__ W, double* __restrict__ sbuf, int imag)
+{
+    const SlabPiece pc = pieces[blockIdx.y];
+    const FabD s = st[pc.fab];
+    const auto sp = s.gp() + (long)comp * s.cs;
+    const long np = (long)pc.len[0] * pc.len[1] * pc.len[2], nx = dom.len(0), ny = dom.len(1);
+    for (long p = (long)blockIdx.x * SPEC_THREADS + threadIdx.x; p < np; p += (long)gridDim.x * SPEC_THREADS) {
+        const int i = (int)(p % pc.len[0]);
+        const long r = p / pc.len[0];
+        const int j = (int)(r % pc.len[1]), k = (int)(r / pc.len[1]);
+        const double v = sp[s.off(pc.lo[0] + i, pc.lo[1] + j, pc.lo[2] + k)];
+        if (pc.off >= 0) { sbuf[pc.off + p] = v; continue; }
+        const long o = (long)(pc.lo[0] - dom.lo[0] + i) + nx * ((long)(pc.lo[1] - dom.lo[1] + j) + ny * (long)(pc.lo[2] - dom.lo[2] + k - k0));
+        if (imag) W[2 * o + 1] = v;
+        else { W[2 * o] = v; W[2 * o + 1] = 0.0; }
+    }
+}
+
+// grid (chunks, pieces): cell p of a received piece lies at rbuf[off + p]
+__global__ void __launch_bounds__(SPEC_THREADS) k_slab_place(const SlabPiece* __restrict__ pieces, const double* __restrict__ rbuf, BoxD dom, int k0,
+                                                             double* __restrict__ W, int imag)
+{
+    const SlabPiece pc = pieces[blockIdx.y];
+    const long np = (long)pc.len[0] * pc.len[1] * pc.len[2], nx = dom.len(0), ny = dom.len(1);
+    for (long p = (long)blockIdx.x * SPEC_THREADS + threadIdx.x; p < np; p += (long)gridDim.x * SPEC_THREADS) {
+        const int i = (int)(p % pc.len[0]);
+        const long r = p / pc.len[0];
+        const int j = (int)(r % pc.len[1]), k = (int)(r / pc.len[1]);
+        const double v = rbuf[pc.off + p];
+        const long o = (long)(pc.lo[0] - dom.lo[0] + i) + nx * ((long)(pc.lo[1] - dom.lo[1] + j) + ny * (long)(pc.lo[2] - dom.lo[2] + k - k0));
+        if (imag) W[2 * o + 1] = v;
+        else { W[2 * o] = v; W[2 * o + 1] = 0.0; }
+    }
+}
+
+// Rows are numbered (block, a, b), b fastest, 2^lna x 2^lnb rows per block and one block per rank.  A row lies at row number
+//   blk * nat.blk + a * nat.a + b * nat.b                    in the image on the natural side (PACK: the source, !PACK: the destination),
+//   (blk - (blk > own)) << (lna + lnb) | a << lnb | b        in the buffer (the own block left out),
+//   obase + a * ownr.a + b * ownr.b                          in the other image, the own block of PACK (ownr.blk is not used).
+struct SlabRows { long blk, a, b; };
+template <bool PACK>
+__global__ void __launch_bounds__(SPEC_THREADS) k_slab_transpose(const double2* __restrict__ src, double2* __restrict__ dst, double2* __restrict__ other, int own,
+                                                                 long nrows, int lna, int lnb, int nx, int ltx, SlabRows nat, SlabRows ownr, long obase)
+{
+    const int tx = 1 << ltx, i0 = threadIdx.x & (tx - 1), rsub = threadIdx.x >> ltx, rpb = SPEC_THREADS >> ltx;
+    for (long row = (long)blockIdx.x * rpb + rsub; row < nrows; row += (long)gridDim.x * rpb) {
+        const long b = row & ((1L << lnb) - 1), a = (row >> lnb) & ((1L << lna) - 1);
+        const int blk = (int)(row >> (lna + lnb));
+        const long natural = blk * nat.blk + a * nat.a + b * nat.b;
+        const long packed = ((long)(blk - (blk > own)) << (lna + lnb)) + (a << lnb) + b;
+        const double2* s;
+        double2* d;
+        if (PACK) {
+            s = src + natural * nx;
+            d = blk == own ? other + (obase + a * ownr.a + b * ownr.b) * nx : dst + packed * nx;
+        } else {
+            if (blk == own) continue;
+            s = src + packed * nx;
+            d = dst + natural * nx;
+        }
+        for (int i = i0; i < nx; i += tx) d[i] = s[i];
     }
 }
 
@@ -350,45 +446,61 @@ void spec_pack(const SpecPlan& p, const Geometry& g, const MultiFab& S, int comp
                        ctx.stream, R.get(), W, p.N);
 }
 
-// dir = 0, 1, 2: the transform along that axis of the whole array
-void spec_fft(const SpecPlan& p, int dir, double2* W)
+// dir = 0, 1, 2: one pass of the transform along that axis over the image W.  dir 0: `other` whole x pencils that follow one another;
+// dir 1, 2: pencils of stride estride (in modes), `other` groups of nx of them that lie ostride apart
+void spec_fft(const SpecPlan& p, int dir, double2* W, long estride, long ostride, long other)
 {
     auto& ctx = Context::get();
-    const long nx = p.sh.nx, ny = p.sh.ny;
+    const long nx = p.sh.nx;
     const int ln = p.ln[dir], n = 1 << ln;
     if (dir == 0) {
-        const int pen = 1 << p.xp;
+        const int xp = std::min(p.xp, ilog2((int)other));          // (a slab may hold fewer pencils than a workgroup takes on one rank)
+        const int pen = 1 << xp;
         const size_t lds = (size_t)pen * (n + (n >> 5)) * sizeof(double2);
-        hipLaunchKernelGGL((k_spec_fft<true>), dim3((unsigned)(p.N / ((long)pen * n))), dim3(SPEC_THREADS), lds, ctx.stream, W, p.tw[0].get(), ln, p.xp, 1, 1L, 0L, p.pair);
+        hipLaunchKernelGGL((k_spec_fft<true>), dim3((unsigned)(other / pen)), dim3(SPEC_THREADS), lds, ctx.stream, W, p.tw[0].get(), ln, xp, 1, 1L, 0L, p.pair);
         return;
     }
     const int ltw = dir == 1 ? p.ytw : p.ztw;
     const int ntile = (int)(nx >> ltw);
     const size_t lds = ((size_t)n << ltw) * sizeof(double2);
-    const long estride = dir == 1 ? nx : nx * ny, ostride = dir == 1 ? nx * ny : nx;
-    const long other = dir == 1 ? p.sh.nz : p.sh.ny;
     hipLaunchKernelGGL((k_spec_fft<false>), dim3((unsigned)(ntile * other)), dim3(SPEC_THREADS), lds, ctx.stream, W, p.tw[dir].get(), ln, ltw, ntile, estride, ostride, p.pair);
 }
 
 // the forward transform of the whole array: the three passes; t (or null): a mark after each
 void spec_forward(const SpecPlan& p, double2* W, PassTimer* t = nullptr)
 {
-    for (int d = 0; d < 3; ++d) { spec_fft(p, d, W); PassTimer::mark(t); }
+    const long nx = p.sh.nx, ny = p.sh.ny, nz = p.sh.nz;
+    spec_fft(p, 0, W, 1, 0, ny * nz); PassTimer::mark(t);
+    spec_fft(p, 1, W, nx, nx * ny, nz); PassTimer::mark(t);
+    spec_fft(p, 2, W, nx * ny, nx, ny); PassTimer::mark(t);
 }
 
-// the shell sums of the NV values of val: out[q * nbins + s] = scale * sum; slots: NV * nwg * nbins entries
+// the workgroups [part.wg0, part.wg0 + nlaunch) of the shell sums of val: their slots of the NV * nwg * nbins
 template <class Val>
-void spec_bin(const SpecPlan& p, const Val& val, typename Val::T* slots, double scale, typename Val::T* out)
+void spec_bin_launch(const SpecPlan& p, const Val& val, const SpecPart& part, int nlaunch, typename Val::T* slots)
 {
     using T = typename Val::T;
-    auto& ctx = Context::get();
     const size_t per_wave = (size_t)Val::NV * p.sh.nbins * sizeof(T);
     int nw = SPEC_THREADS / 64;
     while (nw > 1 && nw * per_wave > 65536) nw >>= 1;
-    hipLaunchKernelGGL((k_spec_bin<Val>), dim3((unsigned)p.nwg), dim3(64 * nw), nw * per_wave, ctx.stream, val, p.sh, slots);
-    for (int q = 0; q < Val::NV; ++q)
-        hipLaunchKernelGGL((k_spec_finish<T>), dim3((unsigned)((p.sh.nbins + 3) / 4)), dim3(SPEC_THREADS), 0, ctx.stream,
+    hipLaunchKernelGGL((k_spec_bin<Val>), dim3((unsigned)nlaunch), dim3(64 * nw), nw * per_wave, Context::get().stream, val, p.sh, part, slots);
+}
+
+// out[q * nbins + s] = scale * the sum of the slots of shell s, in slot order
+template <typename T>
+void spec_finish(const SpecPlan& p, int nv, const T* slots, double scale, T* out)
+{
+    for (int q = 0; q < nv; ++q)
+        hipLaunchKernelGGL((k_spec_finish<T>), dim3((unsigned)((p.sh.nbins + 3) / 4)), dim3(SPEC_THREADS), 0, Context::get().stream,
                            slots + (size_t)q * p.nwg * p.sh.nbins, p.nwg, p.sh.nbins, scale, out + (size_t)q * p.sh.nbins);
+}
+
+// the shell sums of the NV values of val over the whole array: out[q * nbins + s] = scale * sum; slots: NV * nwg * nbins entries
+template <class Val>
+void spec_bin(const SpecPlan& p, const Val& val, typename Val::T* slots, double scale, typename Val::T* out)
+{
+    spec_bin_launch(p, val, SpecPart{0, p.nwg, 0, p.sh.nz}, p.nwg, slots);
+    spec_finish(p, Val::NV, slots, scale, out);
 }
 
 // Z = a + i b of a pair of real fields, which may live on different layouts
@@ -427,22 +539,256 @@ void spec_check(const Geometry& g, const MultiFab& S, int nq, const int* comps)
 // the modes per shell ride in the slots and the output of the sums
 static_assert(sizeof(unsigned long long) == sizeof(double), "the counts share the slots of the sums");
 
-// The shell sums of n transforms.  pack(p, q, W) fills the work array with transform q (one component, or a packed pair), val(W) makes the
-// functor whose Val::NV columns land in out[(Val::NV * q + v) * nbins + s]; count (or null): the modes of every shell.
-template <class Pack, class MakeVal>
-void spec_shell_sums(const Geometry& g, int n, int nbins, const Pack& pack, const MakeVal& val, double* out, long* count)
+// ---- the slab form: one rank's share of a transform
+SpecSlabInfo g_slab_info;
+
+// the shapes of rank r of R
+struct SlabShape {
+    int R, r, nzl, nyl;
+    long nloc;              // N / R: the modes of a slab
+    long nblk;              // N / R^2: the modes of a transpose block
+};
+
+SlabShape slab_shape(const SpecPlan& p, int R, int r)
 {
-    using Val = decltype(val((const double2*)nullptr));
-    const SpecPlan p = spec_plan(g, nbins);
-    const size_t nsum = (size_t)Val::NV * n * nbins;
-    DevBuf<double2> W((size_t)p.N);
-    DevBuf<double> slots((size_t)Val::NV * p.nwg * nbins), d_out(nsum + nbins);
+    SlabShape s;
+    s.R = R; s.r = r; s.nzl = p.sh.nz / R; s.nyl = p.sh.ny / R;
+    s.nloc = p.N / R; s.nblk = s.nloc / R;
+    return s;
+}
+
+// The device memory of a slab call.  Every buffer a message reads or writes lives as long as this object, and the caller drains the
+// stream before it dies (the read-back of the sums): an exchange is not a launch, so nothing here relies on the arena's stream order.
+struct SlabWork {
+    DevBuf<double2> W, Y, M;            // the z-slab, the y-slab, the mirror planes of a packed pair
+    DevBuf<double2> S, Rv;              // send and receive blocks of the transposes: distinct allocations
+    std::vector<DevBuf<double>> keep;   // scatter buffers and piece tables
+    SlabWork(const SlabShape& s, bool mirror) : W((size_t)s.nloc), Y((size_t)s.nloc), S((size_t)std::max<long>(s.nloc - s.nblk, 1)), Rv((size_t)std::max<long>(s.nloc - s.nblk, 1))
+    {
+        if (mirror) M = DevBuf<double2>((size_t)s.nloc);
+    }
+};
+
+void slab_exchange(const std::vector<Message>& sends, const std::vector<Message>& recvs)
+{
+    if (sends.empty() && recvs.empty()) return;
+    auto& ctx = Context::get();
+    ++ctx.n_exchange[0];
+    for (const Message& m : sends) { ctx.exchange_doubles[0] += m.count; g_slab_info.sent += (long)m.count; }
+    for (const Message& m : recvs) g_slab_info.received += (long)m.count;
+    ctx.comm->exchange(sends, recvs, ctx.stream);
+}
+
+DevBuf<double> slab_upload_pieces(const std::vector<SlabPiece>& v)
+{
+    static_assert(sizeof(SlabPiece) % sizeof(double) == 0, "a piece table is allocated in doubles");
+    DevBuf<double> d(v.size() * sizeof(SlabPiece) / sizeof(double));
+    Context::get().upload_async(d, v.data(), v.size() * sizeof(SlabPiece));
+    return d;
+}
+
+dim3 slab_piece_grid(const std::vector<SlabPiece>& v)
+{
+    long big = 1;
+    for (const SlabPiece& pc : v) big = std::max(big, (long)pc.len[0] * pc.len[1] * pc.len[2]);
+    return dim3((unsigned)std::min<long>((big + 4 * SPEC_THREADS - 1) / (4 * SPEC_THREADS), 65535), (unsigned)v.size());
+}
+
+// boxes -> z-slabs: component comp of S into the slab W of rank s.r, as (f, 0) or (imag) as the imaginary part alone.  Both sides of
+// the plan come from the layout's boxes and owners, which every rank knows.
+void slab_scatter(const SlabShape& s, const Geometry& g, const MultiFab& S, int comp, int imag, SlabWork& w)
+{
+    auto& ctx = Context::get();
+    const Layout& lay = *S.layout;
+    std::vector<SpecSlabRow> rows;
+    std::string why;
+    if (!spectrum_slab_plan(g.domain, lay.boxes, lay.owner, s.r, s.R, &why, &rows)) throw Error("spectrum: " + why);
+    // one send and one receive allocation, a part per peer in rank order
+    std::vector<long> nsend(s.R, 0), nrecv(s.R, 0), sbase(s.R, 0), rbase(s.R, 0);
+    for (const SpecSlabRow& r : rows) {
+        const long np = (long)(r.hi[0] - r.lo[0] + 1) * (r.hi[1] - r.lo[1] + 1) * (r.hi[2] - r.lo[2] + 1);
+        if (r.kind == 1) nsend[r.peer] += np;
+        else if (r.kind == 2) nrecv[r.peer] += np;
+    }
+    long tsend = 0, trecv = 0;
+    for (int q = 0; q < s.R; ++q) { sbase[q] = tsend; tsend += nsend[q]; rbase[q] = trecv; trecv += nrecv[q]; }
+    std::vector<SlabPiece> out, in;
+    for (const SpecSlabRow& r : rows) {
+        SlabPiece pc;
+        for (int d = 0; d < 3; ++d) { pc.lo[d] = r.lo[d]; pc.len[d] = r.hi[d] - r.lo[d] + 1; }
+        if (r.kind == 2) { pc.fab = -1; pc.off = rbase[r.peer] + r.off; in.push_back(pc); }
+        else { pc.fab = lay.local_of[r.box]; pc.off = r.kind == 1 ? sbase[r.peer] + r.off : -1; out.push_back(pc); }
+    }
+    double *sbuf = nullptr, *rbuf = nullptr;
+    if (tsend > 0) { w.keep.emplace_back((size_t)tsend); sbuf = w.keep.back(); }
+    if (trecv > 0) { w.keep.emplace_back((size_t)trecv); rbuf = w.keep.back(); }
+    const int k0 = s.r * s.nzl;          // the slab's first plane, counted from the domain's
+    if (!out.empty()) {
+        w.keep.push_back(slab_upload_pieces(out));
+        hipLaunchKernelGGL(k_slab_scatter, slab_piece_grid(out), dim3(SPEC_THREADS), 0, ctx.stream, (const SlabPiece*)w.keep.back().get(), S.d_tab, comp, g.domain, k0,
+                           (double*)w.W.get(), sbuf, imag);
+    }
+    std::vector<Message> sends, recvs;
+    for (int q = 0; q < s.R; ++q) {
+        if (nsend[q] > 0) sends.push_back({q, sbuf + sbase[q], (size_t)nsend[q]});
+        if (nrecv[q] > 0) recvs.push_back({q, rbuf + rbase[q], (size_t)nrecv[q]});
+    }
+    slab_exchange(sends, recvs);
+    if (!in.empty()) {
+        w.keep.push_back(slab_upload_pieces(in));
+        hipLaunchKernelGGL(k_slab_place, slab_piece_grid(in), dim3(SPEC_THREADS), 0, ctx.stream, (const SlabPiece*)w.keep.back().get(), rbuf, g.domain, k0,
+                           (double*)w.W.get(), imag);
+    }
+}
+
+unsigned slab_transpose_grid(long nrows, int ltx) { return (unsigned)std::min<long>((nrows + (SPEC_THREADS >> ltx) - 1) / (SPEC_THREADS >> ltx), 8192); }
+
+// z-slabs -> y-slabs (forward) or back: pack, exchange (xchg; the measurement aid leaves it out), unpack; t (or null): a mark after
+// the pack and after the unpack
+void slab_transpose(const SpecPlan& p, const SlabShape& s, bool forward, SlabWork& w, bool xchg, PassTimer* t)
+{
+    auto& ctx = Context::get();
+    const int nx = p.sh.nx, ny = p.sh.ny, nz = p.sh.nz;
+    const int ltx = std::min(p.ln[0], 8);
+    const int lzl = ilog2(s.nzl), lyl = ilog2(s.nyl);
+    const long nrows = s.nloc / nx;
+    const unsigned grid = slab_transpose_grid(nrows, ltx);
+    // forward: rows (d, kl, jl) of W[kl][d nyl + jl] -> Y[jl][s nzl + kl]; back: rows (d, jl, kl) of Y[jl][d nzl + kl] -> W[kl][s nyl + jl]
+    const double2* src = forward ? w.W : w.Y;
+    double2* dst = forward ? w.Y : w.W;
+    const int lna = forward ? lzl : lyl, lnb = forward ? lyl : lzl;
+    const SlabRows from = forward ? SlabRows{s.nyl, ny, 1} : SlabRows{s.nzl, nz, 1};
+    const SlabRows to = forward ? SlabRows{s.nzl, 1, nz} : SlabRows{s.nyl, 1, ny};
+    const long obase = forward ? (long)s.r * s.nzl : (long)s.r * s.nyl;
+    hipLaunchKernelGGL((k_slab_transpose<true>), dim3(grid), dim3(SPEC_THREADS), 0, ctx.stream, src, w.S.get(), dst, s.r, nrows, lna, lnb, nx, ltx, from, to, obase);
+    PassTimer::mark(t);
+    if (xchg) {
+        std::vector<Message> sends, recvs;
+        for (int q = 0; q < s.R; ++q) {
+            if (q == s.r) continue;
+            const size_t slot = (size_t)(q - (q > s.r));
+            sends.push_back({q, (double*)(w.S.get() + slot * s.nblk), (size_t)(2 * s.nblk)});
+            recvs.push_back({q, (double*)(w.Rv.get() + slot * s.nblk), (size_t)(2 * s.nblk)});
+        }
+        slab_exchange(sends, recvs);
+    }
+    if (s.R > 1)
+        hipLaunchKernelGGL((k_slab_transpose<false>), dim3(grid), dim3(SPEC_THREADS), 0, ctx.stream, (const double2*)w.Rv.get(), dst, (double2*)nullptr, s.r, nrows, lna, lnb,
+                           nx, ltx, to, to, 0L);
+    PassTimer::mark(t);
+}
+
+// the passes of one transform on the slab, from the scattered field in w.W to the modes in w.W
+void slab_forward(const SpecPlan& p, const SlabShape& s, SlabWork& w, bool xchg = true, PassTimer* t = nullptr)
+{
+    const long nx = p.sh.nx, ny = p.sh.ny, nz = p.sh.nz;
+    spec_fft(p, 0, w.W, 1, 0, ny * s.nzl); PassTimer::mark(t);
+    spec_fft(p, 1, w.W, nx, nx * ny, s.nzl); PassTimer::mark(t);
+    slab_transpose(p, s, true, w, xchg, t);
+    spec_fft(p, 2, w.Y, nx, nx * nz, s.nyl); PassTimer::mark(t);
+    slab_transpose(p, s, false, w, xchg, t);
+}
+
+// The mirror planes of a packed pair: the mode -m of a row of plane k lies in plane (nz - k) % nz.  The first plane of rank r mirrors
+// into the first plane of rank (R - r) % R, its other nzl - 1 planes into those of rank R - 1 - r in descending order -- so the planes
+// travel as they lie, plane 0 to M[0] and planes 1 .. nzl - 1 to M[1 ..], and the mirror of the slab's plane kl is M[(nzl - kl) % nzl]:
+// at most two messages per rank, straight out of W and into M; a self-addressed part is a device copy.
+void slab_mirror(const SpecPlan& p, const SlabShape& s, SlabWork& w)
+{
+    auto& ctx = Context::get();
+    const size_t plane = (size_t)p.sh.nx * p.sh.ny;
+    const int p0 = (s.R - s.r) % s.R, p1 = s.R - 1 - s.r;
+    std::vector<Message> sends, recvs;
+    if (p0 == s.r) IAMRX_HIP_CHECK(hipMemcpyAsync(w.M.get(), w.W.get(), plane * sizeof(double2), hipMemcpyDeviceToDevice, ctx.stream));
+    else { sends.push_back({p0, (double*)w.W.get(), 2 * plane}); recvs.push_back({p0, (double*)w.M.get(), 2 * plane}); }
+    if (s.nzl > 1) {
+        const size_t rest = plane * (size_t)(s.nzl - 1);
+        if (p1 == s.r) IAMRX_HIP_CHECK(hipMemcpyAsync(w.M.get() + plane, w.W.get() + plane, rest * sizeof(double2), hipMemcpyDeviceToDevice, ctx.stream));
+        else { sends.push_back({p1, (double*)(w.W.get() + plane), 2 * rest}); recvs.push_back({p1, (double*)(w.M.get() + plane), 2 * rest}); }
+    }
+    slab_exchange(sends, recvs);
+}
+
+// the shell sums of this rank's rows: its workgroups of the one-rank partition write their slots at their global index into the zeroed
+// slot array, the arrays of the ranks are added (exact: a slot has one owner, the others hold +0, and a slot is never -0 because the
+// LDS bins start at +0), and every rank adds the slots of a shell in slot order
+template <class Val>
+void slab_bin(const SpecPlan& p, const SlabShape& s, const Val& val, double* slots, double scale, double* out, bool reduce = true)
+{
+    static_assert(std::is_same_v<typename Val::T, double>, "the slot arrays of the ranks are summed as doubles");
+    auto& ctx = Context::get();
+    const int rows = s.nzl * p.sh.ny;
+    IAMRX_ASSERT(p.sh.rows_per_wg <= p.sh.ny && rows % p.sh.rows_per_wg == 0);        // a workgroup's rows lie in one plane
+    const size_t nslot = (size_t)Val::NV * p.nwg * p.sh.nbins;
+    IAMRX_HIP_CHECK(hipMemsetAsync(slots, 0, nslot * sizeof(double), ctx.stream));
+    spec_bin_launch(p, val, SpecPart{s.r * (rows / p.sh.rows_per_wg), p.nwg, s.r * s.nzl, s.nzl}, rows / p.sh.rows_per_wg, slots);
+    if (reduce) ctx.comm->allreduce_device(slots, (int)nslot, ReduceOp::Sum, ctx.stream);
+    spec_finish(p, Val::NV, slots, scale, out);
+}
+
+// SPECTRUM_DIST = 1 and arrays spread over several ranks: the slab form, or the error that names why not.  All arrays of a call must be
+// spread (an array on a replicated layout needs no transport at all: such a call keeps the one-rank path)
+bool spec_use_slab(const Geometry& g, int n, const std::function<SpecPair(int)>& src)
+{
+    if (tune("SPECTRUM_DIST", 0) == 0) return false;
+    for (int q = 0; q < n; ++q) {
+        const SpecPair s = src(q);
+        if (!dense_needs_gather(*s.a) || (s.b && !dense_needs_gather(*s.b))) return false;
+    }
+    const Comm& c = *Context::get().comm;
+    std::string why;
+    if (!spectrum_slab_plan(g.domain, {}, {}, c.rank, c.nranks, &why, nullptr)) throw Error("spectrum: SPECTRUM_DIST = 1: " + why);
+    return true;
+}
+
+template <class MakeVal>
+void spec_shell_sums_slab(const Geometry& g, const SpecPlan& p, int n, const std::function<SpecPair(int)>& src, const MakeVal& val, double* d_out)
+{
+    using Val = decltype(val((const double2*)nullptr, (const double2*)nullptr));
+    const Comm& c = *Context::get().comm;
+    const SlabShape s = slab_shape(p, c.nranks, c.rank);
+    constexpr bool mirror = Val::NV == CoVal::NV;
+    SlabWork w(s, mirror);
+    DevBuf<double> slots((size_t)Val::NV * p.nwg * p.sh.nbins);
+    g_slab_info.path = 1; g_slab_info.max_image = s.nloc; g_slab_info.per_pass = s.nloc;
     const double invN = 1.0 / (double)p.N;
     for (int q = 0; q < n; ++q) {
-        pack(p, q, W);
-        spec_forward(p, W);
-        spec_bin(p, val(W), slots, invN * invN, d_out + (size_t)Val::NV * q * nbins);
+        const SpecPair f = src(q);
+        slab_scatter(s, g, *f.a, f.acomp, 0, w);
+        if (f.b) slab_scatter(s, g, *f.b, f.bcomp, 1, w);
+        slab_forward(p, s, w);
+        if (mirror) slab_mirror(p, s, w);
+        slab_bin(p, s, val(w.W, mirror ? w.M : w.W), slots, invN * invN, d_out + (size_t)Val::NV * q * p.sh.nbins);
     }
+    Context::get().sync();          // every message has been delivered before the buffers of w return to the arena
+}
+
+// The shell sums of n transforms.  src(q): the component of transform q, or its packed pair (b set); val(W, M) makes the functor whose
+// Val::NV columns land in out[(Val::NV * q + v) * nbins + s] (M: the image of the mirror modes); count (or null): the modes of every shell.
+template <class MakeVal>
+void spec_shell_sums(const Geometry& g, int n, int nbins, const std::function<SpecPair(int)>& src, const MakeVal& val, double* out, long* count)
+{
+    using Val = decltype(val((const double2*)nullptr, (const double2*)nullptr));
+    const bool slab = spec_use_slab(g, n, src);
+    const SpecPlan p = spec_plan(g, nbins);
+    const size_t nsum = (size_t)Val::NV * n * nbins;
+    auto& ctx = Context::get();
+    g_slab_info = SpecSlabInfo{0, ctx.comm ? ctx.comm->nranks : 1, p.N, p.N, 0, 0, n};
+    DevBuf<double> d_out(nsum + nbins);
+    DevBuf<double> slots((size_t)Val::NV * p.nwg * nbins);
+    if (slab) spec_shell_sums_slab(g, p, n, src, val, d_out);
+    else {
+        DevBuf<double2> W((size_t)p.N);
+        const double invN = 1.0 / (double)p.N;
+        for (int q = 0; q < n; ++q) {
+            const SpecPair f = src(q);
+            if (f.b) spec_pack_pair(p, g, *f.a, f.acomp, *f.b, f.bcomp, W);
+            else spec_pack(p, g, *f.a, f.acomp, W);
+            spec_forward(p, W);
+            spec_bin(p, val(W, W), slots, invN * invN, d_out + (size_t)Val::NV * q * nbins);
+        }
+    }
+    // the counts read no data: every rank counts the modes of the whole shape itself (never an integer through a floating-point sum)
     if (count) spec_bin(p, CountVal{}, (unsigned long long*)slots.get(), 1.0, (unsigned long long*)(d_out + nsum));
     const double* h = Context::get().read_back(d_out, nsum + (count ? nbins : 0));
     std::copy(h, h + nsum, out);
@@ -457,7 +803,7 @@ void spec_shell_sums(const Geometry& g, int n, int nbins, const Pack& pack, cons
 template <class Pack, class MakeVal>
 void spec_bench_passes(const Geometry& g, int nbins, const Pack& pack, const MakeVal& val, int reps, float* ms)
 {
-    using Val = decltype(val((const double2*)nullptr));
+    using Val = decltype(val((const double2*)nullptr, (const double2*)nullptr));
     const SpecPlan p = spec_plan(g, nbins);
     DevBuf<double2> W((size_t)p.N);
     DevBuf<double> slots((size_t)Val::NV * p.nwg * nbins), d_out((size_t)Val::NV * nbins);
@@ -468,7 +814,7 @@ void spec_bench_passes(const Geometry& g, int nbins, const Pack& pack, const Mak
         pack(p, W);
         t.mark();
         spec_forward(p, W, &t);
-        spec_bin(p, val(W), slots, invN * invN, d_out);
+        spec_bin(p, val(W, W), slots, invN * invN, d_out);
         t.mark();
         t.finish(ms + 5 * r);
     }
@@ -503,8 +849,7 @@ void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* c
 {
     IAMRX_ASSERT(nq >= 1 && nbins == spectrum_nbins(g));
     spec_check(g, S, nq, comps);
-    spec_shell_sums(g, nq, nbins, [&](const SpecPlan& p, int q, double2* W) { spec_pack(p, g, S, comps[q], W); },
-                    [](const double2* W) { return PowerVal{W}; }, out, count);
+    spec_shell_sums(g, nq, nbins, [&](int q) { return SpecPair{&S, comps[q], nullptr, 0}; }, [](const double2* W, const double2*) { return PowerVal{W}; }, out, count);
 }
 
 void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, float* ms)
@@ -512,7 +857,7 @@ void spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int reps, fl
     const int nbins = spectrum_nbins(g);
     dense_check_cover("spectrum", g, *S.layout);
     IAMRX_ASSERT(S.type.cell() && comp >= 0 && comp < S.ncomp && reps >= 1);
-    spec_bench_passes(g, nbins, [&](const SpecPlan& p, double2* W) { spec_pack(p, g, S, comp, W); }, [](const double2* W) { return PowerVal{W}; }, reps, ms);
+    spec_bench_passes(g, nbins, [&](const SpecPlan& p, double2* W) { spec_pack(p, g, S, comp, W); }, [](const double2* W, const double2*) { return PowerVal{W}; }, reps, ms);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- co-spectra
@@ -524,9 +869,7 @@ void cospectrum_compute(const Geometry& g, int npair, const SpecPair* pairs, int
     for (int q = 0; q < npair; ++q) { spec_check(g, *pairs[q].a, 1, &pairs[q].acomp); spec_check(g, *pairs[q].b, 1, &pairs[q].bcomp); }
     static_assert(CoVal::NV == COSPEC_NV, "the columns of a pair");
     const double k2u = spec_k2_unit(g);
-    spec_shell_sums(g, npair, nbins,
-                    [&](const SpecPlan& p, int q, double2* W) { spec_pack_pair(p, g, *pairs[q].a, pairs[q].acomp, *pairs[q].b, pairs[q].bcomp, W); },
-                    [&](const double2* W) { return CoVal{W, k2u}; }, out, count);
+    spec_shell_sums(g, npair, nbins, [&](int q) { return pairs[q]; }, [&](const double2* W, const double2* M) { return CoVal{W, M, k2u}; }, out, count);
 }
 
 void spectrum_k2_compute(const Geometry& g, const MultiFab& S, int nq, const int* comps, int nbins, double* out)
@@ -534,8 +877,7 @@ void spectrum_k2_compute(const Geometry& g, const MultiFab& S, int nq, const int
     IAMRX_ASSERT(nq >= 1 && nbins == spectrum_nbins(g));
     for (int q = 0; q < nq; ++q) spec_check(g, S, 1, &comps[q]);
     const double k2u = spec_k2_unit(g);
-    spec_shell_sums(g, nq, nbins, [&](const SpecPlan& p, int q, double2* W) { spec_pack(p, g, S, comps[q], W); },
-                    [&](const double2* W) { return K2Val{W, k2u}; }, out, nullptr);
+    spec_shell_sums(g, nq, nbins, [&](int q) { return SpecPair{&S, comps[q], nullptr, 0}; }, [&](const double2* W, const double2*) { return K2Val{W, k2u}; }, out, nullptr);
 }
 
 void cospectrum_bench(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int reps, float* ms)
@@ -545,8 +887,52 @@ void cospectrum_bench(const Geometry& g, const MultiFab& A, int acomp, const Mul
     IAMRX_ASSERT(reps >= 1);
     const double k2u = spec_k2_unit(g);
     spec_bench_passes(g, nbins, [&](const SpecPlan& p, double2* W) { spec_pack_pair(p, g, A, acomp, B, bcomp, W); },
-                      [&](const double2* W) { return CoVal{W, k2u}; }, reps, ms);
+                      [&](const double2* W, const double2* M) { return CoVal{W, M, k2u}; }, reps, ms);
 }
+
+// ---------------------------------------------------------------------------------------------------------------- the slab plan (host only)
+bool spectrum_slab_plan(const BoxD& domain, const std::vector<BoxD>& boxes, const std::vector<int>& owner, int rank, int nranks, std::string* why,
+                        std::vector<SpecSlabRow>* rows)
+{
+    const int R = nranks, ny = domain.len(1), nz = domain.len(2);
+    std::string reason;
+    if (R < 1 || rank < 0 || rank >= R) throw Error("spectrum: rank " + std::to_string(rank) + " outside 0 .. " + std::to_string(R - 1));
+    if ((R & (R - 1)) != 0) reason = "the number of ranks, " + std::to_string(R) + ", is not a power of two";
+    else if (ny % R != 0) reason = std::to_string(R) + " ranks do not divide n_y = " + std::to_string(ny);
+    else if (nz % R != 0) reason = std::to_string(R) + " ranks do not divide n_z = " + std::to_string(nz);
+    if (!reason.empty()) {
+        if (why) *why = "the slab-decomposed transform cannot run: " + reason;
+        return false;
+    }
+    if (!rows) return true;
+    IAMRX_ASSERT(boxes.size() == owner.size());
+    rows->clear();
+    const int nzl = nz / R;
+    // box b cut by the slab of rank q -> a row, or nothing
+    auto cut = [&](int b, int q, SpecSlabRow& r) {
+        r.box = b;
+        for (int d = 0; d < 3; ++d) { r.lo[d] = boxes[b].lo[d]; r.hi[d] = boxes[b].hi[d]; }
+        r.lo[2] = std::max(r.lo[2], domain.lo[2] + q * nzl);
+        r.hi[2] = std::min(r.hi[2], domain.lo[2] + (q + 1) * nzl - 1);
+        return r.lo[2] <= r.hi[2];
+    };
+    auto npts = [](const SpecSlabRow& r) { return (long)(r.hi[0] - r.lo[0] + 1) * (r.hi[1] - r.lo[1] + 1) * (r.hi[2] - r.lo[2] + 1); };
+    SpecSlabRow r;
+    for (int b = 0; b < (int)boxes.size(); ++b)
+        if (owner[b] == rank && cut(b, rank, r)) { r.kind = 0; r.peer = rank; r.off = -1; rows->push_back(r); }
+    for (int q = 0; q < R; ++q) {
+        if (q == rank) continue;
+        long off = 0;
+        for (int b = 0; b < (int)boxes.size(); ++b)          // this rank's boxes in q's slab
+            if (owner[b] == rank && cut(b, q, r)) { r.kind = 1; r.peer = q; r.off = off; off += npts(r); rows->push_back(r); }
+        off = 0;
+        for (int b = 0; b < (int)boxes.size(); ++b)          // q's boxes in this rank's slab
+            if (owner[b] == q && cut(b, rank, r)) { r.kind = 2; r.peer = q; r.off = off; off += npts(r); rows->push_back(r); }
+    }
+    return true;
+}
+
+SpecSlabInfo spectrum_slab_info() { return g_slab_info; }
 
 // ---------------------------------------------------------------------------------------------------------------- the way back
 // Filters, the solenoidal projection and the synthetic field (include/iamrx.h).  The inverse transform is the forward one:
@@ -1058,6 +1444,45 @@ void sgs_bench(const Geometry& g, MultiFab* out, const MultiFab& vel, int vcomp,
         t.finish(ms + SGS_BENCH_NP * r);
     }
     if (nout > 0) specop_written(*out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the slab form, timed
+// What rank 0 of R runs for one plain transform, in one process: a level of one box, the rank's own slab, holds the noise (its scatter is
+// the straight copy into W; pieces that travel are copies of the same kind into and out of buffers), the transposes move all R blocks
+// with the exchanges left out (the received blocks are zeros), the shell sums take the rank's workgroups without the sum over the ranks.
+void spectrum_slab_bench(const Geometry& g, int R, int reps, float* ms)
+{
+    const int nbins = spectrum_nbins(g);
+    IAMRX_ASSERT(reps >= 1 && ms);
+    std::string why;
+    if (R < 2 || !spectrum_slab_plan(g.domain, {}, {}, 0, R, &why, nullptr)) throw Error("spectrum_slab_bench: " + (R < 2 ? std::string("at least two ranks") : why));
+    auto& ctx = Context::get();
+    const SpecPlan p = spec_plan(g, nbins);
+    const SlabShape s = slab_shape(p, R, 0);
+    BoxD slab = g.domain;
+    slab.hi[2] = slab.lo[2] + s.nzl - 1;
+    // (the plan of this one box on one rank of R: a single kept piece)
+    const LayoutP lay = std::make_shared<Layout>(std::vector<BoxD>{slab}, std::vector<int>{0}, 0);
+    MultiFab F(lay, cell_type(), 1, 0);
+    hipLaunchKernelGGL(k_spec_noise, dim3(spec_stream_grid(slab.npts()), 1), dim3(SPEC_THREADS), 0, ctx.stream, lay->d_boxes, F.d_tab, 0, g.domain, spec_noise_key(42ull, 0));
+    SlabWork w(s, false);
+    DevBuf<double> slots((size_t)p.nwg * nbins), d_out((size_t)nbins);
+    IAMRX_HIP_CHECK(hipMemsetAsync(w.Rv.get(), 0, (size_t)(s.nloc - s.nblk) * sizeof(double2), ctx.stream));
+    PassTimer t(SPEC_SLAB_BENCH_NP + 1);
+    const double invN = 1.0 / (double)p.N;
+    for (int r = 0; r < reps; ++r) {
+        t.mark();
+        slab_scatter(s, g, F, 0, 0, w);
+        t.mark();
+        slab_forward(p, s, w, false, &t);
+        slab_bin(p, s, PowerVal{w.W}, slots, invN * invN, d_out, false);
+        t.mark();
+        hipLaunchKernelGGL(k_spec_expand, dim3(spec_stream_grid(s.nloc)), dim3(SPEC_THREADS), 0, ctx.stream, (const double*)w.S.get(), w.Y.get(), s.nloc);
+        t.mark();
+        t.finish(ms + SPEC_SLAB_BENCH_NP * r);
+        w.keep.clear();             // (finish has waited for the stream)
+    }
+    ctx.sync();
 }
 
 }  // namespace iamrx

@@ -89,7 +89,8 @@ int spectrum_nbins(const Geometry& g);
 // out[q * nbins + s] = sum over the modes of shell s of |F(m)|^2 of component comps[q] of S (cell-centred; its boxes tile the domain of
 // g; ghost cells are never read), count[s] (or null) = modes of shell s.  nbins = spectrum_nbins(g).  One component at a time through
 // one complex work array from the arena; sums in a fixed order (the same call gives the same bits, however the level is cut into
-// boxes).  Collective on several ranks: the field is gathered on every rank, every rank transforms it and receives the same bits.
+// boxes).  Collective on several ranks: the field is gathered on every rank, every rank transforms it and receives the same bits; with
+// SPECTRUM_DIST = 1 the slab-decomposed transform below instead (the same bits again; an ineligible call throws on every rank).
 void spectrum_compute(const Geometry& g, const MultiFab& S, int nq, const int* comps, int nbins, double* out, long* count);
 // measurement aid (tools/bench_spectrum.py): reps times the five passes of one component -- pack, x, y, z, shell sums -- with an event
 // between them; ms[5 * r + p] = milliseconds of pass p in repeat r
@@ -108,6 +109,20 @@ void spectrum_k2_compute(const Geometry& g, const MultiFab& S, int nq, const int
 // measurement aid (tools/bench_budget.py): the five passes of one packed pair -- pack, x, y, z, the shell sums with the mirror read --
 // timed as spectrum_bench times its five
 void cospectrum_bench(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int reps, float* ms);
+// ---- the slab-decomposed transform of several ranks (SPECTRUM_DIST = 1; include/iamrx.h, k_spectrum.hip) ----
+// a box cut by a z-slab: kind 0 the piece stays on the rank, 1 sent to peer, 2 received from peer; off: doubles, in the buffer of that
+// peer (-1 for kind 0)
+struct SpecSlabRow { int kind, peer, box; int lo[3], hi[3]; long off; };
+// host only: is the slab path eligible on nranks ranks (why: the reason if not), and the scatter plan of `rank`.  Rows: the kept
+// pieces, then per peer in rank order its send rows and its receive rows, each in box order
+bool spectrum_slab_plan(const BoxD& domain, const std::vector<BoxD>& boxes, const std::vector<int>& owner, int rank, int nranks, std::string* why,
+                        std::vector<SpecSlabRow>* rows);
+// the last shell-sum call of this rank (include/iamrx.h: iamrx_spectrum_slab_info)
+struct SpecSlabInfo { long path = 0, ranks = 1, max_image = 0, per_pass = 0, sent = 0, received = 0, transforms = 0; };
+SpecSlabInfo spectrum_slab_info();
+// measurement aid (tools/bench_spectrum_slab.py): the kernels one rank of R runs for one plain transform, the exchanges left out
+constexpr int SPEC_SLAB_BENCH_NP = 10;
+void spectrum_slab_bench(const Geometry& g, int R, int reps, float* ms);
 // ---- the way back from mode space (include/iamrx.h): filters, the solenoidal projection, a synthetic isotropic field ----
 // f = conj(FFT(conj(N F))) / N through the forward passes; the conjugation and 1 / N ride on the mode-space pass k_spec_mul<Op>
 constexpr int SPECOP_NKIND = 4;             // identity, sharp, Gaussian, box

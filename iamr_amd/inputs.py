@@ -23,7 +23,9 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   ns.spectrum_interval (-1: off) / ns.spectrum_file ("spec"): this library's own keys for the shell-summed spectra of level 0
   (iamr_amd/spectrum.py), carried under "spectrum"; ns.budget_interval (-1: off) / ns.budget_file ("sbud"): the spectral kinetic-energy
   budget of level 0 (iamr_amd/budget.py), carried under "budget", with the preconditions of the spectra; an interval > 0 needs a fully periodic three-dimensional domain whose extents are
-  powers of two in 4 .. 1024,
+  powers of two in 4 .. 1024; ns.spectral_distributed (0 | 1; 0): 1 sets the library's registry key SPECTRUM_DIST, so that the spectra and
+  the budget of a run on several ranks take the slab-decomposed transform instead of the gather; carried as "spectral_distributed",
+  refused in a two-dimensional run as the spectra are,
   ns.sgs_interval (-1: off) / ns.sgs_filter (sharp | gaussian | box; gaussian) / ns.sgs_kc (1 .. 8 cut-offs, required with an interval > 0) /
   ns.sgs_file ("sgs"): this library's own keys for the a-priori LES analysis of level 0 (iamr_amd/sgs.py), carried under "sgs", with the
   preconditions of the spectra,
@@ -582,6 +584,13 @@ class Inputs:
                 if not extent_ok(n[d]):
                     raise ValueError(f"inputs: ns.budget_interval > 0 needs extents that are powers of two in 4 .. 1024, amr.n_cell has "
                                      f"n_{'xyz'[d]} = {n[d]}")
+        # the slab-decomposed transform of the spectra and the budget on several ranks (the library's registry key SPECTRUM_DIST)
+        spectral_distributed = self.integer("ns.spectral_distributed", 0)
+        if spectral_distributed not in (0, 1):
+            raise ValueError(f"inputs: ns.spectral_distributed = {spectral_distributed}: 0 (the gather) or 1 (the slab-decomposed transform)")
+        if spectral_distributed and slab:
+            raise NotImplementedError("inputs: ns.spectral_distributed = 1 in a two-dimensional run: the transform is three-dimensional only "
+                                      "(the slab's thickness direction has two cells)")
         # a-priori LES analysis (this library's own keys; sgs.py): every sgs_interval-th level-0 step and once for the initial data one row
         # per cut-off of ns.sgs_kc in the one text file ns.sgs_file, of level 0; the preconditions of the spectra
         sgs = dict(interval=self.integer("ns.sgs_interval", -1), filter=self.string("ns.sgs_filter", "gaussian"),
@@ -664,7 +673,7 @@ class Inputs:
                     if v in VELGRAD_NAMES and v not in VELGRAD_NAMES_2D:
                         raise NotImplementedError(f"inputs: {key} names '{v}' in a two-dimensional run: of the velocity-gradient fields a slab "
                                                   f"knows {' '.join(VELGRAD_NAMES_2D)}")
-        out = dict(profile=profile, spectrum=spectrum, budget=budget, sgs=sgs, strfn=strfn, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
+        out = dict(profile=profile, spectrum=spectrum, budget=budget, spectral_distributed=spectral_distributed, sgs=sgs, strfn=strfn, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
                    max_step=self.integer("max_step", -1), stop_time=self.real("stop_time", -1.0),
                    plot_int=self.integer("amr.plot_int", -1), plot_file=self.string("amr.plot_file", "plt"), plot_vars=self.name_list("amr.plot_vars", "ALL"),
                    derive_plot_vars=dpv, fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,

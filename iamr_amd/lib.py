@@ -508,6 +508,26 @@ def mf_spectrum(geom, mf, comp=0, ncomp=1):
     return _s.mf_spectrum(geom, mf, comp, ncomp)
 
 
+def host_spectrum_slab_plan(geom, boxes, owners, rank, nranks):
+    """host only: eligibility and the scatter plan of the slab-decomposed transform (include/iamrx.h: iamrx_host_spectrum_slab_plan)
+    -> (eligible, reason, rows (n, 10) int64: spectrum.SLAB_ROW)"""
+    from . import spectrum as _s
+    return _s.host_slab_plan(geom, boxes, owners, rank, nranks)
+
+
+def spectrum_slab_info():
+    """the path, the sizes and the traffic of the last shell-sum call on this rank (include/iamrx.h: iamrx_spectrum_slab_info) -> dict
+    with the keys spectrum.SLAB_INFO"""
+    from . import spectrum as _s
+    return _s.slab_info()
+
+
+def spectrum_slab_bench(geom, nranks, reps=1):
+    """milliseconds (reps, 10) of the kernels one rank of nranks runs for one transform (include/iamrx.h: iamrx_spectrum_slab_bench)"""
+    from . import spectrum as _s
+    return _s.slab_bench(geom, nranks, reps)
+
+
 def mf_cospectrum(geom, a, b, acomp=0, bcomp=0):
     """co-spectrum of component acomp of a and bcomp of b, cell-centred MultiFabs that each tile the fully periodic domain of geom
     (include/iamrx.h: iamrx_mf_cospectrum; one packed transform) -> (C_ab, P_a, P_b, count), each (nbins,)"""

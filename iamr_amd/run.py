@@ -518,6 +518,8 @@ def main(argv, observe=None):
     if pr.get("slab") and world > 1:
         raise NotImplementedError("iamr_amd.run: two-dimensional inputs (run on a y-periodic slab) are single-rank runs")
     hierarchy = bool(pr["fine_boxes"] or pr.get("regrid") or (pr.get("restart") and pr.get("max_level", 0) > 0))
+    if pr.get("spectral_distributed"):          # before the first spectrum or budget: they take the slab-decomposed transform on several ranks
+        lib.tuning_set("SPECTRUM_DIST", 1)
     rc = drive(pr, inp, lib, N, hierarchy, rank, world, observe)
     comm.stop()
     return rc

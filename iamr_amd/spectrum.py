@@ -45,6 +45,46 @@ def mf_spectrum(geom, mf, comp=0, ncomp=1):
     return out[:ncomp * nb.value].reshape(ncomp, nb.value).copy(), cnt[:nb.value].copy()
 
 
+SLAB_ROW = ("kind", "peer", "box", "lo0", "lo1", "lo2", "hi0", "hi1", "hi2", "off")          # kind: 0 kept, 1 sent, 2 received
+SLAB_INFO = ("path", "ranks", "max_image", "per_pass", "sent", "received", "transforms")
+SLAB_BENCH_PASSES = ("scatter", "x", "y", "pack_zy", "unpack_zy", "z", "pack_yz", "unpack_yz", "shell_sums", "expand")
+
+
+def host_slab_plan(geom, boxes, owners, rank, nranks):
+    """iamrx_host_spectrum_slab_plan (host only, no device): is the slab-decomposed transform eligible on nranks ranks, and the scatter
+    plan of `rank` for the boxes [(lo, hi)] with their owners -> (eligible, reason, rows (n, 10) int64 with the columns SLAB_ROW)"""
+    from .lib import lib, check
+    nb = len(boxes)
+    arr = (C.c_int * (6 * max(nb, 1)))()
+    for i, (lo, hi) in enumerate(boxes):
+        for d in range(3):
+            arr[6 * i + d], arr[6 * i + 3 + d] = int(lo[d]), int(hi[d])
+    own = (C.c_int * max(nb, 1))(*[int(o) for o in owners])
+    ok, n, why = C.c_int(), C.c_int(), C.create_string_buffer(256)
+    f = lib().iamrx_host_spectrum_slab_plan
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+    check(f(C.byref(geom), nb, arr, own, int(rank), int(nranks), C.byref(ok), why, 256, 0, None, C.byref(n)))
+    rows = np.zeros((n.value, len(SLAB_ROW)), dtype=np.int64)
+    check(f(C.byref(geom), nb, arr, own, int(rank), int(nranks), C.byref(ok), why, 256, n.value, rows.ctypes.data_as(C.c_void_p), C.byref(n)))
+    return bool(ok.value), why.value.decode(), rows
+
+
+def slab_info():
+    """iamrx_spectrum_slab_info: the last shell-sum call on this rank -> dict with the keys SLAB_INFO (path 0: local or gather, 1: slab)"""
+    from .lib import lib, check
+    v = (C.c_long * len(SLAB_INFO))()
+    check(lib().iamrx_spectrum_slab_info(v))
+    return dict(zip(SLAB_INFO, (int(x) for x in v)))
+
+
+def slab_bench(geom, nranks, reps):
+    """iamrx_spectrum_slab_bench: milliseconds (reps, len(SLAB_BENCH_PASSES)) of the kernels one rank of nranks runs for one transform"""
+    from .lib import lib, check
+    ms = np.zeros((int(reps), len(SLAB_BENCH_PASSES)), dtype=np.float32)
+    check(lib().iamrx_spectrum_slab_bench(C.byref(geom), int(nranks), int(reps), ms.ctypes.data_as(C.POINTER(C.c_float))))
+    return ms
+
+
 def level_spectrum(entry, handle, geom):
     """iamrx_ns_spectrum / iamrx_amr_spectrum (entry: the library's function) on a level or hierarchy handle -> the dict of as_dict"""
     from .lib import lib, check

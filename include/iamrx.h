@@ -632,8 +632,8 @@ int iamrx_ns_plane_profile(iamrx_ns ns, int dir, int nbins_cap, double* out, int
  * returns to the library's arena; sums in a fixed order without floating-point atomics: the same call gives the same bits, and the
  * bits do not depend on how the level is cut into boxes.  Collective on several ranks: every rank writes the cells of its own boxes
  * into a zeroed real array, the arrays are summed through the communicator (exact: a cell has one owner), and EVERY rank then
- * transforms the whole field and receives the same bits -- a gather that does not scale with the number of ranks (a distributed
- * transform is not built).  Error: a direction that is not periodic; an extent that is not a power of two in 4 .. 1024 (the message
+ * transforms the whole field and receives the same bits -- a gather that does not scale with the number of ranks (the default; the
+ * slab-decomposed transform below, SPECTRUM_DIST = 1, gives the same bits from N / R modes per rank).  Error: a direction that is not periodic; an extent that is not a power of two in 4 .. 1024 (the message
  * names it); nbins_cap < *nbins (*nbins is set all the same); boxes that do not cover the domain; more than 2048 shells (side lengths
  * that differ too much for the extents). */
 int iamrx_spectrum_nq(void);
@@ -642,6 +642,36 @@ int iamrx_ns_spectrum(iamrx_ns ns, int nbins_cap, double* out, long* count, int*
 /* measurement aid (tools/bench_spectrum.py): reps times the five passes of one component (pack, x, y, z transform, shell sums) with an
  * event between them; ms[5 * r + p] = milliseconds of pass p in repeat r.  Nothing is read back. */
 int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, float* ms);
+/* The slab-decomposed transform of the shell-summed diagnostics on several ranks (registry key SPECTRUM_DIST = 1, default 0: the gather
+ * above, byte for byte).  With the key at 1, iamrx_mf_spectrum, iamrx_mf_spectrum_k2, iamrx_mf_cospectrum and whatever calls them
+ * (the level and hierarchy spectra and budgets) take this path whenever the array is spread over R > 1 ranks: rank r owns the planes
+ * k in [r n_z / R, (r + 1) n_z / R) as a complex slab of N / R elements; the boxes are cut by the slabs and the pieces that belong to
+ * another rank travel as real doubles; x and y passes on the slab; a transpose to y-slabs, the z pass, a transpose back; the shell sums
+ * with the workgroup partition, the wavefront order and the slot order of one rank (a workgroup's rows lie on one rank; the slot arrays
+ * are summed exactly: a slot has one owner, the others hold +0), so the bytes of the result are those of one rank; a packed pair
+ * receives its mirror planes in at most two messages.  No rank holds an N-sized array.  Eligible: R a power of two that divides n_y and
+ * n_z; with the key at 1 an ineligible call is an error that names the reason, on every rank, before anything is sent.  One rank or a
+ * replicated layout: the key has no effect.  The way back from mode space, the a-priori LES analysis and the structure functions stay on
+ * the gather.
+ * iamrx_host_spectrum_slab_plan: host only, no device.  The scatter plan of rank `rank` of `nranks` for the boxes lo_hi[6 b] .. (lo,
+ * then hi) with owners owner[b] on the domain of g.  *eligible = 1, or 0 with the reason in reason[reason_cap] (may be NULL).
+ * rows[10 * n + .]: kind (0 the piece stays on the rank, 1 sent, 2 received), peer (the own rank for kind 0), global box index, piece
+ * lo[3], hi[3], offset of the piece (doubles) in the buffer to or from that peer (kind 0: -1).  A piece is a box cut by a slab; the
+ * pieces of a buffer follow one another in box order, x fastest inside a piece, so that p's rows to q are q's rows from p.  *nrows is
+ * the number of rows, of which min(*nrows, max_rows) are written (rows may be NULL).
+ * iamrx_spectrum_slab_info: the last shell-sum call on this rank.  out[0] path (0 local or gather, 1 slab), [1] ranks, [2] complex
+ * elements of the largest work image allocated, [3] elements transformed per pass, [4] doubles sent and [5] doubles received through
+ * the communicator's exchange, summed over the call (the all-reduce of the gather and of the slot arrays is not an exchange),
+ * [6] transforms done.
+ * iamrx_spectrum_slab_bench (tools/bench_spectrum_slab.py): the kernels ONE rank of nranks runs for one plain transform, on arena
+ * buffers of the per-rank shapes with the exchanges left out: ms[IAMRX_SPECTRUM_SLAB_BENCH_NP * r + p], p = 0 scatter, 1 x, 2 y, 3 pack,
+ * 4 unpack, 5 z, 6 pack, 7 unpack, 8 shell sums, 9 k_spec_expand over N / nranks elements (the streaming yardstick).  One process, no
+ * communicator needed. */
+#define IAMRX_SPECTRUM_SLAB_BENCH_NP 10
+int iamrx_host_spectrum_slab_plan(const iamrx_geom* g, int nboxes, const int* lo_hi, const int* owner, int rank, int nranks, int* eligible,
+                                  char* reason, size_t reason_cap, int max_rows, long* rows, int* nrows);
+int iamrx_spectrum_slab_info(long out[7]);
+int iamrx_spectrum_slab_bench(const iamrx_geom* g, int nranks, int reps, float* ms);
 /* Co-spectra and the spectral kinetic-energy budget dE(k)/dt = T(k) - D(k) + F(k) of a fully periodic level (this library's own
  * diagnostic; k_spectrum.hip, k_convect.hip).  The transform F, the signed mode numbers, kappa, the shell index s, *nbins and count are
  * those of iamrx_mf_spectrum, and so are the restrictions and the errors, checked in the same order (*nbins is set before the capacity
@@ -672,7 +702,8 @@ int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, f
  * iamrx_budget_nq: the columns of the level and hierarchy entries, 4: E, T, D, F.  iamrx_ns_spectral_budget: out[q * nbins + s]; the
  * velocity is FillPatched once with one ghost layer, N (and f) are formed into arrays that return to the arena, three packed transforms
  * (u_i, N_i) give E, T and D, three more (u_i, f_i) give F when the forcing is on.  Collective on several ranks as the spectra are (a
- * gather).  Not built: density weighting, levels above 0, a distributed transform, time averaging, the eddy-viscosity part of D. */
+ * gather, or the slab-decomposed transform with SPECTRUM_DIST = 1).  Not built: density weighting, levels above 0, time averaging, the
+ * eddy-viscosity part of D. */
 int iamrx_mf_cospectrum(const iamrx_geom* g, iamrx_mf a, int acomp, iamrx_mf b, int bcomp, int nbins_cap, double* out, long* count, int* nbins);
 int iamrx_mf_spectrum_k2(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, int nbins_cap, double* out, int* nbins);
 int iamrx_convective_term(const iamrx_geom* g, iamrx_mf out, int ocomp, iamrx_mf vel, int vcomp);
