@@ -228,6 +228,12 @@ class Amr:
         from . import spectrum as _s
         return _s.level_spectrum(lib().iamrx_amr_spectrum, self.h, self.geom0)
 
+    def plane_spectrum(self, dir):
+        """ring-summed plane spectra of LEVEL 0 of the hierarchy (as spectrum takes its level; include/iamrx.h:
+        iamrx_amr_plane_spectrum) -> the dict of NavierStokes.plane_spectrum; the same bits on every rank.  Collective."""
+        from . import planespec as _p
+        return _p.level_plane_spectrum(lib().iamrx_amr_plane_spectrum, self.h, self.geom0, dir)
+
     def filtered(self, names, kind, kc):
         """the named fields of LEVEL 0 of the hierarchy (as spectrum takes its level) low-pass filtered into a new MultiFab on that
         level's layout -> NavierStokes.filtered of level 0.  Collective."""

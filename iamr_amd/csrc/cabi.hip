@@ -1284,6 +1284,43 @@ int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, f
     IAMRX_CATCH
 }
 
+// ---- plane spectra: ring-summed 2-D spectra along a normal axis (k_spectrum.hip)
+int iamrx_plane_spectrum_nq(void) { return PLANE_SPECTRUM_NQ; }
+int iamrx_mf_plane_spectrum(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, int dir, int nplanes_cap, int nrings_cap, double* out, long* count,
+                            int* nplanes, int* nrings)
+{
+    IAMRX_TRY
+    if (!g || !mf) throw Error("iamrx_mf_plane_spectrum: null geometry or array");
+    std::vector<SpecPair> f;
+    for (int q = 0; q < ncomp; ++q) f.push_back(SpecPair{&mf->mf, comp + q, nullptr, 0});
+    plane_spectrum_of(to_geom(g), (int)f.size(), f.data(), dir, nplanes_cap, nrings_cap, out, count, nplanes, nrings);
+    IAMRX_CATCH
+}
+int iamrx_mf_plane_cospectrum(const iamrx_geom* g, iamrx_mf a, int acomp, iamrx_mf b, int bcomp, int dir, int nplanes_cap, int nrings_cap, double* out,
+                              long* count, int* nplanes, int* nrings)
+{
+    IAMRX_TRY
+    if (!g || !a || !b) throw Error("iamrx_mf_plane_cospectrum: null geometry or array");
+    const SpecPair f{&a->mf, acomp, &b->mf, bcomp};
+    plane_spectrum_of(to_geom(g), 1, &f, dir, nplanes_cap, nrings_cap, out, count, nplanes, nrings);
+    IAMRX_CATCH
+}
+int iamrx_ns_plane_spectrum(iamrx_ns ns, int dir, int nplanes_cap, int nrings_cap, double* out, long* count, int* nplanes, int* nrings)
+{
+    IAMRX_TRY
+    if (!ns) throw Error("iamrx_ns_plane_spectrum: null level");
+    ns->ns->plane_spectrum(dir, nplanes_cap, nrings_cap, out, count, nplanes, nrings);
+    IAMRX_CATCH
+}
+int iamrx_plane_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int dir, int reps, float* ms)
+{
+    IAMRX_TRY
+    static_assert(IAMRX_PLANE_SPECTRUM_BENCH_NP == PLANE_SPECTRUM_BENCH_NP, "the passes of the measurement aid");
+    if (!g || !mf || !ms || reps < 1) throw Error("iamrx_plane_spectrum_bench: null argument or reps < 1");
+    plane_spectrum_bench(to_geom(g), mf->mf, comp, dir, reps, ms);
+    IAMRX_CATCH
+}
+
 // ---- the slab-decomposed transform of several ranks (k_spectrum.hip)
 // host-only (no device needed): eligibility and the scatter plan of rank `rank` of `nranks`; rows of 10 longs: kind, peer, box, lo[3], hi[3], off
 int iamrx_host_spectrum_slab_plan(const iamrx_geom* g, int nboxes, const int* lo_hi, const int* owner, int rank, int nranks, int* eligible,
@@ -1968,6 +2005,13 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
     IAMRX_CATCH
 }
 int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins) { IAMRX_TRY a->amr->level(0).spectrum(nbins_cap, out, count, nbins); IAMRX_CATCH }
+int iamrx_amr_plane_spectrum(iamrx_amr a, int dir, int nplanes_cap, int nrings_cap, double* out, long* count, int* nplanes, int* nrings)
+{
+    IAMRX_TRY
+    if (!a) throw Error("iamrx_amr_plane_spectrum: null hierarchy");
+    a->amr->level(0).plane_spectrum(dir, nplanes_cap, nrings_cap, out, count, nplanes, nrings);
+    IAMRX_CATCH
+}
 int iamrx_amr_sgs(iamrx_amr a, int kind, double kc, iamrx_mf out, int ocomp, int nout, const int* which, double* stats, long* counts)
 {
     IAMRX_TRY a->amr->level(0).sgs(kind, kc, out ? &out->mf : nullptr, ocomp, nout, which, stats, counts); IAMRX_CATCH

@@ -488,12 +488,14 @@ void spec_bin_launch(const SpecPlan& p, const Val& val, const SpecPart& part, in
 
 // out[q * nbins + s] = scale * the sum of the slots of shell s, in slot order
 template <typename T>
-void spec_finish(const SpecPlan& p, int nv, const T* slots, double scale, T* out)
+void spec_finish_slots(int nv, int nwg, int nbins, const T* slots, double scale, T* out)
 {
     for (int q = 0; q < nv; ++q)
-        hipLaunchKernelGGL((k_spec_finish<T>), dim3((unsigned)((p.sh.nbins + 3) / 4)), dim3(SPEC_THREADS), 0, Context::get().stream,
-                           slots + (size_t)q * p.nwg * p.sh.nbins, p.nwg, p.sh.nbins, scale, out + (size_t)q * p.sh.nbins);
+        hipLaunchKernelGGL((k_spec_finish<T>), dim3((unsigned)((nbins + 3) / 4)), dim3(SPEC_THREADS), 0, Context::get().stream,
+                           slots + (size_t)q * nwg * nbins, nwg, nbins, scale, out + (size_t)q * nbins);
 }
+template <typename T>
+void spec_finish(const SpecPlan& p, int nv, const T* slots, double scale, T* out) { spec_finish_slots(nv, p.nwg, p.sh.nbins, slots, scale, out); }
 
 // the shell sums of the NV values of val over the whole array: out[q * nbins + s] = scale * sum; slots: NV * nwg * nbins entries
 template <class Val>
@@ -1481,6 +1483,374 @@ void spectrum_slab_bench(const Geometry& g, int R, int reps, float* ms)
         t.mark();
         t.finish(ms + SPEC_SLAB_BENCH_NP * r);
         w.keep.clear();             // (finish has waited for the stream)
+    }
+    ctx.sync();
+}
+
+// ---------------------------------------------------------------------------------------------------------------- plane spectra
+// Ring-summed 2-D spectra along a normal axis `dir` (include/iamrx.h: iamrx_mf_plane_spectrum): the other two axes a < b are transformed
+// by two spec_fft passes over the whole dense image, the normal axis is not; plane p (the cell index along dir) keeps its own sums
+// P(p, s) over the rings s = (int)(sqrt((m_a r_a)^2 + (m_b r_b)^2) + 0.5).  The image stays W[k][j][i], x fastest, so the ring pass has
+// two shapes:
+//   k_plane_ring<V>    dir = 1, 2: a row along x lies in one plane and the ring index varies along it -- the segmented wave scan of
+//                      k_spec_bin; a workgroup owns rows of ONE plane at a time, LDS bins [wavefront][value][nrings], slots per (plane,
+//                      workgroup of the plane); the grid is capped at SPEC_MAXWG, a workgroup then walks several planes in turn
+//   k_plane_ring_x<V>  dir = 0: every element of a row lies in another plane and the ring index is constant along the row.  The host sorts
+//                      the rows (j, k) by ring, stable in row order, and cuts every ring into chunks of `ch` rows; a wavefront takes one
+//                      (chunk, 64 planes along x) and adds its rows in table order into one register per lane: no LDS at all, every load
+//                      16 B per lane along x.  Chunk c of ring s writes slot c of that ring; rings with fewer chunks keep +0 there.
+// Both write slots[((value * nslot + slot) * nplanes + p) * nrings + s], which k_spec_finish sums in slot order as nplanes * nrings
+// "shells".  No floating-point atomics; the order of every sum depends on the shape alone, not on boxes or ranks.  count(s) is the
+// same for every plane and is counted on the host from the integer ring table.  Several ranks: the gather of spec_pack only
+// (SPECTRUM_DIST does not apply: a slab form along a normal z would need no transpose at all and is left for later).
+namespace {
+
+struct PlaneShape {
+    int nx, nt, nplanes, nrings;    // the row length, the rows of a plane, the planes, the rings
+    int lcw, G, rows_per_wg, npg;   // log2 of the chunk width; workgroups and rows per workgroup of a plane; planes the grid holds at a time
+    long ps, ts;                    // row t of plane p is storage row p * ps + t * ts
+    double rx, rt;                  // L2 / L_x, L2 / L_t
+};
+
+struct PlaneCoVal {                 // C_ab, P_a, P_b with the arithmetic of CoVal (its k^2-weighted column is not formed)
+    using T = double;
+    static constexpr int NV = 3;
+    CoVal co;
+    __device__ __forceinline__ void operator()(long r, int i, long rm, int im, int nx, double, T v[NV]) const
+    {
+        T t[CoVal::NV];
+        co(r, i, rm, im, nx, 0.0, t);
+        v[0] = t[0]; v[1] = t[1]; v[2] = t[2];
+    }
+};
+
+// 64 * nw threads; grid npg * G: workgroup g of plane group pg takes the rows [g rows_per_wg, (g + 1) rows_per_wg) of the planes pg,
+// pg + npg, ...; the mirror mode (-m_x, -m_t) lies in the same plane
+template <class Val>
+__global__ void __launch_bounds__(SPEC_THREADS) k_plane_ring(Val val, PlaneShape sh, typename Val::T* __restrict__ slots)
+{
+    using T = typename Val::T;
+    constexpr int NV = Val::NV;
+    extern __shared__ double2 spec_lds[];
+    T* bins = (T*)spec_lds;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nt = blockDim.x, nw = nt >> 6;
+    const int wstride = NV * sh.nrings;
+    T* mine = bins + wv * wstride;
+    const int cw = 1 << sh.lcw, nchunk = sh.nx >> sh.lcw;
+    const int wg = blockIdx.x % sh.G;
+    const int t0 = wg * sh.rows_per_wg, t1 = min(t0 + sh.rows_per_wg, sh.nt);
+    for (int p = blockIdx.x / sh.G; p < sh.nplanes; p += sh.npg) {
+        for (int q = tid; q < nw * wstride; q += nt) bins[q] = (T)0;
+        __syncthreads();
+        for (int t = t0 + wv; t < t1; t += nw) {
+            const int mt = t < sh.nt / 2 ? t : t - sh.nt;
+            const long rs = (long)p * sh.ps + (long)t * sh.ts;
+            const long rm = (long)p * sh.ps + (long)(t ? sh.nt - t : 0) * sh.ts;
+            const double at = (double)mt * sh.rt;
+            const double at2 = at * at;
+            for (int c = 0; c < nchunk; ++c) {
+                const int i = (c << sh.lcw) + lane;
+                const bool act = lane < cw;
+                int s = -1;
+                T v[NV];
+#pragma unroll
+                for (int q = 0; q < NV; ++q) v[q] = (T)0;
+                if (act) {
+                    const int mx = i < sh.nx / 2 ? i : i - sh.nx;
+                    const double ax = (double)mx * sh.rx;
+                    const double kap2 = ax * ax + at2;                   // x is the lower axis: its square first (no FMA contraction)
+                    s = (int)(sqrt(kap2) + 0.5);
+                    s = min(s, sh.nrings - 1);
+                    val(rs, i, rm, i ? sh.nx - i : 0, sh.nx, kap2, v);
+                }
+                // the segmented scan of k_spec_bin: the ring index is monotone inside a chunk
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const int ks = __shfl_up(s, off, 64);
+#pragma unroll
+                    for (int q = 0; q < NV; ++q) {
+                        const T up = __shfl_up(v[q], off, 64);
+                        if (lane >= off && ks == s) v[q] += up;
+                    }
+                }
+                const int sn = __shfl_down(s, 1, 64);
+                if (act && (lane == cw - 1 || sn != s)) {
+#pragma unroll
+                    for (int q = 0; q < NV; ++q) mine[q * sh.nrings + s] += v[q];
+                }
+            }
+        }
+        __syncthreads();
+        for (int q = tid; q < wstride; q += nt) {
+            T a = bins[q];
+            for (int w = 1; w < nw; ++w) a += bins[w * wstride + q];          // the wavefronts in order
+            slots[(((long)(q / sh.nrings) * sh.G + wg) * sh.nplanes + p) * sh.nrings + q % sh.nrings] = a;
+        }
+        __syncthreads();
+    }
+}
+
+// a chunk of the sorted row table: rows[start .. start + count) lie in ring s and are chunk c of it
+struct RingChunk { int s, c, start, count; };
+
+// 256 threads = four independent wavefronts; unit u = (chunk u / nxt, planes 64 (u % nxt) ..): lane l sums |F|^2 (or the values of a
+// packed pair, whose mirror row (n_y - j, n_z - k) is read at the same i) of plane i over the chunk's rows in table order
+template <class Val>
+__global__ void __launch_bounds__(SPEC_THREADS) k_plane_ring_x(Val val, const int* __restrict__ rows, const RingChunk* __restrict__ chunks, int nchunk, int nx,
+                                                               int nxt, int ny, int nz, int nrings, int maxc, typename Val::T* __restrict__ slots)
+{
+    using T = typename Val::T;
+    constexpr int NV = Val::NV;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long nunit = (long)nchunk * nxt;
+    for (long u = (long)blockIdx.x * (SPEC_THREADS / 64) + wv; u < nunit; u += (long)gridDim.x * (SPEC_THREADS / 64)) {
+        const RingChunk ch = chunks[u / nxt];
+        const int i = (int)(u % nxt) * 64 + lane;
+        if (i >= nx) continue;
+        T acc[NV];
+#pragma unroll
+        for (int q = 0; q < NV; ++q) acc[q] = (T)0;
+#pragma unroll 4
+        for (int t = 0; t < ch.count; ++t) {
+            const int r = rows[ch.start + t];
+            const int j = r % ny, k = r / ny;
+            const long rm = (long)(j ? ny - j : 0) + (long)ny * (k ? nz - k : 0);
+            T v[NV];
+            val((long)r, i, rm, i, nx, 0.0, v);
+#pragma unroll
+            for (int q = 0; q < NV; ++q) acc[q] += v[q];
+        }
+#pragma unroll
+        for (int q = 0; q < NV; ++q) slots[(((long)q * maxc + ch.c) * nx + i) * nrings + ch.s] = acc[q];
+    }
+}
+
+int plane_ring_of(int ma, double ra, int mb, double rb)
+{
+    const double a = (double)ma * ra, b = (double)mb * rb;
+    const double kap2 = a * a + b * b;
+    return (int)(std::sqrt(kap2) + 0.5);
+}
+
+int ctz_long(long v) { int l = 0; while (v > 1 && (v & 1) == 0) { v >>= 1; ++l; } return l; }
+
+struct PlanePlan {
+    SpecPlan fp;                    // what spec_pack and spec_fft read: nx, N, log2 extents and twiddles of a and b, the tiles
+    int dir, a, b, n[3], nplanes, nrings;
+    long M;
+    PlaneShape sh;                  // dir 1, 2
+    DevBuf<int> rows;               // dir 0: the rows j + n_y k sorted by ring, stable in row order
+    DevBuf<RingChunk> chunks;
+    int nchunk = 0, nxt = 0;
+    int nslot = 0;                  // slots per (plane, ring): G (dir 1, 2) or the most chunks of a ring (dir 0)
+    std::vector<long> count;
+};
+
+void plane_axes(int dir, int& a, int& b) { a = dir == 0 ? 1 : 0; b = dir == 2 ? 1 : 2; }
+
+PlanePlan plane_plan(const Geometry& g, int dir, int nrings)
+{
+    PlanePlan p;
+    auto& ctx = Context::get();
+    p.dir = dir; plane_axes(dir, p.a, p.b); p.nrings = nrings;
+    for (int d = 0; d < 3; ++d) p.n[d] = g.domain.len(d);
+    const int a = p.a, b = p.b, na = p.n[a], nb = p.n[b];
+    p.nplanes = p.n[dir]; p.M = (long)na * nb;
+    IAMRX_ASSERT((long)p.nplanes * nrings < (1L << 31));
+    const double La = g.probhi[a] - g.problo[a], Lb = g.probhi[b] - g.problo[b], L2 = std::max(La, Lb);
+    const double ra = L2 / La, rb = L2 / Lb;
+    // the transform passes: the tiles of spec_plan, cut down to what divides a normal extent that is no power of two
+    SpecPlan& f = p.fp;
+    f.sh.nx = p.n[0]; f.sh.ny = p.n[1]; f.sh.nz = p.n[2]; f.sh.nbins = nrings;
+    f.N = (long)p.n[0] * p.n[1] * p.n[2];
+    f.ln[0] = f.ln[1] = f.ln[2] = 0;
+    f.ln[a] = ilog2(na); f.ln[b] = ilog2(nb);
+    const int elems = std::clamp((int)tune("SPECTRUM_TILE_ELEMS", 2048), 256, 4096);
+    const int le = ilog2(elems), lx = ctz_long(p.n[0]);
+    f.pair = tune("SPECTRUM_PAIR_STAGES", 1) != 0;
+    f.xp = std::min(std::max(le - 1 - f.ln[0], 0), ctz_long((long)p.n[1] * p.n[2]));
+    f.ytw = std::min(std::max(le - f.ln[1], 2), lx);
+    f.ztw = std::min(std::max(le - f.ln[2], 2), lx);
+    for (int d : {a, b}) {
+        const std::vector<double2> w = spec_twiddles(1 << f.ln[d]);
+        f.tw[d] = DevBuf<double2>(w.size());
+        ctx.upload_async(f.tw[d], w.data(), w.size() * sizeof(double2));
+    }
+    // the ring of every mode of a plane, index i_a + n_a i_b, and the modes per ring
+    std::vector<int> ring((size_t)p.M);
+    p.count.assign(nrings, 0);
+    for (int ib = 0; ib < nb; ++ib)
+        for (int ia = 0; ia < na; ++ia) {
+            const int s = std::min(plane_ring_of(ia < na / 2 ? ia : ia - na, ra, ib < nb / 2 ? ib : ib - nb, rb), nrings - 1);
+            ring[(size_t)ia + (size_t)na * ib] = s;
+            ++p.count[s];
+        }
+    if (dir != 0) {
+        PlaneShape& s = p.sh;
+        s.nx = na; s.nt = nb; s.nplanes = p.nplanes; s.nrings = nrings;
+        s.lcw = std::min(6, f.ln[0] - 1);
+        s.ps = dir == 2 ? p.n[1] : 1; s.ts = dir == 2 ? 1 : p.n[1];
+        s.rx = ra; s.rt = rb;
+        s.npg = std::min(p.nplanes, SPEC_MAXWG);
+        s.G = std::min(std::max(1, SPEC_MAXWG / s.npg), std::max(1, nb / 4));
+        s.rows_per_wg = (nb + s.G - 1) / s.G;
+        s.G = (nb + s.rows_per_wg - 1) / s.rows_per_wg;
+        p.nslot = s.G;
+        return p;
+    }
+    // dir 0: rows sorted by ring (a counting sort keeps the row order inside a ring), rings cut into chunks of ch rows -- 32, or fewer
+    // while the image would give fewer than 2048 wavefronts something to do (a function of the shape alone)
+    p.nxt = (p.n[0] + 63) / 64;
+    int ch = 32;
+    while (ch > 8 && (p.M / ch) * p.nxt < 2048) ch >>= 1;
+    std::vector<long> off(nrings + 1, 0);
+    for (int s = 0; s < nrings; ++s) off[s + 1] = off[s] + p.count[s];
+    std::vector<int> rows((size_t)p.M);
+    std::vector<long> fill(off.begin(), off.end() - 1);
+    for (long r = 0; r < p.M; ++r) rows[(size_t)fill[ring[(size_t)r]]++] = (int)r;
+    std::vector<RingChunk> chunks;
+    for (int s = 0; s < nrings; ++s) {
+        const int nc = (int)((p.count[s] + ch - 1) / ch);
+        for (int c = 0; c < nc; ++c) chunks.push_back(RingChunk{s, c, (int)(off[s] + (long)c * ch), (int)std::min<long>(ch, p.count[s] - (long)c * ch)});
+        p.nslot = std::max(p.nslot, nc);
+    }
+    p.nchunk = (int)chunks.size();
+    p.rows = DevBuf<int>(rows.size());
+    ctx.upload_async(p.rows, rows.data(), rows.size() * sizeof(int));
+    p.chunks = DevBuf<RingChunk>(chunks.size());
+    ctx.upload_async(p.chunks, chunks.data(), chunks.size() * sizeof(RingChunk));
+    return p;
+}
+
+// the two passes along a and b over the whole image; t (or null): a mark after each
+void plane_forward(const PlanePlan& p, double2* W, PassTimer* t = nullptr)
+{
+    const long nx = p.n[0], ny = p.n[1], nz = p.n[2];
+    for (int d : {p.a, p.b}) {
+        if (d == 0) spec_fft(p.fp, 0, W, 1, 0, ny * nz);
+        else if (d == 1) spec_fft(p.fp, 1, W, nx, nx * ny, nz);
+        else spec_fft(p.fp, 2, W, nx * ny, nx, ny);
+        PassTimer::mark(t);
+    }
+}
+
+size_t plane_slot_count(const PlanePlan& p, int nv) { return (size_t)nv * p.nslot * p.nplanes * p.nrings; }
+
+// the ring sums of the NV values of val: out[(v * nplanes + p) * nrings + s] = scale * sum.  dir 0: slots zeroed once by the caller
+template <class Val>
+void plane_bin(const PlanePlan& p, const Val& val, typename Val::T* slots, double scale, typename Val::T* out)
+{
+    using T = typename Val::T;
+    auto& ctx = Context::get();
+    if (p.dir == 0) {
+        const long units = (long)p.nchunk * p.nxt;
+        const unsigned grid = (unsigned)std::min<long>((units + SPEC_THREADS / 64 - 1) / (SPEC_THREADS / 64), SPEC_MAXWG);
+        hipLaunchKernelGGL((k_plane_ring_x<Val>), dim3(grid), dim3(SPEC_THREADS), 0, ctx.stream, val, (const int*)p.rows.get(), (const RingChunk*)p.chunks.get(), p.nchunk,
+                           p.n[0], p.nxt, p.n[1], p.n[2], p.nrings, p.nslot, slots);
+    } else {
+        const size_t per_wave = (size_t)Val::NV * p.nrings * sizeof(T);
+        int nw = SPEC_THREADS / 64;
+        while (nw > 1 && nw * per_wave > 65536) nw >>= 1;
+        hipLaunchKernelGGL((k_plane_ring<Val>), dim3((unsigned)(p.sh.npg * p.sh.G)), dim3(64 * nw), nw * per_wave, ctx.stream, val, p.sh, slots);
+    }
+    spec_finish_slots(Val::NV, p.nslot, p.nplanes * p.nrings, slots, scale, out);
+}
+
+template <class MakeVal>
+void plane_ring_sums(const Geometry& g, const PlanePlan& p, int n, const std::function<SpecPair(int)>& src, const MakeVal& val, double* out)
+{
+    using Val = decltype(val((const double2*)nullptr));
+    auto& ctx = Context::get();
+    const size_t per = (size_t)Val::NV * p.nplanes * p.nrings;
+    DevBuf<double> d_out(per * n);
+    DevBuf<double> slots(plane_slot_count(p, Val::NV));
+    if (p.dir == 0) IAMRX_HIP_CHECK(hipMemsetAsync(slots.get(), 0, plane_slot_count(p, Val::NV) * sizeof(double), ctx.stream));
+    DevBuf<double2> W((size_t)p.fp.N);
+    const double invM = 1.0 / (double)p.M;
+    for (int q = 0; q < n; ++q) {
+        const SpecPair f = src(q);
+        if (f.b) spec_pack_pair(p.fp, g, *f.a, f.acomp, *f.b, f.bcomp, W);
+        else spec_pack(p.fp, g, *f.a, f.acomp, W);
+        plane_forward(p, W);
+        plane_bin(p, val(W), slots.get(), invM * invM, d_out + per * q);
+    }
+    const double* h = ctx.read_back(d_out, per * n);
+    std::copy(h, h + per * n, out);
+}
+
+}  // namespace
+
+PlaneSpecDims plane_spectrum_check(const Geometry& g, int dir, int n, const SpecPair* f)
+{
+    static const char* axis = "xyz";
+    if (dir < 0 || dir > 2) throw Error("plane_spectrum: dir = " + std::to_string(dir) + " outside 0 .. 2");
+    for (int q = 0; q < n; ++q)
+        for (const MultiFab* S : {f[q].a, f[q].b})
+            if (S && !S->type.cell()) throw Error("plane_spectrum: the array is not cell-centred");
+    if (n < 1) throw Error("plane_spectrum: component range is empty");
+    for (int q = 0; q < n; ++q) {
+        if (f[q].acomp < 0 || f[q].acomp >= f[q].a->ncomp)
+            throw Error("plane_spectrum: component " + std::to_string(f[q].acomp) + " outside 0 .. " + std::to_string(f[q].a->ncomp - 1));
+        if (f[q].b && (f[q].bcomp < 0 || f[q].bcomp >= f[q].b->ncomp))
+            throw Error("plane_spectrum: component " + std::to_string(f[q].bcomp) + " outside 0 .. " + std::to_string(f[q].b->ncomp - 1) + " of the second array");
+    }
+    int a, b;
+    plane_axes(dir, a, b);
+    for (int d : {a, b})
+        if (!g.periodic[d])
+            throw Error(std::string("plane_spectrum: direction ") + axis[d] + " is not periodic (the two directions in the planes normal to " + axis[dir] + " must be)");
+    for (int d : {a, b}) {
+        const int nd = g.domain.len(d);
+        if (nd < 4 || nd > 1024 || (nd & (nd - 1)) != 0)
+            throw Error(std::string("plane_spectrum: extent n_") + axis[d] + " = " + std::to_string(nd) + " is not a power of two in 4 .. 1024");
+    }
+    for (int d = 0; d < 3; ++d)
+        if (!(g.probhi[d] > g.problo[d])) throw Error(std::string("plane_spectrum: the domain has no length along ") + axis[d]);
+    const double La = g.probhi[a] - g.problo[a], Lb = g.probhi[b] - g.problo[b], L2 = std::max(La, Lb);
+    const double ca = (double)(-(g.domain.len(a) / 2)) * (L2 / La), cb = (double)(-(g.domain.len(b) / 2)) * (L2 / Lb);
+    const double kap2 = ca * ca + cb * cb;
+    const double kap = std::sqrt(kap2) + 0.5;
+    if (!(kap < (double)SPEC_MAXBINS))
+        throw Error("plane_spectrum: more than " + std::to_string(SPEC_MAXBINS) + " rings (the side lengths of the plane differ too much for its extents)");
+    for (int q = 0; q < n; ++q)
+        for (const MultiFab* S : {f[q].a, f[q].b})
+            if (S) dense_check_cover("plane_spectrum", g, *S->layout);
+    return PlaneSpecDims{g.domain.len(dir), (int)kap + 1};
+}
+
+void plane_spectrum_compute(const Geometry& g, int n, const SpecPair* f, int dir, PlaneSpecDims dims, double* out, long* count)
+{
+    IAMRX_ASSERT(n >= 1 && f && out);
+    const PlanePlan p = plane_plan(g, dir, dims.nrings);
+    IAMRX_ASSERT(p.nplanes == dims.nplanes);
+    if (f[0].b) {
+        IAMRX_ASSERT(n == 1);
+        plane_ring_sums(g, p, 1, [&](int) { return f[0]; }, [](const double2* W) { return PlaneCoVal{CoVal{W, W, 0.0}}; }, out);
+    } else
+        plane_ring_sums(g, p, n, [&](int q) { return f[q]; }, [](const double2* W) { return PowerVal{W}; }, out);
+    if (count) std::copy(p.count.begin(), p.count.end(), count);
+}
+
+void plane_spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int dir, int reps, float* ms)
+{
+    const SpecPair f{&S, comp, nullptr, 0};
+    const PlaneSpecDims dims = plane_spectrum_check(g, dir, 1, &f);
+    IAMRX_ASSERT(reps >= 1 && ms);
+    auto& ctx = Context::get();
+    const PlanePlan p = plane_plan(g, dir, dims.nrings);
+    DevBuf<double2> W((size_t)p.fp.N);
+    DevBuf<double> slots(plane_slot_count(p, 1)), d_out((size_t)p.nplanes * p.nrings);
+    if (dir == 0) IAMRX_HIP_CHECK(hipMemsetAsync(slots.get(), 0, plane_slot_count(p, 1) * sizeof(double), ctx.stream));
+    PassTimer t(PLANE_SPECTRUM_BENCH_NP + 1);
+    const double invM = 1.0 / (double)p.M;
+    for (int r = 0; r < reps; ++r) {
+        t.mark();
+        spec_pack(p.fp, g, S, comp, W);
+        t.mark();
+        plane_forward(p, W, &t);
+        plane_bin(p, PowerVal{W}, slots.get(), invM * invM, d_out.get());
+        t.mark();
+        t.finish(ms + PLANE_SPECTRUM_BENCH_NP * r);
     }
     ctx.sync();
 }

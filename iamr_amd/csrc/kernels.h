@@ -109,6 +109,23 @@ void spectrum_k2_compute(const Geometry& g, const MultiFab& S, int nq, const int
 // measurement aid (tools/bench_budget.py): the five passes of one packed pair -- pack, x, y, z, the shell sums with the mirror read --
 // timed as spectrum_bench times its five
 void cospectrum_bench(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int reps, float* ms);
+// ---- plane spectra: ring-summed 2-D spectra along a normal axis (include/iamrx.h: iamrx_mf_plane_spectrum; k_spectrum.hip) ----
+// the columns the level and hierarchy entries return: P_u, P_v, P_w, P_rho, P_c (c: the first tracer)
+constexpr int PLANE_SPECTRUM_NQ = 5;
+constexpr int PLANE_SPECTRUM_BENCH_NP = 4;          // pack, the two transform passes, the ring sums
+struct PlaneSpecDims { int nplanes, nrings; };
+// the checks of the plane spectra of n fields (or packed pairs: b set), by name and in the order of include/iamrx.h -- dir, cell-centred,
+// components, the two transformed directions periodic, their extents, the lengths, the rings, the cover -- before anything is allocated
+// -> the planes along dir and the rings.  The normal direction may have any boundary type and any extent.
+PlaneSpecDims plane_spectrum_check(const Geometry& g, int dir, int n, const SpecPair* f);
+// plain fields (every b null): out[(q * nplanes + p) * nrings + s] = sum over the modes of ring s of |F_p|^2 of field q; one packed pair
+// (n = 1, b set): out[(v * nplanes + p) * nrings + s], v = 0, 1, 2: C_ab, P_a, P_b.  count[s] (or null): the modes of ring s, the same in
+// every plane.  dims = plane_spectrum_check(g, dir, n, f).  Fixed-order sums without floating-point atomics: the same bits on a repeated
+// call, for any box layout and any rank count.  Collective on several ranks: the gather of spectrum_compute, whatever SPECTRUM_DIST says.
+void plane_spectrum_compute(const Geometry& g, int n, const SpecPair* f, int dir, PlaneSpecDims dims, double* out, long* count);
+// measurement aid (tools/bench_plane_spectrum.py): ms[PLANE_SPECTRUM_BENCH_NP * r + p] of pack, the first and the second transform pass
+// and the ring sums (with their slot sum) of one component
+void plane_spectrum_bench(const Geometry& g, const MultiFab& S, int comp, int dir, int reps, float* ms);
 // ---- the slab-decomposed transform of several ranks (SPECTRUM_DIST = 1; include/iamrx.h, k_spectrum.hip) ----
 // a box cut by a z-slab: kind 0 the piece stays on the rank, 1 sent to peer, 2 received from peer; off: doubles, in the buffer of that
 // peer (-1 for kind 0)

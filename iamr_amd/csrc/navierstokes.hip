@@ -302,6 +302,26 @@ void NavierStokes::spectrum(int cap, double* out, long* count, int* nbins)
     spectrum_of(g, S[inew], SPECTRUM_NQ, comps, cap, out, count, nbins);
 }
 
+void plane_spectrum_of(const Geometry& g, int n, const SpecPair* f, int dir, int pcap, int rcap, double* out, long* count, int* nplanes, int* nrings)
+{
+    const PlaneSpecDims d = plane_spectrum_check(g, dir, n, f);
+    if (nplanes) *nplanes = d.nplanes;
+    if (nrings) *nrings = d.nrings;
+    if (pcap < d.nplanes || rcap < d.nrings)
+        throw Error("plane_spectrum: " + std::to_string(d.nplanes) + " planes of " + std::to_string(d.nrings) + " rings, the caller's arrays hold " +
+                    std::to_string(pcap) + " of " + std::to_string(rcap));
+    if (!out) throw Error("plane_spectrum: null output array");
+    plane_spectrum_compute(g, n, f, dir, d, out, count);
+}
+
+void NavierStokes::plane_spectrum(int dir, int pcap, int rcap, double* out, long* count, int* nplanes, int* nrings)
+{
+    const int comps[PLANE_SPECTRUM_NQ] = {Xvel, Yvel, Zvel, Density, Tracer};
+    SpecPair f[PLANE_SPECTRUM_NQ];
+    for (int q = 0; q < PLANE_SPECTRUM_NQ; ++q) f[q] = SpecPair{&S[inew], comps[q], nullptr, 0};
+    plane_spectrum_of(g, PLANE_SPECTRUM_NQ, f, dir, pcap, rcap, out, count, nplanes, nrings);
+}
+
 void cospectrum_of(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int cap, double* out, long* count, int* nbins)
 {
     const int n = spectrum_cap(g, cap, out, nbins);

@@ -203,6 +203,8 @@ void spectrum_of(const Geometry& g, const MultiFab& S, int nq, const int* comps,
 void cospectrum_of(const Geometry& g, const MultiFab& A, int acomp, const MultiFab& B, int bcomp, int cap, double* out, long* count, int* nbins);
 // ... and in front of spectrum_k2_compute
 void spectrum_k2_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int cap, double* out, int* nbins);
+// the common part of the plane-spectrum entries: plane_spectrum_check, *nplanes and *nrings, the capacities, plane_spectrum_compute
+void plane_spectrum_of(const Geometry& g, int n, const SpecPair* f, int dir, int pcap, int rcap, double* out, long* count, int* nplanes, int* nrings);
 // the common part of the three structure-function entries: pmax, the separations (strfn_resolve_rmax) and the capacity are checked by
 // name, count[d * rcap + r] (or null) is filled from strfn_count, then strfn_compute (kernels.h)
 void strfn_of(const Geometry& g, const MultiFab& S, int nq, const int* comps, int pmax, const int rmax[3], int rcap, double* out, long long* count,
@@ -341,6 +343,10 @@ public:
     // columns, count[s] (or null) the modes of shell s.  *nbins is set before the capacity is checked.  Collective; every rank receives the
     // result.
     void spectrum(int cap, double* out, long* count, int* nbins);
+    // ring-summed plane spectra of u, v, w, rho and the first tracer of the new-time state along the normal axis dir (k_spectrum.hip):
+    // out[(q * nplanes + p) * nrings + s], PLANE_SPECTRUM_NQ columns; only the two directions in the plane must be periodic.  *nplanes and
+    // *nrings are set before the capacities are checked.  Collective; every rank receives the result.
+    void plane_spectrum(int dir, int pcap, int rcap, double* out, long* count, int* nplanes, int* nrings);
     // spectral kinetic-energy budget of the new-time state (include/iamrx.h): out[q * nbins + s], BUDGET_NQ columns E, T, D, F.  One
     // FillPatch of the velocity (one ghost layer), the skew-symmetric nonlinear term (k_convect.hip) and, with the turbulent forcing on, its
     // acceleration at cur_time() into arrays that return to the arena, then one packed transform per pair (u_i, N_i) and (u_i, f_i).

@@ -26,6 +26,10 @@ keys this library implements onto `ns_params`, the geometry and the box layout:
   powers of two in 4 .. 1024; ns.spectral_distributed (0 | 1; 0): 1 sets the library's registry key SPECTRUM_DIST, so that the spectra and
   the budget of a run on several ranks take the slab-decomposed transform instead of the gather; carried as "spectral_distributed",
   refused in a two-dimensional run as the spectra are,
+  ns.plane_spectrum_interval (0: off) / ns.plane_spectrum_dir (2) / ns.plane_spectrum_file ("pspec"): this library's own keys for the
+  ring-summed plane spectra of level 0 along a normal axis (iamr_amd/planespec.py), carried under "plane_spectrum"; an interval > 0 needs a
+  three-dimensional domain whose two directions in the plane are periodic with extents that are powers of two in 4 .. 1024 (the normal
+  direction may have walls and any extent),
   ns.sgs_interval (-1: off) / ns.sgs_filter (sharp | gaussian | box; gaussian) / ns.sgs_kc (1 .. 8 cut-offs, required with an interval > 0) /
   ns.sgs_file ("sgs"): this library's own keys for the a-priori LES analysis of level 0 (iamr_amd/sgs.py), carried under "sgs", with the
   preconditions of the spectra,
@@ -570,6 +574,18 @@ class Inputs:
                 if not extent_ok(n[d]):
                     raise ValueError(f"inputs: ns.spectrum_interval > 0 needs extents that are powers of two in 4 .. 1024, amr.n_cell has "
                                      f"n_{'xyz'[d]} = {n[d]}")
+        # plane spectra (this library's own keys; planespec.py): every plane_spectrum_interval-th level-0 step and once for the initial
+        # data the ring-summed 2-D spectra of level 0 in the planes normal to plane_spectrum_dir; only the two directions in the plane
+        # must be periodic with power-of-two extents, the normal one may have walls
+        plane_spectrum = dict(interval=self.integer("ns.plane_spectrum_interval", 0), dir=self.integer("ns.plane_spectrum_dir", 2),
+                              file=self.string("ns.plane_spectrum_file", "pspec"))
+        if plane_spectrum["interval"] > 0:
+            from .planespec import refusal
+            why = refusal(n, per, plane_spectrum["dir"], 2 if slab else 3)
+            if why is not None:
+                if slab:
+                    raise NotImplementedError(f"inputs: ns.plane_spectrum_interval > 0 in {why} (the slab's thickness direction has two cells)")
+                raise ValueError(f"inputs: ns.plane_spectrum_interval > 0 with ns.plane_spectrum_dir = {plane_spectrum['dir']}: plane_spectrum: {why}")
         # spectral kinetic-energy budget (this library's own keys; budget.py): as the spectra, with the same preconditions
         budget = dict(interval=self.integer("ns.budget_interval", -1), file=self.string("ns.budget_file", "sbud"))
         if budget["interval"] > 0:
@@ -673,7 +689,7 @@ class Inputs:
                     if v in VELGRAD_NAMES and v not in VELGRAD_NAMES_2D:
                         raise NotImplementedError(f"inputs: {key} names '{v}' in a two-dimensional run: of the velocity-gradient fields a slab "
                                                   f"knows {' '.join(VELGRAD_NAMES_2D)}")
-        out = dict(profile=profile, spectrum=spectrum, budget=budget, spectral_distributed=spectral_distributed, sgs=sgs, strfn=strfn, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
+        out = dict(profile=profile, spectrum=spectrum, plane_spectrum=plane_spectrum, budget=budget, spectral_distributed=spectral_distributed, sgs=sgs, strfn=strfn, pdf=pdf, integrate=integ, n=n, prob_lo=prob_lo, prob_hi=prob_hi, periodic=per, max_grid_size=mgs, params=p, prob=prob, slab=slab,
                    max_step=self.integer("max_step", -1), stop_time=self.real("stop_time", -1.0),
                    plot_int=self.integer("amr.plot_int", -1), plot_file=self.string("amr.plot_file", "plt"), plot_vars=self.name_list("amr.plot_vars", "ALL"),
                    derive_plot_vars=dpv, fine_boxes=fine_boxes, regrid=regrid, max_level=max_level,

@@ -508,6 +508,21 @@ def mf_spectrum(geom, mf, comp=0, ncomp=1):
     return _s.mf_spectrum(geom, mf, comp, ncomp)
 
 
+def mf_plane_spectrum(geom, mf, dir, comp=0, ncomp=1):
+    """ring-summed plane spectra of components comp .. comp + ncomp - 1 of a cell-centred MultiFab along the normal axis dir; only the
+    two directions in the plane must be periodic (include/iamrx.h: iamrx_mf_plane_spectrum) -> (P (ncomp, nplanes, nrings), count
+    (nrings,) int64)"""
+    from . import planespec as _p
+    return _p.mf_plane_spectrum(geom, mf, dir, comp, ncomp)
+
+
+def mf_plane_cospectrum(geom, a, b, dir, acomp=0, bcomp=0):
+    """plane co-spectrum of component acomp of a and bcomp of b along the normal axis dir (include/iamrx.h: iamrx_mf_plane_cospectrum;
+    one packed transform) -> (C_ab, P_a, P_b, each (nplanes, nrings), count (nrings,))"""
+    from . import planespec as _p
+    return _p.mf_plane_cospectrum(geom, a, b, dir, acomp, bcomp)
+
+
 def host_spectrum_slab_plan(geom, boxes, owners, rank, nranks):
     """host only: eligibility and the scatter plan of the slab-decomposed transform (include/iamrx.h: iamrx_host_spectrum_slab_plan)
     -> (eligible, reason, rows (n, 10) int64: spectrum.SLAB_ROW)"""

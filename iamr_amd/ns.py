@@ -379,6 +379,29 @@ class NavierStokes:
         n, L = _s._geom_nL(self.geom)
         return dict(k=np.arange(len(Cab)) * (2.0 * math.pi / max(L)), count=cnt, C=Cab, Pa=Pa, Pb=Pb, n=n, L=L)
 
+    def plane_spectrum(self, dir):
+        """ring-summed 2-D spectra of the new-time state in the planes normal to dir (0, 1, 2), E(k_h; z); only the two directions in the
+        plane must be periodic (include/iamrx.h: iamrx_ns_plane_spectrum) -> dict with "k" (s 2 pi / L2), "count" (modes per ring),
+        "coord" (plane centres), "dir", "n", "L" and the arrays (nplanes, nrings) "E" = (P_u + P_v + P_w) / 2, "Euu", "Evv", "Eww", "Err"
+        (density), "Ecc" (the first tracer); the same bits on every rank.  Collective."""
+        from . import planespec as _p
+        return _p.level_plane_spectrum(lib().iamrx_ns_plane_spectrum, self.h, self.geom, dir)
+
+    def plane_cospectrum(self, a, b, dir):
+        """plane co-spectrum of two named fields of this level, any names cospectrum accepts, in the planes normal to dir (include/iamrx.h:
+        iamrx_mf_plane_cospectrum) -> dict with "k", "count", "coord", "dir", "n", "L" and the arrays (nplanes, nrings) "C" = C_ab, "Pa",
+        "Pb"; the same bits on every rank.  Collective."""
+        from . import planespec as _p
+        from . import spectrum as _s
+        import math
+        import numpy as np
+        f = self.derive_fields([a, b])
+        Cab, Pa, Pb, cnt = _p.mf_plane_cospectrum(self.geom, f, f, dir, 0, 1)
+        n, L = _s._geom_nL(self.geom)
+        ia, ib = _p.axes_of(dir)
+        return dict(k=np.arange(Cab.shape[1]) * (2.0 * math.pi / max(L[ia], L[ib])), count=cnt, coord=_p.coord_of(self.geom, int(dir), Cab.shape[0]),
+                    dir=int(dir), C=Cab, Pa=Pa, Pb=Pb, n=n, L=L)
+
     def filtered(self, names, kind, kc):
         """the named fields of this level -- any names derive_fields knows -- low-pass filtered in mode space into a new MultiFab on the
         level's layout, component q = names[q] (include/iamrx.h: iamrx_mf_filter; spectral.py).  kind: "sharp", "gaussian", "box" (or

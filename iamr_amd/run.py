@@ -192,6 +192,21 @@ def take_spectrum(run, pr, step, rank, say):
         say("SPECTRUM:", path)
 
 
+def take_plane_spectrum(run, pr, step, rank, say):
+    """ns.plane_spectrum_interval > 0: every that many level-0 steps (and for the initial data, step 0) the ring-summed plane spectra of the
+    level, or of level 0 of the hierarchy (planespec.py), along ns.plane_spectrum_dir go to <ns.plane_spectrum_file><step:05d>.
+    Collective: every rank takes part, rank 0 writes.  Off: nothing is launched, allocated or printed."""
+    ps = pr.get("plane_spectrum") or {}
+    if ps.get("interval", 0) <= 0 or step % ps["interval"] != 0:
+        return
+    from .planespec import write_plane_spectrum
+    s = run.plane_spectrum(ps["dir"])
+    if rank == 0:
+        path = f"{ps['file']}{step:05d}"
+        write_plane_spectrum(path, s, step, run.time)
+        say("PLANE SPECTRUM:", path)
+
+
 def take_budget(run, pr, step, rank, say):
     """ns.budget_interval > 0: every that many level-0 steps (and for the initial data, step 0) the spectral kinetic-energy budget of the
     level, or of level 0 of the hierarchy (budget.py), goes to <ns.budget_file><step:05d>.  Collective: every rank takes part, rank 0
@@ -427,7 +442,7 @@ def drive(pr, inp, lib, N, hierarchy, rank=0, world=1, observe=None):
     """a run from amr.restart or from its initial data to max_step / stop_time: a single level, or (hierarchy) an Amr hierarchy.  world > 1:
     the boxes of every level are spread over the ranks (level 0 by Layout.decompose, fixed refined grids round-robin, regridded levels
     by the library's knapsack, restarted levels as checkpoint.restart says) and every rank executes the same sequence of collective
-    operations: step, enforce_plane, sums, time average, profile, spectrum, spectral budget, a-priori LES statistics, structure functions, pdf, integrals, observe, plotfile, checkpoint.  observe: see main"""
+    operations: step, enforce_plane, sums, time average, profile, spectrum, plane spectrum, spectral budget, a-priori LES statistics, structure functions, pdf, integrals, observe, plotfile, checkpoint.  observe: see main"""
     from . import checkpoint
     say = print if rank == 0 else (lambda *a, **k: None)
     plot_int, plot_root = pr.get("plot_int", -1), pr.get("plot_file", "plt")
@@ -439,6 +454,7 @@ def drive(pr, inp, lib, N, hierarchy, rank=0, world=1, observe=None):
         take_time_average(run, pr, step, dt)
         take_profile(run, pr, step, rank, say)
         take_spectrum(run, pr, step, rank, say)
+        take_plane_spectrum(run, pr, step, rank, say)
         take_budget(run, pr, step, rank, say)
         take_sgs(run, pr, step, rank, say)
         take_strfn(run, pr, step, rank, say)

@@ -642,6 +642,50 @@ int iamrx_ns_spectrum(iamrx_ns ns, int nbins_cap, double* out, long* count, int*
 /* measurement aid (tools/bench_spectrum.py): reps times the five passes of one component (pack, x, y, z transform, shell sums) with an
  * event between them; ms[5 * r + p] = milliseconds of pass p in repeat r.  Nothing is read back. */
 int iamrx_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int reps, float* ms);
+/* Plane spectra: ring-summed 2-D spectra along a wall-normal axis, E(k_h; z) (this library's own diagnostic; k_spectrum.hip).  For a
+ * cell-centred field f on n = (n_x, n_y, n_z) cells:
+ *   axes         dir in {0, 1, 2} is the normal axis.  It is not transformed and may have any boundary type and any extent >= 1.  a < b
+ *                are the other two axes; both must be periodic with extents that are powers of two in 4 .. 1024.  M = n_a n_b,
+ *                L2 = max(L_a, L_b) (the normal axis does not enter), r_a = L2 / L_a, r_b = L2 / L_b;
+ *   transform    for plane p, the cell index along dir counted from the domain's low end:
+ *                F_p(m_a, m_b) = (1/M) sum f exp(-2 pi i (m_a x_a / n_a + m_b x_b / n_b)), signed mode numbers as for iamrx_mf_spectrum;
+ *   ring index   s = (int)(kappa + 0.5), kappa = sqrt((m_a r_a)^2 + (m_b r_b)^2) (the squares added left to right in double, no FMA);
+ *                ring s stands for the horizontal wavenumber k_s = s 2 pi / L2;
+ *   rings        *nrings = (int)(kappa(-n_a/2, -n_b/2) + 0.5) + 1, at most 2048;
+ *   power        P(p, s) = sum over the modes of ring s of |F_p|^2, so that sum_s P(p, s) = the plane mean of f^2 (Parseval per plane)
+ *                and P(p, 0) = the plane mean squared;
+ *   count        count(s) = number of modes of ring s: the same for every plane, formed from integers, sum_s count(s) = M;
+ *   co-spectrum  C_ab(p, s) = sum over ring s of Re(F_a conj F_b) of two real fields, with P_a and P_b, from ONE transform of Z = a + i b
+ *                read with its mirror mode (-m_a, -m_b), which lies in the same plane; sum_s C_ab(p, s) = the plane mean of a b.
+ * iamrx_plane_spectrum_nq: the columns of the level and hierarchy entries, 5: P_u, P_v, P_w, P_rho, P_c (c: the first tracer), new-time
+ * state; E = (P_u + P_v + P_w) / 2.  No density weighting.
+ * iamrx_mf_plane_spectrum: out[(q * nplanes + p) * nrings + s] = P(p, s) of component comp + q (q < ncomp) of a caller-owned cell-centred
+ * array whose boxes tile the domain of g; ghost cells are never read (also not those beyond a wall); count[nrings] may be NULL.
+ * iamrx_mf_plane_cospectrum: out[(v * nplanes + p) * nrings + s], v = 0, 1, 2: C_ab, then P_a, then P_b, of component acomp of a and
+ * bcomp of b, which may be the same array and may have different box layouts.
+ * iamrx_ns_plane_spectrum: the five columns from the level's new-time state.  iamrx_amr_plane_spectrum (below): of LEVEL 0.
+ * All of them: the dense image, the transform passes (two of the three), the twiddles and the slot sum of iamrx_mf_spectrum; the ring
+ * sums are kernels of their own: rows along x that lie in one plane (dir 1, 2) go through a segmented wave scan into LDS bins per
+ * plane; for dir 0, where every element of a row lies in another plane, the rows are sorted by ring on the host and lanes along x add
+ * them in table order.  No floating-point atomics, a fixed summation order that depends on the shape alone: the same call gives the same
+ * bits, whatever the box layout and the number of ranks.  Collective on several ranks: the gather of iamrx_mf_spectrum, every rank
+ * receives the same bits.  SPECTRUM_DIST = 1 leaves these calls on the gather, as it leaves the filters (a slab form is not built).
+ * Errors, by name and in this order, before anything is allocated: dir outside 0 .. 2; an array that is not cell-centred; a component
+ * out of range; a transformed direction that is not periodic (the message names the axis); a transformed extent that is not a power of
+ * two in 4 .. 1024; no length along an axis; more than 2048 rings; boxes that do not tile the domain; nplanes_cap < *nplanes or
+ * nrings_cap < *nrings (both are set all the same).  The normal direction is never checked for periodicity or for a power of two.
+ * Not built: a slab-decomposed form, levels above 0, time averaging, density weighting, a per-plane budget, a chosen subset of planes,
+ * two-dimensional runs. */
+int iamrx_plane_spectrum_nq(void);
+int iamrx_mf_plane_spectrum(const iamrx_geom* g, iamrx_mf mf, int comp, int ncomp, int dir, int nplanes_cap, int nrings_cap, double* out, long* count,
+                            int* nplanes, int* nrings);
+int iamrx_mf_plane_cospectrum(const iamrx_geom* g, iamrx_mf a, int acomp, iamrx_mf b, int bcomp, int dir, int nplanes_cap, int nrings_cap, double* out,
+                              long* count, int* nplanes, int* nrings);
+int iamrx_ns_plane_spectrum(iamrx_ns ns, int dir, int nplanes_cap, int nrings_cap, double* out, long* count, int* nplanes, int* nrings);
+/* measurement aid (tools/bench_plane_spectrum.py): reps times the four passes of one component (pack, the first and the second transform
+ * pass, the ring sums with their slot sum) with an event between them; ms[IAMRX_PLANE_SPECTRUM_BENCH_NP * r + p].  Nothing is read back. */
+#define IAMRX_PLANE_SPECTRUM_BENCH_NP 4
+int iamrx_plane_spectrum_bench(const iamrx_geom* g, iamrx_mf mf, int comp, int dir, int reps, float* ms);
 /* The slab-decomposed transform of the shell-summed diagnostics on several ranks (registry key SPECTRUM_DIST = 1, default 0: the gather
  * above, byte for byte).  With the key at 1, iamrx_mf_spectrum, iamrx_mf_spectrum_k2, iamrx_mf_cospectrum and whatever calls them
  * (the level and hierarchy spectra and budgets) take this path whenever the array is spread over R > 1 ranks: rank r owns the planes
@@ -1093,6 +1137,8 @@ int iamrx_amr_plane_profile(iamrx_amr a, int dir, int bin_level, int nbins_cap, 
 /* The spectra of iamrx_ns_spectrum on LEVEL 0 of the hierarchy: after avgDown its covered cells hold the average of the finer data (the
  * role of finestLevel = 0 in derivespect-inputs).  Spectra on finer levels and composite spectra are not built. */
 int iamrx_amr_spectrum(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins);
+/* The plane spectra of iamrx_ns_plane_spectrum on LEVEL 0 of the hierarchy, exactly as iamrx_amr_spectrum takes its level. */
+int iamrx_amr_plane_spectrum(iamrx_amr a, int dir, int nplanes_cap, int nrings_cap, double* out, long* count, int* nplanes, int* nrings);
 /* The budget of iamrx_ns_spectral_budget on LEVEL 0 of the hierarchy, exactly as iamrx_amr_spectrum takes its level. */
 int iamrx_amr_spectral_budget(iamrx_amr a, int nbins_cap, double* out, long* count, int* nbins);
 /* The a-priori LES analysis of iamrx_ns_sgs on LEVEL 0 of the hierarchy, exactly as iamrx_amr_spectrum takes its level. */
