@@ -504,7 +504,17 @@ int iamrx_abec_residual(const iamrx_geom* g, double alpha, double beta, iamrx_mf
                         iamrx_mf out, iamrx_mf phi, iamrx_mf rhs, int tensor)
 {
     IAMRX_TRY
-    abec_residual(to_geom(g), make_coef(alpha, beta, a, bx, by, bz, tensor), out->mf, phi->mf, rhs ? &rhs->mf : nullptr);
+    AbecCoef c = make_coef(alpha, beta, a, bx, by, bz, tensor);
+    const Geometry gg = to_geom(g);
+    if (tensor && bx->mf.ncomp == 1) {
+        // the face viscosities themselves (MLTensorOp::setShearViscosity), as CellMG hands them to its level residual (mlmg.hip:
+        // CellMG::coef, level_residual): constant ones take the fused launch where it applies
+        c.tensor_eta = 1;
+        c.b_uniform = 1;
+        for (int d = 0; d < 3 && c.b_uniform; ++d) c.b_uniform = mf_uniform_value(*c.b[d], &c.bu[d]) ? 1 : 0;
+        if (tensor_residual_fused(gg, c, out->mf, phi->mf, rhs ? &rhs->mf : nullptr, nullptr)) return 0;
+    }
+    abec_residual(gg, c, out->mf, phi->mf, rhs ? &rhs->mf : nullptr);
     IAMRX_CATCH
 }
 

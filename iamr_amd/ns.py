@@ -133,6 +133,13 @@ def tensor_solve(geom, soln, rhs, a, b, acoef, eta, lobc=(0, 0, 0), hibc=(0, 0, 
     return st
 
 
+def tensor_extensive_flux(geom, vel, eta, flux, fac, add=False):
+    """Diffusion::computeExtensiveFluxes on the tensor operator (include/iamrx.h: iamrx_tensor_extensive_flux): flux[d] (3 comps on the
+    d-faces) = or += fac * area_d * (-eta_d (4/3 if n == d) du_n/dx_d + cross terms); vel as tensor_apply / tensor_solve left it"""
+    check(lib().iamrx_tensor_extensive_flux(C.byref(geom), vel.h, eta[0].h, eta[1].h, eta[2].h, flux[0].h, flux[1].h, flux[2].h,
+                                            C.c_double(fac), int(bool(add))))
+
+
 def tensor_apply_cf(geom, out, vel, a, b, acoef, eta, crse_vel, cgeom, ratio=2, lobc=(0, 0, 0), hibc=(0, 0, 0), maxorder=2):
     """tensor operator on a refined level (tensorop.setCoarseFineBC(&crsedata, ratio), Source/Diffusion.cpp:1725-1736); crse_vel None: homogeneous"""
     lo, hi, nbc = _bcn(lobc, hibc)

@@ -253,7 +253,9 @@ int iamrx_abec_form(const iamrx_geom* g, int coef, iamrx_mf rho, int rho_comp, d
                     iamrx_mf phi, iamrx_mf rhs, iamrx_mf out, double omega, const int lobc[3], const int hibc[3], int maxorder);
 int iamrx_abec_gsrb_sweep(const iamrx_geom* g, double alpha, double beta, iamrx_mf a /* may be NULL */, iamrx_mf bx, iamrx_mf by, iamrx_mf bz,
                           iamrx_mf phi, iamrx_mf rhs, double omega, const int lobc[3], const int hibc[3], int maxorder, int fused);
-/* out = rhs - L(phi)  (rhs == NULL: out = L(phi)) */
+/* out = rhs - L(phi)  (rhs == NULL: out = L(phi)).  tensor = 1: MLTensorOp on a 3-component phi whose ghost cells (edges and corners
+ * included) are filled; b* hold b_d(comp) in 3 components, or the face viscosity in 1 component -- then the level residual of a tensor
+ * solve runs, constant viscosity in its fused launch (k_tensor_uni). */
 int iamrx_abec_residual(const iamrx_geom* g, double alpha, double beta, iamrx_mf a, iamrx_mf bx, iamrx_mf by, iamrx_mf bz,
                         iamrx_mf out, iamrx_mf phi, iamrx_mf rhs, int tensor);
 int iamrx_cc_restrict(iamrx_mf crse, iamrx_mf fine);
