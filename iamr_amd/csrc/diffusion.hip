@@ -136,27 +136,31 @@ MGStats diffuse_tensor_velocity(const Geometry& g, const MultiFab* U_old, MultiF
         fx.fac = 1.0 - theta; fx.add = false;                    // computeExtensiveFluxes(..., -b/dt), b = -(1 - theta) dt
         tensor_apply(g, Rhs, Soln0, 0.0, -(1.0 - theta) * dt, nullptr, eta_n, bc_visc, 3, crse ? &cf : nullptr, want_flux ? &fx : nullptr);
     } else if (!from_visc) Rhs.setVal(0.0);
+    double rn3[3];
     {
         const FabD *nt = U_new.d_tab, *ot = U_old ? U_old->d_tab : nullptr, *rt = Rhs.d_tab, *ht = rho_half.d_tab;
         const FabD* vt = from_visc ? visc_old_term->d_tab : nullptr;
         const double va = (1.0 - theta) * dt;
         const bool mom = rho_flag == 3;                          // rho_flag 3 (NavierStokes.cpp:1016): the OLD density (Diffusion.cpp:819)
         IAMRX_ASSERT(!mom || ot);
-        for_each(*layout, cell_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
+        // ... and the pass that writes Rhs also takes its per-component max norms (norm0_comps' terms: |v|, NaN -> +inf)
+        reduce_max_f<3>(*layout, cell_type(), 0, [=] __device__(int i, int j, int k, int f, double (&m)[3]) {
             const double r = mom ? ot[f](i, j, k, rho_comp) : ht[f](i, j, k, 0);
+#pragma unroll
             for (int n = 0; n < 3; ++n) {
                 const double un = nt[f](i, j, k, n) * r;
                 nt[f](i, j, k, n) = un;                          // Diffusion.cpp:825: the state holds rho u* from here on
                 double rr;
                 if (vt) { const double v = vt[f](i, j, k, n); rr = va * v + 0.0 * v; }
                 else rr = rt[f](i, j, k, n);
-                rt[f](i, j, k, n) = rr + un;
+                rr += un;
+                rt[f](i, j, k, n) = rr;
+                const double a = norm_term(rr);
+                m[n] = a > m[n] ? a : m[n];
             }
-        });
+        }, rn3);
     }
     double avg = 0.0;                                            // get_scaled_abs_tol (Diffusion.cpp:193-204)
-    double rn3[3];
-    Rhs.norm0_comps(0, 3, 0, rn3);
     for (int n = 0; n < 3; ++n) avg += (1.0 / 3.0) * rn3[n];
     const double tol_abs = visc_tol * avg;
     // Diffusion.cpp:866: FillPatch(U_new) -- of the velocity components that hold rho u* by now: neighbours and periodic images carry rho u*,

@@ -1062,7 +1062,7 @@ AbecLevel abec_level(const AbecCoef& c, const MultiFab& phi, int rhs_ngrow, int 
     lv.ncomp = phi.ncomp; lv.phi_ngrow = phi.ngrow; lv.rhs_ngrow = rhs_ngrow;
     lv.sig = c.sig != nullptr; lv.sig_ngrow = c.sig ? c.sig->ngrow : 0;
     lv.has_a = c.a && c.alpha != 0.0; lv.a_ngrow = c.a ? c.a->ngrow : 0;
-    lv.b_uniform = c.b_uniform != 0; lv.tensor_eta = c.tensor_eta != 0; lv.tensor = c.tensor != 0; lv.b_ncomp = c.b[0]->ncomp;
+    lv.b_uniform = c.b_uniform != 0; lv.tensor_eta = c.tensor_eta != 0; lv.tensor = c.tensor != 0; lv.b_ncomp = c.b[0] ? c.b[0]->ncomp : 1;
     lv.nbc = nbc; lv.bcs = bcs; lv.has_cf = has_cf; lv.finest = finest;
     return lv;
 }
@@ -2828,7 +2828,75 @@ void face_avgdown(MultiFab& crse, const MultiFab& fine, int dir)
     });
 }
 
+// face_avgdown(crse, b, dir) of b = mac_bcoef(rho, comp, scale) without the array b: the four fine values in face_avgdown's order, each
+// mac_bcoef's expression evaluated in place (the same doubles)
+void mac_bcoef_avgdown(MultiFab& crse, const MultiFab& rho, int rho_comp, double scale, int dir)
+{
+    if (crse.nlocal() == 0) return;
+    const FabD *rt = rho.d_tab, *ct = crse.d_tab;
+    const int d1 = (dir + 1) % 3, d2 = (dir + 2) % 3;
+    const int da = d1 < d2 ? d1 : d2, db = d1 < d2 ? d2 : d1;
+    for_each(*crse.layout, face_type(dir), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
+        const FabD r = rt[f];
+        const int c[3] = {i, j, k};
+        double s = 0.0;
+        for (int rb = 0; rb < 2; ++rb)
+            for (int ra = 0; ra < 2; ++ra) {
+                int q[3], m[3];
+                q[dir] = 2 * c[dir]; q[da] = 2 * c[da] + ra; q[db] = 2 * c[db] + rb;
+                m[0] = q[0]; m[1] = q[1]; m[2] = q[2]; m[dir] -= 1;
+                const double rf = 0.5 * (r(m[0], m[1], m[2], rho_comp) + r(q[0], q[1], q[2], rho_comp));
+                s += scale / rf;
+            }
+        ct[f](i, j, k, 0) = s * 0.25;
+    });
+}
+
 // ---------------------------------------------------------------------------- fluxes / MAC helpers
+// abec_flux for one component with b = mac_bcoef(rho, comp, scale), formed in place, the three directions in ONE launch: over the cells
+// of each box grown by one on the high side (the last face plane of each direction), a thread takes the low face of its cell in every
+// direction whose face lies in the box's face range.  phi and rho: one ghost layer, filled.
+void abec_flux_sig(const Geometry& g, double beta, const MultiFab& rho, int rho_comp, double scale, const MultiFab& phi, MultiFab* const flux[3],
+                   MultiFab* const add_to[3])
+{
+    IAMRX_ASSERT(phi.ncomp == 1 && phi.ngrow >= 1 && rho.ngrow >= 1);
+    if (phi.nlocal() == 0) return;
+    const FabD *pt = phi.d_tab, *rt = rho.d_tab;
+    const BoxD* boxes = phi.layout->d_boxes;
+    const double fx = beta / g.dx[0], fy = beta / g.dx[1], fz = beta / g.dx[2];
+    const FabD* f0 = flux && flux[0] ? flux[0]->d_tab : nullptr;
+    const FabD* f1 = flux && flux[1] ? flux[1]->d_tab : nullptr;
+    const FabD* f2 = flux && flux[2] ? flux[2]->d_tab : nullptr;
+    const FabD* u0 = add_to && add_to[0] ? add_to[0]->d_tab : nullptr;
+    const FabD* u1 = add_to && add_to[1] ? add_to[1]->d_tab : nullptr;
+    const FabD* u2 = add_to && add_to[2] ? add_to[2]->d_tab : nullptr;
+    for_each(*phi.layout, node_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
+        const BoxD b = boxes[f];
+        const bool in0 = i <= b.hi[0], in1 = j <= b.hi[1], in2 = k <= b.hi[2];
+        if ((in0 ? 0 : 1) + (in1 ? 0 : 1) + (in2 ? 0 : 1) >= 2) return;          // beyond two sides: no face of the box's
+        const FabD p = pt[f], r = rt[f];
+        const double p0 = p(i, j, k, 0), r0 = r(i, j, k, rho_comp);
+        if (in1 && in2) {
+            const double bf = scale / (0.5 * (r(i - 1, j, k, rho_comp) + r0));
+            const double fl = -fx * bf * (p0 - p(i - 1, j, k, 0));
+            if (f0) f0[f](i, j, k, 0) = fl;
+            if (u0) u0[f](i, j, k, 0) += fl;
+        }
+        if (in0 && in2) {
+            const double bf = scale / (0.5 * (r(i, j - 1, k, rho_comp) + r0));
+            const double fl = -fy * bf * (p0 - p(i, j - 1, k, 0));
+            if (f1) f1[f](i, j, k, 0) = fl;
+            if (u1) u1[f](i, j, k, 0) += fl;
+        }
+        if (in0 && in1) {
+            const double bf = scale / (0.5 * (r(i, j, k - 1, rho_comp) + r0));
+            const double fl = -fz * bf * (p0 - p(i, j, k - 1, 0));
+            if (f2) f2[f](i, j, k, 0) = fl;
+            if (u2) u2[f](i, j, k, 0) += fl;
+        }
+    });
+}
+
 void abec_flux(const Geometry& g, const AbecCoef& c, const MultiFab& phi, MultiFab* const flux[3], MultiFab* const add_to[3])
 {
     if (phi.nlocal() == 0) return;
@@ -2863,20 +2931,7 @@ void mac_divergence(const Geometry& g, MultiFab& div, const MultiFab* const umac
     });
 }
 
-void mac_rhs(const Geometry& g, MultiFab& rhs, const MultiFab* const umac[3], const MultiFab* S)
-{
-    if (rhs.nlocal() == 0) return;
-    const FabD *rt = rhs.d_tab, *ut = umac[0]->d_tab, *vt = umac[1]->d_tab, *wt = umac[2]->d_tab;
-    const FabD* st = S ? S->d_tab : nullptr;
-    const double dx = g.dx[0], dy = g.dx[1], dz = g.dx[2];
-    for_each(*rhs.layout, cell_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
-        const FabD u = ut[f], v = vt[f], w = wt[f];
-        const double div = (u(i + 1, j, k) - u(i, j, k)) / dx + (v(i, j + 1, k) - v(i, j, k)) / dy + (w(i, j, k + 1) - w(i, j, k)) / dz;
-        double r = -div;
-        if (st) r += st[f](i, j, k, 0);
-        rt[f](i, j, k, 0) = r;
-    });
-}
+// (mac_rhs: k_basic.hip, next to the reductions it shares its second stage with)
 
 void mac_bcoef(MultiFab* const b[3], const MultiFab& rho, int rho_comp, double scale)
 {

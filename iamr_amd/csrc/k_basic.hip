@@ -584,6 +584,72 @@ void mf_add_scalar(MultiFab& y, double a, int comp, int nc, int ng)
     });
 }
 
+// y += a (mf_add_scalar's expression) and the max norm of the result (norm0's terms) in one pass
+double mf_add_scalar_norm0(MultiFab& y, double a, int comp, int ng)
+{
+    const FabD* yt = y.d_tab;
+    double out = 0.0;
+    reduce_max_f<1>(*y.layout, y.type, ng, [=] __device__(int i, int j, int k, int f, double (&m)[1]) {
+        double v = yt[f](i, j, k, comp);
+        v += a;
+        yt[f](i, j, k, comp) = v;
+        const double t = norm_term(v);
+        m[0] = t > m[0] ? t : m[0];
+    }, &out);
+    return out;
+}
+
+// rhs = S - div(umac) on the cells.  sum: also the sum of rhs over the level, formed as rhs.sum_unique(g, 0) forms it -- k_sum_unique's
+// tiling, each thread's planes added in the same order (a cell's owner weight is 1), the same two reduction stages: the same bits --
+// without the second read of the array
+template <bool SUM>
+__global__ void __launch_bounds__(256) k_mac_rhs(Tiling t, const BoxD* __restrict__ boxes, const FabD* __restrict__ rt, const FabD* __restrict__ ut,
+                                                 const FabD* __restrict__ vt, const FabD* __restrict__ wt, const FabD* __restrict__ st,
+                                                 double dx, double dy, double dz, double* __restrict__ partials)
+{
+    const int fab = tile_fab(t);
+    const BoxD b = boxes[fab];
+    int i, j, k0, k1;
+    double s = 0.0;
+    if (tile_ijk(t, b, i, j, k0, k1)) {
+        const FabD u = ut[fab], v = vt[fab], w = wt[fab], rr = rt[fab];
+        for (int k = k0; k <= k1; ++k) {
+            const double div = (u(i + 1, j, k) - u(i, j, k)) / dx + (v(i, j + 1, k) - v(i, j, k)) / dy + (w(i, j, k + 1) - w(i, j, k)) / dz;
+            double r = -div;
+            if (st) r += st[fab](i, j, k, 0);
+            rr(i, j, k, 0) = r;
+            if (SUM) s += r;
+        }
+    }
+    if (SUM) {
+        s = block_reduce<0>(s);
+        if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+void mac_rhs(const Geometry& g, MultiFab& rhs, const MultiFab* const umac[3], const MultiFab* S, double* sum)
+{
+    auto& ctx = Context::get();
+    const bool global = !rhs.layout->replicated;
+    if (rhs.nlocal() == 0) {
+        if (sum) *sum = (global && ctx.comm->nranks > 1) ? finish_to_host(0, 1, 0, true) : 0.0;
+        return;
+    }
+    Tiling t = level_tiling(*rhs.layout, cell_type(), 0, 8, true);
+    dim3 gr = t.grid();
+    const int np = (int)(gr.x * gr.y);
+    const FabD* st = S ? S->d_tab : nullptr;
+    if (!sum) {
+        hipLaunchKernelGGL((k_mac_rhs<false>), gr, Tiling::block(), 0, ctx.stream, t, rhs.layout->d_boxes, rhs.d_tab, umac[0]->d_tab, umac[1]->d_tab,
+                           umac[2]->d_tab, st, g.dx[0], g.dx[1], g.dx[2], (double*)nullptr);
+        return;
+    }
+    ctx.ensure_scratch((size_t)np + 16);
+    hipLaunchKernelGGL((k_mac_rhs<true>), gr, Tiling::block(), 0, ctx.stream, t, rhs.layout->d_boxes, rhs.d_tab, umac[0]->d_tab, umac[1]->d_tab,
+                       umac[2]->d_tab, st, g.dx[0], g.dx[1], g.dx[2], ctx.d_scratch);
+    *sum = finish_to_host(0, 1, np, global);
+}
+
 void mf_mult(MultiFab& y, double a, int comp, int nc, int ng)
 {
     trace_blas_site("mult", y.layout ? y.layout->local_cells() * nc : 0);

@@ -43,6 +43,7 @@ void gs4_probe_stop(double* total_ms, long* launches);
 void mf_lincomb(MultiFab& dst, double a, const MultiFab& x, double b, const MultiFab& y, int comp, int nc, int ng);   // dst = a*x + b*y
 void mf_saxpy(MultiFab& y, double a, const MultiFab& x, int xcomp, int ycomp, int nc, int ng);                          // y += a*x
 void mf_add_scalar(MultiFab& y, double a, int comp, int nc, int ng);
+double mf_add_scalar_norm0(MultiFab& y, double a, int comp, int ng);      // y(comp) += a and the max norm of the result (norm0's), one pass
 void mf_mult(MultiFab& y, double a, int comp, int nc, int ng);
 // the same on the ng ghost layers only (the valid region is not touched): one launch over the shell of every box
 void mf_mult_ghosts(MultiFab& y, double a, int comp, int nc, int ng);
@@ -274,6 +275,7 @@ struct AbecCoef {
     // sig != null: b[d] was made by mac_bcoef(b, *sig, sig_comp, sig_scale) and the smoother / residual kernels may recompute the face
     // value sig_scale / (0.5 (sig(cell - e_d) + sig(cell))) from the cell-centred array instead of reading three face arrays (the same
     // expression, hence the same doubles; one array of HBM traffic instead of three).  sig has >= 1 ghost cell, filled.
+    // b[d] may then be null (CellMG::prepare: no consumer of the level reads the arrays, so none were made).
     const MultiFab* sig = nullptr;
     int sig_comp = 0;
     double sig_scale = 1.0;
@@ -418,8 +420,13 @@ void cc_prolong_add(MultiFab& fine, const MultiFab& crse);       // piecewise co
 void face_avgdown(MultiFab& crse, const MultiFab& fine, int dir);
 // flux_d = -beta*b_d*dphi/dx_d ; if add_to != nullptr: add_to[d] += flux_d instead of storing
 void abec_flux(const Geometry& g, const AbecCoef& c, const MultiFab& phi, MultiFab* const flux[3], MultiFab* const add_to[3]);
-void mac_rhs(const Geometry& g, MultiFab& rhs, const MultiFab* const umac[3], const MultiFab* S);   // rhs = S - div(umac)
+// rhs = S - div(umac); sum != null: also rhs.sum_unique(g, 0), its bits, out of the same pass (k_basic.hip)
+void mac_rhs(const Geometry& g, MultiFab& rhs, const MultiFab* const umac[3], const MultiFab* S, double* sum = nullptr);
 void mac_bcoef(MultiFab* const b[3], const MultiFab& rho, int rho_comp, double scale);                 // b = scale / avg_face(rho)
+// the same doubles without the arrays b: crse = face_avgdown of mac_bcoef(rho) in direction dir; abec_flux (one component) in one launch
+void mac_bcoef_avgdown(MultiFab& crse, const MultiFab& rho, int rho_comp, double scale, int dir);
+void abec_flux_sig(const Geometry& g, double beta, const MultiFab& rho, int rho_comp, double scale, const MultiFab& phi, MultiFab* const flux[3],
+                   MultiFab* const add_to[3]);
 void mac_divergence(const Geometry& g, MultiFab& div, const MultiFab* const umac[3]);
 
 // ---- k_godunov.hip ------------------------------------------------------------------------

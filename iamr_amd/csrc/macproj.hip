@@ -20,11 +20,13 @@ MGStats mlmg_mac_solve(const Geometry& g, MultiFab* const umac[3], const MultiFa
                        const MGOpts& opts, MultiFab* const fluxes[3], const MultiFab* cphi, const Geometry* cgeom, int ratio)
 {
     LayoutP layout = mac_phi.layout;
+    // the face average of the density reads one cell beyond every box face (include/iamrx.h: "rho needs 1 filled ghost")
+    if (rho.ngrow < 1) throw Error("iamrx mlmg_mac_solve: the density needs one filled ghost layer");
     // caller-owned arrays on a level chopped at amr.max_grid_size (the operator boundary as IAMR drives it): solve on the merged boxes --
     // no ghost fills between colour passes, index wrap on periodic domains -- and hand the results back on the caller's
     if (!cgeom) {
         if (LayoutP ml = merged_solve_layout(g, layout)) {
-            MultiFab um_m[3], fl_m[3], rho_m(ml, cell_type(), 1, std::min(rho.ngrow, 1)), phi_m(ml, cell_type(), 1, mac_phi.ngrow), S_m;
+            MultiFab um_m[3], fl_m[3], rho_m(ml, cell_type(), 1, 1), phi_m(ml, cell_type(), 1, mac_phi.ngrow), S_m;
             MultiFab *ump[3], *flp[3];
             for (int d = 0; d < 3; ++d) {
                 um_m[d].define(ml, face_type(d), 1, 0); relayout_copy(um_m[d], *umac[d], 1); ump[d] = &um_m[d];
@@ -40,24 +42,32 @@ MGStats mlmg_mac_solve(const Geometry& g, MultiFab* const umac[3], const MultiFa
             return st;
         }
     }
-    MultiFab bcoef[3];
-    MultiFab* bp[3];
-    const MultiFab* bcp[3];
-    for (int d = 0; d < 3; ++d) { bcoef[d].define(layout, face_type(d), 1, 0); bp[d] = &bcoef[d]; bcp[d] = &bcoef[d]; }
-    mac_bcoef(bp, rho, rho_comp, 1.0 / rhs_scale);
-
-    MultiFab rhs(layout, cell_type(), 1, 0);
-    const MultiFab* um[3] = {umac[0], umac[1], umac[2]};
-    mac_rhs(g, rhs, um, S);
-
+    // A density with its ghost layer is all the solver needs (IAMRX_MAC_GLUE, 1): it forms b = (1 / rhs_scale) / avg_face(rho) where it
+    // is used and makes the three face arrays only if one of its finest-level kernels reads them (CellMG::prepare).  0: the arrays are
+    // made here and handed over, as before
+    const bool from_cell = tune("MAC_GLUE", 1) != 0;
+    // (rhs is allocated here, where it always was, although it is filled behind prepare().  Not a requirement: an unexplained observation
+    // on one machine -- allocated behind the levels, two kernels that stream rhs and res ran 6 % slower at 256^3 -- that another machine
+    // did not show; profiles/mac_glue_bench.txt)
+    MultiFab bcoef[3], rhs(layout, cell_type(), 1, 0);
     CellMG mg(g, layout, 1, bc, opts);
     mg.setScalars(0.0, 1.0);
-    mg.setBCoeffs(bcp);
-    if (rho.ngrow >= 1) mg.setBCoeffsFromCell(&rho, rho_comp, 1.0 / rhs_scale);
+    if (!from_cell) {
+        MultiFab* bp[3];
+        const MultiFab* bcp[3];
+        for (int d = 0; d < 3; ++d) { bcoef[d].define(layout, face_type(d), 1, 0); bp[d] = &bcoef[d]; bcp[d] = &bcoef[d]; }
+        mac_bcoef(bp, rho, rho_comp, 1.0 / rhs_scale);
+        mg.setBCoeffs(bcp);
+    }
+    mg.setBCoeffsFromCell(&rho, rho_comp, 1.0 / rhs_scale);
     // level > 0: Dirichlet data on the coarse/fine faces from the coarse level's MAC phi (MacProj.cpp:1166-1170)
     if (cgeom) mg.setCoarseFineBC(cphi, *cgeom, ratio);
     mg.prepare();
-    MGStats st = mg.solve(mac_phi, rhs, mac_tol, mac_abs_tol);
+    // rhs = S - div(u_mac), a temporary of this solve: a singular solve removes its mean in place, from the sum the same pass leaves
+    const MultiFab* um[3] = {umac[0], umac[1], umac[2]};
+    double rhs_sum = 0.0;
+    mac_rhs(g, rhs, um, S, mg.singular() ? &rhs_sum : nullptr);
+    MGStats st = mg.solve_giving_rhs(mac_phi, rhs, mac_tol, mac_abs_tol, mg.singular() ? &rhs_sum : nullptr);
     // u_mac += (-beta grad phi); optionally hand the fluxes back (MacProj.cpp:1181-1183)
     mg.fluxes(mac_phi, fluxes, umac);
     return st;

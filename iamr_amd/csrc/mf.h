@@ -135,6 +135,7 @@ double tune(const char* key, double dflt);             // key: a string LITERAL 
 double tune_by_name(const char* key, double dflt);     // any string
 void trace_blas_site(const char* what, long points);   // IAMRX_BLAS_TRACE (mf.hip)
 void tuning_set(const char* key, double value);
+void tuning_count(const char* key);     // registry entry key += 1: a counter of the library's, read with iamrx_tuning_get
 void tuning_load_environment();          // called by Context::init
 
 // ------------------------------------------------------------------ scoped profiler (measurement aid)

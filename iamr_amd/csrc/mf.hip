@@ -270,6 +270,9 @@ double tune(const char* key, double dflt)
     return tune_by_name(key, dflt);
 }
 void tuning_set(const char* key, double value) { tuning_map()[key] = value; ++g_tune_version; }
+// a counter the library keeps for iamrx_tuning_get to read (which path a call took): no call site takes such a key through tune(), so the
+// slots stay valid and the version is left alone
+void tuning_count(const char* key) { tuning_map()[key] += 1.0; }
 
 // ---- scoped profiler
 bool ProfScope::enabled = false;

@@ -138,7 +138,8 @@ public:
     void setScalars(double alpha, double beta) { m_alpha = alpha; m_beta = beta; }
     void setACoeffs(const MultiFab* a) { m_a0 = a; }
     void setBCoeffs(const MultiFab* const b[3]) { for (int d = 0; d < 3; ++d) m_b0[d] = b[d]; }
-    // the b of setBCoeffs is mac_bcoef(b, sig, comp, scale): the finest level's smoother and residual recompute it from sig (AbecCoef::sig)
+    // the b of setBCoeffs is mac_bcoef(b, sig, comp, scale): the finest level's smoother and residual recompute it from sig (AbecCoef::sig).
+    // Without setBCoeffs the solver runs from sig alone (sig with >= 1 filled ghost layer) and makes the arrays itself where it must.
     void setBCoeffsFromCell(const MultiFab* sig, int comp, double scale) { m_sig = sig; m_sig_comp = comp; m_sig_scale = scale; }
     void setTensor(bool t) { m_tensor = t; }
     // tensor operator with the B coefficients given as the 1-component face viscosity: the finest level streams eta instead of the
@@ -156,7 +157,11 @@ public:
     // entry (domain faces; coarse/fine faces are taken from setCoarseFineBC's array) and what the stencil reads on exit, edge cells of
     // the tensor operator included
     void fillBoundaryData(MultiFab& phi);
-    MGStats solve(MultiFab& phi, const MultiFab& rhs, double rtol, double atol);
+    MGStats solve(MultiFab& phi, const MultiFab& rhs, double rtol, double atol) { return solve_on(phi, rhs, nullptr, rtol, atol, nullptr); }
+    // the caller gives rhs away (it does not read it again): a singular solve removes the mean IN rhs instead of on a copy;
+    // rhs_sum: rhs.sum_unique of a one-component rhs where the caller has it already (mac_rhs), else it is taken here
+    MGStats solve_giving_rhs(MultiFab& phi, MultiFab& rhs, double rtol, double atol, const double* rhs_sum = nullptr) { return solve_on(phi, rhs, &rhs, rtol, atol, rhs_sum); }
+    bool singular() const { return m_singular; }       // after prepare()
     // out = L(phi) with inhomogeneous BC taken from phi's ghost cells
     void apply(MultiFab& out, MultiFab& phi);
     void fluxes(MultiFab& phi, MultiFab* const flux[3], MultiFab* const add_to[3]);
@@ -187,6 +192,8 @@ private:
         MultiFab cfm;              // coarse/fine mask (levels that do not cover the domain), see cf_build_mask
         CfTab cftab;
     };
+    // rhs_mine: null, or rhs_in itself as an array the solve may write
+    MGStats solve_on(MultiFab& phi, const MultiFab& rhs_in, MultiFab* rhs_mine, double rtol, double atol, const double* rhs_sum);
     int bicgstab(int l, MultiFab& sol, const MultiFab& rhs, double eps_rel, double eps_abs, int& niters);
     void bottom_solve(MGStats& st);
     // nsweeps out-of-place sweeps sweep(in, out, zero, last) between sol and buf, the result in sol (or in acc: see smooth_n)
@@ -202,6 +209,9 @@ private:
     double m_alpha = 0.0, m_beta = 1.0;
     const MultiFab* m_a0 = nullptr;
     const MultiFab* m_b0[3] = {nullptr, nullptr, nullptr};
+    // setBCoeffsFromCell without setBCoeffs: m_b0 stays null unless prepare() finds a reader of the finest level's face arrays and makes them
+    MultiFab m_b0_own[3];
+    void materialise_b();
     bool m_buni = false;                 // the finest level's b arrays are constants (prepare() checks)
     bool m_buni_coarse = false;          // ... and the coarser levels use the constants too (IAMRX_MG_COARSE_UNIFORM, 1)
     double m_bu[3] = {0.0, 0.0, 0.0};

@@ -150,10 +150,23 @@ void CellMG::prepareBoundary()
     prepare_cf(0);
 }
 
+void CellMG::materialise_b()
+{
+    MultiFab* bp[3];
+    for (int d = 0; d < 3; ++d) { m_b0_own[d].define(m_lev[0].layout, face_type(d), 1, 0); bp[d] = &m_b0_own[d]; m_b0[d] = &m_b0_own[d]; }
+    mac_bcoef(bp, *m_sig, m_sig_comp, m_sig_scale);
+    tuning_count("MAC_GLUE_MATERIALISED");
+}
+
 void CellMG::prepare()
 {
     ProfScope ps_prof_("cmg_prepare");
-    IAMRX_ASSERT(m_b0[0] && m_b0[1] && m_b0[2]);
+    IAMRX_ASSERT((m_b0[0] && m_b0[1] && m_b0[2]) || (m_sig && !m_b0[0] && !m_b0[1] && !m_b0[2]));
+    // setBCoeffsFromCell alone: the finest level's face arrays are made only where something reads them.  The density forms of the colour
+    // passes, the sweeps, the residual, the residual + restriction, the level-1 coefficients and the fluxes cover one component without
+    // an a-term; everything else of the operator (tensor, eta form, an a-term, IAMRX_ABEC_SIG = 0) reads the arrays.  What the level's
+    // plan adds is decided next to it, below.
+    if (!m_b0[0] && !(m_ncomp == 1 && !m_tensor && !m_tensor_eta && !(m_a0 && m_alpha != 0.0) && tune("ABEC_SIG", 1) != 0)) materialise_b();
     // singular <=> no 'a' term and no Dirichlet boundary (MLABecLaplacian::m_is_singular)
     m_singular = !(m_alpha != 0.0 && m_a0);
     for (int d = 0; d < 3; ++d)
@@ -188,15 +201,15 @@ void CellMG::prepare()
         double bmax = 0.0;
         for (int d = 0; d < 3; ++d) bmax = std::max(bmax, m_buni ? std::fabs(m_bu[d]) : m_b0[d]->norm0(0, m_b0[d]->ncomp, 0));
         if (m_tensor_eta) bmax *= 4.0 / 3.0;
-        MultiFab inv(m_lev[0].layout, cell_type(), 1, 0);
+        double ainv = 0.0;          // max norm of a > 0 ? 1 / a : 1e300, reduced where it is formed
         {
-            const FabD *it = inv.d_tab, *at = m_a0->d_tab;
-            for_each(*m_lev[0].layout, cell_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
+            const FabD* at = m_a0->d_tab;
+            reduce_max_f<1>(*m_lev[0].layout, cell_type(), 0, [=] __device__(int i, int j, int k, int f, double (&m)[1]) {
                 const double a = at[f](i, j, k);
-                it[f](i, j, k) = a > 0.0 ? 1.0 / a : 1.e300;
-            });
+                const double v = norm_term(a > 0.0 ? 1.0 / a : 1.e300);
+                m[0] = v > m[0] ? v : m[0];
+            }, &ainv);
         }
-        const double ainv = inv.norm0(0, 1, 0);
         double q = 0.0;
         for (int d = 0; d < 3; ++d) q += 2.0 / (m_g.dx[d] * m_g.dx[d]);
         q *= m_beta * bmax;
@@ -267,6 +280,12 @@ void CellMG::prepare()
                 // coarsening the finest level of an eta-form tensor operator: average the three-component coefficients it stands for
                 MultiFab b3;
                 const MultiFab* fb = fc.b[d];
+                if (!fb) {             // level 1 under a finest level without face arrays: the average of mac_bcoef's values, from the density
+                    L.b[d].define(L.layout, face_type(d), 1, 0);
+                    coarsen_into(L.b[d], face_type(d), 1, [&](MultiFab& c) { mac_bcoef_avgdown(c, *m_sig, m_sig_comp, m_sig_scale, d); });
+                    if (d == 0) tuning_count("MAC_GLUE_LEVEL1");
+                    continue;
+                }
                 if (l == 1 && m_tensor_eta && !m_buni_coarse) { b3.define(m_lev[0].layout, face_type(d), 3, 0); tensor_bcoef(b3, *fc.b[d], d); fb = &b3; }
                 L.b[d].define(L.layout, face_type(d), fb->ncomp, 0);
                 coarsen_into(L.b[d], face_type(d), fb->ncomp, [&](MultiFab& c) { face_avgdown(c, *fb, d); });
@@ -274,7 +293,11 @@ void CellMG::prepare()
         }
         // everything a smoothing call on this level depends on is known now: its path is chosen here, once per solve (coef: with the tensor flag)
         L.plan = abec_smooth_plan(L.g, abec_level(coef(l), L.cor, L.res.ngrow, (int)m_bcn.size(), m_bcn.data(), m_cf, l == 0));
+        // ... and with it whether the finest level still needs face arrays it was not given: the fused sweep + shell pass has no density
+        // form, nor has the device bottom solver (a hierarchy of one level)
+        if (l == 0 && !m_b0[0] && (L.plan.path == AbecSmoothPlan::FUSED_SHELL || (nl == 1 && m_bottom_dev))) materialise_b();
     }
+    if (!m_b0[0]) tuning_count("MAC_GLUE_NO_ARRAYS");
     // ... and whether a coarse level's down leg and up leg run as one launch each (abec_leg_plan: IAMRX_MG_LEGS); never the coarsest level
     // (the bottom solver's) nor the level the opt-in fused tail claims
     for (int l = 0; l < nl; ++l) {
@@ -723,10 +746,17 @@ void CellMG::apply(MultiFab& out, MultiFab& phi)
 
 void CellMG::fluxes(MultiFab& phi, MultiFab* const flux[3], MultiFab* const add_to[3])
 {
+    // one component with its b from the density (setBCoeffsFromCell): the three directions in one launch that forms b in place
+    // (IAMRX_MAC_GLUE = 0: a launch per direction on the face arrays, which mlmg_mac_solve then hands over)
+    if (m_sig && m_ncomp == 1 && (!m_b0[0] || tune("MAC_GLUE", 1) != 0)) {
+        abec_flux_sig(m_lev[0].g, m_beta, *m_sig, m_sig_comp, m_sig_scale, phi, flux, add_to);
+        tuning_count("MAC_GLUE_FLUX");
+        return;
+    }
     abec_flux(m_lev[0].g, coef(0), phi, flux, add_to);
 }
 
-MGStats CellMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, double atol)
+MGStats CellMG::solve_on(MultiFab& phi, const MultiFab& rhs_in, MultiFab* rhs_mine, double rtol, double atol, const double* rhs_sum)
 {
     ProfScope ps_prof_("cmg_solve");
     auto& ctx = Context::get();
@@ -735,13 +765,23 @@ MGStats CellMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, double
     Level& L0 = m_lev[0];
     const int nc = m_ncomp;
     // the right-hand side is only changed (mean removed) for a singular system: everything else solves on the caller's array
+    // (on a copy, unless the caller gives its array away); the pass that removes the mean also takes the max norm of what it leaves
     MultiFab rhs_own;
-    if (m_singular) {
+    const bool inplace = m_singular && rhs_mine;
+    if (m_singular && !inplace) {
         rhs_own.define(L0.layout, cell_type(), nc, 0);
         MultiFab::Copy(rhs_own, rhs_in, 0, 0, nc, 0);
-        subtract_mean(0, rhs_own);
     }
-    const MultiFab& rhs = m_singular ? rhs_own : rhs_in;
+    const MultiFab& rhs = !m_singular ? rhs_in : (inplace ? rhs_in : rhs_own);
+    if (m_singular) {
+        MultiFab& w = inplace ? *rhs_mine : rhs_own;
+        const double ncell = (double)L0.g.domain.npts();
+        for (int n = 0; n < nc; ++n) {
+            const double s = (rhs_sum && nc == 1) ? *rhs_sum : w.sum_unique(L0.g, n);
+            const double m = mf_add_scalar_norm0(w, -s / ncell, n, 0);
+            st.rhsnorm0 = m > st.rhsnorm0 ? m : st.rhsnorm0;
+        }
+    }
     // boundary data = the ghost cells of the initial phi (domain faces) and the coarse solution (coarse/fine faces); a fully periodic
     // level without coarse/fine faces has none
     const bool has_bcdata = m_cf || !(L0.g.periodic[0] && L0.g.periodic[1] && L0.g.periodic[2]);
@@ -755,7 +795,7 @@ MGStats CellMG::solve(MultiFab& phi, const MultiFab& rhs_in, double rtol, double
 
     applyBC(0, phi, true, bcvp);
     level_residual(L0.g, coef(0), L0.res, phi, &rhs, &st.resnorm0);      // the residual launch reduces its own max norm
-    st.rhsnorm0 = rhs.norm0(0, nc, 0);
+    if (!m_singular) st.rhsnorm0 = rhs.norm0(0, nc, 0);
     const double max_norm = st.rhsnorm0 >= st.resnorm0 ? st.rhsnorm0 : st.resnorm0;
     // (see NodalMG::solve)
     if (!std::isfinite(max_norm)) throw Error("iamrx MLMG: the right-hand side or the initial residual is not finite");

@@ -268,13 +268,14 @@ int iamrx_abec_solve(const iamrx_geom* g, double alpha, double beta, iamrx_mf a,
 
 /* ---- MAC projection -------------------------------------------------------------------- */
 /* MacProj::mlmg_mac_solve (Source/MacProj.cpp:1084-1184; declaration Source/MacProj.H:82-94):
- * b = (1/rhs_scale)/rho_face, rhs = S - div(u_mac), solve, u_mac -= b grad phi.  rho needs 1 filled ghost. */
+ * b = (1/rhs_scale)/rho_face, rhs = S - div(u_mac), solve, u_mac -= b grad phi.  rho needs 1 filled ghost layer (the face average reads one
+ * cell beyond every box face): a density array without ghost cells is an error. */
 int iamrx_mlmg_mac_solve(const iamrx_geom* g, iamrx_mf umac_x, iamrx_mf umac_y, iamrx_mf umac_z, iamrx_mf rho, int rho_comp,
                          iamrx_mf S /* may be NULL */, iamrx_mf mac_phi, double rhs_scale, const int lobc[3], const int hibc[3],
                          double mac_tol, double mac_abs_tol, const iamrx_mg_opts* o, iamrx_mg_stats* st);
 /* the same on an AMR level > 0: cphi = mac_phi_crse[level-1] (the coarse level's MAC phi on its own layout, geometry cgeom) supplies the
  * Dirichlet data of the coarse/fine faces (macproj.setCoarseFineBC(cphi, ratio), Source/MacProj.cpp:1166-1170).  rho needs its ghost cells
- * filled (FillPatch from the coarse level at coarse/fine faces). */
+ * filled (FillPatch from the coarse level at coarse/fine faces); a density array without ghost cells is an error. */
 int iamrx_mlmg_mac_solve_cf(const iamrx_geom* g, iamrx_mf umac_x, iamrx_mf umac_y, iamrx_mf umac_z, iamrx_mf rho, int rho_comp,
                             iamrx_mf S /* may be NULL */, iamrx_mf mac_phi, double rhs_scale, const int lobc[3], const int hibc[3],
                             iamrx_mf crse_phi, const iamrx_geom* cgeom, int ratio, double mac_tol, double mac_abs_tol,
@@ -282,7 +283,8 @@ int iamrx_mlmg_mac_solve_cf(const iamrx_geom* g, iamrx_mf umac_x, iamrx_mf umac_
 /* MacProj::mac_sync_solve (Source/MacProj.cpp:359-470): coarse-level solve for the correction velocity that removes the mismatch between
  * the coarse MAC velocity and the fine one on the coarse/fine interface.  mac_reg: the interface's register after
  * CrseInit(u_mac_crse, mult = -area_crse) and FineAdd(u_mac_fine, mult = +area_fine / ncycle) (Source/MacProj.cpp:306-346);
- * ucorr_*: coarse face arrays (out), mac_sync_phi: coarse cells, 1 ghost (out); fine: the fine level's layout. */
+ * ucorr_*: coarse face arrays (out), mac_sync_phi: coarse cells, 1 ghost (out); fine: the fine level's layout.  rho_half: 1 filled ghost layer,
+ * as for iamrx_mlmg_mac_solve (without ghost cells: an error). */
 int iamrx_mac_sync_solve(const iamrx_geom* g, iamrx_fluxreg mac_reg, iamrx_mf rho_half, double dt, iamrx_layout fine, int ratio,
                          iamrx_mf ucorr_x, iamrx_mf ucorr_y, iamrx_mf ucorr_z, iamrx_mf mac_sync_phi, const int lobc[3], const int hibc[3],
                          double mac_sync_tol, double mac_abs_tol, const iamrx_mg_opts* o, iamrx_mg_stats* st);
