@@ -108,6 +108,11 @@ __device__ __forceinline__ double slope4v(double qmm, double qm, double qi, doub
 // the left (the low-side state of the lane's face) is the left lane's slope.  Same operands and expressions as slope4v: the same doubles.
 // (measured at 256^3, MI355X: ExtrapVelToFaces 1.02 -> 1.00 ms, ComputeAofs of the velocity 1.845 -> 1.877 ms -- the instructions saved are
 // not what bounds the kernels (two wavefronts per SIMD, four barriers per plane): kept as a build option, off)
+// three barriers per plane in k_god_z instead of four (the comment at its LDS arrays; measured at 256^3: 2.709 -> 2.684 ms per five-component
+// call); -DIAMRX_GOD_B3=0 builds the four-barrier loop for A/B runs
+#ifndef IAMRX_GOD_B3
+#define IAMRX_GOD_B3 1
+#endif
 #ifndef IAMRX_GOD_ROW16
 #define IAMRX_GOD_ROW16 0
 #endif
@@ -1080,7 +1085,8 @@ static void launch_final(const Layout& l, const MultiFab& q, const MultiFab* for
 }
 
 static bool use_z_kernel();
-static void godunov_pred_z(const Layout& l, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3], const GodParams* dP, bool bcs, bool ppm, const Geometry& g);
+static void godunov_pred_z(const Layout& l, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3], const GodParams* dP, bool bcs, bool ppm, const Geometry& g,
+                           bool fit);
 static void set_scheme(int scheme);
 
 void godunov_extrap_vel_to_faces(const Geometry& g, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3],
@@ -1094,7 +1100,7 @@ void godunov_extrap_vel_to_faces(const Geometry& g, const MultiFab& vel, const M
     const Layout& l = *vel.layout;
     if (use_z_kernel()) {
         godunov_pred_z(l, vel, force, umac, upload_params(make_params(g, dt, 3, bc, nullptr, true, use_forces_in_trans, force != nullptr, false)),
-                       !(g.periodic[0] && g.periodic[1] && g.periodic[2]), scheme == 1, g);
+                       !(g.periodic[0] && g.periodic[1] && g.periodic[2]), scheme == 1, g, use_forces_in_trans);
         return;
     }
     MultiFab ad[3], e0[3], sl[3];
@@ -1467,7 +1473,9 @@ __global__ void __launch_bounds__(NTH) k_godunov_tile(const BoxD* __restrict__ b
 //   stage B  C_{x|y}(P), C_{y|x}(P), C_{z|x}(P), C_{z|y}(P)  and  C_{x|z}(P-1), C_{y|z}(P-1)   (these need E_z of the faces P-1, P)
 //   stage C  final states of the x- and y-faces of plane P-1 and of the z-face P
 //   stage D  fluxes and aofs of plane P-1 (the x / y states of the high faces come from the neighbour threads through LDS)
-// Four barriers per plane; all array offsets of a thread are loop invariants.  HBM sees the state (1.6x for the in-plane halo + the
+// Three barriers per plane: stage 0 of plane P+1 runs behind stage C of plane P, in front of the barrier between C and D (the mac /
+// force / divu rings have three slots for that, the final x / y states planes of their own; IAMRX_GOD_B3 = 0: stage 0 at the top of the
+// iteration with a barrier of its own, two-slot rings).  All array offsets of a thread are loop invariants.  HBM sees the state (1.6x for the in-plane halo + the
 // own column), mac, forcing, divu and aofs.  Arithmetic: slope4v / trans_bc_v / corner_core / final_core = the expressions of the
 // multi-pass kernels above, which remain as the PPM path and as the reference of tests/test_gpu_godunov_fused.py.
 struct GodTabs3 { const FabD* t[3]; };
@@ -1584,17 +1592,38 @@ static GodTileList god_tile_lists(const Layout& l, const Geometry& g, int TX, in
     cache.push_back(e);
     return GodTileList{{e.d[0], e.d[1]}, {e.n[0], e.n[1]}, {e.xc[0], e.xc[1]}};
 }
-template <int TX, int TY, int NT, int WPE, bool BCS, bool PPM>
+//
+// Specialised instantiations (IAMRX_GODUNOV_SPEC, default 1).  The flags that are uniform over a launch are template parameters; -1 keeps
+// the flag a run-time value (the kernel as it was: the fallback for every combination not listed, and IAMRX_GODUNOV_SPEC = 0):
+//   FRC  forcing: 0 none, 1 late (use_forces_in_trans = 0), 2 early         DVU  divu: 0 absent, 1 present
+//   OUT  bit 0: edge states are stored, bit 1: fluxes are stored             CNS  0 convective, 1 conservative form
+// A launch runs the components of ONE form: blockIdx.z indexes the component table `comps`, and a call with components of both forms
+// (velocity and tracer convective, density conservative) issues one launch per form -- a dispatch inside one kernel would give every
+// component the registers of the conservative body.  The LDS planes of the forcing and of divu exist only where the flag can be set.
+// Instantiated (14 x 14 tiles, PLM; every one with BCS = false and BCS = true, convective and conservative): what runs with default
+// inputs take -- there the forcing is always present and late, and divu is absent unless the run has a temperature equation (do_temp):
+//   k_god_z   FRC 1, DVU 0 | 1, OUT 0   a level without a coarser or a finer one (TaylorGreen, LidDrivenCavity)
+//   k_god_z   FRC 1, DVU 0 | 1, OUT 2   a level of a hierarchy: the fluxes go to the flux registers
+//   k_pred_z  FRC 1
+// (DVU 1 is the DVU 0 body plus the divu terms: with an array of zeros it gives the doubles of DVU 0, tests/test_gpu_godunov_spec.py.)
+// Everything else (early or no forcing, edge outputs -- the MAC sync --, PPM, 16 x 8 tiles) runs the run-time kernel.
+struct GodComps { int c[GOD_MAXC]; };
+template <int TX, int TY, int NT, int WPE, bool BCS, bool PPM, int FRC = -1, int DVU = -1, int OUT = -1, int CNS = -1>
 __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxes, const FabD* __restrict__ qt, const FabD* __restrict__ ft,
     const FabD* __restrict__ divut, const FabD* __restrict__ uxt, const FabD* __restrict__ uyt, const FabD* __restrict__ uzt,
     const FabD* __restrict__ aofst, int acomp, GodTabs3 edge_t, GodTabs3 flux_t, const GodParams* __restrict__ Pp,
-    int ntx, int nty, GodChunks zc, const int4* __restrict__ tiles, int ntiles, int xcd_cnt)
+    int ntx, int nty, GodChunks zc, const int4* __restrict__ tiles, int ntiles, int xcd_cnt, GodComps comps)
 {
     constexpr int PW = TX + 2, PH = TY + 2, PS = PW * PH, QW = TX + 6, QH = TY + 6, QS = QW * QH;
     constexpr int NQ = (QS + NT - 1) / NT;
     static_assert(NT >= PS, "one thread per column of the grown tile");
+    constexpr int FRS = FRC != 0 ? PS : 1, DVS = DVU != 0 ? PS : 1;
     __shared__ double Qb[QS + QW];      // one spare row in front: the (unused) slope of the cell below the grown tile reads it
-    __shared__ double MX[2][PS], MY[2][PS], MZ[2][PS], FR[2][PS], DV[2][PS];
+    // B3 (IAMRX_GOD_B3): three barriers per plane -- the registers of plane P+1 go to LDS behind stage C of plane P, in front of the barrier
+    // that is there anyway: a third slot for the rings stage C still reads, planes of their own for the x / y states of stage D
+    constexpr bool B3 = IAMRX_GOD_B3 != 0;
+    constexpr int MR = B3 ? 3 : 2, XS = B3 ? PS : 1;
+    __shared__ double MX[MR][PS], MY[MR][PS], MZ[MR][PS], FR[MR][FRS], DV[MR][DVS], XE[XS], YE[XS];
     __shared__ double EX[2][PS], EY[2][PS], EZ[2][PS];
     __shared__ double CZX[2][PS], CZY[2][PS], CXY[2][PS], CYX[2][PS], CXZ[PS], CYZ[PS];
     double* const Q = Qb + QW;
@@ -1612,7 +1641,7 @@ __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxe
     const int tx0 = b.lo[0] + tix * TX, ty0 = b.lo[1] + tiy * TY, k0 = b.lo[2] + zc.start[kci];
     if (tx0 > b.hi[0] || ty0 > b.hi[1] || k0 > b.hi[2]) return;
     const int txe = min(tx0 + TX - 1, b.hi[0]), tye = min(ty0 + TY - 1, b.hi[1]), k1 = min(b.lo[2] + zc.start[kci + 1] - 1, b.hi[2]);
-    const int n = blockIdx.z;
+    const int n = comps.c[blockIdx.z];
     const int tid = threadIdx.x;
     const int li = tid % PW, lj = tid / PW;
     const bool act = tid < PS && tx0 - 1 + li <= txe + 1 && ty0 - 1 + lj <= tye + 1;
@@ -1626,9 +1655,10 @@ __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxe
     const int qo = (ci - (tx0 - 3)) + QW * (cj - (ty0 - 3));
     const bool in_tile = act && ci >= tx0 && ci <= txe && cj >= ty0 && cj <= tye;
 
-    const bool has_force = P.has_force != 0, has_divu = P.has_divu != 0, fit = P.fit != 0, is_vel = P.is_velocity != 0;
+    const bool has_force = FRC < 0 ? P.has_force != 0 : FRC > 0, has_divu = DVU < 0 ? P.has_divu != 0 : DVU > 0;
+    const bool fit = FRC < 0 ? P.fit != 0 : FRC == 2, is_vel = P.is_velocity != 0;
     const bool early_force = fit && has_force, late_force = !fit && has_force;
-    const bool conserv = P.iconserv[n] != 0;
+    const bool conserv = CNS < 0 ? P.iconserv[n] != 0 : CNS > 0;
     const double dt = P.dt, hdt = 0.5 * dt, dt3 = dt / 3.0;
     const double dx0 = P.dx[0], dx1 = P.dx[1], dx2 = P.dx[2];
     const double dtdx0 = dt / dx0, dtdx1 = dt / dx1, dtdx2 = dt / dx2;
@@ -1680,17 +1710,45 @@ __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxe
     const double ax = dx1 * dx2, ay = dx2 * dx0, az = dx0 * dx1, qvol = 1.0 / (dx0 * dx1 * dx2);
     const double rdx0 = 1.0 / dx0, rdx1 = 1.0 / dx1, rdx2 = 1.0 / dx2;
     (void)rdx0; (void)rdx1; (void)rdx2;
-    const bool store_edge = edge_t.t[0] != nullptr, store_flux = flux_t.t[0] != nullptr;
+    const bool store_edge = OUT < 0 ? edge_t.t[0] != nullptr : (OUT & 1) != 0, store_flux = OUT < 0 ? flux_t.t[0] != nullptr : (OUT & 2) != 0;
+    // outputs: pointers of the own column at plane k0 - 2, moved on by one plane per iteration (the descriptors stay out of the plane loop)
+    const long asz = (long)aofs.n[0] * aofs.n[1];
+    auto aop = aofs.gp() + aofs.off(ci, cj, k0 - 2) + aofs.cs * (acomp + n);
+    using GP = decltype(aofs.gp());
+    GP eo0 = nullptr, eo1 = nullptr, eo2 = nullptr, fo0 = nullptr, fo1 = nullptr, fo2 = nullptr;
+    long esz0 = 0, esz1 = 0, esz2 = 0, fsz0 = 0, fsz1 = 0, fsz2 = 0;
+    if (store_edge) {
+        const FabD e0 = edge_t.t[0][fab], e1 = edge_t.t[1][fab], e2 = edge_t.t[2][fab];
+        esz0 = (long)e0.n[0] * e0.n[1]; esz1 = (long)e1.n[0] * e1.n[1]; esz2 = (long)e2.n[0] * e2.n[1];
+        eo0 = e0.gp() + e0.off(ci, cj, k0 - 2) + e0.cs * n; eo1 = e1.gp() + e1.off(ci, cj, k0 - 2) + e1.cs * n;
+        eo2 = e2.gp() + e2.off(ci, cj, k0 - 2) + e2.cs * n;
+    }
+    if (store_flux) {
+        const FabD f0 = flux_t.t[0][fab], f1 = flux_t.t[1][fab], f2 = flux_t.t[2][fab];
+        fsz0 = (long)f0.n[0] * f0.n[1]; fsz1 = (long)f1.n[0] * f1.n[1]; fsz2 = (long)f2.n[0] * f2.n[1];
+        fo0 = f0.gp() + f0.off(ci, cj, k0 - 2) + f0.cs * n; fo1 = f1.gp() + f1.off(ci, cj, k0 - 2) + f1.cs * n;
+        fo2 = f2.gp() + f2.off(ci, cj, k0 - 2) + f2.cs * n;
+    }
 
-    int it = 0;
+    // prefetched registers -> LDS: the mac / force / divu ring slot m and the state plane
+    auto stage0 = [&](int m) {
+        if (act) {
+            MX[m][o] = pmx; MY[m][o] = pmy; MZ[m][o] = pmz;
+            if constexpr (FRC != 0) FR[m][o] = pfr;
+            if constexpr (DVU != 0) DV[m][o] = pdv;
+        }
+#pragma unroll
+        for (int r = 0; r < NQ; ++r) { const int e = tid + r * NT; if (e < QS) Q[e] = pQ[r]; }
+    };
+    if constexpr (B3) { stage0(0); __syncthreads(); }
+    int it = 0, ms = 0, msp = B3 ? 2 : 1, msn = 1;
+    (void)msn;
     for (int Pk = k0 - 1; Pk <= k1 + 1; ++Pk, ++it) {
         const int s = it & 1, sp = s ^ 1;
         // ---------------- stage 0
+        if constexpr (!B3) stage0(ms);
         r0 = r1v; r1v = r2; r2 = r3; r3 = r4; r4 = pq;
         const double mx0 = pmx, my0 = pmy, mz0 = pmz, fr0 = pfr, dv0 = pdv;
-        if (act) { MX[s][o] = mx0; MY[s][o] = my0; MZ[s][o] = mz0; FR[s][o] = fr0; DV[s][o] = dv0; }
-#pragma unroll
-        for (int r = 0; r < NQ; ++r) { const int e = tid + r * NT; if (e < QS) Q[e] = pQ[r]; }
         if (Pk <= k1) {
             qcol += qsz; uxp += uxsz; uyp += uysz; uzp += uzsz; frp += fsz; dvp += dsz;
             if (act) {
@@ -1701,7 +1759,7 @@ __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxe
 #pragma unroll
             for (int r = 0; r < NQ; ++r) { qpo[r] += qsz; pQ[r] = qpv[r] ? q.gp()[qpo[r]] : 0.; }
         }
-        __syncthreads();
+        if constexpr (!B3) __syncthreads();
         // ---------------- stage A: pass 1
         double xl0, xh0, yl0, yh0, zl, zh, qxm0, qym0;
         {
@@ -1722,7 +1780,7 @@ __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxe
             xh0 = c0 + 0.5 * (-1.0 - mx0 * dtdx0) * slh;
             xl0 = a1 + 0.5 * (1.0 - mx0 * dtdx0) * sll;
             }
-            if (early_force) { xl0 += hdt * FR[s][oxm]; xh0 += hdt * fr0; }
+            if (early_force) { xl0 += hdt * FR[ms][oxm]; xh0 += hdt * fr0; }
             if (np0) trans_bc_v(a1, c0, ci, nv0, xl0, xh0, bl0, bh0, dl0, dh0);
             if (act) EX[s][o] = upwind_fu(mx0, xl0, xh0);
         }
@@ -1740,7 +1798,7 @@ __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxe
             yh0 = c0 + 0.5 * (-1.0 - my0 * dtdx1) * slh;
             yl0 = a1 + 0.5 * (1.0 - my0 * dtdx1) * sll;
             }
-            if (early_force) { yl0 += hdt * FR[s][oym]; yh0 += hdt * fr0; }
+            if (early_force) { yl0 += hdt * FR[ms][oym]; yh0 += hdt * fr0; }
             if (np1) trans_bc_v(a1, c0, cj, nv1, yl0, yh0, bl1, bh1, dl1, dh1);
             if (act) EY[s][o] = upwind_fu(my0, yl0, yh0);
         }
@@ -1765,12 +1823,12 @@ __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxe
         __syncthreads();
         // ---------------- stage B: corner coupling
         {
-            const double myA = MY[s][oxm], myB = MY[s][oxm_yp], myD = MY[s][oyp];
-            const double mxA = MX[s][oym], mxB = MX[s][oxp_ym], mxD = MX[s][oxp];
-            const double mxp1 = MX[sp][oxp], myp1 = MY[sp][oyp];
-            const double mzxm1 = MZ[sp][oxm], mzxm0 = MZ[s][oxm], mzym1 = MZ[sp][oym], mzym0 = MZ[s][oym];
-            const double dvxm0 = has_divu ? DV[s][oxm] : 0., dvym0 = has_divu ? DV[s][oym] : 0.;
-            const double dvxm1 = has_divu ? DV[sp][oxm] : 0., dvym1 = has_divu ? DV[sp][oym] : 0.;
+            const double myA = MY[ms][oxm], myB = MY[ms][oxm_yp], myD = MY[ms][oyp];
+            const double mxA = MX[ms][oym], mxB = MX[ms][oxp_ym], mxD = MX[ms][oxp];
+            const double mxp1 = MX[msp][oxp], myp1 = MY[msp][oyp];
+            const double mzxm1 = MZ[msp][oxm], mzxm0 = MZ[ms][oxm], mzym1 = MZ[msp][oym], mzym0 = MZ[ms][oym];
+            const double dvxm0 = has_divu ? DV[ms][oxm] : 0., dvym0 = has_divu ? DV[ms][oym] : 0.;
+            const double dvxm1 = has_divu ? DV[msp][oxm] : 0., dvym1 = has_divu ? DV[msp][oym] : 0.;
             // x-face corrected by y, plane P
             const double cxy = corner_core(xl0, xh0, qxm0, r2, mx0, myA, myB, my0, myD, EY[s][oxm], EY[s][oxm_yp], EY[s][o], EY[s][oyp],
                                            dvxm0, dv0, conserv, co1, dt3, dx1, np0, nv0, ci, bl0, bh0, dl0, dh0);
@@ -1793,29 +1851,31 @@ __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxe
         // ---------------- stage C: final edge states: x, y of plane P-1; z of face P
         double Xe, Ye, Ze, uxh, uyh;
         {
-            const double mxp1 = MX[sp][oxp], myp1 = MY[sp][oyp], mxp0 = MX[s][oxp], myp0 = MY[s][oyp];
+            const double mxp1 = MX[msp][oxp], myp1 = MY[msp][oyp], mxp0 = MX[ms][oxp], myp0 = MY[ms][oyp];
             uxh = mxp1; uyh = myp1;
-            const double mzxm1 = MZ[sp][oxm], mzxm0 = MZ[s][oxm], mzym1 = MZ[sp][oym], mzym0 = MZ[s][oym];
-            Xe = final_core<false>(xl1, xh1, mx1, MY[sp][oxm], MY[sp][oxm_yp], my1, myp1, mzxm1, mzxm0, mz1, mz0,
+            const double mzxm1 = MZ[msp][oxm], mzxm0 = MZ[ms][oxm], mzym1 = MZ[msp][oym], mzym0 = MZ[ms][oym];
+            Xe = final_core<false>(xl1, xh1, mx1, MY[msp][oxm], MY[msp][oxm_yp], my1, myp1, mzxm1, mzxm0, mz1, mz0,
                             CYZ[oxm], CYZ[oxm_yp], CYZ[o], CYZ[oyp], CZY[sp][oxm], CZY[s][oxm], CZY[sp][o], CZY[s][o],
-                            qxm1, r1v, late_force ? FR[sp][oxm] : 0., fr1, has_divu ? DV[sp][oxm] : 0., dv1,
+                            qxm1, r1v, late_force ? FR[msp][oxm] : 0., fr1, has_divu ? DV[msp][oxm] : 0., dv1,
                             conserv, has_divu, late_force, dt, dx1, dx2, np0, nv0, ci, bl0, bh0, dl0, dh0);
-            Ye = final_core<false>(yl1, yh1, my1, MX[sp][oym], MX[sp][oxp_ym], mx1, mxp1, mzym1, mzym0, mz1, mz0,
+            Ye = final_core<false>(yl1, yh1, my1, MX[msp][oym], MX[msp][oxp_ym], mx1, mxp1, mzym1, mzym0, mz1, mz0,
                             CXZ[oym], CXZ[oxp_ym], CXZ[o], CXZ[oxp], CZX[sp][oym], CZX[s][oym], CZX[sp][o], CZX[s][o],
-                            qym1, r1v, late_force ? FR[sp][oym] : 0., fr1, has_divu ? DV[sp][oym] : 0., dv1,
+                            qym1, r1v, late_force ? FR[msp][oym] : 0., fr1, has_divu ? DV[msp][oym] : 0., dv1,
                             conserv, has_divu, late_force, dt, dx0, dx2, np1, nv1, cj, bl1, bh1, dl1, dh1);
             Ze = final_core<false>(zl, zh, mz0, mx1, mxp1, mx0, mxp0, my1, myp1, my0, myp0,
                             CXY[sp][o], CXY[sp][oxp], CXY[s][o], CXY[s][oxp], CYX[sp][o], CYX[sp][oyp], CYX[s][o], CYX[s][oyp],
                             r1v, r2, fr1, fr0, dv1, dv0,
                             conserv, has_divu, late_force, dt, dx0, dx1, np2, nv2, Pk, bl2, bh2, dl2, dh2);
             // x / y states for the neighbour threads: the E_z / E_x slots of face / plane P-1 are free from here on
-            if (act) { EZ[sp][o] = Xe; EX[sp][o] = Ye; }
+            if constexpr (B3) { if (act) { XE[o] = Xe; YE[o] = Ye; } }
+            else if (act) { EZ[sp][o] = Xe; EX[sp][o] = Ye; }
         }
+        if constexpr (B3) { if (Pk <= k1) stage0(msn); }
         __syncthreads();
         // ---------------- stage D: plane P-1
         {
             const int k = Pk - 1;
-            const double exh = EZ[sp][oxp], eyh = EX[sp][oyp];
+            const double exh = B3 ? XE[oxp] : EZ[sp][oxp], eyh = B3 ? YE[oyp] : EX[sp][oyp];
             if (act && k >= k0 && k <= k1) {
                 const double fxl = Xe * mx1 * ax, fyl = Ye * my1 * ay, fzl = Zprev * mz1 * az;
                 if (in_tile) {
@@ -1827,31 +1887,36 @@ __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxe
                         qavg *= 1.0 / 6.0;
                         upd += qavg * divum;
                     }
-                    aofs(ci, cj, k, acomp + n) = -upd;
+                    aop[0] = -upd;
                 }
                 // faces: every face is written by the tile on its high side, the faces on the high end of the box by the last tile
                 const bool wx = cj >= ty0 && cj <= tye && ci >= tx0 && (ci <= txe || ci == b.hi[0] + 1);
                 const bool wy = ci >= tx0 && ci <= txe && cj >= ty0 && (cj <= tye || cj == b.hi[1] + 1);
                 if (store_edge) {
-                    if (wx) edge_t.t[0][fab](ci, cj, k, n) = Xe;
-                    if (wy) edge_t.t[1][fab](ci, cj, k, n) = Ye;
-                    if (in_tile) edge_t.t[2][fab](ci, cj, k, n) = Zprev;
+                    if (wx) eo0[0] = Xe;
+                    if (wy) eo1[0] = Ye;
+                    if (in_tile) eo2[0] = Zprev;
                 }
                 if (store_flux) {
-                    if (wx) flux_t.t[0][fab](ci, cj, k, n) = fxl;
-                    if (wy) flux_t.t[1][fab](ci, cj, k, n) = fyl;
-                    if (in_tile) flux_t.t[2][fab](ci, cj, k, n) = fzl;
+                    if (wx) fo0[0] = fxl;
+                    if (wy) fo1[0] = fyl;
+                    if (in_tile) fo2[0] = fzl;
                 }
             }
             if (in_tile && k == b.hi[2]) {
                 // the z-face on the high end of the box
-                if (store_edge) edge_t.t[2][fab](ci, cj, k + 1, n) = Ze;
-                if (store_flux) flux_t.t[2][fab](ci, cj, k + 1, n) = Ze * mz0 * az;
+                if (store_edge) eo2[esz2] = Ze;
+                if (store_flux) fo2[fsz2] = Ze * mz0 * az;
             }
         }
+        aop += asz;
+        if (store_edge) { eo0 += esz0; eo1 += esz1; eo2 += esz2; }
+        if (store_flux) { fo0 += fsz0; fo1 += fsz1; fo2 += fsz2; }
         xl1 = xl0; xh1 = xh0; yl1 = yl0; yh1 = yh0; qxm1 = qxm0; qym1 = qym0;
         mx1 = mx0; my1 = my0; mz1 = mz0; fr1 = fr0; dv1 = dv0; slz1 = slz0; Zprev = Ze;
         smz1 = smz0; spz1 = spz0;
+        if constexpr (B3) { msp = ms; ms = msn; msn = msn == 2 ? 0 : msn + 1; }
+        else { ms = sp; msp = s; }
     }
 }
 
@@ -1861,11 +1926,21 @@ static bool use_z_kernel()
     return tune("GODUNOV_Z", 1) != 0;
 }
 
-template <int TX, int TY, int WPE, bool BCS, bool PPM>
-static void launch_god_z(const Layout& l, MultiFab& aofs, int acomp, const MultiFab& S, int ncomp, const MultiFab* force, const MultiFab* divu,
-                         MultiFab* const umac[3], MultiFab* const edge_out[3], MultiFab* const flux_out[3], const GodParams* dP, int sel = 0,
-                         const Geometry* sg = nullptr)
+// IAMRX_GODUNOV_SPEC=0 selects the run-time kernels where a specialised instantiation exists (read at every call:
+// tests/test_gpu_godunov_spec.py compares the two)
+static bool use_spec_kernels()
 {
+    return tune("GODUNOV_SPEC", 1) != 0;
+}
+
+static bool g_god_probe_open = false;     // the probe spans the launches of one call (one per form of the components)
+// ncomp components of the launch: blockIdx.z -> comps.c[]
+template <int TX, int TY, int WPE, bool BCS, bool PPM, int FRC = -1, int DVU = -1, int OUT = -1, int CNS = -1>
+static void launch_god_z(const Layout& l, MultiFab& aofs, int acomp, const MultiFab& S, int ncomp, const GodComps& comps, const MultiFab* force,
+                         const MultiFab* divu, MultiFab* const umac[3], MultiFab* const edge_out[3], MultiFab* const flux_out[3],
+                         const GodParams* dP, int sel = 0, const Geometry* sg = nullptr, bool probe_begin = true, bool probe_end = true)
+{
+    if (ncomp == 0) return;
     constexpr int NT = (((TX + 2) * (TY + 2)) + 63) / 64 * 64;
     const int ntx = (l.max_len[0] + TX - 1) / TX, nty = (l.max_len[1] + TY - 1) / TY;
     const int kc_env = (int)tune("GODUNOV_ZKC", 0);
@@ -1885,11 +1960,40 @@ static void launch_god_z(const Layout& l, MultiFab& aofs, int acomp, const Multi
     GodTabs3 et{{nullptr, nullptr, nullptr}}, ftb{{nullptr, nullptr, nullptr}};
     if (edge_out && edge_out[0]) for (int d = 0; d < 3; ++d) et.t[d] = edge_out[d]->d_tab;
     if (flux_out && flux_out[0]) for (int d = 0; d < 3; ++d) ftb.t[d] = flux_out[d]->d_tab;
-    const bool rec = kernel_probe_begin(PROBE_GOD_Z, (long)l.max_len[0] * l.max_len[1] * l.max_len[2]);
-    hipLaunchKernelGGL((k_god_z<TX, TY, NT, WPE, BCS, PPM>), grid, dim3(NT), 0, Context::get().stream, l.d_boxes, S.d_tab, force ? force->d_tab : nullptr,
-                       divu ? divu->d_tab : nullptr, umac[0]->d_tab, umac[1]->d_tab, umac[2]->d_tab, aofs.d_tab, acomp, et, ftb, dP,
-                       ntx, nty, zc, tiles, ntiles, xcd_cnt);
-    if (rec) kernel_probe_end(PROBE_GOD_Z);
+    if (probe_begin) g_god_probe_open = kernel_probe_begin(PROBE_GOD_Z, (long)l.max_len[0] * l.max_len[1] * l.max_len[2]);
+    hipLaunchKernelGGL((k_god_z<TX, TY, NT, WPE, BCS, PPM, FRC, DVU, OUT, CNS>), grid, dim3(NT), 0, Context::get().stream, l.d_boxes, S.d_tab,
+                       force ? force->d_tab : nullptr, divu ? divu->d_tab : nullptr, umac[0]->d_tab, umac[1]->d_tab, umac[2]->d_tab, aofs.d_tab,
+                       acomp, et, ftb, dP, ntx, nty, zc, tiles, ntiles, xcd_cnt, comps);
+    if (probe_end && g_god_probe_open) { kernel_probe_end(PROBE_GOD_Z); g_god_probe_open = false; }
+    tuning_count(CNS < 0 ? "GODUNOV_Z_RUNTIME_LAUNCHES" : (CNS ? "GODUNOV_Z_SPEC_CONS_LAUNCHES" : "GODUNOV_Z_SPEC_CONV_LAUNCHES"));
+}
+
+// one call of the fused advection kernel on the tiles `sel`: the specialised instantiations where the call's flags have one (the list is
+// in front of k_god_z) -- one launch per form of the components --, the run-time kernel otherwise
+template <int TX, int TY, int WPE, bool BCS, bool PPM>
+static void god_z_call(const Layout& l, MultiFab& aofs, int acomp, const MultiFab& S, int ncomp, const int* iconserv, bool fit, const MultiFab* force,
+                       const MultiFab* divu, MultiFab* const umac[3], MultiFab* const edge_out[3], MultiFab* const flux_out[3],
+                       const GodParams* dP, int sel, const Geometry* sg)
+{
+    if constexpr (TX == 14 && TY == 14 && !PPM) {
+        const bool se = edge_out && edge_out[0], sf = flux_out && flux_out[0];
+        if (use_spec_kernels() && force && !fit && !se) {
+            GodComps cv{}, cs{};
+            int ncv = 0, ncs = 0;
+            for (int n = 0; n < ncomp; ++n) { if (iconserv && iconserv[n]) cs.c[ncs++] = n; else cv.c[ncv++] = n; }
+#define IAMRX_GZF(DVU, OUT, CNS, NC, TAB, PB, PE) launch_god_z<TX, TY, WPE, BCS, PPM, 1, DVU, OUT, CNS>(l, aofs, acomp, S, NC, TAB, force, divu, umac, nullptr, \
+                                                                                                         flux_out, dP, sel, sg, PB, PE)
+#define IAMRX_GZO(DVU, OUT) do { IAMRX_GZF(DVU, OUT, 0, ncv, cv, true, ncs == 0); IAMRX_GZF(DVU, OUT, 1, ncs, cs, ncv == 0, true); } while (0)
+            if (divu) { if (sf) IAMRX_GZO(1, 2); else IAMRX_GZO(1, 0); }
+            else { if (sf) IAMRX_GZO(0, 2); else IAMRX_GZO(0, 0); }
+#undef IAMRX_GZO
+#undef IAMRX_GZF
+            return;
+        }
+    }
+    GodComps all{};
+    for (int n = 0; n < ncomp; ++n) all.c[n] = n;
+    launch_god_z<TX, TY, WPE, BCS, PPM>(l, aofs, acomp, S, ncomp, all, force, divu, umac, edge_out, flux_out, dP, sel, sg);
 }
 
 // -------------------------------------------------------------------------------- fused z-marching velocity prediction (PLM)
@@ -1897,8 +2001,8 @@ static void launch_god_z(const Layout& l, MultiFab& aofs, int acomp, const Multi
 // direction, the advective velocities ad_x / ad_y / ad_z (upwinded normal components) take the place of the mac velocities and live
 // in LDS like the pass-1 states; the final x- / y- / z-face state is that of u / v / w, so the corner-coupled state C_{T|O} is formed
 // for the component 3-T-O only: E_x(v,w), E_y(u,w), E_z(u,v), six corner arrays, three final states per column and plane.
-// Three barriers per plane (the final states go straight to umac).
-template <int TX, int TY, int NT, bool BCS, bool PPM>
+// Three barriers per plane (the final states go straight to umac).  FRC: the forcing as a template flag, see k_god_z.
+template <int TX, int TY, int NT, bool BCS, bool PPM, int FRC = -1>
 __global__ void __launch_bounds__(NT, 2) k_pred_z(const BoxD* __restrict__ boxes, const FabD* __restrict__ qt, const FabD* __restrict__ ft,
     const FabD* __restrict__ uxt, const FabD* __restrict__ uyt, const FabD* __restrict__ uzt, const GodParams* __restrict__ Pp,
     int ntx, int nty, GodChunks zc, const int4* __restrict__ tiles, int ntiles, int xcd_cnt)
@@ -1907,7 +2011,8 @@ __global__ void __launch_bounds__(NT, 2) k_pred_z(const BoxD* __restrict__ boxes
     constexpr int NQ = (QS + NT - 1) / NT;
     static_assert(NT >= PS, "one thread per column of the grown tile");
     __shared__ double Qb[3][QS + QW];
-    __shared__ double AX[2][PS], AY[2][PS], AZ[2][PS], FR[2][3][PS];
+    constexpr int FRS = FRC != 0 ? PS : 1;
+    __shared__ double AX[2][PS], AY[2][PS], AZ[2][PS], FR[2][3][FRS];
     __shared__ double EXv[2][PS], EXw[2][PS], EYu[2][PS], EYw[2][PS], EZu[2][PS], EZv[2][PS];
     __shared__ double CZX[2][PS], CZY[2][PS], CXY[2][PS], CYX[2][PS], CXZ[PS], CYZ[PS];
     const GodParams& P = *Pp;
@@ -1937,7 +2042,7 @@ __global__ void __launch_bounds__(NT, 2) k_pred_z(const BoxD* __restrict__ boxes
     const bool wx = act && cj >= ty0 && cj <= tye && ci >= tx0 && (ci <= txe || ci == b.hi[0] + 1);
     const bool wy = act && ci >= tx0 && ci <= txe && cj >= ty0 && (cj <= tye || cj == b.hi[1] + 1);
 
-    const bool has_force = P.has_force != 0, fit = P.fit != 0;
+    const bool has_force = FRC < 0 ? P.has_force != 0 : FRC > 0, fit = FRC < 0 ? P.fit != 0 : FRC == 2;
     const bool early_force = fit && has_force, late_force = !fit && has_force;
     const double dt = P.dt, hdt = 0.5 * dt, dt3 = dt / 3.0;
     const double dx0 = P.dx[0], dx1 = P.dx[1], dx2 = P.dx[2];
@@ -1989,7 +2094,7 @@ __global__ void __launch_bounds__(NT, 2) k_pred_z(const BoxD* __restrict__ boxes
         for (int c = 0; c < 3; ++c) {
             rz[c][0] = rz[c][1]; rz[c][1] = rz[c][2]; rz[c][2] = rz[c][3]; rz[c][3] = rz[c][4]; rz[c][4] = pq[c];
             fr0[c] = pfr[c];
-            if (act && has_force) FR[s][c][o] = fr0[c];
+            if constexpr (FRC != 0) { if (act && has_force) FR[s][c][o] = fr0[c]; }
 #pragma unroll
             for (int r = 0; r < NQ; ++r) { const int e = tid + r * NT; if (e < QS) Qb[c][QW + e] = pQ[c][r]; }
         }
@@ -2157,7 +2262,7 @@ __global__ void __launch_bounds__(NT, 2) k_pred_z(const BoxD* __restrict__ boxes
     }
 }
 
-template <int TX, int TY, bool BCS, bool PPM>
+template <int TX, int TY, bool BCS, bool PPM, int FRC = -1>
 static void launch_pred_z(const Layout& l, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3], const GodParams* dP, int sel = 0,
                           const Geometry* sg = nullptr)
 {
@@ -2178,12 +2283,14 @@ static void launch_pred_z(const Layout& l, const MultiFab& vel, const MultiFab* 
     const int xcd_cnt = sel != 0 ? lx : (total >= 64 ? (total + 7) / 8 : 0);
     dim3 grid((unsigned)(xcd_cnt > 0 ? 8 * xcd_cnt : total), gy, 1u);
     const bool rec = kernel_probe_begin(PROBE_PRED_Z, (long)l.max_len[0] * l.max_len[1] * l.max_len[2]);
-    hipLaunchKernelGGL((k_pred_z<TX, TY, NT, BCS, PPM>), grid, dim3(NT), 0, Context::get().stream, l.d_boxes, vel.d_tab, force ? force->d_tab : nullptr,
+    hipLaunchKernelGGL((k_pred_z<TX, TY, NT, BCS, PPM, FRC>), grid, dim3(NT), 0, Context::get().stream, l.d_boxes, vel.d_tab, force ? force->d_tab : nullptr,
                        umac[0]->d_tab, umac[1]->d_tab, umac[2]->d_tab, dP, ntx, nty, zc, tiles, ntiles, xcd_cnt);
     if (rec) kernel_probe_end(PROBE_PRED_Z);
+    tuning_count(FRC < 0 ? "PRED_Z_RUNTIME_LAUNCHES" : "PRED_Z_SPEC_LAUNCHES");
 }
 
-static void godunov_pred_z(const Layout& l, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3], const GodParams* dP, bool bcs, bool ppm, const Geometry& g)
+static void godunov_pred_z(const Layout& l, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3], const GodParams* dP, bool bcs, bool ppm, const Geometry& g,
+                           bool fit)
 {
     // 14 x 14 cells per workgroup (grown tile 16 x 16 = 256 threads, 80 KB of LDS, two workgroups per CU): 1.04 ms per 256^3 against 1.24 ms with
     // 16 x 8 (192 threads; IAMRX_GODUNOV_PTX = 16), 1.14 ms with 30 x 6 -- see the tile shapes of k_god_z below
@@ -2191,7 +2298,10 @@ static void godunov_pred_z(const Layout& l, const MultiFab& vel, const MultiFab*
     // a domain with walls: the tiles no boundary condition reaches run the plain code (sel = 1), the boundary-condition variant takes the
     // rest (sel = 2: the tiles along the walls, thin first / last z-chunks) -- IAMRX_GODUNOV_SPLIT_BC = 0: one launch of the variant
     const bool split = bcs && tune("GODUNOV_SPLIT_BC", 1) != 0;
-#define IAMRX_PZS(TX, TY, B, PPM, SEL) launch_pred_z<TX, TY, B, PPM>(l, vel, force, umac, dP, SEL, &g)
+    // the specialised instantiation (late forcing, 14 x 14 tiles, PLM: the list in front of k_god_z) where the call has one
+    const bool spec = use_spec_kernels() && force && !fit && !ppm && ptx != 16;
+#define IAMRX_PZS(TX, TY, B, PPM, SEL) do { if constexpr (TX == 14 && !PPM) { if (spec) { launch_pred_z<TX, TY, B, PPM, 1>(l, vel, force, umac, dP, SEL, &g); break; } } \
+                                            launch_pred_z<TX, TY, B, PPM>(l, vel, force, umac, dP, SEL, &g); } while (0)
 #define IAMRX_PZP(TX, TY, PPM) do { if (!bcs) IAMRX_PZS(TX, TY, false, PPM, 0); else if (!split) IAMRX_PZS(TX, TY, true, PPM, 0); \
                                     else { IAMRX_PZS(TX, TY, false, PPM, 1); IAMRX_PZS(TX, TY, true, PPM, 2); } } while (0)
 #define IAMRX_PZ(TX, TY) do { if (ppm) IAMRX_PZP(TX, TY, true); else IAMRX_PZP(TX, TY, false); } while (0)
@@ -2482,7 +2592,8 @@ void godunov_compute_aofs(const Geometry& g, MultiFab& aofs, int acomp, const Mu
         const bool bcs = !(g.periodic[0] && g.periodic[1] && g.periodic[2]);
         // (walls: two launches, see godunov_pred_z)
         const bool split = bcs && tune("GODUNOV_SPLIT_BC", 1) != 0;
-#define IAMRX_GZS(TX, TY, W, B, PPM, SEL) launch_god_z<TX, TY, W, B, PPM>(l, aofs, acomp, S, ncomp, force, divu, umac, edge_out, flux_out, dP, SEL, &g)
+#define IAMRX_GZS(TX, TY, W, B, PPM, SEL) god_z_call<TX, TY, W, B, PPM>(l, aofs, acomp, S, ncomp, iconserv, use_forces_in_trans, force, divu, umac, \
+                                                                        edge_out, flux_out, dP, SEL, &g)
 #define IAMRX_GZP(TX, TY, W, PPM) do { if (!bcs) IAMRX_GZS(TX, TY, W, false, PPM, 0); else if (!split) IAMRX_GZS(TX, TY, W, true, PPM, 0); \
                                        else { IAMRX_GZS(TX, TY, W, false, PPM, 1); IAMRX_GZS(TX, TY, W, true, PPM, 2); } } while (0)
 #define IAMRX_GZ(TX, TY, W) do { if (ppm) IAMRX_GZP(TX, TY, W, true); else IAMRX_GZP(TX, TY, W, false); } while (0)

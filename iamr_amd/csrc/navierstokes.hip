@@ -903,7 +903,8 @@ void NavierStokes::velocity_advection(double dt_)
     MultiFab visc_s;
     const MultiFab& visc = old_visc_or_zero(visc_s);
     MultiFab tf(layout, cell_type(), 3, 1), divu;
-    divu_half(divu, dt_, 1, true);                               // NavierStokesBase.cpp:3377, 3421-3424
+    if (have_divu) divu_half(divu, dt_, 1, true);                // NavierStokesBase.cpp:3377, 3421-3424
+    const MultiFab* dvp = have_divu ? &divu : nullptr;           // no divu: no array of zeros (every term it enters is a product with 0)
     {
         const FabD *tt = tf.d_tab, *vt = visc.d_tab, *gt = Gp[1 - pnew].d_tab, *st = Smf.d_tab;
         const double grav = p.gravity;
@@ -927,10 +928,10 @@ void NavierStokes::velocity_advection(double dt_)
         MultiFab fl[3];
         MultiFab* flp[3];
         for (int d = 0; d < 3; ++d) { fl[d].define(layout, face_type(d), 3, 0); flp[d] = &fl[d]; }
-        godunov_compute_aofs(g, aofs, Xvel, Umf, 3, &tf, &divu, um, iconserv, dt_, bc_vel, true, p.use_forces_in_trans != 0, nullptr, flp, p.use_ppm);
+        godunov_compute_aofs(g, aofs, Xvel, Umf, 3, &tf, dvp, um, iconserv, dt_, bc_vel, true, p.use_forces_in_trans != 0, nullptr, flp, p.use_ppm);
         adv_registers(flp, Xvel, 3, dt_);
     } else
-    godunov_compute_aofs(g, aofs, Xvel, Umf, 3, &tf, &divu, um, iconserv, dt_, bc_vel, true, p.use_forces_in_trans != 0, nullptr, nullptr, p.use_ppm);
+    godunov_compute_aofs(g, aofs, Xvel, Umf, 3, &tf, dvp, um, iconserv, dt_, bc_vel, true, p.use_forces_in_trans != 0, nullptr, nullptr, p.use_ppm);
 }
 
 void NavierStokes::scalar_advection(double dt_)
@@ -942,7 +943,8 @@ void NavierStokes::scalar_advection(double dt_)
     floor_small(Smf);
     MultiFab tf(layout, cell_type(), nscal, 1), divu;
     tf.setVal(0.0);
-    divu_half(divu, dt_, 1, true);                               // NavierStokes.cpp:712-733
+    if (have_divu) divu_half(divu, dt_, 1, true);                // NavierStokes.cpp:712-733
+    const MultiFab* dvp = have_divu ? &divu : nullptr;
     MultiFab visc(layout, cell_type(), 1, 1);
     for (int n = 1; n < nscal; ++n) {            // getForce = 0; density (n = 0) is not diffusive; keep the reference's arithmetic
         if (p.be_cn_theta != 1.0) get_visc_terms_scalar(visc, So, Density + n); else visc.setVal(0.0);
@@ -961,10 +963,10 @@ void NavierStokes::scalar_advection(double dt_)
         MultiFab fl[3];
         MultiFab* flp[3];
         for (int d = 0; d < 3; ++d) { fl[d].define(layout, face_type(d), nscal, 0); flp[d] = &fl[d]; }
-        godunov_compute_aofs(g, aofs, Density, Smf, nscal, &tf, &divu, um, iconserv, dt_, bc_scal, false, p.use_forces_in_trans != 0, nullptr, flp, p.use_ppm);
+        godunov_compute_aofs(g, aofs, Density, Smf, nscal, &tf, dvp, um, iconserv, dt_, bc_scal, false, p.use_forces_in_trans != 0, nullptr, flp, p.use_ppm);
         adv_registers(flp, Density, nscal, dt_);
     } else
-    godunov_compute_aofs(g, aofs, Density, Smf, nscal, &tf, &divu, um, iconserv, dt_, bc_scal, false, p.use_forces_in_trans != 0, nullptr, nullptr, p.use_ppm);
+    godunov_compute_aofs(g, aofs, Density, Smf, nscal, &tf, dvp, um, iconserv, dt_, bc_scal, false, p.use_forces_in_trans != 0, nullptr, nullptr, p.use_ppm);
 }
 
 // velocity_advection + scalar_advection in ONE pass of the Godunov chain over all five state components (NavierStokes.cpp:698-812 calls
@@ -1009,7 +1011,8 @@ void NavierStokes::advection_all(double dt_)
     ScalForm sf;                                 // per scalar slot: 0 convective, 1 conservative, 2 temperature
     for (int n = 0; n < MAXSCAL; ++n) sf.form[n] = (n < nscal && Density + n == Temp) ? 2 : (scal_cons[n] ? 1 : 0);
     MultiFab tf(layout, cell_type(), nstate, 1), divu;
-    divu_half(divu, dt_, 1, true);
+    if (have_divu) divu_half(divu, dt_, 1, true);
+    const MultiFab* dvp = have_divu ? &divu : nullptr;           // no divu: no array of zeros (every term it enters is a product with 0)
     {
         // the density of the forcing (velocity_advection's one-ghost-cell FillPatch of the old density) = rho_ptime (make_rho_prev_time)
         const FabD *tt = tf.d_tab, *vt = visc.d_tab, *wt = svisc.d_tab, *gt = Gp[1 - pnew].d_tab, *rt = rho_ptime.d_tab, *qt = Q.d_tab;
@@ -1049,10 +1052,10 @@ void NavierStokes::advection_all(double dt_)
         MultiFab fl[3];
         MultiFab* flp[3];
         for (int d = 0; d < 3; ++d) { fl[d].define(layout, face_type(d), nstate, 0); flp[d] = &fl[d]; }
-        godunov_compute_aofs(g, aofs, Xvel, Q, nstate, &tf, &divu, um, iconserv, dt_, bc5, true, p.use_forces_in_trans != 0, nullptr, flp, p.use_ppm);
+        godunov_compute_aofs(g, aofs, Xvel, Q, nstate, &tf, dvp, um, iconserv, dt_, bc5, true, p.use_forces_in_trans != 0, nullptr, flp, p.use_ppm);
         adv_registers(flp, Xvel, nstate, dt_);
     } else
-    godunov_compute_aofs(g, aofs, Xvel, Q, nstate, &tf, &divu, um, iconserv, dt_, bc5, true, p.use_forces_in_trans != 0, nullptr, nullptr, p.use_ppm);
+    godunov_compute_aofs(g, aofs, Xvel, Q, nstate, &tf, dvp, um, iconserv, dt_, bc5, true, p.use_forces_in_trans != 0, nullptr, nullptr, p.use_ppm);
 }
 
 // NavierStokesBase::ConservativeScalMinMax / ConvectiveScalMinMax (NavierStokesBase.cpp:4256-4368): the new value (per unit mass if
