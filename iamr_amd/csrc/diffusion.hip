@@ -112,14 +112,17 @@ MGStats diffuse_scalar(const Geometry& g, const MultiFab* S_old, const MultiFab*
 MGStats diffuse_tensor_velocity(const Geometry& g, const MultiFab* U_old, MultiFab& U_new, int rho_comp, double dt, double theta,
                                 const MultiFab& rho_half, int rho_flag, const MultiFab* visc_old_term, const MultiFab* const eta_n[3],
                                 const MultiFab* const eta_np1[3], const DomainBC bc_visc[3], const DiffusionCrse* crse,
-                                MultiFab* const tflux[3], double visc_tol, const MGOpts& o, const std::function<void(MultiFab&)>& fill_new)
+                                MultiFab* const tflux[3], double visc_tol, const MGOpts& o, const std::function<void(MultiFab&)>& fill_new,
+                                const TensorRhsReady* ready)
 {
     LayoutP layout = U_new.layout;
     // The solve runs IN PLACE on the velocity components of U_new and reads alpha from the array that holds it (views, below): U_new comes
     // with at least one ghost layer (level boundary data / initial guess); any wider ghost region is simply not touched (the kernels index
     // through the array descriptors; only the first layer is filled and read).  rho_half is read on the valid cells.
     IAMRX_ASSERT(U_new.ngrow >= 1 && (rho_flag == 1 || rho_flag == 3));
-    MultiFab Rhs(layout, cell_type(), 3, 0);
+    MultiFab rhs_own;
+    if (!ready) rhs_own.define(layout, cell_type(), 3, 0);
+    MultiFab& Rhs = ready ? *ready->rhs : rhs_own;
     const bool want_flux = tflux != nullptr && tflux[0] != nullptr;
     TensorFlux fx{{want_flux ? tflux[0] : nullptr, want_flux ? tflux[1] : nullptr, want_flux ? tflux[2] : nullptr}, 0.0, false};
     if (want_flux) for (int d = 0; d < 3; ++d) tflux[d]->setVal(0.0);
@@ -136,8 +139,10 @@ MGStats diffuse_tensor_velocity(const Geometry& g, const MultiFab* U_old, MultiF
         fx.fac = 1.0 - theta; fx.add = false;                    // computeExtensiveFluxes(..., -b/dt), b = -(1 - theta) dt
         tensor_apply(g, Rhs, Soln0, 0.0, -(1.0 - theta) * dt, nullptr, eta_n, bc_visc, 3, crse ? &cf : nullptr, want_flux ? &fx : nullptr);
     } else if (!from_visc) Rhs.setVal(0.0);
+    IAMRX_ASSERT(!ready || (from_visc && ready->rhs->layout.get() == layout.get() && ready->rhs->ncomp == 3));
     double rn3[3];
-    {
+    if (ready) for (int n = 0; n < 3; ++n) rn3[n] = ready->norm[n];
+    else {
         const FabD *nt = U_new.d_tab, *ot = U_old ? U_old->d_tab : nullptr, *rt = Rhs.d_tab, *ht = rho_half.d_tab;
         const FabD* vt = from_visc ? visc_old_term->d_tab : nullptr;
         const double va = (1.0 - theta) * dt;

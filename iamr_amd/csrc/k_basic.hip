@@ -660,35 +660,78 @@ void mf_mult(MultiFab& y, double a, int comp, int nc, int ng)
         [=] __device__(int i, int j, int k, int f, int n, double v) { yt[f](i, j, k, comp + n) = v; });
 }
 
-// y *= a on the ghost shell: per box two z-slabs (whole grown planes), two y-slabs (grown rows of the valid planes) and two x-slabs
+// point idx of the ghost shell of box b (ng layers): per box two z-slabs (whole grown planes), two y-slabs (grown rows of the valid planes)
+// and two x-slabs
+__device__ __forceinline__ void shell_ijk(const BoxD& b, int ng, long idx, int& i, int& j, int& k)
+{
+    const long nx = b.len(0), ny = b.len(1), nz = b.len(2), gx = nx + 2 * ng, gy = ny + 2 * ng;
+    const long nA = gx * gy * ng, nB = gx * ng * nz, nC = ng * ny * nz;
+    long r = idx;
+    if (r < 2 * nA) {
+        const int side = (int)(r / nA); r -= side * nA;
+        i = b.lo[0] - ng + (int)(r % gx); j = b.lo[1] - ng + (int)((r / gx) % gy);
+        k = (side ? b.hi[2] + 1 : b.lo[2] - ng) + (int)(r / (gx * gy));
+    } else if ((r -= 2 * nA) < 2 * nB) {
+        const int side = (int)(r / nB); r -= side * nB;
+        i = b.lo[0] - ng + (int)(r % gx); k = b.lo[2] + (int)(r / (gx * ng));
+        j = (side ? b.hi[1] + 1 : b.lo[1] - ng) + (int)((r / gx) % ng);
+    } else {
+        r -= 2 * nB;
+        const int side = (int)(r / nC); r -= side * nC;
+        j = b.lo[1] + (int)((r / ng) % ny); k = b.lo[2] + (int)(r / (ng * ny));
+        i = (side ? b.hi[0] + 1 : b.lo[0] - ng) + (int)(r % ng);
+    }
+}
+__device__ __forceinline__ long shell_npts(const BoxD& b, int ng)
+{
+    const long nx = b.len(0), ny = b.len(1), nz = b.len(2), gx = nx + 2 * ng, gy = ny + 2 * ng;
+    return 2 * (gx * gy * ng + gx * ng * nz + ng * ny * nz);
+}
+
+// y *= a on the ghost shell
 __global__ void __launch_bounds__(256) k_mult_shell(const BoxD* __restrict__ boxes, const FabD* __restrict__ yt, int t0, int t1, int t2, int ng, int comp, int nc, double a)
 {
     const int fab = blockIdx.y;
     BoxD b = boxes[fab];
     b.hi[0] += t0; b.hi[1] += t1; b.hi[2] += t2;
     const FabD y = yt[fab];
-    const long nx = b.len(0), ny = b.len(1), nz = b.len(2), gx = nx + 2 * ng, gy = ny + 2 * ng;
-    const long nA = gx * gy * ng, nB = gx * ng * nz, nC = ng * ny * nz;
-    const long total = 2 * (nA + nB + nC);
+    const long total = shell_npts(b, ng);
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        long r = idx;
         int i, j, k;
-        if (r < 2 * nA) {
-            const int side = (int)(r / nA); r -= side * nA;
-            i = b.lo[0] - ng + (int)(r % gx); j = b.lo[1] - ng + (int)((r / gx) % gy);
-            k = (side ? b.hi[2] + 1 : b.lo[2] - ng) + (int)(r / (gx * gy));
-        } else if ((r -= 2 * nA) < 2 * nB) {
-            const int side = (int)(r / nB); r -= side * nB;
-            i = b.lo[0] - ng + (int)(r % gx); k = b.lo[2] + (int)(r / (gx * ng));
-            j = (side ? b.hi[1] + 1 : b.lo[1] - ng) + (int)((r / gx) % ng);
-        } else {
-            r -= 2 * nB;
-            const int side = (int)(r / nC); r -= side * nC;
-            j = b.lo[1] + (int)((r / ng) % ny); k = b.lo[2] + (int)(r / (ng * ny));
-            i = (side ? b.hi[0] + 1 : b.lo[0] - ng) + (int)(r % ng);
-        }
+        shell_ijk(b, ng, idx, i, j, k);
         for (int n = 0; n < nc; ++n) y(i, j, k, comp + n) = y(i, j, k, comp + n) * a;
     }
+}
+
+// h = 0.5 * (a + b) on the ghost shell (cell-centred, component 0)
+__global__ void __launch_bounds__(256) k_half_sum_shell(const BoxD* __restrict__ boxes, const FabD* __restrict__ ht, const FabD* __restrict__ at,
+                                                        const FabD* __restrict__ bt, int ng)
+{
+    const int fab = blockIdx.y;
+    const BoxD b = boxes[fab];
+    const FabD h = ht[fab], pa = at[fab], pb = bt[fab];
+    const long total = shell_npts(b, ng);
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        int i, j, k;
+        shell_ijk(b, ng, idx, i, j, k);
+        h(i, j, k, 0) = 0.5 * (pa(i, j, k, 0) + pb(i, j, k, 0));
+    }
+}
+
+static unsigned shell_blocks(const Layout& l, const IndexType& type, int ng)
+{
+    const long nx = l.max_len[0] + type.t[0], ny = l.max_len[1] + type.t[1], nz = l.max_len[2] + type.t[2];
+    const long total = 2 * ((nx + 2 * ng) * (ny + 2 * ng) * ng + (nx + 2 * ng) * ng * nz + ng * ny * nz);
+    return (unsigned)std::min<long>((total + 255) / 256, 4096);
+}
+
+void mf_half_sum_ghosts(MultiFab& h, const MultiFab& a, const MultiFab& b, int ng)
+{
+    if (ng <= 0 || h.nlocal() == 0) return;
+    IAMRX_ASSERT(ng <= h.ngrow && ng <= a.ngrow && ng <= b.ngrow && a.layout.get() == h.layout.get() && b.layout.get() == h.layout.get());
+    const Layout& l = *h.layout;
+    hipLaunchKernelGGL(k_half_sum_shell, dim3(shell_blocks(l, h.type, ng), (unsigned)l.nlocal()), dim3(256), 0, Context::get().stream, l.d_boxes, h.d_tab,
+                       a.d_tab, b.d_tab, ng);
 }
 
 void mf_mult_ghosts(MultiFab& y, double a, int comp, int nc, int ng)
@@ -696,10 +739,7 @@ void mf_mult_ghosts(MultiFab& y, double a, int comp, int nc, int ng)
     if (!y.base || ng <= 0 || y.nlocal() == 0) return;
     IAMRX_ASSERT(ng <= y.ngrow);
     const Layout& l = *y.layout;
-    const long nx = l.max_len[0] + y.type.t[0], ny = l.max_len[1] + y.type.t[1], nz = l.max_len[2] + y.type.t[2];
-    const long total = 2 * ((nx + 2 * ng) * (ny + 2 * ng) * ng + (nx + 2 * ng) * ng * nz + ng * ny * nz);
-    const long nb = std::min<long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_mult_shell, dim3((unsigned)nb, (unsigned)l.nlocal()), dim3(256), 0, Context::get().stream, l.d_boxes, y.d_tab, y.type.t[0], y.type.t[1],
+    hipLaunchKernelGGL(k_mult_shell, dim3(shell_blocks(l, y.type, ng), (unsigned)l.nlocal()), dim3(256), 0, Context::get().stream, l.d_boxes, y.d_tab, y.type.t[0], y.type.t[1],
                        y.type.t[2], ng, comp, nc, a);
 }
 

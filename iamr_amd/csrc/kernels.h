@@ -47,6 +47,7 @@ double mf_add_scalar_norm0(MultiFab& y, double a, int comp, int ng);      // y(c
 void mf_mult(MultiFab& y, double a, int comp, int nc, int ng);
 // the same on the ng ghost layers only (the valid region is not touched): one launch over the shell of every box
 void mf_mult_ghosts(MultiFab& y, double a, int comp, int nc, int ng);
+void mf_half_sum_ghosts(MultiFab& h, const MultiFab& a, const MultiFab& b, int ng);   // h = 0.5 * (a + b) on the ghost shell, component 0
 // ---- the dense image of a level (k_basic.hip): what the spectra and the structure functions work on ----
 // throws "<who>: ..." unless the boxes of the layout lie inside the domain of g and hold as many cells as it
 void dense_check_cover(const char* who, const Geometry& g, const Layout& lay);

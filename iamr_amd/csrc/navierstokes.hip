@@ -252,7 +252,7 @@ void NavierStokes::set_restart_state(const double v[16])
     dt_prev_mac = v[9]; m_have_mac_prev = v[10] != 0.0; m_have_mac_prev2 = v[11] != 0.0; dt_min_adv = v[12]; m_stop_time = v[13];
     // inew / pnew are not restored: the arrays were handed over as "new" / "old" data, whichever buffers hold them now
     initial_step = false; initial_iter = false;
-    m_visc_old_valid = false; m_eta_n_valid = false;
+    m_visc_old_valid = false; m_eta_n_valid = false; m_force_valid = false; m_visc_rhs_valid = false;
     make_rho_curr_time();
 }
 MultiFab& NavierStokes::mac_phi_history(int which)
@@ -524,10 +524,28 @@ static void floor_small(MultiFab& mf)
 
 void NavierStokes::compute_visc_terms_vel(MultiFab& visc, MultiFab& Sdata)
 {
-    visc.setVal(1.e40);                                       // NavierStokes.cpp:1982
     if (!is_diffusive_vel()) { visc.setVal(0.0); return; }
-    MultiFab stmp(layout, cell_type(), 3, 1);
-    fillpatch(stmp, Sdata, Xvel, 3, bc_vel);
+    // NavierStokes.cpp:1982.  On level 0 every value is written below: the cells by the operator, the ghost cells inside the domain or
+    // across a periodic face by FillBoundary (the level covers the domain), those outside a wall by first_order_extrap -- no fill
+    if (level == 0 && layout->total_cells() == g.domain.npts() && tune("ADVANCE_GLUE", 1) != 0) tuning_count("ADVANCE_GLUE_NO_FILL");
+    else visc.setVal(1.e40);
+    MultiFab stmp;
+    if (level == 0 && m_in_advance && &Sdata == &S[1 - inew] && tune("ADVANCE_GLUE", 1) != 0) {
+        // the old state inside an advance on a single level: FillPatch of its velocity in place on the state's own ghost layer, as
+        // velocity_diffusion_update's refill does, and the operator reads (and, for its boundary data, writes) that layer through a view
+        // -- no copy.  Nothing reads these ghost cells afterwards without filling them first: every FillPatch and every coarse-data
+        // copy (fillpatch, crse_state_at, fillpatch_two_levels) takes valid cells only; velocity_diffusion_update either refills them
+        // in the same way (no cached terms) or does not read them (the cached terms); once the array is the new state again, the viscous
+        // solve's fill_new (run by every step that comes here: the viscosity is positive) writes them before the projection reads them.
+        tuning_count("ADVANCE_GLUE_VISC_IN_PLACE");
+        const int ngv[3] = {1, 1, 1};
+        Sdata.FillBoundary(g, Xvel, 3, ngv);
+        if (any_wall) fill_physbc_cc(g, Sdata, Xvel, 3, bc_vel, ed_vel_lo, ed_vel_hi);
+        stmp.view_of(Sdata, Xvel, 3);
+    } else {
+        stmp.define(layout, cell_type(), 3, 1);
+        fillpatch(stmp, Sdata, Xvel, 3, bc_vel);
+    }
     const MultiFab* ep[3];
     MultiFab eta_les[3];
     get_viscosity(ep, eta_les, Sdata);
@@ -733,11 +751,29 @@ double NavierStokes::predict_velocity(double dt_)
 {
     SectionTimer tm(*this, 0);
     MultiFab& So = S[1 - inew];
+    const bool glue = tune("ADVANCE_GLUE", 1) != 0;
     MultiFab Umf(layout, cell_type(), 3, 3);
-    fillpatch(Umf, So, Xvel, 3, bc_vel);
     double cflmax = 0.0;
     double un3[3];
-    {   // floor_small(Umf) and the max norms of its components (ghost cells included) in one pass
+    if (glue && level == 0 && !any_wall && layout->total_cells() == g.domain.npts()) {
+        // single level, periodic in every direction: every ghost cell of the FillPatch is the copy of a valid cell, and the floor is a
+        // pointwise map, which commutes with copying -- one pass reads the state, writes the floored velocity and takes the maxima (the
+        // maximum over the grown boxes is the maximum over the cells); the ghost cells are filled from the floored cells
+        tuning_count("ADVANCE_GLUE_PRED_VALID");
+        const FabD *ut = Umf.d_tab, *st = So.d_tab;
+        reduce_max_f<3>(*layout, cell_type(), 0, [=] __device__(int i, int j, int k, int f, double (&m)[3]) {
+            const FabD a = ut[f], s = st[f];
+            for (int n = 0; n < 3; ++n) {
+                double v = s(i, j, k, Xvel + n);
+                if (fabs(v) <= 1.e-20) v = 0.0;
+                a(i, j, k, n) = v;
+                const double av = fabs(v);
+                m[n] = av > m[n] ? av : m[n];
+            }
+        }, un3);
+        Umf.FillBoundary(g);
+    } else {   // floor_small(Umf) and the max norms of its components (ghost cells included) in one pass
+        fillpatch(Umf, So, Xvel, 3, bc_vel);
         const FabD* ut = Umf.d_tab;
         reduce_max_f<3>(*layout, cell_type(), Umf.ngrow, [=] __device__(int i, int j, int k, int f, double (&m)[3]) {
             const FabD a = ut[f];
@@ -759,7 +795,12 @@ double NavierStokes::predict_velocity(double dt_)
     MultiFab visc_s;
     const MultiFab& visc = old_visc_or_zero(visc_s);
     // the density of the forcing: FillPatch of the old density on the cells and one ghost cell = rho_ptime (make_rho_prev_time, advance_setup)
-    MultiFab tf(layout, cell_type(), 3, 1);
+    // IAMRX_ADVANCE_GLUE: into the level's array, where advection_all finds it again (nothing between the two writes one of its inputs)
+    MultiFab tf_own;
+    const bool keep = glue && m_in_advance;
+    if (keep) { if (!m_force.defined() || m_force.layout.get() != layout.get() || m_force.ncomp != nstate) m_force.define(layout, cell_type(), nstate, 1); }
+    else tf_own.define(layout, cell_type(), 3, 1);
+    MultiFab& tf = keep ? m_force : tf_own;
     {
         const FabD *tt = tf.d_tab, *vt = visc.d_tab, *gt = Gp[1 - pnew].d_tab, *st = rho_ptime.d_tab;
         const double grav = p.gravity;
@@ -775,6 +816,7 @@ double NavierStokes::predict_velocity(double dt_)
         });
     }
     MultiFab* um[3] = {&u_mac[0], &u_mac[1], &u_mac[2]};
+    m_force_valid = keep;
     godunov_extrap_vel_to_faces(g, Umf, &tf, um, dt_, bc_vel, p.use_forces_in_trans != 0, p.use_ppm);
     return dt_ * tempdt;
 }
@@ -1001,42 +1043,60 @@ void NavierStokes::advection_all(double dt_)
             for (int n = 0; n < ns_; ++n) { const double v = st[f](i, j, k, n); qt[f](i, j, k, Density + n) = fabs(v) <= 1.e-20 ? 0.0 : v; }   // floor_small
         });
     }
-    MultiFab visc_s, svisc(layout, cell_type(), nscal, 1);
-    svisc.setVal(0.0);
-    const MultiFab& visc = old_visc_or_zero(visc_s);
-    if (p.be_cn_theta != 1.0) {
+    const bool glue = tune("ADVANCE_GLUE", 1) != 0;
+    // the scalars' viscous terms: zero when no scalar is diffusive or the solve is fully implicit.  IAMRX_ADVANCE_GLUE: then there is no
+    // array of zeros, the forcing pass takes the literal (the same double)
+    bool any_sdiff = false;
+    for (int n = 1; n < nscal; ++n) any_sdiff = any_sdiff || is_diffusive_scal(Density + n);
+    const bool have_svisc = !glue || (any_sdiff && p.be_cn_theta != 1.0);
+    MultiFab visc_s, svisc;
+    if (have_svisc) { svisc.define(layout, cell_type(), nscal, 1); svisc.setVal(0.0); }
+    else tuning_count("ADVANCE_GLUE_NO_SVISC");
+    // the velocity forcing of predict_velocity: the same expression of the same inputs in the convective form (do_mom_diff = 0; the
+    // momentum form does not divide by rho) -- read where it is, and only the scalar components are formed here
+    const bool vel_done = glue && !mom && m_in_advance && m_force_valid && m_force.layout.get() == layout.get();
+    if (vel_done) tuning_count("ADVANCE_GLUE_FORCE_ONCE");
+    const MultiFab* viscp = nullptr;
+    if (!vel_done) viscp = &old_visc_or_zero(visc_s);
+    if (p.be_cn_theta != 1.0 && have_svisc) {
         MultiFab one(layout, cell_type(), 1, 1);
         for (int n = 1; n < nscal; ++n) { get_visc_terms_scalar(one, So, Density + n); MultiFab::Copy(svisc, one, 0, n, 1, 1); }
     }
     ScalForm sf;                                 // per scalar slot: 0 convective, 1 conservative, 2 temperature
     for (int n = 0; n < MAXSCAL; ++n) sf.form[n] = (n < nscal && Density + n == Temp) ? 2 : (scal_cons[n] ? 1 : 0);
-    MultiFab tf(layout, cell_type(), nstate, 1), divu;
+    MultiFab tf_own, divu;
+    if (!vel_done) tf_own.define(layout, cell_type(), nstate, 1);
+    MultiFab& tf = vel_done ? m_force : tf_own;
     if (have_divu) divu_half(divu, dt_, 1, true);
     const MultiFab* dvp = have_divu ? &divu : nullptr;           // no divu: no array of zeros (every term it enters is a product with 0)
     {
         // the density of the forcing (velocity_advection's one-ghost-cell FillPatch of the old density) = rho_ptime (make_rho_prev_time)
-        const FabD *tt = tf.d_tab, *vt = visc.d_tab, *wt = svisc.d_tab, *gt = Gp[1 - pnew].d_tab, *rt = rho_ptime.d_tab, *qt = Q.d_tab;
+        const FabD *tt = tf.d_tab, *vt = viscp ? viscp->d_tab : nullptr, *wt = have_svisc ? svisc.d_tab : nullptr, *gt = Gp[1 - pnew].d_tab,
+                   *rt = rho_ptime.d_tab, *qt = Q.d_tab;
         const double grav = p.gravity;
         const MultiFab* tfm = turb_force_at(prev_time());                // getForce(prev_time), NavierStokesBase.cpp:3448
         const FabD* ft = tfm ? tfm->d_tab : nullptr;
         for_each(*layout, cell_type(), 1, Context::get().stream, [=] __device__(int i, int j, int k, int f) {
-            const double rho = rt[f](i, j, k, 0);
-            for (int n = 0; n < 3; ++n) {
-                double fr = (fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0;
-                if (ft) fr += rho * ft[f](i, j, k, n);
-                double t = fr + vt[f](i, j, k, n) - gt[f](i, j, k, n);
-                if (!mom) t /= rho;
-                tt[f](i, j, k, n) = t;
+            if (!vel_done) {
+                const double rho = rt[f](i, j, k, 0);
+                for (int n = 0; n < 3; ++n) {
+                    double fr = (fabs(grav) > 0.0001 && n == 2) ? grav * rho : 0.0;
+                    if (ft) fr += rho * ft[f](i, j, k, n);
+                    double t = fr + vt[f](i, j, k, n) - gt[f](i, j, k, n);
+                    if (!mom) t /= rho;
+                    tt[f](i, j, k, n) = t;
+                }
             }
             const double rhof = qt[f](i, j, k, Density);     // scalar_advection divides by the floored density of ITS state
             double t0 = 0.0;
             t0 += 0.0;
             tt[f](i, j, k, Density) = t0;
             for (int n = 1; n < ns_; ++n) {
+                const double w = wt ? (double)wt[f](i, j, k, n) : 0.0;
                 double t1 = 0.0;
-                if (sf.form[n] == 2) t1 = (t1 + wt[f](i, j, k, n)) / rhof;
-                else if (sf.form[n] == 1) t1 += wt[f](i, j, k, n);
-                else t1 = t1 / rhof + wt[f](i, j, k, n);
+                if (sf.form[n] == 2) t1 = (t1 + w) / rhof;
+                else if (sf.form[n] == 1) t1 += w;
+                else t1 = t1 / rhof + w;
                 tt[f](i, j, k, Density + n) = t1;
             }
         });
@@ -1180,6 +1240,92 @@ void NavierStokes::velocity_advection_update(double dt_)
     });
 }
 
+// IAMRX_ADVANCE_GLUE: scalar_update_rho (both passes and make_rho_curr_time's copy), scalar_update_tracers and velocity_advection_update
+// in ONE pass over the cells.  They read and write the same cells without a stencil and each reads what the one before wrote there, so
+// one pass with the same expressions in the same order (-ffp-contract=off) writes the same doubles: the new density, rho_ctime, rho_half
+// = 0.5 (rho_ptime + rho_ctime) from the values just formed, the tracers, u*.  The ghost layer of rho_ctime is filled as FillPatch fills
+// it, that of rho_half by its expression over the ghost shell.  velocity_advection_update moves in front of scalar_diffusion_update,
+// calc_divu and calc_dsdt: it reads the old state, aofs, Gp, the densities -- nothing that those write (the tracers and Temp of the new
+// state, Divu, Dsdt) -- and they do not read the new velocity, so no value changes.
+// When the step then takes the tensor solve from the cached viscous terms (velocity_diffusion_update's `reuse`, no LES, whose eddy
+// viscosity reads u* from the state), the pass also does the first pass of diffuse_tensor_velocity with the u* it holds: rho u* into the
+// state, Rhs = (va v + 0.0 v) + rho u* and its three max norms.
+// Not with do_denminmax / do_scalminmax, which read the new density / tracers through 27-point neighbourhoods between the passes.
+bool NavierStokes::update_all(double dt_)
+{
+    if (tune("ADVANCE_GLUE", 1) == 0 || p.do_denminmax || p.do_scalminmax) return false;
+    SectionTimer tm(*this, 3);
+    tuning_count("ADVANCE_GLUE_UPDATE");
+    const double theta = p.be_cn_theta;
+    const bool want_flux = fine != nullptr || level > 0;
+    const bool rhs = !initial_iter && is_diffusive_vel() && !p.do_LES && theta != 1.0 && !want_flux && m_visc_old_valid;
+    if (rhs) {
+        tuning_count("ADVANCE_GLUE_RHS");
+        if (!m_visc_rhs.defined() || m_visc_rhs.layout.get() != layout.get()) m_visc_rhs.define(layout, cell_type(), 3, 0);
+    }
+    const FabD *nt = S[inew].d_tab, *ot = S[1 - inew].d_tab, *at = aofs.d_tab, *gt = Gp[1 - pnew].d_tab;
+    const FabD *pt = rho_ptime.d_tab, *ct = rho_ctime.d_tab, *ht = rho_half.d_tab;
+    const FabD *vt = rhs ? m_visc_old.d_tab : nullptr, *rt = rhs ? m_visc_rhs.d_tab : nullptr;
+    const int ns_ = nstate;
+    const double grav = p.gravity;
+    const bool zero_force = initial_iter && is_diffusive_vel();
+    const bool mom = p.do_mom_diff != 0;
+    const double va = (1.0 - theta) * dt_;
+    // getForce(half_time) with the half-time density, NavierStokesBase.cpp:3580-3583; half_time = (prevTime + curTime) / 2
+    const MultiFab* tfm = turb_force_at(0.5 * (prev_time() + (amr_times ? st_new : time + dt_)));
+    const FabD* ft = tfm ? tfm->d_tab : nullptr;
+    auto body = [=] __device__(int i, int j, int k, int f, double* m) {
+        const FabD nw = nt[f], od = ot[f], a = at[f];
+        // scalar_update_rho, make_rho_curr_time, get_rho_half_time
+        const double ro = od(i, j, k, Density);
+        const double rn = ro - dt_ * a(i, j, k, Density);
+        nw(i, j, k, Density) = rn;
+        ct[f](i, j, k, 0) = rn;
+        const double rh = 0.5 * (pt[f](i, j, k, 0) + rn);
+        ht[f](i, j, k, 0) = rh;
+        // scalar_update_tracers
+        const double rho = ro - 0.5 * dt_ * a(i, j, k, Density);
+        const double tfv = 0.0;
+        for (int sigma = Tracer; sigma < ns_; ++sigma) nw(i, j, k, sigma) = od(i, j, k, sigma) + dt_ * (-a(i, j, k, sigma) + tfv / rho);
+        // velocity_advection_update
+        const double scal_rho = 0.5 * (ro + rn);
+        for (int n = 0; n < 3; ++n) {
+            double force = (fabs(grav) > 0.0001 && n == 2) ? grav * scal_rho : 0.0;
+            if (ft) force += scal_rho * ft[f](i, j, k, n);
+            if (zero_force) force = 0.0;
+            double velold = od(i, j, k, n);
+            double us;
+            if (mom) {
+                velold *= ro;
+                const double v = velold - dt_ * a(i, j, k, n) + dt_ * force - dt_ * gt[f](i, j, k, n);
+                us = v / rn;
+            } else
+                us = velold - dt_ * a(i, j, k, n) + dt_ * force / rh - dt_ * gt[f](i, j, k, n) / rh;
+            if (rhs) {                                  // diffuse_tensor_velocity's first pass (Diffusion.cpp:819-825)
+                const double un = us * (mom ? ro : rh);
+                nw(i, j, k, n) = un;
+                const double v = vt[f](i, j, k, n);
+                double rr = va * v + 0.0 * v;
+                rr += un;
+                rt[f](i, j, k, n) = rr;
+                const double an = norm_term(rr);
+                m[n] = an > m[n] ? an : m[n];
+            } else
+                nw(i, j, k, n) = us;
+        }
+    };
+    if (rhs) reduce_max_f<3>(*layout, cell_type(), 0, [=] __device__(int i, int j, int k, int f, double (&m)[3]) { body(i, j, k, f, m); }, m_visc_rhs_norm);
+    else for_each(*layout, cell_type(), 0, Context::get().stream, [=] __device__(int i, int j, int k, int f) { body(i, j, k, f, nullptr); });
+    m_visc_rhs_valid = rhs;
+    // the ghost layer of rho_ctime as make_rho_curr_time's FillPatch fills it; on a refined level the two-level fill (which copies the cells again)
+    if (level == 0) {
+        rho_ctime.FillBoundary(g);
+        if (any_wall) fill_physbc_cc(g, rho_ctime, 0, 1, &bc_scal[0], ed_scal_lo, ed_scal_hi);
+    } else make_rho_curr_time();
+    mf_half_sum_ghosts(rho_half, rho_ptime, rho_ctime, 1);
+    return true;
+}
+
 void NavierStokes::initial_velocity_diffusion_update(double dt_)
 {
     if (!is_diffusive_vel()) return;
@@ -1248,8 +1394,14 @@ void NavierStokes::velocity_diffusion_update(double dt_)
         if (theta != 1.0 && !reuse) { crse_state_at(co, st_old, Xvel, 3); dc.crse_old = &co; }
         crse_state_at(cn, st_new, Xvel, 3); dc.crse_new = &cn;
     }
+    // update_all has formed rho u*, the right-hand side and its norms already (under the very conditions of `reuse`)
+    TensorRhsReady ready{&m_visc_rhs, {m_visc_rhs_norm[0], m_visc_rhs_norm[1], m_visc_rhs_norm[2]}};
+    const bool have_rhs = m_visc_rhs_valid;
+    m_visc_rhs_valid = false;
+    IAMRX_ASSERT(!have_rhs || reuse);
     st_visc = diffuse_tensor_velocity(g, &So, Sn, Density, dt_, theta, rho_half, p.do_mom_diff ? 3 : 1, reuse ? &m_visc_old : nullptr, en, ep, bc_visc,
-                                      level > 0 ? &dc : nullptr, want_flux ? tfp : nullptr, p.visc_tol, o, [&](MultiFab& U) { refill(U, U); });
+                                      level > 0 ? &dc : nullptr, want_flux ? tfp : nullptr, p.visc_tol, o, [&](MultiFab& U) { refill(U, U); },
+                                      have_rhs ? &ready : nullptr);
     if (want_flux)
         for (int d = 0; d < 3; ++d) {
             if (level > 0) reg_visc->FineAdd(tflux[d], d, 0, Xvel, 3, dt_);                        // :946-949
@@ -1423,21 +1575,24 @@ void NavierStokes::initial_sync_project(double dt_)
 double NavierStokes::advance(double dt_, int iteration_, int ncycle_)
 {
     advance_setup(dt_, iteration_, ncycle_);
-    m_in_advance = true; m_visc_old_valid = false; m_eta_n_valid = false;
+    m_in_advance = true; m_visc_old_valid = false; m_eta_n_valid = false; m_force_valid = false; m_visc_rhs_valid = false;
     const double dt_test = predict_velocity(dt_);
     mac_project(dt_);
     const bool fused_adv = tune("FUSED_ADVECTION", 1) != 0;
     if (fused_adv) advection_all(dt_);
     else { velocity_advection(dt_); scalar_advection(dt_); }
-    scalar_update_rho(dt_);
-    scalar_update_tracers(dt_);
+    const bool fused_upd = update_all(dt_);                      // IAMRX_ADVANCE_GLUE: the three updates in one pass (see there)
+    if (!fused_upd) {
+        scalar_update_rho(dt_);
+        scalar_update_tracers(dt_);
+    }
     scalar_diffusion_update(dt_);
     if (have_divu) {                                             // NavierStokes.cpp:631-641
         calc_divu(true);
         calc_dsdt(dt_);
         if (initial_step) MultiFab::Copy(S[1 - inew], S[inew], Dsdt, Dsdt, 1, 0);
     }
-    velocity_advection_update(dt_);
+    if (!fused_upd) velocity_advection_update(dt_);
     if (!initial_iter) velocity_diffusion_update(dt_);
     else initial_velocity_diffusion_update(dt_);
     if (!initial_step) {
@@ -1447,7 +1602,7 @@ double NavierStokes::advance(double dt_, int iteration_, int ncycle_)
         if (level > 0 && iteration == 1) p_avg.setVal(0.0);      // :670-671
     }
     if (particles && !initial_step) advect_particles(dt_);       // AdvectWithUmac(u_mac, level, dt), NavierStokes.cpp:672-677
-    m_in_advance = false; m_visc_old_valid = false; m_eta_n_valid = false;
+    m_in_advance = false; m_visc_old_valid = false; m_eta_n_valid = false; m_force_valid = false; m_visc_rhs_valid = false;
     return dt_test;
 }
 

@@ -78,11 +78,15 @@ MGStats diffuse_scalar(const Geometry& g, const MultiFab* S_old, const MultiFab*
 // alpha = rho_half (rho_flag 1) or rho_new with u* weighted by rho_old (rho_flag 3, do_mom_diff).  U_old / U_new: states with the velocity
 // in components 0..2 and the density in rho_comp, 1 filled ghost cell.  visc_old_term (may be null): div tau(u_old) if the caller has it
 // already and wants no fluxes.  tflux (may be null): the summed extensive viscous fluxes.  fill_new: refills the ghost cells of U_new's
-// velocity once it holds rho u* (the FillPatch of Diffusion.cpp:866); null: they are used as they came.
+// velocity once it holds rho u* (the FillPatch of Diffusion.cpp:866); null: they are used as they came.  ready (may be null; needs
+// visc_old_term and no fluxes): the caller's pass that formed u* has already written rho u* into U_new and the right-hand side into
+// ready->rhs and taken its three max norms -- the first pass over the level is skipped.
+struct TensorRhsReady { MultiFab* rhs; double norm[3]; };
 MGStats diffuse_tensor_velocity(const Geometry& g, const MultiFab* U_old, MultiFab& U_new, int rho_comp, double dt, double theta,
                                 const MultiFab& rho_half, int rho_flag, const MultiFab* visc_old_term, const MultiFab* const eta_n[3],
                                 const MultiFab* const eta_np1[3], const DomainBC bc_visc[3], const DiffusionCrse* crse,
-                                MultiFab* const tflux[3], double visc_tol, const MGOpts& o, const std::function<void(MultiFab&)>& fill_new);
+                                MultiFab* const tflux[3], double visc_tol, const MGOpts& o, const std::function<void(MultiFab&)>& fill_new,
+                                const TensorRhsReady* ready = nullptr);
 
 // Diffusion::diffuse_tensor_Vsync (Source/Diffusion.cpp:1010-1178) and Diffusion::diffuse_Ssync as NavierStokes::mac_sync uses them; see diffusion.hip
 MGStats diffuse_tensor_Vsync(const Geometry& g, MultiFab& Vsync, double dt, double theta, const MultiFab& rho_half, int rho_flag,
@@ -477,6 +481,17 @@ private:
     // (times (1 - theta) dt) by the Crank-Nicolson right-hand side -- one tensor apply instead of three (valid only inside advance())
     MultiFab m_visc_old;
     bool m_visc_old_valid = false, m_in_advance = false;
+    // IAMRX_ADVANCE_GLUE ("Advance: the passes around the Godunov kernels").  The velocity forcing (f + visc - Gp) / rho
+    // of the old time on one ghost layer, components 0..2 of an nstate-component array: predict_velocity forms it, advection_all (convective
+    // form) reads it and adds the scalar components instead of forming all of them again.  Validity as m_visc_old.
+    MultiFab m_force;
+    bool m_force_valid = false;
+    // the right-hand side of the viscous solve and its three max norms, formed by update_all from the u* it holds (valid until
+    // velocity_diffusion_update has taken them)
+    MultiFab m_visc_rhs;
+    double m_visc_rhs_norm[3] = {0.0, 0.0, 0.0};
+    bool m_visc_rhs_valid = false;
+    bool update_all(double dt);                // the update passes between the advection and the solves in one; false: not applicable
     // ns.do_LES: the face viscosity visc_coef + mu_t of the old state, computed once per advance (the old state does not change inside
     // one; validity as m_visc_old), and that of the new state as velocity_diffusion_update last saw it.  Not allocated without LES.
     MultiFab m_eta_n[3], m_eta_np1[3];
