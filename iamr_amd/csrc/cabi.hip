@@ -219,6 +219,25 @@ int iamrx_host_nodal_smoother_plan(int nboxes, const int* lo_hi, const iamrx_geo
     IAMRX_CATCH
 }
 
+// host-only (no device needed): the launches one call of the fused Godunov kernels issues on a level, and the tiles of its two classes
+// (god_z_plan, k_godunov.hip).  *ntiles: the number of tile entries; the first min(*ntiles, max_tiles) are written
+int iamrx_host_godunov_plan(int pred, int nboxes, const int* lo_hi, const iamrx_geom* g, int scheme, int has_force, int fit, int has_divu, int edge_out,
+                            int flux_out, int ncomp, const int* iconserv, int head[5], int launches[64], int starts[20], int* tiles, int max_tiles, int* ntiles)
+{
+    IAMRX_TRY
+    if (nboxes < 1) throw Error("iamrx_host_godunov_plan: at least one box");
+    std::vector<BoxD> b(nboxes);
+    for (int i = 0; i < nboxes; ++i)
+        for (int d = 0; d < 3; ++d) { b[i].lo[d] = lo_hi[6 * i + d]; b[i].hi[d] = lo_hi[6 * i + 3 + d]; }
+    std::vector<int> la, st, ti;
+    godunov_plan_host(pred != 0, b, to_geom(g), scheme, has_force != 0, fit != 0, has_divu != 0, edge_out != 0, flux_out != 0, ncomp, iconserv, head, la, st, ti);
+    std::copy(la.begin(), la.end(), launches);
+    std::copy(st.begin(), st.end(), starts);
+    *ntiles = (int)ti.size() / 5;
+    if (tiles) std::copy(ti.begin(), ti.begin() + 5 * std::min(*ntiles, max_tiles), tiles);
+    IAMRX_CATCH
+}
+
 static hipEvent_t g_ev0 = nullptr, g_ev1 = nullptr;
 int iamrx_timer_start(void)
 {

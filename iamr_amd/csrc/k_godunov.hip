@@ -11,11 +11,11 @@
 //   pass 1  k_trace   : per face of each direction (transverse grown by 1): 4th-order limited slopes are
 //                       evaluated in registers, the two traced states are upwinded at once ->
 //                       advective velocity (predict mode) + single-valued transverse states.
-//   pass 2  k_final   : per face: the four corner-coupled transverse states per transverse direction are
-//                       rebuilt in registers from pass-1 data (re-evaluating slopes instead of storing
-//                       lo/hi arrays), transverse terms + forcing + BCs + final upwinding.
+//                       By-product: the limited slopes of every cell (PLM), read again by pass 2.
+//   pass 2  k_dir     : per direction and face: the corner-coupled transverse states of a tile pass through LDS ring
+//                       planes, transverse terms + forcing + BCs + final upwinding.
 //   pass 3  k_aofs    : per cell: area-weighted fluxes, -div, convective correction, aofs = -update.
-// Only 3+3*ncomp face arrays are materialised in HBM between the passes.
+// Only the pass-1 face arrays and the slope arrays are materialised in HBM between the passes.
 // The direction is a template parameter and all index shifts are linear strides, so every array index is
 // static after unrolling (no scratch memory); run-time parameters live in a small device-resident block.
 #include "kernels.h"
@@ -506,148 +506,7 @@ __device__ __forceinline__ double corner_state(PQ qn, PV vT, long sT, int fT,
     return fu * st + (1.0 - fu) * 0.5 * (h + l);
 }
 
-// the four corner states (low-side cell / high-side cell of the D-face) x (T-face c / c+1) for transverse direction T
-template <bool PRED, int D, int T, class PQ, class PF, class PD>
-__device__ __forceinline__ void corner_quad(const GodParams& P, int n, bool conserv, int fT,
-    PQ qn, PQ qT, const FabD& q,
-    const FabD& mT, long mTo, const FabD& mO, long mOo, const FabD& eO, long eOo,
-    PF frcn, const FabD& frc, PD dvp, const FabD& dv,
-    double& Tl0, double& Tl1, double& Th0, double& Th1)
-{
-    constexpr int O = 3 - D - T;
-    const long qsD = stride_of<D>(q), qsT = stride_of<T>(q);
-    const long mTsD = stride_of<D>(mT), mTsT = stride_of<T>(mT);
-    const long mOsD = stride_of<D>(mO), mOsT = stride_of<T>(mO), mOsO = stride_of<O>(mO);
-    const long eOsD = stride_of<D>(eO), eOsT = stride_of<T>(eO), eOsO = stride_of<O>(eO);
-    const long fsD = frcn ? stride_of<D>(frc) : 0, fsT = frcn ? stride_of<T>(frc) : 0;
-    const long dsD = dvp ? stride_of<D>(dv) : 0, dsT = dvp ? stride_of<T>(dv) : 0;
-    const double c_o = conserv ? P.dt / (3.0 * P.dx[O]) : P.dt / (6.0 * P.dx[O]);
-    const double dt3 = P.dt / 3.0;
-    const double dtdxT = P.dt / P.dx[T];
-    const double hdt = 0.5 * P.dt;
-    const int bl = P.bc.bc[n].lo[T], bh = P.bc.bc[n].hi[T];
-    const bool nonperT = !P.bc.per[T];
-    const bool nvel = P.is_velocity && n == T;
-    const bool fit = P.fit != 0;
-    const int dlo = P.bc.dlo[T], dhi = P.bc.dhi[T];
-#define IAMRX_CORNER(SIDE, UP)                                                                                                   \
-    corner_state<PRED>(qn + ((SIDE) ? 0 : -qsD) + (UP) * qsT, qT + ((SIDE) ? 0 : -qsD) + (UP) * qsT, qsT, fT + (UP),                \
-                       mT.gp()[mTo + ((SIDE) ? 0 : -mTsD) + (UP) * mTsT], mO.gp() + mOo + ((SIDE) ? 0 : -mOsD) + (UP) * mOsT, mOsT, mOsO, \
-                       eO.gp() + eOo + ((SIDE) ? 0 : -eOsD) + (UP) * eOsT, eOsT, eOsO,                                                \
-                       frcn ? frcn + ((SIDE) ? 0 : -fsD) + (UP) * fsT : nullptr, fsT, dtdxT, c_o, dt3, P.dx[O], conserv,             \
-                       dvp ? dvp + ((SIDE) ? 0 : -dsD) + (UP) * dsT : nullptr, dsT, fit, hdt, nonperT, nvel, bl, bh, dlo, dhi)
-    Tl0 = IAMRX_CORNER(0, 0);
-    Tl1 = IAMRX_CORNER(0, 1);
-    Th0 = IAMRX_CORNER(1, 0);
-    Th1 = IAMRX_CORNER(1, 1);
-#undef IAMRX_CORNER
-}
-
-// -------------------------------------------------------------------------------- pass 2
-// grid over the valid faces of direction D.  PRED: only component n = D, output umac[D];
-// ADV: all components, output final edge states edge[D](ncomp).
-template <bool PRED, int D>
-__global__ void __launch_bounds__(256) k_final(Tiling t, const BoxD* __restrict__ boxes,
-    const FabD* __restrict__ qt, const FabD* __restrict__ ft, const FabD* __restrict__ divut,
-    const FabD* __restrict__ m0t, const FabD* __restrict__ m1t, const FabD* __restrict__ m2t,
-    const FabD* __restrict__ e0t, const FabD* __restrict__ e1t, const FabD* __restrict__ e2t,
-    const FabD* __restrict__ outt, const GodParams* __restrict__ Pp)
-{
-    constexpr int TA = D == 0 ? 1 : 0;            // transverse directions in ascending order
-    constexpr int TB = D == 2 ? 1 : 2;
-    const GodParams& P = *Pp;
-    const int fab = blockIdx.y;
-    BoxD b = boxes[fab];
-    b.hi[D] += 1;
-    int i, j, k0, k1;
-    if (!tile_ijk(t, b, i, j, k0, k1)) return;
-    const FabD q = qt[fab], out = outt[fab];
-    const FabD m0 = m0t[fab], m1 = m1t[fab], m2 = m2t[fab];
-    const FabD e0 = e0t[fab], e1 = e1t[fab], e2 = e2t[fab];
-    const FabD& mD = D == 0 ? m0 : (D == 1 ? m1 : m2);
-    const FabD& mA = TA == 0 ? m0 : (TA == 1 ? m1 : m2);
-    const FabD& mB = TB == 0 ? m0 : (TB == 1 ? m1 : m2);
-    const FabD& eA = TA == 0 ? e0 : (TA == 1 ? e1 : e2);
-    const FabD& eB = TB == 0 ? e0 : (TB == 1 ? e1 : e2);
-    const bool has_force = P.has_force != 0, has_divu = P.has_divu != 0, fit = P.fit != 0;
-    FabD frc; if (has_force) frc = ft[fab];
-    FabD dv; if (has_divu) dv = divut[fab];
-    const long qsD = stride_of<D>(q);
-    const long fsD = has_force ? stride_of<D>(frc) : 0, dsD = has_divu ? stride_of<D>(dv) : 0;
-    const long mAsD = stride_of<D>(mA), mAsT = stride_of<TA>(mA), mBsD = stride_of<D>(mB), mBsT = stride_of<TB>(mB);
-    const double dt = P.dt, hdt = 0.5 * P.dt;
-    const double dtdxD = dt / P.dx[D];
-    const int nbeg = PRED ? D : (gridDim.z > 1 ? (int)blockIdx.z : 0), nend = PRED ? D + 1 : (gridDim.z > 1 ? nbeg + 1 : P.ncomp);
-    const bool nonperD = !P.bc.per[D];
-    const int dloD = P.bc.dlo[D], dhiD = P.bc.dhi[D];
-    const bool is_vel = P.is_velocity != 0;
-    for (int k = k0; k <= k1; ++k) {
-        const int f = D == 0 ? i : (D == 1 ? j : k);
-        const int fA = TA == 0 ? i : (TA == 1 ? j : k), fB = TB == 0 ? i : (TB == 1 ? j : k);
-        const long qo = q.off(i, j, k);
-        const long fo = has_force ? frc.off(i, j, k) : 0;
-        const long dvo = has_divu ? dv.off(i, j, k) : 0;
-        const long mAo = mA.off(i, j, k), mBo = mB.off(i, j, k);
-        const double umD = mD(i, j, k, 0);
-        for (int n = nbeg; n < nend; ++n) {
-            const auto qn = q.gp() + qo + q.cs * n;
-            const auto frcn = has_force ? frc.gp() + fo + frc.cs * n : (decltype(frc.gp()))nullptr;
-            const auto dvp = has_divu ? dv.gp() + dvo : (decltype(dv.gp()))nullptr;
-            const bool conserv = !PRED && P.iconserv[n] != 0;
-            const int blD = P.bc.bc[n].lo[D], bhD = P.bc.bc[n].hi[D];
-            // own traced states along D
-            double stl, sth;
-            {
-                const bool edlo = nonperD && ed_or_ho(blD), edhi = nonperD && ed_or_ho(bhD);
-                trace_lohi<PRED>(qn, q.gp() + qo + q.cs * D, qsD, umD, dtdxD, edlo, edhi, f, dloD, dhiD, stl, sth);
-                if (fit && has_force) { stl += hdt * frcn[-fsD]; sth += hdt * frcn[0]; }
-                if (nonperD) trans_bc(qn, qsD, f, is_vel && n == D, stl, sth, blD, bhD, dloD, dhiD);
-            }
-            // corner-coupled transverse states: direction TA is corrected with the TB-derivative and vice versa
-            double Al0, Al1, Ah0, Ah1, Bl0, Bl1, Bh0, Bh1;
-            corner_quad<PRED, D, TA>(P, n, conserv, fA, qn, q.gp() + qo + q.cs * TA, q, mA, mAo, mB, mBo, eB, eB.off(i, j, k) + eB.cs * n,
-                                     frcn, frc, dvp, dv, Al0, Al1, Ah0, Ah1);
-            corner_quad<PRED, D, TB>(P, n, conserv, fB, qn, q.gp() + qo + q.cs * TB, q, mB, mBo, mA, mAo, eA, eA.off(i, j, k) + eA.cs * n,
-                                     frcn, frc, dvp, dv, Bl0, Bl1, Bh0, Bh1);
-            const double mA_l0 = mA.gp()[mAo - mAsD], mA_l1 = mA.gp()[mAo - mAsD + mAsT], mA_h0 = mA.gp()[mAo], mA_h1 = mA.gp()[mAo + mAsT];
-            const double mB_l0 = mB.gp()[mBo - mBsD], mB_l1 = mB.gp()[mBo - mBsD + mBsT], mB_h0 = mB.gp()[mBo], mB_h1 = mB.gp()[mBo + mBsT];
-            if (conserv) {
-                const double cA = 0.5 * dt / P.dx[TA], cB = 0.5 * dt / P.dx[TB];
-                stl += -cA * (Al1 * mA_l1 - Al0 * mA_l0);
-                sth += -cA * (Ah1 * mA_h1 - Ah0 * mA_h0);
-                stl += -cB * (Bl1 * mB_l1 - Bl0 * mB_l0);
-                sth += -cB * (Bh1 * mB_h1 - Bh0 * mB_h0);
-                stl += cA * qn[-qsD] * (mA_l1 - mA_l0);
-                sth += cA * qn[0] * (mA_h1 - mA_h0);
-                stl += cB * qn[-qsD] * (mB_l1 - mB_l0);
-                sth += cB * qn[0] * (mB_h1 - mB_h0);
-                if (has_divu) { stl -= 0.5 * dt * qn[-qsD] * dvp[-dsD]; sth -= 0.5 * dt * qn[0] * dvp[0]; }
-            } else {
-                const double cA = 0.25 * dt / P.dx[TA], cB = 0.25 * dt / P.dx[TB];
-                stl -= cA * (mA_l1 + mA_l0) * (Al1 - Al0);
-                sth -= cA * (mA_h1 + mA_h0) * (Ah1 - Ah0);
-                stl -= cB * (mB_l1 + mB_l0) * (Bl1 - Bl0);
-                sth -= cB * (mB_h1 + mB_h0) * (Bh1 - Bh0);
-            }
-            if (!fit && has_force) { stl += hdt * frcn[-fsD]; sth += hdt * frcn[0]; }
-            if (nonperD) edge_bc(qn, qsD, f, is_vel && n == D, stl, sth, blD, bhD, dloD, dhiD);
-            if (PRED) {
-                const double st = ((stl + sth) >= 0.) ? stl : sth;
-                const bool ltm = ((stl <= 0. && sth >= 0.) || (fabs(stl + sth) < SMALL_VEL));
-                out(i, j, k, 0) = ltm ? 0. : st;
-            } else {
-                double temp = (umD >= 0.) ? stl : sth;
-                temp = (fabs(umD) < SMALL_VEL) ? 0.5 * (stl + sth) : temp;
-                out(i, j, k, n) = temp;
-            }
-        }
-    }
-}
-
-// -------------------------------------------------------------------------------- pass 2a / 2b (split variant)
-// 2a: k_corner<D,T> materialises the corner-coupled transverse states on the T-faces (cells grown by 1 in D)
-// 2b: k_final_s<D> combines them.  Less register pressure and no slope recomputation per corner than the
-// fully fused k_final above (which stays selectable with IAMRX_GODUNOV_FUSED=1 for A/B measurements).
+// -------------------------------------------------------------------------------- pass 2: the device functions of k_dir
 // corner-coupled state of component n on the T-face (i,j,k), corrected with the O-derivative (O = the third direction)
 template <bool PRED, int D, int T, bool SL = false>
 __device__ __forceinline__ double corner_at(const GodParams& P, int n, int i, int j, int k, const FabD& q, const FabD& frc, const FabD& dv,
@@ -680,32 +539,9 @@ __device__ __forceinline__ double corner_at(const GodParams& P, int n, int i, in
         P.bc.bc[n].lo[T], P.bc.bc[n].hi[T], dlo, dhi);
 }
 
-template <bool PRED, int D, int T>
-__global__ void __launch_bounds__(256) k_corner(Tiling t, const BoxD* __restrict__ boxes,
-    const FabD* __restrict__ qt, const FabD* __restrict__ ft, const FabD* __restrict__ divut,
-    const FabD* __restrict__ mTt, const FabD* __restrict__ mOt, const FabD* __restrict__ eOt,
-    const FabD* __restrict__ outt, const GodParams* __restrict__ Pp)
-{
-    const GodParams& P = *Pp;
-    const int fab = blockIdx.y;
-    BoxD b = boxes[fab];
-    b.hi[T] += 1; b.lo[D] -= 1; b.hi[D] += 1;
-    int i, j, k0, k1;
-    if (!tile_ijk(t, b, i, j, k0, k1)) return;
-    const FabD q = qt[fab], mT = mTt[fab], mO = mOt[fab], eO = eOt[fab], out = outt[fab];
-    const bool has_force = P.has_force != 0, has_divu = P.has_divu != 0;
-    FabD frc; if (has_force) frc = ft[fab];
-    FabD dv; if (has_divu) dv = divut[fab];
-    // advection: one component per blockIdx.z (fewer live registers, more workgroups); prediction: the normal component only
-    const int nbeg = PRED ? D : (gridDim.z > 1 ? (int)blockIdx.z : 0), nend = PRED ? D + 1 : (gridDim.z > 1 ? nbeg + 1 : P.ncomp);
-    for (int k = k0; k <= k1; ++k)
-        for (int n = nbeg; n < nend; ++n)
-            out(i, j, k, PRED ? 0 : n) = corner_at<PRED, D, T>(P, n, i, j, k, q, frc, dv, mT, mO, eO, has_force, has_divu);
-}
-
 // final edge state of component n on the D-face (i,j,k) from the two corner-coupled transverse arrays.  cAp / cBp point at the
 // entry (i,j,k) of the TA- / TB-face corner states of component n; strides: s?D towards the low-side cell of the D-face,
-// s?T to the next TA- / TB-face (global arrays in k_final_s, LDS ring planes in k_dir).  mA / mB: the four transverse mac
+// s?T to the next TA- / TB-face (the LDS ring planes of k_dir).  mA / mB: the four transverse mac
 // velocities (low-side cell: face 0/1, high-side cell: face 0/1).
 template <bool PRED, int D, bool SL = false, class PC>
 __device__ __forceinline__ double final_edge(const GodParams& P, int n, int i, int j, int k, const FabD& q, const FabD& frc, const FabD& dv,
@@ -773,56 +609,18 @@ __device__ __forceinline__ double final_edge(const GodParams& P, int n, int i, i
     return temp;
 }
 
-template <bool PRED, int D>
-__global__ void __launch_bounds__(256) k_final_s(Tiling t, const BoxD* __restrict__ boxes,
-    const FabD* __restrict__ qt, const FabD* __restrict__ ft, const FabD* __restrict__ divut,
-    const FabD* __restrict__ mDt, const FabD* __restrict__ mAt, const FabD* __restrict__ mBt,
-    const FabD* __restrict__ cAt, const FabD* __restrict__ cBt, const FabD* __restrict__ outt, const GodParams* __restrict__ Pp)
-{
-    constexpr int TA = D == 0 ? 1 : 0;
-    constexpr int TB = D == 2 ? 1 : 2;
-    const GodParams& P = *Pp;
-    const int fab = blockIdx.y;
-    BoxD b = boxes[fab];
-    b.hi[D] += 1;
-    int i, j, k0, k1;
-    if (!tile_ijk(t, b, i, j, k0, k1)) return;
-    const FabD q = qt[fab], out = outt[fab], mD = mDt[fab], mA = mAt[fab], mB = mBt[fab], cA = cAt[fab], cB = cBt[fab];
-    const bool has_force = P.has_force != 0, has_divu = P.has_divu != 0;
-    FabD frc; if (has_force) frc = ft[fab];
-    FabD dv; if (has_divu) dv = divut[fab];
-    const long mAsD = stride_of<D>(mA), mAsT = stride_of<TA>(mA), mBsD = stride_of<D>(mB), mBsT = stride_of<TB>(mB);
-    const long cAsD = stride_of<D>(cA), cAsT = stride_of<TA>(cA), cBsD = stride_of<D>(cB), cBsT = stride_of<TB>(cB);
-    const int nbeg = PRED ? D : (gridDim.z > 1 ? (int)blockIdx.z : 0), nend = PRED ? D + 1 : (gridDim.z > 1 ? nbeg + 1 : P.ncomp);
-    for (int k = k0; k <= k1; ++k) {
-        const long mAo = mA.off(i, j, k), mBo = mB.off(i, j, k);
-        const double umD = mD(i, j, k, 0);
-        const double mA_l0 = mA.gp()[mAo - mAsD], mA_l1 = mA.gp()[mAo - mAsD + mAsT], mA_h0 = mA.gp()[mAo], mA_h1 = mA.gp()[mAo + mAsT];
-        const double mB_l0 = mB.gp()[mBo - mBsD], mB_l1 = mB.gp()[mBo - mBsD + mBsT], mB_h0 = mB.gp()[mBo], mB_h1 = mB.gp()[mBo + mBsT];
-        for (int n = nbeg; n < nend; ++n) {
-            const int cn = PRED ? 0 : n;
-            out(i, j, k, cn) = final_edge<PRED, D>(P, n, i, j, k, q, frc, dv, has_force, has_divu, umD, mA_l0, mA_l1, mA_h0, mA_h1,
-                                                  mB_l0, mB_l1, mB_h0, mB_h1, cA.gp() + cA.off(i, j, k) + cA.cs * cn, cAsD, cAsT,
-                                                  cB.gp() + cB.off(i, j, k) + cB.cs * cn, cBsD, cBsT);
-        }
-    }
-}
-
-// -------------------------------------------------------------------------------- pass 2 fused per direction (default)
-// k_dir<D>: the two corner-coupled arrays of direction D never reach HBM.  A workgroup owns a TX x TY tile of D-faces and
-// marches through the planes k0..k1.  Its 14 wavefronts are specialised:
-//   (TX x TY = 32 x 8: 14 wavefronts)
-//   waves 0-4  (producer A): corner states on the TA-faces the tile needs (tile grown by one cell / one face), one per thread
-//   waves 5-9  (producer B): the same for the TB-faces
-//   waves 10-13 (consumer) : final edge state of one D-face per thread from the LDS ring planes written by the producers
-// Every thread keeps ONE (i,j) for the whole march, so all array offsets are loop invariants (as in k_corner / k_final_s);
+// -------------------------------------------------------------------------------- pass 2 fused per direction
+// k_dir<D>: the two corner-coupled arrays of direction D never reach HBM.  A workgroup owns a TX x TY tile of D-faces (16 x 8 is
+// the one shape instantiated: 8 wavefronts) and marches through the planes k0..k1.  Its wavefronts are specialised:
+//   the first WP   (producer A): corner states on the TA-faces the tile needs (tile grown by one cell / one face), one per thread
+//   the next WP    (producer B): the same for the TB-faces
+//   the rest       (consumer)  : final edge state of one D-face per thread from the LDS ring planes written by the producers
+// Every thread keeps ONE (i,j) for the whole march, so all array offsets are loop invariants;
 // the consumer runs one plane behind the producers and the three ring slots per array make one barrier per plane enough:
 //   D = 0, 1: iteration t: A -> cA(plane k0+t), B -> cB(z-face k0+t+1)  [prologue: cB(k0)],  consumer -> faces of plane k0+t-1
 //   D = 2   : iteration t: A, B -> cell plane k0+t                      [prologue: plane k0-1], consumer -> z-face k0+t-1
-// Arithmetic: corner_at / final_edge, the device functions k_corner / k_final_s run, with the limited slopes read from the
-// arrays k_trace wrote instead of being recomputed (same values), so the result is bit-identical to the split passes.
-// SLA: the limited slopes come from the arrays k_trace wrote (true) or are recomputed from q (false: 24 B per cell and component less
-// HBM traffic, the slope arithmetic again; same values)
+// Arithmetic: corner_at / final_edge.  SLA: the limited slopes come from the arrays k_trace wrote (true, the one form instantiated)
+// or are recomputed from q (false; same values)
 template <bool PRED, int D, int TX, int TY, bool SLA>
 __global__ void __launch_bounds__((2 * (((TX + 1) * (TY + 1) + 63) / 64) + (TX * TY + 63) / 64) * 64) k_dir(const BoxD* __restrict__ boxes,
     const FabD* __restrict__ qt, const FabD* __restrict__ ft, const FabD* __restrict__ divut,
@@ -961,20 +759,6 @@ static const GodParams* upload_params(const GodParams& P)
     return d;
 }
 
-// planes marched per thread.  Kernels whose stencil extends in z re-read the planes shared with the z-neighbouring tiles;
-// those tiles are far apart in launch order, so the re-reads miss L2: march more planes per thread there.
-static int tz_for(bool z_stencil)
-{
-    const int tzz = (int)tune("GODUNOV_TZ", 4);
-    return z_stencil ? tzz : 4;
-}
-
-static bool comp_split()
-{
-    const int v = (int)tune("GODUNOV_COMP_SPLIT", 0);
-    return v != 0;
-}
-
 static Tiling face_tiling(const Layout& l, int D, int gt, int tz)
 {
     int ml[3];
@@ -983,111 +767,39 @@ static Tiling face_tiling(const Layout& l, int D, int gt, int tz)
 }
 
 template <bool PRED, int D>
-static void launch_trace(const Layout& l, const MultiFab& q, const MultiFab* force, const MultiFab& mac, const MultiFab& e0, const MultiFab* sl,
+static void launch_trace(const Layout& l, const MultiFab& q, const MultiFab* force, const MultiFab& mac, const MultiFab& e0, const MultiFab& sl,
                          const GodParams* dP)
 {
-    Tiling t = face_tiling(l, D, 1, tz_for(D == 2));
+    Tiling t = face_tiling(l, D, 1, 4);
     hipLaunchKernelGGL((k_trace<PRED, D>), t.grid(), Tiling::block(), 0, Context::get().stream, t, l.d_boxes, q.d_tab,
-                       force ? force->d_tab : nullptr, mac.d_tab, e0.d_tab, sl ? sl->d_tab : nullptr, dP);
+                       force ? force->d_tab : nullptr, mac.d_tab, e0.d_tab, sl.d_tab, dP);
 }
 
-static bool use_fused_final()
-{
-    const int v = tune("GODUNOV_FUSED", 0) == 1 ? 1 : 0;
-    return v == 1;
-}
-
-template <bool PRED, int D, int T>
-static void launch_corner(const Layout& l, const MultiFab& q, const MultiFab* force, const MultiFab* divu, const MultiFab& mT,
-                          const MultiFab& mO, const MultiFab& eO, MultiFab& out, const GodParams* dP)
-{
-    int ml[3];
-    for (int e = 0; e < 3; ++e) ml[e] = l.max_len[e] + (e == T ? 1 : 0) + (e == D ? 2 : 0);
-    Tiling t = make_tiling(ml, l.nlocal(), tz_for(T == 2 || D == 2));
-    dim3 gr = t.grid();
-    if (!PRED && comp_split()) gr.z = (unsigned)out.ncomp;
-    hipLaunchKernelGGL((k_corner<PRED, D, T>), gr, Tiling::block(), 0, Context::get().stream, t, l.d_boxes, q.d_tab,
-                       force ? force->d_tab : nullptr, divu ? divu->d_tab : nullptr, mT.d_tab, mO.d_tab, eO.d_tab, out.d_tab, dP);
-}
-
-template <bool PRED, int D>
-static void launch_final_split(const Layout& l, const MultiFab& q, int ncomp, const MultiFab* force, const MultiFab* divu,
-                               MultiFab* const mac[3], const MultiFab e0[3], MultiFab& out, const GodParams* dP)
-{
-    constexpr int TA = D == 0 ? 1 : 0;
-    constexpr int TB = D == 2 ? 1 : 2;
-    const int nc = PRED ? 1 : ncomp;
-    MultiFab cA(q.layout, face_type(TA), nc, 1), cB(q.layout, face_type(TB), nc, 1);
-    launch_corner<PRED, D, TA>(l, q, force, divu, *mac[TA], *mac[TB], e0[TB], cA, dP);
-    launch_corner<PRED, D, TB>(l, q, force, divu, *mac[TB], *mac[TA], e0[TA], cB, dP);
-    Tiling t = face_tiling(l, D, 0, tz_for(true));
-    dim3 gr = t.grid();
-    if (!PRED && comp_split()) gr.z = (unsigned)nc;
-    hipLaunchKernelGGL((k_final_s<PRED, D>), gr, Tiling::block(), 0, Context::get().stream, t, l.d_boxes, q.d_tab,
-                       force ? force->d_tab : nullptr, divu ? divu->d_tab : nullptr, mac[D]->d_tab, mac[TA]->d_tab, mac[TB]->d_tab,
-                       cA.d_tab, cB.d_tab, out.d_tab, dP);
-}
-
-static bool use_dir_fused()
-{
-    const int v = (int)tune("GODUNOV_DIR", 1);
-    return v != 0;
-}
-
-template <bool PRED, int D, int DTX, int DTY>
-static void launch_dir_t(const Layout& l, const MultiFab& q, int ncomp, const MultiFab* force, const MultiFab* divu,
-                       MultiFab* const mac[3], const MultiFab e0[3], const MultiFab sl[3], MultiFab& out, const GodParams* dP)
-{
-    constexpr int TA = D == 0 ? 1 : 0;
-    constexpr int TB = D == 2 ? 1 : 2;
-    constexpr int TX = DTX, TY = DTY;
-    constexpr int NT = (2 * (((TX + 1) * (TY + 1) + 63) / 64) + (TX * TY + 63) / 64) * 64;
-    int nf[3];
-    for (int e = 0; e < 3; ++e) nf[e] = l.max_len[e] + (e == D ? 1 : 0);
-    const int ntx = (nf[0] + TX - 1) / TX, nty = (nf[1] + TY - 1) / TY;
-    const int kc_env = (int)tune("GODUNOV_KC", 0);
-    const int kc = kc_env > 0 ? kc_env : std::min(32, std::max(8, nf[2] / 8));       // planes marched per workgroup
-    const int nkc = (nf[2] + kc - 1) / kc;
-    const int total = ntx * nty * nkc;
-    const int xcd_cnt = total >= 64 ? (total + 7) / 8 : 0;
-    dim3 grid((unsigned)(xcd_cnt > 0 ? 8 * xcd_cnt : total), (unsigned)l.nlocal(), (unsigned)(PRED ? 1 : ncomp));
-    const bool sla = tune("GODUNOV_DIR_SLOPES", 1) != 0;
-#define IAMRX_KDIR(SLA) hipLaunchKernelGGL((k_dir<PRED, D, TX, TY, SLA>), grid, dim3(NT), 0, Context::get().stream, l.d_boxes, q.d_tab, \
-                       force ? force->d_tab : nullptr, divu ? divu->d_tab : nullptr, mac[D]->d_tab, mac[TA]->d_tab, mac[TB]->d_tab, \
-                       e0[TA].d_tab, e0[TB].d_tab, sl[D].d_tab, sl[TA].d_tab, sl[TB].d_tab, out.d_tab, dP, ntx, nty, nkc, kc, xcd_cnt)
-    if (sla) IAMRX_KDIR(true); else IAMRX_KDIR(false);
-#undef IAMRX_KDIR
-}
-
+// pass 2 of direction D: k_dir on 16 x 8 tiles (8 wavefronts, 2 workgroups per CU) with the slopes k_trace wrote
 template <bool PRED, int D>
 static void launch_dir(const Layout& l, const MultiFab& q, int ncomp, const MultiFab* force, const MultiFab* divu,
                        MultiFab* const mac[3], const MultiFab e0[3], const MultiFab sl[3], MultiFab& out, const GodParams* dP)
 {
-    // 16 x 8 tiles (8 wavefronts, 2 workgroups per CU) measured 6% faster than 32 x 8 (14 wavefronts, 1 per CU) at 256^3
-    const int tx = (int)tune("GODUNOV_DIR_TX", 16);
-    const int ty = (int)tune("GODUNOV_DIR_TY", 8);
-    if (tx == 16 && ty == 4) launch_dir_t<PRED, D, 16, 4>(l, q, ncomp, force, divu, mac, e0, sl, out, dP);
-    else if (tx == 32 && ty == 4) launch_dir_t<PRED, D, 32, 4>(l, q, ncomp, force, divu, mac, e0, sl, out, dP);
-    else if (tx == 16) launch_dir_t<PRED, D, 16, 8>(l, q, ncomp, force, divu, mac, e0, sl, out, dP);
-    else launch_dir_t<PRED, D, 32, 8>(l, q, ncomp, force, divu, mac, e0, sl, out, dP);
-}
-
-template <bool PRED, int D>
-static void launch_final(const Layout& l, const MultiFab& q, const MultiFab* force, const MultiFab* divu, MultiFab* const mac[3],
-                         const MultiFab e0[3], const MultiFab sl[3], MultiFab& out, const GodParams* dP)
-{
-    if (use_dir_fused()) { launch_dir<PRED, D>(l, q, e0[0].ncomp, force, divu, mac, e0, sl, out, dP); return; }
-    if (!use_fused_final()) { launch_final_split<PRED, D>(l, q, e0[0].ncomp, force, divu, mac, e0, out, dP); return; }
-    Tiling t = face_tiling(l, D, 0, 4);
-    hipLaunchKernelGGL((k_final<PRED, D>), t.grid(), Tiling::block(), 0, Context::get().stream, t, l.d_boxes, q.d_tab,
-                       force ? force->d_tab : nullptr, divu ? divu->d_tab : nullptr, mac[0]->d_tab, mac[1]->d_tab, mac[2]->d_tab,
-                       e0[0].d_tab, e0[1].d_tab, e0[2].d_tab, out.d_tab, dP);
+    constexpr int TA = D == 0 ? 1 : 0;
+    constexpr int TB = D == 2 ? 1 : 2;
+    constexpr int TX = 16, TY = 8;
+    constexpr int NT = (2 * (((TX + 1) * (TY + 1) + 63) / 64) + (TX * TY + 63) / 64) * 64;
+    int nf[3];
+    for (int e = 0; e < 3; ++e) nf[e] = l.max_len[e] + (e == D ? 1 : 0);
+    const int ntx = (nf[0] + TX - 1) / TX, nty = (nf[1] + TY - 1) / TY;
+    const int kc = std::min(32, std::max(8, nf[2] / 8));       // planes marched per workgroup
+    const int nkc = (nf[2] + kc - 1) / kc;
+    const int total = ntx * nty * nkc;
+    const int xcd_cnt = total >= 64 ? (total + 7) / 8 : 0;
+    dim3 grid((unsigned)(xcd_cnt > 0 ? 8 * xcd_cnt : total), (unsigned)l.nlocal(), (unsigned)(PRED ? 1 : ncomp));
+    hipLaunchKernelGGL((k_dir<PRED, D, TX, TY, true>), grid, dim3(NT), 0, Context::get().stream, l.d_boxes, q.d_tab,
+                       force ? force->d_tab : nullptr, divu ? divu->d_tab : nullptr, mac[D]->d_tab, mac[TA]->d_tab, mac[TB]->d_tab,
+                       e0[TA].d_tab, e0[TB].d_tab, sl[D].d_tab, sl[TA].d_tab, sl[TB].d_tab, out.d_tab, dP, ntx, nty, nkc, kc, xcd_cnt);
 }
 
 static bool use_z_kernel();
-static void godunov_pred_z(const Layout& l, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3], const GodParams* dP, bool bcs, bool ppm, const Geometry& g,
+static void godunov_pred_z(const Layout& l, const Geometry& g, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3], const GodParams* dP, bool ppm,
                            bool fit);
-static void set_scheme(int scheme);
 
 void godunov_extrap_vel_to_faces(const Geometry& g, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3],
                                  double dt, const BCRec* bc, bool use_forces_in_trans, int scheme)
@@ -1099,24 +811,23 @@ void godunov_extrap_vel_to_faces(const Geometry& g, const MultiFab& vel, const M
     IAMRX_ASSERT(!force || force->ngrow >= 1);
     const Layout& l = *vel.layout;
     if (use_z_kernel()) {
-        godunov_pred_z(l, vel, force, umac, upload_params(make_params(g, dt, 3, bc, nullptr, true, use_forces_in_trans, force != nullptr, false)),
-                       !(g.periodic[0] && g.periodic[1] && g.periodic[2]), scheme == 1, g, use_forces_in_trans);
+        godunov_pred_z(l, g, vel, force, umac, upload_params(make_params(g, dt, 3, bc, nullptr, true, use_forces_in_trans, force != nullptr, false)),
+                       scheme == 1, use_forces_in_trans);
         return;
     }
     MultiFab ad[3], e0[3], sl[3];
     MultiFab* adp[3];
     for (int d = 0; d < 3; ++d) {
         ad[d].define(vel.layout, face_type(d), 1, 1); e0[d].define(vel.layout, face_type(d), 3, 1); adp[d] = &ad[d];
-        if (use_dir_fused()) sl[d].define(vel.layout, cell_type(), 3, 1);
+        sl[d].define(vel.layout, cell_type(), 3, 1);
     }
-    const bool ws = use_dir_fused();
     const GodParams* dP = upload_params(make_params(g, dt, 3, bc, nullptr, true, use_forces_in_trans, force != nullptr, false));
-    launch_trace<true, 0>(l, vel, force, ad[0], e0[0], ws ? &sl[0] : nullptr, dP);
-    launch_trace<true, 1>(l, vel, force, ad[1], e0[1], ws ? &sl[1] : nullptr, dP);
-    launch_trace<true, 2>(l, vel, force, ad[2], e0[2], ws ? &sl[2] : nullptr, dP);
-    launch_final<true, 0>(l, vel, force, nullptr, adp, e0, sl, *umac[0], dP);
-    launch_final<true, 1>(l, vel, force, nullptr, adp, e0, sl, *umac[1], dP);
-    launch_final<true, 2>(l, vel, force, nullptr, adp, e0, sl, *umac[2], dP);
+    launch_trace<true, 0>(l, vel, force, ad[0], e0[0], sl[0], dP);
+    launch_trace<true, 1>(l, vel, force, ad[1], e0[1], sl[1], dP);
+    launch_trace<true, 2>(l, vel, force, ad[2], e0[2], sl[2], dP);
+    launch_dir<true, 0>(l, vel, 3, force, nullptr, adp, e0, sl, *umac[0], dP);
+    launch_dir<true, 1>(l, vel, 3, force, nullptr, adp, e0, sl, *umac[1], dP);
+    launch_dir<true, 2>(l, vel, 3, force, nullptr, adp, e0, sl, *umac[2], dP);
 }
 
 // -------------------------------------------------------------------------------- pass 3
@@ -1159,308 +870,6 @@ __global__ void __launch_bounds__(256) k_aofs(Tiling t, const BoxD* __restrict__
     }
 }
 
-// -------------------------------------------------------------------------------- single-pass tile kernel (advection)
-// One workgroup = one TXxTYxTZ tile of cells and one component at a time.  The state tile (3 ghost cells) is staged in
-// LDS, the pass-1 transverse states E[d], the corner-coupled states C (two arrays per final direction) and the final edge
-// states G[d] of the tile never leave LDS, and aofs is written straight from them: per cell and component HBM sees the
-// state, the forcing, the mac velocities and aofs -- the algorithmic traffic of SURVEY 8d -- instead of 6+3 intermediate
-// face arrays.  Faces on tile boundaries (and the one-cell rings the corner coupling needs) are recomputed by both tiles
-// with identical arithmetic, so the result is bit-identical to the multi-pass kernels above.
-struct LBox {
-    int lo0, lo1, lo2, n0, n1, n2;
-    __device__ __forceinline__ int off(int i, int j, int k) const { return (i - lo0) + n0 * ((j - lo1) + n1 * (k - lo2)); }
-    __device__ __forceinline__ int size() const { return n0 * n1 * n2; }
-    template <int D> __device__ __forceinline__ int stride() const { return D == 0 ? 1 : (D == 1 ? n0 : n0 * n1); }
-    __device__ __forceinline__ void ijk(int idx, int& i, int& j, int& k) const
-    {
-        i = lo0 + idx % n0; const int r = idx / n0; j = lo1 + r % n1; k = lo2 + r / n1;
-    }
-};
-__device__ __forceinline__ LBox make_lbox(const int lo[3], const int hi[3])
-{
-    LBox b; b.lo0 = lo[0]; b.lo1 = lo[1]; b.lo2 = lo[2]; b.n0 = hi[0] - lo[0] + 1; b.n1 = hi[1] - lo[1] + 1; b.n2 = hi[2] - lo[2] + 1; return b;
-}
-
-struct TileCtx {
-    const GodParams* P;
-    FabD q, frc, dv, mac[3];
-    bool has_force, has_divu, fit, is_vel;
-    int tlo[3], thi[3];
-    LBox qb, eb[3], gb[3], mb[3], fb;
-    double *Qs, *Es[3], *Gs[3], *Ca, *Cb, *Ms[3], *Fs;
-};
-
-// pass 1 on the tile: E[D] on the D-faces [tlo_D, thi_D+1] x (transverse cells grown by 1)
-template <int D>
-__device__ __forceinline__ void tile_stage1(const TileCtx& c, int n)
-{
-    const GodParams& P = *c.P;
-    const LBox eb = c.eb[D];
-    const int s = c.qb.template stride<D>();
-    const double hdt = 0.5 * P.dt, dtdx = P.dt / P.dx[D];
-    const int domlo = P.bc.dlo[D], domhi = P.bc.dhi[D];
-    const bool nonper = !P.bc.per[D];
-    const int bl = P.bc.bc[n].lo[D], bh = P.bc.bc[n].hi[D];
-    const bool edlo = nonper && ed_or_ho(bl), edhi = nonper && ed_or_ho(bh);
-    const int fs = c.fb.template stride<D>();
-    for (int idx = threadIdx.x; idx < eb.size(); idx += blockDim.x) {
-        int i, j, k; eb.ijk(idx, i, j, k);
-        const int f = D == 0 ? i : (D == 1 ? j : k);
-        const double uad = c.Ms[D][c.mb[D].off(i, j, k)];
-        const double fu = (fabs(uad) < SMALL_VEL) ? 0.0 : 1.0;
-        const double* qn = c.Qs + c.qb.off(i, j, k);
-        double l, h;
-        trace_lohi<false>(qn, nullptr, s, uad, dtdx, edlo, edhi, f, domlo, domhi, l, h);
-        if (c.fit && c.has_force) { const int fo = c.fb.off(i, j, k); l += hdt * c.Fs[fo - fs]; h += hdt * c.Fs[fo]; }
-        if (nonper) trans_bc(qn, s, f, c.is_vel && n == D, l, h, bl, bh, domlo, domhi);
-        const double st = (uad >= 0.) ? l : h;
-        c.Es[D][idx] = fu * st + (1.0 - fu) * 0.5 * (h + l);
-    }
-}
-
-// pass 2a on the tile: corner-coupled states on the T-faces [tlo_T, thi_T+1], D cells grown by 1, O cells of the tile
-template <int D, int T>
-__device__ __forceinline__ void tile_corner(const TileCtx& c, int n, double* out, const LBox& cb)
-{
-    constexpr int O = 3 - D - T;
-    const GodParams& P = *c.P;
-    const bool conserv = P.iconserv[n] != 0;
-    const double c_o = conserv ? P.dt / (3.0 * P.dx[O]) : P.dt / (6.0 * P.dx[O]);
-    const double dt3 = P.dt / 3.0, dtdxT = P.dt / P.dx[T], hdt = 0.5 * P.dt;
-    const bool nonperT = !P.bc.per[T];
-    const int dlo = P.bc.dlo[T], dhi = P.bc.dhi[T];
-    const int qsT = c.qb.template stride<T>();
-    const LBox eo = c.eb[O];
-    const int eOsT = eo.template stride<T>(), eOsO = eo.template stride<O>();
-    const LBox mo = c.mb[O];
-    const int mOsT = mo.template stride<T>(), mOsO = mo.template stride<O>();
-    const int fsT = c.fb.template stride<T>();
-    const long dsT = c.has_divu ? stride_of<T>(c.dv) : 0;
-    for (int idx = threadIdx.x; idx < cb.size(); idx += blockDim.x) {
-        int i, j, k; cb.ijk(idx, i, j, k);
-        const int fT = T == 0 ? i : (T == 1 ? j : k);
-        const double macT = c.Ms[T][c.mb[T].off(i, j, k)];
-        out[idx] = corner_state<false>(c.Qs + c.qb.off(i, j, k), nullptr, qsT, fT, macT, c.Ms[O] + mo.off(i, j, k), mOsT, mOsO,
-            c.Es[O] + eo.off(i, j, k), eOsT, eOsO, c.has_force ? c.Fs + c.fb.off(i, j, k) : nullptr, fsT, dtdxT, c_o, dt3,
-            P.dx[O], conserv, c.has_divu ? c.dv.p + c.dv.off(i, j, k) : nullptr, dsT, c.fit, hdt, nonperT, c.is_vel && n == T,
-            P.bc.bc[n].lo[T], P.bc.bc[n].hi[T], dlo, dhi);
-    }
-}
-
-// pass 2b on the tile: final edge states on the D-faces [tlo_D, thi_D+1] of the tile's cells -> G[D]
-template <int D>
-__device__ __forceinline__ void tile_final(const TileCtx& c, int n, const LBox& ab, const LBox& bb)
-{
-    constexpr int TA = D == 0 ? 1 : 0;
-    constexpr int TB = D == 2 ? 1 : 2;
-    const GodParams& P = *c.P;
-    const LBox gb = c.gb[D];
-    const int qsD = c.qb.template stride<D>();
-    const int fsD = c.fb.template stride<D>();
-    const long dsD = c.has_divu ? stride_of<D>(c.dv) : 0;
-    const LBox ma = c.mb[TA], mbx = c.mb[TB];
-    const double* mAp = c.Ms[TA]; const double* mBp = c.Ms[TB];
-    const int mAsD = ma.template stride<D>(), mAsT = ma.template stride<TA>(), mBsD = mbx.template stride<D>(), mBsT = mbx.template stride<TB>();
-    const int cAsD = ab.template stride<D>(), cAsT = ab.template stride<TA>(), cBsD = bb.template stride<D>(), cBsT = bb.template stride<TB>();
-    const double dt = P.dt, hdt = 0.5 * P.dt, dtdxD = dt / P.dx[D];
-    const bool nonperD = !P.bc.per[D];
-    const int dloD = P.bc.dlo[D], dhiD = P.bc.dhi[D];
-    const bool conserv = P.iconserv[n] != 0;
-    const int blD = P.bc.bc[n].lo[D], bhD = P.bc.bc[n].hi[D];
-    const bool edlo = nonperD && ed_or_ho(blD), edhi = nonperD && ed_or_ho(bhD);
-    for (int idx = threadIdx.x; idx < gb.size(); idx += blockDim.x) {
-        int i, j, k; gb.ijk(idx, i, j, k);
-        const int f = D == 0 ? i : (D == 1 ? j : k);
-        const double* qn = c.Qs + c.qb.off(i, j, k);
-        const int fo = c.fb.off(i, j, k);
-        const long dvo = c.has_divu ? c.dv.off(i, j, k) : 0;
-        const int mAo = ma.off(i, j, k), mBo = mbx.off(i, j, k);
-        const double umD = c.Ms[D][c.mb[D].off(i, j, k)];
-        const double mA_l0 = mAp[mAo - mAsD], mA_l1 = mAp[mAo - mAsD + mAsT], mA_h0 = mAp[mAo], mA_h1 = mAp[mAo + mAsT];
-        const double mB_l0 = mBp[mBo - mBsD], mB_l1 = mBp[mBo - mBsD + mBsT], mB_h0 = mBp[mBo], mB_h1 = mBp[mBo + mBsT];
-        double stl, sth;
-        trace_lohi<false>(qn, nullptr, qsD, umD, dtdxD, edlo, edhi, f, dloD, dhiD, stl, sth);
-        if (c.fit && c.has_force) { stl += hdt * c.Fs[fo - fsD]; sth += hdt * c.Fs[fo]; }
-        if (nonperD) trans_bc(qn, qsD, f, c.is_vel && n == D, stl, sth, blD, bhD, dloD, dhiD);
-        const int cAo = ab.off(i, j, k), cBo = bb.off(i, j, k);
-        const double Al0 = c.Ca[cAo - cAsD], Al1 = c.Ca[cAo - cAsD + cAsT], Ah0 = c.Ca[cAo], Ah1 = c.Ca[cAo + cAsT];
-        const double Bl0 = c.Cb[cBo - cBsD], Bl1 = c.Cb[cBo - cBsD + cBsT], Bh0 = c.Cb[cBo], Bh1 = c.Cb[cBo + cBsT];
-        if (conserv) {
-            const double cfA = 0.5 * dt / P.dx[TA], cfB = 0.5 * dt / P.dx[TB];
-            stl += -cfA * (Al1 * mA_l1 - Al0 * mA_l0);
-            sth += -cfA * (Ah1 * mA_h1 - Ah0 * mA_h0);
-            stl += -cfB * (Bl1 * mB_l1 - Bl0 * mB_l0);
-            sth += -cfB * (Bh1 * mB_h1 - Bh0 * mB_h0);
-            stl += cfA * qn[-qsD] * (mA_l1 - mA_l0);
-            sth += cfA * qn[0] * (mA_h1 - mA_h0);
-            stl += cfB * qn[-qsD] * (mB_l1 - mB_l0);
-            sth += cfB * qn[0] * (mB_h1 - mB_h0);
-            if (c.has_divu) { stl -= 0.5 * dt * qn[-qsD] * c.dv.p[dvo - dsD]; sth -= 0.5 * dt * qn[0] * c.dv.p[dvo]; }
-        } else {
-            const double cfA = 0.25 * dt / P.dx[TA], cfB = 0.25 * dt / P.dx[TB];
-            stl -= cfA * (mA_l1 + mA_l0) * (Al1 - Al0);
-            sth -= cfA * (mA_h1 + mA_h0) * (Ah1 - Ah0);
-            stl -= cfB * (mB_l1 + mB_l0) * (Bl1 - Bl0);
-            sth -= cfB * (mB_h1 + mB_h0) * (Bh1 - Bh0);
-        }
-        if (!c.fit && c.has_force) { stl += hdt * c.Fs[fo - fsD]; sth += hdt * c.Fs[fo]; }
-        if (nonperD) edge_bc(qn, qsD, f, c.is_vel && n == D, stl, sth, blD, bhD, dloD, dhiD);
-        double temp = (umD >= 0.) ? stl : sth;
-        temp = (fabs(umD) < SMALL_VEL) ? 0.5 * (stl + sth) : temp;
-        c.Gs[D][idx] = temp;
-    }
-}
-
-// both corner arrays + the final states of direction D
-template <int D>
-__device__ __forceinline__ void tile_direction(const TileCtx& c, int n)
-{
-    constexpr int TA = D == 0 ? 1 : 0;
-    constexpr int TB = D == 2 ? 1 : 2;
-    int lo[3], hi[3];
-    for (int e = 0; e < 3; ++e) { lo[e] = c.tlo[e]; hi[e] = c.thi[e]; }
-    lo[D] -= 1; hi[D] += 1;
-    int la[3] = {lo[0], lo[1], lo[2]}, ha[3] = {hi[0], hi[1], hi[2]};
-    ha[TA] += 1;
-    const LBox ab = make_lbox(la, ha);
-    int lb[3] = {lo[0], lo[1], lo[2]}, hb[3] = {hi[0], hi[1], hi[2]};
-    hb[TB] += 1;
-    const LBox bb = make_lbox(lb, hb);
-    tile_corner<D, TA>(c, n, c.Ca, ab);
-    tile_corner<D, TB>(c, n, c.Cb, bb);
-    __syncthreads();
-    tile_final<D>(c, n, ab, bb);
-    __syncthreads();
-}
-
-template <int TX, int TY, int TZ, int NTH>
-__global__ void __launch_bounds__(NTH) k_godunov_tile(const BoxD* __restrict__ boxes, const FabD* __restrict__ qt, const FabD* __restrict__ ft,
-    const FabD* __restrict__ divut, const FabD* __restrict__ uxt, const FabD* __restrict__ uyt, const FabD* __restrict__ uzt,
-    const FabD* __restrict__ aofst, int acomp, const FabD* __restrict__ e0t, const FabD* __restrict__ e1t, const FabD* __restrict__ e2t,
-    const FabD* __restrict__ f0t, const FabD* __restrict__ f1t, const FabD* __restrict__ f2t,
-    const GodParams* __restrict__ Pp, int ntx, int nty, int ntz)
-{
-    constexpr int NQ = (TX + 6) * (TY + 6) * (TZ + 6);
-    constexpr int NE0 = (TX + 1) * (TY + 2) * (TZ + 2), NE1 = (TX + 2) * (TY + 1) * (TZ + 2), NE2 = (TX + 2) * (TY + 2) * (TZ + 1);
-    constexpr int NG0 = (TX + 1) * TY * TZ, NG1 = TX * (TY + 1) * TZ, NG2 = TX * TY * (TZ + 1);
-    constexpr int c01 = (TX + 2) * (TY + 1) * TZ, c02 = (TX + 2) * TY * (TZ + 1);     // D = 0: T = 1, 2
-    constexpr int c10 = (TX + 1) * (TY + 2) * TZ, c12 = TX * (TY + 2) * (TZ + 1);     // D = 1: T = 0, 2
-    constexpr int c20 = (TX + 1) * TY * (TZ + 2), c21 = TX * (TY + 1) * (TZ + 2);     // D = 2: T = 0, 1
-    constexpr int NCA = c01 > c10 ? (c01 > c20 ? c01 : c20) : (c10 > c20 ? c10 : c20);
-    constexpr int NCB = c02 > c12 ? (c02 > c21 ? c02 : c21) : (c12 > c21 ? c12 : c21);
-    __shared__ double Qs[NQ];
-    __shared__ double E0[NE0], E1[NE1], E2[NE2];
-    __shared__ double G0[NG0], G1[NG1], G2[NG2];
-    __shared__ double Ca[NCA], Cb[NCB];
-    constexpr int NM0 = (TX + 3) * (TY + 2) * (TZ + 2), NM1 = (TX + 2) * (TY + 3) * (TZ + 2), NM2 = (TX + 2) * (TY + 2) * (TZ + 3);
-    constexpr int NF = (TX + 2) * (TY + 2) * (TZ + 2);
-    __shared__ double M0[NM0], M1[NM1], M2[NM2];
-    __shared__ double Fs[NF];
-    const GodParams& P = *Pp;
-    const int fab = blockIdx.y;
-    const BoxD bx = boxes[fab];
-    const int bid = blockIdx.x;
-    const int tix = bid % ntx, r1 = bid / ntx, tiy = r1 % nty, tiz = r1 / nty;
-    TileCtx c;
-    c.P = Pp;
-    c.tlo[0] = bx.lo[0] + tix * TX; c.tlo[1] = bx.lo[1] + tiy * TY; c.tlo[2] = bx.lo[2] + tiz * TZ;
-    if (c.tlo[0] > bx.hi[0] || c.tlo[1] > bx.hi[1] || c.tlo[2] > bx.hi[2]) return;
-    c.thi[0] = min(c.tlo[0] + TX - 1, bx.hi[0]); c.thi[1] = min(c.tlo[1] + TY - 1, bx.hi[1]); c.thi[2] = min(c.tlo[2] + TZ - 1, bx.hi[2]);
-    c.q = qt[fab];
-    c.has_force = P.has_force != 0; c.has_divu = P.has_divu != 0; c.fit = P.fit != 0; c.is_vel = P.is_velocity != 0;
-    if (c.has_force) c.frc = ft[fab];
-    if (c.has_divu) c.dv = divut[fab];
-    c.mac[0] = uxt[fab]; c.mac[1] = uyt[fab]; c.mac[2] = uzt[fab];
-    c.Ms[0] = M0; c.Ms[1] = M1; c.Ms[2] = M2; c.Fs = Fs;
-    c.Qs = Qs; c.Es[0] = E0; c.Es[1] = E1; c.Es[2] = E2; c.Gs[0] = G0; c.Gs[1] = G1; c.Gs[2] = G2; c.Ca = Ca; c.Cb = Cb;
-    {
-        int lo[3], hi[3];
-        for (int e = 0; e < 3; ++e) { lo[e] = c.tlo[e] - 3; hi[e] = c.thi[e] + 3; }
-        c.qb = make_lbox(lo, hi);
-        for (int d = 0; d < 3; ++d) {
-            for (int e = 0; e < 3; ++e) { lo[e] = c.tlo[e] - (e == d ? 0 : 1); hi[e] = c.thi[e] + 1; }
-            c.eb[d] = make_lbox(lo, hi);
-            for (int e = 0; e < 3; ++e) { lo[e] = c.tlo[e]; hi[e] = c.thi[e] + (e == d ? 1 : 0); }
-            c.gb[d] = make_lbox(lo, hi);
-            for (int e = 0; e < 3; ++e) { lo[e] = c.tlo[e] - 1; hi[e] = c.thi[e] + 1 + (e == d ? 1 : 0); }
-            c.mb[d] = make_lbox(lo, hi);
-        }
-        for (int e = 0; e < 3; ++e) { lo[e] = c.tlo[e] - 1; hi[e] = c.thi[e] + 1; }
-        c.fb = make_lbox(lo, hi);
-    }
-    // the mac velocities of the tile (cells grown by 1) are shared by all components
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const FabD::gdouble* mp = (const FabD::gdouble*)c.mac[d].p;
-        for (int idx = threadIdx.x; idx < c.mb[d].size(); idx += NTH) {
-            int i, j, k; c.mb[d].ijk(idx, i, j, k);
-            c.Ms[d][idx] = mp[c.mac[d].off(i, j, k)];
-        }
-    }
-    const FabD aofs = aofst[fab];
-    const double dx0 = P.dx[0], dx1 = P.dx[1], dx2 = P.dx[2];
-    const double ax = dx1 * dx2, ay = dx2 * dx0, az = dx0 * dx1;
-    const double qvol = 1.0 / (dx0 * dx1 * dx2);
-    const int ncomp = P.ncomp;
-    const int tnx = c.thi[0] - c.tlo[0] + 1, tny = c.thi[1] - c.tlo[1] + 1, tnz = c.thi[2] - c.tlo[2] + 1;
-    for (int n = 0; n < ncomp; ++n) {
-        // stage the state tile (3 ghost cells) of component n
-        {
-            const FabD::gdouble* qp = (const FabD::gdouble*)c.q.p + c.q.cs * n;
-            for (int idx = threadIdx.x; idx < c.qb.size(); idx += NTH) {
-                int i, j, k; c.qb.ijk(idx, i, j, k);
-                Qs[idx] = qp[c.q.off(i, j, k)];
-            }
-            if (c.has_force) {
-                const FabD::gdouble* fp = (const FabD::gdouble*)c.frc.p + c.frc.cs * n;
-                for (int idx = threadIdx.x; idx < c.fb.size(); idx += NTH) {
-                    int i, j, k; c.fb.ijk(idx, i, j, k);
-                    Fs[idx] = fp[c.frc.off(i, j, k)];
-                }
-            }
-        }
-        __syncthreads();
-        tile_stage1<0>(c, n);
-        tile_stage1<1>(c, n);
-        tile_stage1<2>(c, n);
-        __syncthreads();
-        tile_direction<0>(c, n);
-        tile_direction<1>(c, n);
-        tile_direction<2>(c, n);
-        // aofs (ComputeFluxes, ComputeDivergence(-1), ComputeConvectiveTerm) and the optional edge-state / flux outputs
-        for (int idx = threadIdx.x; idx < tnx * tny * tnz; idx += NTH) {
-            const int i = c.tlo[0] + idx % tnx, r = idx / tnx, j = c.tlo[1] + r % tny, k = c.tlo[2] + r / tny;
-            const double uxl = M0[c.mb[0].off(i, j, k)], uxh = M0[c.mb[0].off(i + 1, j, k)], uyl = M1[c.mb[1].off(i, j, k)], uyh = M1[c.mb[1].off(i, j + 1, k)];
-            const double uzl = M2[c.mb[2].off(i, j, k)], uzh = M2[c.mb[2].off(i, j, k + 1)];
-            const double exl = G0[c.gb[0].off(i, j, k)], exh = G0[c.gb[0].off(i + 1, j, k)];
-            const double eyl = G1[c.gb[1].off(i, j, k)], eyh = G1[c.gb[1].off(i, j + 1, k)];
-            const double ezl = G2[c.gb[2].off(i, j, k)], ezh = G2[c.gb[2].off(i, j, k + 1)];
-            const double fxl = exl * uxl * ax, fxh = exh * uxh * ax, fyl = eyl * uyl * ay, fyh = eyh * uyh * ay, fzl = ezl * uzl * az, fzh = ezh * uzh * az;
-            if (e0t) {
-                e0t[fab](i, j, k, n) = exl; e1t[fab](i, j, k, n) = eyl; e2t[fab](i, j, k, n) = ezl;
-                if (i == bx.hi[0]) e0t[fab](i + 1, j, k, n) = exh;
-                if (j == bx.hi[1]) e1t[fab](i, j + 1, k, n) = eyh;
-                if (k == bx.hi[2]) e2t[fab](i, j, k + 1, n) = ezh;
-            }
-            if (f0t) {
-                f0t[fab](i, j, k, n) = fxl; f1t[fab](i, j, k, n) = fyl; f2t[fab](i, j, k, n) = fzl;
-                if (i == bx.hi[0]) f0t[fab](i + 1, j, k, n) = fxh;
-                if (j == bx.hi[1]) f1t[fab](i, j + 1, k, n) = fyh;
-                if (k == bx.hi[2]) f2t[fab](i, j, k + 1, n) = fzh;
-            }
-            double upd = -1.0 * qvol * ((fxh - fxl) + (fyh - fyl) + (fzh - fzl));
-            if (!P.iconserv[n]) {
-                const double divum = 1.0 * ((uxh - uxl) / dx0 + (uyh - uyl) / dx1 + (uzh - uzl) / dx2);
-                double qavg = exl + exh + eyl + eyh + ezl + ezh;
-                qavg *= 1.0 / 6.0;
-                upd += qavg * divum;
-            }
-            aofs(i, j, k, acomp + n) = -upd;
-        }
-        __syncthreads();
-    }
-}
-
 // -------------------------------------------------------------------------------- fused z-marching advection (default, PLM)
 // k_god_z: one launch = ComputeFluxesOnBoxFromState + ComputeDivergence / ComputeConvectiveTerm for one component per blockIdx.z.
 // A workgroup owns a TX x TY column of cells and marches through the planes of its z-chunk; thread (ci,cj) of the tile grown by one
@@ -1500,7 +909,6 @@ static GodChunks god_chunks(int len, int kc, bool thin_ends)
 // XCD 0 and 7 in the XCD-aware order: measured 3.83 + 1.89 ms against 5.19 ms for the one-launch wall variant at 256^3).
 // Boundary-condition code looks at the cells dlo, dlo + 1, dhi - 1, dhi (slopes) and the faces dlo, dhi + 1; a tile forms slopes of the
 // cells tx0 - 2 .. txe + 1 and states of the faces tx0 - 1 .. txe + 1 (likewise in y; planes k0 - 1 .. k1 + 1); one cell of margin.
-struct GodTileList { const int4* d[2]; int n[2]; int xcd_cnt[2]; };
 static bool god_tile_at_wall(const Geometry& g, int tx0, int txe, int ty0, int tye, int k0, int k1)
 {
     bool w = false;
@@ -1509,44 +917,17 @@ static bool god_tile_at_wall(const Geometry& g, int tx0, int txe, int ty0, int t
     if (!g.periodic[2]) w = w || k0 <= g.domain.lo[2] + 3 || k1 >= g.domain.hi[2] - 3;
     return w;
 }
-// lists [0]: tiles off the walls, [1]: tiles at the walls.  The workgroups b, b + 8, b + 16, ... of a launch run on XCD b % 8 and take the
-// entries [q, q + 1) * xcd_cnt of the list (q = b % 8): the tiles are dealt to eight buckets in runs of neighbouring tiles (shared halos meet in
-// one L2), each run to the bucket with the least work so far (work of a tile = the planes it marches + its prologue; the wall list mixes
-// tiles of 8 and of ~60 planes), the longest tiles first inside a bucket; short buckets are padded with dead entries (fab < 0).
-// Cached per (layout, tile shape, chunks, domain).
-static GodTileList god_tile_lists(const Layout& l, const Geometry& g, int TX, int TY, const GodChunks& zc)
+// list[0]: tiles off the walls, list[1]: tiles at the walls, of the boxes given (host data only).  The workgroups b, b + 8, b + 16, ... of a
+// launch run on XCD b % 8 and take the entries [q, q + 1) * xcd_cnt of the list (q = b % 8): the tiles are dealt to eight buckets in runs of
+// neighbouring tiles (shared halos meet in one L2), each run to the bucket with the least work so far (work of a tile = the planes it marches
+// + its prologue; the wall list mixes tiles of 8 and of ~60 planes), the longest tiles first inside a bucket; short buckets are padded with
+// dead entries (fab < 0).  A class of fewer than 64 tiles is listed in box order, without padding: xcd_cnt = 0.
+static void god_tile_lists_host(const BoxD* boxes, int nboxes, const Geometry& g, int TX, int TY, const GodChunks& zc, std::vector<int4> list[2])
 {
-    struct Entry { std::vector<long> key; int4* d[2]; int n[2]; int xc[2]; };
-    static std::vector<Entry> cache;
-    // entries leave with their layout (a regridding run on a domain with walls makes a new layout per regrid: ADVICE round 5) ...
-    static const bool registered = [] {
-        register_layout_evictor([](uint64_t lid) {
-            bool any = false;
-            for (const Entry& e : cache) any = any || (uint64_t)e.key[0] == lid;
-            if (!any) return;
-            Context::get().sync();
-            for (auto it = cache.begin(); it != cache.end();) {
-                if ((uint64_t)it->key[0] != lid) { ++it; continue; }
-                for (int c = 0; c < 2; ++c) if (it->d[c]) (void)hipFree(it->d[c]);
-                it = cache.erase(it);
-            }
-        });
-        return true;
-    }();
-    (void)registered;
-    std::vector<long> key = {(long)l.id, TX, TY, zc.n};
-    for (int i = 0; i <= zc.n; ++i) key.push_back(zc.start[i]);
-    for (int d = 0; d < 3; ++d) { key.push_back(g.domain.lo[d]); key.push_back(g.domain.hi[d]); key.push_back(g.periodic[d]); }
-    for (const Entry& e : cache) if (e.key == key) return GodTileList{{e.d[0], e.d[1]}, {e.n[0], e.n[1]}, {e.xc[0], e.xc[1]}};
-    if (cache.size() >= 64) {                    // ... (fallback: other tile shapes / chunkings of living layouts)
-        Context::get().sync();
-        for (Entry& e : cache) for (int c = 0; c < 2; ++c) if (e.d[c]) IAMRX_HIP_CHECK(hipFree(e.d[c]));
-        cache.clear();
-    }
     struct T { int4 t; int w; };
     std::vector<T> h[2];
-    for (int f = 0; f < l.nlocal(); ++f) {
-        const BoxD& b = l.lbox(f);
+    for (int f = 0; f < nboxes; ++f) {
+        const BoxD& b = boxes[f];
         const int ntx = (b.len(0) + TX - 1) / TX, nty = (b.len(1) + TY - 1) / TY;
         for (int c = 0; c < zc.n; ++c) {
             const int k0 = b.lo[2] + zc.start[c], k1 = std::min(b.lo[2] + zc.start[c + 1] - 1, b.hi[2]);
@@ -1559,55 +940,138 @@ static GodTileList god_tile_lists(const Layout& l, const Geometry& g, int TX, in
                 }
         }
     }
-    Entry e;
-    e.key = key;
     for (int c = 0; c < 2; ++c) {
-        std::vector<int4> list;
-        e.xc[c] = 0;
-        if (h[c].size() < 64) for (const T& t : h[c]) list.push_back(t.t);
-        else {
-            std::vector<T> bucket[8];
-            long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            constexpr size_t RUN = 6;
-            for (size_t i = 0; i < h[c].size(); i += RUN) {
-                int q = 0;
-                for (int r = 1; r < 8; ++r) if (load[r] < load[q]) q = r;
-                for (size_t j = i; j < std::min(i + RUN, h[c].size()); ++j) { bucket[q].push_back(h[c][j]); load[q] += h[c][j].w; }
-            }
-            size_t mx = 0;
-            for (int q = 0; q < 8; ++q) {
-                std::stable_sort(bucket[q].begin(), bucket[q].end(), [](const T& a, const T& b) { return a.w > b.w; });
-                mx = std::max(mx, bucket[q].size());
-            }
-            for (int q = 0; q < 8; ++q)
-                for (size_t i = 0; i < mx; ++i) list.push_back(i < bucket[q].size() ? bucket[q][i].t : make_int4(-1, 0, 0, 0));
-            e.xc[c] = (int)mx;
+        list[c].clear();
+        if (h[c].size() < 64) { for (const T& t : h[c]) list[c].push_back(t.t); continue; }
+        std::vector<T> bucket[8];
+        long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        constexpr size_t RUN = 6;
+        for (size_t i = 0; i < h[c].size(); i += RUN) {
+            int q = 0;
+            for (int r = 1; r < 8; ++r) if (load[r] < load[q]) q = r;
+            for (size_t j = i; j < std::min(i + RUN, h[c].size()); ++j) { bucket[q].push_back(h[c][j]); load[q] += h[c][j].w; }
         }
-        e.n[c] = (int)list.size(); e.d[c] = nullptr;
-        if (e.n[c] > 0) {
-            IAMRX_HIP_CHECK(hipMalloc(&e.d[c], list.size() * sizeof(int4)));
-            IAMRX_HIP_CHECK(hipMemcpy(e.d[c], list.data(), list.size() * sizeof(int4), hipMemcpyHostToDevice));
+        size_t mx = 0;
+        for (int q = 0; q < 8; ++q) {
+            std::stable_sort(bucket[q].begin(), bucket[q].end(), [](const T& a, const T& b) { return a.w > b.w; });
+            mx = std::max(mx, bucket[q].size());
         }
+        for (int q = 0; q < 8; ++q)
+            for (size_t i = 0; i < mx; ++i) list[c].push_back(i < bucket[q].size() ? bucket[q][i].t : make_int4(-1, 0, 0, 0));
     }
-    cache.push_back(e);
-    return GodTileList{{e.d[0], e.d[1]}, {e.n[0], e.n[1]}, {e.xc[0], e.xc[1]}};
 }
-//
-// Specialised instantiations (IAMRX_GODUNOV_SPEC, default 1).  The flags that are uniform over a launch are template parameters; -1 keeps
-// the flag a run-time value (the kernel as it was: the fallback for every combination not listed, and IAMRX_GODUNOV_SPEC = 0):
+// the list of class cls on the device: it belongs to the layout and leaves with it (layout_int4_list).  The chunks are a function of the
+// layout's max_len, kc and the periodicity in z, so (tile shape, class, kc, domain) identify the list.  (A miss builds both classes on
+// the host and keeps the one asked for: the first call on a layout runs the builder twice, every later one not at all.)
+static const int4* god_tile_list(const Layout& l, const Geometry& g, int TX, int TY, int kc, const GodChunks& zc, int cls, int* n)
+{
+    // (one reference captured, [&a]: the closure fits std::function's inline buffer, so this per-call path allocates nothing -- a
+    // lambda that captures the six names itself would be put on the heap at every call)
+    struct { const Layout& l; const Geometry& g; int TX, TY; const GodChunks& zc; int cls; } a{l, g, TX, TY, zc, cls};
+    return layout_int4_list(l, {5, TX, TY, cls, kc, g.periodic[0] + 2 * g.periodic[1] + 4 * g.periodic[2], g.domain.lo[0], g.domain.hi[0],
+                                g.domain.lo[1], g.domain.hi[1], g.domain.lo[2], g.domain.hi[2]}, [&a](std::vector<int4>& h) {
+        std::vector<BoxD> boxes(a.l.nlocal());
+        for (int f = 0; f < a.l.nlocal(); ++f) boxes[f] = a.l.lbox(f);
+        std::vector<int4> list[2];
+        god_tile_lists_host(boxes.data(), (int)boxes.size(), a.g, a.TX, a.TY, a.zc, list);
+        h.swap(list[a.cls]);
+    }, n);
+}
+
+// ---- THE plan of one call of a fused kernel: which launches, of which instantiation, on which tiles.  Host data only; made at every call
+// (the tuning keys are read at the point of use: the tests switch them between calls), nothing is kept.
 //   FRC  forcing: 0 none, 1 late (use_forces_in_trans = 0), 2 early         DVU  divu: 0 absent, 1 present
 //   OUT  bit 0: edge states are stored, bit 1: fluxes are stored             CNS  0 convective, 1 conservative form
-// A launch runs the components of ONE form: blockIdx.z indexes the component table `comps`, and a call with components of both forms
-// (velocity and tracer convective, density conservative) issues one launch per form -- a dispatch inside one kernel would give every
-// component the registers of the conservative body.  The LDS planes of the forcing and of divu exist only where the flag can be set.
-// Instantiated (14 x 14 tiles, PLM; every one with BCS = false and BCS = true, convective and conservative): what runs with default
-// inputs take -- there the forcing is always present and late, and divu is absent unless the run has a temperature equation (do_temp):
-//   k_god_z   FRC 1, DVU 0 | 1, OUT 0   a level without a coarser or a finer one (TaylorGreen, LidDrivenCavity)
-//   k_god_z   FRC 1, DVU 0 | 1, OUT 2   a level of a hierarchy: the fluxes go to the flux registers
-//   k_pred_z  FRC 1
-// (DVU 1 is the DVU 0 body plus the divu terms: with an array of zeros it gives the doubles of DVU 0, tests/test_gpu_godunov_spec.py.)
-// Everything else (early or no forcing, edge outputs -- the MAC sync --, PPM, 16 x 8 tiles) runs the run-time kernel.
+// are the flags of a launch that k_god_z / k_pred_z take as template parameters; -1 keeps the flag a run-time value (the kernel as it was).
 struct GodComps { int c[GOD_MAXC]; };
+struct GodLaunch {
+    int sel;                    // its tiles: 0 the full tile grid, 1 the list off the walls, 2 the list at the walls
+    bool bcs;                   // the boundary-condition variant of the kernel
+    int frc, dvu, out, cns;     // the instantiation: all -1 (run-time kernel) or specialised (k_pred_z: frc alone)
+    int ncomp;                  // the components the launch computes, comps.c[0 .. ncomp): blockIdx.z of k_god_z
+    GodComps comps;
+};
+struct GodZPlan {
+    bool pred, ppm;             // k_pred_z or k_god_z; the reconstruction
+    int tx, ty;                 // cells of a tile: 14 x 14 or 16 x 8
+    int kc;                     // planes of a z-chunk
+    GodChunks zc;
+    int nlaunch;
+    GodLaunch launch[4];        // in issue order
+};
+struct GodCall { bool ppm, force, fit, divu, edge_out, flux_out; int ncomp; const int* iconserv; };      // what a call is asked for
+// The rules:
+//   tile     16 x 8 if IAMRX_GODUNOV_ZTX (advection) / IAMRX_GODUNOV_PTX (prediction) is 16, else 14 x 14
+//   kc       IAMRX_GODUNOV_ZKC if > 0, else min(64, max(8, max_len[2] / 4))
+//   classes  a fully periodic domain: the full tile grid with the plain code; walls: the tiles no boundary condition reaches run the plain
+//            code (sel 1), the boundary-condition variant takes the rest (sel 2; thin first / last z-chunks where z has walls) --
+//            IAMRX_GODUNOV_SPLIT_BC = 0: the full tile grid with the variant
+//   kernel   a specialised instantiation exists for 14 x 14 tiles, PLM, late forcing and no edge outputs (what runs with default inputs
+//            take; IAMRX_GODUNOV_SPEC = 0 turns them off): k_pred_z with FRC 1; k_god_z with FRC 1, DVU and OUT (0 or 2) as the call has
+//            them and ONE form per launch, the convective components first -- a dispatch inside one kernel would give every component the
+//            registers of the conservative body.  Every other call (early or no forcing, edge outputs -- the MAC sync --, PPM, 16 x 8
+//            tiles) runs the run-time kernel on all components in one launch.
+static GodZPlan god_z_plan(bool pred, const int max_len[3], const Geometry& g, const GodCall& c)
+{
+    GodZPlan p{};
+    p.pred = pred; p.ppm = c.ppm;
+    const bool t16 = (int)(pred ? tune("GODUNOV_PTX", 14) : tune("GODUNOV_ZTX", 14)) == 16;
+    p.tx = t16 ? 16 : 14; p.ty = t16 ? 8 : 14;
+    const int kc_env = (int)tune("GODUNOV_ZKC", 0);
+    p.kc = kc_env > 0 ? kc_env : std::min(64, std::max(8, max_len[2] / 4));
+    const bool walls = !(g.periodic[0] && g.periodic[1] && g.periodic[2]);
+    const bool split = walls && tune("GODUNOV_SPLIT_BC", 1) != 0;
+    p.zc = god_chunks(max_len[2], p.kc, split && !g.periodic[2]);
+    const bool spec = tune("GODUNOV_SPEC", 1) != 0 && !t16 && !c.ppm && c.force && !c.fit && (pred || !c.edge_out);     // (k_pred_z has no outputs to select)
+    for (int cls = 0; cls < (split ? 2 : 1); ++cls)
+        for (int form = 0; form < (spec && !pred ? 2 : 1); ++form) {
+            GodLaunch L{};
+            L.sel = split ? cls + 1 : 0; L.bcs = split ? cls == 1 : walls;
+            L.frc = spec ? 1 : -1;
+            L.dvu = spec && !pred ? (c.divu ? 1 : 0) : -1; L.out = spec && !pred ? (c.flux_out ? 2 : 0) : -1; L.cns = spec && !pred ? form : -1;
+            for (int n = 0; n < c.ncomp; ++n)
+                if (L.cns < 0 || (c.iconserv && c.iconserv[n] != 0) == (form == 1)) L.comps.c[L.ncomp++] = n;
+            if (L.ncomp > 0) p.launch[p.nlaunch++] = L;
+        }
+    return p;
+}
+
+// where the launches of one class run: the grid (z: one entry per component, set by the caller), the tile grid of a box or the tile list
+struct GodGrid { dim3 grid; int ntx, nty; const int4* tiles; int ntiles, xcd_cnt; };
+static bool god_launch_grid(const Layout& l, const Geometry& g, const GodZPlan& p, int sel, GodGrid& o)       // false: no tile, nothing to launch
+{
+    o.ntx = (l.max_len[0] + p.tx - 1) / p.tx; o.nty = (l.max_len[1] + p.ty - 1) / p.ty;
+    o.tiles = nullptr; o.ntiles = 0;
+    int total = o.ntx * o.nty * p.zc.n;
+    if (sel == 0) o.xcd_cnt = total >= 64 ? (total + 7) / 8 : 0;
+    else {
+        o.tiles = god_tile_list(l, g, p.tx, p.ty, p.kc, p.zc, sel - 1, &o.ntiles);
+        if (o.ntiles == 0) return false;
+        total = o.ntiles;
+        o.xcd_cnt = total >= 64 ? total / 8 : 0;          // (a class of >= 64 tiles: dealt to the XCDs and padded, god_tile_lists_host)
+    }
+    o.grid = dim3((unsigned)(o.xcd_cnt > 0 ? 8 * o.xcd_cnt : total), sel == 0 ? (unsigned)l.nlocal() : 1u, 1u);
+    return true;
+}
+// the launches of a plan, class by class: launch(L, grid) issues one; a probe pair (kernels.h) spans the launches of a class
+template <class F>
+static void god_run_plan(const Layout& l, const Geometry& g, const GodZPlan& p, int probe, F launch)
+{
+    for (int i = 0; i < p.nlaunch;) {
+        const int sel = p.launch[i].sel;
+        GodGrid gg;
+        const bool any = god_launch_grid(l, g, p, sel, gg);
+        const bool rec = any && kernel_probe_begin(probe, (long)l.max_len[0] * l.max_len[1] * l.max_len[2]);
+        for (; i < p.nlaunch && p.launch[i].sel == sel; ++i) if (any) launch(p.launch[i], gg);
+        if (rec) kernel_probe_end(probe);
+    }
+}
+
+// -------------------------------------------------------------------------------- the fused advection kernel
+// k_god_z<.., BCS, PPM, FRC, DVU, OUT, CNS>: the flags that are uniform over a launch are template parameters (god_z_plan above says which
+// launch gets which; god_z_kernel below holds the list of instantiations).  A launch runs the components of its table `comps`, one per
+// blockIdx.z.  The LDS planes of the forcing and of divu exist only where the flag can be set.
+// (DVU 1 is the DVU 0 body plus the divu terms: with an array of zeros it gives the doubles of DVU 0, tests/test_gpu_godunov_spec.py.)
 template <int TX, int TY, int NT, int WPE, bool BCS, bool PPM, int FRC = -1, int DVU = -1, int OUT = -1, int CNS = -1>
 __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxes, const FabD* __restrict__ qt, const FabD* __restrict__ ft,
     const FabD* __restrict__ divut, const FabD* __restrict__ uxt, const FabD* __restrict__ uyt, const FabD* __restrict__ uzt,
@@ -1633,7 +1097,7 @@ __global__ void __launch_bounds__(NT, WPE) k_god_z(const BoxD* __restrict__ boxe
         bid = (bid & 7) * xcd_cnt + (bid >> 3);          // XCD-aware order, see make_tiling
         if (bid >= (tiles ? ntiles : ntx * nty * zc.n)) return;
     }
-    // the tile: from the launch's list (god_tile_lists) or from the full tile grid of the box blockIdx.y
+    // the tile: from the launch's list (god_tile_list) or from the full tile grid of the box blockIdx.y
     int fab = blockIdx.y, tix, tiy, kci;
     if (tiles) { const int4 t = tiles[bid]; if (t.x < 0) return; fab = t.x; tix = t.y; tiy = t.z; kci = t.w; }
     else { tix = bid % ntx; const int r1 = bid / ntx; tiy = r1 % nty; kci = r1 / nty; }
@@ -1926,74 +1390,31 @@ static bool use_z_kernel()
     return tune("GODUNOV_Z", 1) != 0;
 }
 
-// IAMRX_GODUNOV_SPEC=0 selects the run-time kernels where a specialised instantiation exists (read at every call:
-// tests/test_gpu_godunov_spec.py compares the two)
-static bool use_spec_kernels()
-{
-    return tune("GODUNOV_SPEC", 1) != 0;
-}
+// threads of a workgroup of the fused kernels: one per column of the tile grown by one cell, in whole wavefronts
+constexpr int god_threads(int tx, int ty) { return ((tx + 2) * (ty + 2) + 63) / 64 * 64; }
 
-static bool g_god_probe_open = false;     // the probe spans the launches of one call (one per form of the components)
-// ncomp components of the launch: blockIdx.z -> comps.c[]
-template <int TX, int TY, int WPE, bool BCS, bool PPM, int FRC = -1, int DVU = -1, int OUT = -1, int CNS = -1>
-static void launch_god_z(const Layout& l, MultiFab& aofs, int acomp, const MultiFab& S, int ncomp, const GodComps& comps, const MultiFab* force,
-                         const MultiFab* divu, MultiFab* const umac[3], MultiFab* const edge_out[3], MultiFab* const flux_out[3],
-                         const GodParams* dP, int sel = 0, const Geometry* sg = nullptr, bool probe_begin = true, bool probe_end = true)
+// the instantiation of a planned launch.  ALL of k_god_z is listed here: the run-time kernel for tile shape x BCS x PPM (8), the specialised
+// ones -- 14 x 14, PLM, FRC 1 -- for BCS x DVU x OUT {0, 2} x CNS (16); WPE, the second launch bound, is 2 throughout
+// counter: the launch counter of the instantiation, named where the instantiation is -- it says which kernel ran, not what was planned
+// (tests/test_gpu_godunov_spec.py asserts the counters)
+using GodZKernel = decltype(&k_god_z<14, 14, 256, 2, false, false>);
+static GodZKernel god_z_kernel(const GodZPlan& p, const GodLaunch& L, const char*& counter)
 {
-    if (ncomp == 0) return;
-    constexpr int NT = (((TX + 2) * (TY + 2)) + 63) / 64 * 64;
-    const int ntx = (l.max_len[0] + TX - 1) / TX, nty = (l.max_len[1] + TY - 1) / TY;
-    const int kc_env = (int)tune("GODUNOV_ZKC", 0);
-    const int kc = kc_env > 0 ? kc_env : std::min(64, std::max(8, l.max_len[2] / 4));       // planes marched per workgroup
-    const GodChunks zc = god_chunks(l.max_len[2], kc, sel != 0 && !sg->periodic[2]);
-    int total = ntx * nty * zc.n, ntiles = 0, lx = 0;
-    unsigned gy = (unsigned)l.nlocal();
-    const int4* tiles = nullptr;
-    if (sel != 0) {           // this launch's share of the tiles of a domain with walls (god_tile_lists)
-        const GodTileList tl = god_tile_lists(l, *sg, TX, TY, zc);
-        tiles = tl.d[sel - 1]; ntiles = tl.n[sel - 1];
-        if (ntiles == 0) return;
-        total = ntiles; gy = 1u; lx = tl.xcd_cnt[sel - 1];
-    }
-    const int xcd_cnt = sel != 0 ? lx : (total >= 64 ? (total + 7) / 8 : 0);
-    dim3 grid((unsigned)(xcd_cnt > 0 ? 8 * xcd_cnt : total), gy, (unsigned)ncomp);
-    GodTabs3 et{{nullptr, nullptr, nullptr}}, ftb{{nullptr, nullptr, nullptr}};
-    if (edge_out && edge_out[0]) for (int d = 0; d < 3; ++d) et.t[d] = edge_out[d]->d_tab;
-    if (flux_out && flux_out[0]) for (int d = 0; d < 3; ++d) ftb.t[d] = flux_out[d]->d_tab;
-    if (probe_begin) g_god_probe_open = kernel_probe_begin(PROBE_GOD_Z, (long)l.max_len[0] * l.max_len[1] * l.max_len[2]);
-    hipLaunchKernelGGL((k_god_z<TX, TY, NT, WPE, BCS, PPM, FRC, DVU, OUT, CNS>), grid, dim3(NT), 0, Context::get().stream, l.d_boxes, S.d_tab,
-                       force ? force->d_tab : nullptr, divu ? divu->d_tab : nullptr, umac[0]->d_tab, umac[1]->d_tab, umac[2]->d_tab, aofs.d_tab,
-                       acomp, et, ftb, dP, ntx, nty, zc, tiles, ntiles, xcd_cnt, comps);
-    if (probe_end && g_god_probe_open) { kernel_probe_end(PROBE_GOD_Z); g_god_probe_open = false; }
-    tuning_count(CNS < 0 ? "GODUNOV_Z_RUNTIME_LAUNCHES" : (CNS ? "GODUNOV_Z_SPEC_CONS_LAUNCHES" : "GODUNOV_Z_SPEC_CONV_LAUNCHES"));
-}
-
-// one call of the fused advection kernel on the tiles `sel`: the specialised instantiations where the call's flags have one (the list is
-// in front of k_god_z) -- one launch per form of the components --, the run-time kernel otherwise
-template <int TX, int TY, int WPE, bool BCS, bool PPM>
-static void god_z_call(const Layout& l, MultiFab& aofs, int acomp, const MultiFab& S, int ncomp, const int* iconserv, bool fit, const MultiFab* force,
-                       const MultiFab* divu, MultiFab* const umac[3], MultiFab* const edge_out[3], MultiFab* const flux_out[3],
-                       const GodParams* dP, int sel, const Geometry* sg)
-{
-    if constexpr (TX == 14 && TY == 14 && !PPM) {
-        const bool se = edge_out && edge_out[0], sf = flux_out && flux_out[0];
-        if (use_spec_kernels() && force && !fit && !se) {
-            GodComps cv{}, cs{};
-            int ncv = 0, ncs = 0;
-            for (int n = 0; n < ncomp; ++n) { if (iconserv && iconserv[n]) cs.c[ncs++] = n; else cv.c[ncv++] = n; }
-#define IAMRX_GZF(DVU, OUT, CNS, NC, TAB, PB, PE) launch_god_z<TX, TY, WPE, BCS, PPM, 1, DVU, OUT, CNS>(l, aofs, acomp, S, NC, TAB, force, divu, umac, nullptr, \
-                                                                                                         flux_out, dP, sel, sg, PB, PE)
-#define IAMRX_GZO(DVU, OUT) do { IAMRX_GZF(DVU, OUT, 0, ncv, cv, true, ncs == 0); IAMRX_GZF(DVU, OUT, 1, ncs, cs, ncv == 0, true); } while (0)
-            if (divu) { if (sf) IAMRX_GZO(1, 2); else IAMRX_GZO(1, 0); }
-            else { if (sf) IAMRX_GZO(0, 2); else IAMRX_GZO(0, 0); }
-#undef IAMRX_GZO
-#undef IAMRX_GZF
-            return;
-        }
-    }
-    GodComps all{};
-    for (int n = 0; n < ncomp; ++n) all.c[n] = n;
-    launch_god_z<TX, TY, WPE, BCS, PPM>(l, aofs, acomp, S, ncomp, all, force, divu, umac, edge_out, flux_out, dP, sel, sg);
+    GodZKernel k = nullptr;
+    if (L.cns >= 0) {
+        IAMRX_ASSERT(p.tx == 14 && !p.ppm && L.frc == 1);
+        dispatch_bools([&](auto B, auto D, auto O, auto C) {
+            constexpr int CNS = decltype(C)::value ? 1 : 0;
+            k = k_god_z<14, 14, 256, 2, decltype(B)::value, false, 1, decltype(D)::value ? 1 : 0, decltype(O)::value ? 2 : 0, CNS>;
+            counter = CNS ? "GODUNOV_Z_SPEC_CONS_LAUNCHES" : "GODUNOV_Z_SPEC_CONV_LAUNCHES";
+        }, L.bcs, L.dvu > 0, L.out == 2, L.cns > 0);
+    } else
+        dispatch_bools([&](auto T16, auto B, auto P) {
+            constexpr int TX = decltype(T16)::value ? 16 : 14, TY = decltype(T16)::value ? 8 : 14;
+            k = k_god_z<TX, TY, god_threads(TX, TY), 2, decltype(B)::value, decltype(P)::value>;
+            counter = "GODUNOV_Z_RUNTIME_LAUNCHES";
+        }, p.tx == 16, L.bcs, p.ppm);
+    return k;
 }
 
 // -------------------------------------------------------------------------------- fused z-marching velocity prediction (PLM)
@@ -2021,7 +1442,7 @@ __global__ void __launch_bounds__(NT, 2) k_pred_z(const BoxD* __restrict__ boxes
         bid = (bid & 7) * xcd_cnt + (bid >> 3);          // XCD-aware order, see make_tiling
         if (bid >= (tiles ? ntiles : ntx * nty * zc.n)) return;
     }
-    // the tile: from the launch's list (god_tile_lists) or from the full tile grid of the box blockIdx.y
+    // the tile: from the launch's list (god_tile_list) or from the full tile grid of the box blockIdx.y
     int fab = blockIdx.y, tix, tiy, kci;
     if (tiles) { const int4 t = tiles[bid]; if (t.x < 0) return; fab = t.x; tix = t.y; tiy = t.z; kci = t.w; }
     else { tix = bid % ntx; const int r1 = bid / ntx; tiy = r1 % nty; kci = r1 / nty; }
@@ -2262,53 +1683,36 @@ __global__ void __launch_bounds__(NT, 2) k_pred_z(const BoxD* __restrict__ boxes
     }
 }
 
-template <int TX, int TY, bool BCS, bool PPM, int FRC = -1>
-static void launch_pred_z(const Layout& l, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3], const GodParams* dP, int sel = 0,
-                          const Geometry* sg = nullptr)
+// ALL of k_pred_z: the run-time kernel for tile shape x BCS x PPM (8), FRC 1 -- 14 x 14, PLM -- for BCS (2)
+using PredZKernel = decltype(&k_pred_z<14, 14, 256, false, false>);
+static PredZKernel pred_z_kernel(const GodZPlan& p, const GodLaunch& L, const char*& counter)       // counter: as for god_z_kernel
 {
-    constexpr int NT = (((TX + 2) * (TY + 2)) + 63) / 64 * 64;
-    const int ntx = (l.max_len[0] + TX - 1) / TX, nty = (l.max_len[1] + TY - 1) / TY;
-    const int kc_env = (int)tune("GODUNOV_ZKC", 0);
-    const int kc = kc_env > 0 ? kc_env : std::min(64, std::max(8, l.max_len[2] / 4));
-    const GodChunks zc = god_chunks(l.max_len[2], kc, sel != 0 && !sg->periodic[2]);
-    int total = ntx * nty * zc.n, ntiles = 0, lx = 0;
-    unsigned gy = (unsigned)l.nlocal();
-    const int4* tiles = nullptr;
-    if (sel != 0) {           // this launch's share of the tiles of a domain with walls (god_tile_lists)
-        const GodTileList tl = god_tile_lists(l, *sg, TX, TY, zc);
-        tiles = tl.d[sel - 1]; ntiles = tl.n[sel - 1];
-        if (ntiles == 0) return;
-        total = ntiles; gy = 1u; lx = tl.xcd_cnt[sel - 1];
-    }
-    const int xcd_cnt = sel != 0 ? lx : (total >= 64 ? (total + 7) / 8 : 0);
-    dim3 grid((unsigned)(xcd_cnt > 0 ? 8 * xcd_cnt : total), gy, 1u);
-    const bool rec = kernel_probe_begin(PROBE_PRED_Z, (long)l.max_len[0] * l.max_len[1] * l.max_len[2]);
-    hipLaunchKernelGGL((k_pred_z<TX, TY, NT, BCS, PPM, FRC>), grid, dim3(NT), 0, Context::get().stream, l.d_boxes, vel.d_tab, force ? force->d_tab : nullptr,
-                       umac[0]->d_tab, umac[1]->d_tab, umac[2]->d_tab, dP, ntx, nty, zc, tiles, ntiles, xcd_cnt);
-    if (rec) kernel_probe_end(PROBE_PRED_Z);
-    tuning_count(FRC < 0 ? "PRED_Z_RUNTIME_LAUNCHES" : "PRED_Z_SPEC_LAUNCHES");
+    PredZKernel k = nullptr;
+    if (L.frc >= 0) {
+        IAMRX_ASSERT(p.tx == 14 && !p.ppm && L.frc == 1);
+        dispatch_bools([&](auto B) { k = k_pred_z<14, 14, 256, decltype(B)::value, false, 1>; counter = "PRED_Z_SPEC_LAUNCHES"; }, L.bcs);
+    } else
+        dispatch_bools([&](auto T16, auto B, auto P) {
+            constexpr int TX = decltype(T16)::value ? 16 : 14, TY = decltype(T16)::value ? 8 : 14;
+            k = k_pred_z<TX, TY, god_threads(TX, TY), decltype(B)::value, decltype(P)::value>;
+            counter = "PRED_Z_RUNTIME_LAUNCHES";
+        }, p.tx == 16, L.bcs, p.ppm);
+    return k;
 }
 
-static void godunov_pred_z(const Layout& l, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3], const GodParams* dP, bool bcs, bool ppm, const Geometry& g,
+// 14 x 14 cells per workgroup (grown tile 16 x 16 = 256 threads, 80 KB of LDS, two workgroups per CU): 1.04 ms per 256^3 against 1.24 ms with
+// 16 x 8 (192 threads; IAMRX_GODUNOV_PTX = 16), 1.14 ms with 30 x 6 -- see the tile shapes of k_god_z in godunov_compute_aofs
+static void godunov_pred_z(const Layout& l, const Geometry& g, const MultiFab& vel, const MultiFab* force, MultiFab* const umac[3], const GodParams* dP, bool ppm,
                            bool fit)
 {
-    // 14 x 14 cells per workgroup (grown tile 16 x 16 = 256 threads, 80 KB of LDS, two workgroups per CU): 1.04 ms per 256^3 against 1.24 ms with
-    // 16 x 8 (192 threads; IAMRX_GODUNOV_PTX = 16), 1.14 ms with 30 x 6 -- see the tile shapes of k_god_z below
-    const int ptx = (int)tune("GODUNOV_PTX", 14);
-    // a domain with walls: the tiles no boundary condition reaches run the plain code (sel = 1), the boundary-condition variant takes the
-    // rest (sel = 2: the tiles along the walls, thin first / last z-chunks) -- IAMRX_GODUNOV_SPLIT_BC = 0: one launch of the variant
-    const bool split = bcs && tune("GODUNOV_SPLIT_BC", 1) != 0;
-    // the specialised instantiation (late forcing, 14 x 14 tiles, PLM: the list in front of k_god_z) where the call has one
-    const bool spec = use_spec_kernels() && force && !fit && !ppm && ptx != 16;
-#define IAMRX_PZS(TX, TY, B, PPM, SEL) do { if constexpr (TX == 14 && !PPM) { if (spec) { launch_pred_z<TX, TY, B, PPM, 1>(l, vel, force, umac, dP, SEL, &g); break; } } \
-                                            launch_pred_z<TX, TY, B, PPM>(l, vel, force, umac, dP, SEL, &g); } while (0)
-#define IAMRX_PZP(TX, TY, PPM) do { if (!bcs) IAMRX_PZS(TX, TY, false, PPM, 0); else if (!split) IAMRX_PZS(TX, TY, true, PPM, 0); \
-                                    else { IAMRX_PZS(TX, TY, false, PPM, 1); IAMRX_PZS(TX, TY, true, PPM, 2); } } while (0)
-#define IAMRX_PZ(TX, TY) do { if (ppm) IAMRX_PZP(TX, TY, true); else IAMRX_PZP(TX, TY, false); } while (0)
-    if (ptx == 16) IAMRX_PZ(16, 8); else IAMRX_PZ(14, 14);
-#undef IAMRX_PZ
-#undef IAMRX_PZP
-#undef IAMRX_PZS
+    const GodZPlan p = god_z_plan(true, l.max_len, g, GodCall{ppm, force != nullptr, fit, false, false, false, 3, nullptr});
+    god_run_plan(l, g, p, PROBE_PRED_Z, [&](const GodLaunch& L, const GodGrid& gg) {
+        const char* counter = nullptr;
+        hipLaunchKernelGGL(pred_z_kernel(p, L, counter), gg.grid, dim3(god_threads(p.tx, p.ty)), 0, Context::get().stream, l.d_boxes, vel.d_tab,
+                           force ? force->d_tab : nullptr, umac[0]->d_tab, umac[1]->d_tab, umac[2]->d_tab, dP, gg.ntx, gg.nty, p.zc, gg.tiles, gg.ntiles,
+                           gg.xcd_cnt);
+        tuning_count(counter);
+    });
 }
 
 
@@ -2541,12 +1945,6 @@ static void bds_edge_states(const Geometry& g, const MultiFab& S, int ncomp, con
     }
 }
 
-static bool use_tile_kernel()
-{
-    const int v = (int)tune("GODUNOV_TILE", 0);
-    return v != 0;
-}
-
 void godunov_compute_aofs(const Geometry& g, MultiFab& aofs, int acomp, const MultiFab& S, int ncomp, const MultiFab* force,
                           const MultiFab* divu, MultiFab* const umac[3], const int* iconserv, double dt, const BCRec* bc,
                           bool is_velocity, bool use_forces_in_trans, MultiFab* const edge_out[3], MultiFab* const flux_out[3], int scheme)
@@ -2556,9 +1954,6 @@ void godunov_compute_aofs(const Geometry& g, MultiFab& aofs, int acomp, const Mu
     IAMRX_ASSERT(umac[0]->ngrow >= 1);
     auto& ctx = Context::get();
     const Layout& l = *S.layout;
-    MultiFab e0[3], edge[3], sl[3];
-    MultiFab* ed[3];
-    const bool ws = use_dir_fused();
     if (scheme == 2) {
         // BDS edge states, then the flux / divergence / convective-term kernel of the Godunov path
         IAMRX_ASSERT(force == nullptr || force->ngrow >= 1);
@@ -2577,62 +1972,74 @@ void godunov_compute_aofs(const Geometry& g, MultiFab& aofs, int acomp, const Mu
                            sfb ? flux_out[0]->d_tab : nullptr, sfb ? flux_out[1]->d_tab : nullptr, sfb ? flux_out[2]->d_tab : nullptr, dPb);
         return;
     }
-    const bool ppm = scheme == 1;
     set_scheme(scheme);
-    const bool zk = use_z_kernel();
-    for (int d = 0; d < 3 && !use_tile_kernel() && !zk; ++d) {
-        e0[d].define(S.layout, face_type(d), ncomp, 1);
-        if (ws) sl[d].define(S.layout, cell_type(), ncomp, 1);
-        if (edge_out && edge_out[d]) ed[d] = edge_out[d];
-        else { edge[d].define(S.layout, face_type(d), ncomp, 0); ed[d] = &edge[d]; }
-    }
     const GodParams* dP = upload_params(make_params(g, dt, ncomp, bc, iconserv, is_velocity, use_forces_in_trans, force != nullptr, divu != nullptr));
-    if (zk) {
-        const int ztx = (int)tune("GODUNOV_ZTX", 14);
-        const bool bcs = !(g.periodic[0] && g.periodic[1] && g.periodic[2]);
-        // (walls: two launches, see godunov_pred_z)
-        const bool split = bcs && tune("GODUNOV_SPLIT_BC", 1) != 0;
-#define IAMRX_GZS(TX, TY, W, B, PPM, SEL) god_z_call<TX, TY, W, B, PPM>(l, aofs, acomp, S, ncomp, iconserv, use_forces_in_trans, force, divu, umac, \
-                                                                        edge_out, flux_out, dP, SEL, &g)
-#define IAMRX_GZP(TX, TY, W, PPM) do { if (!bcs) IAMRX_GZS(TX, TY, W, false, PPM, 0); else if (!split) IAMRX_GZS(TX, TY, W, true, PPM, 0); \
-                                       else { IAMRX_GZS(TX, TY, W, false, PPM, 1); IAMRX_GZS(TX, TY, W, true, PPM, 2); } } while (0)
-#define IAMRX_GZ(TX, TY, W) do { if (ppm) IAMRX_GZP(TX, TY, W, true); else IAMRX_GZP(TX, TY, W, false); } while (0)
+    const bool se = edge_out && edge_out[0], sf = flux_out && flux_out[0];
+    if (use_z_kernel()) {
         // Tile shapes, 3 components at 256^3 (periodic, PLM): the 251 VGPRs of the kernel allow 8 wavefronts per CU, so a 192-thread
         // workgroup (16 x 8 cells, grown tile 18 x 10) leaves the CU with 6 wavefronts -- two SIMDs run one -- and 128 useful columns per
         // 192 threads: 2.46 ms.  14 x 14 cells = a grown tile of exactly 16 x 16 = 256 threads: two workgroups = 8 wavefronts per CU, 196
         // useful columns per 256 threads, 53 KB of LDS: 1.84 ms.  30 x 6 (32 x 8 grown): 2.03 ms; 512 threads (30 x 14: 2.25 ms, 14 x 30:
         // 2.33 ms; one workgroup per CU); round 2's 16 x 16 and 32 x 8 cells (384 threads): slower than 16 x 8.
         // IAMRX_GODUNOV_ZTX = 16: the 16 x 8 tiles.
-        if (ztx == 16) IAMRX_GZ(16, 8, 2);
-        else IAMRX_GZ(14, 14, 2);
-#undef IAMRX_GZ
-#undef IAMRX_GZP
-#undef IAMRX_GZS
+        const GodZPlan p = god_z_plan(false, l.max_len, g, GodCall{scheme == 1, force != nullptr, use_forces_in_trans, divu != nullptr, se, sf, ncomp, iconserv});
+        GodTabs3 et{{nullptr, nullptr, nullptr}}, ftb{{nullptr, nullptr, nullptr}};
+        for (int d = 0; d < 3; ++d) { if (se) et.t[d] = edge_out[d]->d_tab; if (sf) ftb.t[d] = flux_out[d]->d_tab; }
+        god_run_plan(l, g, p, PROBE_GOD_Z, [&](const GodLaunch& L, const GodGrid& gg) {
+            const char* counter = nullptr;
+            hipLaunchKernelGGL(god_z_kernel(p, L, counter), dim3(gg.grid.x, gg.grid.y, (unsigned)L.ncomp), dim3(god_threads(p.tx, p.ty)), 0, ctx.stream, l.d_boxes,
+                               S.d_tab, force ? force->d_tab : nullptr, divu ? divu->d_tab : nullptr, umac[0]->d_tab, umac[1]->d_tab, umac[2]->d_tab,
+                               aofs.d_tab, acomp, et, ftb, dP, gg.ntx, gg.nty, p.zc, gg.tiles, gg.ntiles, gg.xcd_cnt, L.comps);
+            tuning_count(counter);
+        });
         return;
     }
-    if (use_tile_kernel()) {
-        constexpr int TX = 16, TY = 8, TZ = 4, NTH = 1024;
-        const int ntx = (l.max_len[0] + TX - 1) / TX, nty = (l.max_len[1] + TY - 1) / TY, ntz = (l.max_len[2] + TZ - 1) / TZ;
-        const bool se = edge_out && edge_out[0], sf = flux_out && flux_out[0];
-        dim3 grid((unsigned)(ntx * nty * ntz), (unsigned)l.nlocal());
-        hipLaunchKernelGGL((k_godunov_tile<TX, TY, TZ, NTH>), grid, dim3(NTH), 0, ctx.stream, l.d_boxes, S.d_tab, force ? force->d_tab : nullptr,
-                           divu ? divu->d_tab : nullptr, umac[0]->d_tab, umac[1]->d_tab, umac[2]->d_tab, aofs.d_tab, acomp,
-                           se ? edge_out[0]->d_tab : nullptr, se ? edge_out[1]->d_tab : nullptr, se ? edge_out[2]->d_tab : nullptr,
-                           sf ? flux_out[0]->d_tab : nullptr, sf ? flux_out[1]->d_tab : nullptr, sf ? flux_out[2]->d_tab : nullptr,
-                           dP, ntx, nty, ntz);
-        return;
+    // the multi-pass chain: k_trace x 3 (with the slope arrays), k_dir x 3, k_aofs
+    MultiFab e0[3], edge[3], sl[3];
+    MultiFab* ed[3];
+    for (int d = 0; d < 3; ++d) {
+        e0[d].define(S.layout, face_type(d), ncomp, 1);
+        sl[d].define(S.layout, cell_type(), ncomp, 1);
+        if (edge_out && edge_out[d]) ed[d] = edge_out[d];
+        else { edge[d].define(S.layout, face_type(d), ncomp, 0); ed[d] = &edge[d]; }
     }
-    launch_trace<false, 0>(l, S, force, *umac[0], e0[0], ws ? &sl[0] : nullptr, dP);
-    launch_trace<false, 1>(l, S, force, *umac[1], e0[1], ws ? &sl[1] : nullptr, dP);
-    launch_trace<false, 2>(l, S, force, *umac[2], e0[2], ws ? &sl[2] : nullptr, dP);
-    launch_final<false, 0>(l, S, force, divu, umac, e0, sl, *ed[0], dP);
-    launch_final<false, 1>(l, S, force, divu, umac, e0, sl, *ed[1], dP);
-    launch_final<false, 2>(l, S, force, divu, umac, e0, sl, *ed[2], dP);
+    launch_trace<false, 0>(l, S, force, *umac[0], e0[0], sl[0], dP);
+    launch_trace<false, 1>(l, S, force, *umac[1], e0[1], sl[1], dP);
+    launch_trace<false, 2>(l, S, force, *umac[2], e0[2], sl[2], dP);
+    launch_dir<false, 0>(l, S, ncomp, force, divu, umac, e0, sl, *ed[0], dP);
+    launch_dir<false, 1>(l, S, ncomp, force, divu, umac, e0, sl, *ed[1], dP);
+    launch_dir<false, 2>(l, S, ncomp, force, divu, umac, e0, sl, *ed[2], dP);
     Tiling t = level_tiling(l, cell_type(), 0, 4);
-    const bool sf = flux_out && flux_out[0];
     hipLaunchKernelGGL(k_aofs, t.grid(), Tiling::block(), 0, ctx.stream, t, l.d_boxes, aofs.d_tab, acomp,
                        ed[0]->d_tab, ed[1]->d_tab, ed[2]->d_tab, umac[0]->d_tab, umac[1]->d_tab, umac[2]->d_tab,
                        sf ? flux_out[0]->d_tab : nullptr, sf ? flux_out[1]->d_tab : nullptr, sf ? flux_out[2]->d_tab : nullptr, dP);
+}
+
+// host-only (no device, no Context, no allocator): the plan of a call of the fused kernels on the boxes given, flattened for the C entry
+// iamrx_host_godunov_plan.  head: tx, ty, kc, launches, chunks; launch (16 ints each): sel, bcs, frc, dvu, out, cns, ncomp, 0, comps[8];
+// starts: the chunk starts (chunks + 1); tiles (5 ints each): class (0 off the walls, 1 at the walls), box, tile x, tile y, chunk, in list
+// order, dead entries (box -1) included -- none for a plan that runs on the full tile grid
+void godunov_plan_host(bool pred, const std::vector<BoxD>& boxes, const Geometry& g, int scheme, bool has_force, bool fit, bool has_divu, bool edge_out,
+                       bool flux_out, int ncomp, const int* iconserv, int head[5], std::vector<int>& launch, std::vector<int>& starts, std::vector<int>& tiles)
+{
+    IAMRX_ASSERT(ncomp >= 0 && ncomp <= GOD_MAXC && (scheme == 0 || scheme == 1));
+    int max_len[3] = {0, 0, 0};
+    for (const BoxD& b : boxes) for (int d = 0; d < 3; ++d) max_len[d] = std::max(max_len[d], b.len(d));
+    const GodZPlan p = god_z_plan(pred, max_len, g, GodCall{scheme == 1, has_force, fit, has_divu, edge_out, flux_out, ncomp, iconserv});
+    const int h[5] = {p.tx, p.ty, p.kc, p.nlaunch, p.zc.n};
+    std::copy(h, h + 5, head);
+    launch.clear(); starts.assign(p.zc.start, p.zc.start + p.zc.n + 1); tiles.clear();
+    for (int i = 0; i < p.nlaunch; ++i) {
+        const GodLaunch& L = p.launch[i];
+        const int v[8] = {L.sel, L.bcs ? 1 : 0, L.frc, L.dvu, L.out, L.cns, L.ncomp, 0};
+        launch.insert(launch.end(), v, v + 8);
+        launch.insert(launch.end(), L.comps.c, L.comps.c + GOD_MAXC);
+    }
+    if (p.nlaunch == 0 || p.launch[0].sel == 0) return;
+    std::vector<int4> list[2];
+    god_tile_lists_host(boxes.data(), (int)boxes.size(), g, p.tx, p.ty, p.zc, list);
+    for (int c = 0; c < 2; ++c)
+        for (const int4& t : list[c]) { const int v[5] = {c, t.x, t.y, t.z, t.w}; tiles.insert(tiles.end(), v, v + 5); }
 }
 
 }  // namespace iamrx

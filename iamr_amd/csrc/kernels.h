@@ -440,6 +440,10 @@ void godunov_extrap_vel_to_faces(const Geometry& g, const MultiFab& vel, const M
 void godunov_compute_aofs(const Geometry& g, MultiFab& aofs, int acomp, const MultiFab& S, int ncomp, const MultiFab* force,
                           const MultiFab* divu, MultiFab* const umac[3], const int* iconserv, double dt, const BCRec* bc,
                           bool is_velocity, bool use_forces_in_trans, MultiFab* const edge_out[3], MultiFab* const flux_out[3], int scheme = 0);
+// host data only: the launches a call of the fused kernels (pred: k_pred_z, else k_god_z) would issue on these boxes, and their tiles --
+// god_z_plan and god_tile_lists_host flattened for iamrx_host_godunov_plan (layout of the outputs: at the definition)
+void godunov_plan_host(bool pred, const std::vector<BoxD>& boxes, const Geometry& g, int scheme, bool has_force, bool fit, bool has_divu, bool edge_out,
+                       bool flux_out, int ncomp, const int* iconserv, int head[5], std::vector<int>& launch, std::vector<int>& starts, std::vector<int>& tiles);
 
 
 // ---- k_nodal.hip --------------------------------------------------------------------------

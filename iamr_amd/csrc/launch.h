@@ -10,6 +10,7 @@
 #include <map>
 #include <array>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 namespace iamrx {
@@ -61,8 +62,21 @@ inline Tiling make_tiling(const int maxlen[3], int nfab, int tz = 4)
 
 // (mf.hip) cached flat tile list of the local boxes of l (converted to type, grown by ng), tz planes per thread; *total = its length
 const int4* level_tile_list(const Layout& l, const IndexType& type, int ng, int tz, int* total, int xdiv = 1);
-// (mf.hip) any other device-resident int4 work list that belongs to a layout: built once per (layout, subkey), freed with the layout
-const int4* layout_int4_list(const Layout& l, const std::array<long, 5>& subkey, const std::function<void(std::vector<int4>&)>& build, int* total);
+// (mf.hip) any other device-resident int4 work list that belongs to a layout: built once per (layout, subkey), freed with the layout.
+// subkey[0] names the call site (1 level_tile_list, 2 k_abec.hip, 3 k_nodal.hip, 4 k_profile.hip, 5 k_godunov.hip); trailing zeros may be left out
+using LayoutListKey = std::array<long, 12>;
+const int4* layout_int4_list(const Layout& l, const LayoutListKey& subkey, const std::function<void(std::vector<int4>&)>& build, int* total);
+
+// run-time booleans to template arguments: dispatch_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>(), std::bool_constant<b1>(), ...),
+// so a generic lambda picks one instantiation out of the 2^n it names, with no macro ladder at the call site
+template <class F>
+inline void dispatch_bools(F&& f) { f(); }
+template <class F, class... R>
+inline void dispatch_bools(F&& f, bool b, R... rest)
+{
+    if (b) dispatch_bools([&](auto... c) { f(std::true_type(), c...); }, rest...);
+    else dispatch_bools([&](auto... c) { f(std::false_type(), c...); }, rest...);
+}
 
 // tiling for the local boxes of `l` converted to `type` and grown by ng.  allow_list: the kernel takes its box from tile_fab(t), so a level
 // whose boxes differ in size (a regridded refined level and its multigrid levels: boxes of 2 ... 32 cells side by side) may be given a flat

@@ -717,10 +717,10 @@ static CopyDesc* upload(const std::vector<CopyDesc>& v)
 // ------------------------------------------------------------------ flat tile lists (launch.h: level_tiling with allow_list)
 // a device-resident list of int4 work items that belongs to a layout (flat tile lists, the ghost-shell list of k_cf_fill ...): built once
 // per (layout, subkey) by `build`, freed with the layout
-const int4* layout_int4_list(const Layout& l, const std::array<long, 5>& subkey, const std::function<void(std::vector<int4>&)>& build, int* total)
+const int4* layout_int4_list(const Layout& l, const LayoutListKey& subkey, const std::function<void(std::vector<int4>&)>& build, int* total)
 {
     struct Entry { int4* d; int n; };
-    using Key = std::array<long, 6>;
+    using Key = std::array<long, 13>;
     static std::map<Key, Entry>& cache = [] () -> std::map<Key, Entry>& {
         auto* c = new std::map<Key, Entry>();
         register_layout_evictor([c](uint64_t lid) {
@@ -736,7 +736,9 @@ const int4* layout_int4_list(const Layout& l, const std::array<long, 5>& subkey,
         });
         return *c;
     }();
-    const Key key = {(long)l.id, subkey[0], subkey[1], subkey[2], subkey[3], subkey[4]};
+    Key key;
+    key[0] = (long)l.id;
+    std::copy(subkey.begin(), subkey.end(), key.begin() + 1);
     auto it = cache.find(key);
     if (it == cache.end()) {
         std::vector<int4> h;

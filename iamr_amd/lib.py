@@ -468,6 +468,27 @@ def host_nodal_smoother_plan(geom, boxes, has_mask=False, nodal_smoother=0, bott
     return d
 
 
+def host_godunov_plan(geom, boxes, pred=False, scheme=0, has_force=True, fit=False, has_divu=False, edge_out=False, flux_out=False, iconserv=(0, 0, 0)):
+    """host-only: the launches one call of the fused Godunov kernels issues on a level and the tiles of its classes (include/iamrx.h:
+    iamrx_host_godunov_plan) as a dict; boxes: [(lo, hi), ...]; iconserv: one entry per component (prediction: the three velocities).
+    launches: dicts in issue order; chunks: [(first plane, last plane)] relative to a box; tiles: (class, box, tile x, tile y, chunk) in
+    list order, box -1 = padding"""
+    arr = (C.c_int * (6 * len(boxes)))(*[int(v) for lo, hi in boxes for v in tuple(lo) + tuple(hi)])
+    ncomp = 3 if pred else len(iconserv)
+    ic = (C.c_int * max(1, ncomp))(*([0, 0, 0] if pred else [int(v) for v in iconserv]))
+    head, la, st, nt = (C.c_int * 5)(), (C.c_int * 64)(), (C.c_int * 20)(), C.c_int()
+    args = (int(pred), len(boxes), arr, C.byref(geom), int(scheme), int(has_force), int(fit), int(has_divu), int(edge_out), int(flux_out), ncomp, ic, head, la, st)
+    check(lib().iamrx_host_godunov_plan(*args, None, 0, C.byref(nt)))
+    ti = (C.c_int * max(1, 5 * nt.value))()
+    check(lib().iamrx_host_godunov_plan(*args, ti, nt.value, C.byref(nt)))
+    launches = []
+    for i in range(head[3]):
+        v = la[16 * i:16 * i + 16]
+        launches.append(dict(sel=v[0], bcs=bool(v[1]), frc=v[2], dvu=v[3], out=v[4], cns=v[5], comps=tuple(v[8:8 + v[6]])))
+    return dict(tile=(head[0], head[1]), kc=head[2], launches=launches, chunks=[(st[c], st[c + 1] - 1) for c in range(head[4])],
+                tiles=[tuple(ti[5 * i:5 * i + 5]) for i in range(nt.value)])
+
+
 # the 17 values of a forcing mode, in the order of upstream's arrays (Tutorials/HIT/NS_getForce.cpp:249-281)
 TURB_FIELDS = ("FTX", "TAT", "FPX", "FPY", "FPZ", "FAX", "FAY", "FAZ", "FPXX", "FPXY", "FPXZ", "FPYX", "FPYY", "FPYZ", "FPZX", "FPZY", "FPZZ")
 

@@ -227,6 +227,18 @@ int iamrx_host_abec_leg_plan(int nboxes, const int* lo_hi, const iamrx_geom* g, 
 int iamrx_host_nodal_smoother_plan(int nboxes, const int* lo_hi, const iamrx_geom* g, const int lobc[3], const int hibc[3], int has_mask,
                                    int nodal_smoother, int bottom_smoother_only, int device_bottom, int nodal_sweeps, int coarsest, const int ngrow[2],
                                    int out[11]);
+/* host-only (works without a GPU): the launches ONE call of the fused Godunov kernels issues on a level -- pred 1: ExtrapVelToFaces
+ * (k_pred_z, ncomp 3), pred 0: ComputeAofs (k_god_z) -- decided at every call from the level's box list (lo_hi: 6 ints per box, a single
+ * rank's view), the geometry, the call's flags (scheme 0 PLM / 1 PPM, forcing present, use_forces_in_trans, divu present, edge states /
+ * fluxes stored, the components' iconserv) and the tuning keys IAMRX_GODUNOV_ZTX / _PTX / _ZKC / _SPLIT_BC / _SPEC.
+ * head: tile cells in x and y, planes of a z-chunk, launches (<= 4), z-chunks (<= 18).  launches: 16 ints each, in issue order -- sel (0 the
+ * full tile grid, 1 the tiles off the walls, 2 the tiles at the walls), boundary-condition variant, the template flags FRC, DVU, OUT, CNS (-1:
+ * run-time value), components, 0, the component table (8).  starts: first plane of every chunk relative to the box, then the length.
+ * tiles (5 ints each; none when sel is 0): class (0 off / 1 at the walls), box, tile x, tile y, chunk, in the order the launch works through
+ * them; box -1: padding of a class of >= 64 tiles, whose list is dealt to the eight XCDs.  *ntiles entries exist, at most max_tiles are
+ * written (tiles may be null).  No counterpart upstream. */
+int iamrx_host_godunov_plan(int pred, int nboxes, const int* lo_hi, const iamrx_geom* g, int scheme, int has_force, int fit, int has_divu, int edge_out,
+                            int flux_out, int ncomp, const int* iconserv, int head[5], int launches[64], int starts[20], int* tiles, int max_tiles, int* ntiles);
 
 /* ---- cell-centred linear operator primitives (amrex::MLABecLaplacian role) ---- */
 /* one red or black Gauss-Seidel pass of (alpha*a - beta div b grad) phi = rhs; ghost cells of phi must be filled */
